@@ -294,6 +294,45 @@ typedef struct {
 int zs_mbv_bwd(const ZsMbvBwd* p, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * zs_gumbel_st_fwd / zs_gumbel_st_bwd: the other encoder discretisers (model/model.py:93-110, 457-472).
+ * logits rows [B*T'][ld] hold n_lin columns: n_lin = E (ONE_HOT, CONTINUES) or E*E (BINARY).
+ *  ONE_HOT:   one softmax group of E: enc = (hard - y) + y, y = softmax((l+g)/tau), hard = one-hot of
+ *             argmax(y) (first index on ties).  dl_j = y_j (d_j - sum_k d_k y_k) / tau.
+ *  BINARY:    E groups i of E (column i*E + j), softmax over j; s_j = sum_i out_{i,j} (fp32, increasing i),
+ *             enc_j = clamp(s_j, 0, 1).  d_{i,j} = denc_j * [0 <= s_j <= 1], then the ONE_HOT formula per
+ *             group.  Requires E <= 64.
+ *  CONTINUES: enc = leaky_relu(l, slope), no noise.  dl = denc * (l > 0 ? 1 : slope).
+ * Noise as in ZsMbvFwd (kind 0: Gumbel G, 1: uniform U, 2: counter-hash RNG(seed + *seed_ptr), its own
+ * stream tag), laid out [rows][n_lin] (the reference's torch.rand shape).  Outputs: bits (compute dtype,
+ * columns [E, bits_fill_cols) zeroed), optional compact fp32 bits_f32 [rows][E], y = the fp32 softmax
+ * [rows][n_lin] (ONE_HOT / BINARY, for the backward), s = the unclamped sums [rows][E] (BINARY).
+ * Backward: y / ld_y is the saved softmax (ONE_HOT / BINARY) or the fp32 logits (CONTINUES); writes
+ * dlogits (compute dtype, ld) for columns [0, fill_cols), zeros past n_lin.
+ */
+enum { ZS_ENC_ONE_HOT = 0, ZS_ENC_BINARY = 1, ZS_ENC_CONTINUES = 2 };
+typedef struct {
+  int32_t dtype; int32_t mode;
+  const void* logits; int64_t ld; int32_t logits_f32;
+  const float* noise; int32_t noise_kind; uint64_t seed;
+  int64_t rows; int32_t E; float tau; float slope;
+  void* bits; int64_t ld_bits; int32_t bits_fill_cols;
+  float* bits_f32;               /* optional compact [rows][E] fp32 copy (API output) */
+  float* y;                      /* [rows][n_lin], ONE_HOT / BINARY (needed by the backward) */
+  float* s;                      /* [rows][E], BINARY (needed by the backward) */
+  const uint64_t* seed_ptr;      /* optional device scalar added to `seed` */
+} ZsGumbelStFwd;
+int zs_gumbel_st_fwd(const ZsGumbelStFwd* p, void* stream);
+typedef struct {
+  int32_t dtype; int32_t mode;
+  const void* dbits; int64_t ld_dbits;
+  const float* y; int64_t ld_y;
+  const float* s;
+  int64_t rows; int32_t E; float tau; float slope;
+  void* dlogits; int64_t ld; int32_t fill_cols;
+} ZsGumbelStBwd;
+int zs_gumbel_st_bwd(const ZsGumbelStBwd* p, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * zs_gru_fwd / zs_gru_bwd: bidirectional single-layer nn.GRU with zero initial state
  * (model/model.py:59-66, 389, 299), gate order r,z,n.  gi = X W_ih^T + b_ih for BOTH directions
  * ([B*T][ldgi], columns dir*3H + {r,z,n}*H) comes from zs_gemm_conv.  Per time step the library

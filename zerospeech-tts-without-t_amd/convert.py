@@ -444,7 +444,8 @@ def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, m
     one (convert.py:151-165), as a few large batches on the GPU.
     specs: list of [T_i, 513] arrays (host arrays, or torch tensors already on the device).  decode_speakers: optional list of
     target speaker ids -> also returns the decoded spectrograms (enc_only path of convert()).  noise_fn(n_frag, T', E) -> Gumbel
-    noise [n, T', E, 2] or None makes the stochastic discretiser reproducible (called once per batch; T' = encoded frames of the
+    noise of the encoder mode's shape ([n, T', E, 2] multilabel_binary, [n, T', E] one_hot, [n, T', E, E] binary; None for
+    continues, which draws none) or None makes the stochastic discretiser reproducible (called once per batch; T' = encoded frames of the
     longest member).  Returns (encodings list, decoded list or None); to_host=False leaves the decoded spectrograms on the
     device (torch tensors [T_out, 513]) for spectrogram2wav_batch."""
     q = _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host=to_host)

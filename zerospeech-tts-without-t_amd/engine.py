@@ -24,12 +24,23 @@ def _half_up(t):
     return (t + 1) // 2
 
 
+# enc_mode -> discretiser of zs_gumbel_st_fwd / _bwd ('multilabel_binary' runs zs_mbv_fwd / _bwd)
+GUMBEL_MODES = {'one_hot': L.ZS_ENC_ONE_HOT, 'binary': L.ZS_ENC_BINARY, 'continues': L.ZS_ENC_CONTINUES}
+
+
+def linear_width(enc_mode, E):
+    """Output columns of the encoder's `linear` (model/model.py:391-398): the width of `enc`."""
+    return {'multilabel_binary': 2 * E, 'binary': E * E}.get(enc_mode, E)
+
+
 class EncoderEngine(object):
-    def __init__(self, ctx, P, G, c_in, c_h1, c_h2, c_h3, enc_size, ns, dp, seg_len):
+    def __init__(self, ctx, P, G, c_in, c_h1, c_h2, c_h3, enc_size, ns, dp, seg_len, enc_mode='multilabel_binary'):
         """P / G: dicts name -> fp32 parameter / gradient tensors (reference state_dict names)."""
         self.ctx = ctx
         self.uid = _uid()
         self.c_in, self.c1, self.c2, self.H, self.E = c_in, c_h1, c_h2, c_h3, enc_size
+        self.mode = enc_mode
+        self.n_lin = linear_width(enc_mode, enc_size)
         self.ns, self.dp = float(ns), float(dp)
         self.pad_mode = L.ZS_PAD_REFLECT if seg_len >= 64 else L.ZS_PAD_ZERO     # model/model.py:38
         if c_h1 % 8 or c_h2 % 8:
@@ -56,7 +67,8 @@ class EncoderEngine(object):
     # ------------------------------------------------------------------------------------------
     def forward(self, x, training, noise=None, noise_kind=2, seed=0, drop_masks=None, seed_ptr=None, lengths=None):
         """x: fp32 [B, T, c_in] contiguous on device.  Returns (bits Act [B,T',E] (T dtype, feeds the decoder),
-        bits_f32 [B,T',E], logits_f32 [B,T',ld]).  noise: fp32 [B,T',E,2] (Gumbel if noise_kind 0, uniform if 1).
+        bits_f32 [B,T',E], logits_f32 [B,T',ld] with n_lin valid columns).  noise (Gumbel if noise_kind 0, uniform if 1): fp32
+        [B,T',E,2] (multilabel_binary), [B,T',E] (one_hot), [B,T',E,E] (binary); continues takes none.
         lengths: host int sequence [B], frames per sample (ragged batch, inference only): sample b is computed exactly as if it ran
         alone with T = lengths[b] (padding, InstanceNorm statistics and the reverse GRU at its own end); its first
         ceil(ceil(ceil(lengths[b]/2)/2)/2) output rows are valid, the rest is garbage."""
@@ -125,15 +137,25 @@ class EncoderEngine(object):
         gi = c.act('e_gi' + tag, B, T4, 6 * H)
         gates = c.raw('e_gates' + tag, B * T4 * 8 * H, c.tdt) if training else None
         self.gru.fwd(a, cat2, c2, gi, gates, lengths=Ls[3])                                                 # :454-455
-        logits = c.act('e_logits' + tag, B, T4, 2 * E, dtype=torch.float32)
+        logits = c.act('e_logits' + tag, B, T4, self.n_lin, dtype=torch.float32)
         self.linear.fwd(cat2, out=logits, out_f32=True)                                                      # :475
         bits = c.act('e_bits' + tag, B, T4, E)
         bits_f32 = c.f32('e_bitsf' + tag, B * T4 * E)
-        y0 = c.f32('e_y0' + tag, B * T4 * E)
-        L.call('zs_mbv_fwd', 'ZsMbvFwd', st, dtype=c.dt, logits=logits.ptr(), ld=logits.ld, logits_f32=1,
-               noise=L.ptr(noise), noise_kind=noise_kind, seed=seed, seed_ptr=seed_ptr, rows=B * T4, E=E, tau=0.1, bits=bits.ptr(),
-               ld_bits=bits.ld, bits_fill_cols=bits.ld, bits_f32=L.ptr(bits_f32), y0=L.ptr(y0))               # :476-480
-        tp.update(cat2=cat2, gates=gates, y0=y0, T4=T4, gru_in=a, logits=logits)
+        s = None
+        if self.mode == 'multilabel_binary':
+            y0 = c.f32('e_y0' + tag, B * T4 * E)
+            L.call('zs_mbv_fwd', 'ZsMbvFwd', st, dtype=c.dt, logits=logits.ptr(), ld=logits.ld, logits_f32=1,
+                   noise=L.ptr(noise), noise_kind=noise_kind, seed=seed, seed_ptr=seed_ptr, rows=B * T4, E=E, tau=0.1, bits=bits.ptr(),
+                   ld_bits=bits.ld, bits_fill_cols=bits.ld, bits_f32=L.ptr(bits_f32), y0=L.ptr(y0))           # :476-480
+        else:                                                                                                # :457-472
+            soft = self.mode != 'continues'
+            y0 = c.f32('e_y0' + tag, B * T4 * self.n_lin) if (training and soft) else None
+            s = c.f32('e_s' + tag, B * T4 * E) if (training and self.mode == 'binary') else None
+            L.call('zs_gumbel_st_fwd', 'ZsGumbelStFwd', st, dtype=c.dt, mode=GUMBEL_MODES[self.mode], logits=logits.ptr(),
+                   ld=logits.ld, logits_f32=1, noise=(L.ptr(noise) if soft else None), noise_kind=noise_kind, seed=seed,
+                   seed_ptr=seed_ptr, rows=B * T4, E=E, tau=0.1, slope=self.ns, bits=bits.ptr(), ld_bits=bits.ld,
+                   bits_fill_cols=bits.ld, bits_f32=L.ptr(bits_f32), y=L.ptr(y0), s=L.ptr(s))
+        tp.update(cat2=cat2, gates=gates, y0=y0, s=s, T4=T4, gru_in=a, logits=logits)
         self.tape = tp
         return bits, bits_f32[:B * T4 * E].view(B, T4, E), logits
 
@@ -165,7 +187,7 @@ class EncoderEngine(object):
 
     # ------------------------------------------------------------------------------------------
     def backward(self, dbits, dlogits_extra=None):
-        """dbits: Act [B,T',E] gradient w.r.t. enc_act (may be None); dlogits_extra: Act [B,T',2E] gradient w.r.t. the
+        """dbits: Act [B,T',E] gradient w.r.t. enc_act (may be None); dlogits_extra: Act [B,T',n_lin] gradient w.r.t. the
         pre-activation `enc` (speaker-classifier term of trainer.py:444).  Fills every encoder parameter gradient."""
         self.backward_main(dbits, dlogits_extra)
         self.backward_bank()
@@ -180,10 +202,17 @@ class EncoderEngine(object):
         st = c.stream
         tag = '_%d_%d_%d' % (self.uid, B, T)
         cat2 = tp['cat2']
-        dlog = c.act('e_dlog' + tag, B, T4, 2 * E)
+        dlog = c.act('e_dlog' + tag, B, T4, self.n_lin)
         if dbits is not None:
-            L.call('zs_mbv_bwd', 'ZsMbvBwd', st, dtype=c.dt, dbits=dbits.ptr(), ld_dbits=dbits.ld, y0=L.ptr(tp['y0']),
-                   rows=B * T4, E=E, tau=0.1, dlogits=dlog.ptr(), ld=dlog.ld, fill_cols=dlog.ld)
+            if self.mode == 'multilabel_binary':
+                L.call('zs_mbv_bwd', 'ZsMbvBwd', st, dtype=c.dt, dbits=dbits.ptr(), ld_dbits=dbits.ld, y0=L.ptr(tp['y0']),
+                       rows=B * T4, E=E, tau=0.1, dlogits=dlog.ptr(), ld=dlog.ld, fill_cols=dlog.ld)
+            else:
+                cont = self.mode == 'continues'          # leaky_relu backward reads the pre-activation itself
+                y, ld_y = (tp['logits'].ptr(), tp['logits'].ld) if cont else (L.ptr(tp['y0']), self.n_lin)
+                L.call('zs_gumbel_st_bwd', 'ZsGumbelStBwd', st, dtype=c.dt, mode=GUMBEL_MODES[self.mode], dbits=dbits.ptr(),
+                       ld_dbits=dbits.ld, y=y, ld_y=ld_y, s=L.ptr(tp['s']), rows=B * T4, E=E, tau=0.1, slope=ns,
+                       dlogits=dlog.ptr(), ld=dlog.ld, fill_cols=dlog.ld)
             if dlogits_extra is not None:
                 dlog.t[:B * T4 * dlog.ld].add_(dlogits_extra.t[:B * T4 * dlogits_extra.ld])
         else:

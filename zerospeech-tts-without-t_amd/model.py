@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .engine import ClassifierEngine, DecoderEngine, EncoderEngine
+from .engine import ClassifierEngine, DecoderEngine, EncoderEngine, linear_width
 from .layers import Act, Ctx, rup
 
 
@@ -119,18 +119,29 @@ class ZsModule(nn.Module):
         return out
 
 
+ENC_MODES = ('multilabel_binary', 'one_hot', 'binary', 'continues')
+
+
 class Encoder(ZsModule):
-    """model/model.py:368-489 (enc_mode 'multilabel_binary' is the accelerated path)."""
+    """model/model.py:368-489.  enc_mode 'multilabel_binary' (zs_mbv_fwd), 'one_hot', 'binary' (zs_gumbel_st_fwd, Gumbel-softmax
+    straight-through) or 'continues' (leaky_relu); 'gumbel_t' is not built."""
 
     def __init__(self, c_in=513, c_h1=128, c_h2=512, c_h3=128, ns=0.2, dp=0.5, enc_size=512, seg_len=64,
                  enc_mode='continues', dtype=None):
         super(Encoder, self).__init__(dtype)
         self.ns, self.dp, self.enc_size, self.seg_len, self.enc_mode = ns, dp, enc_size, seg_len, enc_mode
         self.c_in, self.c_h1, self.c_h2, self.c_h3 = c_in, c_h1, c_h2, c_h3
-        if enc_mode != 'multilabel_binary':
-            if enc_mode in ('continues', 'one_hot', 'binary', 'gumbel_t'):
-                raise NotImplementedError("enc_mode %r is not on the MI355X hot path (only 'multilabel_binary' is)" % enc_mode)
+        if enc_mode not in ENC_MODES:
+            if enc_mode == 'gumbel_t':
+                raise NotImplementedError("enc_mode 'gumbel_t' (softmax over time) is not built: use one of %s" % ', '.join(ENC_MODES))
             raise NotImplementedError('Invalid encoding mode!')
+        if enc_mode in ('one_hot', 'continues'):
+            assert enc_size % 2 == 0                                                              # model/model.py:396
+        if enc_mode == 'binary' and enc_size > 64:
+            raise ValueError("enc_mode 'binary' supports enc_size <= 64 (its linear layer has enc_size^2 = %d outputs)" % enc_size ** 2)
+        if enc_mode == 'one_hot' and enc_size > 1024:
+            raise ValueError("enc_mode 'one_hot' supports enc_size <= 1024 (got %d)" % enc_size)
+        self.n_lin = linear_width(enc_mode, enc_size)
         self.conv1s = nn.ModuleList([nn.Conv1d(c_in, c_h1, kernel_size=k) for k in range(1, 8)])
         self.conv2 = nn.Conv1d(len(self.conv1s) * c_h1 + c_in, c_h2, kernel_size=1)
         self.conv3 = nn.Conv1d(c_h2, c_h2, kernel_size=5)
@@ -144,18 +155,39 @@ class Encoder(ZsModule):
         self.dense3 = nn.Linear(c_h2, c_h2)
         self.dense4 = nn.Linear(c_h2, c_h2)
         self.RNN = nn.GRU(input_size=c_h2, hidden_size=c_h3, num_layers=1, bidirectional=True)
-        self.linear = nn.Linear(c_h2 + 2 * c_h3, enc_size * 2)
+        self.linear = nn.Linear(c_h2 + 2 * c_h3, self.n_lin)
 
     def _make_engine(self, ctx, P, G):
-        return EncoderEngine(ctx, P, G, self.c_in, self.c_h1, self.c_h2, self.c_h3, self.enc_size, self.ns, self.dp, self.seg_len)
+        return EncoderEngine(ctx, P, G, self.c_in, self.c_h1, self.c_h2, self.c_h3, self.enc_size, self.ns, self.dp, self.seg_len,
+                             enc_mode=self.enc_mode)
+
+    def noise_shape(self, B, T4):
+        """Shape of the U / G this mode draws for B samples of T4 encoded frames (the reference's torch.rand shape), or None."""
+        E = self.enc_size
+        return {'multilabel_binary': (B, T4, E, 2), 'one_hot': (B, T4, E), 'binary': (B, T4, E, E)}.get(self.enc_mode)
+
+    def check_noise(self, x, U=None, G=None):
+        """ValueError (before any launch) if U / G does not fit this mode's noise for input x [B, c_in, T]."""
+        noise = G if G is not None else U
+        if noise is None or self.enc_mode == 'multilabel_binary':
+            return
+        B, T = x.shape[0], x.shape[2]
+        want = self.noise_shape(B, (((T + 1) // 2 + 1) // 2 + 1) // 2)
+        if want is None:
+            raise ValueError("enc_mode %r draws no noise: U / G must be None" % self.enc_mode)
+        if tuple(noise.shape) != want:
+            raise ValueError('enc_mode %r: %s must have shape %s, got %s' % (self.enc_mode, 'G' if G is not None else 'U', want,
+                                                                             tuple(noise.shape)))
 
     def forward(self, x, U=None, G=None, drop_masks=None, seed=None, lengths=None):
-        """x [B, c_in, T] -> (enc_act [B, E, T/8], enc [B, 2E, T/8]).  The Gumbel-softmax draws noise in
-        eval mode too (reference behaviour, model/model.py:95-98): pass U (uniform) or G (Gumbel) to make
-        it reproducible; otherwise a counter-hash stream seeded from torch's RNG is used.
+        """x [B, c_in, T] -> (enc_act [B, E, T/8], enc [B, n_lin, T/8]), n_lin = 2E (multilabel_binary), E (one_hot, continues)
+        or E^2 (binary).  The Gumbel-softmax draws noise in eval mode too (reference behaviour, model/model.py:95-98): pass U
+        (uniform) or G (Gumbel), shaped [B, T/8, E, 2] / [B, T/8, E] / [B, T/8, E, E] by mode, to make it reproducible;
+        otherwise a counter-hash stream seeded from torch's RNG is used.  'continues' takes no noise.
         lengths (eval only): frames per sample of a ragged batch padded to T -- every sample is computed exactly as if it were
         forwarded alone with its own length (the reference forwards such fragments one at a time, convert.py:154-165); the
         first ceil(lengths[b] / 8) output frames of sample b are valid."""
+        self.check_noise(x, U=U, G=G)
         eng = self._engine()
         xb = x.detach().permute(0, 2, 1).contiguous().float()
         noise, kind = None, 2

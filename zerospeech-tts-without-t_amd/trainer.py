@@ -492,7 +492,8 @@ class ClfStep(object):
         self._dl = None
 
     def _classify(self, logits_act, c, grad_scale, seed, drop_masks=None):
-        """enc logits Act fp32 [B,T',2E] -> CE loss (device scalar), fills self._dl = grad_scale * dCE/dlogits."""
+        """enc logits Act fp32 [B,T',n_lin] (the encoder's pre-activation: 2E, E or E^2 columns by enc_mode) -> CE loss (device
+        scalar), fills self._dl = grad_scale * dCE/dlogits."""
         clf = self.clf
         clf.train()
         ce = clf._engine()
