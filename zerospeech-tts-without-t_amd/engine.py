@@ -2,6 +2,7 @@
 
 EncoderEngine  <->  Encoder.forward          (reference model/model.py:440-489) and its autograd backward
 DecoderEngine  <->  Decoder.forward          (reference model/model.py:344-365) and its autograd backward
+PatcherEngine  <->  Spectrogram_Patcher.forward (reference model/model.py:532-549) and its backward to the parameters
 Every arithmetic step is a libzs_amd.so kernel; torch only owns the memory.
 """
 import os
@@ -295,6 +296,7 @@ class DecoderEngine(object):
         self.linear = mk('linear')
         self.emb = [P['emb%d.weight' % i] for i in range(1, 6)]
         self.gemb = [G['emb%d.weight' % i] for i in range(1, 6)]
+        self.e_dense, self.e_rnn = 3, 4                   # emb4 feeds the dense blocks, emb5 the GRU input and append_emb
         self.layers = [self.input_emb] + [l for p in self.convs for l in p] + [l for p in self.dense for l in p] + \
             [self.dense5, self.linear]
         self.tape = None
@@ -340,23 +342,29 @@ class DecoderEngine(object):
             stt = self._in(yb, xn, xen, nxt, cidx, L.ZS_RES_UPSAMPLE2, x, training, 'c%d' % i, lengths=Ls[i + 1])
             tp['blocks'].append((x, xe, ya, s, yb, stt, T))
             x, xe, T = xn, xen, 2 * T
+        return self._fwd_dense(tp, x, xe, cidx, T, tag, B, training, Ls[3])
+
+    def _fwd_dense(self, tp, x, xe, cidx, T, tag, B, training, lengths):
+        """The two dense blocks, the GRU and the tail from x (and xe = x + emb[e_dense]) on; shared with PatcherEngine."""
+        c, ns, ch, emb = self.ctx, self.ns, self.ch, self.emb
+        ed, er = self.e_dense, self.e_rnn
         cat3 = c.act('d_cat3' + tag, B, T, 3 * ch)
         for j, (la, lb) in enumerate(self.dense):                                                        # :333-342, :350-351
             y1 = c.act('d_y1%d' % j + tag, B, T, ch)
             y1e = c.act('d_y1e%d' % j + tag, B, T, ch)
-            la.fwd(xe, out=y1, act=LRELU, slope=ns, out2=y1e, vec2=emb[3], idx=cidx)
+            la.fwd(xe, out=y1, act=LRELU, slope=ns, out2=y1e, vec2=emb[ed], idx=cidx)
             y2 = c.act('d_y2%d' % j + tag, B, T, ch)
             lb.fwd(y1e, out=y2, act=LRELU, slope=ns)
             xn = c.act('d_dx%d' % j + tag, B, T, ch) if j == 0 else Act(cat3.t, B, T, ch, cat3.ld, 0, ch)
             xen = c.act('d_dxe%d' % j + tag, B, T, ch)
-            stt = self._in(y2, xn, xen, emb[3] if j == 0 else emb[4], cidx, L.ZS_RES_IDENTITY, x, training, 'd%d' % j, lengths=Ls[3])
+            stt = self._in(y2, xn, xen, emb[ed] if j == 0 else emb[er], cidx, L.ZS_RES_IDENTITY, x, training, 'd%d' % j, lengths=lengths)
             tp['dense'].append((x, xe, y1, y1e, y2, stt))
             x, xe = xn, xen
         H = ch // 2
         gi = c.act('d_gi' + tag, B, T, 6 * H)
         gates = c.raw('d_gates' + tag, B * T * 8 * H, c.tdt) if training else None
         # :352-356, and append_emb (:357) rides on the recurrence's stores (third block of cat3 = emb5[c_b] at every t)
-        self.gru.fwd(xe, cat3, ch, gi, gates, bcast=(emb[4], cidx, 2 * ch), lengths=Ls[3])
+        self.gru.fwd(xe, cat3, ch, gi, gates, bcast=(emb[er], cidx, 2 * ch), lengths=lengths)
         h5 = c.act('d_h5' + tag, B, T, ch)
         self.dense5.fwd(cat3, out=h5, act=LRELU, slope=ns)                                                # :358-359
         return self._fwd_tail(c, tp, h5, cat3, gates, xe, T, tag, B)
@@ -415,6 +423,7 @@ class DecoderEngine(object):
         tag = '_%d_%d_%d' % (self.uid, B, T0)
         cat3, h5 = tp['cat3'], tp['h5']
         H = ch // 2
+        ed, er = self.e_dense, self.e_rnn
         self._embsum = c.f32('d_embsum' + tag, 6 * B * ch)      # slots 0..4: per-sample sums for emb1..emb5; 5: column sums of dz5
         self._embsum.zero_()
         self.linear.wgrad(dlogit, h5)
@@ -436,23 +445,23 @@ class DecoderEngine(object):
             sT = c.act('d_s5' + tag, B, 1, ch)
             L.call('zs_cast_rows', 'ZsCastRows', c.stream, dtype=c.dt, src=s32.ptr(), ld_src=ch, src_f32=1, dst=sT.ptr(), ld_dst=sT.ld,
                    dst_f32=0, col_off=0, rows=B, cols=ch, fill_cols=sT.ld, act=L.ZS_ACT_NONE)
-            slot4 = Act(self._embsum, B, 1, ch, ch, 4 * B * ch)
+            slot4 = Act(self._embsum, B, 1, ch, ch, er * B * ch)
             self.dense5.dgrad(sT, 1, slot4, add_src=slot4, out_f32=True, add_f32=True, n_cols=ch, n_off=2 * ch)
         elif fuse:                                                                           # d emb5 via append_emb: the third
-            self.dense5.dgrad(dz5, T, dcat3, colsum=slot(4, 2 * ch), out_cols=2 * ch)        # column block is summed, not stored
+            self.dense5.dgrad(dz5, T, dcat3, colsum=slot(er, 2 * ch), out_cols=2 * ch)        # column block is summed, not stored
         else:
             self.dense5.dgrad(dz5, T, dcat3)
-            self._combine(dcat3.sub(2 * ch, ch), T, 0, 0, None, emb_i=4)
+            self._combine(dcat3.sub(2 * ch, ch), T, 0, 0, None, emb_i=er)
         dgi = c.act('d_dgi' + tag, B, T, 6 * H)
         dgh = c.act('d_dgh' + tag, B, T, 6 * H)
         gp = c.act('d_gpA' + tag, B, T + 2, ch)
         gpv = Act(gp.t, B, T, ch, gp.ld)
         dx = c.act('d_dxA' + tag, B, T, ch)
         if fuse:                                                                                     # out+emb5 (:353)
-            self.gru.bwd(dcat3, ch, cat3, ch, tp['gates'], tp['gru_in'], dgi, dgh, dx, add_src=dcat3.sub(0, ch), colsum=slot(4))
+            self.gru.bwd(dcat3, ch, cat3, ch, tp['gates'], tp['gru_in'], dgi, dgh, dx, add_src=dcat3.sub(0, ch), colsum=slot(er))
         else:
             self.gru.bwd(dcat3, ch, cat3, ch, tp['gates'], tp['gru_in'], dgi, dgh, gpv)
-            self._combine(gpv, T, 0, 0, dx, emb_i=4, res_mode=L.ZS_RES_IDENTITY, res=dcat3.sub(0, ch))
+            self._combine(gpv, T, 0, 0, dx, emb_i=er, res_mode=L.ZS_RES_IDENTITY, res=dcat3.sub(0, ch))
         for j in (1, 0):
             la, lb = self.dense[j]
             xin, xe, y1, y1e, y2, stt = tp['dense'][j]
@@ -461,17 +470,17 @@ class DecoderEngine(object):
             lb.wgrad(dz2, y1e)
             dz1 = c.act('d_dz1%d' % j + tag, B, T, ch)
             if fuse:
-                lb.dgrad(dz2, T, dz1, dact_src=y1, slope=ns, colsum=slot(3))
+                lb.dgrad(dz2, T, dz1, dact_src=y1, slope=ns, colsum=slot(ed))
             else:
                 lb.dgrad(dz2, T, gpv)
-                self._combine(gpv, T, 0, 0, dz1, emb_i=3, dact=y1)
+                self._combine(gpv, T, 0, 0, dz1, emb_i=ed, dact=y1)
             la.wgrad(dz1, xe)
             dn = c.act('d_dxD%d' % j + tag, B, T, ch)
             if fuse:
-                la.dgrad(dz1, T, dn, add_src=dx, colsum=slot(3))
+                la.dgrad(dz1, T, dn, add_src=dx, colsum=slot(ed))
             else:
                 la.dgrad(dz1, T, gpv)
-                self._combine(gpv, T, 0, 0, dn, emb_i=3, res_mode=L.ZS_RES_IDENTITY, res=dx)
+                self._combine(gpv, T, 0, 0, dn, emb_i=ed, res_mode=L.ZS_RES_IDENTITY, res=dx)
             dx = dn
         self._bw = (dx, gp, tag)
 
@@ -510,6 +519,73 @@ class DecoderEngine(object):
             dbits = c.act('d_dbits' + tag, B, T0, self.E)
             self.input_emb.dgrad(dx, T0, dbits)
         return dbits
+
+
+class PatcherEngine(DecoderEngine):
+    """Spectrogram_Patcher.forward (reference model/model.py:532-549) and its backward to the parameter gradients (stage 2 steps
+    only the patcher: no gradient w.r.t. its input).  The decoder's two dense blocks, GRU and tail at the input's own time
+    resolution, behind one K = c_in linear (input_layer, no activation) instead of the conv blocks; emb1 feeds all four dense
+    layers, emb2 the GRU input and append_emb."""
+
+    def __init__(self, ctx, P, G, c_in, c_out, c_h, c_a, ns):
+        self.ctx = ctx
+        self.uid = _uid()
+        self.E, self.F, self.ch, self.n_spk = c_in, c_out, c_h, c_a
+        self.ns = float(ns)
+        self.pad_mode = L.ZS_PAD_ZERO                     # every layer is a Linear: no time padding anywhere
+        self.out_act = L.ZS_ACT_SIGMOID
+        if c_h % 32:
+            raise ValueError('Spectrogram_Patcher c_h must be a multiple of 32 (got %d)' % c_h)
+        mk = lambda n: ConvLayer(ctx, P[n + '.weight'], P[n + '.bias'], G[n + '.weight'], G[n + '.bias'], pad_mode=self.pad_mode, name=n)
+        self.input_layer = mk('input_layer')
+        self.dense = [(mk('dense%d' % a), mk('dense%d' % b)) for a, b in ((1, 2), (3, 4))]
+        self.gru = GruLayer(ctx, P, G, 'RNN.', name='sp%d' % self.uid)
+        self.dense5 = mk('dense5')
+        self.linear = mk('linear')
+        self.emb = [P['emb1.weight'], P['emb2.weight']]
+        self.gemb = [G['emb1.weight'], G['emb2.weight']]
+        self.e_dense, self.e_rnn = 0, 1
+        self.layers = [self.input_layer] + [l for p in self.dense for l in p] + [self.dense5, self.linear]
+        self.tape = None
+
+    def forward(self, xd, cidx, training, lengths=None):
+        """xd: Act fp32 [B, T, c_in] (a decoder's output rows, any ld >= c_in); cidx int64 [B].  Returns Act fp32 [B, T, c_out]
+        (after the sigmoid).  lengths: host int sequence [B], frames per sample (ragged batch, inference only): sample b is computed
+        as if it ran alone with T = lengths[b] (InstanceNorm statistics and the reverse GRU over its own frames); its first
+        lengths[b] output rows are valid."""
+        c, ch = self.ctx, self.ch
+        B, T = xd.B, xd.T
+        ln = None
+        if lengths is not None:
+            if training:
+                raise L.ZsError('PatcherEngine: ragged batches are an inference feature')
+            l0 = torch.as_tensor(lengths, dtype=torch.int32).reshape(-1)
+            if l0.numel() != B or int(l0.max()) > T or int(l0.min()) < 1:
+                raise L.ZsError('PatcherEngine: lengths must be %d values in [1, %d]' % (B, T))
+            ln = l0.to(c.device, non_blocking=True)
+        tag = '_%d_%d_%d' % (self.uid, B, T)
+        xin = c.act('p_xin' + tag, B, T, self.E)
+        L.call('zs_cast_rows', 'ZsCastRows', c.stream, dtype=c.dt, src=xd.ptr(), ld_src=xd.ld, src_f32=1, dst=xin.ptr(), ld_dst=xin.ld,
+               dst_f32=0, col_off=0, rows=B * T, cols=self.E, fill_cols=xin.ld, act=L.ZS_ACT_NONE)
+        tp = {'B': B, 'T0': T, 'training': training, 'cidx': cidx, 'xin': xin, 'dense': []}
+        x = c.act('d_x0' + tag, B, T, ch)
+        xe = c.act('d_xe0' + tag, B, T, ch)
+        self.input_layer.fwd(xin, out=x, out2=xe, vec2=self.emb[0], idx=cidx)                          # :537, + emb1 (:523)
+        return self._fwd_dense(tp, x, xe, cidx, T, tag, B, training, ln)                                # :539-549
+
+    def backward(self, dlogit, need_dbits=False):
+        """dlogit: Act [B, T, c_out] gradient w.r.t. the pre-sigmoid output.  Fills (overwrites) every parameter gradient; weight
+        gradients may still run on the side streams (join_side)."""
+        if need_dbits:
+            raise L.ZsError('PatcherEngine: the gradient w.r.t. the input spectrogram is not computed')
+        self.backward_head(dlogit)
+        dx, _, _ = self._bw
+        c, tp, B, ch = self.ctx, self.tape, self.tape['B'], self.ch
+        for k in range(2):                                 # nn.Embedding backward, fixed sample order
+            L.call('zs_emb_scatter', 'ZsEmbScatter', c.stream, emb_sum=L.ptr(self._embsum, k * B * ch), emb_ld=ch, idx=L.ptr(tp['cidx']),
+                   B=B, demb=L.ptr(self.gemb[k]), demb_ld=ch, n_rows=self.n_spk, C=ch, accumulate=0)
+        self.input_layer.wgrad(dx, tp['xin'])
+        return None
 
 
 class ClassifierEngine(object):

@@ -1,4 +1,4 @@
-"""Drop-in Encoder / Decoder / SpeakerClassifier modules (reference: model/model.py:231-489).
+"""Drop-in Encoder / Decoder / SpeakerClassifier / Spectrogram_Patcher modules (reference: model/model.py:231-549).
 
 Same constructor arguments, same parameter names and shapes (so reference checkpoints load with
 load_state_dict), same forward signatures and return tuples in the reference's [B, C, T] layout.
@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .engine import ClassifierEngine, DecoderEngine, EncoderEngine, linear_width
+from .engine import ClassifierEngine, DecoderEngine, EncoderEngine, PatcherEngine, linear_width
 from .layers import Act, Ctx, rup
 
 
@@ -253,6 +253,44 @@ class Decoder(ZsModule):
         cidx = c.detach().to(xb.device, torch.int64).contiguous()
         xdec = eng.forward(bits, cidx, self.training, lengths=lengths)
         return xdec.valid().permute(0, 2, 1).clone()
+
+
+class Spectrogram_Patcher(ZsModule):
+    """model/model.py:505-549: the stage-2 generator of g_mode 'spectrogram', a post-filter on the decoder's output spectrogram
+    (trainer.py:283-284: x_gen = x_dec + G(x_dec, c - shift)).  ins_norm1 / ins_norm2 have no parameters (no affine); the
+    engine runs them as the InstanceNorm kernel."""
+
+    def __init__(self, c_in=512, c_out=513, c_h=512, c_a=8, ns=0.2, seg_len=64, dtype=None):
+        super(Spectrogram_Patcher, self).__init__(dtype)
+        self.ns, self.seg_len = ns, seg_len
+        self.c_in, self.c_out, self.c_h, self.c_a = c_in, c_out, c_h, c_a
+        self.input_layer = nn.Linear(c_in, c_h)
+        self.dense1 = nn.Linear(c_h, c_h)
+        self.dense2 = nn.Linear(c_h, c_h)
+        self.dense3 = nn.Linear(c_h, c_h)
+        self.dense4 = nn.Linear(c_h, c_h)
+        self.RNN = nn.GRU(input_size=c_h, hidden_size=c_h // 2, num_layers=1, bidirectional=True)
+        self.dense5 = nn.Linear(2 * c_h + c_h, c_h)
+        self.linear = nn.Linear(c_h, c_out)
+        self.emb1 = nn.Embedding(c_a, c_h)
+        self.emb2 = nn.Embedding(c_a, c_h)
+
+    def _make_engine(self, ctx, P, G):
+        return PatcherEngine(ctx, P, G, self.c_in, self.c_out, self.c_h, self.c_a, self.ns)
+
+    def forward(self, x, c, lengths=None):
+        """x: spectrogram [B, c_in, T] (fp32);  c: int64 [B]  ->  [B, c_out, T] (after the sigmoid).
+        lengths (eval only): frames per sample of a ragged batch padded to T; the first lengths[b] output frames are valid."""
+        eng = self._engine()
+        ctx = eng.ctx
+        xb = x.detach().permute(0, 2, 1).contiguous().float()
+        B, T, F = xb.shape
+        if F != self.c_in:
+            raise ValueError('Spectrogram_Patcher expects %d channels (got %d)' % (self.c_in, F))
+        xa = Act(xb.reshape(-1), B, T, F, F)
+        cidx = c.detach().to(xb.device, torch.int64).contiguous()
+        out = eng.forward(xa, cidx, self.training, lengths=lengths)
+        return out.valid().permute(0, 2, 1).clone()
 
 
 class SpeakerClassifier(ZsModule):

@@ -6,7 +6,9 @@ One D step  (trainer.py:470-497):  loss = -beta_dis * mean(D(x_t) - D(x_gen)) + 
 One G step  (trainer.py:514-533):  loss = beta_clf * CE(D_clf(x_gen), c_t - shift) - beta_gen * mean D(x_gen);
                                             clip(Generator), Adam
 Target-guided (trainer.py:535-541): loss_rec = mean|gen_step(Encoder(x_t), c_t) - x_t|;  Adam WITHOUT clipping.
-x_gen = gen_step(Encoder(x_s), c_t) = x_dec + x_dec * Generator(enc, c_t - shift)   ('targeted_residual', trainer.py:266-278).
+x_gen = gen_step(Encoder(x_s), c_t) = x_dec + x_dec * Generator(enc, c_t - shift)   ('targeted_residual', trainer.py:266-278),
+                                     = x_dec + Generator(x_dec, c_t - shift)          ('spectrogram', trainer.py:283-284: the
+                                       Spectrogram_Patcher post-filters the decoder's output; x_dec is a constant to it).
 
 Only the network that the reference's optimizer steps receives gradients here: the reference lets autograd fill the
 gradients of Encoder / Decoder (and of the discriminator in the G step) as well but never uses them (reset_grad is called on
@@ -17,6 +19,8 @@ import torch
 from . import _lib as L
 from . import layers, parallel
 from .layers import join_side
+
+G_MODES = ('naive', 'targeted', 'targeted_residual', 'spectrogram')
 
 
 class NetOpt(object):
@@ -50,7 +54,7 @@ class PatchGANStep(object):
     def __init__(self, encoder, decoder, generator, discriminator, hps, g_mode):
         self.Encoder, self.Decoder, self.Generator, self.D = encoder, decoder, generator, discriminator
         self.hps, self.g_mode = hps, g_mode
-        if g_mode not in ('naive', 'targeted', 'targeted_residual'):
+        if g_mode not in G_MODES:
             raise NotImplementedError('Invalid generator mode to call gen_step()!')
         self.shift = 0 if g_mode == 'naive' else int(hps.n_speakers - hps.n_target_speakers)
         self.device = encoder.flat_params()[0].device
@@ -71,24 +75,40 @@ class PatchGANStep(object):
             raise RuntimeError('This generator can only convert to target speakers!')
 
     # ---- gen_step (trainer.py:266-278) ---------------------------------------------------------------------------------------
-    def gen_forward(self, x_btf, c, train_generator, noise=None, noise_kind=2, drop_masks=None, seed=None):
-        """x_btf fp32 [B, T, F] (source batch), c int64 [B] target speakers -> x_gen fp32 [B, T_out, F] contiguous."""
+    def gen_forward(self, x_btf, c, train_generator, noise=None, noise_kind=2, drop_masks=None, seed=None, x_dec=None):
+        """x_btf fp32 [B, T, F] (source batch), c int64 [B] target speakers -> x_gen fp32 [B, T_out, F] contiguous.
+        x_dec ('spectrogram' only): fp32 [B, T, F], a decoder output to post-filter in place of Decoder(Encoder(x_btf), c) (x_btf
+        is then unused): the patcher sees nothing else."""
         enc, dec, gen = self.Encoder, self.Decoder, self.Generator
         enc.train(); dec.train(); gen.train()
-        ee, de, ge = enc._engine(), dec._engine(), gen._engine()
-        if seed is None:
-            self.step_no += 1
-            seed = (self.step_no * 0x9E3779B97F4A7C15 + 12345) % (1 << 62) + 7 * parallel.rank()
-        bits, _, _ = ee.forward(x_btf, True, noise=noise, noise_kind=noise_kind, seed=seed, drop_masks=drop_masks)   # encode_step
-        xd = de.forward(bits, c, False)                                       # Decoder(enc, c)
+        ge = gen._engine()
+        ctx = ge.ctx
         # c - shift_c (trainer.py:277-279).  The range of c is checked where the batch is still on the host (check_targets(),
         # called once per host batch by the training loop / DevicePrefetcher): no device-to-host sync per step here
         cg = (c - self.shift) if self.shift else c
-        m = ge.forward(bits, cg.contiguous(), train_generator)                # Generator(enc, c - shift_c)
-        B, T = xd.B, xd.T
-        F = de.F
-        st = de.ctx.stream
-        x_gen = de.ctx.f32('s2_xgen_%d_%d' % (B, T), B * T * F)[:B * T * F].view(B, T, F)
+        if x_dec is not None:
+            if self.g_mode != 'spectrogram':
+                raise ValueError("gen_forward(x_dec=...) post-filters a given spectrogram: g_mode 'spectrogram' only")
+            B, T, F = x_dec.shape
+            xsrc = x_dec.contiguous()
+            xd = ge.ctx.act('s2_xdin_%d_%d' % (B, T), B, T, F, dtype=torch.float32)
+            L.call('zs_cast_rows', 'ZsCastRows', ge.ctx.stream, dtype=ge.ctx.dt, src=L.ptr(xsrc), ld_src=F, src_f32=1,
+                   dst=xd.ptr(), ld_dst=xd.ld, dst_f32=1, col_off=0, rows=B * T, cols=F, fill_cols=xd.ld, act=L.ZS_ACT_NONE)
+        else:
+            ee, de = enc._engine(), dec._engine()
+            ctx = de.ctx
+            if seed is None:
+                self.step_no += 1
+                seed = (self.step_no * 0x9E3779B97F4A7C15 + 12345) % (1 << 62) + 7 * parallel.rank()
+            bits, _, _ = ee.forward(x_btf, True, noise=noise, noise_kind=noise_kind, seed=seed, drop_masks=drop_masks)   # encode_step
+            xd = de.forward(bits, c, False)                                   # Decoder(enc, c)
+        if self.g_mode == 'spectrogram':
+            m = ge.forward(xd, cg.contiguous(), train_generator)              # Generator(x_dec, c - shift_c) (trainer.py:283)
+        else:
+            m = ge.forward(bits, cg.contiguous(), train_generator)            # Generator(enc, c - shift_c)
+        B, T, F = xd.B, xd.T, xd.C
+        st = ctx.stream
+        x_gen = ctx.f32('s2_xgen_%d_%d' % (B, T), B * T * F)[:B * T * F].view(B, T, F)
         L.check(L.lib().zs_gen_combine_fwd(xd.ptr(), m.ptr(), xd.ld, L.ptr(x_gen), B * T, F, int(self.g_mode == 'targeted_residual'), st),
                 'zs_gen_combine_fwd')
         self._xd, self._m = xd, m
@@ -102,7 +122,7 @@ class PatchGANStep(object):
         dpre = ge.ctx.act('s2_dpre_%d_%d' % (B, T), B, T, F)
         L.call('zs_gen_combine_bwd', 'ZsGenCombineBwd', ge.ctx.stream, dtype=ge.ctx.dt, dx_gen=L.ptr(dx_gen), ld_dx=F, xd=xd.ptr(), m=m.ptr(),
                ld_in=m.ld, dpre=dpre.ptr(), ldo=dpre.ld, fill_cols=dpre.ld, rows=B * T, F=F, mode=int(self.g_mode == 'targeted_residual'),
-               tanh_out=int(self.Generator.output_mask))
+               tanh_out=int(getattr(self.Generator, 'output_mask', False)))
         ge.backward(dpre, need_dbits=False)
         join_side(self.device)
 

@@ -19,7 +19,7 @@ from . import _lib as L
 from . import parallel
 from . import layers
 from .layers import Act, join_side
-from .model import Decoder, Encoder, SpeakerClassifier
+from .model import Decoder, Encoder, SpeakerClassifier, Spectrogram_Patcher
 from .patch import PatchDiscriminator, TargetClassifier
 from .stage2 import PatchGANStep
 from .utils import Logger
@@ -608,8 +608,12 @@ class Trainer(object):
         elif self.g_mode in ('targeted', 'targeted_residual'):
             self.Generator = Decoder(ns=ns, c_in=hps.enc_size, c_h=hps.emb_size, c_a=hps.n_target_speakers, seg_len=hps.seg_len,
                                      output_mask=(self.g_mode == 'targeted_residual'), dtype=dt).to(dev)
-        elif self.g_mode in ('enhanced', 'spectrogram', 'tacotron'):
-            raise NotImplementedError('g_mode %r (stage-2 generator) is outside the MI355X hot path' % self.g_mode)
+        elif self.g_mode == 'spectrogram':                                        # trainer.py:77-78
+            self.Generator = Spectrogram_Patcher(ns=ns, c_in=513, c_h=hps.emb_size, c_a=hps.n_target_speakers, seg_len=hps.seg_len,
+                                                 dtype=dt).to(dev)
+        elif self.g_mode in ('enhanced', 'tacotron'):
+            raise NotImplementedError('g_mode %r (stage-2 generator) is not built: use naive, targeted, targeted_residual or '
+                                      'spectrogram' % self.g_mode)
         else:
             raise NotImplementedError('Invalid Generator mode!')
         enc_size = hps.enc_size
@@ -723,6 +727,8 @@ class Trainer(object):
                 x_dec = x_dec + self.Generator(enc, c - self.testing_shift_c)
             elif self.g_mode == 'targeted_residual':
                 x_dec = (x_dec * 1.0) + (1.0 * x_dec * self.Generator(enc, c - self.testing_shift_c))
+            elif self.g_mode == 'spectrogram':                                        # trainer.py:212-213
+                x_dec = x_dec + self.Generator(x_dec, c - self.testing_shift_c)
             else:
                 raise NotImplementedError('Invalid Generator mode!')
         elif verbose:
