@@ -47,6 +47,12 @@ const char* zs_last_error(void);
  *       packed weight has a multiple of 256 rows and the problem has at least that many 256x256 tiles
  *   "wgrad_p8" (ZS_WGRAD_P8, 1): 256x256 ping-pong weight-gradient kernel (bf16) where its heuristics accept the shape;
  *       0 = always the 128x128 kernel, 2 = whenever bf16 (tests)
+ *   "wgrad_dma" (ZS_WGRAD_DMA, 1): bf16 128x128 weight-gradient tiles by the LDS-DMA kernel; 0 = the register-staged kernel
+ *       (bit-identical at equal splits; tests)
+ *   "wgrad_reduce_taps" (ZS_WGRAD_REDUCE_TAPS, 1): Conv1d weight gradients (si = taps, sj = 1) reduced with stores in dW order;
+ *       0 = the per-(co, tap)-row reduce (bit-identical; tests)
+ *   "wgrad_alone" (ZS_WGRAD_ALONE, 0): weight gradients run alone on the chip (set by the context when it does not overlap them):
+ *       the split-K plan uses "wgrad_wgs128_alone" / "wgrad_slab_cost_alone" instead of "wgrad_wgs128" / "wgrad_slab_cost"
  *   "gru_persist" (ZS_GRU_PERSIST, 1): one persistent launch per GRU pass (forward and BPTT: the time loop runs on the
  *       device, W_hh stays in registers, h / dgh travel between workgroups as data-tagged 8-byte granules) when the grid fits
  *       one workgroup per CU and H allows it; 0 = one launch per time step

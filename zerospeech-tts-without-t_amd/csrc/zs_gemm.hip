@@ -7,7 +7,8 @@
 //      gemm_conv_ring_kernel                            256x128 tile, 3-stage LDS-DMA ring (>= 256 tiles)
 //      gemm_conv_dma_kernel                             128x128 tile, LDS-DMA double buffer (default for small layers)
 //      gemm_conv_kernel                                 128x128 tile, register-staged (reference variant, ZS_GEMM_DMA=0)
-//    and two weight-gradient kernels (gemm_wgrad_p8_kernel bf16 256x256 ping-pong, gemm_wgrad_kernel 128x128).
+//    and three weight-gradient kernels (gemm_wgrad_p8_kernel bf16 256x256 ping-pong, gemm_wgrad_dma_kernel bf16 128x128 LDS-DMA,
+//    gemm_wgrad_kernel 128x128 register-staged: fp32, and the bf16 reference variant, ZS_WGRAD_DMA=0).
 //  * The MI355X is power-capped (1400 W) in these kernels, not issue-bound: what counts is bytes moved per FLOP and the
 //    MFMA shape (16x16x32 is the cheaper instruction), see DESIGN.md section 7.
 //  * Operand rows are whole channels-last activation rows, so the conv "im2col" is a per-row pointer
@@ -1396,6 +1397,57 @@ template <> struct WFrag<bf16_t> {
   }
 };
 
+// End of a 128x128 weight-gradient tile (gemm_wgrad_kernel and gemm_wgrad_dma_kernel; the K loop ended with a barrier, so LDS is
+// free): the bias partials bsum[i][e] of rows lrow[i] (channels lseg[i]*EPS + e) are summed over the 32 rows of a K chunk in row
+// order into the bias slab, then the accumulators go to slab[split][co][tap][ci], restaged through LDS so that each thread stores
+// 8 consecutive ci (two 16-byte stores) of a co row.
+template <int LPT, int EPS>
+__device__ __forceinline__ void wgrad_tile_store(const ZsGemmWgrad& p, unsigned char* smem, f32x16 (&acc)[2][2], bool do_bias,
+                                                 const float (&bsum)[LPT][EPS], const int (&lrow)[LPT], const int (&lseg)[LPT],
+                                                 int split, int nsplit, int co0, int ci0, int tap, int cout_r, int cin_r, int wm, int wn,
+                                                 int lane, int tid) {
+  if (do_bias) {
+    // red[32 rows][128 cols] fp32 = 16 KiB
+    float* red = reinterpret_cast<float*>(smem);
+#pragma unroll
+    for (int i = 0; i < LPT; ++i)
+#pragma unroll
+      for (int e = 0; e < EPS; ++e) red[lrow[i] * 128 + lseg[i] * EPS + e] = bsum[i][e];
+    __syncthreads();
+    if (tid < 128) {
+      float t = 0.f;
+#pragma unroll 8
+      for (int r = 0; r < WK; ++r) t += red[r * 128 + tid];
+      float* bslab = (float*)p.workspace + (int64_t)nsplit * cout_r * p.taps * cin_r + (int64_t)split * cout_r;
+      bslab[co0 + tid] = t;
+    }
+  }
+  float* slab = (float*)p.workspace + (int64_t)split * cout_r * p.taps * cin_r;
+  float* sC = reinterpret_cast<float*>(smem);
+  __syncthreads();                                  // bias reduction above (if any) is done with LDS
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int col = wn * 64 + ni * 32 + (lane & 31);
+        sC[row * CPITCH + col] = acc[mi][ni][r];
+      }
+  __syncthreads();
+  const int cg = tid & 15, rr0 = tid >> 4;
+#pragma unroll 1
+  for (int it = 0; it < 8; ++it) {
+    const int row = rr0 + 16 * it;
+    const float4 x0 = *reinterpret_cast<const float4*>(sC + row * CPITCH + cg * 8);
+    const float4 x1 = *reinterpret_cast<const float4*>(sC + row * CPITCH + cg * 8 + 4);
+    float* d = slab + ((int64_t)(co0 + row) * p.taps + tap) * cin_r + ci0 + cg * 8;
+    *reinterpret_cast<float4*>(d) = x0;
+    *reinterpret_cast<float4*>(d + 4) = x1;
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(NT, 2) void gemm_wgrad_kernel(const ZsGemmWgrad p, int ci_tiles, int rows_per_split,
                                                           int cout_r, int cin_r) {
@@ -1503,48 +1555,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_wgrad_kernel(const ZsGemmWgrad p, 
     __syncthreads();
   }
 
-  if (do_bias) {
-    // LDS is free now (the K loop ended with a barrier): red[32 rows][128 cols] fp32 = 16 KiB
-    float* red = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int i = 0; i < LPT; ++i)
-#pragma unroll
-      for (int e = 0; e < EPS; ++e) red[lrow[i] * 128 + lseg[i] * EPS + e] = bsum[i][e];
-    __syncthreads();
-    if (tid < 128) {
-      float t = 0.f;
-#pragma unroll 8
-      for (int r = 0; r < WK; ++r) t += red[r * 128 + tid];
-      float* bslab = (float*)p.workspace + (int64_t)nsplit * cout_r * p.taps * cin_r + (int64_t)split * cout_r;
-      bslab[co0 + tid] = t;
-    }
-  }
-  // slab[split][co][tap][ci], co < cout_r, ci < cin_r (full tiles: no guards needed).  Accumulators are restaged
-  // through LDS so that each thread stores 8 consecutive ci (two 16-byte stores) of a co row.
-  float* slab = (float*)p.workspace + (int64_t)split * cout_r * p.taps * cin_r;
-  float* sC = reinterpret_cast<float*>(smem);
-  __syncthreads();                                  // bias reduction above (if any) is done with LDS
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const int col = wn * 64 + ni * 32 + (lane & 31);
-        sC[row * CPITCH + col] = acc[mi][ni][r];
-      }
-  __syncthreads();
-  const int cg = tid & 15, rr0 = tid >> 4;
-#pragma unroll 1
-  for (int it = 0; it < 8; ++it) {
-    const int row = rr0 + 16 * it;
-    const float4 x0 = *reinterpret_cast<const float4*>(sC + row * CPITCH + cg * 8);
-    const float4 x1 = *reinterpret_cast<const float4*>(sC + row * CPITCH + cg * 8 + 4);
-    float* d = slab + ((int64_t)(co0 + row) * p.taps + tap) * cin_r + ci0 + cg * 8;
-    *reinterpret_cast<float4*>(d) = x0;
-    *reinterpret_cast<float4*>(d + 4) = x1;
-  }
+  wgrad_tile_store<LPT, EPS>(p, smem, acc, do_bias, bsum, lrow, lseg, split, nsplit, co0, ci0, tap, cout_r, cin_r, wm, wn, lane, tid);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1808,21 +1819,155 @@ __global__ __launch_bounds__(PNT, 2) void gemm_wgrad_p8_kernel(const ZsGemmWgrad
   }
 }
 
-// Fixed-order sum of the split-K slabs (deterministic): one thread per 4 consecutive ci of a (co, tap) row, eight slab
-// loads in flight per thread (the slab pitch cin_r is a multiple of 128, so the float4 loads are aligned and in bounds).
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const ZsGemmWgrad p, int splits, int cout_r, int cin_r) {
-  const int cin4 = (p.Cin + 3) >> 2;
-  const int64_t total = (int64_t)p.Cout * p.taps * cin4;
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const int c4 = (int)(idx % cin4);
-  const int64_t rowi = idx / cin4;
-  const int j = (int)(rowi % p.taps);
-  const int co = (int)(rowi / p.taps);
-  const int half = p.Cout >> 1;
-  const int cop = p.co_split2 ? ((co & 1) * half + (co >> 1)) : co;
-  const int64_t sstride = (int64_t)cout_r * p.taps * cin_r;
-  const float* ws = (const float*)p.workspace + ((int64_t)cop * p.taps + j) * cin_r + c4 * 4;
+// ------------------------------------------------------------------------------------------------
+// bf16 weight gradient, 128 co x 128 ci tile of one tap (the tile, grid map, bias column sum and slab of gemm_wgrad_kernel<bf16_t>)
+// staged by LDS-DMA: K stage = 64 rows m, double-buffered, one barrier per stage; the DMA of stage kt+1 runs under the 16 MFMAs per
+// wave of stage kt.  A stage is [dY | gathered X] x [channel block cb = 0, 1][64 rows k] x 128 B (64 channels), 32 KiB; a 1-KiB
+// DMA piece is 8 rows k of one channel block, the two 64-byte halves of row k swapped when (k>>1)&1 (source side), and fragments
+// come from ds_read_b64_tr_b16 exactly as in gemm_wgrad_p8_kernel.  Each lane's MFMA sequence is that of gemm_wgrad_kernel
+// (16-row k-steps in ascending order, same operand lanes), so at equal splits the two kernels give bit-identical slabs; a split
+// whose row count is an odd number of 32-row chunks ends with zero rows (exact zero products).  The bias partials keep the
+// 32-row-chunk structure of gemm_wgrad_kernel: partial r sums rows r and r + 32 of each stage, in row order.
+// ------------------------------------------------------------------------------------------------
+constexpr int WDSTAGE = 2 * 2 * 64 * 128;                      // 32,768 B
+constexpr int WD_LDS = (2 * WDSTAGE > EPI_LDS_BYTES) ? 2 * WDSTAGE : EPI_LDS_BYTES;
+
+__global__ __launch_bounds__(NT, 2) void gemm_wgrad_dma_kernel(const ZsGemmWgrad p, int ci_tiles, int rows_per_split, int cout_r,
+                                                              int cin_r) {
+  const Geom2 g2 = make_geom2(p.w_in, p.w_out, p.taps_h, p.T_in);
+  typedef bf16_t T;
+  typedef __attribute__((address_space(1))) const void* gptr_t;
+  typedef __attribute__((address_space(3))) void* lptr_t;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  // 1-D grid, XCD-aware (see gemm_wgrad_kernel)
+  const int per_co = p.taps * ci_tiles;
+  const int tiles = (cout_r / 128) * per_co;
+  const int vid = xcd_remap(blockIdx.x, gridDim.x);
+  const int split = vid / tiles, tile = vid - split * tiles;
+  const int cot = tile / per_co;
+  const int rem = tile - cot * per_co;
+  const int tap = rem / ci_tiles, cit = rem - tap * ci_tiles;
+  const int co0 = cot * 128, ci0 = cit * 128;
+  const int M = p.B * p.T_out;
+  const int nsplit = gridDim.x / tiles;
+  const int mbeg = split * rows_per_split;
+  const int mend = min(M, mbeg + rows_per_split);
+  const int nk = (mend - mbeg + 63) / 64;
+  const T* __restrict__ dY = (const T*)p.dY;
+  const T* __restrict__ X = (const T*)p.X;
+  const T* zline = reinterpret_cast<const T*>(zs_zero_line);
+
+  // loader: this wave's pieces are rows k = 16*wave + 8h + lane/8 (h = 0, 1) of both channel blocks, lane&7 the physical slot
+  const int lrow8 = lane >> 3, slot = lane & 7;
+  const int k0 = wave * 16 + lrow8, k1 = k0 + 8;
+  const int sg0 = slot ^ (((k0 >> 1) & 1) << 2), sg1 = slot ^ (((k1 >> 1) & 1) << 2);
+  auto dma = [&](int kt, int st) {
+    unsigned char* const dy = smem + st * WDSTAGE + wave * 2048;
+    unsigned char* const dx = dy + 16384;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int m = mbeg + kt * 64 + (h ? k1 : k0);
+      const int sg = h ? sg1 : sg0;
+      const bool in = m < mend;
+      bool ok = false;
+      const T* xr = zline;
+      if (in) {
+        const int b = m / p.T_out, t = m - b * p.T_out;
+        const int srow = conv_src_row_g(0, p.pad_mode, p.stride, p.pad_left, p.T_in, t, tap, ok, g2);
+        xr = X + (int64_t)b * p.x_batch_stride + (int64_t)srow * p.ldx;
+      }
+      const T* yr = dY + (int64_t)m * p.ldy;
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+        const int cy = co0 + cb * 64 + sg * 8, cx = ci0 + cb * 64 + sg * 8;
+        __builtin_amdgcn_global_load_lds((gptr_t)((in && cy < p.y_cols) ? yr + cy : zline), (lptr_t)(dy + cb * 8192 + h * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t)((ok && cx < p.x_cols) ? xr + cx : zline), (lptr_t)(dx + cb * 8192 + h * 1024), 16, 0, 0);
+      }
+    }
+  };
+
+  // fragment addresses (gemm_wgrad_p8_kernel): 16-lane group gi: channels 16*(gi&1).., rows 8*(gi>>1)..; lane 4q+pp: row q, channels 4pp..
+  const int gi = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
+  const int sw = ((q >> 1) & 1) << 2;
+  const int segl = 2 * (gi & 1) + (pp >> 1);
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
+  const unsigned rowoff = (unsigned)((8 * (gi >> 1) + q) * 128 + (pp & 1) * 8);
+  const unsigned a_l0 = lds0 + (unsigned)(wm * 8192) + rowoff + (unsigned)(((0 + segl) ^ sw) * 16);
+  const unsigned a_l1 = lds0 + (unsigned)(wm * 8192) + rowoff + (unsigned)(((4 + segl) ^ sw) * 16);
+  const unsigned b_l0 = lds0 + 16384u + (unsigned)(wn * 8192) + rowoff + (unsigned)(((0 + segl) ^ sw) * 16);
+  const unsigned b_l1 = lds0 + 16384u + (unsigned)(wn * 8192) + rowoff + (unsigned)(((4 + segl) ^ sw) * 16);
+
+  // bias (wave-uniform): thread tid sums channels 8*(tid&15).. of rows lrow[i] = (tid>>4) + 16i of each 32-row chunk
+  const bool do_bias = (p.db != nullptr) && tap == 0 && cit == 0;
+  int lrow[2], lseg[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) { lrow[i] = (tid >> 4) + 16 * i; lseg[i] = tid & 15; }
+  const int bcb = (tid & 15) >> 3, bg8 = tid & 7;
+  const int boff = bcb * 8192 + (tid >> 4) * 128 + ((bg8 ^ ((((tid >> 4) >> 1) & 1) << 2)) * 16);   // row (tid>>4); +16, +32, +48 keep (k>>1)&1
+  float bsum[2][8];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) bsum[i][e] = 0.f;
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  if (nk > 0) dma(0, 0);
+  uint2 y0a0, y0b0, y0a1, y0b1, y0a2, y0b2, y0a3, y0b3, y1a0, y1b0, y1a1, y1b1, y1a2, y1b2, y1a3, y1b3;   // dY: [mi] [ks] rows +0..3 / +4..7
+  uint2 x0a0, x0b0, x0a1, x0b1, x0a2, x0b2, x0a3, x0b3, x1a0, x1b0, x1a1, x1b1, x1a2, x1b2, x1a3, x1b3;   // X: [ni]
+  for (int kt = 0; kt < nk; ++kt) {
+    const int st = kt & 1;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();                                  // stage kt has landed (all waves); stage kt-1's reads are done
+    if (kt + 1 < nk) dma(kt + 1, st ^ 1);
+    const unsigned so = (unsigned)(st * WDSTAGE);
+    const unsigned sa0 = a_l0 + so, sa1 = a_l1 + so, sb0 = b_l0 + so, sb1 = b_l1 + so;
+    ZS_WP_READ_B(y0, sa0)
+    ZS_WP_READ_B(y1, sa1)
+    ZS_WP_READ_B(x0, sb0)
+    ZS_WP_READ_B(x1, sb1)
+    if (do_bias) {
+      const unsigned char* by = smem + st * WDSTAGE + boff;
+      const uint4 v0 = *reinterpret_cast<const uint4*>(by), v1 = *reinterpret_cast<const uint4*>(by + 16 * 128);
+      const uint4 v2 = *reinterpret_cast<const uint4*>(by + 32 * 128), v3 = *reinterpret_cast<const uint4*>(by + 48 * 128);
+      const uint32_t w[4][4] = {{v0.x, v0.y, v0.z, v0.w}, {v1.x, v1.y, v1.z, v1.w}, {v2.x, v2.y, v2.z, v2.w}, {v3.x, v3.y, v3.z, v3.w}};
+#pragma unroll
+      for (int c = 0; c < 4; ++c)                     // chunk 2kt (rows r, r+16), then chunk 2kt+1 (rows r+32, r+48)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          bsum[c & 1][2 * e] += __uint_as_float(w[c][e] << 16);
+          bsum[c & 1][2 * e + 1] += __uint_as_float(w[c][e] & 0xffff0000u);
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);                // MFMAs (register-only) must not be hoisted above the wait
+#define ZS_WD_KS(ks)                                                                                                    \
+    ZS_WP_MMA(y0a##ks, y0b##ks, x0a##ks, x0b##ks, acc[0][0]); ZS_WP_MMA(y0a##ks, y0b##ks, x1a##ks, x1b##ks, acc[0][1]); \
+    ZS_WP_MMA(y1a##ks, y1b##ks, x0a##ks, x0b##ks, acc[1][0]); ZS_WP_MMA(y1a##ks, y1b##ks, x1a##ks, x1b##ks, acc[1][1]);
+    ZS_WD_KS(0) ZS_WD_KS(1) ZS_WD_KS(2) ZS_WD_KS(3)
+#undef ZS_WD_KS
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  wgrad_tile_store<2, 8>(p, smem, acc, do_bias, bsum, lrow, lseg, split, nsplit, co0, ci0, tap, cout_r, cin_r, wm, wn, lane, tid);
+}
+
+// Fixed-order sum of the split-K slabs (deterministic: every output is summed over splits k = 0, 1, ... in that order).
+//  * wgrad_reduce_kernel: one thread per 4 consecutive ci of a (co, tap) row, eight slab loads in flight per thread (the slab pitch
+//    cin_r is a multiple of 128, so the float4 loads are aligned and in bounds); dW element (co, ci, tap) at co*so + ci*si + tap*sj.
+//  * wgrad_reduce_taps_kernel (Conv1d weights: si = taps, sj = 1): a workgroup owns (co, a block of 4*c4n ci) for every tap.  It
+//    sums each tap's slab row with the same float4 loads, transposes through LDS and writes the contiguous run
+//    dW[co][ci0 .. ci0 + 4*c4n)[0 .. taps) -- the generic kernel's stores land taps floats apart.
+//  * the bias slabs are summed by the grid's last workgroups, one lane per co (wgrad_reduce_bias).
+__device__ __forceinline__ float4 wgrad_sum_splits(const float* ws, int splits, int64_t sstride) {
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   int k = 0;
   for (; k + 8 <= splits; k += 8) {
@@ -1836,6 +1981,43 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const ZsGemmWgrad p, 
     const float4 v = *reinterpret_cast<const float4*>(ws + (int64_t)k * sstride);
     acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
   }
+  return acc;
+}
+
+__device__ __forceinline__ int wgrad_co_perm(const ZsGemmWgrad& p, int co) {
+  return p.co_split2 ? ((co & 1) * (p.Cout >> 1) + (co >> 1)) : co;
+}
+
+__device__ __forceinline__ void wgrad_reduce_bias(const ZsGemmWgrad& p, int splits, int cout_r, int64_t sstride, int bblk) {
+  const int co = bblk * 256 + (int)threadIdx.x;
+  if (co >= p.Cout) return;
+  const float* bs = (const float*)p.workspace + (int64_t)splits * sstride + wgrad_co_perm(p, co);
+  float t = 0.f;
+  int q = 0;
+  for (; q + 8 <= splits; q += 8) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = bs[(int64_t)(q + u) * cout_r];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) t += v[u];
+  }
+  for (; q < splits; ++q) t += bs[(int64_t)q * cout_r];
+  p.db[co] = p.accumulate ? (p.db[co] + t) : t;
+}
+
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const ZsGemmWgrad p, int splits, int cout_r, int cin_r, int nmain) {
+  const int64_t sstride = (int64_t)cout_r * p.taps * cin_r;
+  if ((int)blockIdx.x >= nmain) { wgrad_reduce_bias(p, splits, cout_r, sstride, (int)blockIdx.x - nmain); return; }
+  const int cin4 = (p.Cin + 3) >> 2;
+  const int64_t total = (int64_t)p.Cout * p.taps * cin4;
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int c4 = (int)(idx % cin4);
+  const int64_t rowi = idx / cin4;
+  const int j = (int)(rowi % p.taps);
+  const int co = (int)(rowi / p.taps);
+  const float* ws = (const float*)p.workspace + ((int64_t)wgrad_co_perm(p, co) * p.taps + j) * cin_r + c4 * 4;
+  const float4 acc = wgrad_sum_splits(ws, splits, sstride);
   const float r[4] = {acc.x, acc.y, acc.z, acc.w};
   float* d = p.dW + (int64_t)co * p.so + (int64_t)j * p.sj;
 #pragma unroll
@@ -1846,12 +2028,31 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const ZsGemmWgrad p, 
       *q = p.accumulate ? (*q + r[e]) : r[e];
     }
   }
-  if (p.db != nullptr && c4 == 0 && j == 0) {
-    const float* bs = (const float*)p.workspace + (int64_t)splits * sstride + cop;
-    float t = 0.f;
-    for (int q2 = 0; q2 < splits; ++q2) t += bs[(int64_t)q2 * cout_r];
-    p.db[co] = p.accumulate ? (p.db[co] + t) : t;
+}
+
+constexpr int WRT_LDS_FLOATS = 1024;   // wgrad_reduce_taps_kernel: 4 * c4n * taps <= 4 * 256 (host: taps <= 256)
+
+__global__ __launch_bounds__(256) void wgrad_reduce_taps_kernel(const ZsGemmWgrad p, int splits, int cout_r, int cin_r, int c4n,
+                                                                int nblk, int nmain) {
+  __shared__ float sT[WRT_LDS_FLOATS];
+  const int64_t sstride = (int64_t)cout_r * p.taps * cin_r;
+  if ((int)blockIdx.x >= nmain) { wgrad_reduce_bias(p, splits, cout_r, sstride, (int)blockIdx.x - nmain); return; }
+  const int co = (int)blockIdx.x / nblk, blk = (int)blockIdx.x - co * nblk;
+  const int ci0 = blk * 4 * c4n;
+  const int taps = p.taps;
+  const float* wrow = (const float*)p.workspace + (int64_t)wgrad_co_perm(p, co) * taps * cin_r + ci0;
+  // item (tap j, float4 column c): consecutive lanes read consecutive float4 of one slab row
+  for (int it = (int)threadIdx.x; it < c4n * taps; it += 256) {
+    const int j = it / c4n, c = it - j * c4n;
+    if (ci0 + 4 * c >= p.Cin) continue;
+    const float4 acc = wgrad_sum_splits(wrow + (int64_t)j * cin_r + 4 * c, splits, sstride);
+    sT[(4 * c + 0) * taps + j] = acc.x; sT[(4 * c + 1) * taps + j] = acc.y;
+    sT[(4 * c + 2) * taps + j] = acc.z; sT[(4 * c + 3) * taps + j] = acc.w;
   }
+  __syncthreads();
+  const int n = min(4 * c4n, p.Cin - ci0) * taps;
+  float* d = p.dW + (int64_t)co * p.so + (int64_t)ci0 * taps;
+  for (int i = (int)threadIdx.x; i < n; i += 256) d[i] = p.accumulate ? (d[i] + sT[i]) : sT[i];
 }
 
 int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
@@ -1877,22 +2078,33 @@ Knob g_wgrad_wgs("ZS_WGRAD_WGS", 256);      // workgroups one weight-gradient la
 // re-read less slab: 448 measured 10.93 against 10.98 ms/step (384-512 equal, 256 and 1024 worse)
 Knob g_wgrad_wgs128("ZS_WGRAD_WGS128", 448);
 Knob g_wgrad_slab_cost("ZS_WGRAD_SLAB_COST", 13);   // cost of one split's slab write + re-read in K-tile times
+// Weight gradients launched alone on the chip (the single-stream step: zs_set_option("wgrad_alone", 1), set by the context when it
+// does not overlap weight gradients) use their own split-K constants; the two above were fitted for four launches side by side.
+// Re-fitted on the single-stream step with gemm_wgrad_dma_kernel: wgs128 448 11.92 ms/step, 768 12.01, 1024 12.06,
+// 1536 12.13; slab cost 6 / 13 / 20 within noise (11.99-12.01 at wgs128 768).  Alone, the same constants are the best measured.
+Knob g_wgrad_alone("ZS_WGRAD_ALONE", 0);
+Knob g_wgrad_wgs128_alone("ZS_WGRAD_WGS128_ALONE", 448);
+Knob g_wgrad_slab_cost_alone("ZS_WGRAD_SLAB_COST_ALONE", 13);
+Knob g_wgrad_dma("ZS_WGRAD_DMA", 1);                 // bf16 128x128 tiles: 1 = gemm_wgrad_dma_kernel, 0 = gemm_wgrad_kernel (reference)
+Knob g_wgrad_reduce_taps("ZS_WGRAD_REDUCE_TAPS", 1); // Conv1d weights: 1 = wgrad_reduce_taps_kernel, 0 = wgrad_reduce_kernel (reference)
 Knob g_wgrad_waste("ZS_WGRAD_P8_WASTE", 135);       // 256x256 weight-gradient tiles only while padded/real output area <= this / 100
 
-struct WgradPlan { int p8, splits, tile, co_tiles, ci_tiles, cout_r, cin_r, rows_per_split; };
+struct WgradPlan { int p8, dma, splits, tile, co_tiles, ci_tiles, cout_r, cin_r, rows_per_split; };
 
-// Split-K plan.  128x128 tiles (fp32, small outputs): ~448 workgroups (wgrad_wgs128).  256x256 ping-pong tiles (bf16): one workgroup per
+// Split-K plan.  128x128 tiles (fp32, small outputs): ~448 workgroups (wgrad_wgs128; wgrad_wgs128_alone for a launch alone).  256x256 ping-pong tiles (bf16): one workgroup per
 // CU and round, each split pays a 256-KiB slab write + re-read (~13 K-tile times at 1/256 of HBM), so minimise
 // rounds x (K tiles per split + 13).
 WgradPlan wgrad_plan(const ZsGemmWgrad* p) {
   WgradPlan w;
   const int wgrad_p8 = g_wgrad_p8.get();
+  const bool alone = g_wgrad_alone.get() != 0;
   const int64_t M = (int64_t)p->B * p->T_out;
   const int64_t t256 = (int64_t)((p->Cout + 255) / 256) * p->taps * ((p->Cin + 255) / 256);
   // padding waste of 256-wide tiles must stay small, and there must be enough K per workgroup to amortise the slab
   const double waste = (double)(((p->Cout + 255) / 256) * 256) * (((p->Cin + 255) / 256) * 256) / ((double)p->Cout * p->Cin);
   w.p8 = wgrad_p8 && p->dtype == ZS_BF16 && waste <= 0.01 * (double)g_wgrad_waste.get() && M >= 2048 && (wgrad_p8 > 1 || t256 * M >= (int64_t)16 * 8192);
   if (wgrad_p8 > 1 && p->dtype == ZS_BF16) w.p8 = 1;                   // forced (tests)
+  w.dma = !w.p8 && p->dtype == ZS_BF16 && g_wgrad_dma.get() != 0;
   w.tile = w.p8 ? 256 : 128;
   w.co_tiles = (p->Cout + w.tile - 1) / w.tile; w.ci_tiles = (p->Cin + w.tile - 1) / w.tile;
   w.cout_r = w.co_tiles * w.tile; w.cin_r = w.ci_tiles * w.tile;
@@ -1902,7 +2114,7 @@ WgradPlan wgrad_plan(const ZsGemmWgrad* p) {
   } else if (w.p8) {
     const int64_t kt = (M + 63) / 64;
     const int64_t wgs = g_wgrad_wgs.get() > 0 ? g_wgrad_wgs.get() : 256;
-    const double slab_cost = (double)g_wgrad_slab_cost.get();
+    const double slab_cost = (double)(alone ? g_wgrad_slab_cost_alone.get() : g_wgrad_slab_cost.get());
     double best = 1e30; int bs = 1;
     for (int sp = 1; sp <= 64 && (int64_t)sp * 4 <= kt; ++sp) {
       const double rounds = (double)((tiles * sp + wgs - 1) / wgs);
@@ -1911,7 +2123,8 @@ WgradPlan wgrad_plan(const ZsGemmWgrad* p) {
     }
     w.splits = bs;
   } else {
-    const int64_t target = g_wgrad_wgs128.get() > 0 ? g_wgrad_wgs128.get() : 448;
+    const int knob = alone ? g_wgrad_wgs128_alone.get() : g_wgrad_wgs128.get();
+    const int64_t target = knob > 0 ? knob : 448;
     int64_t sp = (target + tiles - 1) / tiles;
     int64_t maxs = (M + 255) / 256;
     if (sp > maxs) sp = maxs;
@@ -2046,6 +2259,11 @@ extern "C" int zs_set_option(const char* key, int value) {
   else if (key && !strcmp(key, "wgrad_wgs128")) slot = &g_wgrad_wgs128;
   else if (key && !strcmp(key, "wgrad_slab_cost")) slot = &g_wgrad_slab_cost;
   else if (key && !strcmp(key, "wgrad_p8_waste")) slot = &g_wgrad_waste;
+  else if (key && !strcmp(key, "wgrad_alone")) slot = &g_wgrad_alone;
+  else if (key && !strcmp(key, "wgrad_wgs128_alone")) slot = &g_wgrad_wgs128_alone;
+  else if (key && !strcmp(key, "wgrad_slab_cost_alone")) slot = &g_wgrad_slab_cost_alone;
+  else if (key && !strcmp(key, "wgrad_dma")) slot = &g_wgrad_dma;
+  else if (key && !strcmp(key, "wgrad_reduce_taps")) slot = &g_wgrad_reduce_taps;
   if (key && !strcmp(key, "gru_persist")) return zs_gru_persist_option(value);
   if (key && !strcmp(key, "gru_wide")) return zs_gru_wide_option(value);
   if (key && !strcmp(key, "gru_spin_limit")) return zs_gru_spin_limit_option(value);
@@ -2096,13 +2314,26 @@ extern "C" int zs_gemm_wgrad(const ZsGemmWgrad* p, void* stream) {
   } else if (p->dtype == ZS_F32) {
     const size_t lds = (4 * WK * WFrag<float>::PITCHW > EPI_LDS_BYTES) ? 4 * WK * WFrag<float>::PITCHW : EPI_LDS_BYTES;
     hipLaunchKernelGGL(gemm_wgrad_kernel<float>, grid, dim3(NT), lds, s, *p, ci_tiles, rows_per_split, cout_r, cin_r);
+  } else if (w.dma) {
+    hipLaunchKernelGGL(gemm_wgrad_dma_kernel, grid, dim3(NT), WD_LDS, s, *p, ci_tiles, rows_per_split, cout_r, cin_r);
   } else {
     const size_t lds = (4 * WK * WFrag<bf16_t>::PITCHW > EPI_LDS_BYTES) ? 4 * WK * WFrag<bf16_t>::PITCHW : EPI_LDS_BYTES;
     hipLaunchKernelGGL(gemm_wgrad_kernel<bf16_t>, grid, dim3(NT), lds, s, *p, ci_tiles, rows_per_split, cout_r, cin_r);
   }
   int rc = zs_check_launch("zs_gemm_wgrad");
   if (rc) return rc;
-  const int64_t relems = (int64_t)p->Cout * p->taps * ((p->Cin + 3) / 4);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((relems + 255) / 256)), dim3(256), 0, s, *p, splits, cout_r, cin_r);
+  const int nbias = p->db ? (p->Cout + 255) / 256 : 0;          // trailing workgroups: the bias sums, one lane per co
+  if (g_wgrad_reduce_taps.get() && p->taps > 1 && p->taps <= 256 && p->si == p->taps && p->sj == 1) {
+    const int c4n = 256 / p->taps;                               // ci per workgroup: 4 * c4n, so that c4n * taps <= 256 items
+    const int nblk = (p->Cin + 4 * c4n - 1) / (4 * c4n);
+    ZS_REQUIRE((int64_t)p->Cout * nblk + nbias < (1ll << 31), "zs_gemm_wgrad: reduce grid too large");
+    const int nmain = p->Cout * nblk;
+    hipLaunchKernelGGL(wgrad_reduce_taps_kernel, dim3((unsigned)(nmain + nbias)), dim3(256), 0, s, *p, splits, cout_r, cin_r, c4n, nblk, nmain);
+  } else {
+    const int64_t relems = (int64_t)p->Cout * p->taps * ((p->Cin + 3) / 4);
+    const int64_t nmain = (relems + 255) / 256;
+    ZS_REQUIRE(nmain + nbias < (1ll << 31), "zs_gemm_wgrad: reduce grid too large");
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(nmain + nbias)), dim3(256), 0, s, *p, splits, cout_r, cin_r, (int)nmain);
+  }
   return zs_check_launch("zs_gemm_wgrad.reduce");
 }

@@ -174,6 +174,7 @@ class Ctx(object):
         # weight gradients are only needed by the optimizer: run them on a second stream under the latency-bound
         # phases of the backward chain (GRU steps, small norms)
         self.overlap_wgrad = os.environ.get('ZS_OVERLAP_WGRAD', '1' if MULTI_STREAM else '0') == '1'
+        L.set_option('wgrad_alone', 0 if self.overlap_wgrad else 1)     # the split-K plan of a weight gradient alone on the chip
 
     @property
     def stream(self):
