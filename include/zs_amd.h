@@ -38,31 +38,37 @@ enum { ZS_RES_NONE = 0, ZS_RES_IDENTITY = 1, ZS_RES_AVGPOOL2 = 2, ZS_RES_UPSAMPL
 
 int zs_abi_version(void);
 const char* zs_last_error(void);
-/* Kernel-selection knobs (defaults also read from the environment at first use):
- *   "gemm_dma" (ZS_GEMM_DMA, 1): LDS-DMA operand staging; 0 = register-staged kernel
+/* Kernel-selection knobs, one line each: "key" (environment variable that gives the default at first use, or -; default): effect.
+ *   "gemm_dma" (ZS_GEMM_DMA, 1): zs_gemm_conv stages operands by LDS-DMA; 0 = the register-staged kernel
  *   "gemm_ring" (ZS_GEMM_RING, 1): allow the 256x128 3-stage-ring kernel
- *   "gemm_ring_min_tiles" (ZS_GEMM_RING_MIN_TILES, 256): use it when the problem has at least that many 256x128 tiles
+ *   "gemm_ring_min_tiles" (ZS_GEMM_RING_MIN_TILES, 256): ... when the problem has at least that many 256x128 tiles
  *   "gemm_pp" (ZS_GEMM_PP, 1): ping-pong schedule of the ring kernel (two wave groups one barrier apart)
- *   "gemm_p8" (ZS_GEMM_P8, 1) / "gemm_p8_min_tiles" (ZS_GEMM_P8_MIN_TILES, 200): 256x256 quadrant ping-pong kernel when the
- *       packed weight has a multiple of 256 rows and the problem has at least that many 256x256 tiles
- *   "wgrad_p8" (ZS_WGRAD_P8, 1): 256x256 ping-pong weight-gradient kernel (bf16) where its heuristics accept the shape;
- *       0 = always the 128x128 kernel, 2 = whenever bf16 (tests)
- *   "wgrad_dma" (ZS_WGRAD_DMA, 1): bf16 128x128 weight-gradient tiles by the LDS-DMA kernel; 0 = the register-staged kernel
- *       (bit-identical at equal splits; tests)
- *   "wgrad_reduce_taps" (ZS_WGRAD_REDUCE_TAPS, 1): Conv1d weight gradients (si = taps, sj = 1) reduced with stores in dW order;
- *       0 = the per-(co, tap)-row reduce (bit-identical; tests)
- *   "wgrad_alone" (ZS_WGRAD_ALONE, 0): weight gradients run alone on the chip (set by the context when it does not overlap them):
- *       the split-K plan uses "wgrad_wgs128_alone" / "wgrad_slab_cost_alone" instead of "wgrad_wgs128" / "wgrad_slab_cost"
- *   "gru_persist" (ZS_GRU_PERSIST, 1): one persistent launch per GRU pass (forward and BPTT: the time loop runs on the
- *       device, W_hh stays in registers, h / dgh travel between workgroups as data-tagged 8-byte granules) when the grid fits
- *       one workgroup per CU and H allows it; 0 = one launch per time step
- *   "gru_wide" (ZS_GRU_WIDE, 1): bf16, H in {128, 256, 512}: the persistent kernels in their 16-row x 64-unit tiling (a wave
- *       owns 16 units over the full K, W_hh slice in registers, one barrier per step, h / dgh of the group in an LDS image);
- *       0 = the 32 x 32 (forward) / 16 x 64 K-split (BPTT) tilings, which also serve fp32 and other H
- *   "gru_spin_limit" (ZS_GRU_SPIN_LIMIT, 2^21): granule sweeps a persistent GRU wave makes before it gives up on its group
- *       (sets the status word, see ZsGruFwd.status); 0 forces the timeout path (tests)
- * The knobs are process-wide atomics: they may be set from any thread; a launch reads each knob once.
- * Returns the previous value, or ZS_EINVAL for an unknown key. */
+ *   "gemm_p8" (ZS_GEMM_P8, 1): 256x256 quadrant ping-pong kernel when the packed weight has a multiple of 256 rows
+ *   "gemm_p8_min_tiles" (ZS_GEMM_P8_MIN_TILES, 200): ... and the problem has at least that many 256x256 tiles
+ *   "gemm_dma64" (ZS_GEMM_DMA64, 1): 64-row tiles of the LDS-DMA kernel for under-filled grids
+ *   "gemm_dma64_max_tiles" (ZS_GEMM_DMA64_MAX_TILES, 256): ... when twice the 128-row tile count is at most this
+ *   "wgrad_p8" (ZS_WGRAD_P8, 1): bf16 weight gradients by the 256x256 ping-pong kernel where the plan accepts the shape; 0 = never, 2 = always
+ *   "wgrad_p8_waste" (ZS_WGRAD_P8_WASTE, 135): ... only while the padded output area is at most this / 100 of the real one
+ *   "wgrad_wgs" (ZS_WGRAD_WGS, 256): workgroups the split-K plan of the 256x256 weight-gradient kernel aims for
+ *   "wgrad_wgs128" (ZS_WGRAD_WGS128, 448): workgroups the split-K plan of the 128x128 weight-gradient kernels aims for
+ *   "wgrad_slab_cost" (ZS_WGRAD_SLAB_COST, 13): cost of one split's slab write + re-read in K-tile times (256x256 split-K plan)
+ *   "wgrad_alone" (ZS_WGRAD_ALONE, 0): weight gradients run alone on the chip (set by the context): the plan uses the two "_alone" knobs
+ *   "wgrad_wgs128_alone" (ZS_WGRAD_WGS128_ALONE, 448): "wgrad_wgs128" while "wgrad_alone" is set
+ *   "wgrad_slab_cost_alone" (ZS_WGRAD_SLAB_COST_ALONE, 13): "wgrad_slab_cost" while "wgrad_alone" is set
+ *   "wgrad_dma" (ZS_WGRAD_DMA, 1): bf16 128x128 weight-gradient tiles by LDS-DMA; 0 = register-staged (bit-identical at equal splits)
+ *   "wgrad_reduce_taps" (ZS_WGRAD_REDUCE_TAPS, 1): Conv1d weight gradients reduced with stores in dW order; 0 = per-(co, tap) rows (bit-identical)
+ *   "gru_persist" (ZS_GRU_PERSIST, 1): one persistent launch per GRU pass where H allows and the grid fits one workgroup per CU
+ *   "gru_wide" (ZS_GRU_WIDE, 1): bf16, H in {128, 256, 512}: the persistent kernels' 16-row x 64-unit tiling
+ *   "gru_spin_limit" (ZS_GRU_SPIN_LIMIT, 2097152): granule sweeps a persistent GRU wave waits for its group (see ZsGruFwd.status); 0 = timeout
+ *   "norm_wide" (-, 1): InstanceNorm kernels in 8 row groups x 256 channels for short bf16 samples
+ *   "norm_lim0" (-, 64): longest T that zs_instnorm_fwd runs in the 8 x 256 decomposition
+ *   "norm_lim1" (-, 32): longest T that zs_instnorm_bwd runs in the 8 x 256 decomposition
+ *   "norm_lim2" (-, 64): longest T that zs_grad_combine runs in the 8 x 256 decomposition
+ *   "gl_prefetch" (-, 1): Griffin-Lim waves request the next inverse frame's spectrum behind the current transform
+ *   "gl_chains" (-, 3): independent launch chains of zs_griffin_lim (see there)
+ * Stored values are normalised: gru_persist, gru_wide, norm_wide and gl_prefetch store v ? 1 : 0, gl_chains is clamped to [1, 4],
+ * norm_lim0..2 store v, every other knob stores max(v, 0).  The knobs are process-wide atomics: they may be set from any thread; a
+ * launch reads each knob once.  Returns the previous value, or ZS_EINVAL for an unknown key. */
 int zs_set_option(const char* key, int value);
 
 /* ---------------------------------------------------------------------------------------------

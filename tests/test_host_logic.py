@@ -4,6 +4,7 @@ reducer over gloo) behaves like the reference's."""
 import ctypes
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -60,6 +61,50 @@ def test_invalid_calls_return_errors_not_crashes(lib):
     with pytest.raises(lib.ZsError):
         lib.call('zs_instnorm_fwd', 'ZsInstNormFwd', 0, dtype=7)
     assert 'zs_' in lib.last_error()
+
+
+def _knob_probes(key):
+    """(value set, value stored) pairs for the normalisation documented at zs_set_option in zs_amd.h."""
+    if key in ('gru_persist', 'gru_wide', 'norm_wide', 'gl_prefetch'):
+        return [(2, 1), (-1, 1), (0, 0)]
+    if key == 'gl_chains':
+        return [(0, 1), (9, 4), (2, 2)]
+    if key.startswith('norm_lim'):
+        return [(5, 5), (0, 0)]          # stored as given (a negative value would come back as an error code)
+    return [(-5, 0), (7, 7)]
+
+
+def test_set_option_knobs_are_documented_and_normalised(lib):
+    """Every knob defined in csrc/ is documented at zs_set_option with its environment variable and default; each stores the
+    documented normalisation of what is set or read from the environment; an unknown key is an error.  No GPU is touched."""
+    hdr = open(lib.HEADER).read()
+    doc = hdr[hdr.index('/* Kernel-selection knobs'):hdr.index('int zs_set_option(')]
+    documented = {k: (env, int(d)) for k, env, d in re.findall(r'^ \*   "(\w+)" \((ZS_\w+|-), (\d+)\):', doc, flags=re.M)}
+    assert len(documented) == doc.count('\n *   "')
+    csrc = os.path.join(ROOT, 'zerospeech-tts-without-t_amd', 'csrc')
+    defined = []
+    for f in sorted(os.listdir(csrc)):
+        defined += re.findall(r'\b\w+\("(\w+)", (?:"(ZS_\w+)"|nullptr), ', open(os.path.join(csrc, f)).read())
+    assert len(defined) == len({k for k, _ in defined}), defined
+    assert {k: env or '-' for k, env in defined} == {k: env for k, (env, _) in documented.items()}
+    for key in documented:
+        orig = lib.set_option(key, 0)
+        try:
+            for value, stored in _knob_probes(key):
+                lib.set_option(key, value)
+                assert lib.set_option(key, value) == stored, (key, value)
+        finally:
+            lib.set_option(key, orig)
+    with pytest.raises(lib.ZsError, match='unknown key no_such_knob'):
+        lib.set_option('no_such_knob', 1)
+    # defaults, and environment values normalised like set values, in a process of their own
+    env = {k: v for k, v in os.environ.items() if k != 'ZS_OPTIONS' and k not in {e for e, _ in documented.values()}}
+    env.update(ZS_GRU_PERSIST='2', ZS_GEMM_RING_MIN_TILES='-7')
+    script = 'import json, sys, zs_amd; from zs_amd import _lib as L; print(json.dumps({k: L.set_option(k, 1) for k in sys.argv[1:]}))'
+    out = subprocess.check_output([sys.executable, '-c', script] + list(documented), env=env, cwd=ROOT, timeout=300)
+    want = {k: d for k, (_, d) in documented.items()}
+    want.update(gru_persist=1, gemm_ring_min_tiles=0)
+    assert json.loads(out.decode().strip().splitlines()[-1]) == want
 
 
 def test_no_cpu_fallback():

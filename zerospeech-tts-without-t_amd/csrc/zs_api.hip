@@ -1,4 +1,4 @@
-// zs_api.hip -- error state and version of libzs_amd.so (see include/zs_amd.h).
+// zs_api.hip -- error state, version and kernel-selection knobs of libzs_amd.so (see include/zs_amd.h).
 #include <stdarg.h>
 
 #include "zs_common.h"
@@ -10,6 +10,15 @@ void zs_set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+}
+
+Knob* g_knobs = nullptr;
+
+extern "C" int zs_set_option(const char* key, int value) {
+  for (Knob* k = g_knobs; key && k; k = k->next)
+    if (!strcmp(k->key, key)) return k->set(value);
+  zs_set_error("zs_set_option: unknown key %s", key ? key : "(null)");
+  return ZS_EINVAL;
 }
 
 int zs_check_launch(const char* what) {

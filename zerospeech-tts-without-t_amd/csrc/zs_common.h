@@ -3,7 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
+
+#include <atomic>
+#include <mutex>
 
 #include "../../include/zs_amd.h"
 
@@ -14,13 +18,34 @@ typedef unsigned short bf16_t;   // raw bf16 bits in memory
 
 void zs_set_error(const char* fmt, ...);
 int zs_check_launch(const char* what);
-int zs_gl_prefetch_option(int value);    // zs_griffin.hip: "gl_prefetch" knob
-int zs_norm_wide_option(int value);      // zs_norm.hip: "norm_wide" knob (8 row groups x 256 channels for T <= 64)
-int zs_norm_lim_option(int i, int value);
-int zs_gl_chains_option(int value);      // zs_griffin.hip: "gl_chains" knob (independent launch chains of zs_griffin_lim)
-int zs_gru_spin_limit_option(int value); // zs_gru.hip: "gru_spin_limit" knob, returns the previous value
-int zs_gru_persist_option(int value);   // zs_gru.hip: "gru_persist" knob, returns the previous value
-int zs_gru_wide_option(int value);      // zs_gru.hip: "gru_wide" knob, returns the previous value
+
+// ---- kernel-selection knobs (zs_set_option, include/zs_amd.h) ------------------------------------
+// A knob is a process-wide relaxed atomic: zs_set_option may write it from any thread while another launches, so a launch reads
+// each knob it needs once, into a local.  Every knob is defined in the file that uses it and links itself into the registry that
+// zs_set_option searches (g_knobs is zero-initialised, so the order of the files' static constructors does not matter).
+// A knob with an environment variable takes its default from it at first use.  `norm` maps every stored value, set or read from
+// the environment, into the knob's range.
+inline int knob_nonneg(int v) { return v < 0 ? 0 : v; }
+inline int knob_flag(int v) { return v ? 1 : 0; }
+inline int knob_raw(int v) { return v; }
+struct Knob;
+extern Knob* g_knobs;
+struct Knob {
+  const char* const key;
+  const char* const env;          // nullptr: no environment variable
+  int (*const norm)(int);
+  Knob* const next;
+  std::atomic<int> v;
+  std::once_flag env_once;
+  Knob(const char* k, const char* e, int dflt, int (*n)(int) = knob_nonneg) : key(k), env(e), norm(n), next(g_knobs), v(n(dflt)) {
+    g_knobs = this;
+  }
+  int get() {
+    if (env) std::call_once(env_once, [this] { if (const char* s = getenv(env)) v.store(norm(atoi(s)), std::memory_order_relaxed); });
+    return v.load(std::memory_order_relaxed);
+  }
+  int set(int nv) { get(); return v.exchange(norm(nv), std::memory_order_relaxed); }   // the previous value
+};
 
 #define ZS_REQUIRE(cond, ...)                  \
   do {                                         \

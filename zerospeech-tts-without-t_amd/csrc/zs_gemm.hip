@@ -2055,39 +2055,25 @@ __global__ __launch_bounds__(256) void wgrad_reduce_taps_kernel(const ZsGemmWgra
   for (int i = (int)threadIdx.x; i < n; i += 256) d[i] = p.accumulate ? (d[i] + sT[i]) : sT[i];
 }
 
-int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-// Kernel-selection knobs: process-wide relaxed atomics (settable from any thread; every launch reads each knob once into a
-// local).  Defaults come from the environment on first use.
-struct Knob {
-  std::atomic<int> v{-1};
-  const char* env; int dflt;
-  Knob(const char* e, int d) : env(e), dflt(d) {}
-  int get() {
-    int x = v.load(std::memory_order_relaxed);
-    if (x < 0) { x = env_int(env, dflt); if (x < 0) x = 0; v.store(x, std::memory_order_relaxed); }
-    return x;
-  }
-  int set(int nv) { const int old = get(); v.store(nv < 0 ? 0 : nv, std::memory_order_relaxed); return old; }
-};
-Knob g_dma64("ZS_GEMM_DMA64", 1);                 // 64-row tiles of the LDS-DMA kernel for under-filled grids
-Knob g_dma64_max_tiles("ZS_GEMM_DMA64_MAX_TILES", 256);   // ... when twice the 128-row tile count is at most this
-Knob g_wgrad_p8("ZS_WGRAD_P8", 1);
-Knob g_wgrad_wgs("ZS_WGRAD_WGS", 256);      // workgroups one weight-gradient launch aims for (split-K plan of the 256x256 kernel)
+Knob g_dma64("gemm_dma64", "ZS_GEMM_DMA64", 1);                             // 64-row tiles of the LDS-DMA kernel for under-filled grids
+Knob g_dma64_max_tiles("gemm_dma64_max_tiles", "ZS_GEMM_DMA64_MAX_TILES", 256);   // ... when twice the 128-row tile count is at most this
+Knob g_wgrad_p8("wgrad_p8", "ZS_WGRAD_P8", 1);
+Knob g_wgrad_wgs("wgrad_wgs", "ZS_WGRAD_WGS", 256);   // workgroups one weight-gradient launch aims for (split-K plan of the 256x256 kernel)
 // workgroups a 128x128 weight-gradient launch aims for.  768 (three per CU-pair slot) is best for a launch alone; the launches of
 // this kernel run four side by side (the conv bank's seven at the end of the step), where fewer, deeper splits write and
 // re-read less slab: 448 measured 10.93 against 10.98 ms/step (384-512 equal, 256 and 1024 worse)
-Knob g_wgrad_wgs128("ZS_WGRAD_WGS128", 448);
-Knob g_wgrad_slab_cost("ZS_WGRAD_SLAB_COST", 13);   // cost of one split's slab write + re-read in K-tile times
+Knob g_wgrad_wgs128("wgrad_wgs128", "ZS_WGRAD_WGS128", 448);
+Knob g_wgrad_slab_cost("wgrad_slab_cost", "ZS_WGRAD_SLAB_COST", 13);   // cost of one split's slab write + re-read in K-tile times
 // Weight gradients launched alone on the chip (the single-stream step: zs_set_option("wgrad_alone", 1), set by the context when it
 // does not overlap weight gradients) use their own split-K constants; the two above were fitted for four launches side by side.
 // Re-fitted on the single-stream step with gemm_wgrad_dma_kernel: wgs128 448 11.92 ms/step, 768 12.01, 1024 12.06,
 // 1536 12.13; slab cost 6 / 13 / 20 within noise (11.99-12.01 at wgs128 768).  Alone, the same constants are the best measured.
-Knob g_wgrad_alone("ZS_WGRAD_ALONE", 0);
-Knob g_wgrad_wgs128_alone("ZS_WGRAD_WGS128_ALONE", 448);
-Knob g_wgrad_slab_cost_alone("ZS_WGRAD_SLAB_COST_ALONE", 13);
-Knob g_wgrad_dma("ZS_WGRAD_DMA", 1);                 // bf16 128x128 tiles: 1 = gemm_wgrad_dma_kernel, 0 = gemm_wgrad_kernel (reference)
-Knob g_wgrad_reduce_taps("ZS_WGRAD_REDUCE_TAPS", 1); // Conv1d weights: 1 = wgrad_reduce_taps_kernel, 0 = wgrad_reduce_kernel (reference)
-Knob g_wgrad_waste("ZS_WGRAD_P8_WASTE", 135);       // 256x256 weight-gradient tiles only while padded/real output area <= this / 100
+Knob g_wgrad_alone("wgrad_alone", "ZS_WGRAD_ALONE", 0);
+Knob g_wgrad_wgs128_alone("wgrad_wgs128_alone", "ZS_WGRAD_WGS128_ALONE", 448);
+Knob g_wgrad_slab_cost_alone("wgrad_slab_cost_alone", "ZS_WGRAD_SLAB_COST_ALONE", 13);
+Knob g_wgrad_dma("wgrad_dma", "ZS_WGRAD_DMA", 1);                             // bf16 128x128 tiles: 1 = gemm_wgrad_dma_kernel, 0 = gemm_wgrad_kernel (reference)
+Knob g_wgrad_reduce_taps("wgrad_reduce_taps", "ZS_WGRAD_REDUCE_TAPS", 1);   // Conv1d weights: 1 = wgrad_reduce_taps_kernel, 0 = wgrad_reduce_kernel (reference)
+Knob g_wgrad_waste("wgrad_p8_waste", "ZS_WGRAD_P8_WASTE", 135);            // 256x256 weight-gradient tiles only while padded/real output area <= this / 100
 
 struct WgradPlan { int p8, dma, splits, tile, co_tiles, ci_tiles, cout_r, cin_r, rows_per_split; };
 
@@ -2113,7 +2099,8 @@ WgradPlan wgrad_plan(const ZsGemmWgrad* p) {
     w.splits = p->splits;
   } else if (w.p8) {
     const int64_t kt = (M + 63) / 64;
-    const int64_t wgs = g_wgrad_wgs.get() > 0 ? g_wgrad_wgs.get() : 256;
+    const int wgs_knob = g_wgrad_wgs.get();
+    const int64_t wgs = wgs_knob > 0 ? wgs_knob : 256;
     const double slab_cost = (double)(alone ? g_wgrad_slab_cost_alone.get() : g_wgrad_slab_cost.get());
     double best = 1e30; int bs = 1;
     for (int sp = 1; sp <= 64 && (int64_t)sp * 4 <= kt; ++sp) {
@@ -2140,8 +2127,9 @@ WgradPlan wgrad_plan(const ZsGemmWgrad* p) {
 
 bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-Knob g_use_dma("ZS_GEMM_DMA", 1), g_use_ring("ZS_GEMM_RING", 1), g_ring_min_tiles("ZS_GEMM_RING_MIN_TILES", 256), g_use_pp("ZS_GEMM_PP", 1),
-    g_use_p8("ZS_GEMM_P8", 1), g_p8_min_tiles("ZS_GEMM_P8_MIN_TILES", 200);
+Knob g_use_dma("gemm_dma", "ZS_GEMM_DMA", 1), g_use_ring("gemm_ring", "ZS_GEMM_RING", 1),
+    g_ring_min_tiles("gemm_ring_min_tiles", "ZS_GEMM_RING_MIN_TILES", 256), g_use_pp("gemm_pp", "ZS_GEMM_PP", 1), g_use_p8("gemm_p8", "ZS_GEMM_P8", 1),
+    g_p8_min_tiles("gemm_p8_min_tiles", "ZS_GEMM_P8_MIN_TILES", 200);
 
 // one-time raise of the dynamic-LDS limit of the big-tile kernels (std::call_once: launches may come from several threads)
 std::once_flag g_lds_attr_once;
@@ -2242,37 +2230,6 @@ extern "C" int zs_gemm_conv(const ZsGemmConv* p, void* stream) {
     else hipLaunchKernelGGL(gemm_conv_kernel<bf16_t>, grid, dim3(NT), lds, s, *p);
   }
   return zs_check_launch("zs_gemm_conv");
-}
-
-extern "C" int zs_set_option(const char* key, int value) {
-  Knob* slot = nullptr;
-  if (key && !strcmp(key, "gemm_dma")) slot = &g_use_dma;
-  else if (key && !strcmp(key, "gemm_ring")) slot = &g_use_ring;
-  else if (key && !strcmp(key, "gemm_ring_min_tiles")) slot = &g_ring_min_tiles;
-  else if (key && !strcmp(key, "gemm_pp")) slot = &g_use_pp;
-  else if (key && !strcmp(key, "gemm_p8")) slot = &g_use_p8;
-  else if (key && !strcmp(key, "gemm_p8_min_tiles")) slot = &g_p8_min_tiles;
-  else if (key && !strcmp(key, "gemm_dma64")) slot = &g_dma64;
-  else if (key && !strcmp(key, "gemm_dma64_max_tiles")) slot = &g_dma64_max_tiles;
-  else if (key && !strcmp(key, "wgrad_p8")) slot = &g_wgrad_p8;
-  else if (key && !strcmp(key, "wgrad_wgs")) slot = &g_wgrad_wgs;
-  else if (key && !strcmp(key, "wgrad_wgs128")) slot = &g_wgrad_wgs128;
-  else if (key && !strcmp(key, "wgrad_slab_cost")) slot = &g_wgrad_slab_cost;
-  else if (key && !strcmp(key, "wgrad_p8_waste")) slot = &g_wgrad_waste;
-  else if (key && !strcmp(key, "wgrad_alone")) slot = &g_wgrad_alone;
-  else if (key && !strcmp(key, "wgrad_wgs128_alone")) slot = &g_wgrad_wgs128_alone;
-  else if (key && !strcmp(key, "wgrad_slab_cost_alone")) slot = &g_wgrad_slab_cost_alone;
-  else if (key && !strcmp(key, "wgrad_dma")) slot = &g_wgrad_dma;
-  else if (key && !strcmp(key, "wgrad_reduce_taps")) slot = &g_wgrad_reduce_taps;
-  if (key && !strcmp(key, "gru_persist")) return zs_gru_persist_option(value);
-  if (key && !strcmp(key, "gru_wide")) return zs_gru_wide_option(value);
-  if (key && !strcmp(key, "gru_spin_limit")) return zs_gru_spin_limit_option(value);
-  if (key && !strcmp(key, "gl_prefetch")) return zs_gl_prefetch_option(value);
-  if (key && !strcmp(key, "gl_chains")) return zs_gl_chains_option(value);
-  if (key && !strcmp(key, "norm_wide")) return zs_norm_wide_option(value);
-  if (key && !strncmp(key, "norm_lim", 8) && key[8] >= '0' && key[8] <= '2' && !key[9]) return zs_norm_lim_option(key[8] - '0', value);
-  if (!slot) { zs_set_error("zs_set_option: unknown key %s", key ? key : "(null)"); return ZS_EINVAL; }
-  return slot->set(value);
 }
 
 extern "C" size_t zs_gemm_wgrad_workspace_bytes(const ZsGemmWgrad* p) {

@@ -392,7 +392,7 @@ __global__ __launch_bounds__(256) void gl_frame_mse_kernel(const float* wav, int
   if (tid == 0) mse[(int64_t)u * mse_ld + f] = red[0] / (double)frame_length;
 }
 
-std::atomic<int> g_gl_prefetch{1};
+Knob g_gl_prefetch("gl_prefetch", nullptr, 1, knob_flag);
 std::once_flag g_gl_lds_once;
 
 size_t gl_lds_bytes(int F, int nwave) { return (size_t)WTAB * 8 + WLEN * 4 + HOP * 4 + (size_t)nwave * WBUF * 8 + ((size_t)(F - 1) * HOP + 800) * 4; }
@@ -404,7 +404,7 @@ int gl_launch(const ZsGlIter* p, const float* in, float* out, hipStream_t s, int
   // frame, 29.2 against 30.9 ms for 300 iterations of 64 utterances of 200..700 frames), else 10 frames on 4 waves (more workgroups)
   const int F = p->tile_frames > 0 ? p->tile_frames : ((int64_t)p->n_utt * p->T_max >= 8192 ? GL_TILE_LARGE : GL_TILE_DEFAULT);
   dim3 grid((unsigned)((p->T_max + F - 1) / F), (unsigned)p->n_utt);
-  const bool pf = g_gl_prefetch.load(std::memory_order_relaxed) != 0;
+  const bool pf = g_gl_prefetch.get() != 0;
 #define ZS_GL_LAUNCH(PFV, NW, FM) hipLaunchKernelGGL((gl_iter_kernel<PFV, NW, FM>), grid, dim3(64 * NW), gl_lds_bytes(F, NW), s, *p, in, out, F)
   // FROM_MAG (the first iteration reads X0 = S from the magnitudes) is a template parameter: as a run-time branch it took the
   // steady-state kernel over 128 VGPRs, i.e. from two workgroups per CU to one (26 -> 39 ms)
@@ -433,9 +433,6 @@ int gl_check(const ZsGlIter* p, const char* what) {
 
 }  // namespace
 
-// "gl_prefetch" / "gl_chains" knobs of zs_set_option
-int zs_gl_prefetch_option(int value) { return g_gl_prefetch.exchange(value ? 1 : 0, std::memory_order_relaxed); }
-
 extern "C" int zs_gl_iter(const ZsGlIter* p, void* stream) {
   int rc = gl_check(p, "zs_gl_iter");
   if (rc) return rc;
@@ -462,7 +459,8 @@ struct GlSide {
 std::mutex g_gl_side_mu;
 GlSide g_gl_side[16];
 std::atomic<int> g_gl_chains_used{1};
-std::atomic<int> g_gl_chains{3};   // measured on 64 utterances of 200..700 frames: 1 chain 29.7, 2: 26.0, 3: 25.7, 4: 32.0 ms per 300 iterations
+// measured on 64 utterances of 200..700 frames: 1 chain 29.7, 2: 26.0, 3: 25.7, 4: 32.0 ms per 300 iterations
+Knob g_gl_chains("gl_chains", nullptr, 3, [](int v) { return v < 1 ? 1 : (v > GL_MAX_CHAINS ? GL_MAX_CHAINS : v); });
 
 // one wave busy for `ticks` of the 100 MHz wall clock (bounded: the loop ends when the clock has advanced)
 __global__ void gl_spin_kernel(long long ticks) {
@@ -528,8 +526,6 @@ int gl_chain(const ZsGlIter& q, float* spec_a, float* spec_b, int n_iter, hipStr
 
 }  // namespace
 
-int zs_gl_chains_option(int value) { return g_gl_chains.exchange(value < 1 ? 1 : (value > GL_MAX_CHAINS ? GL_MAX_CHAINS : value), std::memory_order_relaxed); }
-
 extern "C" int zs_gl_chains_used(void) { return g_gl_chains_used.load(std::memory_order_relaxed); }
 
 extern "C" int zs_griffin_lim(const ZsGlIter* p, float* spec_a, float* spec_b, int32_t n_iter, void* stream) {
@@ -540,7 +536,7 @@ extern "C" int zs_griffin_lim(const ZsGlIter* p, float* spec_a, float* spec_b, i
   hipStream_t main_s = (hipStream_t)stream;
   hipLaunchKernelGGL(gl_tables_kernel, dim3(4), dim3(256), 0, main_s);
   // chains only when every one of them still has a chip's worth of frames per launch and the caller is not capturing a graph
-  int chains = g_gl_chains.load(std::memory_order_relaxed);
+  int chains = g_gl_chains.get();
   while (chains > 1 && ((int64_t)p->n_utt * p->T_max / chains < 8192 || p->n_utt < 2 * chains)) --chains;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (chains > 1 && (hipStreamIsCapturing(main_s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)) chains = 1;

@@ -1169,25 +1169,10 @@ size_t gru_hx_bytes(int B, int H, int es) {
   const size_t rows = (size_t)((B + 16 * RB - 1) / (16 * RB)) * 16 * RB;
   return (size_t)2 * 2 * rows * ((size_t)H * es / 4) * 8;
 }
-// options: relaxed atomics (zs_set_option may be called from any thread; a launch reads each knob once)
-std::atomic<int> g_gru_persist{-1};
-std::atomic<int> g_gru_wide{-1};
-bool gru_wide_enabled() {
-  int v = g_gru_wide.load(std::memory_order_relaxed);
-  if (v < 0) { const char* e = getenv("ZS_GRU_WIDE"); v = e ? atoi(e) : 1; g_gru_wide.store(v, std::memory_order_relaxed); }
-  return v != 0;
-}
-std::atomic<int> g_gru_spin_limit{-1};
-bool gru_persist_enabled() {
-  int v = g_gru_persist.load(std::memory_order_relaxed);
-  if (v < 0) { const char* e = getenv("ZS_GRU_PERSIST"); v = e ? atoi(e) : 1; g_gru_persist.store(v, std::memory_order_relaxed); }
-  return v != 0;
-}
-unsigned gru_spin_limit() {
-  int v = g_gru_spin_limit.load(std::memory_order_relaxed);
-  if (v < 0) { const char* e = getenv("ZS_GRU_SPIN_LIMIT"); v = e ? atoi(e) : (int)GRU_SPIN_LIMIT; g_gru_spin_limit.store(v, std::memory_order_relaxed); }
-  return (unsigned)v;
-}
+
+Knob g_gru_persist("gru_persist", "ZS_GRU_PERSIST", 1, knob_flag);
+Knob g_gru_wide("gru_wide", "ZS_GRU_WIDE", 1, knob_flag);         // the 16-row x 64-unit tiling of the persistent kernels
+Knob g_gru_spin_limit("gru_spin_limit", "ZS_GRU_SPIN_LIMIT", (int)GRU_SPIN_LIMIT);   // tests force a timeout with 0
 // workgroups that are certainly co-resident: one per CU
 int64_t gru_resident_limit() {
   static std::atomic<int> cus{0};
@@ -1201,14 +1186,60 @@ int64_t gru_resident_limit() {
   return c;
 }
 
-}  // namespace
+// the wide kernels move gate inputs / outputs as 16-byte vectors
+bool gru_wide_aligned(const ZsGruFwd* p) {
+  return (p->out_col % 8) == 0 && (p->ldo % 8) == 0 && (p->ldgi % 8) == 0 && ((uintptr_t)p->out % 16) == 0 && ((uintptr_t)p->gi % 16) == 0 &&
+         (!p->gates || ((uintptr_t)p->gates % 16) == 0) && (!p->bcast_vec || (p->bcast_col % 8) == 0);
+}
+bool gru_wide_aligned(const ZsGruBwd* p) {
+  return (p->dout_col % 8) == 0 && (p->out_col % 8) == 0 && (p->ldd % 8) == 0 && (p->ldo % 8) == 0 && (p->ldgi % 8) == 0 && (p->ldgh % 8) == 0 &&
+         (((uintptr_t)p->dout | (uintptr_t)p->out | (uintptr_t)p->gates | (uintptr_t)p->dgi | (uintptr_t)p->dgh) % 16) == 0;
+}
 
-// "gru_wide" knob of zs_set_option: the 16-row x 64-unit tiling of the persistent kernels (bf16, H in {128, 256, 512})
-int zs_gru_wide_option(int value) { const int old = gru_wide_enabled() ? 1 : 0; g_gru_wide.store(value ? 1 : 0, std::memory_order_relaxed); return old; }
-// "gru_persist" knob of zs_set_option
-int zs_gru_persist_option(int value) { const int old = gru_persist_enabled() ? 1 : 0; g_gru_persist.store(value ? 1 : 0, std::memory_order_relaxed); return old; }
-// "gru_spin_limit": sweeps a persistent GRU wave waits for its group before it gives up (tests force a timeout with 0)
-int zs_gru_spin_limit_option(int value) { const int old = (int)gru_spin_limit(); g_gru_spin_limit.store(value < 0 ? 0 : value, std::memory_order_relaxed); return old; }
+// How one GRU pass runs.  WIDE: one persistent launch of 16-row x 64-unit tiles (bf16, H in {128, 256, 512}).  PERSIST: one
+// persistent launch of 32 x 32 (forward) / 16 x 64 K-split (BPTT) tiles.  STEP_FUSED: one rowblock_gemm_kernel launch per step,
+// recurrent product and gate math fused.  STEP_GEMM: zs_gemm_conv and a gate kernel per step.
+enum GruPath { GRU_WIDE, GRU_PERSIST, GRU_STEP_FUSED, GRU_STEP_GEMM };
+struct GruPlan {
+  GruPath path;
+  int per;               // PERSIST: the kernel's PER (forward) / PERB (BPTT)
+  int rb;                // row blocks of the grid (grid.y); 0 for STEP_GEMM
+  unsigned spin_limit;
+};
+
+// Each plan reads the GRU knobs once.  The forward's persistent and fused paths need W_hh interleaved.
+GruPlan gru_fwd_plan(const ZsGruFwd* p) {
+  const int B = p->B, H = p->H;
+  if (!p->whh_interleaved || H % 32 != 0) return {GRU_STEP_GEMM, 0, 0, 0};
+  const bool persist = g_gru_persist.get() != 0 && p->T > 1, wide = g_gru_wide.get() != 0;
+  const unsigned spin = (unsigned)g_gru_spin_limit.get();
+  const int nrb16 = (B + 15) / 16, nrb = (B + 16 * RB - 1) / (16 * RB);
+  const int kstep = p->dtype == ZS_F32 ? 16 : 32;
+  const int per = (H % (4 * kstep) == 0) ? H / (4 * kstep) : 0;
+  if (persist && wide && p->dtype == ZS_BF16 && (H == 128 || H == 256 || H == 512) && (int64_t)(H / 64) * nrb16 * 2 <= gru_resident_limit() &&
+      gru_wide_aligned(p))
+    return {GRU_WIDE, 0, nrb16, spin};
+  if (persist && (per == 1 || per == 2 || per == 4) && (int64_t)(H / 32) * nrb * 2 <= gru_resident_limit()) return {GRU_PERSIST, per, nrb, spin};
+  return {GRU_STEP_FUSED, 0, nrb, spin};
+}
+
+GruPlan gru_bwd_plan(const ZsGruBwd* p) {
+  const int B = p->B, H = p->H;
+  if (H % 32 != 0) return {GRU_STEP_GEMM, 0, 0, 0};
+  const bool persist = g_gru_persist.get() != 0 && p->T > 1, wide = g_gru_wide.get() != 0;
+  const unsigned spin = (unsigned)g_gru_spin_limit.get();
+  const int nrb16 = (B + 15) / 16;                       // both persistent BPTT tilings: 16 rows x 64 units per workgroup
+  const int kstep = p->dtype == ZS_F32 ? 16 : 32;
+  const int perb = ((3 * H) % (4 * kstep) == 0 && H % (16 * BNT) == 0) ? (3 * H) / (4 * kstep) : 0;
+  if (persist && wide && p->dtype == ZS_BF16 && (H == 128 || H == 256 || H == 512) && (int64_t)(H / 64) * nrb16 * 2 <= gru_resident_limit() &&
+      gru_wide_aligned(p))
+    return {GRU_WIDE, 0, nrb16, spin};
+  if (persist && (perb == 3 || perb == 6 || perb == 12) && (int64_t)(H / (16 * BNT)) * nrb16 * 2 <= gru_resident_limit())
+    return {GRU_PERSIST, perb, nrb16, spin};
+  return {GRU_STEP_FUSED, 0, (B + 16 * RB - 1) / (16 * RB), spin};
+}
+
+}  // namespace
 
 extern "C" size_t zs_gru_work_bytes(int32_t B, int32_t H) {
   // gh [2][B][3H] + hstate/dhd [2][B][H] + dhg [2][B][H], fp32; or the persistent kernel's exchange granules (fp32 size) + error word
@@ -1231,12 +1262,6 @@ extern "C" int zs_gru_check(const float* work, int32_t B, int32_t H, void* strea
   return ZS_OK;
 }
 
-// the wide kernels move gate inputs / outputs as 16-byte vectors
-static bool gru_wide_aligned(const ZsGruFwd* p) {
-  return (p->out_col % 8) == 0 && (p->ldo % 8) == 0 && (p->ldgi % 8) == 0 && ((uintptr_t)p->out % 16) == 0 && ((uintptr_t)p->gi % 16) == 0 &&
-         (!p->gates || ((uintptr_t)p->gates % 16) == 0) && (!p->bcast_vec || (p->bcast_col % 8) == 0);
-}
-
 extern "C" int zs_gru_fwd(const ZsGruFwd* p, void* stream) {
   ZS_REQUIRE(p && p->gi && p->whh && p->bhh && p->out && p->work, "zs_gru_fwd: null operand");
   ZS_REQUIRE(p->dtype == ZS_F32 || p->dtype == ZS_BF16, "zs_gru_fwd: bad dtype");
@@ -1251,19 +1276,9 @@ extern "C" int zs_gru_fwd(const ZsGruFwd* p, void* stream) {
   float* hstate = wbase + (size_t)2 * B * 3 * H;
   const char* outb = (const char*)p->out;
   ZS_REQUIRE(!p->bcast_vec || (p->bcast_idx && (p->bcast_col * es) % 4 == 0), "zs_gru_fwd: bcast_idx / bcast_col");
-  bool bcast_pending = p->bcast_vec != nullptr;        // every path but the persistent kernel: a launch of its own, first
-  {
-    const int nrb0 = (B + 16 * RB - 1) / (16 * RB);
-    const int kstep0 = p->dtype == ZS_F32 ? 16 : 32;
-    const int per0 = (H % (4 * kstep0) == 0) ? H / (4 * kstep0) : 0;
-    if (p->whh_interleaved && H % 32 == 0 && gru_persist_enabled() && (per0 == 1 || per0 == 2 || per0 == 4) &&
-        (int64_t)(H / 32) * nrb0 * 2 <= gru_resident_limit() && T > 1)
-      bcast_pending = false;
-    if (p->whh_interleaved && gru_persist_enabled() && gru_wide_enabled() && p->dtype == ZS_BF16 && (H == 128 || H == 256 || H == 512) && T > 1 &&
-        (int64_t)(H / 64) * ((B + 15) / 16) * 2 <= gru_resident_limit() && gru_wide_aligned(p))
-      bcast_pending = false;
-  }
-  if (bcast_pending) {
+  const GruPlan pl = gru_fwd_plan(p);
+  const bool persistent = pl.path == GRU_WIDE || pl.path == GRU_PERSIST;
+  if (p->bcast_vec && !persistent) {                   // the persistent kernels write it with the recurrence; the others: a launch first
     ZsAddRowvec r;
     memset(&r, 0, sizeof(r));
     r.dtype = p->dtype; r.vec = p->bcast_vec; r.vec_ld = p->bcast_ld; r.idx = p->bcast_idx;
@@ -1271,45 +1286,38 @@ extern "C" int zs_gru_fwd(const ZsGruFwd* p, void* stream) {
     int rc = zs_add_rowvec(&r, stream);
     if (rc) return rc;
   }
-  if (p->whh_interleaved && H % 32 == 0) {
+  if (persistent) {
     // persistent kernel: the time loop runs on the device (see gru_persist_fwd_kernel)
-    const int nrb = (B + 16 * RB - 1) / (16 * RB);
-    const int kstep = p->dtype == ZS_F32 ? 16 : 32;
-    const int per = (H % (4 * kstep) == 0) ? H / (4 * kstep) : 0;
-    const int64_t nwg = (int64_t)(H / 32) * nrb * 2;
-    const int nrb16 = (B + 15) / 16;
-    const bool wide = gru_persist_enabled() && gru_wide_enabled() && p->dtype == ZS_BF16 && (H == 128 || H == 256 || H == 512) && T > 1 &&
-                      (int64_t)(H / 64) * nrb16 * 2 <= gru_resident_limit() && gru_wide_aligned(p);
-    if (wide || (gru_persist_enabled() && (per == 1 || per == 2 || per == 4) && nwg <= gru_resident_limit() && T > 1)) {
-      GruPersistArgs a;
-      memset(&a, 0, sizeof(a));
-      a.gi = p->gi; a.ldgi = p->ldgi; a.whh = p->whh; a.ldw = p->ldw; a.w_gstride = p->w_gstride;
-      a.bhh = p->bhh; a.bhh_gstride = p->bhh_gstride; a.out = p->out; a.ldo = p->ldo; a.out_col = p->out_col; a.gates = p->gates;
-      const size_t hx_bytes = gru_hx_bytes(B, H, es);
-      a.hx = reinterpret_cast<unsigned long long*>(wbase);
-      a.err = reinterpret_cast<unsigned*>(p->work);
-      a.status = p->status; a.spin_limit = gru_spin_limit();
-      a.B = B; a.T = T; a.H = H; a.rows_pad = wide ? nrb16 * 16 : nrb * 16 * RB;
-      a.bcast_vec = p->bcast_vec; a.bcast_ld = p->bcast_ld; a.bcast_idx = p->bcast_idx; a.bcast_col = p->bcast_col;
-      a.dir1_forward = p->dir1_forward != 0;
-      if (hipMemsetAsync(p->work, 0, GRU_WORK_HDR + hx_bytes, (hipStream_t)stream) != hipSuccess) {
-        zs_set_error("zs_gru_fwd: memset failed");
-        return ZS_ELAUNCH;
-      }
-      if (wide) {
-        dim3 wgrid(H / 64, nrb16, 2);
-        if (H == 512) hipLaunchKernelGGL(gru_wide_fwd_kernel<16>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
-        else if (H == 256) hipLaunchKernelGGL(gru_wide_fwd_kernel<8>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(gru_wide_fwd_kernel<4>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
-        return zs_check_launch("zs_gru_fwd.wide");
-      }
-      dim3 grid(H / 32, nrb, 2);
-#define ZS_GRU_PF(TT, PP) hipLaunchKernelGGL((gru_persist_fwd_kernel<TT, PP>), grid, dim3(256), 0, (hipStream_t)stream, a)
-      if (p->dtype == ZS_F32) { if (per == 1) ZS_GRU_PF(float, 1); else if (per == 2) ZS_GRU_PF(float, 2); else ZS_GRU_PF(float, 4); }
-      else { if (per == 1) ZS_GRU_PF(bf16_t, 1); else if (per == 2) ZS_GRU_PF(bf16_t, 2); else ZS_GRU_PF(bf16_t, 4); }
-#undef ZS_GRU_PF
-      return zs_check_launch("zs_gru_fwd.persist");
+    GruPersistArgs a;
+    memset(&a, 0, sizeof(a));
+    a.gi = p->gi; a.ldgi = p->ldgi; a.whh = p->whh; a.ldw = p->ldw; a.w_gstride = p->w_gstride;
+    a.bhh = p->bhh; a.bhh_gstride = p->bhh_gstride; a.out = p->out; a.ldo = p->ldo; a.out_col = p->out_col; a.gates = p->gates;
+    a.hx = reinterpret_cast<unsigned long long*>(wbase);
+    a.err = reinterpret_cast<unsigned*>(p->work);
+    a.status = p->status; a.spin_limit = pl.spin_limit;
+    a.B = B; a.T = T; a.H = H; a.rows_pad = pl.path == GRU_WIDE ? pl.rb * 16 : pl.rb * 16 * RB;
+    a.bcast_vec = p->bcast_vec; a.bcast_ld = p->bcast_ld; a.bcast_idx = p->bcast_idx; a.bcast_col = p->bcast_col;
+    a.dir1_forward = p->dir1_forward != 0;
+    if (hipMemsetAsync(p->work, 0, GRU_WORK_HDR + gru_hx_bytes(B, H, es), (hipStream_t)stream) != hipSuccess) {
+      zs_set_error("zs_gru_fwd: memset failed");
+      return ZS_ELAUNCH;
     }
+    if (pl.path == GRU_WIDE) {
+      dim3 wgrid(H / 64, pl.rb, 2);
+      if (H == 512) hipLaunchKernelGGL(gru_wide_fwd_kernel<16>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
+      else if (H == 256) hipLaunchKernelGGL(gru_wide_fwd_kernel<8>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
+      else hipLaunchKernelGGL(gru_wide_fwd_kernel<4>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
+      return zs_check_launch("zs_gru_fwd.wide");
+    }
+    dim3 grid(H / 32, pl.rb, 2);
+    const int per = pl.per;
+#define ZS_GRU_PF(TT, PP) hipLaunchKernelGGL((gru_persist_fwd_kernel<TT, PP>), grid, dim3(256), 0, (hipStream_t)stream, a)
+    if (p->dtype == ZS_F32) { if (per == 1) ZS_GRU_PF(float, 1); else if (per == 2) ZS_GRU_PF(float, 2); else ZS_GRU_PF(float, 4); }
+    else { if (per == 1) ZS_GRU_PF(bf16_t, 1); else if (per == 2) ZS_GRU_PF(bf16_t, 2); else ZS_GRU_PF(bf16_t, 4); }
+#undef ZS_GRU_PF
+    return zs_check_launch("zs_gru_fwd.persist");
+  }
+  if (pl.path == GRU_STEP_FUSED) {
     // one fused launch per step: recurrent product + gates (see rowblock_gemm_kernel)
     for (int s = 0; s < T; ++s) {
       RowGemmArgs a;
@@ -1324,7 +1332,7 @@ extern "C" int zs_gru_fwd(const ZsGruFwd* p, void* stream) {
       g.gi = p->gi; g.ldgi = p->ldgi; g.gh = nullptr; g.bhh = p->bhh; g.bhh_gstride = p->bhh_gstride; g.hstate = hstate;
       g.out = p->out; g.ldo = p->ldo; g.out_col = p->out_col; g.gates = p->gates; g.B = B; g.T = T; g.H = H; g.step = s;
       g.dir1_forward = p->dir1_forward != 0;
-      dim3 grid(H / 32, (B + 16 * RB - 1) / (16 * RB), 2);
+      dim3 grid(H / 32, pl.rb, 2);
       if (p->dtype == ZS_F32) hipLaunchKernelGGL((rowblock_gemm_kernel<float, 6, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
       else hipLaunchKernelGGL((rowblock_gemm_kernel<bf16_t, 6, 1>), grid, dim3(256), 0, (hipStream_t)stream, a);
       int rc = zs_check_launch("zs_gru_fwd.step");
@@ -1375,58 +1383,37 @@ extern "C" int zs_gru_bwd(const ZsGruBwd* p, void* stream) {
   float* dhd = wbase + (size_t)2 * B * 3 * H;
   float* dhg = dhd + (size_t)2 * B * H;
   const char* dghb = (const char*)p->dgh;
-  const bool fast = (H % 32 == 0);
-  if (fast && gru_persist_enabled() && T > 1) {
-    const int nrb = (B + 15) / 16;                         // 16 rows x 64 units per workgroup
-    if (gru_wide_enabled() && p->dtype == ZS_BF16 && (H == 128 || H == 256 || H == 512) && (int64_t)(H / 64) * nrb * 2 <= gru_resident_limit() &&
-        (p->dout_col % 8) == 0 && (p->out_col % 8) == 0 && (p->ldd % 8) == 0 && (p->ldo % 8) == 0 && (p->ldgi % 8) == 0 && (p->ldgh % 8) == 0 &&
-        (((uintptr_t)p->dout | (uintptr_t)p->out | (uintptr_t)p->gates | (uintptr_t)p->dgi | (uintptr_t)p->dgh) % 16) == 0) {
-      GruPersistBwdArgs a;
-      memset(&a, 0, sizeof(a));
-      a.dout = p->dout; a.ldd = p->ldd; a.dout_col = p->dout_col; a.out = p->out; a.ldo = p->ldo; a.out_col = p->out_col;
-      a.gates = p->gates; a.whh_t = p->whh_t; a.ldw = p->ldw; a.w_gstride = p->w_gstride;
-      a.dgi = p->dgi; a.ldgi = p->ldgi; a.dgh = p->dgh; a.ldgh = p->ldgh;
-      const size_t dx_bytes = gru_hx_bytes(B, 3 * H, es);
-      a.dx = reinterpret_cast<unsigned long long*>(wbase);
-      a.err = reinterpret_cast<unsigned*>(p->work);
-      a.status = p->status; a.spin_limit = gru_spin_limit();
-      a.B = B; a.T = T; a.H = H; a.rows_pad = nrb * 16;
-      if (hipMemsetAsync(p->work, 0, GRU_WORK_HDR + dx_bytes, (hipStream_t)stream) != hipSuccess) {
-        zs_set_error("zs_gru_bwd: memset failed");
-        return ZS_ELAUNCH;
-      }
-      dim3 wgrid(H / 64, nrb, 2);
+  const GruPlan pl = gru_bwd_plan(p);
+  if (pl.path == GRU_WIDE || pl.path == GRU_PERSIST) {
+    GruPersistBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dout = p->dout; a.ldd = p->ldd; a.dout_col = p->dout_col; a.out = p->out; a.ldo = p->ldo; a.out_col = p->out_col;
+    a.gates = p->gates; a.whh_t = p->whh_t; a.ldw = p->ldw; a.w_gstride = p->w_gstride;
+    a.dgi = p->dgi; a.ldgi = p->ldgi; a.dgh = p->dgh; a.ldgh = p->ldgh;
+    a.dx = reinterpret_cast<unsigned long long*>(wbase);
+    a.err = reinterpret_cast<unsigned*>(p->work);
+    a.status = p->status; a.spin_limit = pl.spin_limit;
+    a.B = B; a.T = T; a.H = H; a.rows_pad = pl.rb * 16;
+    if (hipMemsetAsync(p->work, 0, GRU_WORK_HDR + gru_hx_bytes(B, 3 * H, es), (hipStream_t)stream) != hipSuccess) {
+      zs_set_error("zs_gru_bwd: memset failed");
+      return ZS_ELAUNCH;
+    }
+    if (pl.path == GRU_WIDE) {
+      dim3 wgrid(H / 64, pl.rb, 2);
       if (H == 512) hipLaunchKernelGGL(gru_wide_bwd_kernel<16>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
       else if (H == 256) hipLaunchKernelGGL(gru_wide_bwd_kernel<8>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
       else hipLaunchKernelGGL(gru_wide_bwd_kernel<4>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
       return zs_check_launch("zs_gru_bwd.wide");
     }
-    const int kstep = p->dtype == ZS_F32 ? 16 : 32;
-    const int perb = ((3 * H) % (4 * kstep) == 0 && H % (16 * BNT) == 0) ? (3 * H) / (4 * kstep) : 0;
-    const int64_t nwg = (int64_t)(H / (16 * BNT)) * nrb * 2;
-    if ((perb == 3 || perb == 6 || perb == 12) && nwg <= gru_resident_limit()) {
-      GruPersistBwdArgs a;
-      memset(&a, 0, sizeof(a));
-      a.dout = p->dout; a.ldd = p->ldd; a.dout_col = p->dout_col; a.out = p->out; a.ldo = p->ldo; a.out_col = p->out_col;
-      a.gates = p->gates; a.whh_t = p->whh_t; a.ldw = p->ldw; a.w_gstride = p->w_gstride;
-      a.dgi = p->dgi; a.ldgi = p->ldgi; a.dgh = p->dgh; a.ldgh = p->ldgh;
-      const size_t dx_bytes = gru_hx_bytes(B, 3 * H, es);
-      a.dx = reinterpret_cast<unsigned long long*>(wbase);
-      a.err = reinterpret_cast<unsigned*>(p->work);
-      a.status = p->status; a.spin_limit = gru_spin_limit();
-      a.B = B; a.T = T; a.H = H; a.rows_pad = nrb * 16;
-      if (hipMemsetAsync(p->work, 0, GRU_WORK_HDR + dx_bytes, (hipStream_t)stream) != hipSuccess) {
-        zs_set_error("zs_gru_bwd: memset failed");
-        return ZS_ELAUNCH;
-      }
-      dim3 grid(H / (16 * BNT), nrb, 2);
+    dim3 grid(H / (16 * BNT), pl.rb, 2);
+    const int perb = pl.per;
 #define ZS_GRU_PB(TT, PP) hipLaunchKernelGGL((gru_persist_bwd_kernel<TT, PP>), grid, dim3(256), 0, (hipStream_t)stream, a)
-      if (p->dtype == ZS_F32) { if (perb == 3) ZS_GRU_PB(float, 3); else if (perb == 6) ZS_GRU_PB(float, 6); else ZS_GRU_PB(float, 12); }
-      else { if (perb == 3) ZS_GRU_PB(bf16_t, 3); else if (perb == 6) ZS_GRU_PB(bf16_t, 6); else ZS_GRU_PB(bf16_t, 12); }
+    if (p->dtype == ZS_F32) { if (perb == 3) ZS_GRU_PB(float, 3); else if (perb == 6) ZS_GRU_PB(float, 6); else ZS_GRU_PB(float, 12); }
+    else { if (perb == 3) ZS_GRU_PB(bf16_t, 3); else if (perb == 6) ZS_GRU_PB(bf16_t, 6); else ZS_GRU_PB(bf16_t, 12); }
 #undef ZS_GRU_PB
-      return zs_check_launch("zs_gru_bwd.persist");
-    }
+    return zs_check_launch("zs_gru_bwd.persist");
   }
+  const bool fast = pl.path == GRU_STEP_FUSED;
   for (int s = 0; s < T; ++s) {
     GateBwdArgs a;
     a.dout = p->dout; a.ldd = p->ldd; a.dout_col = p->dout_col; a.out = p->out; a.ldo = p->ldo; a.out_col = p->out_col;
@@ -1450,7 +1437,7 @@ extern "C" int zs_gru_bwd(const ZsGruBwd* p, void* stream) {
       ra.W = p->whh_t; ra.ldw = p->ldw; ra.w_gstride = p->w_gstride;
       ra.M = B; ra.N = H; ra.K = 3 * H;
       ra.gbw = a; ra.gbw.step = s + 1;
-      dim3 grid(H / 32, (B + 16 * RB - 1) / (16 * RB), 2);
+      dim3 grid(H / 32, pl.rb, 2);
       if (p->dtype == ZS_F32) hipLaunchKernelGGL((rowblock_gemm_kernel<float, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, ra);
       else hipLaunchKernelGGL((rowblock_gemm_kernel<bf16_t, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, ra);
       rc = zs_check_launch("zs_gru_bwd.step");

@@ -7,8 +7,6 @@
 // each activation is read from HBM exactly once.  These kernels are HBM-bound.
 #include <stdlib.h>
 
-#include <atomic>
-
 #include "zs_common.h"
 
 namespace {
@@ -346,9 +344,9 @@ __global__ __launch_bounds__(S::NTN) void grad_combine_kernel(const ZsGradCombin
 
 bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-std::atomic<int> g_norm_wide{1};
-// longest T that takes the 8x256 decomposition in instnorm_fwd, instnorm_bwd, grad_combine ("norm_lim0..2" knobs: tools/instnorm_probe.py)
-int g_norm_lim[3] = {64, 32, 64};
+Knob g_norm_wide("norm_wide", nullptr, 1, knob_flag);
+// longest T that takes the 8x256 decomposition in instnorm_fwd, instnorm_bwd, grad_combine (tools/instnorm_probe.py)
+Knob g_norm_lim0("norm_lim0", nullptr, 64, knob_raw), g_norm_lim1("norm_lim1", nullptr, 32, knob_raw), g_norm_lim2("norm_lim2", nullptr, 64, knob_raw);
 // Wide8 for short samples of wide layers in bf16 (fp32 rows are twice the registers; it is the parity dtype, not the fast one)
 // Measured at B = 256, C = 1024, bf16 (tools/instnorm_probe.py; us for 32x64 | 8x256):
 //   forward   T = 16: 29.2 | 11.9   32: 31.4 | 17.0   64: 36.6 | 26.2
@@ -358,7 +356,7 @@ int g_norm_lim[3] = {64, 32, 64};
 // (11.05-11.07 against 11.01-11.03 ms with 8x256 only, same box): not kept.
 // 8x256 for short samples of wide layers in bf16 (fp32 rows are twice the registers; it is the parity dtype, not the fast one)
 bool norm_wide(int dtype, int T, int C, int max_T) {
-  return g_norm_wide.load(std::memory_order_relaxed) != 0 && dtype == ZS_BF16 && T <= max_T && T <= Wide8::RG * RPT && C >= Wide8::CHUNK;
+  return g_norm_wide.get() != 0 && dtype == ZS_BF16 && T <= max_T && T <= Wide8::RG * RPT && C >= Wide8::CHUNK;
 }
 
 #define ZS_NORM_LAUNCH(KERNEL, MAXT)                                                                                        \
@@ -375,10 +373,6 @@ bool norm_wide(int dtype, int T, int C, int max_T) {
 
 }  // namespace
 
-int zs_norm_lim_option(int i, int value) { const int o = g_norm_lim[i]; g_norm_lim[i] = value; return o; }
-// "norm_wide" knob of zs_set_option
-int zs_norm_wide_option(int value) { return g_norm_wide.exchange(value ? 1 : 0, std::memory_order_relaxed); }
-
 extern "C" int zs_instnorm_fwd(const ZsInstNormFwd* p, void* stream) {
   ZS_REQUIRE(p && p->x && p->out, "zs_instnorm_fwd: null operand");
   ZS_REQUIRE(!p->stats_given || (p->mean && p->rstd), "zs_instnorm_fwd: stats_given needs mean and rstd");
@@ -394,7 +388,7 @@ extern "C" int zs_instnorm_fwd(const ZsInstNormFwd* p, void* stream) {
     if (p->res_mode == ZS_RES_AVGPOOL2) ZS_REQUIRE((p->T_res + 1) / 2 == p->T && p->T_res >= 2, "zs_instnorm_fwd: avgpool T_res %d vs T %d", p->T_res, p->T);
   }
   ZS_REQUIRE(p->drop_p >= 0.f && p->drop_p < 1.f, "zs_instnorm_fwd: drop_p");
-  ZS_NORM_LAUNCH(instnorm_fwd_kernel, g_norm_lim[0]);
+  ZS_NORM_LAUNCH(instnorm_fwd_kernel, g_norm_lim0.get());
   return zs_check_launch("zs_instnorm_fwd");
 }
 
@@ -405,7 +399,7 @@ extern "C" int zs_instnorm_bwd(const ZsInstNormBwd* p, void* stream) {
   ZS_REQUIRE(p->B > 0 && p->T > 0 && p->T <= Narrow::RG * RPT && p->C > 0 && p->C % 8 == 0, "zs_instnorm_bwd: sizes");
   ZS_REQUIRE(al16(p->dout) && al16(p->x) && al16(p->dz) && (p->ldd * es) % 16 == 0 && (p->ldx * es) % 16 == 0 && (p->ldz * es) % 16 == 0,
              "zs_instnorm_bwd: alignment");
-  ZS_NORM_LAUNCH(instnorm_bwd_kernel, g_norm_lim[1]);
+  ZS_NORM_LAUNCH(instnorm_bwd_kernel, g_norm_lim1.get());
   return zs_check_launch("zs_instnorm_bwd");
 }
 
@@ -423,6 +417,6 @@ extern "C" int zs_grad_combine(const ZsGradCombine* p, void* stream) {
   }
   ZS_REQUIRE(!p->unshuffle || (p->T % 2 == 0 && (p->C * es) % 16 == 0), "zs_grad_combine: unshuffle");
   ZS_REQUIRE(!p->dact_src || (al16(p->dact_src) && (p->dact_ld * es) % 16 == 0), "zs_grad_combine: dact");
-  ZS_NORM_LAUNCH(grad_combine_kernel, g_norm_lim[2]);
+  ZS_NORM_LAUNCH(grad_combine_kernel, g_norm_lim2.get());
   return zs_check_launch("zs_grad_combine");
 }
