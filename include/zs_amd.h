@@ -522,6 +522,22 @@ int zs_pre_spectrogram(const ZsPreSpec* p, void* stream);
  * (librosa.filters.mel(sr, n_fft, n_mels), preprocess.py:243-252) */
 int zs_pre_mel(const float* amp, const float* basis, float* mel, int64_t rows, int32_t n_mels, float ref_db, float max_db, void* stream);
 int zs_gl_denormalize(const float* mag_norm, float* mag_amp, int64_t n, void* stream);
+/* zs_gen_scatter: the stage-2 converted spectrogram of one inference chunk, straight into the vocoder's padded amplitude input
+ * (trainer.py:206-213 combine, then convert.py:56-58 when denorm is set).  xd, m: fp32 rows [rows][ld_xd] / [rows][ld_m], e.g. the
+ * decoder's and the generator's outputs of a chunk (r = b*T + t), read in place:
+ *   amp[dst[r]][f] = denorm(combine(xd[r][f], m[r][f]))     f < 513, for every r with 0 <= dst[r] < amp_rows (dst < 0: skip)
+ *   combine: mode 0  xd;  mode 1  xd + m;  mode 2  xd + xd*m, the product rounded before the add (no FMA contraction, as torch)
+ *   denorm:  the expression of zs_gl_denormalize (one shared device function: the same bits for the same input) or, if 0, none.
+ * ld_xd == 0 reads the same row for every r (mode 0 over a zero row: the padding rows of the vocoder input).  m may be null in
+ * mode 0.  One wave per row, no allocation, no synchronisation. */
+typedef struct {
+  const float* xd; int64_t ld_xd;
+  const float* m; int64_t ld_m;
+  const int32_t* dst; int64_t rows;
+  float* amp; int64_t amp_ld, amp_rows;
+  int32_t mode, denorm;
+} ZsGenScatter;
+int zs_gen_scatter(const ZsGenScatter* p, void* stream);
 int zs_gl_deemphasis(float* wav, int64_t wav_ld, const int32_t* lengths, int32_t n_utt, float coef, void* stream);
 /* zs_gl_frame_mse: the frame statistics of librosa.effects.trim (convert.py:61; librosa's rms on the centred, reflect-padded
  * signal): mse[u][f] = mean_{i < frame_length} y_u[reflect(f*hop + i - frame_length/2)]^2, f <= L_u / hop, L_u = 200 *

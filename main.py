@@ -5,10 +5,11 @@
   python main.py --train_p | --train_tgat [--load_model] [--synthetic]     (stage 2: patchGAN from an ae checkpoint)
   python main.py --test --enc_only | --test_encode        (needs the preprocessed HDF5 + a checkpoint)
   python main.py --test_single --s_speaker S015 --t_speaker V002 [--enc_only]      (one wav -> result.wav + result.txt)
+  python main.py --cross_test [--enc_only]                 (every test utterance to every V* speaker, batched)
 
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
-(--train_al, --train_c, --train_t, --cross_test,
+(--train_al, --train_c, --train_t,
 --test_classify, --encode, --test_asr) are not part of this build and exit with a clear error.
 """
 import argparse
@@ -18,13 +19,13 @@ import sys
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-OUT_OF_SCOPE = ['train_al', 'train_c', 'train_t', 'test_asr', 'cross_test', 'test_classify', 'encode']
+OUT_OF_SCOPE = ['train_al', 'train_c', 'train_t', 'test_asr', 'test_classify', 'encode']
 
 
 def build_parser():
     p = argparse.ArgumentParser(description='zerospeech_project (MI355X autoencoder hot path)')
-    for flag in ['preprocess', 'train', 'train_ae', 'train_p', 'train_tgat', 'test', 'test_encode', 'test_single', 'load_model', 'enc_only',
-                 'remake', 'synthetic'] + OUT_OF_SCOPE:
+    for flag in ['preprocess', 'train', 'train_ae', 'train_p', 'train_tgat', 'test', 'cross_test', 'test_encode', 'test_single', 'load_model',
+                 'enc_only', 'remake', 'synthetic'] + OUT_OF_SCOPE:
         p.add_argument('--' + flag, default=False, action='store_true')
     p.add_argument('--flag', type=str, default='train')
     p.add_argument('--g_mode', default='set_from_hps',
@@ -85,7 +86,7 @@ def main(argv=None):
     if bad:
         raise NotImplementedError('--%s is outside the stage-1 autoencoder hot path this build covers' % bad[0])
     from zs_amd import parallel
-    from zs_amd.convert import get_trainer, test_encode, test_from_list, test_single
+    from zs_amd.convert import cross_test, get_trainer, test_encode, test_from_list, test_single
     from zs_amd.dataloader import DataLoader, Dataset, SyntheticDataset
     from zs_amd.trainer import Trainer
 
@@ -126,7 +127,7 @@ def main(argv=None):
             print("[Runner] - --train ran the pretrain_AE and patchGAN stages; the reference's autolocker / t_classify / Tacotron "
                   'stages are not part of this build and were skipped')
 
-    if args.test or args.test_encode or args.test_single:
+    if args.test or args.cross_test or args.test_encode or args.test_single:
         os.makedirs(args.result_dir, exist_ok=True)
         model_path = args.ckpt_pth if args.ckpt_pth is not None else os.path.join(args.ckpt_dir, args.load_test_model_name)
         trainer = get_trainer(args.hps_path, model_path, args.g_mode, args.enc_mode, None)
@@ -134,6 +135,8 @@ def main(argv=None):
         os.makedirs(result_dir, exist_ok=True)
         if args.test:
             test_from_list(trainer, hps.seg_len, args.synthesis_list, args.dataset_path, args.speaker2id_path, result_dir, args.enc_only)
+        if args.cross_test:                               # main.py:188-189
+            cross_test(trainer, hps.seg_len, args.dataset_path, args.speaker2id_path, args.result_dir, args.enc_only, flag='test')
         if args.test_single:                              # main.py:190-191
             test_single(trainer, hps.seg_len, args.speaker2id_path, args.result_dir, args.enc_only, args.s_speaker, args.t_speaker)
         if args.test_encode:

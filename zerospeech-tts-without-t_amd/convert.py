@@ -127,12 +127,16 @@ def trim_bounds(mse, n, top_db=60, hop_length=TRIM_HOP):
     return int(nz[0]) * hop_length, min(n, (int(nz[-1]) + 1) * hop_length)
 
 
-def _enqueue_vocoder(t, lens, n_iter, do_trim, dev):
-    """t: normalised magnitudes [n, T_max, 513] fp32 on the device.  Enqueues convert.py:55-62 and returns the function that
-    waits for it and cuts the waveforms (librosa.effects.trim restated on device-computed frame statistics)."""
+def _enqueue_vocoder(t, lens, n_iter, do_trim, dev, amplitudes=False):
+    """t: normalised magnitudes [n, T_max, 513] fp32 on the device (amplitudes=True: already de-normalised, e.g. by
+    zs_gen_scatter).  Enqueues convert.py:55-62 and returns the function that waits for it and cuts the waveforms
+    (librosa.effects.trim restated on device-computed frame statistics)."""
     st = torch.cuda.current_stream(dev).cuda_stream
-    amp = torch.empty_like(t)
-    L.check(L.lib().zs_gl_denormalize(L.ptr(t), L.ptr(amp), t.numel(), st), 'zs_gl_denormalize')     # convert.py:56-58
+    if amplitudes:
+        amp = t
+    else:
+        amp = torch.empty_like(t)
+        L.check(L.lib().zs_gl_denormalize(L.ptr(t), L.ptr(amp), t.numel(), st), 'zs_gl_denormalize')     # convert.py:56-58
     wav, lengths, lens = griffin_lim_batch(None, n_iter=n_iter, device=dev, mag_padded=(amp, lens))
     L.check(L.lib().zs_gl_deemphasis(L.ptr(wav), wav.shape[1], L.ptr(lengths), len(lens), float(hp.preemphasis), st),
             'zs_gl_deemphasis')                               # signal.lfilter([1], [1, -0.97], wav)
@@ -349,13 +353,42 @@ def _t8(n):
 
 
 class _Enqueued(object):
-    """What _enqueue_encode leaves behind: nothing here has been waited for."""
-    __slots__ = ('n_utt', 'chunks', 'enc_host', 'dec_dev', 'dec_host', 'enc_done', 'dev')
+    """What _enqueue_encode leaves behind: nothing here has been waited for.  With the generator (enc_only=False), `conv` holds
+    the converted spectrograms [n_utt, T_max, 513] fp32 on the device (amplitudes when de-normalised) and `ulens` their frames."""
+    __slots__ = ('n_utt', 'chunks', 'enc_host', 'dec_dev', 'dec_host', 'enc_done', 'dev', 'conv', 'ulens')
 
 
-def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host):
+GEN_COMBINE = {'naive': 1, 'targeted': 1, 'spectrogram': 1, 'targeted_residual': 2}     # zs_gen_scatter modes (trainer.py:206-213)
+
+
+def check_gen_targets(trainer, speakers):
+    """test_step's target check (trainer.py:202-203) for a whole batch, on the host, before anything is enqueued: a generator other
+    than 'naive' only converts to the target speakers [shift, shift + n_target_speakers); 'naive' takes any id below n_speakers
+    (an id outside its embedding table would be read past on the GPU).  Returns the shift subtracted from the targets."""
+    if trainer.g_mode not in GEN_COMBINE:
+        raise NotImplementedError('g_mode %r has no batched conversion path' % trainer.g_mode)
+    n_spk = int(trainer.hps.n_speakers)
+    bad = [int(s) for s in speakers if not 0 <= int(s) < n_spk]
+    if bad:
+        raise ValueError('speaker id %d is outside [0, n_speakers = %d)' % (bad[0], n_spk))
+    if trainer.g_mode == 'naive':
+        return 0
+    shift = n_spk - int(trainer.hps.n_target_speakers)
+    if any(not shift <= int(s) < shift + int(trainer.Generator.c_a) for s in speakers):
+        raise RuntimeError('This generator can only convert to target speakers!')
+    return shift
+
+
+def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host, enc_only=True, denorm=False):
     """Fragment rule + every Encoder / Decoder launch of a batch of utterances, WITHOUT a host synchronisation: the caller decides
-    what else to put on the stream (the vocoder) before it waits."""
+    what else to put on the stream (the vocoder) before it waits.
+    enc_only=False (decode_speakers required): the stage-2 generator as well, and zs_gen_scatter writes every chunk's converted rows
+    into q.conv right behind it (de-normalised when `denorm`): the engines reuse their output buffers for the next chunk of the
+    same shape."""
+    if not enc_only:
+        if decode_speakers is None:
+            raise ValueError('conversion with the generator (enc_only=False) needs the target speakers')
+        shift = check_gen_targets(trainer, decode_speakers)
     trainer.set_eval()
     enc, dec = trainer.Encoder, trainer.Decoder
     dev = trainer.device
@@ -387,7 +420,12 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
     zero_row = int(offs[-1])
     q = _Enqueued()
     q.n_utt, q.dev, q.chunks, q.enc_host, q.dec_dev, q.dec_host = len(specs), dev, [], [], [], []
-    for chunk, ragged in chunks:
+    q.conv = q.ulens = None
+    if not enc_only:
+        q.conv, q.ulens, dsts = _plan_scatter(items, chunks, len(specs), denorm, dev)
+        gen = trainer.Generator._engine()
+        mode = GEN_COMBINE[trainer.g_mode]
+    for ci, (chunk, ragged) in enumerate(chunks):
         lens = [b - a for (_, _, a, b, _) in chunk]
         Tm = max(lens)
         idx = np.full((len(chunk), Tm), zero_row, dtype=np.int64)
@@ -397,10 +435,26 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
         G = noise_fn(len(chunk), _t8(Tm), enc.enc_size) if noise_fn is not None else None
         act, _ = enc(x.permute(0, 2, 1), G=G, lengths=(lens if ragged else None))
         xd = None
-        if decode_speakers is not None:
+        if decode_speakers is not None and enc_only:
             ch = torch.tensor([decode_speakers[u] for (u, _, _, _, _) in chunk], dtype=torch.int64)
             lens_p = [_t8(n) for n in lens]
             xd = dec(act, ch.to(dev, non_blocking=True), lengths=(lens_p if ragged else None)).permute(0, 2, 1).contiguous()
+        elif not enc_only:
+            # the engines directly (the modules would clone their outputs): x_dec and the generator's rows are read in place
+            ch = torch.tensor([decode_speakers[u] for (u, _, _, _, _) in chunk], dtype=torch.int64).to(dev, non_blocking=True)
+            lens_p = [_t8(n) for n in lens]
+            bits, xr = dec.forward_rows(act, ch, lengths=(lens_p if ragged else None))
+            cg = (ch - shift) if shift else ch                                   # trainer.py:207-213
+            if trainer.g_mode == 'spectrogram':                                  # G(x_dec, c - shift), T = 8 T' frames per sample
+                m = gen.forward(xr, cg, False, lengths=([8 * n for n in lens_p] if ragged else None))
+            else:                                                                # G(enc, c [- shift]) on the decoder's own input
+                m = gen.forward(bits, cg, False, lengths=(lens_p if ragged else None))
+            dst = dsts[ci]
+            if dst.numel() != xr.B * xr.T or m.B * m.T != xr.B * xr.T:
+                raise L.ZsError('conversion chunk %d: %d destination rows for %d output rows' % (ci, dst.numel(), xr.B * xr.T))
+            L.call('zs_gen_scatter', 'ZsGenScatter', torch.cuda.current_stream(dev).cuda_stream, xd=xr.ptr(), ld_xd=xr.ld, m=m.ptr(),
+                   ld_m=m.ld, dst=L.ptr(dst), rows=dst.numel(), amp=L.ptr(q.conv), amp_ld=q.conv.shape[2],
+                   amp_rows=q.conv.shape[0] * q.conv.shape[1], mode=mode, denorm=int(denorm))
         q.chunks.append((chunk, lens))
         q.enc_host.append(_to_host(act.permute(0, 2, 1).contiguous()))
         q.dec_dev.append(xd)
@@ -408,6 +462,41 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
     q.enc_done = torch.cuda.Event()
     q.enc_done.record(torch.cuda.current_stream(dev))
     return q
+
+
+def _plan_scatter(items, chunks, n_utt, denorm, dev):
+    """The converted spectrograms' buffer [n_utt, T_max, 513] and, per chunk, the destination row of each of its output rows
+    (b*T + t -> u*T_max + frame, -1 past a fragment's 8 T' rows): utterance u's frames are its fragments' rows in fragment order.
+    The padding rows (frames past an utterance's length) are filled here, once: what the per-utterance path gives them,
+    (denorm of) zero.  All destination tables go to the device in one copy."""
+    out_rows = {}
+    for (u, k, a, b, _) in items:
+        out_rows[(u, k)] = 8 * _t8(b - a)
+    start, ulens = {}, [0] * n_utt
+    for (u, k) in sorted(out_rows):
+        start[(u, k)] = ulens[u]
+        ulens[u] += out_rows[(u, k)]
+    Tm = max(ulens)
+    tables = []
+    for chunk, _ in chunks:
+        T = 8 * _t8(max(b - a for (_, _, a, b, _) in chunk))
+        d = np.full((len(chunk), T), -1, dtype=np.int32)
+        for i, (u, k, _, _, _) in enumerate(chunk):
+            n = out_rows[(u, k)]
+            d[i, :n] = np.arange(u * Tm + start[(u, k)], u * Tm + start[(u, k)] + n, dtype=np.int32)
+        tables.append(d.reshape(-1))
+    pad = np.concatenate([np.arange(u * Tm + ulens[u], (u + 1) * Tm, dtype=np.int32) for u in range(n_utt)])
+    sizes = [len(t) for t in tables] + [len(pad)]
+    if n_utt * Tm >= 2 ** 31:
+        raise ValueError('converted batch too large: %d rows' % (n_utt * Tm))
+    dev_t = torch.from_numpy(np.concatenate(tables + [pad])).to(dev, non_blocking=True)
+    parts = list(torch.split(dev_t, sizes))
+    conv = torch.empty(n_utt, Tm, 513, dtype=torch.float32, device=dev)
+    if len(pad):
+        zero = torch.zeros(513, dtype=torch.float32, device=dev)
+        L.call('zs_gen_scatter', 'ZsGenScatter', torch.cuda.current_stream(dev).cuda_stream, xd=L.ptr(zero), ld_xd=0, dst=L.ptr(parts[-1]),
+               rows=len(pad), amp=L.ptr(conv), amp_ld=513, amp_rows=n_utt * Tm, mode=0, denorm=int(denorm))
+    return conv, ulens, parts[:-1]
 
 
 def _assemble(q, want_dec):
@@ -439,7 +528,7 @@ def _assemble(q, want_dec):
     return encs, decs
 
 
-def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, max_batch=256, to_host=True):
+def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, max_batch=256, to_host=True, enc_only=True):
     """Batched encode()/convert() for many utterances: the same fragments the reference would send through the network one by
     one (convert.py:151-165), as a few large batches on the GPU.
     specs: list of [T_i, 513] arrays (host arrays, or torch tensors already on the device).  decode_speakers: optional list of
@@ -447,15 +536,22 @@ def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, m
     noise of the encoder mode's shape ([n, T', E, 2] multilabel_binary, [n, T', E] one_hot, [n, T', E, E] binary; None for
     continues, which draws none) or None makes the stochastic discretiser reproducible (called once per batch; T' = encoded frames of the
     longest member).  Returns (encodings list, decoded list or None); to_host=False leaves the decoded spectrograms on the
-    device (torch tensors [T_out, 513]) for spectrogram2wav_batch."""
-    q = _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host=to_host)
+    device (torch tensors [T_out, 513]) for spectrogram2wav_batch.
+    enc_only=False: convert() with the stage-2 generator (trainer.py:198-213) -- the decoded list holds the CONVERTED spectrograms
+    (normalised, as test_step returns them), bit for bit the concatenated per-fragment test_step outputs given the same noise."""
+    q = _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host=to_host, enc_only=enc_only)
+    conv_h = _to_host(q.conv) if (q.conv is not None and to_host) else None
     torch.cuda.current_stream(q.dev).synchronize()
     from . import layers
     layers.check_status(q.dev)                                # synchronised: a timed-out GRU pass raises here
-    return _assemble(q, None if decode_speakers is None else ('host' if to_host else 'device'))
+    if enc_only:
+        return _assemble(q, None if decode_speakers is None else ('host' if to_host else 'device'))
+    encs, _ = _assemble(q, None)
+    conv = conv_h.numpy() if to_host else q.conv
+    return encs, [conv[u, :n] for u, n in enumerate(q.ulens)]
 
 
-def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, noise_fn=None, max_batch=256, defer=False):
+def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, noise_fn=None, max_batch=256, defer=False, enc_only=True):
     """test_encode + convert(enc_only) + spectrogram2wav for a batch of utterances as ONE enqueue (convert.py:151-165, 55-62):
     the fragments' Encoder / Decoder launches, the gather of the decoded fragments into the vocoder's padded [n, T_max, 513]
     input (one index kernel on the device), de-normalisation, the Griffin-Lim loop, de-emphasis, the trim statistics and the
@@ -463,7 +559,12 @@ def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, 
     Returns (encodings list, wav list) -- the same values as encode_batch(...) followed by spectrogram2wav_batch(...).
     defer=True returns a function instead that waits for THIS batch (an event behind its last copy) and returns that pair: a
     serving loop enqueues batch i + 1 before it calls the function of batch i, so the host-side assembly and the D2H copies of one
-    batch run under the GPU work of the next."""
+    batch run under the GPU work of the next.
+    enc_only=False: convert() with the stage-2 generator; zs_gen_scatter writes each chunk's de-normalised converted rows straight
+    into the vocoder's input, so the gather / combine / de-normalisation passes below do not exist on that path."""
+    if not enc_only:
+        q = _enqueue_encode(specs, trainer, seg_len, speakers, noise_fn, max_batch, dec_to_host=False, enc_only=False, denorm=True)
+        return _finish_resynth(q, _enqueue_vocoder(q.conv, q.ulens, n_iter, do_trim, q.dev, amplitudes=True), defer)
     q = _enqueue_encode(specs, trainer, seg_len, speakers, noise_fn, max_batch, dec_to_host=False)
     dev = q.dev
     # row table of all decoded fragments + a zero row; utterance u's frames are its fragments' rows in order
@@ -489,15 +590,17 @@ def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, 
             at += n
     table = torch.cat([x.reshape(-1, x.shape[2]) for x in q.dec_dev] + [torch.zeros(1, q.dec_dev[0].shape[2], dtype=q.dec_dev[0].dtype, device=dev)], dim=0)
     t = table[torch.from_numpy(idx).to(dev, non_blocking=True)].float()                               # [n, Tm, 513]
-    fin = _enqueue_vocoder(t, ulens, n_iter, do_trim, dev)
+    return _finish_resynth(q, _enqueue_vocoder(t, ulens, n_iter, do_trim, dev), defer)
 
+
+def _finish_resynth(q, fin, defer):
     def finish():
         q.enc_done.synchronize()                              # the encodings are on the host; the vocoder is still running
         encs, _ = _assemble(q, None)
         wavs = fin()
         if fin.status:                                        # a persistent GRU pass timed out before this batch's end
             from . import layers
-            layers.check_status(dev)                          # synchronises, clears the word and raises
+            layers.check_status(q.dev)                        # synchronises, clears the word and raises
         return encs, wavs
     return finish if defer else finish()
 
@@ -536,6 +639,78 @@ def test_from_list(trainer, seg_len, synthesis_list, data_path, speaker2id_path,
             convert(trainer, seg_len, src_speaker_spec=f_h5[f"test/{feed['s_id']}/{feed['utt_id']}/lin"][()], src_speaker=feed['s_id'],
                     tar_speaker=feed['t_id'], utt_id=feed['utt_id'], speaker2id=speaker2id, result_dir=dir_path, enc_only=enc_only,
                     save=['wav'])
+
+
+def store_keys(store, prefix):
+    """Names directly under `prefix` of the dataset container: list(f[prefix].keys()) for HDF5, NpzStore.keys(prefix) for .npz."""
+    from .dataloader import NpzStore
+    if isinstance(store, NpzStore):
+        return store.keys(prefix)
+    return sorted(store[prefix].keys())
+
+
+def cross_test_plan(keys, flag, result_dir):
+    """The work list of cross_test (convert.py:268-300): every utterance of every source speaker to every target speaker.
+    keys(prefix) lists the names under a container prefix (store_keys).  Sources: the speakers under test/ (flag 'test') or the
+    S* speakers under train/ (flag 'train'); targets: the V* speakers under train/.  Returns one dict per (source utterance,
+    target) pair, in the reference's loop order, with the spectrogram's key and the two files convert() would write:
+    {result_dir}/{src}_to_{tar}/{tar}_{utt}.wav and .../{src}_{utt}.txt."""
+    if flag == 'test':
+        sources = sorted(keys('test'))
+    elif flag == 'train':
+        sources = [s for s in sorted(keys('train')) if s[0] == 'S']
+    else:
+        raise ValueError("cross_test flag must be 'test' or 'train' (got %r)" % (flag,))
+    targets = [s for s in sorted(keys('train')) if s[0] == 'V']
+    plan = []
+    for src in sources:
+        utts = sorted(keys('%s/%s' % (flag, src)))
+        for tar in targets:
+            if src == tar:
+                raise ValueError('cross_test: speaker %s is both a source and a target' % src)
+            d = os.path.join(result_dir, '%s_to_%s' % (src, tar))
+            for utt in utts:
+                plan.append({'src': src, 'tar': tar, 'utt': utt, 'key': '%s/%s/%s/lin' % (flag, src, utt), 'dir': d,
+                             'wav': os.path.join(d, '%s_%s.wav' % (tar, utt)), 'txt': os.path.join(d, '%s_%s.txt' % (src, utt))})
+    return plan
+
+
+def cross_test(trainer, seg_len, data_path, speaker2id_path, result_dir, enc_only, flag='test', batch=64, n_iter=None):
+    """convert.py:268-300, as the reference means it (its call passes the target in the source speaker's slot and raises
+    TypeError): convert() of every source utterance to every target speaker, with convert()'s default outputs.  Every (utterance,
+    target) pair is an item of its own with its own Gumbel noise; items go through resynth_batch in groups of `batch`, and group
+    i + 1 is enqueued before group i is written (defer=True)."""
+    with open(speaker2id_path, 'r') as f_json:
+        speaker2id = json.load(f_json)
+    with _open_h5(data_path) as f_h5:
+        plan = cross_test_plan(lambda prefix: store_keys(f_h5, prefix), flag, result_dir)
+        n_src = len({it['src'] for it in plan})
+        n_tar = len({it['tar'] for it in plan})
+        print('[Tester] - Testing on the {}ing set...'.format(flag))
+        print('[Tester] - Source speakers: %i, Target speakers: %i, conversions: %i' % (n_src, n_tar, len(plan)))
+        groups = [plan[lo:lo + batch] for lo in range(0, len(plan), batch)]
+        check = [speaker2id[it['tar']] for it in plan]
+        if not enc_only and check:
+            check_gen_targets(trainer, check)                 # before the first group is enqueued
+
+        def write(group, fin):
+            encs, wavs = fin()
+            for it, e, w in zip(group, encs, wavs):
+                os.makedirs(it['dir'], exist_ok=True)
+                write_wav(it['wav'], w, hp.sr)
+                write_encodings(it['txt'], e)
+
+        pending = None
+        for group in groups:
+            specs = [np.asarray(f_h5[it['key']][()], dtype=np.float32) for it in group]
+            fin = resynth_batch(specs, trainer, seg_len, [speaker2id[it['tar']] for it in group], n_iter=n_iter, defer=True,
+                                enc_only=enc_only)
+            if pending is not None:
+                write(*pending)
+            pending = (group, fin)
+        if pending is not None:
+            write(*pending)
+    return plan
 
 
 SINGLE_FILES = {            # convert.py:308-317: the utterances --test_single knows per source speaker

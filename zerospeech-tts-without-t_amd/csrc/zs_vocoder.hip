@@ -172,10 +172,44 @@ __global__ void pre_mel_kernel(const float* amp, const float* basis, float* mel,
   }
 }
 
+// normalised magnitude -> amplitude (convert.py:56-58).  The one place this expression is compiled: gl_denorm_kernel and
+// gen_scatter_kernel both call it, so both produce the same bits for the same input.
+__device__ __forceinline__ float gl_denorm(float x) {
+  const float m = fminf(fmaxf(x, 0.f), 1.f) * 100.f - 100.f + 20.f;         // convert.py:57
+  return powf(10.0f, m * 0.05f);                                             // convert.py:58
+}
+
 __global__ void gl_denorm_kernel(const float* in, float* out, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float m = fminf(fmaxf(in[i], 0.f), 1.f) * 100.f - 100.f + 20.f;   // convert.py:57
-    out[i] = powf(10.0f, m * 0.05f);                                          // convert.py:58
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = gl_denorm(in[i]);
+}
+
+// x + x*m with the product rounded before the add, as torch computes it.  hipcc contracts a + a*b into an FMA by default.
+// __fmul_rn / __fadd_rn do not stop that here: this ROCm defines them as plain '*' and '+' in a header compiled with contraction
+// on.  The pragma leaves both operations without the 'contract' flag, so they stay a v_mul_f32 and a v_add_f32.
+__device__ __forceinline__ float add_mul_rn(float x, float m) {
+#pragma clang fp contract(off)
+  const float p = x * m;
+  return x + p;
+}
+
+// zs_gen_scatter: one wave per source row r = b*T + t, written to row dst[r] (< 0: skipped) of the padded vocoder input.  Lanes
+// stride the 513 columns with dword loads (the row length is odd: no wider aligned access).  The combine uses explicit
+// round-to-nearest operations and no FMA contraction (add_mul_rn): torch rounds the product first.
+__global__ void gen_scatter_kernel(const ZsGenScatter p) {
+  const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (r >= p.rows) return;
+  const int64_t d = p.dst[r];
+  if (d < 0 || d >= p.amp_rows) return;
+  const float* xr = p.xd + r * p.ld_xd;                   // ld_xd == 0: every row reads the same (zero) row
+  const float* mr = p.mode ? p.m + r * p.ld_m : nullptr;
+  float* out = p.amp + d * p.amp_ld;
+  for (int f = threadIdx.x & 63; f < NBIN; f += 64) {
+    const float x = xr[f];
+    float v = x;
+    if (p.mode == 1) v = __fadd_rn(x, mr[f]);
+    else if (p.mode == 2) v = add_mul_rn(x, mr[f]);
+    out[f] = p.denorm ? gl_denorm(v) : v;
   }
 }
 
@@ -218,4 +252,16 @@ extern "C" int zs_gl_denormalize(const float* mag_norm, float* mag_amp, int64_t 
   int64_t nb = (n + 255) / 256; if (nb > 4096) nb = 4096;
   hipLaunchKernelGGL(gl_denorm_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, mag_norm, mag_amp, n);
   return zs_check_launch("zs_gl_denormalize");
+}
+
+extern "C" int zs_gen_scatter(const ZsGenScatter* p, void* stream) {
+  ZS_REQUIRE(p && p->xd && p->dst && p->amp && p->rows > 0 && p->amp_rows > 0, "zs_gen_scatter: null operand or empty");
+  ZS_REQUIRE(p->ld_xd >= NBIN || p->ld_xd == 0, "zs_gen_scatter: ld_xd must be >= 513 (or 0: one broadcast row)");
+  ZS_REQUIRE(p->amp_ld >= NBIN, "zs_gen_scatter: amp_ld must be >= 513");
+  ZS_REQUIRE(p->mode >= 0 && p->mode <= 2, "zs_gen_scatter: mode must be 0 (xd), 1 (xd + m) or 2 (xd + xd*m)");
+  ZS_REQUIRE(p->mode == 0 || (p->m && p->ld_m >= NBIN), "zs_gen_scatter: modes 1 and 2 need m with ld_m >= 513");
+  ZS_REQUIRE(p->rows <= (int64_t)4 * 0x7fffffff, "zs_gen_scatter: too many rows");
+  const int64_t nb = (p->rows + 3) / 4;                   // 4 waves (rows) per 256-thread workgroup
+  hipLaunchKernelGGL(gen_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, *p);
+  return zs_check_launch("zs_gen_scatter");
 }

@@ -243,6 +243,13 @@ class Decoder(ZsModule):
     def forward(self, x, c, lengths=None):
         """x: enc_act [B, c_in, T'] (fp32);  c: int64 [B]  ->  [B, c_out, 8T'].
         lengths (eval only): encoded frames per sample of a ragged batch; the first 8 * lengths[b] output frames are valid."""
+        _, xdec = self.forward_rows(x, c, lengths=lengths)
+        return xdec.valid().permute(0, 2, 1).clone()
+
+    def forward_rows(self, x, c, lengths=None):
+        """forward() without the copy out: (bits, x_dec), the input as the engine reads it (Act [B, T', c_in], compute dtype) and
+        the output rows (Act fp32 [B, 8T', c_out]).  Both live in the engine's buffers, which the next forward of the same shape
+        overwrites."""
         eng = self._engine()
         ctx = eng.ctx
         xb = x.detach().permute(0, 2, 1).contiguous().float()
@@ -251,8 +258,7 @@ class Decoder(ZsModule):
         L.call('zs_cast_rows', 'ZsCastRows', ctx.stream, dtype=ctx.dt, src=L.ptr(xb), ld_src=E, src_f32=1, dst=bits.ptr(),
                ld_dst=bits.ld, dst_f32=0, col_off=0, rows=B * T0, cols=E, fill_cols=bits.ld, act=L.ZS_ACT_NONE)
         cidx = c.detach().to(xb.device, torch.int64).contiguous()
-        xdec = eng.forward(bits, cidx, self.training, lengths=lengths)
-        return xdec.valid().permute(0, 2, 1).clone()
+        return bits, eng.forward(bits, cidx, self.training, lengths=lengths)
 
 
 class Spectrogram_Patcher(ZsModule):
