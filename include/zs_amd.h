@@ -538,6 +538,28 @@ typedef struct {
   int32_t mode, denorm;
 } ZsGenScatter;
 int zs_gen_scatter(const ZsGenScatter* p, void* stream);
+/* zs_frag_gather: the fragments --test_classify sends through the TargetClassifier (convert.py:379-397), out of a batch of
+ * spectrograms, in one launch.  src fp32 [n_utt][T_max][513] (utterance u at src + u * utt_stride, rows of 513 floats: only
+ * 4-byte alignment), table int32 [n_frag][2] = (utt, start):
+ *   dst[f][t][k] = src[utt_f][start_f + t][k]      t < seg_len, k < 513;   dst fp32 [n_frag][seg_len][513], contiguous
+ * An entry outside 0 <= utt < n_utt, 0 <= start <= T_max - seg_len writes a zero fragment and reads nothing (the caller plans the
+ * table on the host and checks it there).  No allocation, no synchronisation. */
+typedef struct {
+  const float* src; int64_t utt_stride; int32_t n_utt, T_max;
+  const int32_t* table; int32_t n_frag, seg_len;
+  float* dst;
+} ZsFragGather;
+int zs_frag_gather(const ZsFragGather* p, void* stream);
+/* zs_tclf_score: the scoring loop of target_classify (convert.py:400-413) on the device.  logits fp32 [n_frag][ld] (3 valid columns),
+ * target int32 [n_frag] (0 V001, 1 V002, 2 'None', -1 any other speaker: never correct):
+ *   pred[f] = argmax_j logits[f][j] (first maximum, NaN as the maximum: numpy's rule; pred may be null)
+ *   *correct += #{f : pred[f] == target[f]},   *count += n_frag          (device int32 counters, added with atomics) */
+typedef struct {
+  const float* logits; int64_t ld;
+  const int32_t* target; int32_t n_frag;
+  int32_t* pred; int32_t* correct; int32_t* count;
+} ZsTclfScore;
+int zs_tclf_score(const ZsTclfScore* p, void* stream);
 int zs_gl_deemphasis(float* wav, int64_t wav_ld, const int32_t* lengths, int32_t n_utt, float coef, void* stream);
 /* zs_gl_frame_mse: the frame statistics of librosa.effects.trim (convert.py:61; librosa's rms on the centred, reflect-padded
  * signal): mse[u][f] = mean_{i < frame_length} y_u[reflect(f*hop + i - frame_length/2)]^2, f <= L_u / hop, L_u = 200 *

@@ -6,11 +6,13 @@
   python main.py --test --enc_only | --test_encode        (needs the preprocessed HDF5 + a checkpoint)
   python main.py --test_single --s_speaker S015 --t_speaker V002 [--enc_only]      (one wav -> result.wav + result.txt)
   python main.py --cross_test [--enc_only]                 (every test utterance to every V* speaker, batched)
+  python main.py --train_c [--load_model] [--synthetic]    (the target speaker classifier, mode t_classify)
+  python main.py --test_classify --load_tclf_model_name CKPT   (scores the wavs --test wrote; hps load_model_list must name
+                                                           target_classifier)
 
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
-(--train_al, --train_c, --train_t,
---test_classify, --encode, --test_asr) are not part of this build and exit with a clear error.
+(--train_al, --train_t, --encode, --test_asr) are not part of this build and exit with a clear error.
 """
 import argparse
 import os
@@ -19,13 +21,13 @@ import sys
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-OUT_OF_SCOPE = ['train_al', 'train_c', 'train_t', 'test_asr', 'test_classify', 'encode']
+OUT_OF_SCOPE = ['train_al', 'train_t', 'test_asr', 'encode']
 
 
 def build_parser():
     p = argparse.ArgumentParser(description='zerospeech_project (MI355X autoencoder hot path)')
-    for flag in ['preprocess', 'train', 'train_ae', 'train_p', 'train_tgat', 'test', 'cross_test', 'test_encode', 'test_single', 'load_model',
-                 'enc_only', 'remake', 'synthetic'] + OUT_OF_SCOPE:
+    for flag in ['preprocess', 'train', 'train_ae', 'train_p', 'train_tgat', 'train_c', 'test', 'cross_test', 'test_encode', 'test_single',
+                 'test_classify', 'load_model', 'enc_only', 'remake', 'synthetic'] + OUT_OF_SCOPE:
         p.add_argument('--' + flag, default=False, action='store_true')
     p.add_argument('--flag', type=str, default='train')
     p.add_argument('--g_mode', default='set_from_hps',
@@ -51,6 +53,7 @@ def build_parser():
     p.add_argument('--load_train_model_name', type=str, default='model.pth-ae-424000')
     p.add_argument('--load_test_model_name', type=str, default='model.pth-s2-150000')
     p.add_argument('--ckpt_pth', type=str, default=None)
+    p.add_argument('--load_tclf_model_name', type=str, default=None)     # main.py:79: a path, used as given
     p.add_argument('--s_speaker', type=str, default='S015')
     p.add_argument('--t_speaker', type=str, default='V002')
     return p
@@ -86,7 +89,7 @@ def main(argv=None):
     if bad:
         raise NotImplementedError('--%s is outside the stage-1 autoencoder hot path this build covers' % bad[0])
     from zs_amd import parallel
-    from zs_amd.convert import cross_test, get_trainer, test_encode, test_from_list, test_single
+    from zs_amd.convert import cross_test, get_trainer, target_classify, test_encode, test_from_list, test_single
     from zs_amd.dataloader import DataLoader, Dataset, SyntheticDataset
     from zs_amd.trainer import Trainer
 
@@ -96,7 +99,7 @@ def main(argv=None):
                    args.index_target_path, args.speaker2id_path, seg_len=hps.seg_len, n_samples=hps.n_samples, dset=args.flag,
                    remake=args.remake)
 
-    if args.train or args.train_ae or args.train_p or args.train_tgat:                   # main.py:129-162
+    if args.train or args.train_ae or args.train_p or args.train_tgat or args.train_c:   # main.py:129-171
         rank, world, _ = parallel.init_from_env()
         n_syn = max(4 * hps.batch_size * world, 64)
         if args.synthetic:
@@ -122,15 +125,18 @@ def main(argv=None):
             trainer.add_duo_loader(source_loader, target_loader)
             trainer.train(model_path, args.flag, mode='patchGAN', target_guided=args.train_tgat)     # stage 2
             trainer.reset_keep()
+        if args.train_c:                                  # main.py:165-167 (--train keeps the stages above)
+            trainer.train(model_path, args.flag, mode='t_classify')                      # the target speaker classifier
+            trainer.reset_keep()
         if args.train and parallel.rank() == 0:
             # reference main.py:163-173 goes on to the autolocker, t_classify and Tacotron stages: outside the path this build covers
             print("[Runner] - --train ran the pretrain_AE and patchGAN stages; the reference's autolocker / t_classify / Tacotron "
                   'stages are not part of this build and were skipped')
 
-    if args.test or args.cross_test or args.test_encode or args.test_single:
+    if args.test or args.cross_test or args.test_encode or args.test_single or args.test_classify:
         os.makedirs(args.result_dir, exist_ok=True)
         model_path = args.ckpt_pth if args.ckpt_pth is not None else os.path.join(args.ckpt_dir, args.load_test_model_name)
-        trainer = get_trainer(args.hps_path, model_path, args.g_mode, args.enc_mode, None)
+        trainer = get_trainer(args.hps_path, model_path, args.g_mode, args.enc_mode, args.load_tclf_model_name)
         result_dir = os.path.join(args.result_dir, args.sub_result_dir)
         os.makedirs(result_dir, exist_ok=True)
         if args.test:
@@ -141,6 +147,8 @@ def main(argv=None):
             test_single(trainer, hps.seg_len, args.speaker2id_path, args.result_dir, args.enc_only, args.s_speaker, args.t_speaker)
         if args.test_encode:
             test_encode(trainer, hps.seg_len, args.test_path, args.dataset_path, result_dir, flag='test')
+        if args.test_classify:                            # main.py:196-199
+            target_classify(trainer, hps.seg_len, args.synthesis_list, result_dir, flag='test')
 
 
 if __name__ == '__main__':

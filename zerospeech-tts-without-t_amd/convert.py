@@ -754,3 +754,109 @@ def test_encode(trainer, seg_len, test_path, data_path, result_dir, flag='test')
         for feed in feeds:
             encode(f_h5[f"test/{feed['s_id']}/{feed['utt_id']}/lin"][()], trainer, seg_len, s_speaker=feed['s_id'],
                    utt_id=feed['utt_id'], result_dir=dir_path)
+
+
+# ---------------------------------------------------------------------------------------------------
+# target speaker classification (convert.py:364-414), batched
+# ---------------------------------------------------------------------------------------------------
+
+TCLF_SPEAKERS = ('V001', 'V002', 'None')           # the TargetClassifier's argmax 0 / 1 / 2 (convert.py:401-407)
+
+
+def tclf_plan(frames, seg_len):
+    """The fragments target_classify scores, as [(utterance, start)]: each is spec[start:start + seg_len] (convert.py:379-395).
+    An utterance shorter than seg_len is zero-padded to seg_len first, so, by the `spec[idx:-1]` tail rule, any utterance of
+    seg_len frames or fewer raises RuntimeError (as in the reference); the rows a fragment reads are all real frames."""
+    plan = []
+    for u, n in enumerate(frames):
+        for start, _ in fragments(max(int(n), seg_len), seg_len):
+            plan.append((u, start))
+    return plan
+
+
+def tclf_targets(speakers):
+    """Target class per speaker name for zs_tclf_score: V001 0, V002 1, 'None' 2 (the name the reference compares its third class
+    with), anything else -1 (never correct)."""
+    return np.array([TCLF_SPEAKERS.index(s) if s in TCLF_SPEAKERS else -1 for s in speakers], dtype=np.int32)
+
+
+def tclf_predict(logits):
+    """The reference's per-fragment decision on host logits [n, 3]: numpy argmax (ties to the first index) -> speaker name."""
+    return [TCLF_SPEAKERS[int(np.argmax(l))] for l in np.asarray(logits)]
+
+
+def classify_batch(specs, trainer, seg_len, max_batch=256):
+    """TargetClassifier eval-mode logits of every fragment of a batch of utterances, on the device, with no host synchronisation.
+    specs: a list of normalised magnitude spectrograms [T_i, 513] (host arrays or torch tensors), or the pair (mag [n, T_max, 513]
+    on the trainer's device, frames [n]) that preprocess.get_spectrograms_device returns.  One zs_frag_gather launch copies every
+    fragment of tclf_plan into a contiguous [n_frag, seg_len, 513] batch, then the classifier runs on chunks of at most max_batch.
+    Returns (logits fp32 [n_frag, 3] on the device, plan [(utterance, start)])."""
+    dev = trainer.device
+    if isinstance(specs, tuple):
+        mag, frames = specs
+        frames = [int(t) for t in frames]
+        if not (torch.is_tensor(mag) and mag.device == dev and mag.dtype == torch.float32 and mag.dim() == 3 and mag.shape[2] == 513):
+            raise ValueError('classify_batch: (mag, frames) needs mag fp32 [n, T_max, 513] on %s' % dev)
+        if len(frames) != mag.shape[0] or max(frames) > mag.shape[1]:
+            raise ValueError('classify_batch: frames do not fit mag %s' % (tuple(mag.shape),))
+        src, n_utt, T_max = mag.contiguous(), int(mag.shape[0]), int(mag.shape[1])
+        plan = tclf_plan(frames, seg_len)
+        table = [(u, s) for u, s in plan]
+    else:
+        frames = [int(s.shape[0]) for s in specs]
+        if any(int(s.shape[1]) != 513 for s in specs):
+            raise ValueError('classify_batch: spectrograms must have 513 bins')
+        plan = tclf_plan(frames, seg_len)
+        src, offs = _stage_rows(specs, dev)            # every utterance back to back: one 'utterance' of sum(T_i) + 1 rows
+        n_utt, T_max = 1, int(src.shape[0])
+        table = [(0, int(offs[u]) + s) for u, s in plan]
+    n_frag = len(plan)
+    clf = trainer.TargetClassifier
+    clf.eval()
+    eng = clf._engine()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    tab = torch.tensor(table, dtype=torch.int32).reshape(n_frag, 2).pin_memory().to(dev, non_blocking=True)
+    frags = torch.empty(n_frag, seg_len, 513, dtype=torch.float32, device=dev)
+    L.call('zs_frag_gather', 'ZsFragGather', st, src=L.ptr(src), utt_stride=T_max * 513, n_utt=n_utt, T_max=T_max, table=L.ptr(tab),
+           n_frag=n_frag, seg_len=seg_len, dst=L.ptr(frags))
+    out = torch.empty(n_frag, clf.n_class, dtype=torch.float32, device=dev)
+    for lo in range(0, n_frag, max_batch):
+        hi = min(n_frag, lo + max_batch)
+        _, logits = eng.forward(frags[lo:hi], 'tclf_eval', False, classify=True, need_val=False)
+        out[lo:hi].copy_(logits)
+    return out, plan
+
+
+def target_classify(trainer, seg_len, synthesis_list, result_dir, flag='test', max_batch=256):
+    """convert.py:364-414: the accuracy of the TargetClassifier on the wavs --test wrote, {result_dir}/{flag}/{tar}_{utt}.wav for
+    each line of the synthesis list, over every fragment of every utterance (V001 / V002 / 'None' against the target speaker).
+    All wavs go through one zs_pre_spectrogram batch, the fragments through classify_batch, the scoring through zs_tclf_score;
+    the only host synchronisation is the read of the two counts at the end.  Prints and returns the accuracy."""
+    from .preprocess import get_spectrograms_device, load_wav
+    dir_path = os.path.join(result_dir, f'{flag}/')
+    with open(synthesis_list, 'r') as f:
+        lines = [l for l in f.readlines() if l.strip()]
+    wavs, tars = [], []
+    for line in lines:
+        line = line.split('\n')[0].split(' ')
+        utt_id = line[0].split('/')[1].split('_')[1]
+        tar_speaker = line[1]
+        wavs.append(load_wav(os.path.join(dir_path, f'{tar_speaker}_{utt_id}.wav')))
+        tars.append(tar_speaker)
+    if not getattr(trainer, 'tclf_loaded', False):
+        print('[Converter] - warning: no target_classifier was loaded (hps load_model_list does not name it, or loading failed): '
+              'scoring with untrained weights')
+    if not wavs:
+        print('Classification Acc: {:.3f}'.format(float('nan')))
+        return float('nan')
+    dev = trainer.device
+    mag, frames = get_spectrograms_device(wavs, device=dev)
+    logits, plan = classify_batch((mag, frames), trainer, seg_len, max_batch=max_batch)
+    target = torch.from_numpy(tclf_targets([tars[u] for u, _ in plan])).pin_memory().to(dev, non_blocking=True)
+    counts = torch.zeros(2, dtype=torch.int32, device=dev)
+    L.call('zs_tclf_score', 'ZsTclfScore', torch.cuda.current_stream(dev).cuda_stream, logits=L.ptr(logits), ld=logits.stride(0),
+           target=L.ptr(target), n_frag=len(plan), correct=L.ptr(counts), count=L.ptr(counts, 1))
+    correct, count = counts.cpu().tolist()                    # the one synchronisation
+    acc = correct / float(count)
+    print('Classification Acc: {:.3f}'.format(acc))
+    return acc

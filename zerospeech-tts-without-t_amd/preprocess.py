@@ -49,11 +49,21 @@ def mel_basis(sr=None, n_fft=None, n_mels=None):
 _BASIS = {}
 
 
-def get_spectrograms_batch(wavs, do_trim=True, device=None):
-    """wavs: list of 1-D float arrays at hp.sr.  Returns a list of (mel [T, 80], mag [T, 513]) float32 NumPy pairs."""
+def _device_of(device):
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     if dev.type != 'cuda':
         raise L.ZsError('zs_amd.preprocess runs on an MI355X only (there is no CPU path)')
+    return dev
+
+
+def _pinned(a, dev):
+    """Host array -> device tensor through a pinned staging buffer, asynchronously (a pageable .to() waits for the stream)."""
+    return torch.from_numpy(a).pin_memory().to(dev, non_blocking=True)
+
+
+def _enqueue_spectrograms(wavs, do_trim, dev, with_amp):
+    """Trim on the host (preprocess.py:238), then ONE zs_pre_spectrogram launch over the zero-padded batch, enqueued without a
+    host synchronisation.  Returns (mag fp32 [n, T_max, 513], amp (the same shape) or None, samples int32 [n] host array)."""
     ys = []
     for w in wavs:
         y = np.asarray(w, dtype=np.float32)
@@ -69,17 +79,26 @@ def get_spectrograms_batch(wavs, do_trim=True, device=None):
     host = np.zeros((n, ld), dtype=np.float32)
     for i, y in enumerate(ys):
         host[i, :len(y)] = y
-    wav = torch.from_numpy(host).to(dev)
-    ns = torch.from_numpy(lens).to(dev)
+    wav = _pinned(host, dev)
+    ns = _pinned(lens, dev)
     mag = torch.zeros(n, T_max, 513, dtype=torch.float32, device=dev)
-    amp = torch.zeros(n, T_max, 513, dtype=torch.float32, device=dev)
+    amp = torch.zeros(n, T_max, 513, dtype=torch.float32, device=dev) if with_amp else None
+    st = torch.cuda.current_stream(dev).cuda_stream
+    L.call('zs_pre_spectrogram', 'ZsPreSpec', st, wav=L.ptr(wav), wav_ld=ld, n_samples=L.ptr(ns), n_utt=n, T_max=T_max,
+           preemph=hp.preemphasis, ref_db=float(hp.ref_db), max_db=float(hp.max_db), mag=L.ptr(mag), mag_ld=513, amp=L.ptr(amp))
+    return mag, amp, lens
+
+
+def get_spectrograms_batch(wavs, do_trim=True, device=None):
+    """wavs: list of 1-D float arrays at hp.sr.  Returns a list of (mel [T, 80], mag [T, 513]) float32 NumPy pairs."""
+    dev = _device_of(device)
+    mag, amp, lens = _enqueue_spectrograms(wavs, do_trim, dev, True)
+    n, T_max = mag.shape[0], mag.shape[1]
     mel = torch.zeros(n, T_max, hp.n_mels, dtype=torch.float32, device=dev)
     key = (dev.index, hp.sr, hp.n_fft, hp.n_mels)
     if key not in _BASIS:
         _BASIS[key] = torch.from_numpy(mel_basis()).to(dev)
     st = torch.cuda.current_stream(dev).cuda_stream
-    L.call('zs_pre_spectrogram', 'ZsPreSpec', st, wav=L.ptr(wav), wav_ld=ld, n_samples=L.ptr(ns), n_utt=n, T_max=T_max,
-           preemph=hp.preemphasis, ref_db=float(hp.ref_db), max_db=float(hp.max_db), mag=L.ptr(mag), mag_ld=513, amp=L.ptr(amp))
     fn = L.lib().zs_pre_mel
     L.check(fn(L.ptr(amp), L.ptr(_BASIS[key]), L.ptr(mel), n * T_max, hp.n_mels, float(hp.ref_db), float(hp.max_db), st), 'zs_pre_mel')
     mag_h, mel_h = mag.cpu().numpy(), mel.cpu().numpy()
@@ -88,6 +107,13 @@ def get_spectrograms_batch(wavs, do_trim=True, device=None):
         T = 1 + int(lens[i]) // hp.hop_length
         out.append((mel_h[i, :T].copy(), mag_h[i, :T].copy()))
     return out
+
+
+def get_spectrograms_device(wavs, do_trim=True, device=None):
+    """The magnitudes of get_spectrograms_batch left on the device: (mag fp32 [n, T_max, 513] on `device`, frames int64 [n] host
+    array).  Utterance i is mag[i, :frames[i]]; the rows behind it are zeros.  No mel, no host copy, no synchronisation."""
+    mag, _, lens = _enqueue_spectrograms(wavs, do_trim, _device_of(device), False)
+    return mag, 1 + lens.astype(np.int64) // hp.hop_length
 
 
 def load_wav(sound_file):

@@ -21,8 +21,10 @@ from . import layers
 from .layers import Act, join_side
 from .model import Decoder, Encoder, SpeakerClassifier, Spectrogram_Patcher
 from .patch import PatchDiscriminator, TargetClassifier
-from .stage2 import PatchGANStep
+from .stage2 import NetOpt, PatchGANStep
 from .utils import Logger
+
+TCLF_CLASSES = 3                       # TargetClassifier(n_class=3): V001, V002, 'None' (trainer.py:97, convert.py:402-407)
 
 
 class AEStep(object):
@@ -573,6 +575,60 @@ class ClfStep(object):
         return ae._loss, self.loss, self.correct
 
 
+def tclf_labels(c, n_speakers, n_target_speakers, g_mode):
+    """The t_classify targets (trainer.py:617-624) from HOST speaker ids: c[c < 100] = 102, then c - shift_c with
+    shift_c = n_speakers - n_target_speakers (100 -> V001 = 0, 101 -> V002 = 1, every other speaker -> 'None' = 2 for the
+    english / surprise sets).  Raises ValueError where the reference could not run: g_mode 'naive' (it defines no shift_c) and a
+    target outside [0, 3) (nn.CrossEntropyLoss would fail; here it would index past the logits on the GPU)."""
+    if g_mode == 'naive':
+        raise ValueError("t_classify needs shift_c = n_speakers - n_target_speakers, which the reference defines only for a g_mode "
+                         "other than 'naive'")
+    c = torch.as_tensor(c).long().clone()
+    c[c < 100] = 102
+    y = c - int(n_speakers - n_target_speakers)
+    if y.numel() and (int(y.min()) < 0 or int(y.max()) >= TCLF_CLASSES):
+        raise ValueError('t_classify target %d outside [0, %d): relabelled speaker ids (c < 100 -> 102) minus shift_c = %d must be '
+                         '100, 101 or 102' % (int(y.min()) if int(y.min()) < 0 else int(y.max()), TCLF_CLASSES,
+                                                 int(n_speakers - n_target_speakers)))
+    return y
+
+
+class TclfStep(object):
+    """One --train_c iteration (trainer.py:615-628): TargetClassifier forward in train mode (Dropout2d p = dp), CE on the relabelled
+    targets, backward to the parameters only, clip_grad_norm(max_grad_norm) + Adam(lr, betas (0.5, 0.9)).  The relabel runs on
+    the device (no host sync); the targets are range-checked on the host by tclf_labels before a batch is copied over."""
+
+    def __init__(self, classifier, lr, max_grad_norm, shift):
+        self.clf, self.max_grad_norm, self.shift = classifier, float(max_grad_norm), int(shift)
+        self.opt = NetOpt(classifier, lr, betas=(0.5, 0.9))
+        self.device = classifier.flat_params()[0].device
+        self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.correct = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._dl = None
+
+    def step(self, x_btf, c, masks=None, update=True):
+        """x_btf fp32 [B, T, 513], c int64 [B] raw speaker ids on the device.  masks: optional six [B, C] Dropout2d keep masks.
+        Returns (loss, n_correct) device scalars; parameter gradients are left in the classifier's flat gradient buffer."""
+        clf = self.clf
+        clf.train()
+        eng = clf._engine()
+        B = x_btf.shape[0]
+        y = c.masked_fill(c < 100, 102) - self.shift                           # c[c < 100] = 102; c - shift_c
+        eng.zero_grads()
+        _, logits = eng.forward(x_btf.contiguous(), 'tclf', True, masks=masks, classify=True, need_val=False)
+        if self._dl is None or self._dl.shape[0] != B:
+            self._dl = torch.zeros(B, clf.n_class, dtype=torch.float32, device=self.device)
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        L.call('zs_softmax_ce', 'ZsSoftmaxCE', st, logits=L.ptr(logits), ld=logits.stride(0), target=L.ptr(y), B=B, n_class=clf.n_class,
+               loss_out=L.ptr(self.loss), dlogits=L.ptr(self._dl), ldg=clf.n_class, grad_scale=1.0,
+               correct_out=L.ptr(self.correct))                                 # cal_loss / cal_acc (trainer.py:297-313)
+        eng.backward('tclf', dlogits=self._dl, need_dx=False, param_grads=True)
+        eng.flush_grads()
+        if update:
+            self.opt.step(self.max_grad_norm)
+        return self.loss, self.correct
+
+
 class Trainer(object):
     def __init__(self, hps, data_loader, g_mode, enc_mode, log_dir='./log/', dtype=None, device=None):
         self.hps = hps
@@ -630,6 +686,8 @@ class Trainer(object):
         self.s2 = None                      # PatchGANStep, built on first use (its optimizer state is 2 x 53 M floats)
         self.source_loader = self.target_loader = None
         self.testing_shift_c = None
+        self.tclf = None                    # TclfStep, built on first use (--train_c)
+        self.tclf_loaded = False            # load_model restored target_classifier
         self.sync_params()
 
     def nets(self):
@@ -694,6 +752,8 @@ class Trainer(object):
                         tag = 'target_classifier_another'
                     else:
                         net.load_state_dict(strip(all_model[key]))
+                    if key == 'target_classifier':
+                        self.tclf_loaded = True
                     if verbose:
                         print('[%s], ' % tag, end='')
                 except Exception as e:                                   # reference: bare except, prints [x - X]
@@ -745,6 +805,15 @@ class Trainer(object):
         layers.check_status(self.device)
         return out
 
+    def classify(self, x):
+        """trainer.py:231-235: x [B, T, 513] -> the TargetClassifier's eval-mode logits [B, 3] (numpy)."""
+        self.set_eval()
+        clf = self.TargetClassifier
+        clf.eval()
+        x = torch.as_tensor(x).to(self.device, torch.float32).contiguous()
+        _, logits = clf._engine().forward(x, 'eval', False, classify=True, need_val=False)
+        return logits.cpu().numpy()
+
     # ---- training pieces (trainer.py:238-254) --------------------------------------------------
     def permute_data(self, data, load_mel=False):
         C = data[0].to(self.device, non_blocking=True)
@@ -780,6 +849,24 @@ class Trainer(object):
             self._duo = (DevicePrefetcher(self.source_loader, self.device, n_speakers=self.hps.n_speakers),
                          DevicePrefetcher(self.target_loader, self.device, n_speakers=self.hps.n_speakers, check=self.stage2().check_targets))
         return next(self._duo[0]), next(self._duo[1])
+
+    def tclf_labels(self, c_host):
+        """t_classify targets of a HOST batch (tclf_labels above with this trainer's hps / g_mode); raises ValueError."""
+        return tclf_labels(c_host, self.hps.n_speakers, self.hps.n_target_speakers, self.g_mode)
+
+    def tclf_step(self):
+        if self.tclf is None:
+            self.tclf = TclfStep(self.TargetClassifier, self.hps.lr, self.hps.max_grad_norm,
+                                 self.hps.n_speakers - self.hps.n_target_speakers)
+        return self.tclf
+
+    def _tclf_batch(self):
+        """next(data_loader) through a prefetcher whose check range-checks the relabelled targets of every batch on the host
+        (tclf_labels, raising ValueError) before it is copied; the relabel the step uses runs on the device (TclfStep.step)."""
+        if getattr(self, '_tclf_prefetch', None) is None:
+            from .dataloader import DevicePrefetcher
+            self._tclf_prefetch = DevicePrefetcher(self.data_loader, self.device, check=self.tclf_labels)
+        return next(self._tclf_prefetch)
 
     def train(self, model_path, flag='train', mode='train', target_guided=False):
         hps = self.hps
@@ -892,5 +979,28 @@ class Trainer(object):
             layers.check_status(self.device)
             if is_main:
                 print()
+        elif mode == 't_classify':                                                        # trainer.py:613-643
+            if self.g_mode == 'naive':
+                self.tclf_labels(torch.zeros(0, dtype=torch.int64))                        # raises: no shift_c
+            c, x = self._tclf_batch()                                                     # the first batch is checked before any launch
+            step = self.tclf_step()
+            for iteration in range(hps.tclf_iters):
+                if iteration:
+                    c, x = self._tclf_batch()
+                _, corr = step.step(x, c)
+                if (iteration % self.log_every == 0) or (iteration + 1 == hps.tclf_iters):
+                    info = {f'{flag}/acc': corr.item() / float(c.shape[0])}
+                    layers.check_status(self.device)
+                    slot_value = (iteration + 1, hps.tclf_iters) + tuple(info.values())
+                    if is_main:
+                        print('Target Classifier:[%05d/%05d], acc=%.2f' % slot_value, end='\r')
+                        if iteration % 100 == 0:
+                            for tag, value in info.items():
+                                self.logger.scalar_summary(tag, value, iteration + 1)
+                if (iteration + 1) % self.ckpt_every == 0 and is_main:
+                    self.save_model(model_path, 'tclf', iteration + 1)
+            layers.check_status(self.device)
+            if is_main:
+                print()
         else:
-            raise NotImplementedError("mode %r (autolocker / t_classify / Tacotron) is outside the path this build covers" % mode)
+            raise NotImplementedError("mode %r (autolocker / Tacotron) is outside the path this build covers" % mode)
