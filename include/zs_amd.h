@@ -732,6 +732,37 @@ typedef struct {
 int zs_gen_combine_bwd(const ZsGenCombineBwd* p, void* stream);
 int zs_l1_plain(const float* a, const float* b, int64_t n, float scale, float* partial, float* loss_out, float* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The autolocker step (trainer.py:563-611): re-encode x_gen, BCE against the first encode's units, back to the encoder input.
+ * zs_bce_mbv_bwd: torch.nn.BCELoss (mean over N = rows*E) of x = bits (the re-encode's enc_act) against y = target (the first
+ * encode's enc_act, both fp32 [rows][E]), logs clamped at -100: loss_out = sum l / N (double partials per block, fixed grid,
+ * summed in order by one thread: deterministic).  Fused with the MBV straight-through backward (zs_mbv_bwd):
+ *   dx = (x - y) / max(x (1 - x), 1e-12) * grad_scale / N;   dlogits[2e] = dx * y0 (1 - y0) / tau,  dlogits[2e + 1] = -that,
+ * with y0 the re-encode's soft unit-0 probability (ZsMbvFwd.y0).  On hard units (x, y in {0, 1}) loss = 100 * mismatches / N and
+ * dx = +-1e12 / N at the mismatches.  dlogits: compute dtype [rows][ld], columns [2E, fill_cols) zeroed.
+ * partial: >= 1024 doubles.  grad_scale 0 = 1. */
+typedef struct {
+  int32_t dtype;
+  const float* bits; const float* y0; const float* target;
+  int64_t rows; int32_t E; float tau; float grad_scale;
+  void* dlogits; int64_t ld; int32_t fill_cols;
+  double* partial; float* loss_out;
+} ZsBceMbvBwd;
+int zs_bce_mbv_bwd(const ZsBceMbvBwd* p, void* stream);
+
+/* zs_enc_dx_fold: the encoder's input gradient from its two parts.  g: fp32 [B][T + 2 pad][ldg], the data gradient of the
+ * conv bank over its input padded by `pad` rows on both sides; pass_through (optional, compute dtype [B][T][ld_pass]): the gradient of
+ * the concatenation's pass-through columns.  dx fp32 [B][T][ldx] = g[b, t + pad] + (REFLECT: the padding rows that mirror row t)
+ * + pass_through[b, t].  ZERO padding drops the padding rows.  REFLECT needs T > pad. */
+typedef struct {
+  int32_t dtype;
+  const float* g; int64_t ldg;
+  const void* pass_through; int64_t ld_pass;
+  int32_t B, T, C, pad, pad_mode;
+  float* dx; int64_t ldx;
+} ZsEncDxFold;
+int zs_enc_dx_fold(const ZsEncDxFold* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,21 +58,28 @@ class EncoderEngine(object):
             [self.linear]
         self.ncat = 7 * c_h1 + c_in
         self.tape = None
+        self.tapes = {}
+        self.bank_d = None            # the bank's data-gradient operand (backward_input), packed on first use after pack()
 
     def pack(self):
         with L.pack_batch(self.ctx.stream):
             for l in self.layers:
                 l.pack()
             self.gru.pack()
+            if self.bank_d is not None:
+                self._pack_bank_d()
 
     # ------------------------------------------------------------------------------------------
-    def forward(self, x, training, noise=None, noise_kind=2, seed=0, drop_masks=None, seed_ptr=None, lengths=None):
+    def forward(self, x, training, noise=None, noise_kind=2, seed=0, drop_masks=None, seed_ptr=None, lengths=None, tape=None):
         """x: fp32 [B, T, c_in] contiguous on device.  Returns (bits Act [B,T',E] (T dtype, feeds the decoder),
         bits_f32 [B,T',E], logits_f32 [B,T',ld] with n_lin valid columns).  noise (Gumbel if noise_kind 0, uniform if 1): fp32
         [B,T',E,2] (multilabel_binary), [B,T',E] (one_hot), [B,T',E,E] (binary); continues takes none.
         lengths: host int sequence [B], frames per sample (ragged batch, inference only): sample b is computed exactly as if it ran
         alone with T = lengths[b] (padding, InstanceNorm statistics and the reverse GRU at its own end); its first
-        ceil(ceil(ceil(lengths[b]/2)/2)/2) output rows are valid, the rest is garbage."""
+        ceil(ceil(ceil(lengths[b]/2)/2)/2) output rows are valid, the rest is garbage.
+        tape: None, or a key (str) of a tape of its own: the buffers of this pass (outputs and the backward's tape) are then
+        distinct from those of the untagged pass and of other keys, so that e.g. the autolocker's re-encode leaves the first
+        encode's bits alive.  backward* use the tape of the latest forward unless given a key."""
         c, ns = self.ctx, self.ns
         B, T, F = x.shape
         Ls = [None] * 4
@@ -93,8 +100,10 @@ class EncoderEngine(object):
         masks = drop_masks if drop_masks is not None else [None] * 6
         Ts = [T, _half_up(T), _half_up(_half_up(T)), _half_up(_half_up(_half_up(T)))]
         T4 = Ts[3]
-        tag = '_%d_%d_%d' % (self.uid, B, T)
-        tp = {'B': B, 'T': T, 'Ts': Ts, 'training': training, 'seed': seed, 'masks': masks, 'dp': dp, 'seed_ptr': seed_ptr}
+        ksfx = '' if tape is None else '_' + str(tape)
+        tag = '_%d_%d_%d' % (self.uid, B, T) + ksfx
+        tp = {'B': B, 'T': T, 'Ts': Ts, 'training': training, 'seed': seed, 'masks': masks, 'dp': dp, 'seed_ptr': seed_ptr,
+              'tag': tag, 'ksfx': ksfx}
 
         xin = c.act('e_xin' + tag, B, T, F)
         cat = c.act('e_cat' + tag, B, T, self.ncat)
@@ -156,8 +165,9 @@ class EncoderEngine(object):
                    ld=logits.ld, logits_f32=1, noise=(L.ptr(noise) if soft else None), noise_kind=noise_kind, seed=seed,
                    seed_ptr=seed_ptr, rows=B * T4, E=E, tau=0.1, slope=self.ns, bits=bits.ptr(), ld_bits=bits.ld,
                    bits_fill_cols=bits.ld, bits_f32=L.ptr(bits_f32), y=L.ptr(y0), s=L.ptr(s))
-        tp.update(cat2=cat2, gates=gates, y0=y0, s=s, T4=T4, gru_in=a, logits=logits)
+        tp.update(cat2=cat2, gates=gates, y0=y0, s=s, T4=T4, gru_in=a, logits=logits, bits_f32=bits_f32)
         self.tape = tp
+        self.tapes[tape] = tp
         return bits, bits_f32[:B * T4 * E].view(B, T4, E), logits
 
     def _in(self, x, out, tp, k, res_mode, res=None, lengths=None, res_lengths=None):
@@ -166,8 +176,8 @@ class EncoderEngine(object):
         B, T, C = x.B, x.T, x.ld
         mean = rstd = None
         if tp['training']:
-            mean = c.f32('e_mean%d_%d_%d_%d' % (self.uid, k, B, T), B * C)
-            rstd = c.f32('e_rstd%d_%d_%d_%d' % (self.uid, k, B, T), B * C)
+            mean = c.f32('e_mean%d_%d_%d_%d' % (self.uid, k, B, T) + tp['ksfx'], B * C)
+            rstd = c.f32('e_rstd%d_%d_%d_%d' % (self.uid, k, B, T) + tp['ksfx'], B * C)
         m = tp['masks'][k]
         L.call('zs_instnorm_fwd', 'ZsInstNormFwd', c.stream, dtype=c.dt, x=x.ptr(), ldx=x.ld, out=out.ptr(), ldo=out.ld,
                mean=L.ptr(mean), rstd=L.ptr(rstd), B=B, T=T, C=C, eps=EPS_IN, drop_p=tp['dp'], seed=tp['seed'],
@@ -193,15 +203,19 @@ class EncoderEngine(object):
         self.backward_main(dbits, dlogits_extra)
         self.backward_bank()
 
-    def backward_main(self, dbits, dlogits_extra=None):
+    def backward_main(self, dbits, dlogits_extra=None, param_grads=True, tape=None):
         """Everything but the conv bank's seven weight gradients (the last gradients of the step: data parallel training starts
-        the all-reduce of the rest of the encoder before them, trainer.AEStep)."""
-        c, ns, tp = self.ctx, self.ns, self.tape
+        the all-reduce of the rest of the encoder before them, trainer.AEStep).
+        param_grads=False: the data gradients alone (no weight gradient, no gradient buffer written), and conv2's data gradient
+        over all 7*c_h1 + c_in columns of the concatenation; returns that Act (see backward_input)."""
+        c, ns = self.ctx, self.ns
+        tp = self.tape if tape is None else self.tapes[tape]
         assert tp is not None and tp['training']
+        pg = param_grads
         B, T, Ts, T4 = tp['B'], tp['T'], tp['Ts'], tp['T4']
         c1, c2, H, E = self.c1, self.c2, self.H, self.E
         st = c.stream
-        tag = '_%d_%d_%d' % (self.uid, B, T)
+        tag = tp['tag']
         cat2 = tp['cat2']
         dlog = c.act('e_dlog' + tag, B, T4, self.n_lin)
         if dbits is not None:
@@ -218,23 +232,26 @@ class EncoderEngine(object):
                 dlog.t[:B * T4 * dlog.ld].add_(dlogits_extra.t[:B * T4 * dlogits_extra.ld])
         else:
             dlog = dlogits_extra
-        self.linear.wgrad(dlog, cat2)
+        if pg:
+            self.linear.wgrad(dlog, cat2)
         dcat2 = c.act('e_dcat2' + tag, B, T4, cat2.C)
         self.linear.dgrad(dlog, T4, dcat2)
         dgi = c.act('e_dgi' + tag, B, T4, 6 * H)
         dgh = c.act('e_dgh' + tag, B, T4, 6 * H)
         gin = tp['gru_in']
         da = c.act('e_da_d' + tag, B, T4, c2)
-        self.gru.bwd(dcat2, c2, cat2, c2, tp['gates'], gin, dgi, dgh, da, add_src=dcat2)
+        self.gru.bwd(dcat2, c2, cat2, c2, tp['gates'], gin, dgi, dgh, da, add_src=dcat2, param_grads=pg)
         for j in (1, 0):
             la, lb = self.dense[j]
             xin, d1, d2, stt = tp['dense'][j]
             dz2 = c.act('e_dz2%d' % j + tag, B, T4, c2)          # unique per block: read later by the side-stream wgrad
             self._in_bwd(da, d2, stt, dz2, tp)
-            lb.wgrad(dz2, d1)
+            if pg:
+                lb.wgrad(dz2, d1)
             dz1 = c.act('e_dz1%d' % j + tag, B, T4, c2)
             lb.dgrad(dz2, T4, dz1, dact_src=d1, slope=ns)
-            la.wgrad(dz1, xin)
+            if pg:
+                la.wgrad(dz1, xin)
             dn = c.act('e_da_d%d' % j + tag, B, T4, c2)
             la.dgrad(dz1, T4, dn, add_src=da)
             da = dn
@@ -243,12 +260,14 @@ class EncoderEngine(object):
             a, ya, yb, stt = tp['blocks'][i]
             dzb = c.act('e_dzb%d' % i + tag, B, Ts[i + 1], c2)
             self._in_bwd(da, yb, stt, dzb, tp)
-            lb.wgrad(dzb, ya)
+            if pg:
+                lb.wgrad(dzb, ya)
             gp = c.act('e_gp%d' % i + tag, B, Ts[i] + 4, c2)
             lb.dgrad(dzb, Ts[i], gp)
             dza = c.act('e_dza%d' % i + tag, B, Ts[i], c2)
             self._combine(gp, Ts[i], 2, 2, dza, dact=ya)
-            la.wgrad(dza, a)
+            if pg:
+                la.wgrad(dza, a)
             la.dgrad(dza, Ts[i], gp)
             dn = c.act('e_da%d' % i + tag, B, Ts[i], c2)
             self._combine(gp, Ts[i], 2, 2, dn, res_mode=L.ZS_RES_AVGPOOL2, res=da)
@@ -256,12 +275,72 @@ class EncoderEngine(object):
         y2, cat, xin = tp['y2'], tp['cat'], tp['xin']
         dz = c.act('e_dzy2' + tag, B, T, c2)
         self._in_bwd(da, y2, tp['st0'], dz, tp)
-        self.conv2.wgrad(dz, cat)
         dcat = c.act('e_dcat' + tag, B, T, self.ncat)
+        if not pg:
+            # every column: the bank's 7*c_h1 (through its data gradient) and the pass-through ones (the gradient w.r.t. the input)
+            self.conv2.dgrad(dz, T, dcat, dact_src=cat, slope=ns)
+            return dcat
+        self.conv2.wgrad(dz, cat)
         # only the conv bank's 7*c_h1 columns are consumed: the pass-through columns of the concatenation are the gradient w.r.t.
         # the input spectrogram, which the reference computes and drops (utils.py:43-45) -- a third of this GEMM
         self.conv2.dgrad(dz, T, dcat, dact_src=cat, slope=ns, n_cols=7 * c1)
         self._bank = (dcat, xin)
+
+    # ---- gradient w.r.t. the input spectrogram (the autolocker step, zs_amd.stage2.AutolockerStep) ----------------------------
+    # The seven bank convolutions (k = 1..7, pads (k//2, k//2 - 1 + k%2)) are ONE 7-tap convolution over the input padded 3/3 with
+    # the taps outside a kernel's own pad set to zero: every pad fits inside 3/3, and the inner rows of a reflect pad do not depend on
+    # its width.  Their data gradient is then one transposed GEMM (K = 7 taps x 7*c_h1, 28 of the 49 tap blocks nonzero) into the
+    # 3/3-padded domain, and one fold (zs_enc_dx_fold) that adds the padding rows back and the pass-through columns.
+    BANK_PAD = 3
+
+    def _pack_bank_d(self):
+        """The transposed operand of the bank's 7-tap data gradient: rows = c_in (padded to 128), K = 7 slots x cp (cp = 7*c_h1
+        padded to the K chunk); slot s of kernel i (k = i + 1) holds its tap j = s - 3 + k//2 in columns [s*cp + i*c_h1, +c_h1)."""
+        c, c1 = self.ctx, self.c1
+        ld, cp = self.bank_d_ld, self.bank_d_cp
+        for i, l in enumerate(self.conv1s):
+            k = l.k
+            for j in range(k):
+                s = j + self.BANK_PAD - k // 2
+                L.call('zs_pack_weight', 'ZsPackWeight', c.stream, dtype=c.dt, W=L.ptr(l.w, j), so=self.c_in * k, si=k, sj=1,
+                       Cout=c1, Cin=self.c_in, taps=1, transpose=1, co_split2=0, inner_pad=c1, dst=L.ptr(self.bank_d), ldw=ld,
+                       n_rows=self.bank_d_rows, n_cols=c1, row_offset=0, col_offset=s * cp + i * c1)
+
+    def _bank_operand(self):
+        if self.bank_d is None:
+            c = self.ctx
+            self.bank_d_cp = rup(7 * self.c1, c.kc)
+            self.bank_d_ld = 7 * self.bank_d_cp
+            self.bank_d_rows = rup(self.c_in, 128)
+            self.bank_d = torch.zeros(self.bank_d_rows * self.bank_d_ld + 512, dtype=c.tdt, device=c.device)
+            with L.pack_batch(c.stream):
+                self._pack_bank_d()                  # from now on pack() re-packs it with the other operands
+        return self.bank_d
+
+    def backward_input(self, dbits=None, dlogits=None, tape=None):
+        """Gradient of a loss w.r.t. the encoder's INPUT spectrogram, for the tape of the latest forward (or of key `tape`):
+        dbits (Act [B,T',E], w.r.t. enc_act) or dlogits (Act [B,T',n_lin], w.r.t. the pre-activation `enc`).  No weight gradient
+        is computed and no gradient buffer of the encoder is written.  Returns dx fp32 [B, T, c_in], contiguous (the encoder's
+        own buffer: valid until the next backward_input at this shape)."""
+        if dbits is None and dlogits is None:
+            raise ValueError('backward_input: dbits or dlogits')
+        tp = self.tape if tape is None else self.tapes[tape]
+        dcat = self.backward_main(dbits, dlogits, param_grads=False, tape=tape)
+        c = self.ctx
+        B, T, P = tp['B'], tp['T'], self.BANK_PAD
+        W = self._bank_operand()
+        if dcat.ld < self.bank_d_cp:          # the GEMM reads cp columns of every dcat row (K of one tap)
+            raise L.ZsError('backward_input: concatenation rows of %d columns < K chunk %d' % (dcat.ld, self.bank_d_cp))
+        g = c.act('e_gbank' + tp['tag'], B, T + 2 * P, self.c_in, dtype=torch.float32)
+        L.call('zs_gemm_conv', 'ZsGemmConv', c.stream, dtype=c.dt, A=dcat.ptr(), lda=dcat.ld, a_batch_stride=T * dcat.ld, B=B, T_in=T,
+               T_out=T + 2 * P, taps=7, stride=1, pad_left=0, pad_mode=L.ZS_PAD_ZERO, gather=1, cin_pad=self.bank_d_cp, W=L.ptr(W),
+               ldw=self.bank_d_ld, N=self.c_in, n_pad=self.bank_d_rows, act=L.ZS_ACT_NONE, out=g.ptr(), ldc=g.ld,
+               out_cols=g.ld, store_mode=L.ZS_STORE_ROWS, groups=1, out_f32=1)
+        n = B * T * self.c_in
+        dx = c.f32('e_dx' + tp['tag'], n)[:n].view(B, T, self.c_in)
+        L.call('zs_enc_dx_fold', 'ZsEncDxFold', c.stream, dtype=c.dt, g=g.ptr(), ldg=g.ld, pass_through=dcat.ptr(7 * self.c1), ld_pass=dcat.ld, B=B, T=T, C=self.c_in, pad=P,
+               pad_mode=self.pad_mode, dx=L.ptr(dx), ldx=self.c_in)
+        return dx
 
     def backward_bank(self):
         dcat, xin = self._bank

@@ -100,7 +100,7 @@ class PatchGANStep(object):
             if seed is None:
                 self.step_no += 1
                 seed = (self.step_no * 0x9E3779B97F4A7C15 + 12345) % (1 << 62) + 7 * parallel.rank()
-            bits, _, _ = ee.forward(x_btf, True, noise=noise, noise_kind=noise_kind, seed=seed, drop_masks=drop_masks)   # encode_step
+            bits, self._enc_f32, _ = ee.forward(x_btf, True, noise=noise, noise_kind=noise_kind, seed=seed, drop_masks=drop_masks)  # encode_step
             xd = de.forward(bits, c, False)                                   # Decoder(enc, c)
         if self.g_mode == 'spectrogram':
             m = ge.forward(xd, cg.contiguous(), train_generator)              # Generator(x_dec, c - shift_c) (trainer.py:283)
@@ -200,3 +200,55 @@ class PatchGANStep(object):
         if update:
             self.gen_opt.step(0.0)                                             # no grad_clip in the reference here
         return self.loss_rec
+
+
+class AutolockerStep(PatchGANStep):
+    """The autolocker mode of the reference (trainer.py:563-611): the generator is trained so that the encoder, run again on the
+    converted spectrogram, gives back the source's discrete units.
+
+    One step:  enc_act = Encoder(x_s);  x_gen = gen_step(enc_act, c_t);  re_enc = Encoder(x_gen)  (train mode, fresh noise);
+               loss = BCELoss(re_enc, enc_act.detach());  clip(Generator, max_grad_norm);  Adam.  The target-guided half is tg_step.
+    Only the generator is stepped, and only its gradients are computed: the encoder's backward is its input gradient alone
+    (EncoderEngine.backward_input), the encoder's and decoder's parameter gradients are neither computed nor touched.
+    multilabel_binary only: both enc_act and re_enc are then exactly 0 / 1, the loss is 100 * mismatches / N and its gradient
+    +-1e12 / N at the mismatches (torch clamps the logs at -100 and the backward's denominator at 1e-12).  The other encoder modes
+    give values that BCELoss rejects (one_hot / binary: 1 + ulp) or that are unbounded (continues)."""
+
+    ENC_MODE = 'multilabel_binary'
+
+    def __init__(self, encoder, decoder, generator, discriminator, hps, g_mode):
+        mode = getattr(encoder, 'enc_mode', None)
+        if mode != self.ENC_MODE:
+            raise ValueError("mode 'autolocker' needs enc_mode %r (BCE on the hard units), got %r" % (self.ENC_MODE, mode))
+        super(AutolockerStep, self).__init__(encoder, decoder, generator, discriminator, hps, g_mode)
+        self.loss_reenc = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._bce_part = torch.zeros(1024, dtype=torch.float64, device=self.device)
+
+    def al_step(self, x_s, c_t, update=True, noise2=None, drop_masks2=None, seed2=None, **gen_kw):
+        """x_s fp32 [B, T, F] source batch, c_t int64 [B] target speakers.  noise2 / drop_masks2 / seed2: the re-encode's Gumbel
+        noise (same kind as gen_kw's noise_kind), Dropout keep masks and RNG seed (default: derived from the first encode's).
+        Returns the re_enc loss (device scalar)."""
+        ee = self.Encoder._engine()
+        x_gen = self.gen_forward(x_s, c_t, True, **gen_kw)
+        target = self._enc_f32
+        if seed2 is None:
+            seed = gen_kw.get('seed')
+            seed = seed if seed is not None else (self.step_no * 0x9E3779B97F4A7C15 + 12345) % (1 << 62) + 7 * parallel.rank()
+            seed2 = (seed * 0x2545F4914F6CDD1D + 0x632BE59BD9B4E019) % (1 << 62)
+        _, re_enc, _ = ee.forward(x_gen, True, noise=noise2, noise_kind=gen_kw.get('noise_kind', 2), seed=seed2,
+                                  drop_masks=drop_masks2, tape='al')
+        tp = ee.tapes['al']
+        c = ee.ctx
+        B, T4, E = tp['B'], tp['T4'], ee.E
+        if tuple(target.shape) != (B, T4, E):
+            raise ValueError('al_step: the re-encode gives %s units, the first encode %s' % ((B, T4, E), tuple(target.shape)))
+        dlog = c.act('e_dlog_al' + tp['tag'], B, T4, ee.n_lin)
+        L.call('zs_bce_mbv_bwd', 'ZsBceMbvBwd', c.stream, dtype=c.dt, bits=L.ptr(tp['bits_f32']), y0=L.ptr(tp['y0']),
+               target=L.ptr(target), rows=B * T4, E=E, tau=0.1, grad_scale=1.0, dlogits=dlog.ptr(), ld=dlog.ld, fill_cols=dlog.ld,
+               partial=L.ptr(self._bce_part), loss_out=L.ptr(self.loss_reenc))
+        dx = ee.backward_input(dlogits=dlog, tape='al')
+        self._gen_backward(dx)
+        self.last = {'x_gen': x_gen, 'enc_act': target, 're_enc': re_enc, 'dx_gen': dx}   # (inspection)
+        if update:
+            self.gen_opt.step(self.hps.max_grad_norm)
+        return self.loss_reenc

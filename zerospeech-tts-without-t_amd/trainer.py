@@ -21,7 +21,7 @@ from . import layers
 from .layers import Act, join_side
 from .model import Decoder, Encoder, SpeakerClassifier, Spectrogram_Patcher
 from .patch import PatchDiscriminator, TargetClassifier
-from .stage2 import NetOpt, PatchGANStep
+from .stage2 import AutolockerStep, NetOpt, PatchGANStep
 from .utils import Logger
 
 TCLF_CLASSES = 3                       # TargetClassifier(n_class=3): V001, V002, 'None' (trainer.py:97, convert.py:402-407)
@@ -698,7 +698,14 @@ class Trainer(object):
         self.source_loader, self.target_loader = source_loader, target_loader
         self._duo = None
 
-    def stage2(self):
+    def stage2(self, autolocker=False):
+        """The stage-2 step object.  autolocker=True: an AutolockerStep (raises ValueError before any launch unless enc_mode is
+        multilabel_binary); a PatchGANStep built earlier hands it its optimizers (the reference has one gen_opt / patch_opt)."""
+        if autolocker and not isinstance(self.s2, AutolockerStep):
+            al = AutolockerStep(self.Encoder, self.Decoder, self.Generator, self.PatchDiscriminator, self.hps, self.g_mode)
+            if self.s2 is not None:
+                al.gen_opt, al.patch_opt, al.step_no = self.s2.gen_opt, self.s2.patch_opt, self.s2.step_no
+            self.s2 = al
         if self.s2 is None:
             self.s2 = PatchGANStep(self.Encoder, self.Decoder, self.Generator, self.PatchDiscriminator, self.hps, self.g_mode)
         return self.s2
@@ -1002,5 +1009,26 @@ class Trainer(object):
             layers.check_status(self.device)
             if is_main:
                 print()
+        elif mode == 'autolocker':                                                        # trainer.py:563-611
+            s2 = self.stage2(autolocker=True)                                             # ValueError unless multilabel_binary
+            for iteration in range(hps.patch_iters):
+                log_now = (iteration % self.log_every == 0) or (iteration + 1 == hps.patch_iters)
+                (_, x_s), (c_t, x_t) = self._duo_batch()                                  # train G
+                loss_reenc = s2.al_step(x_s, c_t)
+                loss_rec = s2.tg_step(x_t, c_t) if target_guided else None                # teacher forcing, no clip
+                if log_now:
+                    layers.check_status(self.device)
+                if log_now and is_main:
+                    info = {f'{flag}/re_enc': loss_reenc.item(), f'{flag}/tg_rec': loss_rec.item() if target_guided else 0.000}
+                    print('patch_G:[%06d/%06d], re_enc=%.3f, tg_rec=%.3f' % ((iteration + 1, hps.patch_iters) + tuple(info.values())),
+                          end='\r')
+                    if iteration % 100 == 0:
+                        for tag, value in info.items():
+                            self.logger.scalar_summary(tag, value, iteration + 1)
+                if (iteration + 1) % self.ckpt_every == 0 and is_main:
+                    self.save_model(model_path, 's2', iteration + 1)
+            layers.check_status(self.device)
+            if is_main:
+                print()
         else:
-            raise NotImplementedError("mode %r (autolocker / Tacotron) is outside the path this build covers" % mode)
+            raise NotImplementedError("mode %r (Tacotron) is outside the path this build covers" % mode)
