@@ -270,6 +270,9 @@ typedef struct {
   void* out; int64_t ldo; int32_t unshuffle;
 } ZsGradCombine;
 int zs_grad_combine(const ZsGradCombine* p, void* stream);
+/* zs_norm_decomposition: 1 if zs_instnorm_fwd (kernel 0), zs_instnorm_bwd (1) or zs_grad_combine (2) launched now with this dtype,
+ * T and C would run the 8 x 256 decomposition, 0 for 32 x 64 (the same test the launch makes, under the current knobs). */
+int zs_norm_decomposition(int32_t kernel, int32_t dtype, int32_t T, int32_t C);
 
 /* zs_emb_scatter: nn.Embedding weight gradient from per-sample sums, in fixed sample order:
  *   demb[r][c] (+)= sum_{b : idx[b] == r} emb_sum[b][c]      (model/model.py:310-314 lookups) */

@@ -420,3 +420,9 @@ extern "C" int zs_grad_combine(const ZsGradCombine* p, void* stream) {
   ZS_NORM_LAUNCH(grad_combine_kernel, g_norm_lim2.get());
   return zs_check_launch("zs_grad_combine");
 }
+
+extern "C" int zs_norm_decomposition(int32_t kernel, int32_t dtype, int32_t T, int32_t C) {
+  ZS_REQUIRE(kernel >= 0 && kernel <= 2, "zs_norm_decomposition: kernel 0 (fwd), 1 (bwd) or 2 (combine)");
+  const int lim = kernel == 0 ? g_norm_lim0.get() : kernel == 1 ? g_norm_lim1.get() : g_norm_lim2.get();
+  return norm_wide(dtype, T, C, lim) ? 1 : 0;
+}
