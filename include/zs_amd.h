@@ -410,6 +410,18 @@ typedef struct {
   uint32_t* status;              /* sticky status word, see ZsGruFwd */
 } ZsGruBwd;
 int zs_gru_bwd(const ZsGruBwd* p, void* stream);
+/* zs_gru_path: the plan a zs_gru_fwd (pass 0) or zs_gru_bwd (pass 1) launch with these sizes would take now, under the current
+ * knobs and the device's CU count -- the same function the launches call.  Returns path | per << 8: the path is ZS_GRU_PATH_*,
+ * per is PER in {1, 2, 4} (forward) / PERB in {3, 6, 12} (BPTT) of the PERSIST kernels and 0 otherwise; negative on bad arguments.
+ *   WIDE: one persistent launch, 16-row x 64-unit tiles (bf16, H in {128, 256, 512}, "gru_wide", 16-byte operand layout);
+ *   PERSIST: one persistent launch, 32 x 32 (forward) / 16 x 64 (BPTT) tiles;  STEP_FUSED: one launch per step, product and gate
+ *   math fused;  STEP_GEMM: a zs_gemm_conv product and a gate kernel per step (H % 32 != 0, or W_hh not interleaved).
+ * Both persistent paths need T > 1, "gru_persist" and a grid of at most one workgroup per CU.  whh_interleaved is
+ * ZsGruFwd.whh_interleaved (ignored by pass 1); wide_aligned is 1 when the launch's operands meet the WIDE kernels' 16-byte
+ * layout: forward: out_col, ldo, ldgi (and bcast_col) multiples of 8 elements, out, gi, gates 16-byte aligned; BPTT: also
+ * dout_col, ldd and ldgh multiples of 8, dout, out, gates, dgi, dgh 16-byte aligned (zs_gru_fwd / zs_gru_bwd test it themselves). */
+enum { ZS_GRU_PATH_WIDE = 0, ZS_GRU_PATH_PERSIST = 1, ZS_GRU_PATH_STEP_FUSED = 2, ZS_GRU_PATH_STEP_GEMM = 3 };
+int zs_gru_path(int32_t pass, int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t whh_interleaved, int32_t wide_aligned);
 
 /* ---------------------------------------------------------------------------------------------
  * zs_l1_loss: loss = mean|x_dec - x| over rows*F (trainer.py:328) and the gradient w.r.t. the

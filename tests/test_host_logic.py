@@ -107,6 +107,58 @@ def test_set_option_knobs_are_documented_and_normalised(lib):
     assert json.loads(out.decode().strip().splitlines()[-1]) == want
 
 
+def test_gru_path_query_cases_independent_of_the_cu_count(lib):
+    """zs_gru_path: the plan of a zs_gru_fwd (pass 0) / zs_gru_bwd (pass 1) launch, for grids small enough to fit any device
+    (B <= 16, H <= 512: at most 16 workgroups).  No GPU is touched."""
+    q = lib.lib().zs_gru_path
+    WIDE, PERSIST, FUSED, GEMM = (lib.ZS_GRU_PATH_WIDE, lib.ZS_GRU_PATH_PERSIST, lib.ZS_GRU_PATH_STEP_FUSED,
+                                  lib.ZS_GRU_PATH_STEP_GEMM)
+    F32, BF16 = lib.ZS_F32, lib.ZS_BF16
+
+    def path(pas, dt, T, H, inter=1, aligned=1, B=16):
+        rc = q(pas, dt, B, T, H, inter, aligned)
+        assert rc >= 0, lib.last_error()
+        return rc & 255, rc >> 8
+
+    old = {k: lib.set_option(k, 1) for k in ('gru_persist', 'gru_wide')}
+    try:
+        for pas in (0, 1):
+            for dt in (F32, BF16):
+                for H in (8, 40, 72, 520):                       # H % 32 != 0: a product launch and a gate launch per step
+                    assert path(pas, dt, 9, H) == (GEMM, 0)
+                for T in (2, 9):
+                    assert path(pas, dt, T, 96) == (FUSED, 0)   # no persistent kernel for H = 96
+                for H in (64, 128, 256, 512):                  # T = 1: nothing to persist
+                    assert path(pas, dt, 1, H) == (FUSED, 0)
+            # bf16, H in {128, 256, 512}: the wide tiling when the operands allow 16-byte transfers, else the 32 x 32 / 16 x 64 one
+            for H, per, perb in ((128, 1, 3), (256, 2, 6), (512, 4, 12)):
+                assert path(pas, BF16, 2, H) == (WIDE, 0)
+                assert path(pas, BF16, 2, H, aligned=0) == (PERSIST, per if pas == 0 else perb)
+        assert path(0, BF16, 9, 128, inter=0) == (GEMM, 0)       # the forward's fused paths need W_hh gate-interleaved ...
+        assert path(1, BF16, 9, 128, inter=0) == (WIDE, 0)       # ... the BPTT reads the transposed packing
+        for H, per, perb in ((64, 1, 3), (128, 2, 6), (256, 4, 12)):   # fp32 never takes the wide kernels
+            assert path(0, F32, 5, H) == (PERSIST, per) and path(1, F32, 5, H) == (PERSIST, perb)
+        for pas in (0, 1):
+            assert path(pas, F32, 5, 512)[0] == FUSED                    # fp32 H = 512: no register-resident W_hh slice
+            assert path(pas, BF16, 5, 192)[0] == FUSED                   # PER / PERB of 1.5 / 4.5
+        lib.set_option('gru_wide', 0)
+        for pas in (0, 1):
+            assert path(pas, BF16, 2, 512) == (PERSIST, 4 if pas == 0 else 12)
+        lib.set_option('gru_persist', 0)
+        for pas in (0, 1):
+            for dt in (F32, BF16):
+                assert path(pas, dt, 9, 128) == (FUSED, 0)
+                assert path(pas, dt, 9, 72) == (GEMM, 0)
+        lib.set_option('gru_wide', 1)
+        assert path(0, BF16, 9, 512) == (FUSED, 0)                       # gru_wide alone does not make a launch persistent
+    finally:
+        for k, v in old.items():
+            lib.set_option(k, v)
+    assert q(2, BF16, 4, 8, 128, 1, 1) < 0 and 'zs_gru_path' in lib.last_error()
+    assert q(0, 7, 4, 8, 128, 1, 1) < 0
+    assert q(0, BF16, 4, 8, 100, 1, 1) < 0                               # H % 8 != 0 is refused by the launches too
+
+
 def test_no_cpu_fallback():
     import zs_amd  # noqa: F401
     from zs_amd import _lib

@@ -1196,47 +1196,47 @@ bool gru_wide_aligned(const ZsGruBwd* p) {
          (((uintptr_t)p->dout | (uintptr_t)p->out | (uintptr_t)p->gates | (uintptr_t)p->dgi | (uintptr_t)p->dgh) % 16) == 0;
 }
 
-// How one GRU pass runs.  WIDE: one persistent launch of 16-row x 64-unit tiles (bf16, H in {128, 256, 512}).  PERSIST: one
-// persistent launch of 32 x 32 (forward) / 16 x 64 K-split (BPTT) tiles.  STEP_FUSED: one rowblock_gemm_kernel launch per step,
-// recurrent product and gate math fused.  STEP_GEMM: zs_gemm_conv and a gate kernel per step.
-enum GruPath { GRU_WIDE, GRU_PERSIST, GRU_STEP_FUSED, GRU_STEP_GEMM };
+// How one GRU pass runs (the paths are ZS_GRU_PATH_* in zs_amd.h).  WIDE: one persistent launch of 16-row x 64-unit tiles (bf16,
+// H in {128, 256, 512}).  PERSIST: one persistent launch of 32 x 32 (forward) / 16 x 64 K-split (BPTT) tiles.  STEP_FUSED: one
+// rowblock_gemm_kernel launch per step, recurrent product and gate math fused.  STEP_GEMM: zs_gemm_conv and a gate kernel per step.
 struct GruPlan {
-  GruPath path;
+  int path;              // ZS_GRU_PATH_*
   int per;               // PERSIST: the kernel's PER (forward) / PERB (BPTT)
   int rb;                // row blocks of the grid (grid.y); 0 for STEP_GEMM
   unsigned spin_limit;
 };
 
-// Each plan reads the GRU knobs once.  The forward's persistent and fused paths need W_hh interleaved.
-GruPlan gru_fwd_plan(const ZsGruFwd* p) {
-  const int B = p->B, H = p->H;
-  if (!p->whh_interleaved || H % 32 != 0) return {GRU_STEP_GEMM, 0, 0, 0};
-  const bool persist = g_gru_persist.get() != 0 && p->T > 1, wide = g_gru_wide.get() != 0;
+// The one plan of both passes (pass 0: zs_gru_fwd, 1: zs_gru_bwd); the launches and zs_gru_path call it.  It reads the GRU knobs
+// once.  The forward's persistent and fused paths need W_hh interleaved (the BPTT reads the transposed packing and ignores it).
+GruPlan gru_plan(int pass, int dtype, int B, int T, int H, bool whh_interleaved, bool wide_aligned) {
+  const bool bwd = pass != 0;
+  if (H % 32 != 0 || (!bwd && !whh_interleaved)) return {ZS_GRU_PATH_STEP_GEMM, 0, 0, 0};
+  const bool persist = g_gru_persist.get() != 0 && T > 1, wide = g_gru_wide.get() != 0;
   const unsigned spin = (unsigned)g_gru_spin_limit.get();
   const int nrb16 = (B + 15) / 16, nrb = (B + 16 * RB - 1) / (16 * RB);
-  const int kstep = p->dtype == ZS_F32 ? 16 : 32;
-  const int per = (H % (4 * kstep) == 0) ? H / (4 * kstep) : 0;
-  if (persist && wide && p->dtype == ZS_BF16 && (H == 128 || H == 256 || H == 512) && (int64_t)(H / 64) * nrb16 * 2 <= gru_resident_limit() &&
-      gru_wide_aligned(p))
-    return {GRU_WIDE, 0, nrb16, spin};
-  if (persist && (per == 1 || per == 2 || per == 4) && (int64_t)(H / 32) * nrb * 2 <= gru_resident_limit()) return {GRU_PERSIST, per, nrb, spin};
-  return {GRU_STEP_FUSED, 0, nrb, spin};
+  const int kstep = dtype == ZS_F32 ? 16 : 32;
+  if (persist && wide && dtype == ZS_BF16 && (H == 128 || H == 256 || H == 512) && (int64_t)(H / 64) * nrb16 * 2 <= gru_resident_limit() &&
+      wide_aligned)
+    return {ZS_GRU_PATH_WIDE, 0, nrb16, spin};
+  if (!bwd) {
+    const int per = (H % (4 * kstep) == 0) ? H / (4 * kstep) : 0;
+    if (persist && (per == 1 || per == 2 || per == 4) && (int64_t)(H / 32) * nrb * 2 <= gru_resident_limit())
+      return {ZS_GRU_PATH_PERSIST, per, nrb, spin};
+    return {ZS_GRU_PATH_STEP_FUSED, 0, nrb, spin};
+  }
+  // both persistent BPTT tilings: 16 rows x 64 units per workgroup
+  const int perb = ((3 * H) % (4 * kstep) == 0 && H % (16 * BNT) == 0) ? (3 * H) / (4 * kstep) : 0;
+  if (persist && (perb == 3 || perb == 6 || perb == 12) && (int64_t)(H / (16 * BNT)) * nrb16 * 2 <= gru_resident_limit())
+    return {ZS_GRU_PATH_PERSIST, perb, nrb16, spin};
+  return {ZS_GRU_PATH_STEP_FUSED, 0, nrb, spin};
+}
+
+GruPlan gru_fwd_plan(const ZsGruFwd* p) {
+  return gru_plan(0, p->dtype, p->B, p->T, p->H, p->whh_interleaved != 0, gru_wide_aligned(p));
 }
 
 GruPlan gru_bwd_plan(const ZsGruBwd* p) {
-  const int B = p->B, H = p->H;
-  if (H % 32 != 0) return {GRU_STEP_GEMM, 0, 0, 0};
-  const bool persist = g_gru_persist.get() != 0 && p->T > 1, wide = g_gru_wide.get() != 0;
-  const unsigned spin = (unsigned)g_gru_spin_limit.get();
-  const int nrb16 = (B + 15) / 16;                       // both persistent BPTT tilings: 16 rows x 64 units per workgroup
-  const int kstep = p->dtype == ZS_F32 ? 16 : 32;
-  const int perb = ((3 * H) % (4 * kstep) == 0 && H % (16 * BNT) == 0) ? (3 * H) / (4 * kstep) : 0;
-  if (persist && wide && p->dtype == ZS_BF16 && (H == 128 || H == 256 || H == 512) && (int64_t)(H / 64) * nrb16 * 2 <= gru_resident_limit() &&
-      gru_wide_aligned(p))
-    return {GRU_WIDE, 0, nrb16, spin};
-  if (persist && (perb == 3 || perb == 6 || perb == 12) && (int64_t)(H / (16 * BNT)) * nrb16 * 2 <= gru_resident_limit())
-    return {GRU_PERSIST, perb, nrb16, spin};
-  return {GRU_STEP_FUSED, 0, (B + 16 * RB - 1) / (16 * RB), spin};
+  return gru_plan(1, p->dtype, p->B, p->T, p->H, true, gru_wide_aligned(p));
 }
 
 }  // namespace
@@ -1262,6 +1262,14 @@ extern "C" int zs_gru_check(const float* work, int32_t B, int32_t H, void* strea
   return ZS_OK;
 }
 
+extern "C" int zs_gru_path(int32_t pass, int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t whh_interleaved, int32_t wide_aligned) {
+  ZS_REQUIRE(pass == 0 || pass == 1, "zs_gru_path: pass 0 (zs_gru_fwd) or 1 (zs_gru_bwd)");
+  ZS_REQUIRE(dtype == ZS_F32 || dtype == ZS_BF16, "zs_gru_path: bad dtype");
+  ZS_REQUIRE(B > 0 && T > 0 && H > 0 && H % 8 == 0, "zs_gru_path: sizes");
+  const GruPlan pl = gru_plan(pass, dtype, B, T, H, whh_interleaved != 0, wide_aligned != 0);
+  return pl.path | (pl.per << 8);
+}
+
 extern "C" int zs_gru_fwd(const ZsGruFwd* p, void* stream) {
   ZS_REQUIRE(p && p->gi && p->whh && p->bhh && p->out && p->work, "zs_gru_fwd: null operand");
   ZS_REQUIRE(p->dtype == ZS_F32 || p->dtype == ZS_BF16, "zs_gru_fwd: bad dtype");
@@ -1277,7 +1285,7 @@ extern "C" int zs_gru_fwd(const ZsGruFwd* p, void* stream) {
   const char* outb = (const char*)p->out;
   ZS_REQUIRE(!p->bcast_vec || (p->bcast_idx && (p->bcast_col * es) % 4 == 0), "zs_gru_fwd: bcast_idx / bcast_col");
   const GruPlan pl = gru_fwd_plan(p);
-  const bool persistent = pl.path == GRU_WIDE || pl.path == GRU_PERSIST;
+  const bool persistent = pl.path == ZS_GRU_PATH_WIDE || pl.path == ZS_GRU_PATH_PERSIST;
   if (p->bcast_vec && !persistent) {                   // the persistent kernels write it with the recurrence; the others: a launch first
     ZsAddRowvec r;
     memset(&r, 0, sizeof(r));
@@ -1295,14 +1303,14 @@ extern "C" int zs_gru_fwd(const ZsGruFwd* p, void* stream) {
     a.hx = reinterpret_cast<unsigned long long*>(wbase);
     a.err = reinterpret_cast<unsigned*>(p->work);
     a.status = p->status; a.spin_limit = pl.spin_limit;
-    a.B = B; a.T = T; a.H = H; a.rows_pad = pl.path == GRU_WIDE ? pl.rb * 16 : pl.rb * 16 * RB;
+    a.B = B; a.T = T; a.H = H; a.rows_pad = pl.path == ZS_GRU_PATH_WIDE ? pl.rb * 16 : pl.rb * 16 * RB;
     a.bcast_vec = p->bcast_vec; a.bcast_ld = p->bcast_ld; a.bcast_idx = p->bcast_idx; a.bcast_col = p->bcast_col;
     a.dir1_forward = p->dir1_forward != 0;
     if (hipMemsetAsync(p->work, 0, GRU_WORK_HDR + gru_hx_bytes(B, H, es), (hipStream_t)stream) != hipSuccess) {
       zs_set_error("zs_gru_fwd: memset failed");
       return ZS_ELAUNCH;
     }
-    if (pl.path == GRU_WIDE) {
+    if (pl.path == ZS_GRU_PATH_WIDE) {
       dim3 wgrid(H / 64, pl.rb, 2);
       if (H == 512) hipLaunchKernelGGL(gru_wide_fwd_kernel<16>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
       else if (H == 256) hipLaunchKernelGGL(gru_wide_fwd_kernel<8>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
@@ -1317,7 +1325,7 @@ extern "C" int zs_gru_fwd(const ZsGruFwd* p, void* stream) {
 #undef ZS_GRU_PF
     return zs_check_launch("zs_gru_fwd.persist");
   }
-  if (pl.path == GRU_STEP_FUSED) {
+  if (pl.path == ZS_GRU_PATH_STEP_FUSED) {
     // one fused launch per step: recurrent product + gates (see rowblock_gemm_kernel)
     for (int s = 0; s < T; ++s) {
       RowGemmArgs a;
@@ -1384,7 +1392,7 @@ extern "C" int zs_gru_bwd(const ZsGruBwd* p, void* stream) {
   float* dhg = dhd + (size_t)2 * B * H;
   const char* dghb = (const char*)p->dgh;
   const GruPlan pl = gru_bwd_plan(p);
-  if (pl.path == GRU_WIDE || pl.path == GRU_PERSIST) {
+  if (pl.path == ZS_GRU_PATH_WIDE || pl.path == ZS_GRU_PATH_PERSIST) {
     GruPersistBwdArgs a;
     memset(&a, 0, sizeof(a));
     a.dout = p->dout; a.ldd = p->ldd; a.dout_col = p->dout_col; a.out = p->out; a.ldo = p->ldo; a.out_col = p->out_col;
@@ -1398,7 +1406,7 @@ extern "C" int zs_gru_bwd(const ZsGruBwd* p, void* stream) {
       zs_set_error("zs_gru_bwd: memset failed");
       return ZS_ELAUNCH;
     }
-    if (pl.path == GRU_WIDE) {
+    if (pl.path == ZS_GRU_PATH_WIDE) {
       dim3 wgrid(H / 64, pl.rb, 2);
       if (H == 512) hipLaunchKernelGGL(gru_wide_bwd_kernel<16>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
       else if (H == 256) hipLaunchKernelGGL(gru_wide_bwd_kernel<8>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
@@ -1413,7 +1421,7 @@ extern "C" int zs_gru_bwd(const ZsGruBwd* p, void* stream) {
 #undef ZS_GRU_PB
     return zs_check_launch("zs_gru_bwd.persist");
   }
-  const bool fast = pl.path == GRU_STEP_FUSED;
+  const bool fast = pl.path == ZS_GRU_PATH_STEP_FUSED;
   for (int s = 0; s < T; ++s) {
     GateBwdArgs a;
     a.dout = p->dout; a.ldd = p->ldd; a.dout_col = p->dout_col; a.out = p->out; a.ldo = p->ldo; a.out_col = p->out_col;
