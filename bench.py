@@ -1,6 +1,10 @@
 """bench.py -- throughput of the --train_ae step (BASELINE.json metric) on N MI355X GPUs.
 
-  python bench.py --gpus N --steps K --warmup W [--dtype bf16|fp32] [--batch 256] [--no-cpu-baseline]
+  python bench.py --gpus N --steps K --warmup W [--dtype bf16|fp32] [--batch 256] [--full [--no-cpu-baseline] [--no-secondary]]
+  A plain run does what its headline needs and nothing more: set-up, W warm-up steps, the K timed steps, --dump-outputs, the
+  JSON line.  --full adds everything that takes runs of its own: the roofline's instrumented eager steps (graph mode) and the
+  isolated-kernel rate, the CPU baselines, and the secondary records of the train_ae line (host-fed rate, bf16-vs-fp32 parity,
+  BASELINE configs 4 and 5); with --mode resynth, the pipelined and host-input rates and the CPU baseline.
   N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK / WORLD_SIZE in
   the environment), or plainly as `python bench.py --gpus N`: the parent then starts N rank processes itself (before it makes
   any GPU call) and returns rank 0's JSON line.  A world size that differs from --gpus is an error, never a silent 1-rank run.
@@ -14,7 +18,8 @@ roofline: the dominant kernel is gemm_conv_kernel (implicit-GEMM conv / linear f
   achieved = algorithmic FLOPs of those launches (2*M*Cout*Cin*k per call, unpadded sizes) / their summed
   duration, measured with HIP events on the launch stream during the timed steps; peak = dense MFMA peak
   of the dtype (bf16 2.5 PFLOP/s, exact-fp32 157.3 TFLOP/s; MI355X_MICROARCH.md).
-cpu_baseline: the oracle (CPU port of the reference, oracle/zs_oracle.py) timed on the host cores on a bounded
+  A plain run in graph mode reports no achieved rate (the timed steps are replays); --no-graph times the launches in place.
+cpu_baseline (--full): the oracle (CPU port of the reference, oracle/zs_oracle.py) timed on the host cores on a bounded
   sample of the same workload (full-size model, reference batch 16), rank 0, N=1 only.
 --dump-outputs DIR: rank 0 writes what the last timed step computed to DIR/<name>.npy (float32 / float64, 64 MB at most; an
   output of more than 4 Mi elements is a fixed, seeded sample of them, see dump_sample).  train_ae: loss, x_dec (the decoder
@@ -41,6 +46,8 @@ def parse():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--dtype', default=os.environ.get('ZS_BENCH_DTYPE', 'bf16'))
     ap.add_argument('--batch', type=int, default=256)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: roofline and isolated-kernel rates, CPU baselines, secondary records')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernel-events', action='store_true')
     ap.add_argument('--no-graph', action='store_true', help='issue every launch from the host instead of replaying hipGraphs')
@@ -224,7 +231,7 @@ def spawn_ranks(args):
     return rc
 
 
-def resynth_record(args, rank, world, dev, steps, warmup, cpu=True, dump_dir=None):
+def resynth_record(args, rank, world, dev, steps, warmup, full=True, cpu=True, dump_dir=None):
     """BASELINE config 4: test_encode + convert.py Griffin-Lim resynthesis of 64 utterances of U{200..700} frames on one MI355X
     (full-size english model, random weights, bf16 network, fp32 vocoder, n_iter = 300).  A "step" = the whole batch once:
     fragmenting, Encoder + Decoder over every fragment, de-normalisation, 300 Griffin-Lim iterations, de-emphasis, trim.
@@ -237,6 +244,7 @@ def resynth_record(args, rank, world, dev, steps, warmup, cpu=True, dump_dir=Non
     utterances).  achieved = ALGORITHMIC bytes per launch (per frame: 513 complex64 read + 513 complex64 written + 513 fp32
     magnitudes read = 10.3 KB) / the HIP-event time of a launch on the launch stream, against 8 TB/s; the FLOP rate of the
     transforms (2 real 1024-point FFTs per frame and iteration, 2.5 N log2 N each) is reported beside it.
+    full=False leaves out the runs made after the timed steps for the pipelined and host-input rates.
     Returns the record (rank 0) or None."""
     import tempfile
     import numpy as np
@@ -299,27 +307,28 @@ def resynth_record(args, rank, world, dev, steps, warmup, cpu=True, dump_dir=Non
             'encoding_shapes': np.asarray([np.shape(e) for e in encs], dtype=np.float64),
             'wavs': dump_sample(torch.from_numpy(np.concatenate([np.asarray(w, dtype=np.float32).reshape(-1) for w in wavs]))),
             'wav_lengths': np.asarray([len(w) for w in wavs], dtype=np.float64)})
-    # the same batches as a serving loop issues them: batch i + 1 enqueued before the results of batch i are waited for
-    # (resynth_batch(defer=True)); reported beside `value`, which keeps one host wait per batch inside every step
-    pend = None
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(steps):
-        f = cv.resynth_batch(specs_dev, tr, 128, spk, n_iter=n_iter, do_trim=True, defer=True)
-        if pend is not None:
-            pend()
-        pend = f
-    pend()
-    torch.cuda.synchronize()
-    dt_pipe = (time.perf_counter() - t1) / steps
-    # beside it: the same batch handed over as host arrays (the reference's loader), pinned staging + H2D inside the time
-    run(False, specs)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(steps):
+    if full:
+        # the same batches as a serving loop issues them: batch i + 1 enqueued before the results of batch i are waited for
+        # (resynth_batch(defer=True)); reported beside `value`, which keeps one host wait per batch inside every step
+        pend = None
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(steps):
+            f = cv.resynth_batch(specs_dev, tr, 128, spk, n_iter=n_iter, do_trim=True, defer=True)
+            if pend is not None:
+                pend()
+            pend = f
+        pend()
+        torch.cuda.synchronize()
+        dt_pipe = (time.perf_counter() - t1) / steps
+        # beside it: the same batch handed over as host arrays (the reference's loader), pinned staging + H2D inside the time
         run(False, specs)
-    torch.cuda.synchronize()
-    dt_host = (time.perf_counter() - t1) / steps
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(steps):
+            run(False, specs)
+        torch.cuda.synchronize()
+        dt_host = (time.perf_counter() - t1) / steps
     t1 = time.perf_counter()
     _, decs = cv.encode_batch(specs_dev, tr, 128, decode_speakers=spk, to_host=False)
     torch.cuda.synchronize()
@@ -358,15 +367,16 @@ def resynth_record(args, rank, world, dev, steps, warmup, cpu=True, dump_dir=Non
            'config': {'workload': 'BASELINE config 4: encode + decode (english hps, enc_size=1024, emb_size=1024) + spectrogram2wav '
                                   '(Griffin-Lim n_iter=%d, de-emphasis, trim) of %d utterances of U{200..700} frames per GPU, spectrograms '
                                   'resident in HBM, host fragmenting and D2H of the results included' % (n_iter, len(lens)), 'parallelism': 'replicas%d' % world},
-           'frames_per_s': float(sum(lens_all)) * steps / dt, 'host_input_utt_per_s': len(lens_all) / dt_host,
-           'host_input_ms_per_step': 1e3 * dt_host, 'pipelined_utt_per_s': len(lens_all) / dt_pipe, 'pipelined_ms_per_step': 1e3 * dt_pipe,
-           'encode_decode_ms': 1e3 * dt_enc, 'griffin_lim_ms': 1e3 * gl,
+           'frames_per_s': float(sum(lens_all)) * steps / dt, 'encode_decode_ms': 1e3 * dt_enc, 'griffin_lim_ms': 1e3 * gl,
            'roofline': {'bound': 'hbm', 'achieved': by / launch_s / 1e9, 'peak': 8000.0, 'unit': 'GB/s', 'frac': by / launch_s / 8e12,
                         'traffic': gl_traffic, 'traffic_unit': 'bytes/launch (committed rocprofv3 --pmc passes of this command)',
                         'kernel': 'gl_iter_kernel (one fused Griffin-Lim iteration of ALL utterances = one "launch" here; issued as up to 3 '
                                   'concurrent launches over utterance ranges on independent streams, %d iterations per batch)' % (n_iter + 1),
                         'avg_launch_ms': 1e3 * launch_s, 'algorithmic_bytes_per_launch': by, 'concurrent_kernel_launches_per_launch': chains,
                         'fft_tflops': fl / gl / 1e12, 'fft_frac_of_fp32_vector_peak': fl / gl / 1e12 / 157.3}}
+    if full:
+        out.update({'host_input_utt_per_s': len(lens_all) / dt_host, 'host_input_ms_per_step': 1e3 * dt_host,
+                    'pipelined_utt_per_s': len(lens_all) / dt_pipe, 'pipelined_ms_per_step': 1e3 * dt_pipe})
     if cpu:
         sys.path.insert(0, os.path.join(ROOT, 'oracle'))
         import zs_oracle as O      # CPU baseline beside the measurement only
@@ -394,7 +404,8 @@ def resynth_main(args):
     dev = torch.device('cuda', local)
     torch.cuda.set_device(dev)
     os.environ['LOCAL_RANK'] = str(local)
-    out = resynth_record(args, rank, world, dev, args.steps, args.warmup, cpu=not args.no_cpu_baseline, dump_dir=args.dump_outputs)
+    out = resynth_record(args, rank, world, dev, args.steps, args.warmup, full=args.full, cpu=args.full and not args.no_cpu_baseline,
+                         dump_dir=args.dump_outputs)
     if out is not None:
         emit_json(out)
     if torch.distributed.is_initialized():
@@ -674,7 +685,7 @@ def main():
         # weights its Adam update left (the instrumented steps further down change them)
         dumped = {'loss': ae._loss.detach().float().cpu().numpy(), 'x_dec': dump_sample(ae.xdec.valid()),
                   'encoder_params': dump_sample(net_params(enc)), 'decoder_params': dump_sample(net_params(dec))}
-    if ae.use_graph and not args.no_kernel_events:
+    if args.full and ae.use_graph and not args.no_kernel_events:
         # HIP events cannot bracket kernels inside a replayed graph: the per-kernel durations for the roofline come from
         # instrumented EAGER steps of the same workload, run right after the timed region in this process
         ae.use_graph = False
@@ -686,7 +697,7 @@ def main():
         ae.use_graph = True
         log('instrumented eager steps for the roofline: %d gemm_conv launches timed' % len(ke.pairs))
     isolated = None
-    if rank == 0 and not args.no_kernel_events:
+    if args.full and rank == 0 and not args.no_kernel_events:
         isolated = isolated_kernel_rate(dev, args.dtype)
     loss = float(ae._loss.item())
     from zs_amd import layers
@@ -735,12 +746,12 @@ def main():
         isolated['frac'] = isolated['achieved'] / peak
         out['roofline']['isolated'] = isolated
     out['step_tflops'] = 180.7e6 * value / 1e12          # 180.7 MFLOP per frame for the whole step
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(seg_len, F, E, ch, nspk)                    # the reference's own batch size
         if B != 16:
             big = cpu_baseline(seg_len, F, E, ch, nspk, steps=1, batch=B)              # and the GPU configuration's
             out['cpu_baseline']['at_gpu_batch'] = {k: big[k] for k in ('value', 'unit', 'sample')}
-    if world == 1 and not parallel.multi_rank() and not args.no_secondary and args.dtype == 'bf16':
+    if args.full and world == 1 and not parallel.multi_rank() and not args.no_secondary and args.dtype == 'bf16':
         # secondary records, all outside the timed region: parity of the benchmarked bf16 model, BASELINE configs 4 and 5
         ke.uninstall()
         sec = {}

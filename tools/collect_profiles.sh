@@ -13,9 +13,9 @@ echo "train trace done"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/train_f -- python3 $R/bench.py $B --steps 3 --warmup 1 > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/train_w -- python3 $R/bench.py $B --steps 3 --warmup 1 > /dev/null 2>&1
 echo "train counters done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/resynth -- python3 $R/bench.py --mode resynth --no-cpu-baseline --steps 2 --warmup 1 > $O/resynth.json 2> /dev/null
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/resynth_f -- python3 $R/bench.py --mode resynth --no-cpu-baseline --steps 1 --warmup 1 > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/resynth_w -- python3 $R/bench.py --mode resynth --no-cpu-baseline --steps 1 --warmup 1 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/resynth -- python3 $R/bench.py --mode resynth --full --no-cpu-baseline --steps 2 --warmup 1 > $O/resynth.json 2> /dev/null
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/resynth_f -- python3 $R/bench.py --mode resynth --full --no-cpu-baseline --steps 1 --warmup 1 > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/resynth_w -- python3 $R/bench.py --mode resynth --full --no-cpu-baseline --steps 1 --warmup 1 > /dev/null 2>&1
 echo "resynth done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/dstep -- python3 $R/tools/dstep_bench.py 5 > $O/dstep.txt 2>&1
 echo "dstep done"
