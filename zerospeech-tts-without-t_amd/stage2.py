@@ -19,35 +19,9 @@ import torch
 from . import _lib as L
 from . import layers, parallel
 from .layers import join_side
+from .optim import NetOpt, softmax_ce
 
 G_MODES = ('naive', 'targeted', 'targeted_residual', 'spectrogram')
-
-
-class NetOpt(object):
-    """clip_grad_norm_(net, max_norm) + Adam(lr, betas) over ONE net's flat parameter buffer (zs_sqnorm + zs_adam_clip)."""
-
-    def __init__(self, net, lr, betas=(0.5, 0.9)):
-        self.net, self.lr, self.betas, self.t = net, float(lr), betas, 0
-        flat, _ = net.flat_params()
-        dev = flat.device
-        self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat)
-        self.sq = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.part = torch.zeros(1024, dtype=torch.float64, device=dev)
-        self.reducer = parallel.GradReducer()
-
-    def step(self, max_norm):
-        flat, gflat = self.net.flat_params()
-        st = torch.cuda.current_stream(flat.device).cuda_stream
-        if parallel.world_size() > 1:
-            self.reducer.start(gflat)
-            self.reducer.finish()
-        L.check(L.lib().zs_sqnorm(L.ptr(gflat), gflat.numel(), L.ptr(self.part), L.ptr(self.sq), st), 'zs_sqnorm')
-        self.t += 1
-        b1, b2 = self.betas
-        L.call('zs_adam_clip', 'ZsAdam', st, p=L.ptr(flat), g=L.ptr(gflat), m=L.ptr(self.m), v=L.ptr(self.v), n=flat.numel(), lr=self.lr,
-               beta1=b1, beta2=b2, eps=1e-8, bc1=1.0 - b1 ** self.t, bc2=1.0 - b2 ** self.t, sumsq=L.ptr(self.sq),
-               max_norm=float(max_norm) if max_norm else 0.0, write_clipped_grad=0, grad_scale=self.reducer.scale)
-        self.net.mark_dirty()
 
 
 class PatchGANStep(object):
@@ -128,14 +102,8 @@ class PatchGANStep(object):
 
     def _ce(self, logits, c, grad_scale):
         """CE(logits, c - shift) (trainer.py:297-304, shift=True) -> dlogits fp32 [B, n_class] * grad_scale; loss / #correct on device."""
-        B, n = logits.shape
         tgt = ((c - self.shift) if self.shift else c).contiguous()
-        lg = logits.contiguous()
-        dl = torch.zeros(B, n, dtype=torch.float32, device=self.device)
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        L.call('zs_softmax_ce', 'ZsSoftmaxCE', st, logits=L.ptr(lg), ld=n, target=L.ptr(tgt), B=B, n_class=n, loss_out=L.ptr(self.loss_clf),
-               dlogits=L.ptr(dl), ldg=n, grad_scale=float(grad_scale), correct_out=L.ptr(self.correct))
-        return dl
+        return softmax_ce(self.D._engine().ctx, logits, tgt, self.loss_clf, self.correct, grad_scale)
 
     # ---- D step -----------------------------------------------------------------------------------------------------------------
     def d_step(self, x_s, x_t, c_t, alpha=None, masks=None, update=True, x_gen=None, **gen_kw):

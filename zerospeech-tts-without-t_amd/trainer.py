@@ -21,7 +21,8 @@ from . import layers
 from .layers import Act, join_side
 from .model import Decoder, Encoder, SpeakerClassifier, Spectrogram_Patcher
 from .patch import PatchDiscriminator, TargetClassifier
-from .stage2 import AutolockerStep, NetOpt, PatchGANStep
+from .optim import NetOpt, softmax_ce
+from .stage2 import AutolockerStep, PatchGANStep
 from .utils import Logger
 
 TCLF_CLASSES = 3                       # TargetClassifier(n_class=3): V001, V002, 'None' (trainer.py:97, convert.py:402-407)
@@ -41,16 +42,10 @@ class AEStep(object):
 
     def __init__(self, encoder, decoder, lr=1e-4, betas=(0.5, 0.9), max_grad_norm=5.0, use_graph=None):
         self.Encoder, self.Decoder = encoder, decoder
-        self.lr, self.betas, self.max_grad_norm = float(lr), betas, float(max_grad_norm)
-        self.adam_step = 0
-        self._opt = {}
+        self.adam_step = 0                   # the pair's Adam step count (on the device: _step_dev)
+        self.opt = {name: NetOpt(net, lr, betas, max_grad_norm, reduce=False) for name, net in (('enc', encoder), ('dec', decoder))}
         dev = encoder.flat_params()[0].device
         self.device = dev
-        for name, net in (('enc', encoder), ('dec', decoder)):
-            flat, gflat = net.flat_params()
-            self._opt[name] = dict(m=torch.zeros_like(flat), v=torch.zeros_like(flat),
-                                   sq=torch.zeros(1, dtype=torch.float32, device=dev),
-                                   part=torch.zeros(1024, dtype=torch.float64, device=dev))
         self._loss = torch.zeros(1, dtype=torch.float32, device=dev)
         self._lpart = torch.zeros(1024, dtype=torch.float32, device=dev)
         self._seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)      # uint64 bits, advanced by zs_step_counters
@@ -139,9 +134,8 @@ class AEStep(object):
 
     def _do_action(self, a):
         """Execute a 'reduce' / 'wait' action (the 'run' / 'update' actions are launches: eager or captured)."""
-        net = self.Decoder if a[1] == 'dec' else self.Encoder
         if a[0] == 'reduce':
-            self.reducer.start(net.flat_params()[1][a[2]:a[3]], tag=a[1])
+            self.reducer.start(self.opt[a[1]].net.flat_params()[1][a[2]:a[3]], tag=a[1])
         elif a[0] == 'wait':
             self.reducer.finish(a[1])
 
@@ -182,7 +176,7 @@ class AEStep(object):
                 if a[0] == 'run':
                     a[1]()
                 elif a[0] == 'update':
-                    self._net_device_update(a[1], self.Decoder if a[1] == 'dec' else self.Encoder)
+                    self._device_update(a[1])
                 else:
                     self._do_action(a)
             self.adam_step += 1
@@ -195,17 +189,9 @@ class AEStep(object):
         self._seg_encbwd()
         self._optimizer_device_step()
 
-    def _net_device_update(self, name, net):
+    def _device_update(self, name):
         """Per-net clip (utils.py:53-55) + Adam with the step count read from device memory + re-pack, on the current stream."""
-        o = self._opt[name]
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        flat, gflat = net.flat_params()
-        L.check(L.lib().zs_sqnorm(L.ptr(gflat), gflat.numel(), L.ptr(o['part']), L.ptr(o['sq']), st), 'zs_sqnorm')
-        b1, b2 = self.betas
-        L.call('zs_adam_clip', 'ZsAdam', st, p=L.ptr(flat), g=L.ptr(gflat), m=L.ptr(o['m']), v=L.ptr(o['v']),
-               n=flat.numel(), lr=self.lr, beta1=b1, beta2=b2, eps=1e-8, bc1=1.0, bc2=1.0, sumsq=L.ptr(o['sq']),
-               max_norm=self.max_grad_norm, write_clipped_grad=0, step_ptr=L.ptr(self._step_dev), grad_scale=self.reducer.scale)
-        net.repack()
+        self.opt[name].device_step(L.ptr(self._step_dev))
 
     def _early_decoder_update(self):
         """Single rank: the decoder's gradients are final once its backward (main stream) and its weight gradients (side
@@ -218,20 +204,19 @@ class AEStep(object):
         for ev in layers.side_events(self.device):
             os_.wait_event(ev)
         with torch.cuda.stream(os_):
-            self._net_device_update('dec', self.Decoder)
+            self._device_update('dec')
         self._dec_updated = True
 
     def _optimizer_device_step(self):
         """clip + Adam with the step count read from device memory, then re-pack the GEMM operands."""
-        if getattr(self, '_dec_updated', False):
-            self._net_device_update('enc', self.Encoder)
+        self._device_update('enc')
+        if self._dec_updated:
             ev = torch.cuda.Event()
             ev.record(layers.opt_stream(self.device))
             torch.cuda.current_stream(self.device).wait_event(ev)
             self._dec_updated = False
         else:
-            self._net_device_update('enc', self.Encoder)
-            self._net_device_update('dec', self.Decoder)
+            self._device_update('dec')
         self.adam_step += 1
 
     def _graph_step(self, x_btf, c, multi):
@@ -343,7 +328,7 @@ class AEStep(object):
                 first[0] = False
                 plan.append(('graph', capture(seg)))
             elif a[0] == 'update':
-                plan.append(('graph', capture(lambda n=a[1]: self._net_device_update(n, self.Decoder if n == 'dec' else self.Encoder))))
+                plan.append(('graph', capture(lambda n=a[1]: self._device_update(n))))
             else:
                 plan.append(a)
         return {'graphs': graphs, 'x': xs, 'c': cs, 'plan': plan}
@@ -368,29 +353,14 @@ class AEStep(object):
         """Squared per-net gradient norms as device scalars (Encoder, Decoder are clipped separately).  With more than one
         rank the gradient buffers hold the SUM over ranks after the reduce (the 1/world is applied inside zs_adam_clip):
         these are the squared norms of that sum, i.e. world^2 times those of the averaged gradient."""
-        out = []
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        for name, net in (('enc', self.Encoder), ('dec', self.Decoder)):
-            o = self._opt[name]
-            _, gflat = net.flat_params()
-            L.check(L.lib().zs_sqnorm(L.ptr(gflat), gflat.numel(), L.ptr(o['part']), L.ptr(o['sq']), st), 'zs_sqnorm')
-            out.append(o['sq'])
-        return out
+        return [self.opt['enc'].sqnorm(), self.opt['dec'].sqnorm()]
 
     def optimizer_step(self):
         """grad_clip([Encoder, Decoder], max_grad_norm) + ae_opt.step()  (trainer.py:331-332)."""
         self.grad_norms()
         self.adam_step += 1
-        b1, b2 = self.betas
-        bc1, bc2 = 1.0 - b1 ** self.adam_step, 1.0 - b2 ** self.adam_step
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        for name, net in (('enc', self.Encoder), ('dec', self.Decoder)):
-            o = self._opt[name]
-            flat, gflat = net.flat_params()
-            L.call('zs_adam_clip', 'ZsAdam', st, p=L.ptr(flat), g=L.ptr(gflat), m=L.ptr(o['m']), v=L.ptr(o['v']),
-                   n=flat.numel(), lr=self.lr, beta1=b1, beta2=b2, eps=1e-8, bc1=bc1, bc2=bc2, sumsq=L.ptr(o['sq']),
-                   max_norm=self.max_grad_norm, write_clipped_grad=0, grad_scale=self.reducer.scale)
-            net.mark_dirty()
+        self.opt['enc'].adam(self.adam_step)
+        self.opt['dec'].adam(self.adam_step)
         self._step_dev.fill_(self.adam_step)
 
 
@@ -481,34 +451,22 @@ class ClfStep(object):
 
     def __init__(self, ae, classifier, lr=1e-4, betas=(0.5, 0.9), max_grad_norm=5.0):
         self.ae, self.clf = ae, classifier
-        self.lr, self.betas, self.max_grad_norm = float(lr), betas, float(max_grad_norm)
-        self.adam_step = 0
-        dev = ae.device
-        self.device = dev
-        flat, _ = classifier.flat_params()
-        self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat)
-        self.sq = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.part = torch.zeros(1024, dtype=torch.float64, device=dev)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.correct = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._dl = None
+        self.device = ae.device
+        self.opt = NetOpt(classifier, lr, betas, max_grad_norm, reduce=False)     # reduced in d_step, even without an update
+        self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.correct = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    adam_step = property(lambda self: self.opt.t)
 
     def _classify(self, logits_act, c, grad_scale, seed, drop_masks=None):
-        """enc logits Act fp32 [B,T',n_lin] (the encoder's pre-activation: 2E, E or E^2 columns by enc_mode) -> CE loss (device
-        scalar), fills self._dl = grad_scale * dCE/dlogits."""
+        """enc logits Act fp32 [B,T',n_lin] (the encoder's pre-activation: 2E, E or E^2 columns by enc_mode) -> (classifier engine,
+        grad_scale * dCE/dlogits fp32 [B, n_class]); the CE loss and #correct in self.loss / self.correct."""
         clf = self.clf
         clf.train()
         ce = clf._engine()
-        B, T = logits_act.B, logits_act.T
         x = clf.input_act(logits_act.valid())
         out = ce.forward(x, True, seed=seed, drop_masks=drop_masks)
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        if self._dl is None or self._dl.shape != (B, out.ld):
-            self._dl = torch.zeros(B, out.ld, dtype=torch.float32, device=self.device)
-        L.call('zs_softmax_ce', 'ZsSoftmaxCE', st, logits=out.ptr(), ld=out.ld, target=L.ptr(c), B=B, n_class=clf.n_class,
-               loss_out=L.ptr(self.loss), dlogits=L.ptr(self._dl), ldg=out.ld, grad_scale=float(grad_scale),
-               correct_out=L.ptr(self.correct))                                              # cal_loss / cal_acc, trainer.py:297-313
-        return ce, out
+        return ce, softmax_ce(ce.ctx, out.valid()[:, 0], c, self.loss, self.correct, grad_scale)
 
     def d_step(self, x_btf, c, alpha_dis=1.0, seed=None, update=True, noise=None, noise_kind=2, drop_masks=None, clf_masks=None):
         """One classifier update (trainer.py:352-366 / 396-411).  Returns (loss_clf, n_correct) device scalars."""
@@ -518,8 +476,8 @@ class ClfStep(object):
         if seed is None:
             seed = (self.adam_step + 1) * 0x9E3779B97F4A7C15 % (1 << 62) + 17 * parallel.rank()
         _, _, logits = ee.forward(x_btf, True, noise=noise, noise_kind=noise_kind, seed=seed, drop_masks=drop_masks)
-        ce, out = self._classify(logits, c, alpha_dis, seed + 1, clf_masks)
-        ce.backward(self._dl, out.ld, need_dx=False)
+        ce, dl = self._classify(logits, c, alpha_dis, seed + 1, clf_masks)
+        ce.backward(dl, dl.stride(0), need_dx=False)
         join_side(self.device)
         if parallel.world_size() > 1:
             self.ae.reducer.start(self.clf.flat_params()[1])
@@ -529,15 +487,7 @@ class ClfStep(object):
         return self.loss, self.correct
 
     def optimizer_step(self):
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        flat, gflat = self.clf.flat_params()
-        L.check(L.lib().zs_sqnorm(L.ptr(gflat), gflat.numel(), L.ptr(self.part), L.ptr(self.sq), st), 'zs_sqnorm')
-        self.adam_step += 1
-        b1, b2 = self.betas
-        L.call('zs_adam_clip', 'ZsAdam', st, p=L.ptr(flat), g=L.ptr(gflat), m=L.ptr(self.m), v=L.ptr(self.v), n=flat.numel(),
-               lr=self.lr, beta1=b1, beta2=b2, eps=1e-8, bc1=1.0 - b1 ** self.adam_step, bc2=1.0 - b2 ** self.adam_step,
-               sumsq=L.ptr(self.sq), max_norm=self.max_grad_norm, write_clipped_grad=0, grad_scale=self.ae.reducer.scale)
-        self.clf.mark_dirty()
+        self.opt.step()
 
     def g_step(self, x_btf, c, alpha, seed=None, update=True, noise=None, noise_kind=2, drop_masks=None, clf_masks=None):
         """One autoencoder update with the adversarial term (trainer.py:427-447): loss = loss_rec - alpha * loss_clf.
@@ -557,9 +507,9 @@ class ClfStep(object):
         L.call('zs_l1_loss', 'ZsL1Loss', st, dtype=ctx.dt, x_dec=xdec.ptr(), ld_dec=xdec.ld, x=L.ptr(x_btf), ldx=F,
                rows=B * xdec.T, F=F, dlogits=dlogit.ptr(), ldg=dlogit.ld, fill_cols=dlogit.ld, partial=L.ptr(ae._lpart),
                loss_out=L.ptr(ae._loss), grad_scale=1.0)
-        ce, out = self._classify(logits, c, -float(alpha), seed + 1, clf_masks)          # maximise the classification loss
+        ce, dl = self._classify(logits, c, -float(alpha), seed + 1, clf_masks)           # maximise the classification loss
         dbits = de.backward(dlogit)
-        dx = ce.backward(self._dl, out.ld, need_dx=True, param_grads=False)
+        dx = ce.backward(dl, dl.stride(0), need_dx=True, param_grads=False)
         multi = parallel.multi_rank()
         if multi:
             join_side(self.device)
@@ -599,12 +549,11 @@ class TclfStep(object):
     the device (no host sync); the targets are range-checked on the host by tclf_labels before a batch is copied over."""
 
     def __init__(self, classifier, lr, max_grad_norm, shift):
-        self.clf, self.max_grad_norm, self.shift = classifier, float(max_grad_norm), int(shift)
-        self.opt = NetOpt(classifier, lr, betas=(0.5, 0.9))
-        self.device = classifier.flat_params()[0].device
-        self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.correct = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._dl = None
+        self.clf, self.shift = classifier, int(shift)
+        self.opt = NetOpt(classifier, lr, betas=(0.5, 0.9), max_norm=max_grad_norm)
+        dev = classifier.flat_params()[0].device
+        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.correct = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def step(self, x_btf, c, masks=None, update=True):
         """x_btf fp32 [B, T, 513], c int64 [B] raw speaker ids on the device.  masks: optional six [B, C] Dropout2d keep masks.
@@ -612,20 +561,14 @@ class TclfStep(object):
         clf = self.clf
         clf.train()
         eng = clf._engine()
-        B = x_btf.shape[0]
         y = c.masked_fill(c < 100, 102) - self.shift                           # c[c < 100] = 102; c - shift_c
         eng.zero_grads()
         _, logits = eng.forward(x_btf.contiguous(), 'tclf', True, masks=masks, classify=True, need_val=False)
-        if self._dl is None or self._dl.shape[0] != B:
-            self._dl = torch.zeros(B, clf.n_class, dtype=torch.float32, device=self.device)
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        L.call('zs_softmax_ce', 'ZsSoftmaxCE', st, logits=L.ptr(logits), ld=logits.stride(0), target=L.ptr(y), B=B, n_class=clf.n_class,
-               loss_out=L.ptr(self.loss), dlogits=L.ptr(self._dl), ldg=clf.n_class, grad_scale=1.0,
-               correct_out=L.ptr(self.correct))                                 # cal_loss / cal_acc (trainer.py:297-313)
-        eng.backward('tclf', dlogits=self._dl, need_dx=False, param_grads=True)
+        dl = softmax_ce(eng.ctx, logits, y, self.loss, self.correct)
+        eng.backward('tclf', dlogits=dl, need_dx=False, param_grads=True)
         eng.flush_grads()
         if update:
-            self.opt.step(self.max_grad_norm)
+            self.opt.step()
         return self.loss, self.correct
 
 
