@@ -186,6 +186,25 @@ def test_conv_backward(zs, dtype, case, gemm_variant):
     _close('db', l.gb, b.grad, _tol(dtype))
 
 
+def test_dgrad_stride2_rejects_epilogue_operands(zs):
+    """The stride-2 (k > 1) data gradient runs by output parity and has no epilogue: each operand it cannot apply raises."""
+    L, layers = zs
+    ctx = _ctx(layers, 'fp32')
+    B, T, Cin, Cout = 2, 16, 32, 48
+    l = _mk_conv(layers, ctx, torch.randn(Cout, Cin, 5), torch.zeros(Cout), stride=2)
+    assert l.parity
+    dY = _to_act(layers, ctx, 'dy', torch.randn(B, l.t_out(T), Cout))
+    gp = ctx.act('gp', B, T + l.pad_l + l.pad_r, Cin)
+    src = ctx.act('src', B, T + l.pad_l + l.pad_r, Cin)
+    sums = torch.zeros(B * Cin, dtype=torch.float32, device=ctx.device)
+    for kw in (dict(dact_src=src, slope=0.01), dict(add_src=src), dict(colsum=(L.ptr(sums), Cin, 0)), dict(n_cols=16),
+               dict(n_off=16)):
+        with pytest.raises(ValueError, match='stride-2 dgrad'):
+            l.dgrad(dY, T, gp, **kw)
+    l.dgrad(dY, T, gp)                       # the plain call still runs
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize('dtype', DTYPES)
 def test_wgrad_split2_and_shift(zs, dtype, gemm_variant):
     L, layers = zs

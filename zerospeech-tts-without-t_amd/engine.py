@@ -5,24 +5,37 @@ DecoderEngine  <->  Decoder.forward          (reference model/model.py:344-365) 
 PatcherEngine  <->  Spectrogram_Patcher.forward (reference model/model.py:532-549) and its backward to the parameters
 Every arithmetic step is a libzs_amd.so kernel; torch only owns the memory.
 """
+import functools
 import os
 import torch
 
 from . import _lib as L
-from .layers import Act, ConvLayer, GruLayer, colsum_ok, fork_side, join_side, rup
+from .layers import (Act, ConvLayer, GruLayer, cast_rows, colsum_ok, fork_side, grad_combine, instnorm_bwd, instnorm_fwd, join_side,
+                     next_uid, rup)
 
 LRELU = L.ZS_ACT_LRELU
-EPS_IN = 1e-5
-_UID = [0]
-
-
-def _uid():
-    _UID[0] += 1
-    return _UID[0]
 
 
 def _half_up(t):
     return (t + 1) // 2
+
+
+def _norm_stats(ctx, training, prefix, key, n):
+    """The InstanceNorm statistics (mean, rstd) a training pass keeps for its backward, as buffers prefix + 'mean' / 'rstd' + key
+    of ctx; (None, None) otherwise."""
+    if not training:
+        return None, None
+    return ctx.f32(prefix + 'mean' + key, n), ctx.f32(prefix + 'rstd' + key, n)
+
+
+def ragged_lengths(who, lengths, training, B, T, lo):
+    """A ragged batch's host `lengths` checked (inference only, B values in [lo, T]) -> int32 tensor [B] on the host."""
+    if training:
+        raise L.ZsError('%s: ragged batches are an inference feature' % who)
+    l0 = torch.as_tensor(lengths, dtype=torch.int32).reshape(-1)
+    if l0.numel() != B or int(l0.max()) > T or int(l0.min()) < lo:
+        raise L.ZsError('%s: lengths must be %d values in [%d, %d]' % (who, B, lo, T))
+    return l0
 
 
 # enc_mode -> discretiser of zs_gumbel_st_fwd / _bwd ('multilabel_binary' runs zs_mbv_fwd / _bwd)
@@ -38,7 +51,7 @@ class EncoderEngine(object):
     def __init__(self, ctx, P, G, c_in, c_h1, c_h2, c_h3, enc_size, ns, dp, seg_len, enc_mode='multilabel_binary'):
         """P / G: dicts name -> fp32 parameter / gradient tensors (reference state_dict names)."""
         self.ctx = ctx
-        self.uid = _uid()
+        self.uid = next_uid()
         self.c_in, self.c1, self.c2, self.H, self.E = c_in, c_h1, c_h2, c_h3, enc_size
         self.mode = enc_mode
         self.n_lin = linear_width(enc_mode, enc_size)
@@ -46,8 +59,7 @@ class EncoderEngine(object):
         self.pad_mode = L.ZS_PAD_REFLECT if seg_len >= 64 else L.ZS_PAD_ZERO     # model/model.py:38
         if c_h1 % 8 or c_h2 % 8:
             raise ValueError('c_h1 and c_h2 must be multiples of 8 (16-byte rows)')
-        mk = lambda n, **kw: ConvLayer(ctx, P[n + '.weight'], P[n + '.bias'], G[n + '.weight'], G[n + '.bias'],
-                                       pad_mode=self.pad_mode, name=n, **kw)
+        mk = functools.partial(ConvLayer.from_params, ctx, P, G, pad_mode=self.pad_mode)
         self.conv1s = [mk('conv1s.%d' % i) for i in range(7)]
         self.conv2 = mk('conv2')
         self.convs = [(mk('conv%d' % a), mk('conv%d' % b, stride=2)) for a, b in ((3, 4), (5, 6), (7, 8))]
@@ -84,11 +96,7 @@ class EncoderEngine(object):
         B, T, F = x.shape
         Ls = [None] * 4
         if lengths is not None:
-            if training:
-                raise L.ZsError('EncoderEngine: ragged batches are an inference feature')
-            l0 = torch.as_tensor(lengths, dtype=torch.int32).reshape(-1)
-            if l0.numel() != B or int(l0.max()) > T or int(l0.min()) < 9:
-                raise L.ZsError('EncoderEngine: lengths must be %d values in [9, %d]' % (B, T))     # MIN_LEN (convert.py:36)
+            l0 = ragged_lengths('EncoderEngine', lengths, training, B, T, 9)                  # MIN_LEN (convert.py:36)
             l1 = (l0 + 1) // 2; l2 = (l1 + 1) // 2; l3 = (l2 + 1) // 2
             self.last_lengths = l3
             ld = torch.stack([l0, l1, l2, l3]).to(c.device, non_blocking=True)
@@ -104,12 +112,13 @@ class EncoderEngine(object):
         tag = '_%d_%d_%d' % (self.uid, B, T) + ksfx
         tp = {'B': B, 'T': T, 'Ts': Ts, 'training': training, 'seed': seed, 'masks': masks, 'dp': dp, 'seed_ptr': seed_ptr,
               'tag': tag, 'ksfx': ksfx}
+        # norm k (InstanceNorm + Dropout + residual, model/model.py:421-427, 434-437): dropout stream k + 1 or drop_masks[k]
+        drop = dict(p=dp, seed=seed, seed_ptr=seed_ptr)
+        skey = lambda k, Tk: '%d_%d_%d_%d' % (self.uid, k, B, Tk) + ksfx
 
         xin = c.act('e_xin' + tag, B, T, F)
         cat = c.act('e_cat' + tag, B, T, self.ncat)
-        L.call('zs_cast_rows', 'ZsCastRows', st, dtype=c.dt, src=L.ptr(x), ld_src=F, src_f32=1, dst=xin.ptr(), ld_dst=xin.ld,
-               dst_f32=0, col_off=0, rows=B * T, cols=F, fill_cols=xin.ld, act=L.ZS_ACT_NONE,
-               dst2=cat.ptr(), ld_dst2=cat.ld, col_off2=7 * c1, fill_cols2=cat.ld - 7 * c1, act2=LRELU, slope2=ns)    # :445-446
+        cast_rows(c, L.ptr(x), F, xin, dst2=cat, col_off2=7 * c1, act2=LRELU, slope2=ns)                         # :445-446
         if c.overlap_wgrad and B * T >= 4096:
             # the seven bank convs are independent and each fills half the chip at most (N = 128): run them side by side
             sts = fork_side(c.device)
@@ -123,16 +132,20 @@ class EncoderEngine(object):
         y2 = c.act('e_y2' + tag, B, T, c2)
         self.conv2.fwd(cat, out=y2, act=LRELU, slope=ns)                                                      # :447
         a = c.act('e_a0' + tag, B, T, c2)
-        st0 = self._in(y2, a, tp, 0, res_mode=L.ZS_RES_NONE, lengths=Ls[0])
-        tp.update(xin=xin, cat=cat, y2=y2, a0=a, st0=st0, blocks=[], dense=[])
+        mean, rstd = _norm_stats(c, training, 'e_', skey(0, T), B * y2.ld)
+        instnorm_fwd(c, y2, a, mean, rstd, self.pad_mode, lengths=Ls[0], stream_id=1, mask=masks[0], **drop)
+        tp.update(xin=xin, cat=cat, y2=y2, a0=a, st0=(mean, rstd, 0), blocks=[], dense=[])
         for i, (la, lb) in enumerate(self.convs):                                                            # :448-450
             ya = c.act('e_ya%d' % i + tag, B, Ts[i], c2)
             la.fwd(a, out=ya, act=LRELU, slope=ns, lengths=Ls[i])
             yb = c.act('e_yb%d' % i + tag, B, Ts[i + 1], c2)
             lb.fwd(ya, out=yb, act=LRELU, slope=ns, lengths=Ls[i])
             an = c.act('e_a%d' % (i + 1) + tag, B, Ts[i + 1], c2)
-            stt = self._in(yb, an, tp, 1 + i, res_mode=L.ZS_RES_AVGPOOL2, res=a, lengths=Ls[i + 1], res_lengths=Ls[i])
-            tp['blocks'].append((a, ya, yb, stt))
+            k = 1 + i
+            mean, rstd = _norm_stats(c, training, 'e_', skey(k, Ts[i + 1]), B * yb.ld)
+            instnorm_fwd(c, yb, an, mean, rstd, self.pad_mode, res_mode=L.ZS_RES_AVGPOOL2, res=a, lengths=Ls[i + 1],
+                         res_lengths=Ls[i], stream_id=k + 1, mask=masks[k], **drop)
+            tp['blocks'].append((a, ya, yb, (mean, rstd, k)))
             a = an
         cat2 = c.act('e_cat2' + tag, B, T4, c2 + 2 * H)
         for j, (la, lb) in enumerate(self.dense):                                                            # :452-453
@@ -141,8 +154,11 @@ class EncoderEngine(object):
             d2 = c.act('e_d2%d' % j + tag, B, T4, c2)
             lb.fwd(d1, out=d2, act=LRELU, slope=ns)
             out = c.act('e_do%d' % j + tag, B, T4, c2) if j == 0 else Act(cat2.t, B, T4, c2, cat2.ld, 0, rup(c2, 32))
-            stt = self._in(d2, out, tp, 4 + j, res_mode=L.ZS_RES_IDENTITY, res=a, lengths=Ls[3])
-            tp['dense'].append((a, d1, d2, stt))
+            k = 4 + j
+            mean, rstd = _norm_stats(c, training, 'e_', skey(k, T4), B * d2.ld)
+            instnorm_fwd(c, d2, out, mean, rstd, self.pad_mode, res_mode=L.ZS_RES_IDENTITY, res=a, lengths=Ls[3], stream_id=k + 1,
+                         mask=masks[k], **drop)
+            tp['dense'].append((a, d1, d2, (mean, rstd, k)))
             a = out
         gi = c.act('e_gi' + tag, B, T4, 6 * H)
         gates = c.raw('e_gates' + tag, B * T4 * 8 * H, c.tdt) if training else None
@@ -170,32 +186,6 @@ class EncoderEngine(object):
         self.tapes[tape] = tp
         return bits, bits_f32[:B * T4 * E].view(B, T4, E), logits
 
-    def _in(self, x, out, tp, k, res_mode, res=None, lengths=None, res_lengths=None):
-        """InstanceNorm + Dropout + residual (model/model.py:421-427, 434-437)."""
-        c = self.ctx
-        B, T, C = x.B, x.T, x.ld
-        mean = rstd = None
-        if tp['training']:
-            mean = c.f32('e_mean%d_%d_%d_%d' % (self.uid, k, B, T) + tp['ksfx'], B * C)
-            rstd = c.f32('e_rstd%d_%d_%d_%d' % (self.uid, k, B, T) + tp['ksfx'], B * C)
-        m = tp['masks'][k]
-        L.call('zs_instnorm_fwd', 'ZsInstNormFwd', c.stream, dtype=c.dt, x=x.ptr(), ldx=x.ld, out=out.ptr(), ldo=out.ld,
-               mean=L.ptr(mean), rstd=L.ptr(rstd), B=B, T=T, C=C, eps=EPS_IN, drop_p=tp['dp'], seed=tp['seed'],
-               stream_id=k + 1, mask=L.ptr(m), mask_ld=(m.shape[-1] if m is not None else 0), res_mode=res_mode,
-               res=(res.ptr() if res is not None else None), ldres=(res.ld if res is not None else 0),
-               T_res=(res.T if res is not None else 0), res_pad_mode=self.pad_mode, seed_ptr=tp.get('seed_ptr'),
-               lengths=L.ptr(lengths), res_lengths=L.ptr(res_lengths))
-        return (mean, rstd, k)
-
-    def _in_bwd(self, dout, x, stt, dz, tp):
-        c = self.ctx
-        mean, rstd, k = stt
-        m = tp['masks'][k]
-        L.call('zs_instnorm_bwd', 'ZsInstNormBwd', c.stream, dtype=c.dt, dout=dout.ptr(), ldd=dout.ld, x=x.ptr(), ldx=x.ld,
-               mean=L.ptr(mean), rstd=L.ptr(rstd), dz=dz.ptr(), ldz=dz.ld, B=x.B, T=x.T, C=x.ld, drop_p=tp['dp'],
-               seed=tp['seed'], stream_id=k + 1, mask=L.ptr(m), mask_ld=(m.shape[-1] if m is not None else 0), slope=self.ns,
-               seed_ptr=tp.get('seed_ptr'))
-
     # ------------------------------------------------------------------------------------------
     def backward(self, dbits, dlogits_extra=None):
         """dbits: Act [B,T',E] gradient w.r.t. enc_act (may be None); dlogits_extra: Act [B,T',n_lin] gradient w.r.t. the
@@ -217,6 +207,7 @@ class EncoderEngine(object):
         st = c.stream
         tag = tp['tag']
         cat2 = tp['cat2']
+        drop, masks = dict(p=tp['dp'], seed=tp['seed'], seed_ptr=tp['seed_ptr']), tp['masks']     # as in forward()
         dlog = c.act('e_dlog' + tag, B, T4, self.n_lin)
         if dbits is not None:
             if self.mode == 'multilabel_binary':
@@ -243,9 +234,9 @@ class EncoderEngine(object):
         self.gru.bwd(dcat2, c2, cat2, c2, tp['gates'], gin, dgi, dgh, da, add_src=dcat2, param_grads=pg)
         for j in (1, 0):
             la, lb = self.dense[j]
-            xin, d1, d2, stt = tp['dense'][j]
+            xin, d1, d2, (mean, rstd, k) = tp['dense'][j]
             dz2 = c.act('e_dz2%d' % j + tag, B, T4, c2)          # unique per block: read later by the side-stream wgrad
-            self._in_bwd(da, d2, stt, dz2, tp)
+            instnorm_bwd(c, da, d2, mean, rstd, dz2, ns, stream_id=k + 1, mask=masks[k], **drop)
             if pg:
                 lb.wgrad(dz2, d1)
             dz1 = c.act('e_dz1%d' % j + tag, B, T4, c2)
@@ -257,24 +248,25 @@ class EncoderEngine(object):
             da = dn
         for i in (2, 1, 0):
             la, lb = self.convs[i]
-            a, ya, yb, stt = tp['blocks'][i]
+            a, ya, yb, (mean, rstd, k) = tp['blocks'][i]
             dzb = c.act('e_dzb%d' % i + tag, B, Ts[i + 1], c2)
-            self._in_bwd(da, yb, stt, dzb, tp)
+            instnorm_bwd(c, da, yb, mean, rstd, dzb, ns, stream_id=k + 1, mask=masks[k], **drop)
             if pg:
                 lb.wgrad(dzb, ya)
             gp = c.act('e_gp%d' % i + tag, B, Ts[i] + 4, c2)
             lb.dgrad(dzb, Ts[i], gp)
             dza = c.act('e_dza%d' % i + tag, B, Ts[i], c2)
-            self._combine(gp, Ts[i], 2, 2, dza, dact=ya)
+            grad_combine(c, gp, Ts[i], 2, 2, self.pad_mode, gp.ld, dza, ns, dact=ya)
             if pg:
                 la.wgrad(dza, a)
             la.dgrad(dza, Ts[i], gp)
             dn = c.act('e_da%d' % i + tag, B, Ts[i], c2)
-            self._combine(gp, Ts[i], 2, 2, dn, res_mode=L.ZS_RES_AVGPOOL2, res=da)
+            grad_combine(c, gp, Ts[i], 2, 2, self.pad_mode, gp.ld, dn, ns, res_mode=L.ZS_RES_AVGPOOL2, res=da)
             da = dn
         y2, cat, xin = tp['y2'], tp['cat'], tp['xin']
         dz = c.act('e_dzy2' + tag, B, T, c2)
-        self._in_bwd(da, y2, tp['st0'], dz, tp)
+        mean, rstd, k = tp['st0']
+        instnorm_bwd(c, da, y2, mean, rstd, dz, ns, stream_id=k + 1, mask=masks[k], **drop)
         dcat = c.act('e_dcat' + tag, B, T, self.ncat)
         if not pg:
             # every column: the bank's 7*c_h1 (through its data gradient) and the pass-through ones (the gradient w.r.t. the input)
@@ -347,26 +339,18 @@ class EncoderEngine(object):
         for i, l in enumerate(self.conv1s):
             l.wgrad(dcat.sub(i * self.c1, self.c1), xin)
 
-    def _combine(self, gp, T, pl, pr, out, res_mode=L.ZS_RES_NONE, res=None, dact=None):
-        c = self.ctx
-        L.call('zs_grad_combine', 'ZsGradCombine', c.stream, dtype=c.dt, gp=gp.ptr(), ldg=gp.ld, pad_left=pl, pad_right=pr,
-               pad_mode=self.pad_mode, B=gp.B, T=T, C=gp.ld, res_mode=res_mode, res=(res.ptr() if res is not None else None),
-               ldres=(res.ld if res is not None else 0), dact_src=(dact.ptr() if dact is not None else None),
-               dact_ld=(dact.ld if dact is not None else 0), slope=self.ns, out=out.ptr(), ldo=out.ld, unshuffle=0)
-
 
 class DecoderEngine(object):
     def __init__(self, ctx, P, G, c_in, c_out, c_h, c_a, ns, seg_len, output_mask=False):
         self.ctx = ctx
-        self.uid = _uid()
+        self.uid = next_uid()
         self.E, self.F, self.ch, self.n_spk = c_in, c_out, c_h, c_a
         self.ns = float(ns)
         self.pad_mode = L.ZS_PAD_REFLECT if seg_len >= 64 else L.ZS_PAD_ZERO
         self.out_act = L.ZS_ACT_TANH if output_mask else L.ZS_ACT_SIGMOID
         if c_h % 32:
             raise ValueError('Decoder c_h must be a multiple of 32 (got %d)' % c_h)
-        mk = lambda n, **kw: ConvLayer(ctx, P[n + '.weight'], P[n + '.bias'], G[n + '.weight'], G[n + '.bias'],
-                                       pad_mode=self.pad_mode, name=n, **kw)
+        mk = functools.partial(ConvLayer.from_params, ctx, P, G, pad_mode=self.pad_mode)
         self.input_emb = mk('input_emb')
         self.convs = [(mk('conv%d' % a, split2=True), mk('conv%d' % b)) for a, b in ((1, 2), (3, 4), (5, 6))]
         self.dense = [(mk('dense%d' % a), mk('dense%d' % b)) for a, b in ((1, 2), (3, 4))]
@@ -394,11 +378,7 @@ class DecoderEngine(object):
         B, T0 = bits.B, bits.T
         Ls = [None] * 4
         if lengths is not None:
-            if training:
-                raise L.ZsError('DecoderEngine: ragged batches are an inference feature')
-            l0 = torch.as_tensor(lengths, dtype=torch.int32).reshape(-1)
-            if l0.numel() != B or int(l0.max()) > T0 or int(l0.min()) < 2:
-                raise L.ZsError('DecoderEngine: lengths must be %d values in [2, %d]' % (B, T0))    # reflect pad 1 of conv k3 needs 2 rows
+            l0 = ragged_lengths('DecoderEngine', lengths, training, B, T0, 2)        # reflect pad 1 of conv k3 needs 2 rows
             ld = torch.stack([l0, 2 * l0, 4 * l0, 8 * l0]).to(c.device, non_blocking=True)
             Ls = [ld[i] for i in range(4)]
         tag = '_%d_%d_%d' % (self.uid, B, T0)
@@ -418,7 +398,9 @@ class DecoderEngine(object):
             xn = c.act('d_x%d' % (i + 1) + tag, B, 2 * T, ch)
             xen = c.act('d_xe%d' % (i + 1) + tag, B, 2 * T, ch)
             nxt = emb[i + 1] if i < 2 else emb[3]                                                        # emb2, emb3, then emb4 (:350)
-            stt = self._in(yb, xn, xen, nxt, cidx, L.ZS_RES_UPSAMPLE2, x, training, 'c%d' % i, lengths=Ls[i + 1])
+            stt = _norm_stats(c, training, 'd_', '%d_c%d_%d_%d' % (self.uid, i, B, 2 * T), B * yb.ld)
+            instnorm_fwd(c, yb, xn, *stt, self.pad_mode, res_mode=L.ZS_RES_UPSAMPLE2, res=x, lengths=Ls[i + 1], out2=xen, vec2=nxt,
+                         idx=cidx)
             tp['blocks'].append((x, xe, ya, s, yb, stt, T))
             x, xe, T = xn, xen, 2 * T
         return self._fwd_dense(tp, x, xe, cidx, T, tag, B, training, Ls[3])
@@ -436,7 +418,9 @@ class DecoderEngine(object):
             lb.fwd(y1e, out=y2, act=LRELU, slope=ns)
             xn = c.act('d_dx%d' % j + tag, B, T, ch) if j == 0 else Act(cat3.t, B, T, ch, cat3.ld, 0, ch)
             xen = c.act('d_dxe%d' % j + tag, B, T, ch)
-            stt = self._in(y2, xn, xen, emb[ed] if j == 0 else emb[er], cidx, L.ZS_RES_IDENTITY, x, training, 'd%d' % j, lengths=lengths)
+            stt = _norm_stats(c, training, 'd_', '%d_d%d_%d_%d' % (self.uid, j, B, T), B * y2.ld)
+            instnorm_fwd(c, y2, xn, *stt, self.pad_mode, res_mode=L.ZS_RES_IDENTITY, res=x, lengths=lengths, out2=xen,
+                         vec2=(emb[ed] if j == 0 else emb[er]), idx=cidx)
             tp['dense'].append((x, xe, y1, y1e, y2, stt))
             x, xe = xn, xen
         H = ch // 2
@@ -454,37 +438,6 @@ class DecoderEngine(object):
         tp.update(cat3=cat3, gates=gates, gru_in=xe, h5=h5, T=T)
         self.tape = tp
         return xdec
-
-    def _in(self, x, out, out2, vec2, cidx, res_mode, res, training, key, lengths=None):
-        c = self.ctx
-        B, T, C = x.B, x.T, x.ld
-        mean = rstd = None
-        if training:
-            mean = c.f32('d_mean%d_%s_%d_%d' % (self.uid, key, B, T), B * C)
-            rstd = c.f32('d_rstd%d_%s_%d_%d' % (self.uid, key, B, T), B * C)
-        L.call('zs_instnorm_fwd', 'ZsInstNormFwd', c.stream, dtype=c.dt, x=x.ptr(), ldx=x.ld, out=out.ptr(), ldo=out.ld,
-               out2=out2.ptr(), ldo2=out2.ld, vec2=L.ptr(vec2), vec2_ld=vec2.shape[1], vec2_cols=vec2.shape[1], idx=L.ptr(cidx),
-               mean=L.ptr(mean), rstd=L.ptr(rstd), B=B, T=T, C=C, eps=EPS_IN, drop_p=0.0, res_mode=res_mode, res=res.ptr(),
-               ldres=res.ld, T_res=res.T, res_pad_mode=self.pad_mode, lengths=L.ptr(lengths))
-        return (mean, rstd)
-
-    def _in_bwd(self, dout, x, stt, dz):
-        c = self.ctx
-        L.call('zs_instnorm_bwd', 'ZsInstNormBwd', c.stream, dtype=c.dt, dout=dout.ptr(), ldd=dout.ld, x=x.ptr(), ldx=x.ld,
-               mean=L.ptr(stt[0]), rstd=L.ptr(stt[1]), dz=dz.ptr(), ldz=dz.ld, B=x.B, T=x.T, C=x.ld, drop_p=0.0, slope=self.ns)
-
-    def _combine(self, gp, T, pl, pr, out, emb_i=None, res_mode=L.ZS_RES_NONE, res=None, dact=None, unshuffle=0, C=None):
-        c = self.ctx
-        esum = None
-        if emb_i is not None:                      # per-sample sums for embedding emb_i (finished by zs_emb_scatter)
-            esum = L.ptr(self._embsum, emb_i * gp.B * self.ch)
-        L.call('zs_grad_combine', 'ZsGradCombine', c.stream, dtype=c.dt, gp=gp.ptr(), ldg=gp.ld, pad_left=pl, pad_right=pr,
-               pad_mode=self.pad_mode, B=gp.B, T=T, C=(C if C is not None else self.ch),
-               emb_sum=esum, emb_ld=self.ch, emb_cols=self.ch, res_mode=res_mode,
-               res=(res.ptr() if res is not None else None), ldres=(res.ld if res is not None else 0),
-               dact_src=(dact.ptr() if dact is not None else None), dact_ld=(dact.ld if dact is not None else 0),
-               slope=self.ns, out=(out.ptr() if out is not None else None), ldo=(out.ld if out is not None else 0),
-               unshuffle=unshuffle)
 
     def backward(self, dlogit, need_dbits=True):
         """dlogit: Act [B,T,F] gradient w.r.t. the pre-sigmoid output.  Fills (overwrites) every decoder parameter
@@ -510,7 +463,8 @@ class DecoderEngine(object):
         # the embedding parts of the k = 1 data gradients (per-sample column sums) come out of the GEMM epilogues when whole
         # samples fit a tile (ZsGemmConv.colsum); otherwise a zs_grad_combine pass over the gradient computes them
         fuse = colsum_ok(T) and os.environ.get('ZS_FUSE_COLSUM', '1') == '1'
-        slot = lambda k, col0=0: (L.ptr(self._embsum, k * B * ch), ch, col0)
+        esum = lambda k: L.ptr(self._embsum, k * B * ch)       # per-sample sums for embedding k (finished by zs_emb_scatter)
+        slot = lambda k, col0=0: (esum(k), ch, col0)
         # append_emb's block of dense5 (model/model.py:357) multiplies a vector that is constant over time, so its input gradient
         # is only needed summed over t: sum_t (dz5[b,t] W5e) = (sum_t dz5[b,t]) W5e -- the column sums of dz5 (epilogue of the
         # GEMM that produces it) times the block, a B-row GEMM, instead of a third of dense5's data gradient
@@ -522,15 +476,14 @@ class DecoderEngine(object):
             self.dense5.dgrad(dz5, T, dcat3, n_cols=2 * ch)
             s32 = Act(self._embsum, B, 1, ch, ch, 5 * B * ch)
             sT = c.act('d_s5' + tag, B, 1, ch)
-            L.call('zs_cast_rows', 'ZsCastRows', c.stream, dtype=c.dt, src=s32.ptr(), ld_src=ch, src_f32=1, dst=sT.ptr(), ld_dst=sT.ld,
-                   dst_f32=0, col_off=0, rows=B, cols=ch, fill_cols=sT.ld, act=L.ZS_ACT_NONE)
+            cast_rows(c, s32.ptr(), ch, sT)
             slot4 = Act(self._embsum, B, 1, ch, ch, er * B * ch)
             self.dense5.dgrad(sT, 1, slot4, add_src=slot4, out_f32=True, add_f32=True, n_cols=ch, n_off=2 * ch)
         elif fuse:                                                                           # d emb5 via append_emb: the third
             self.dense5.dgrad(dz5, T, dcat3, colsum=slot(er, 2 * ch), out_cols=2 * ch)        # column block is summed, not stored
         else:
             self.dense5.dgrad(dz5, T, dcat3)
-            self._combine(dcat3.sub(2 * ch, ch), T, 0, 0, None, emb_i=er)
+            grad_combine(c, dcat3.sub(2 * ch, ch), T, 0, 0, self.pad_mode, ch, None, ns, emb_sum=esum(er))
         dgi = c.act('d_dgi' + tag, B, T, 6 * H)
         dgh = c.act('d_dgh' + tag, B, T, 6 * H)
         gp = c.act('d_gpA' + tag, B, T + 2, ch)
@@ -540,26 +493,26 @@ class DecoderEngine(object):
             self.gru.bwd(dcat3, ch, cat3, ch, tp['gates'], tp['gru_in'], dgi, dgh, dx, add_src=dcat3.sub(0, ch), colsum=slot(er))
         else:
             self.gru.bwd(dcat3, ch, cat3, ch, tp['gates'], tp['gru_in'], dgi, dgh, gpv)
-            self._combine(gpv, T, 0, 0, dx, emb_i=er, res_mode=L.ZS_RES_IDENTITY, res=dcat3.sub(0, ch))
+            grad_combine(c, gpv, T, 0, 0, self.pad_mode, ch, dx, ns, emb_sum=esum(er), res_mode=L.ZS_RES_IDENTITY, res=dcat3.sub(0, ch))
         for j in (1, 0):
             la, lb = self.dense[j]
             xin, xe, y1, y1e, y2, stt = tp['dense'][j]
             dz2 = c.act('d_dz2%d' % j + tag, B, T, ch)           # unique per block: read later by the side-stream wgrad
-            self._in_bwd(dx, y2, stt, dz2)
+            instnorm_bwd(c, dx, y2, *stt, dz2, ns)
             lb.wgrad(dz2, y1e)
             dz1 = c.act('d_dz1%d' % j + tag, B, T, ch)
             if fuse:
                 lb.dgrad(dz2, T, dz1, dact_src=y1, slope=ns, colsum=slot(ed))
             else:
                 lb.dgrad(dz2, T, gpv)
-                self._combine(gpv, T, 0, 0, dz1, emb_i=ed, dact=y1)
+                grad_combine(c, gpv, T, 0, 0, self.pad_mode, ch, dz1, ns, emb_sum=esum(ed), dact=y1)
             la.wgrad(dz1, xe)
             dn = c.act('d_dxD%d' % j + tag, B, T, ch)
             if fuse:
                 la.dgrad(dz1, T, dn, add_src=dx, colsum=slot(ed))
             else:
                 la.dgrad(dz1, T, gpv)
-                self._combine(gpv, T, 0, 0, dn, emb_i=ed, res_mode=L.ZS_RES_IDENTITY, res=dx)
+                grad_combine(c, gpv, T, 0, 0, self.pad_mode, ch, dn, ns, emb_sum=esum(ed), res_mode=L.ZS_RES_IDENTITY, res=dx)
             dx = dn
         self._bw = (dx, gp, tag)
 
@@ -571,19 +524,21 @@ class DecoderEngine(object):
         for i in (2, 1, 0):
             la, lb = self.convs[i]
             xin, xe, ya, s, yb, stt, Ti = tp['blocks'][i]
+            esum = L.ptr(self._embsum, i * B * ch)                   # per-sample sums for emb_i+1
             T2 = 2 * Ti
             dzb = c.act('d_dzb%d' % i + tag, B, T2, ch)
-            self._in_bwd(dx, yb, stt, dzb)
+            instnorm_bwd(c, dx, yb, *stt, dzb, ns)
             lb.wgrad(dzb, s)
             gp2 = Act(gp.t, B, T2 + 2, ch, gp.ld)
             lb.dgrad(dzb, T2, gp2)
             dza = c.act('d_dza%d' % i + tag, B, Ti, 2 * ch)
-            self._combine(gp2, T2, 1, 1, dza, emb_i=i, dact=ya, unshuffle=1)                # pixel_shuffle^T, +emb (:323-324)
+            grad_combine(c, gp2, T2, 1, 1, self.pad_mode, ch, dza, ns, emb_sum=esum, dact=ya, unshuffle=1)   # pixel_shuffle^T, +emb (:323-324)
             la.wgrad(dza, xe)
             gp1 = Act(gp.t, B, Ti + 2, ch, gp.ld)
             la.dgrad(dza, Ti, gp1)
             dn = c.act('d_dxC%d' % i + tag, B, Ti, ch)
-            self._combine(gp1, Ti, 1, 1, dn, emb_i=i, res_mode=L.ZS_RES_UPSAMPLE2, res=dx)   # x+emb (:319) and upsample(x) (:329)
+            grad_combine(c, gp1, Ti, 1, 1, self.pad_mode, ch, dn, ns, emb_sum=esum, res_mode=L.ZS_RES_UPSAMPLE2,
+                         res=dx)                                                                # x+emb (:319) and upsample(x) (:329)
             dx = dn
         # nn.Embedding backward, fixed sample order.  Only the optimizer needs these: off the main chain, side by side
         sts = fork_side(c.device) if c.overlap_wgrad else None
@@ -608,14 +563,14 @@ class PatcherEngine(DecoderEngine):
 
     def __init__(self, ctx, P, G, c_in, c_out, c_h, c_a, ns):
         self.ctx = ctx
-        self.uid = _uid()
+        self.uid = next_uid()
         self.E, self.F, self.ch, self.n_spk = c_in, c_out, c_h, c_a
         self.ns = float(ns)
         self.pad_mode = L.ZS_PAD_ZERO                     # every layer is a Linear: no time padding anywhere
         self.out_act = L.ZS_ACT_SIGMOID
         if c_h % 32:
             raise ValueError('Spectrogram_Patcher c_h must be a multiple of 32 (got %d)' % c_h)
-        mk = lambda n: ConvLayer(ctx, P[n + '.weight'], P[n + '.bias'], G[n + '.weight'], G[n + '.bias'], pad_mode=self.pad_mode, name=n)
+        mk = functools.partial(ConvLayer.from_params, ctx, P, G, pad_mode=self.pad_mode)
         self.input_layer = mk('input_layer')
         self.dense = [(mk('dense%d' % a), mk('dense%d' % b)) for a, b in ((1, 2), (3, 4))]
         self.gru = GruLayer(ctx, P, G, 'RNN.', name='sp%d' % self.uid)
@@ -636,16 +591,10 @@ class PatcherEngine(DecoderEngine):
         B, T = xd.B, xd.T
         ln = None
         if lengths is not None:
-            if training:
-                raise L.ZsError('PatcherEngine: ragged batches are an inference feature')
-            l0 = torch.as_tensor(lengths, dtype=torch.int32).reshape(-1)
-            if l0.numel() != B or int(l0.max()) > T or int(l0.min()) < 1:
-                raise L.ZsError('PatcherEngine: lengths must be %d values in [1, %d]' % (B, T))
-            ln = l0.to(c.device, non_blocking=True)
+            ln = ragged_lengths('PatcherEngine', lengths, training, B, T, 1).to(c.device, non_blocking=True)
         tag = '_%d_%d_%d' % (self.uid, B, T)
         xin = c.act('p_xin' + tag, B, T, self.E)
-        L.call('zs_cast_rows', 'ZsCastRows', c.stream, dtype=c.dt, src=xd.ptr(), ld_src=xd.ld, src_f32=1, dst=xin.ptr(), ld_dst=xin.ld,
-               dst_f32=0, col_off=0, rows=B * T, cols=self.E, fill_cols=xin.ld, act=L.ZS_ACT_NONE)
+        cast_rows(c, xd.ptr(), xd.ld, xin)
         tp = {'B': B, 'T0': T, 'training': training, 'cidx': cidx, 'xin': xin, 'dense': []}
         x = c.act('d_x0' + tag, B, T, ch)
         xe = c.act('d_xe0' + tag, B, T, ch)
@@ -673,12 +622,11 @@ class ClassifierEngine(object):
     final un-padded Conv1d whose kernel spans the whole sequence (k = seg_len/8) -> logits [B, n_class]."""
 
     def __init__(self, ctx, P, G, c_in, c_h, n_class, dp, ns, seg_len):
-        self.ctx, self.uid = ctx, _uid()
+        self.ctx, self.uid = ctx, next_uid()
         self.c_in, self.c_h, self.n_class = c_in, c_h, n_class
         self.ns, self.dp = float(ns), float(dp)
         self.pad_mode = L.ZS_PAD_REFLECT if seg_len >= 64 else L.ZS_PAD_ZERO
-        mk = lambda n, **kw: ConvLayer(ctx, P[n + '.weight'], P[n + '.bias'], G[n + '.weight'], G[n + '.bias'],
-                                       pad_mode=self.pad_mode, name=n, **kw)
+        mk = functools.partial(ConvLayer.from_params, ctx, P, G, pad_mode=self.pad_mode)
         self.blocks = [(mk('conv1'), mk('conv2'), False), (mk('conv3'), mk('conv4'), True), (mk('conv5'), mk('conv6'), True),
                        (mk('conv7'), mk('conv8'), False)]
         self.conv9 = mk('conv9', padded=False)
@@ -707,16 +655,9 @@ class ClassifierEngine(object):
             yb = c.act('c_yb%d' % i + tag, B, T, lb.Cout)
             lb.fwd(ya, out=yb, act=LRELU, slope=ns)
             out = c.act('c_o%d' % i + tag, B, T, lb.Cout)
-            C = yb.ld
-            mean = rstd = None
-            if training:
-                mean, rstd = c.f32('c_mean%d' % i + tag, B * C), c.f32('c_rstd%d' % i + tag, B * C)
-            m = masks[i]
-            L.call('zs_instnorm_fwd', 'ZsInstNormFwd', c.stream, dtype=c.dt, x=yb.ptr(), ldx=yb.ld, out=out.ptr(), ldo=out.ld,
-                   mean=L.ptr(mean), rstd=L.ptr(rstd), B=B, T=T, C=C, eps=EPS_IN, drop_p=dp, seed=seed, stream_id=20 + i,
-                   mask=L.ptr(m), mask_ld=(m.shape[-1] if m is not None else 0),
-                   res_mode=(L.ZS_RES_IDENTITY if res else L.ZS_RES_NONE), res=(a.ptr() if res else None),
-                   ldres=(a.ld if res else 0), T_res=(T if res else 0), res_pad_mode=self.pad_mode)
+            mean, rstd = _norm_stats(c, training, 'c_', '%d' % i + tag, B * yb.ld)
+            instnorm_fwd(c, yb, out, mean, rstd, self.pad_mode, res_mode=(L.ZS_RES_IDENTITY if res else L.ZS_RES_NONE),
+                         res=(a if res else None), p=dp, seed=seed, stream_id=20 + i, mask=masks[i])
             tp['blocks'].append((a, ya, yb, (mean, rstd, i), res))
             a = out
         logits = c.act('c_logits' + tag, B, 1, self.n_class, dtype=torch.float32)
@@ -731,8 +672,7 @@ class ClassifierEngine(object):
         B, T = tp['B'], tp['T']
         tag = '_%d_%d_%d' % (self.uid, B, T)
         dl = c.act('c_dl' + tag, B, 1, self.n_class)
-        L.call('zs_cast_rows', 'ZsCastRows', c.stream, dtype=c.dt, src=L.ptr(dlogits_f32), ld_src=ld, src_f32=1, dst=dl.ptr(),
-               ld_dst=dl.ld, dst_f32=0, col_off=0, rows=B, cols=self.n_class, fill_cols=dl.ld, act=L.ZS_ACT_NONE)
+        cast_rows(c, L.ptr(dlogits_f32), ld, dl)
         if param_grads:
             self.conv9.wgrad(dl, tp['last'])
         da = c.act('c_da_last' + tag, B, T, self.conv9.Cin)
@@ -741,17 +681,14 @@ class ClassifierEngine(object):
             la, lb, _ = self.blocks[i]
             a, ya, yb, stt, res = tp['blocks'][i]
             mean, rstd, k = stt
-            m = tp['masks'][k]
             dzb = c.act('c_dzb%d' % i + tag, B, T, lb.Cout)
-            L.call('zs_instnorm_bwd', 'ZsInstNormBwd', c.stream, dtype=c.dt, dout=da.ptr(), ldd=da.ld, x=yb.ptr(), ldx=yb.ld,
-                   mean=L.ptr(mean), rstd=L.ptr(rstd), dz=dzb.ptr(), ldz=dzb.ld, B=B, T=T, C=yb.ld, drop_p=tp['dp'], seed=tp['seed'],
-                   stream_id=20 + k, mask=L.ptr(m), mask_ld=(m.shape[-1] if m is not None else 0), slope=ns)
+            instnorm_bwd(c, da, yb, mean, rstd, dzb, ns, p=tp['dp'], seed=tp['seed'], stream_id=20 + k, mask=tp['masks'][k])
             if param_grads:
                 lb.wgrad(dzb, ya)
             gp = c.act('c_gp%d' % i + tag, B, T + lb.pad_l + lb.pad_r, lb.Cin)
             lb.dgrad(dzb, T, gp)
             dza = c.act('c_dza%d' % i + tag, B, T, la.Cout)
-            self._combine(gp, T, lb.pad_l, lb.pad_r, dza, dact=ya)
+            grad_combine(c, gp, T, lb.pad_l, lb.pad_r, self.pad_mode, gp.ld, dza, ns, dact=ya)
             if param_grads:
                 la.wgrad(dza, a)
             if i == 0 and not need_dx:
@@ -759,13 +696,7 @@ class ClassifierEngine(object):
             gp2 = c.act('c_gq%d' % i + tag, B, T + la.pad_l + la.pad_r, la.Cin)
             la.dgrad(dza, T, gp2)
             dn = c.act('c_da%d' % i + tag, B, T, la.Cin)
-            self._combine(gp2, T, la.pad_l, la.pad_r, dn, res_mode=(L.ZS_RES_IDENTITY if res else L.ZS_RES_NONE), res=(da if res else None))
+            grad_combine(c, gp2, T, la.pad_l, la.pad_r, self.pad_mode, gp2.ld, dn, ns, res_mode=(L.ZS_RES_IDENTITY if res else L.ZS_RES_NONE),
+                         res=(da if res else None))
             da = dn
         return da
-
-    def _combine(self, gp, T, pl, pr, out, res_mode=L.ZS_RES_NONE, res=None, dact=None):
-        c = self.ctx
-        L.call('zs_grad_combine', 'ZsGradCombine', c.stream, dtype=c.dt, gp=gp.ptr(), ldg=gp.ld, pad_left=pl, pad_right=pr,
-               pad_mode=self.pad_mode, B=gp.B, T=T, C=gp.ld, res_mode=res_mode, res=(res.ptr() if res is not None else None),
-               ldres=(res.ld if res is not None else 0), dact_src=(dact.ptr() if dact is not None else None),
-               dact_ld=(dact.ld if dact is not None else 0), slope=self.ns, out=out.ptr(), ldo=out.ld, unshuffle=0)

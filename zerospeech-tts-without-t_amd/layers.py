@@ -19,6 +19,7 @@ def rup(x, m):
 
 DTYPES = {'fp32': (L.ZS_F32, torch.float32), 'bf16': (L.ZS_BF16, torch.bfloat16)}
 SLACK = 512   # elements of zeroed slack behind every activation buffer (K-padding reads may run past a row)
+EPS_IN = 1e-5
 
 
 class Act(object):
@@ -241,6 +242,11 @@ class ConvLayer(object):
         # each -- half the MFMA work of feeding zero rows for the other taps (see dgrad)
         self.parity = (stride == 2 and self.k > 1)
 
+    @classmethod
+    def from_params(cls, ctx, P, G, name, pad_mode, **kw):
+        """The layer of parameters name.weight / name.bias in the dicts P (values) and G (gradients)."""
+        return cls(ctx, P[name + '.weight'], P[name + '.bias'], G[name + '.weight'], G[name + '.bias'], pad_mode=pad_mode, name=name, **kw)
+
     def pack(self):
         c = self.ctx
         common = dict(dtype=c.dt, W=L.ptr(self.w), so=self.so, si=self.si, sj=self.sj, Cout=self.Cout, Cin=self.Cin,
@@ -303,10 +309,13 @@ class ConvLayer(object):
         input gradient when k == 1).  Optional epilogue: *lrelu'(dact_src), +add_src (both only meaningful for k == 1).
         colsum = (fp32 pointer, ld, col0): per-sample column sums of the raw gradient, columns >= col0 (see colsum_ok).
         n_cols (, n_off): only the gradient of the n_cols input channels from n_off on is wanted (the rest is neither computed nor
-        stored; column 0 of `out` is channel n_off).  colsum_post: the column sums are taken of the stored value (after mask / add)."""
+        stored; column 0 of `out` is channel n_off).  colsum_post: the column sums are taken of the stored value (after mask / add).
+        A stride-2 layer with k > 1 takes none of dact_src, add_src, colsum, n_cols, n_off (ValueError)."""
         c = self.ctx
         Tp = T_x + self.pad_l + self.pad_r
         if self.parity:
+            if dact_src is not None or add_src is not None or colsum is not None or n_cols is not None or n_off:
+                raise ValueError('stride-2 dgrad: dact_src, add_src, colsum, n_cols and n_off are not supported')
             return self._dgrad_parity(dY, Tp, out, out_f32, out_cols)
         N, n_pad = self.Cin, self.n_pad_d
         if n_cols is not None and (n_cols < self.Cin or n_off):
@@ -467,11 +476,18 @@ class Conv2dLayer(object):
 
 
 _SID = [0]
+_UID = [0]
 
 
 def next_sid():
     _SID[0] += 1
     return _SID[0]
+
+
+def next_uid():
+    """A process-unique number for an engine: it keys the engine's buffers in a Ctx."""
+    _UID[0] += 1
+    return _UID[0]
 
 
 def side_launch(ctx, sid, need):
@@ -516,6 +532,45 @@ def wgrad_call(ctx, kw, sid=None):
     s.workspace = ws.data_ptr()
     s.workspace_bytes = ws.numel()
     L.check(L.lib().zs_gemm_wgrad(ctypes.byref(s), ctypes.c_void_p(stream)), 'zs_gemm_wgrad')
+
+
+# The norm-family launches of the engines.  An optional operand left at None leaves its struct fields zero (absent).
+def instnorm_fwd(ctx, x, out, mean, rstd, pad_mode, res_mode=L.ZS_RES_NONE, res=None, lengths=None, res_lengths=None, p=0.0,
+                 seed=0, stream_id=0, mask=None, seed_ptr=None, out2=None, vec2=None, idx=None):
+    """InstanceNorm over T of x (C = x.ld) + Dropout(p) + residual into out, and out2 = out + vec2[idx[b]] (ZsInstNormFwd)."""
+    L.call('zs_instnorm_fwd', 'ZsInstNormFwd', ctx.stream, dtype=ctx.dt, x=x.ptr(), ldx=x.ld, out=out.ptr(), ldo=out.ld,
+           out2=(out2.ptr() if out2 is not None else None), ldo2=(out2.ld if out2 is not None else 0), vec2=L.ptr(vec2),
+           vec2_ld=(vec2.shape[1] if vec2 is not None else 0), vec2_cols=(vec2.shape[1] if vec2 is not None else 0), idx=L.ptr(idx),
+           mean=L.ptr(mean), rstd=L.ptr(rstd), B=x.B, T=x.T, C=x.ld, eps=EPS_IN, drop_p=p, seed=seed, stream_id=stream_id,
+           mask=L.ptr(mask), mask_ld=(mask.shape[-1] if mask is not None else 0), res_mode=res_mode,
+           res=(res.ptr() if res is not None else None), ldres=(res.ld if res is not None else 0), T_res=(res.T if res is not None else 0),
+           res_pad_mode=pad_mode, seed_ptr=seed_ptr, lengths=L.ptr(lengths), res_lengths=L.ptr(res_lengths))
+
+
+def instnorm_bwd(ctx, dout, x, mean, rstd, dz, slope, p=0.0, seed=0, stream_id=0, mask=None, seed_ptr=None):
+    """Gradient through instnorm_fwd (same dropout arguments) and the leaky_relu that produced its input x, into dz (ZsInstNormBwd)."""
+    L.call('zs_instnorm_bwd', 'ZsInstNormBwd', ctx.stream, dtype=ctx.dt, dout=dout.ptr(), ldd=dout.ld, x=x.ptr(), ldx=x.ld,
+           mean=L.ptr(mean), rstd=L.ptr(rstd), dz=dz.ptr(), ldz=dz.ld, B=x.B, T=x.T, C=x.ld, drop_p=p, seed=seed, stream_id=stream_id,
+           mask=L.ptr(mask), mask_ld=(mask.shape[-1] if mask is not None else 0), slope=slope, seed_ptr=seed_ptr)
+
+
+def grad_combine(ctx, gp, T, pad_l, pad_r, pad_mode, C, out, slope, res_mode=L.ZS_RES_NONE, res=None, dact=None, emb_sum=None,
+                 unshuffle=0):
+    """Fold of a padded-domain gradient gp (+ residual gradient, * lrelu'(dact), += per-sample sums [B, C] at emb_sum) into out (ZsGradCombine)."""
+    L.call('zs_grad_combine', 'ZsGradCombine', ctx.stream, dtype=ctx.dt, gp=gp.ptr(), ldg=gp.ld, pad_left=pad_l, pad_right=pad_r,
+           pad_mode=pad_mode, B=gp.B, T=T, C=C, emb_sum=emb_sum, emb_ld=(C if emb_sum is not None else 0),
+           emb_cols=(C if emb_sum is not None else 0), res_mode=res_mode, res=(res.ptr() if res is not None else None),
+           ldres=(res.ld if res is not None else 0), dact_src=(dact.ptr() if dact is not None else None),
+           dact_ld=(dact.ld if dact is not None else 0), slope=slope, out=(out.ptr() if out is not None else None),
+           ldo=(out.ld if out is not None else 0), unshuffle=unshuffle)
+
+
+def cast_rows(ctx, src, ld_src, dst, dst_f32=False, dst2=None, col_off2=0, act2=L.ZS_ACT_NONE, slope2=0.0):
+    """dst.rows fp32 rows of dst.C values at pointer src (stride ld_src) -> dst, and act2 of them into dst2 from col_off2 (ZsCastRows)."""
+    L.call('zs_cast_rows', 'ZsCastRows', ctx.stream, dtype=ctx.dt, src=src, ld_src=ld_src, src_f32=1, dst=dst.ptr(), ld_dst=dst.ld,
+           dst_f32=int(dst_f32), col_off=0, rows=dst.rows, cols=dst.C, fill_cols=dst.ld, act=L.ZS_ACT_NONE,
+           dst2=(dst2.ptr() if dst2 is not None else None), ld_dst2=(dst2.ld if dst2 is not None else 0), col_off2=col_off2,
+           fill_cols2=(dst2.ld - col_off2 if dst2 is not None else 0), act2=act2, slope2=slope2)
 
 
 class GruLayer(object):

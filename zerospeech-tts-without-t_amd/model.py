@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .engine import ClassifierEngine, DecoderEngine, EncoderEngine, PatcherEngine, linear_width
-from .layers import Act, Ctx, rup
+from .layers import Act, Ctx, cast_rows, rup
 
 
 def default_dtype():
@@ -255,8 +255,7 @@ class Decoder(ZsModule):
         xb = x.detach().permute(0, 2, 1).contiguous().float()
         B, T0, E = xb.shape
         bits = ctx.act('d_in_%d_%d_%d' % (eng.uid, B, T0), B, T0, E)
-        L.call('zs_cast_rows', 'ZsCastRows', ctx.stream, dtype=ctx.dt, src=L.ptr(xb), ld_src=E, src_f32=1, dst=bits.ptr(),
-               ld_dst=bits.ld, dst_f32=0, col_off=0, rows=B * T0, cols=E, fill_cols=bits.ld, act=L.ZS_ACT_NONE)
+        cast_rows(ctx, L.ptr(xb), E, bits)
         cidx = c.detach().to(xb.device, torch.int64).contiguous()
         return bits, eng.forward(bits, cidx, self.training, lengths=lengths)
 
@@ -332,8 +331,7 @@ class SpeakerClassifier(ZsModule):
         ctx = eng.ctx
         B, T, C = x_btc_f32.shape
         a = ctx.act('c_in_%d_%d_%d' % (eng.uid, B, T), B, T, C)
-        L.call('zs_cast_rows', 'ZsCastRows', ctx.stream, dtype=ctx.dt, src=L.ptr(x_btc_f32), ld_src=x_btc_f32.stride(1), src_f32=1,
-               dst=a.ptr(), ld_dst=a.ld, dst_f32=0, col_off=0, rows=B * T, cols=C, fill_cols=a.ld, act=L.ZS_ACT_NONE)
+        cast_rows(ctx, L.ptr(x_btc_f32), x_btc_f32.stride(1), a)
         return a
 
     def forward(self, x, drop_masks=None, seed=None):

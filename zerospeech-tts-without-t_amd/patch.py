@@ -18,13 +18,11 @@ import torch.nn as nn
 from . import _lib as L
 import os
 
-from .layers import Act, ConvLayer, Ctx, join_side, rup, side_launch
+from .layers import EPS_IN, Act, ConvLayer, Ctx, cast_rows, join_side, next_uid, rup, side_launch
 from .model import ZsModule
 
 LRELU = L.ZS_ACT_LRELU
 DIRECT_CONV1 = os.environ.get('ZS_PATCH_CONV1_DIRECT', '1') == '1'
-EPS_IN = 1e-5
-_UID = [0]
 
 
 def _half(n):
@@ -141,8 +139,7 @@ class _HeadLayer(object):
 
 class PatchEngine(object):
     def __init__(self, ctx, P, G, n_class, ns, dp, seg_len):
-        _UID[0] += 1
-        self.uid = _UID[0]
+        self.uid = next_uid()
         self.ctx = ctx
         # several weight gradients accumulate into one buffer per step (real / fake / penalty passes): every layer's weight
         # gradients are pinned to ONE side stream, so stream order is the summation order (ZS_PATCH_OVERLAP=0: all on the main stream)
@@ -263,8 +260,7 @@ class PatchEngine(object):
         """fp32 tensor [B, n] -> Act [B, 1, n] in the compute dtype."""
         c = self.ctx
         a = c.act(name, B, 1, n)
-        L.call('zs_cast_rows', 'ZsCastRows', c.stream, dtype=c.dt, src=L.ptr(t), ld_src=t.stride(0), src_f32=1, dst=a.ptr(), ld_dst=a.ld,
-               dst_f32=0, col_off=0, rows=B, cols=n, fill_cols=a.ld, act=L.ZS_ACT_NONE)
+        cast_rows(c, L.ptr(t), t.stride(0), a)
         return a
 
     # ---- forward ------------------------------------------------------------------------------------------------------------

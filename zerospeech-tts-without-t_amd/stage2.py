@@ -66,8 +66,7 @@ class PatchGANStep(object):
             B, T, F = x_dec.shape
             xsrc = x_dec.contiguous()
             xd = ge.ctx.act('s2_xdin_%d_%d' % (B, T), B, T, F, dtype=torch.float32)
-            L.call('zs_cast_rows', 'ZsCastRows', ge.ctx.stream, dtype=ge.ctx.dt, src=L.ptr(xsrc), ld_src=F, src_f32=1,
-                   dst=xd.ptr(), ld_dst=xd.ld, dst_f32=1, col_off=0, rows=B * T, cols=F, fill_cols=xd.ld, act=L.ZS_ACT_NONE)
+            layers.cast_rows(ge.ctx, L.ptr(xsrc), F, xd, dst_f32=True)
         else:
             ee, de = enc._engine(), dec._engine()
             ctx = de.ctx
