@@ -274,7 +274,7 @@ def _dp_worker(rank, world, port, q):
     _, (ge, gd), _, _ = O.train_ae_grads(sub_sd(d, 'enc0.'), sub_sd(d, 'dec0.'), x[lo:hi], c[lo:hi], hp, G=G[lo:hi])
     flat = torch.cat([v.reshape(-1) for v in list(ge.values()) + list(gd.values())])
     red = parallel.GradReducer(bucket_bytes=64 << 10)          # several buckets
-    # tagged ranges in backward order (trainer.AEStep._multi_actions): the decoder's ranges first, the encoder's last; a wait
+    # tagged ranges in backward order (trainer.AEStep.plan): the decoder's ranges first, the encoder's last; a wait
     # for one tag leaves the other tag's collectives pending
     ne = sum(v.numel() for v in ge.values())
     cut = ne + (flat.numel() - ne) // 3
@@ -313,7 +313,7 @@ def test_data_parallel_gradient_average_gloo():
 
 
 def test_gradient_buckets_partition_the_flat_buffers_in_backward_order():
-    """The bucket ranges of the data-parallel step (trainer.AEStep._multi_actions) tile each net's flat gradient buffer exactly,
+    """The bucket ranges of the data-parallel step (trainer.AEStep.plan) tile each net's flat gradient buffer exactly,
     and every bucket is a contiguous range whose parameters' gradients are final when its all-reduce starts."""
     from zs_amd.model import Decoder, Encoder
     enc = Encoder(c_in=80, c_h1=16, c_h2=32, c_h3=16, ns=0.01, dp=0.5, enc_size=8, seg_len=128, enc_mode='multilabel_binary')

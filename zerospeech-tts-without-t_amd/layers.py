@@ -56,7 +56,7 @@ N_SIDE = max(1, int(os.environ.get('ZS_SIDE_STREAMS', '4')))
 # The step's multi-stream schedule (weight gradients and the encoder's conv bank on side streams, the decoder's optimizer on its own
 # stream) was built for the four hardware queues the runtime gives a process by default.  With GPU_MAX_HW_QUEUES below four, the
 # eager launches of that schedule run, but the first replay of its captured hipGraph segfaults inside the HIP graph executor: the
-# step then stays on one stream (ZS_OVERLAP_WGRAD / ZS_EARLY_DEC_UPDATE, when set, still decide).
+# step then stays on one stream (ZS_OVERLAP_WGRAD, when set, still decides for the weight gradients).
 HW_QUEUES = int(os.environ.get('GPU_MAX_HW_QUEUES') or 4)
 MULTI_STREAM = HW_QUEUES >= 4
 

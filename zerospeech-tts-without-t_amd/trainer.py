@@ -10,6 +10,7 @@ all-reduce of decoder grads] -> Encoder bwd -> [all-reduce encoder grads] -> per
 clip + Adam(lr, betas=(0.5, 0.9)) on the flat parameter buffers.  Everything is enqueued on one HIP
 stream without host synchronisation; the loss is read back only when it is logged.
 """
+import functools
 import os
 
 import numpy as np
@@ -33,12 +34,14 @@ class AEStep(object):
     fwd, L1, bwd, gradient all-reduce, per-net clip (utils.py:53-55) and Adam(betas=(0.5,0.9)) over both nets
     (trainer.py:65-66).  All state lives on the device; nothing here synchronises with the host.
 
-    Graph mode (ZS_GRAPH=1, default): after two eager warm-up steps the ~600 kernel launches of a step are captured
-    into hipGraphs and replayed, so the host cost per step is a handful of calls instead of ~15 ms of Python/ctypes
-    launches.  Everything that changes from step to step lives in device memory (RNG seed, Adam step count:
-    zs_step_counters).  With more than one rank the step is one graph per segment of _multi_actions (forward + decoder tail
-    backward | decoder conv blocks | encoder backward | conv bank weight gradients | decoder optimizer | encoder optimizer) with
-    the RCCL all-reduces of the gradient buckets launched eagerly between them, each as soon as its bucket is final."""
+    The step is one ordered list of actions (plan) that three executors share: eager (_execute), capture (_capture) and replay
+    (_execute of the captured plan).  Graph mode (ZS_GRAPH=1, default): after two eager warm-up steps the ~600 kernel launches of a
+    step are captured into hipGraphs and replayed, so the host cost per step is a handful of calls instead of ~15 ms of
+    Python/ctypes launches.  Everything that changes from step to step lives in device memory (RNG seed, Adam step count:
+    zs_step_counters).  One rank: one graph.  More than one rank: one graph per run of launches between two host actions (forward +
+    decoder tail backward | decoder conv blocks | encoder backward | conv bank weight gradients | decoder optimizer | encoder
+    optimizer), with the RCCL all-reduces of the gradient buckets launched eagerly between them, each as soon as its bucket is
+    final."""
 
     def __init__(self, encoder, decoder, lr=1e-4, betas=(0.5, 0.9), max_grad_norm=5.0, use_graph=None):
         self.Encoder, self.Decoder = encoder, decoder
@@ -53,187 +56,163 @@ class AEStep(object):
         self.reducer = parallel.GradReducer()
         self.xdec = None
         self.use_graph = (os.environ.get('ZS_GRAPH', '1') == '1') if use_graph is None else bool(use_graph)
-        self.early_dec_update = os.environ.get('ZS_EARLY_DEC_UPDATE', '1' if layers.MULTI_STREAM else '0') == '1'
-        self._dec_updated = False
-        self.fetch_by_kernel = os.environ.get('ZS_FETCH_KERNEL', '1') == '1'     # in-graph H2D by zs_host_fetch instead of a memcpy node
-        self.fetch_wgs = int(os.environ.get('ZS_FETCH_WGS', '32'))
-        # data parallel: gradient buckets in backward order (decoder tail layers first, the encoder's conv bank last), each
-        # all-reduce started as soon as its range of the flat gradient buffer is final (ZS_DP_BUCKETS=0: one per net)
-        self.buckets = os.environ.get('ZS_DP_BUCKETS', '1') == '1'
-        self._graphs = {}            # (B, T, F) -> dict(graphs=[...], x=static x, c=static c)
+        self._graphs = {}            # (B, T, F) -> dict(graphs=[...], plan=[...], x=static x, c=static c)
         self._statics = {}           # (B, T, F) -> (x, c) handed out by static_inputs()
         self._eager_calls = 0
         self.graph_warmup = 2        # eager steps (same launches) before the capture
 
-    # ---- the stream-ordered segments of a step --------------------------------------------------------------------
-    def _seg_forward(self, x_btf, c, noise, noise_kind, drop_masks, seed, seed_ptr):
-        """Encoder + Decoder forward and the L1 loss; returns dlogit (the gradient w.r.t. the pre-sigmoid output)."""
-        enc, dec = self.Encoder, self.Decoder
-        ee, de = enc._engine(), dec._engine()
-        ctx = ee.ctx
+    # ---- the step as a plan ----------------------------------------------------------------------------------------
+    def l1_loss(self, de, x_btf, xdec):
+        """loss_rec = mean |x_dec - x| (trainer.py:328) into self._loss (partial sums in self._lpart), on the current stream; xdec
+        (the decoder engine de's output) is kept as self.xdec.  Returns dlogit, the gradient w.r.t. the pre-sigmoid output."""
         B, T, F = x_btf.shape
-        bits, _, _ = ee.forward(x_btf, True, noise=noise, noise_kind=noise_kind, seed=seed, drop_masks=drop_masks, seed_ptr=seed_ptr)
-        xdec = de.forward(bits, c, True)
-        dlogit = de.ctx.act('t_dlogit_%d_%d' % (B, T), B, xdec.T, F)
+        ctx = de.ctx
+        dlogit = ctx.act('t_dlogit_%d_%d' % (B, T), B, xdec.T, F)
         L.call('zs_l1_loss', 'ZsL1Loss', ctx.stream, dtype=ctx.dt, x_dec=xdec.ptr(), ld_dec=xdec.ld, x=L.ptr(x_btf), ldx=F,
                rows=B * xdec.T, F=F, dlogits=dlogit.ptr(), ldg=dlogit.ld, fill_cols=dlogit.ld, partial=L.ptr(self._lpart),
-               loss_out=L.ptr(self._loss), grad_scale=1.0)                                   # trainer.py:328
+               loss_out=L.ptr(self._loss), grad_scale=1.0)
         self.xdec = xdec
         return dlogit
 
-    def _seg_forward_decbwd(self, x_btf, c, noise, noise_kind, drop_masks, seed, seed_ptr):
-        dlogit = self._seg_forward(x_btf, c, noise, noise_kind, drop_masks, seed, seed_ptr)
-        self._dbits = self.Decoder._engine().backward(dlogit)                                # loss.backward(), trainer.py:330
+    def plan(self, x_btf, c, multi, counted, noise=None, noise_kind=2, drop_masks=None, seed=None):
+        """The step as an ordered list of actions: ('run', fn) = launches on the current stream, ('reduce', net name, lo, hi) =
+        start the all-reduce of that range (a bucket) of the net's flat gradient buffer, ('wait', net name) = the current stream
+        waits for that net's all-reduces.  multi: the data-parallel step (parallel.multi_rank()).  counted: the seed and the Adam
+        step count come from device memory (zs_step_counters) and the per-net clip + Adam + re-pack are the plan's last 'run'
+        actions, as a captured step needs them; otherwise the caller's seed and no update (step() runs the host-counted
+        optimizer_step after the plan).
 
-    def _multi_actions(self, x_btf, c, noise, noise_kind, drop_masks, seed, seed_ptr, counted):
-        """The data-parallel step as an ordered list of actions: ('run', fn) = launches on the current stream (one hipGraph each
-        in graph mode), ('reduce', net name, lo, hi) = start the all-reduce of that range of the net's flat gradient buffer (a
-        bucket), ('wait', net name) = the current stream waits for that net's all-reduces, ('update', net name) = the per-net clip +
-        Adam.  Buckets in backward order: decoder dense1 .. linear (50 MB) start under the decoder's conv blocks, the conv blocks +
-        embeddings (120 MB) under the encoder's backward, the encoder without its conv bank (47 MB) under the bank's seven weight
-        gradients, the bank (7 MB) last; every 'run' ends with the side streams joined, so its gradients are final."""
+        Several ranks: buckets in backward order.  Decoder dense1 .. linear (50 MB) start under the decoder's conv blocks, the conv
+        blocks + embeddings (120 MB) under the encoder's backward, the encoder without its conv bank (47 MB) under the bank's seven
+        weight gradients, the bank (7 MB) last; every 'run' ends with the side streams joined, so its gradients are final.  The
+        decoder's clip + Adam + re-pack run while the encoder's all-reduces are still in flight.
+        One rank (counted): the decoder's gradients are final once its backward (main stream) and its weight gradients (side
+        streams) are done, so with layers.MULTI_STREAM its clip + Adam + re-pack run on a third stream under the encoder's backward."""
         enc, dec = self.Encoder, self.Decoder
-        ee, de = enc._engine(), dec._engine()
+        dev = self.device
+        if counted:
+            seed = parallel.rank()
+        seed_ptr = L.ptr(self._seed_dev) if counted else None
         st = {}
 
-        def fwd_and_dec_head():
+        def forward():
+            """Encoder + Decoder forward and the L1 loss; returns dlogit."""
             if counted:
-                L.check(L.lib().zs_step_counters(L.ptr(self._seed_dev), L.ptr(self._step_dev), torch.cuda.current_stream(self.device).cuda_stream),
-                        'zs_step_counters')
-            st['dlogit'] = self._seg_forward(x_btf, c, noise, noise_kind, drop_masks, seed, seed_ptr)
-            if self.buckets:
-                de.backward_head(st['dlogit'])
+                L.check(L.lib().zs_step_counters(L.ptr(self._seed_dev), L.ptr(self._step_dev),
+                                                 torch.cuda.current_stream(dev).cuda_stream), 'zs_step_counters')
+            ee, de = enc._engine(), dec._engine()
+            bits, _, _ = ee.forward(x_btf, True, noise=noise, noise_kind=noise_kind, seed=seed, drop_masks=drop_masks,
+                                    seed_ptr=seed_ptr)
+            return self.l1_loss(de, x_btf, de.forward(bits, c, True))
+
+        def update(name):
+            return 'run', lambda: self.opt[name].device_step(L.ptr(self._step_dev))
+
+        if multi:
+            ee, de = enc._engine(), dec._engine()
+
+            def fwd_and_dec_head():
+                de.backward_head(forward())
+                join_side(dev)
+
+            def dec_convs():
+                st['dbits'] = de.backward_convs()
+                join_side(dev)
+
+            def enc_main():
+                ee.backward_main(st['dbits'])
+                join_side(dev)
+
+            def enc_bank():
+                ee.backward_bank()
+                join_side(dev)
+
+            acts = [('run', fwd_and_dec_head), ('reduce', 'dec') + dec.flat_range('dense1.weight', 'linear.bias'), ('run', dec_convs),
+                    ('reduce', 'dec') + dec.flat_range('conv1.weight', 'conv6.bias'),
+                    ('reduce', 'dec') + dec.flat_range('input_emb.weight', 'emb5.weight'),
+                    ('run', enc_main), ('reduce', 'enc') + enc.flat_range('conv2.weight', 'linear.bias'),
+                    ('run', enc_bank), ('reduce', 'enc') + enc.flat_range('conv1s.0.weight', 'conv1s.6.bias'), ('wait', 'dec')]
+            return acts + ([update('dec'), ('wait', 'enc'), update('enc')] if counted else [('wait', 'enc')])
+
+        def fwd_and_dec_bwd():
+            dlogit = forward()
+            st['dbits'] = dec._engine().backward(dlogit)                               # loss.backward(), trainer.py:330
+
+        def dec_update_aside():
+            os_ = layers.opt_stream(dev)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            os_.wait_event(ev)
+            for side in layers.side_events(dev):
+                os_.wait_event(side)
+            with torch.cuda.stream(os_):
+                self.opt['dec'].device_step(L.ptr(self._step_dev))
+
+        def enc_bwd():
+            enc._engine().backward(st['dbits'])
+            join_side(dev)
+
+        def join_dec_update():
+            ev = torch.cuda.Event()
+            ev.record(layers.opt_stream(dev))
+            torch.cuda.current_stream(dev).wait_event(ev)
+
+        if not counted:
+            return [('run', fwd_and_dec_bwd), ('run', enc_bwd)]
+        if layers.MULTI_STREAM:
+            return [('run', fwd_and_dec_bwd), ('run', dec_update_aside), ('run', enc_bwd), update('enc'), ('run', join_dec_update)]
+        return [('run', fwd_and_dec_bwd), ('run', enc_bwd), update('enc'), update('dec')]
+
+    def _execute(self, acts, counted=False):
+        """Run a plan eagerly (or replay a captured one): 'run' actions launch, the reduce / wait actions are issued from the host.
+        counted: the plan carries its own Adam update, the one place where a counted step advances adam_step."""
+        for a in acts:
+            if a[0] == 'run':
+                a[1]()
+            elif a[0] == 'reduce':
+                self.reducer.start(self.opt[a[1]].net.flat_params()[1][a[2]:a[3]], tag=a[1])
             else:
-                self._dbits = de.backward(st['dlogit'])
-            join_side(self.device)
-
-        def dec_convs():
-            self._dbits = de.backward_convs()
-            join_side(self.device)
-
-        def enc_main():
-            ee.backward_main(self._dbits)
-            join_side(self.device)
-
-        def enc_bank():
-            ee.backward_bank()
-            join_side(self.device)
-
-        acts = [('run', fwd_and_dec_head)]
-        if self.buckets:
-            acts += [('reduce', 'dec') + dec.flat_range('dense1.weight', 'linear.bias'), ('run', dec_convs),
-                     ('reduce', 'dec') + dec.flat_range('conv1.weight', 'conv6.bias'),
-                     ('reduce', 'dec') + dec.flat_range('input_emb.weight', 'emb5.weight'),
-                     ('run', enc_main), ('reduce', 'enc') + enc.flat_range('conv2.weight', 'linear.bias'),
-                     ('run', enc_bank), ('reduce', 'enc') + enc.flat_range('conv1s.0.weight', 'conv1s.6.bias')]
-        else:
-            acts += [('reduce', 'dec', 0, dec.flat_params()[1].numel()), ('run', self._seg_encbwd),
-                     ('reduce', 'enc', 0, enc.flat_params()[1].numel())]
-        # the decoder's clip + Adam + re-pack run while the encoder's all-reduces are still in flight
-        return acts + [('wait', 'dec'), ('update', 'dec'), ('wait', 'enc'), ('update', 'enc')]
-
-    def _do_action(self, a):
-        """Execute a 'reduce' / 'wait' action (the 'run' / 'update' actions are launches: eager or captured)."""
-        if a[0] == 'reduce':
-            self.reducer.start(self.opt[a[1]].net.flat_params()[1][a[2]:a[3]], tag=a[1])
-        elif a[0] == 'wait':
-            self.reducer.finish(a[1])
-
-    def _seg_encbwd(self):
-        self.Encoder._engine().backward(self._dbits)
-        join_side(self.device)
+                self.reducer.finish(a[1])
+        if counted:
+            self.adam_step += 1
 
     def step(self, x_btf, c, noise=None, noise_kind=2, drop_masks=None, seed=None, update=True):
         """x_btf: fp32 [B, T, F] on the device (the loader's native layout), c: int64 [B].
         Returns the device scalar holding loss_rec."""
         enc, dec = self.Encoder, self.Decoder
         enc.train(); dec.train()
-        multi = parallel.multi_rank()
-        plain = noise is None and drop_masks is None and seed is None and update
-        # multi-rank: three graphs with the all-reduces launched between them (ZS_GRAPH_MULTI=0: every launch from the host)
-        if plain and self.use_graph and (not multi or os.environ.get('ZS_GRAPH_MULTI', '1') == '1'):
-            return self._graph_step(x_btf, c, multi)
+        if noise is None and drop_masks is None and seed is None and update and self.use_graph:
+            return self._graph_step(x_btf, c)
         if seed is None:
             seed = (self.adam_step + 1) * 0x9E3779B97F4A7C15 % (1 << 63) + parallel.rank()
-        if multi:
-            for a in self._multi_actions(x_btf, c, noise, noise_kind, drop_masks, seed, None, counted=False):
-                if a[0] == 'run':
-                    a[1]()
-                elif a[0] != 'update':             # (the update below: host-side bias correction, optional)
-                    self._do_action(a)
-        else:
-            self._seg_forward_decbwd(x_btf, c, noise, noise_kind, drop_masks, seed, None)
-            self._seg_encbwd()
+        self._execute(self.plan(x_btf, c, parallel.multi_rank(), False, noise, noise_kind, drop_masks, seed))
         if update:
             self.optimizer_step()
         return self._loss
 
     # ---- graph mode ------------------------------------------------------------------------------------------------
-    def _counted_step_eager(self, x_btf, c, multi):
-        """Same launches as the captured step (device-side seed / step count), executed eagerly."""
-        if multi:
-            for a in self._multi_actions(x_btf, c, None, 2, None, parallel.rank(), L.ptr(self._seed_dev), counted=True):
-                if a[0] == 'run':
-                    a[1]()
-                elif a[0] == 'update':
-                    self._device_update(a[1])
-                else:
-                    self._do_action(a)
-            self.adam_step += 1
-            return
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        L.check(L.lib().zs_step_counters(L.ptr(self._seed_dev), L.ptr(self._step_dev), st), 'zs_step_counters')
-        self._seg_forward_decbwd(x_btf, c, None, 2, None, parallel.rank(), L.ptr(self._seed_dev))
-        if self.early_dec_update:
-            self._early_decoder_update()
-        self._seg_encbwd()
-        self._optimizer_device_step()
+    def _warm_up_or_capture(self, x_btf, c, capture):
+        """Before a shape's graphs exist: the first graph_warmup calls run the counted step eagerly on (x_btf, c) -- the launches
+        of the captured step; every buffer allocated, every workspace grown -- and return None; after them, return capture()."""
+        if self._eager_calls < self.graph_warmup:
+            self._eager_calls += 1
+            self._execute(self.plan(x_btf, c, parallel.multi_rank(), True), counted=True)
+            return None
+        return capture()
 
-    def _device_update(self, name):
-        """Per-net clip (utils.py:53-55) + Adam with the step count read from device memory + re-pack, on the current stream."""
-        self.opt[name].device_step(L.ptr(self._step_dev))
-
-    def _early_decoder_update(self):
-        """Single rank: the decoder's gradients are final once its backward (main stream) and its weight gradients (side
-        stream) are done, so its clip + Adam + re-pack run on a third stream under the encoder's backward."""
-        main = torch.cuda.current_stream(self.device)
-        os_ = layers.opt_stream(self.device)
-        ev_main = torch.cuda.Event()
-        ev_main.record(main)
-        os_.wait_event(ev_main)
-        for ev in layers.side_events(self.device):
-            os_.wait_event(ev)
-        with torch.cuda.stream(os_):
-            self._device_update('dec')
-        self._dec_updated = True
-
-    def _optimizer_device_step(self):
-        """clip + Adam with the step count read from device memory, then re-pack the GEMM operands."""
-        self._device_update('enc')
-        if self._dec_updated:
-            ev = torch.cuda.Event()
-            ev.record(layers.opt_stream(self.device))
-            torch.cuda.current_stream(self.device).wait_event(ev)
-            self._dec_updated = False
-        else:
-            self._device_update('dec')
-        self.adam_step += 1
-
-    def _graph_step(self, x_btf, c, multi):
+    def _graph_step(self, x_btf, c):
         key = tuple(x_btf.shape)
         ent = self._graphs.get(key)
         if ent is None:
-            if self._eager_calls < self.graph_warmup:          # warm-up: allocate every buffer, grow the workspaces
-                self._eager_calls += 1
-                self._counted_step_eager(x_btf, c, multi)
+            ent = self._warm_up_or_capture(x_btf, c, lambda: self._capture(*(self._statics.get(key) or (x_btf.clone(), c.clone()))))
+            if ent is None:
                 return self._loss
-            ent = self._capture(x_btf, c, multi, statics=self._statics.get(key))
             self._graphs[key] = ent
         if x_btf.data_ptr() != ent['x'].data_ptr():        # (a loader that fills static_inputs() directly skips these copies)
             ent['x'].copy_(x_btf, non_blocking=True)
         if c.data_ptr() != ent['c'].data_ptr():
             ent['c'].copy_(c, non_blocking=True)
-        self._replay(ent, multi)
+        self._execute(ent['plan'], counted=True)
         return self._loss
 
     def static_inputs(self, B, T, F):
@@ -250,99 +229,58 @@ class AEStep(object):
                                       torch.zeros(B, dtype=torch.int64, device=self.device))
         return self._statics[key]
 
-    def _capture(self, x_btf, c, multi, statics=None, prefetch=None):
-        """Capture the step on static inputs.  prefetch = (dst_x, src_x_pinned, dst_c, src_c_pinned): an H2D copy of the NEXT
-        batch captured as a parallel branch of the (first) graph -- it runs on its own stream beside the kernels of this step."""
-        xs, cs = statics if statics is not None else (x_btf.clone(), c.clone())
+    def _capture(self, xs, cs, prefetch=()):
+        """Capture the counted step on the static inputs xs, cs: each run of consecutive 'run' actions becomes one hipGraph, a host
+        action ends it.  Returns the entry whose plan is the step with every graph as a 'run' of its replay.  prefetch: (src
+        pinned, dst) pairs, the H2D copy of the NEXT batch, forked at the start of the first graph and joined at its end (one
+        rank: the end of the step) -- it runs on its own stream beside the kernels of this step."""
         torch.cuda.synchronize(self.device)
-        st_ptr = L.ptr(self._seed_dev)
-        graphs = []
-        step0 = self.adam_step
+        graphs, plan, runs = [], [], []
+        pool = None
 
-        state = {'ev': None}
-
-        def join_prefetch():
-            if state['ev'] is not None:                            # join inside the same graph
-                torch.cuda.current_stream(self.device).wait_event(state['ev'])
-                state['ev'] = None
-
-        def fork_prefetch():
-            main = torch.cuda.current_stream(self.device)
-            if prefetch is not None:
-                # The fetch of the NEXT batch forks at the very start of the graph and joins at its very end: measured with kernel
-                # traces (DESIGN section 7b), wherever the branch forks the executor of this ROCm stack does not run it truly
-                # beside the chain (the 1.2 ms transfer costs 1.1-1.4 ms of step time); this placement is the cheapest.
-                cs_ = layers.copy_stream(self.device) if layers.MULTI_STREAM else main      # (one stream: layers.MULTI_STREAM)
-                ev0 = torch.cuda.Event()
-                ev0.record(main)
-                cs_.wait_event(ev0)
-                with torch.cuda.stream(cs_):
-                    if self.fetch_by_kernel:                       # kernel nodes that read the pinned buffers over PCIe (zs_amd.h)
-                        for src, dst in ((prefetch[3], prefetch[2]), (prefetch[1], prefetch[0])):
-                            L.check(L.lib().zs_host_fetch(L.ptr(src), L.ptr(dst), dst.numel() * dst.element_size(), self.fetch_wgs,
-                                                          cs_.cuda_stream), 'zs_host_fetch')
-                    else:
-                        prefetch[0].copy_(prefetch[1], non_blocking=True)
-                        prefetch[2].copy_(prefetch[3], non_blocking=True)
-                    state['ev'] = torch.cuda.Event()
-                    state['ev'].record(cs_)
-
-        def single():
-            fork_prefetch()
-            L.check(L.lib().zs_step_counters(L.ptr(self._seed_dev), L.ptr(self._step_dev), torch.cuda.current_stream(self.device).cuda_stream),
-                    'zs_step_counters')
-            self._seg_forward_decbwd(xs, cs, None, 2, None, parallel.rank(), st_ptr)
-            if self.early_dec_update:
-                self._early_decoder_update()
-            self._seg_encbwd()
-            self._optimizer_device_step()
-            self.adam_step = step0                             # capture does not execute: the caller counts the step
-            # the fetch branch joins at the very END of the graph (wherever the executor schedules it, it then runs beside the
-            # encoder's backward instead of holding it up)
-            join_prefetch()
-
-        pool = [None]
-
-        def capture(fn):
+        def close():
+            nonlocal pool
+            if not runs:
+                return
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool[0], capture_error_mode='thread_local'):   # other threads (RCCL watchdog) may call HIP
-                fn()
-            pool[0] = g.pool()
-            graphs.append(g)
-            return g
-
-        if not multi:
-            capture(single)
-            return {'graphs': graphs, 'x': xs, 'c': cs, 'plan': None}
-        # data parallel: one graph per 'run' / 'update' action, the all-reduces are issued between the replays
-        plan = []
-        first = [True]
-        for a in self._multi_actions(xs, cs, None, 2, None, parallel.rank(), st_ptr, counted=True):
-            if a[0] == 'run':
-                def seg(fn=a[1], with_fetch=first[0]):
-                    if with_fetch:
-                        fork_prefetch()
+            with torch.cuda.graph(g, pool=pool, capture_error_mode='thread_local'):   # other threads (RCCL watchdog) may call HIP
+                fetched = self._fork_fetch(prefetch) if prefetch and not graphs else None
+                for fn in runs:
                     fn()
-                    if with_fetch:
-                        join_prefetch()                            # several graphs: the branch must end inside the first
-                first[0] = False
-                plan.append(('graph', capture(seg)))
-            elif a[0] == 'update':
-                plan.append(('graph', capture(lambda n=a[1]: self._device_update(n))))
-            else:
-                plan.append(a)
-        return {'graphs': graphs, 'x': xs, 'c': cs, 'plan': plan}
+                if fetched is not None:                            # the branch joins inside the graph it forked in
+                    torch.cuda.current_stream(self.device).wait_event(fetched)
+            pool = g.pool()
+            graphs.append(g)
+            plan.append(('run', g.replay))
+            del runs[:]
 
-    def _replay(self, ent, multi):
-        if not multi:
-            ent['graphs'][0].replay()
-        else:
-            for a in ent['plan']:
-                if a[0] == 'graph':
-                    a[1].replay()
-                else:
-                    self._do_action(a)
-        self.adam_step += 1
+        for a in self.plan(xs, cs, parallel.multi_rank(), True):
+            if a[0] == 'run':
+                runs.append(a[1])
+            else:
+                close()
+                plan.append(a)
+        close()
+        return {'graphs': graphs, 'plan': plan, 'x': xs, 'c': cs}
+
+    def _fork_fetch(self, pairs):
+        """Inside a capture: copy each pinned src to its device dst by zs_host_fetch kernel nodes (they read the pinned buffers over
+        PCIe, zs_amd.h) on the copy stream, forked from the current stream here.  Returns the event that ends the branch.
+        Measured with kernel traces: wherever the branch forks, the executor of this ROCm stack does not run it
+        truly beside the chain (the 1.2 ms transfer costs 1.1-1.4 ms of step time); forking at the very start of the graph and
+        joining at the very end is the cheapest placement."""
+        main = torch.cuda.current_stream(self.device)
+        cs_ = layers.copy_stream(self.device) if layers.MULTI_STREAM else main      # (one stream: layers.MULTI_STREAM)
+        ev0 = torch.cuda.Event()
+        ev0.record(main)
+        cs_.wait_event(ev0)
+        with torch.cuda.stream(cs_):
+            for src, dst in pairs:
+                L.check(L.lib().zs_host_fetch(L.ptr(src), L.ptr(dst), dst.numel() * dst.element_size(), 32, cs_.cuda_stream),
+                        'zs_host_fetch')
+            ev = torch.cuda.Event()
+            ev.record(cs_)
+        return ev
 
     def host_feeder(self, loader):
         """Iterator that runs one training step per `next()` on the batches of a HOST loader (`next(loader)` -> (c int64 [B],
@@ -409,30 +347,25 @@ class HostFedStep(object):
 
     def __next__(self):
         ae = self.ae
-        multi = parallel.multi_rank()
         c, x = self._next
         if self.P is None:
             self._alloc(c, x)
         if self.ents is None:
-            if ae._eager_calls < ae.graph_warmup or not ae.use_graph:       # warm-up (or graphs off): synchronous copy, eager launches
-                ae._eager_calls += 1
-                self.X[0].copy_(x); self.C[0].copy_(c)
-                if ae.use_graph:
-                    ae._counted_step_eager(self.X[0], self.C[0], multi)
-                else:
-                    ae.step(self.X[0], self.C[0])
-                self._next = self._fetch()
-                return ae._loss
-            # capture graph k on X[k] with the prefetch of the other slot as a branch; batch i -> X[0], batch i+1 -> P[1]
-            self.ents = [ae._capture(None, None, multi, statics=(self.X[k], self.C[k]),
-                                     prefetch=(self._Xfull[1 - k], self._Pfull[1 - k], self._Cfull[1 - k], self._PCfull[1 - k]))
-                         for k in range(2)]
-            self.X[0].copy_(x); self.C[0].copy_(c)
-            self.i = 0
+            self.X[0].copy_(x); self.C[0].copy_(c)                            # batch i -> X[0]
+            if not ae.use_graph:
+                ae.step(self.X[0], self.C[0])
+            else:
+                # capture graph k on X[k] with the fetch of the other slot as a branch (speaker ids first)
+                self.ents = ae._warm_up_or_capture(self.X[0], self.C[0], lambda: [
+                    ae._capture(self.X[k], self.C[k], prefetch=((self._PCfull[1 - k], self._Cfull[1 - k]),
+                                                                (self._Pfull[1 - k], self._Xfull[1 - k]))) for k in range(2)])
             self._next = self._fetch()
-            self.P[1].copy_(self._next[1]); self.PC[1].copy_(self._next[0])
+            if self.ents is None:                                                 # graphs off, or a warm-up step: done
+                return ae._loss
+            self.i = 0
+            self.P[1].copy_(self._next[1]); self.PC[1].copy_(self._next[0])      # batch i+1 -> P[1]
         k = self.i % 2
-        ae._replay(self.ents[k], multi)                                       # step i on X[k]; P[1-k] -> X[1-k] beside it
+        ae._execute(self.ents[k]['plan'], counted=True)                          # step i on X[k]; P[1-k] -> X[1-k] beside it
         self.done[k].record(torch.cuda.current_stream(self.dev))
         # stage batch i+2 into P[k]: its last reader was graph 1-k at step i-1
         self._next = self._fetch()                                            # = batch i+2 (batch i+1 is already in P[1-k])
@@ -496,17 +429,10 @@ class ClfStep(object):
         enc, dec = ae.Encoder, ae.Decoder
         enc.train(); dec.train()
         ee, de = enc._engine(), dec._engine()
-        ctx = ee.ctx
-        st = ctx.stream
-        B, T, F = x_btf.shape
         if seed is None:
             seed = (ae.adam_step + 1) * 0x9E3779B97F4A7C15 % (1 << 62) + 31 * parallel.rank()
         bits, _, logits = ee.forward(x_btf, True, noise=noise, noise_kind=noise_kind, seed=seed, drop_masks=drop_masks)
-        xdec = de.forward(bits, c, True)
-        dlogit = de.ctx.act('t_dlogit_%d_%d' % (B, T), B, xdec.T, F)
-        L.call('zs_l1_loss', 'ZsL1Loss', st, dtype=ctx.dt, x_dec=xdec.ptr(), ld_dec=xdec.ld, x=L.ptr(x_btf), ldx=F,
-               rows=B * xdec.T, F=F, dlogits=dlogit.ptr(), ldg=dlogit.ld, fill_cols=dlogit.ld, partial=L.ptr(ae._lpart),
-               loss_out=L.ptr(ae._loss), grad_scale=1.0)
+        dlogit = ae.l1_loss(de, x_btf, de.forward(bits, c, True))
         ce, dl = self._classify(logits, c, -float(alpha), seed + 1, clf_masks)           # maximise the classification loss
         dbits = de.backward(dlogit)
         dx = ce.backward(dl, dl.stride(0), need_dx=True, param_grads=False)
@@ -519,7 +445,6 @@ class ClfStep(object):
         if multi:
             ae.reducer.start(enc.flat_params()[1])
             ae.reducer.finish()
-        ae.xdec = xdec
         if update:
             ae.optimizer_step()
         return ae._loss, self.loss, self.correct
@@ -589,7 +514,6 @@ class Trainer(object):
             device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
         self.device = torch.device(device)
         self.log_every = int(os.environ.get('ZS_LOG_EVERY', '1'))
-        self.h2d_in_graph = os.environ.get('ZS_H2D_IN_GRAPH', '1') == '1'
         self.ckpt_every = int(os.environ.get('ZS_CKPT_EVERY', '1000'))     # the reference saves every 1000 iterations (trainer.py:345)
         self.build_model()
 
@@ -818,160 +742,114 @@ class Trainer(object):
             self._tclf_prefetch = DevicePrefetcher(self.data_loader, self.device, check=self.tclf_labels)
         return next(self._tclf_prefetch)
 
+    def _log(self, iteration, iters, fmt, info, head=()):
+        """One logged record: every rank reads the GRU status word (the .item() reads that made `info` synchronised the host
+        already); rank 0 prints the line over the previous one and writes `info` to the logger every 100 iterations."""
+        layers.check_status(self.device)
+        if parallel.rank() == 0:
+            print(fmt % (head + (iteration + 1, iters) + tuple(info.values())), end='\r')
+            if iteration % 100 == 0:
+                for tag, value in info.items():
+                    self.logger.scalar_summary(tag, value, iteration + 1)
+
+    def _loop(self, iters, model_path, ckpt_name, iteration_fn):
+        """The loop of every mode: iteration_fn(iteration, log) runs one iteration, log = self._log bound to it at a logged
+        iteration (every log_every-th and the last) and None otherwise; rank 0 saves a checkpoint every ckpt_every iterations."""
+        is_main = parallel.rank() == 0
+        for iteration in range(iters):
+            log_now = (iteration % self.log_every == 0) or (iteration + 1 == iters)
+            iteration_fn(iteration, functools.partial(self._log, iteration, iters) if log_now else None)
+            if (iteration + 1) % self.ckpt_every == 0 and is_main:
+                self.save_model(model_path, ckpt_name, iteration + 1)
+        layers.check_status(self.device)                                                  # every rank, after the last step
+        if is_main:
+            print()
+
     def train(self, model_path, flag='train', mode='train', target_guided=False):
         hps = self.hps
-        is_main = parallel.rank() == 0
         if mode == 'pretrain_AE':                                                         # trainer.py:320-347
-            feeder = self.ae.host_feeder(self.data_loader) if (self.h2d_in_graph and self.ae.use_graph) else None
-            for iteration in range(hps.enc_pretrain_iters):
+            feeder = self.ae.host_feeder(self.data_loader) if self.ae.use_graph else None  # H2D of the next batch inside the graph
+
+            def iteration_fn(iteration, log):
                 if feeder is not None:
-                    loss_t = next(feeder)                                                 # H2D of the next batch inside the captured step
+                    loss_t = next(feeder)
                 else:
                     c, x = self._batch()
                     loss_t = self.ae_step(x, c)
-                if (iteration % self.log_every == 0) or (iteration + 1 == hps.enc_pretrain_iters):
-                    loss_rec = loss_t.item()                                              # the only host sync
-                    layers.check_status(self.device)                                      # ... so the GRU status word is read here
-                    info = {f'{flag}/pre_loss_rec': loss_rec}
-                    slot_value = (iteration + 1, hps.enc_pretrain_iters) + tuple(info.values())
-                    if is_main:
-                        print('pre_AE:[%06d/%06d], loss_rec=%.3f' % slot_value, end='\r')
-                        if iteration % 100 == 0:
-                            for tag, value in info.items():
-                                self.logger.scalar_summary(tag, value, iteration + 1)
-                if (iteration + 1) % self.ckpt_every == 0 and is_main:
-                    self.save_model(model_path, 'ae', iteration + 1)
-            layers.check_status(self.device)                                              # every rank, after the last step
-            if is_main:
-                print()
+                if log:
+                    log('pre_AE:[%06d/%06d], loss_rec=%.3f', {f'{flag}/pre_loss_rec': loss_t.item()})    # the only host sync
+            self._loop(hps.enc_pretrain_iters, model_path, 'ae', iteration_fn)
         elif mode == 'pretrain_C':                                                        # trainer.py:349-382
-            for iteration in range(hps.dis_pretrain_iters):
+            def iteration_fn(iteration, log):
                 c, x = self._batch()
                 loss_t, corr = self.clf.d_step(x, c)
-                if (iteration % self.log_every == 0) or (iteration + 1 == hps.dis_pretrain_iters):
-                    info = {f'{flag}/pre_loss_clf': loss_t.item(), f'{flag}/pre_acc': corr.item() / float(c.shape[0])}
-                    layers.check_status(self.device)
-                    slot_value = (iteration + 1, hps.dis_pretrain_iters) + tuple(info.values())
-                    if is_main:
-                        print('pre_C:[%06d/%06d], loss_clf=%.2f, acc=%.2f' % slot_value, end='\r')
-                        if iteration % 100 == 0:
-                            for tag, value in info.items():
-                                self.logger.scalar_summary(tag, value, iteration + 1)
-                if (iteration + 1) % self.ckpt_every == 0 and is_main:
-                    self.save_model(model_path, 'c', iteration + 1)
-            layers.check_status(self.device)                                              # every rank, after the last step
-            if is_main:
-                print()
+                if log:
+                    log('pre_C:[%06d/%06d], loss_clf=%.2f, acc=%.2f',
+                        {f'{flag}/pre_loss_clf': loss_t.item(), f'{flag}/pre_acc': corr.item() / float(c.shape[0])})
+            self._loop(hps.dis_pretrain_iters, model_path, 'c', iteration_fn)
         elif mode == 'train':                                                             # trainer.py:384-465
-            for iteration in range(hps.iters):
+            def iteration_fn(iteration, log):
                 if iteration < hps.lat_sched_iters:
                     current_alpha = hps.alpha_enc * (iteration / hps.lat_sched_iters)
                 else:
                     current_alpha = hps.alpha_enc
-                log_now = (iteration % self.log_every == 0) or (iteration + 1 == hps.iters)
                 for step in range(hps.n_latent_steps):                                    # train D
                     c, x = self._batch()
                     loss_t, corr = self.clf.d_step(x, c, alpha_dis=hps.alpha_dis)
-                    if log_now and is_main:
-                        info = {f'{flag}/D_loss_clf': loss_t.item(),
-                                f'{flag}/D_acc': corr.item() / float(c.shape[0])}
-                        print('D-%d:[%06d/%06d], loss_clf=%.2f, acc=%.2f' % ((step, iteration + 1, hps.iters) + tuple(info.values())), end='\r')
-                        if iteration % 100 == 0:
-                            for tag, value in info.items():
-                                self.logger.scalar_summary(tag, value, iteration + 1)
+                    if log:
+                        log('D-%d:[%06d/%06d], loss_clf=%.2f, acc=%.2f',
+                            {f'{flag}/D_loss_clf': loss_t.item(), f'{flag}/D_acc': corr.item() / float(c.shape[0])}, (step,))
                 c, x = self._batch()                                                      # train G
                 l_rec, l_clf, corr = self.clf.g_step(x, c, current_alpha)
-                if log_now and is_main:
-                    info = {f'{flag}/loss_rec': l_rec.item(), f'{flag}/G_loss_clf': l_clf.item(), f'{flag}/alpha': current_alpha,
-                            f'{flag}/G_acc': corr.item() / float(c.shape[0])}
-                    layers.check_status(self.device)
-                    print('G:[%06d/%06d], loss_rec=%.3f, loss_clf=%.2f, alpha=%.2e, acc=%.2f' % ((iteration + 1, hps.iters) + tuple(info.values())),
-                          end='\r')
-                    if iteration % 100 == 0:
-                        for tag, value in info.items():
-                            self.logger.scalar_summary(tag, value, iteration + 1)
-                if (iteration + 1) % self.ckpt_every == 0 and is_main:
-                    self.save_model(model_path, 's1', iteration + 1)
-            layers.check_status(self.device)                                              # every rank, after the last step
-            if is_main:
-                print()
+                if log:
+                    log('G:[%06d/%06d], loss_rec=%.3f, loss_clf=%.2f, alpha=%.2e, acc=%.2f',
+                        {f'{flag}/loss_rec': l_rec.item(), f'{flag}/G_loss_clf': l_clf.item(), f'{flag}/alpha': current_alpha,
+                         f'{flag}/G_acc': corr.item() / float(c.shape[0])})
+            self._loop(hps.iters, model_path, 's1', iteration_fn)
         elif mode == 'patchGAN':                                                          # trainer.py:467-560
             s2 = self.stage2()
             B = float(hps.batch_size)
-            for iteration in range(hps.patch_iters):
-                log_now = (iteration % self.log_every == 0) or (iteration + 1 == hps.patch_iters)
+
+            def iteration_fn(iteration, log):
                 for step in range(hps.n_patch_steps):                                     # train D
                     (_, x_s), (c_t, x_t) = self._duo_batch()
                     r = s2.d_step(x_s, x_t, c_t)
-                    if log_now and is_main:
-                        info = {f'{flag}/w_dis': r['w_dis'].item(), f'{flag}/gp': r['gp'].item(), f'{flag}/real_loss_clf': r['real_loss_clf'].item(),
-                                f'{flag}/real_acc': r['correct'].item() / B}
-                        print('patch_D-%d:[%06d/%06d], w_dis=%.2f, gp=%.2f, loss_clf=%.2f, acc=%.2f' %
-                              ((step, iteration + 1, hps.patch_iters) + tuple(info.values())), end='\r')
-                        if iteration % 100 == 0:
-                            for tag, value in info.items():
-                                self.logger.scalar_summary(tag, value, iteration + 1)
+                    if log:
+                        log('patch_D-%d:[%06d/%06d], w_dis=%.2f, gp=%.2f, loss_clf=%.2f, acc=%.2f',
+                            {f'{flag}/w_dis': r['w_dis'].item(), f'{flag}/gp': r['gp'].item(),
+                             f'{flag}/real_loss_clf': r['real_loss_clf'].item(), f'{flag}/real_acc': r['correct'].item() / B}, (step,))
                 (_, x_s), (c_t, x_t) = self._duo_batch()                                  # train G
                 r = s2.g_step(x_s, x_t, c_t)
                 loss_rec = s2.tg_step(x_t, c_t) if target_guided else None                # teacher forcing (trainer.py:535-541)
-                if log_now:
-                    layers.check_status(self.device)
-                if log_now and is_main:
-                    info = {f'{flag}/loss_adv': r['loss_adv'].item(), f'{flag}/fake_loss_clf': r['fake_loss_clf'].item(),
-                            f'{flag}/fake_acc': r['correct'].item() / B, f'{flag}/tg_rec': loss_rec.item() if target_guided else 0.000}
-                    print('patch_G:[%06d/%06d], loss_adv=%.2f, loss_clf=%.2f, acc=%.2f, tg_rec=%.3f' %
-                          ((iteration + 1, hps.patch_iters) + tuple(info.values())), end='\r')
-                    if iteration % 100 == 0:
-                        for tag, value in info.items():
-                            self.logger.scalar_summary(tag, value, iteration + 1)
-                if (iteration + 1) % self.ckpt_every == 0 and is_main:
-                    self.save_model(model_path, 's2', iteration + 1)
-            layers.check_status(self.device)
-            if is_main:
-                print()
+                if log:
+                    log('patch_G:[%06d/%06d], loss_adv=%.2f, loss_clf=%.2f, acc=%.2f, tg_rec=%.3f',
+                        {f'{flag}/loss_adv': r['loss_adv'].item(), f'{flag}/fake_loss_clf': r['fake_loss_clf'].item(),
+                         f'{flag}/fake_acc': r['correct'].item() / B, f'{flag}/tg_rec': loss_rec.item() if target_guided else 0.000})
+            self._loop(hps.patch_iters, model_path, 's2', iteration_fn)
         elif mode == 't_classify':                                                        # trainer.py:613-643
             if self.g_mode == 'naive':
                 self.tclf_labels(torch.zeros(0, dtype=torch.int64))                        # raises: no shift_c
-            c, x = self._tclf_batch()                                                     # the first batch is checked before any launch
+            batch = [self._tclf_batch()]                                                  # the first batch is checked before any launch
             step = self.tclf_step()
-            for iteration in range(hps.tclf_iters):
+
+            def iteration_fn(iteration, log):
                 if iteration:
-                    c, x = self._tclf_batch()
+                    batch[0] = self._tclf_batch()
+                c, x = batch[0]
                 _, corr = step.step(x, c)
-                if (iteration % self.log_every == 0) or (iteration + 1 == hps.tclf_iters):
-                    info = {f'{flag}/acc': corr.item() / float(c.shape[0])}
-                    layers.check_status(self.device)
-                    slot_value = (iteration + 1, hps.tclf_iters) + tuple(info.values())
-                    if is_main:
-                        print('Target Classifier:[%05d/%05d], acc=%.2f' % slot_value, end='\r')
-                        if iteration % 100 == 0:
-                            for tag, value in info.items():
-                                self.logger.scalar_summary(tag, value, iteration + 1)
-                if (iteration + 1) % self.ckpt_every == 0 and is_main:
-                    self.save_model(model_path, 'tclf', iteration + 1)
-            layers.check_status(self.device)
-            if is_main:
-                print()
+                if log:
+                    log('Target Classifier:[%05d/%05d], acc=%.2f', {f'{flag}/acc': corr.item() / float(c.shape[0])})
+            self._loop(hps.tclf_iters, model_path, 'tclf', iteration_fn)
         elif mode == 'autolocker':                                                        # trainer.py:563-611
             s2 = self.stage2(autolocker=True)                                             # ValueError unless multilabel_binary
-            for iteration in range(hps.patch_iters):
-                log_now = (iteration % self.log_every == 0) or (iteration + 1 == hps.patch_iters)
+
+            def iteration_fn(iteration, log):
                 (_, x_s), (c_t, x_t) = self._duo_batch()                                  # train G
                 loss_reenc = s2.al_step(x_s, c_t)
                 loss_rec = s2.tg_step(x_t, c_t) if target_guided else None                # teacher forcing, no clip
-                if log_now:
-                    layers.check_status(self.device)
-                if log_now and is_main:
-                    info = {f'{flag}/re_enc': loss_reenc.item(), f'{flag}/tg_rec': loss_rec.item() if target_guided else 0.000}
-                    print('patch_G:[%06d/%06d], re_enc=%.3f, tg_rec=%.3f' % ((iteration + 1, hps.patch_iters) + tuple(info.values())),
-                          end='\r')
-                    if iteration % 100 == 0:
-                        for tag, value in info.items():
-                            self.logger.scalar_summary(tag, value, iteration + 1)
-                if (iteration + 1) % self.ckpt_every == 0 and is_main:
-                    self.save_model(model_path, 's2', iteration + 1)
-            layers.check_status(self.device)
-            if is_main:
-                print()
+                if log:
+                    log('patch_G:[%06d/%06d], re_enc=%.3f, tg_rec=%.3f',
+                        {f'{flag}/re_enc': loss_reenc.item(), f'{flag}/tg_rec': loss_rec.item() if target_guided else 0.000})
+            self._loop(hps.patch_iters, model_path, 's2', iteration_fn)
         else:
             raise NotImplementedError("mode %r (Tacotron) is outside the path this build covers" % mode)
