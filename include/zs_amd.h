@@ -508,6 +508,8 @@ typedef struct {
   int32_t tile_frames;           /* STFT frames per workgroup tile (4..42), 0 = default 10 */
   const int32_t* host_lengths;   /* optional copy of `lengths` in HOST memory: zs_griffin_lim then cuts its launch chains at equal frame
                                     counts instead of equal utterance counts (utterances stay in order) */
+  float momentum;                /* FGLA alpha in [0, 1); 0 = the plain loop (spec_prev ignored) */
+  float* spec_prev;              /* complex64 [n_utt][T_max][513]: E of the previous iteration at each frame */
 } ZsGlIter;
 int zs_gl_iter(const ZsGlIter* p, void* stream);
 int zs_griffin_lim(const ZsGlIter* p, float* spec_a, float* spec_b, int32_t n_iter, void* stream);
@@ -518,6 +520,17 @@ int zs_griffin_lim(const ZsGlIter* p, float* spec_a, float* spec_b, int32_t n_it
  * utterances do not depend on each other, and a chain's partly filled last round of workgroups is filled by the others.  One chain
  * for small batches (< 8192 frames per chain) and under stream capture.  zs_gl_chains_used: chains of the last call (reporting). */
 int zs_gl_chains_used(void);
+/* Fast Griffin-Lim (Perraudin et al. 2013; librosa / torchaudio `momentum`): with momentum = alpha > 0 an iteration projects
+ *     A_n = E_n - beta E_{n-1},  beta = alpha / (1 + alpha)       X_n = mag * A_n / max(1e-8, |A_n|)
+ * instead of E_n (A_1 = E_1).  alpha = 0 is the plain loop above, bit for bit.  spec_prev holds E of the previous iteration at
+ * every frame; each iteration reads and rewrites it at the utterances' frames (rows past lengths[u] are never touched):
+ *   zs_griffin_lim: spec_prev is SCRATCH like spec_a / spec_b (contents on entry ignored: the first iteration initialises it);
+ *                   the chains use it at the same utterance offsets as spec_a / spec_b.
+ *   zs_gl_iter:     spec_prev is read and written; a zero-filled buffer means "first iteration" (A = E - beta 0 = E exactly), so a
+ *                   caller that drives the loop itself gets FGLA by zero-filling it once.  The final pass (spec_out == NULL)
+ *                   neither reads nor writes it.
+ * Errors (nothing is launched): momentum not finite or outside [0, 1); momentum > 0 with spec_prev == NULL or with spec_prev
+ * overlapping spec_in / spec_out (zs_gl_iter) or spec_a / spec_b (zs_griffin_lim). */
 /* spectrogram2wav pre/post (convert.py:56-60): de-normalise to amplitude; de-preemphasis IIR. */
 /* ---------------------------------------------------------------------------------------------
  * Feature extraction feeding the path (preprocess.py:227-258 get_spectrograms after the host-side

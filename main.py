@@ -10,6 +10,10 @@
   python main.py --test_classify --load_tclf_model_name CKPT   (scores the wavs --test wrote; hps load_model_list must name
                                                            target_classifier)
 
+Vocoder of --test, --cross_test and --test_single: --gl_iters N sets the Griffin-Lim iterations (hp.n_iter, default 300),
+--gl_momentum A in [0, 1) the fast Griffin-Lim momentum (hp.gl_momentum, default 0: the reference's plain loop), e.g.
+`--gl_iters 100 --gl_momentum 0.99`.
+
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
 (--train_al, --train_t, --encode, --test_asr) are not part of this build and exit with a clear error.
@@ -22,6 +26,23 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 OUT_OF_SCOPE = ['train_al', 'train_t', 'test_asr', 'encode']
+
+
+def _gl_iters(text):
+    n = int(text)
+    if n < 0:
+        raise argparse.ArgumentTypeError('--gl_iters must be a non-negative integer (got %s)' % text)
+    return n
+
+
+def _gl_momentum(text):
+    try:
+        a = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('--gl_momentum must be a number in [0, 1) (got %s)' % text)
+    if not 0.0 <= a < 1.0:                    # NaN fails too
+        raise argparse.ArgumentTypeError('--gl_momentum must be in [0, 1) (got %s)' % text)
+    return a
 
 
 def build_parser():
@@ -56,11 +77,14 @@ def build_parser():
     p.add_argument('--load_tclf_model_name', type=str, default=None)     # main.py:79: a path, used as given
     p.add_argument('--s_speaker', type=str, default='S015')
     p.add_argument('--t_speaker', type=str, default='V002')
+    p.add_argument('--gl_iters', type=_gl_iters, default=None, help='Griffin-Lim iterations (hp.n_iter); default: leave hp as it is')
+    p.add_argument('--gl_momentum', type=_gl_momentum, default=None,
+                   help='fast Griffin-Lim momentum in [0, 1) (hp.gl_momentum); default: leave hp as it is')
     return p
 
 
 def argument_runner(argv=None):
-    from zs_amd.hps import Hps
+    from zs_amd.hps import Hps, hp
     parser = build_parser()
     args = parser.parse_args(argv)
     if args.dataset == 'surprise':            # main.py:83-88: english -> surprise in every default path
@@ -70,6 +94,10 @@ def argument_runner(argv=None):
                 action.default = action.default.replace('english', 'surprise')
         args = parser.parse_args(argv)
     print('[Runner] - Dataset: ', args.dataset)
+    if args.gl_iters is not None:             # the vocoder of --test / --cross_test / --test_single reads hp
+        hp.n_iter = args.gl_iters
+    if args.gl_momentum is not None:
+        hp.gl_momentum = args.gl_momentum
     hps = Hps(args.hps_path).get_tuple()
     if args.g_mode == 'set_from_hps':
         args.g_mode = hps.g_mode

@@ -4,7 +4,8 @@ convert() / encode() reproduce the reference's fragment rule exactly (MIN_LEN ze
 tail that drops the last frame, tails shorter than seg_len skipped, RuntimeError for a too-short input),
 call Trainer.test_step / encoder_test_step per fragment and concatenate.  spectrogram2wav() /
 griffin_lim() run the 300-iteration Griffin-Lim on the MI355X (zs_gl_* kernels: 1024-point FFTs in LDS),
-batched over utterances by griffin_lim_batch(); de-preemphasis on the device, librosa.effects.trim restated
+batched over utterances by griffin_lim_batch(); `momentum` (default hp.gl_momentum = 0) selects the fast Griffin-Lim of
+Perraudin et al. (2013), as librosa / torchaudio name it; de-preemphasis on the device, librosa.effects.trim restated
 on the host (librosa itself is not required).  Utterances are independent: multi-GPU = replicas over a
 sharded utterance list (zs_amd.parallel.shard_range), no collective.
 """
@@ -32,14 +33,31 @@ def _device():
     return torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
 
 
-def griffin_lim_batch(mags, n_iter=None, device=None, impl=None, tile_frames=0, mag_padded=None):
+def gl_momentum(momentum):
+    """The fast Griffin-Lim momentum to use: hp.gl_momentum when None; ValueError unless it is a finite number in [0, 1)."""
+    m = hp.gl_momentum if momentum is None else momentum
+    try:
+        m = float(m)
+    except (TypeError, ValueError):
+        raise ValueError('Griffin-Lim momentum must be a number in [0, 1) (got %r)' % (m,))
+    if not (np.isfinite(m) and 0.0 <= m < 1.0):
+        raise ValueError('Griffin-Lim momentum must be in [0, 1) (got %r)' % (m,))
+    return m
+
+
+def griffin_lim_batch(mags, n_iter=None, device=None, impl=None, tile_frames=0, mag_padded=None, momentum=None):
     """mags: list of real [513, T_i] amplitude spectrograms (or mag_padded).  Returns (wav [n, 200*(T_max-1)] on the device, lengths, lens).
     X = S (zero phase); n_iter x { x = istft(X); E = stft(x); X = S * E / max(1e-8, |E|) }; x = istft(X)  (convert.py:39-52).
+    momentum alpha > 0 (None: hp.gl_momentum): fast Griffin-Lim -- X = S * A / max(1e-8, |A|) with A = E - alpha / (1 + alpha) *
+    (E of the previous iteration), A = E in the first; alpha = 0 is the loop above, bit for bit.
     impl 'fused' (default): zs_griffin_lim -- one fused kernel per iteration, the whole loop issued by one C call;
     impl 'split' (ZS_GL_IMPL=split): the older per-transform kernels (zs_gl_istft + zs_gl_stft_project per iteration), kept as
-    the variant the tests compare the fused kernel with."""
+    the variant the tests compare the fused kernel with (plain loop only)."""
     n_iter = hp.n_iter if n_iter is None else n_iter
+    momentum = gl_momentum(momentum)
     impl = impl or os.environ.get('ZS_GL_IMPL', 'fused')
+    if impl == 'split' and momentum > 0:
+        raise ValueError("griffin_lim impl 'split' runs the plain loop only (momentum must be 0)")
     dev = device or _device()
     st = torch.cuda.current_stream(dev).cuda_stream
     if mag_padded is not None:                    # (amplitudes [n, T_max, 513] fp32 on the device, frame counts)
@@ -63,8 +81,10 @@ def griffin_lim_batch(mags, n_iter=None, device=None, impl=None, tile_frames=0, 
         spec = torch.empty(n, Tm, 513, 2, dtype=torch.float32, device=dev)     # scratch: the first iteration reads X0 = S from `mag`
         spec_b = torch.empty_like(spec)
         host_lens = np.asarray(lens, dtype=np.int32)                # the chains of zs_griffin_lim are cut at equal frame counts
+        prev = torch.empty_like(spec) if momentum > 0 else None     # scratch as well: the first iteration writes it
         S = L.STRUCTS['ZsGlIter'](mag=L.ptr(mag), lengths=L.ptr(lengths), n_utt=n, T_max=Tm, wav=L.ptr(wav), wav_ld=wav_ld,
-                                  tile_frames=int(tile_frames), host_lengths=host_lens.ctypes.data)
+                                  tile_frames=int(tile_frames), host_lengths=host_lens.ctypes.data, momentum=momentum,
+                                  spec_prev=L.ptr(prev))
         L.check(L.lib().zs_griffin_lim(ctypes.addressof(S), L.ptr(spec), L.ptr(spec_b), int(n_iter), st), 'zs_griffin_lim')
         return wav, lengths, lens
     if impl != 'split':
@@ -82,9 +102,9 @@ def griffin_lim_batch(mags, n_iter=None, device=None, impl=None, tile_frames=0, 
     return wav, lengths, lens
 
 
-def griffin_lim(spectrogram, n_iter=None, impl=None):
+def griffin_lim(spectrogram, n_iter=None, impl=None, momentum=None):
     """convert.py:39-52 for one [513, T] amplitude spectrogram."""
-    wav, _, lens = griffin_lim_batch([spectrogram], n_iter=n_iter, impl=impl)
+    wav, _, lens = griffin_lim_batch([spectrogram], n_iter=n_iter, impl=impl, momentum=momentum)
     return wav[0, :200 * (lens[0] - 1)].cpu().numpy()
 
 
@@ -127,7 +147,7 @@ def trim_bounds(mse, n, top_db=60, hop_length=TRIM_HOP):
     return int(nz[0]) * hop_length, min(n, (int(nz[-1]) + 1) * hop_length)
 
 
-def _enqueue_vocoder(t, lens, n_iter, do_trim, dev, amplitudes=False):
+def _enqueue_vocoder(t, lens, n_iter, do_trim, dev, amplitudes=False, momentum=None):
     """t: normalised magnitudes [n, T_max, 513] fp32 on the device (amplitudes=True: already de-normalised, e.g. by
     zs_gen_scatter).  Enqueues convert.py:55-62 and returns the function that waits for it and cuts the waveforms
     (librosa.effects.trim restated on device-computed frame statistics)."""
@@ -137,7 +157,7 @@ def _enqueue_vocoder(t, lens, n_iter, do_trim, dev, amplitudes=False):
     else:
         amp = torch.empty_like(t)
         L.check(L.lib().zs_gl_denormalize(L.ptr(t), L.ptr(amp), t.numel(), st), 'zs_gl_denormalize')     # convert.py:56-58
-    wav, lengths, lens = griffin_lim_batch(None, n_iter=n_iter, device=dev, mag_padded=(amp, lens))
+    wav, lengths, lens = griffin_lim_batch(None, n_iter=n_iter, device=dev, mag_padded=(amp, lens), momentum=momentum)
     L.check(L.lib().zs_gl_deemphasis(L.ptr(wav), wav.shape[1], L.ptr(lengths), len(lens), float(hp.preemphasis), st),
             'zs_gl_deemphasis')                               # signal.lfilter([1], [1, -0.97], wav)
     mse_h = None
@@ -171,11 +191,12 @@ def _enqueue_vocoder(t, lens, n_iter, do_trim, dev, amplitudes=False):
     return finish
 
 
-def spectrogram2wav_batch(mags_tf, n_iter=None, do_trim=True):
+def spectrogram2wav_batch(mags_tf, n_iter=None, do_trim=True, momentum=None):
     """Batched spectrogram2wav (convert.py:55-62): list of [T_i, 513] normalised magnitudes -> list of float32 wavs.
     One padded buffer, one H2D copy (unless the magnitudes are on the device already), one de-normalisation launch, one
     zs_griffin_lim call, one de-emphasis launch, one D2H copy; librosa.effects.trim (restated) from frame statistics computed on
-    the device."""
+    the device.  momentum: see griffin_lim_batch."""
+    momentum = gl_momentum(momentum)
     dev = _device()
     lens = [int(m.shape[0]) for m in mags_tf]
     n, Tm = len(lens), max(lens)
@@ -188,11 +209,11 @@ def spectrogram2wav_batch(mags_tf, n_iter=None, do_trim=True):
         for i, m in enumerate(mags_tf):
             host[i, :lens[i]] = np.asarray(m.cpu() if torch.is_tensor(m) else m, dtype=np.float32)
         t = torch.from_numpy(host).to(dev)
-    return _enqueue_vocoder(t, lens, n_iter, do_trim, dev)()
+    return _enqueue_vocoder(t, lens, n_iter, do_trim, dev, momentum=momentum)()
 
 
-def spectrogram2wav(mag, n_iter=None):
-    return spectrogram2wav_batch([mag], n_iter=n_iter)[0]
+def spectrogram2wav(mag, n_iter=None, momentum=None):
+    return spectrogram2wav_batch([mag], n_iter=n_iter, momentum=momentum)[0]
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -551,7 +572,8 @@ def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, m
     return encs, [conv[u, :n] for u, n in enumerate(q.ulens)]
 
 
-def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, noise_fn=None, max_batch=256, defer=False, enc_only=True):
+def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, noise_fn=None, max_batch=256, defer=False, enc_only=True,
+                  momentum=None):
     """test_encode + convert(enc_only) + spectrogram2wav for a batch of utterances as ONE enqueue (convert.py:151-165, 55-62):
     the fragments' Encoder / Decoder launches, the gather of the decoded fragments into the vocoder's padded [n, T_max, 513]
     input (one index kernel on the device), de-normalisation, the Griffin-Lim loop, de-emphasis, the trim statistics and the
@@ -561,10 +583,12 @@ def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, 
     serving loop enqueues batch i + 1 before it calls the function of batch i, so the host-side assembly and the D2H copies of one
     batch run under the GPU work of the next.
     enc_only=False: convert() with the stage-2 generator; zs_gen_scatter writes each chunk's de-normalised converted rows straight
-    into the vocoder's input, so the gather / combine / de-normalisation passes below do not exist on that path."""
+    into the vocoder's input, so the gather / combine / de-normalisation passes below do not exist on that path.
+    momentum: the vocoder's fast Griffin-Lim momentum (see griffin_lim_batch; None: hp.gl_momentum)."""
+    momentum = gl_momentum(momentum)
     if not enc_only:
         q = _enqueue_encode(specs, trainer, seg_len, speakers, noise_fn, max_batch, dec_to_host=False, enc_only=False, denorm=True)
-        return _finish_resynth(q, _enqueue_vocoder(q.conv, q.ulens, n_iter, do_trim, q.dev, amplitudes=True), defer)
+        return _finish_resynth(q, _enqueue_vocoder(q.conv, q.ulens, n_iter, do_trim, q.dev, amplitudes=True, momentum=momentum), defer)
     q = _enqueue_encode(specs, trainer, seg_len, speakers, noise_fn, max_batch, dec_to_host=False)
     dev = q.dev
     # row table of all decoded fragments + a zero row; utterance u's frames are its fragments' rows in order
@@ -590,7 +614,7 @@ def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, 
             at += n
     table = torch.cat([x.reshape(-1, x.shape[2]) for x in q.dec_dev] + [torch.zeros(1, q.dec_dev[0].shape[2], dtype=q.dec_dev[0].dtype, device=dev)], dim=0)
     t = table[torch.from_numpy(idx).to(dev, non_blocking=True)].float()                               # [n, Tm, 513]
-    return _finish_resynth(q, _enqueue_vocoder(t, ulens, n_iter, do_trim, dev), defer)
+    return _finish_resynth(q, _enqueue_vocoder(t, ulens, n_iter, do_trim, dev, momentum=momentum), defer)
 
 
 def _finish_resynth(q, fin, defer):
@@ -675,11 +699,12 @@ def cross_test_plan(keys, flag, result_dir):
     return plan
 
 
-def cross_test(trainer, seg_len, data_path, speaker2id_path, result_dir, enc_only, flag='test', batch=64, n_iter=None):
+def cross_test(trainer, seg_len, data_path, speaker2id_path, result_dir, enc_only, flag='test', batch=64, n_iter=None, momentum=None):
     """convert.py:268-300, as the reference means it (its call passes the target in the source speaker's slot and raises
     TypeError): convert() of every source utterance to every target speaker, with convert()'s default outputs.  Every (utterance,
     target) pair is an item of its own with its own Gumbel noise; items go through resynth_batch in groups of `batch`, and group
-    i + 1 is enqueued before group i is written (defer=True)."""
+    i + 1 is enqueued before group i is written (defer=True).  n_iter / momentum: the vocoder's (None: hp.n_iter / hp.gl_momentum)."""
+    momentum = gl_momentum(momentum)
     with open(speaker2id_path, 'r') as f_json:
         speaker2id = json.load(f_json)
     with _open_h5(data_path) as f_h5:
@@ -704,7 +729,7 @@ def cross_test(trainer, seg_len, data_path, speaker2id_path, result_dir, enc_onl
         for group in groups:
             specs = [np.asarray(f_h5[it['key']][()], dtype=np.float32) for it in group]
             fin = resynth_batch(specs, trainer, seg_len, [speaker2id[it['tar']] for it in group], n_iter=n_iter, defer=True,
-                                enc_only=enc_only)
+                                enc_only=enc_only, momentum=momentum)
             if pending is not None:
                 write(*pending)
             pending = (group, fin)

@@ -23,9 +23,17 @@
 //    the current transform: 36.9 -> 29.2 ms for 300 iterations of 64 utterances of 200..700 frames.
 // zs_griffin_lim runs the whole loop (n_iter launches ping-ponging two spectrogram buffers + the final inverse pass) from
 // one C call.  The older one-transform-per-workgroup kernels (zs_vocoder.hip) remain as the variant the tests compare with.
+//  * Fast Griffin-Lim (Perraudin et al. 2013; librosa / torchaudio `momentum`), opt-in through ZsGlIter::momentum = alpha > 0: the
+//    projection is applied to A = E - beta E_prev, beta = alpha / (1 + alpha), with E_prev the previous iteration's E of the same
+//    frame, kept in an fp32 state buffer that each frame's owning tile reads and rewrites in place (+8.2 KB per frame and
+//    iteration).  MOM is a template parameter, as FROM_MAG: the plain instantiations take the same arguments and compile to the
+//    same code as before the state existed.
 #include <atomic>
 #include <chrono>
+#include <cmath>
+#include <cstddef>
 #include <mutex>
+#include <type_traits>
 
 #include "zs_common.h"
 
@@ -127,11 +135,42 @@ __global__ void gl_tables_kernel() {
 
 __device__ __forceinline__ int floordiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
 
+// The kernels' parameter block: ZsGlIter up to host_lengths, laid out as before the momentum fields were appended, so the plain
+// instantiations keep their kernel arguments; the momentum instantiations append beta and the state.
+struct GlArgs {
+  const float* spec_in; float* spec_out;
+  const float* mag; const int32_t* lengths; int32_t n_utt, T_max;
+  float* wav; int64_t wav_ld;
+  int32_t tile_frames;
+  const int32_t* host_lengths;
+};
+struct GlMomArgs : GlArgs {
+  float beta;                                                                  // alpha / (1 + alpha)
+  float* prev;                                                                 // complex64 [n_utt][T_max][513]: E of the previous iteration
+};
+static_assert(offsetof(ZsGlIter, host_lengths) == offsetof(GlArgs, host_lengths) && sizeof(GlArgs) == offsetof(ZsGlIter, momentum),
+              "GlArgs must keep the layout of ZsGlIter's leading fields");
+
+// FGLA at one bin: st holds E_prev; returns A = E - beta E_prev (FIRST: nothing is read, A = E) and leaves E in the state.
+template <bool FIRST>
+__device__ __forceinline__ float2 fgla_step(float2* st, float2 e, float beta) {
+  float2 a = e;
+  if (!FIRST) {
+    const float2 q = *st;
+    a = make_float2(e.x - beta * q.x, e.y - beta * q.y);
+  }
+  *st = e;
+  return a;
+}
+
 // PF: request the spectrum of a wave's next inverse frame right behind the current transform (see below).  NWAVE: waves per
 // workgroup (4 or 8): a tile of F frames inverse-transforms F + 6 frames in four phases, so the phases are balanced over the waves
 // when F + 6 is a multiple of 4 NWAVE -- F = 10 with 4 waves (1.6 inverse transforms per frame), F = 26 with 8 waves (1.23).
-template <bool PF, int NWAVE, bool FROM_MAG>
-__global__ __launch_bounds__(64 * NWAVE) void gl_iter_kernel(const ZsGlIter p, const float* spec_in, float* spec_out, int F) {
+// MOM: fast Griffin-Lim -- the own frames project A = E - beta E_prev and store E in p.prev (FROM_MAG: the first iteration,
+// which reads no state).  The final pass (spec_out == nullptr) never runs a MOM instantiation.
+template <bool PF, int NWAVE, bool FROM_MAG, bool MOM>
+__global__ __launch_bounds__(64 * NWAVE) void gl_iter_kernel(const std::conditional_t<MOM, GlMomArgs, GlArgs> p, const float* spec_in,
+                                                             float* spec_out, int F) {
   constexpr int NT_ = 64 * NWAVE;
   extern __shared__ __align__(16) unsigned char gl_smem[];
   float2* W = reinterpret_cast<float2*>(gl_smem);
@@ -301,6 +340,8 @@ __global__ __launch_bounds__(64 * NWAVE) void gl_iter_kernel(const ZsGlIter p, c
       }
     }
     const float* M = Mu + (int64_t)t * NB;
+    float2* Pt = nullptr;                                                     // this frame's momentum state (MOM), touched by this tile only
+    if constexpr (MOM) Pt = reinterpret_cast<float2*>(p.prev) + ((int64_t)u * p.T_max + t) * NB;
     float mg[8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) mg[r] = M[lane + 64 * r];                     // in flight under the transform
@@ -318,7 +359,8 @@ __global__ __launch_bounds__(64 * NWAVE) void gl_iter_kernel(const ZsGlIter p, c
       b.y = -b.y;
       const float2 s = cadd(a, b), d = csub(a, b);
       const float2 tt = cmul(d, W[k]);
-      const float2 e = make_float2(0.5f * (s.x + tt.y), 0.5f * (s.y - tt.x));   // E[k] = (a+b)/2 - (i/2) W^k (a-b)
+      float2 e = make_float2(0.5f * (s.x + tt.y), 0.5f * (s.y - tt.x));         // E[k] = (a+b)/2 - (i/2) W^k (a-b)
+      if constexpr (MOM) e = fgla_step<FROM_MAG>(Pt + k, e, p.beta);             // read after the transform: no registers held under it
       // X = S * E / max(1e-8, |E|)   (convert.py:50) as S * E * rsqrt(max(1e-16, |E|^2)): one v_rsq_f32 (1 ulp) instead of a
       // square root and a division (the projection was a fifth of the kernel's vector instructions)
       const float sc = mg[r] * __builtin_amdgcn_rsqf(fmaxf(1e-16f, e.x * e.x + e.y * e.y));
@@ -327,8 +369,14 @@ __global__ __launch_bounds__(64 * NWAVE) void gl_iter_kernel(const ZsGlIter p, c
     if (lane == 0) {                                                          // Nyquist bin: E[512] = Re Z0 - Im Z0
       const float2 z0 = mybuf[0];
       const float e = z0.x - z0.y;
-      const float sc = mg_ny / fmaxf(1e-8f, fabsf(e));
-      So[HALF] = make_float2(e * sc, 0.f);
+      if constexpr (MOM) {                                                    // A may be complex here: E_prev is the caller's for zs_gl_iter
+        const float2 a = fgla_step<FROM_MAG>(Pt + HALF, make_float2(e, 0.f), p.beta);
+        const float sc = mg_ny / fmaxf(1e-8f, sqrtf(a.x * a.x + a.y * a.y));
+        So[HALF] = make_float2(a.x * sc, a.y * sc);
+      } else {
+        const float sc = mg_ny / fmaxf(1e-8f, fabsf(e));
+        So[HALF] = make_float2(e * sc, 0.f);
+      }
     }
     wave_lds_sync();
   }
@@ -399,13 +447,10 @@ size_t gl_lds_bytes(int F, int nwave) { return (size_t)WTAB * 8 + WLEN * 4 + HOP
 
 void gl_set_lds_attr();
 
-int gl_launch(const ZsGlIter* p, const float* in, float* out, hipStream_t s, int from_mag = 0) {
-  // default tile: 26 frames on 8 waves once the batch fills the chip (>= 8192 frames: 1.23 instead of 1.6 inverse transforms per
-  // frame, 29.2 against 30.9 ms for 300 iterations of 64 utterances of 200..700 frames), else 10 frames on 4 waves (more workgroups)
-  const int F = p->tile_frames > 0 ? p->tile_frames : ((int64_t)p->n_utt * p->T_max >= 8192 ? GL_TILE_LARGE : GL_TILE_DEFAULT);
-  dim3 grid((unsigned)((p->T_max + F - 1) / F), (unsigned)p->n_utt);
-  const bool pf = g_gl_prefetch.get() != 0;
-#define ZS_GL_LAUNCH(PFV, NW, FM) hipLaunchKernelGGL((gl_iter_kernel<PFV, NW, FM>), grid, dim3(64 * NW), gl_lds_bytes(F, NW), s, *p, in, out, F)
+template <bool MOM, class A>
+void gl_dispatch(const A& a, const float* in, float* out, hipStream_t s, int F, bool pf, int from_mag) {
+  dim3 grid((unsigned)((a.T_max + F - 1) / F), (unsigned)a.n_utt);
+#define ZS_GL_LAUNCH(PFV, NW, FM) hipLaunchKernelGGL((gl_iter_kernel<PFV, NW, FM, MOM>), grid, dim3(64 * NW), gl_lds_bytes(F, NW), s, a, in, out, F)
   // FROM_MAG (the first iteration reads X0 = S from the magnitudes) is a template parameter: as a run-time branch it took the
   // steady-state kernel over 128 VGPRs, i.e. from two workgroups per CU to one (26 -> 39 ms)
   if (F > 16) {                                                               // large tiles: 8 waves share the segment
@@ -415,26 +460,63 @@ int gl_launch(const ZsGlIter* p, const float* in, float* out, hipStream_t s, int
   } else if (from_mag) { if (pf) ZS_GL_LAUNCH(true, 4, true); else ZS_GL_LAUNCH(false, 4, true); }
   else { if (pf) ZS_GL_LAUNCH(true, 4, false); else ZS_GL_LAUNCH(false, 4, false); }
 #undef ZS_GL_LAUNCH
+}
+
+int gl_launch(const ZsGlIter* p, const float* in, float* out, hipStream_t s, int from_mag = 0) {
+  // default tile: 26 frames on 8 waves once the batch fills the chip (>= 8192 frames: 1.23 instead of 1.6 inverse transforms per
+  // frame, 29.2 against 30.9 ms for 300 iterations of 64 utterances of 200..700 frames), else 10 frames on 4 waves (more workgroups)
+  const int F = p->tile_frames > 0 ? p->tile_frames : ((int64_t)p->n_utt * p->T_max >= 8192 ? GL_TILE_LARGE : GL_TILE_DEFAULT);
+  const bool pf = g_gl_prefetch.get() != 0;
+  const GlArgs a{p->spec_in, p->spec_out, p->mag, p->lengths, p->n_utt, p->T_max, p->wav, p->wav_ld, p->tile_frames, p->host_lengths};
+  if (out != nullptr && p->momentum > 0.f) {                                  // the final pass reads no state: always the plain kernel
+    GlMomArgs m;
+    static_cast<GlArgs&>(m) = a;
+    m.beta = p->momentum / (1.0f + p->momentum);
+    m.prev = p->spec_prev;
+    gl_dispatch<true>(m, in, out, s, F, pf, from_mag);
+  } else {
+    gl_dispatch<false>(a, in, out, s, F, pf, from_mag);
+  }
   return zs_check_launch("zs_gl_iter");
 }
 
-void gl_set_lds_attr() {                                                      // 8-wave tiles of F = 42 frames need 79 KB of LDS
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gl_iter_kernel<true, 8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gl_iter_kernel<false, 8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gl_iter_kernel<true, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gl_iter_kernel<false, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+template <bool MOM>
+void gl_set_lds_attr_mom() {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gl_iter_kernel<true, 8, false, MOM>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gl_iter_kernel<false, 8, false, MOM>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gl_iter_kernel<true, 8, true, MOM>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gl_iter_kernel<false, 8, true, MOM>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
 }
 
-int gl_check(const ZsGlIter* p, const char* what) {
+void gl_set_lds_attr() {                                                      // 8-wave tiles of F = 42 frames need 79 KB of LDS
+  gl_set_lds_attr_mom<false>();
+  gl_set_lds_attr_mom<true>();
+}
+
+bool gl_overlap(const void* x, const void* y, size_t bytes) {
+  const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
+  return x != nullptr && y != nullptr && a < b + bytes && b < a + bytes;
+}
+
+// momentum in [0, 1); with momentum > 0 the state must be given and share no byte with the spectrogram buffers a, b
+int gl_check(const ZsGlIter* p, const char* what, const void* a, const void* b) {
   ZS_REQUIRE(p && p->mag && p->lengths && p->n_utt > 0 && p->T_max >= 4, "%s: bad args", what);
   ZS_REQUIRE(p->tile_frames == 0 || (p->tile_frames >= 4 && p->tile_frames <= 42), "%s: tile_frames must be in [4, 42]", what);
+  ZS_REQUIRE(std::isfinite(p->momentum) && p->momentum >= 0.f && p->momentum < 1.f, "%s: momentum %g is outside [0, 1)", what,
+             (double)p->momentum);
+  if (p->momentum > 0.f) {
+    ZS_REQUIRE(p->spec_prev != nullptr, "%s: momentum > 0 needs spec_prev", what);
+    const size_t bytes = (size_t)p->n_utt * p->T_max * NB * 2 * sizeof(float);
+    ZS_REQUIRE(!gl_overlap(p->spec_prev, a, bytes) && !gl_overlap(p->spec_prev, b, bytes),
+               "%s: spec_prev must not overlap the spectrogram buffers", what);
+  }
   return ZS_OK;
 }
 
 }  // namespace
 
 extern "C" int zs_gl_iter(const ZsGlIter* p, void* stream) {
-  int rc = gl_check(p, "zs_gl_iter");
+  int rc = gl_check(p, "zs_gl_iter", p ? p->spec_in : nullptr, p ? p->spec_out : nullptr);
   if (rc) return rc;
   hipLaunchKernelGGL(gl_tables_kernel, dim3(4), dim3(256), 0, (hipStream_t)stream);
   ZS_REQUIRE(p->spec_in && p->spec_in != p->spec_out, "zs_gl_iter: spec_in must be given and differ from spec_out");
@@ -529,7 +611,7 @@ int gl_chain(const ZsGlIter& q, float* spec_a, float* spec_b, int n_iter, hipStr
 extern "C" int zs_gl_chains_used(void) { return g_gl_chains_used.load(std::memory_order_relaxed); }
 
 extern "C" int zs_griffin_lim(const ZsGlIter* p, float* spec_a, float* spec_b, int32_t n_iter, void* stream) {
-  int rc = gl_check(p, "zs_griffin_lim");
+  int rc = gl_check(p, "zs_griffin_lim", spec_a, spec_b);
   if (rc) return rc;
   ZS_REQUIRE(spec_a && spec_b && spec_a != spec_b && n_iter >= 0, "zs_griffin_lim: two distinct spectrogram buffers are required");
   ZS_REQUIRE(p->wav && p->wav_ld >= (int64_t)HOP * (p->T_max - 1), "zs_griffin_lim: wav_ld too small");
@@ -575,6 +657,7 @@ extern "C" int zs_griffin_lim(const ZsGlIter* p, float* spec_a, float* spec_b, i
     q[c] = *p;
     q[c].mag = p->mag + u0 * per_utt; q[c].lengths = p->lengths + u0; q[c].n_utt = u1 - u0; q[c].wav = p->wav + (int64_t)u0 * p->wav_ld;
     q[c].tile_frames = F;
+    if (p->spec_prev != nullptr) q[c].spec_prev = p->spec_prev + u0 * per_utt * 2;
     cur[c] = spec_a + u0 * per_utt * 2; nxt[c] = spec_b + u0 * per_utt * 2;
     cs[c] = g->s[c];
     ZS_REQUIRE(hipStreamWaitEvent(cs[c], g->fork, 0) == hipSuccess, "zs_griffin_lim: stream wait");
