@@ -1570,13 +1570,38 @@ __global__ __launch_bounds__(NT, 2) void gemm_wgrad_kernel(const ZsGemmWgrad p, 
 // 32-lane half touches fall on 4 distinct 64-byte bank windows.
 // The (tap 0, ci tile 0) workgroup of each co tile also column-sums its dY tiles (bias gradient): 4 extra ds_read_b128
 // per thread and K tile in the light phase 2, reduced through LDS at the end.
+// K-loop addresses: a lane's dY rows advance by 64 rows per K tile (one carried pointer per row).  Its gathered X rows are
+// carried too when the launch is 1-D, stride 1 and T_out divides 128 (wgrad_p8_carried): splits start at multiples of 64 rows,
+// so rows 128 apart share their in-sample position, and a lane keeps the pointers of tiles kt+2 and kt+3, each stepping by
+// 128 / T_out samples.  Every other launch computes (sample, position, source row) per tile.
+// Slab store: all workgroups of a launch store their 256-KiB tiles at the same time, so the store runs at the chip's write
+// bandwidth whatever its instruction schedule (a fully unrolled copy with an LDS-only wait between the halves measured equal).
+// Fragment reads: a read part that outlasts the partner group's MFMA part is exposed time (a tile takes
+// 2 x sum over phases of max(read part, partner's MFMA part)), so only what the first MFMAs of a phase need is read ahead
+// of its opening barrier.  Phase 1 reads k-steps 0,1 of A0 and B(nq 0) ahead; k-steps 2,3 and all of B(nq 1) go out between
+// its own MFMAs behind counted waits (lgkmcnt counts to 15: at most 14 reads are in flight).  Phase 2 finds B(nq 1) in
+// registers and reads k-steps 0..2 of A1 into the A registers its MFMAs have finished with (a k-step's registers are
+// reloaded only after the MFMAs of the following k-step have issued); phase 3 reads k-step 3.  Each accumulator still
+// sees k-steps 0..3 in order.
+// -DZS_WGP8_PROFILE (diagnostic build, tools/wgrad_p8_profile.py): waves 0 and 4 (one per wave group) of every workgroup stamp
+// the prologue, each phase's read part / opening barrier / MFMA part / closing barrier and the slab store with the cycle
+// counter and add them to zs_wgp8_prof; no stamp exists in the product build.
 // ------------------------------------------------------------------------------------------------
 #define ZS_DSRT(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #off : "=v"(dst) : "v"(addr))
-#define ZS_WP_READ_A(base)                                                                        \
-  ZS_DSRT(ya00, sa0, base + 0);    ZS_DSRT(yb00, sa0, base + 512);  ZS_DSRT(ya01, sa1, base + 0);    ZS_DSRT(yb01, sa1, base + 512);  \
-  ZS_DSRT(ya10, sa0, base + 2048); ZS_DSRT(yb10, sa0, base + 2560); ZS_DSRT(ya11, sa1, base + 2048); ZS_DSRT(yb11, sa1, base + 2560); \
-  ZS_DSRT(ya20, sa0, base + 4096); ZS_DSRT(yb20, sa0, base + 4608); ZS_DSRT(ya21, sa1, base + 4096); ZS_DSRT(yb21, sa1, base + 4608); \
-  ZS_DSRT(ya30, sa0, base + 6144); ZS_DSRT(yb30, sa0, base + 6656); ZS_DSRT(ya31, sa1, base + 6144); ZS_DSRT(yb31, sa1, base + 6656);
+// the four A reads / two B reads of k-step ks (16 rows) at byte offsets o0 (rows +0..3) and o1 = o0 + 512 (rows +4..7)
+#define ZS_WP_RA(ks, o0, o1)                                                                      \
+  __builtin_amdgcn_sched_barrier(0);                                                              \
+  ZS_DSRT(ya##ks##0, sa0, o0); ZS_DSRT(yb##ks##0, sa0, o1); ZS_DSRT(ya##ks##1, sa1, o0); ZS_DSRT(yb##ks##1, sa1, o1); \
+  __builtin_amdgcn_sched_barrier(0);
+#define ZS_WP_RB(x, ks, sbx, o0, o1)                                                              \
+  __builtin_amdgcn_sched_barrier(0);                                                              \
+  ZS_DSRT(x##a##ks, sbx, o0); ZS_DSRT(x##b##ks, sbx, o1);                                         \
+  __builtin_amdgcn_sched_barrier(0);
+// counted wait on the fragment reads (they return in order): at most n of them still in flight
+#define ZS_WP_WAIT(n)                                                                             \
+  __builtin_amdgcn_sched_barrier(0);                                                              \
+  asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory");                                         \
+  __builtin_amdgcn_sched_barrier(0);
 #define ZS_WP_READ_B(x, sbx)                                                                      \
   ZS_DSRT(x##a0, sbx, 0);    ZS_DSRT(x##b0, sbx, 512);  ZS_DSRT(x##a1, sbx, 2048); ZS_DSRT(x##b1, sbx, 2560); \
   ZS_DSRT(x##a2, sbx, 4096); ZS_DSRT(x##b2, sbx, 4608); ZS_DSRT(x##a3, sbx, 6144); ZS_DSRT(x##b3, sbx, 6656);
@@ -1595,6 +1620,15 @@ __global__ __launch_bounds__(NT, 2) void gemm_wgrad_kernel(const ZsGemmWgrad p, 
   ZS_WP_DMA(cond, src1, dst1)                                                                     \
   ZS_WP_MMA(ya21, yb21, x##a2, x##b2, c1); ZS_WP_MMA(ya30, yb30, x##a3, x##b3, c0); ZS_WP_MMA(ya31, yb31, x##a3, x##b3, c1); \
   __builtin_amdgcn_s_setprio(0);
+
+#ifdef ZS_WGP8_PROFILE
+__device__ unsigned long long zs_wgp8_prof[2][24];
+#define ZS_WPT(k) { __builtin_amdgcn_sched_barrier(0); const long long pt1_ = __builtin_readcyclecounter(); pc[k] += pt1_ - pt0; pt0 = pt1_; \
+                    __builtin_amdgcn_sched_barrier(0); }
+#else
+#define ZS_WPT(k)
+#endif
+__device__ __forceinline__ bool wgrad_p8_carried(const ZsGemmWgrad& p) { return p.w_in == 0 && p.stride == 1 && (128 % p.T_out) == 0; }
 
 __global__ __launch_bounds__(PNT, 2) void gemm_wgrad_p8_kernel(const ZsGemmWgrad p, int ci_tiles, int rows_per_split,
                                                               int cout_r, int cin_r) {
@@ -1634,14 +1668,24 @@ __global__ __launch_bounds__(PNT, 2) void gemm_wgrad_p8_kernel(const ZsGemmWgrad
   auto y_ptr = [&](int m, int col) -> const T* {
     return (m < mend && col < p.y_cols) ? dY + (int64_t)m * p.ldy + col : zline;
   };
-  auto x_row = [&](int m, bool& ok) -> const T* {                            // gathered source row of output row m for this tap
-    ok = false;
-    if (m >= mend) return zline;
+  auto x_src = [&](int m, bool& ok) -> const T* {                            // gathered source row of output row m for this tap
     const int b = m / p.T_out, t = m - b * p.T_out;
     const int srow = conv_src_row_g(0, p.pad_mode, p.stride, p.pad_left, p.T_in, t, tap, ok, g2);
     return X + (int64_t)b * p.x_batch_stride + (int64_t)srow * p.ldx;
   };
+  auto x_row = [&](int m, bool& ok) -> const T* {
+    ok = false;
+    if (m >= mend) return zline;
+    return x_src(m, ok);
+  };
+  const bool ycv0 = yc0 < p.y_cols, ycv1 = yc1 < p.y_cols, ycv0h = yc0 + 128 < p.y_cols, ycv1h = yc1 + 128 < p.y_cols;
+  const bool xcv0 = xc0 < p.x_cols, xcv1 = xc1 < p.x_cols, xcv0h = xc0 + 128 < p.x_cols, xcv1h = xc1 + 128 < p.x_cols;
 
+#ifdef ZS_WGP8_PROFILE
+  long long pc[19], pt0 = __builtin_readcyclecounter();
+#pragma unroll
+  for (int i = 0; i < 19; ++i) pc[i] = 0;
+#endif
   unsigned char* const ldsA = smem + wave * 2048;
   unsigned char* const ldsB = smem + 32768 + wave * 2048;
 
@@ -1693,6 +1737,21 @@ __global__ __launch_bounds__(PNT, 2) void gemm_wgrad_p8_kernel(const ZsGemmWgrad
   }
   __builtin_amdgcn_s_barrier();
   if (grp1) __builtin_amdgcn_s_barrier();
+  ZS_WPT(0)
+
+  // carried addresses: dY rows of tile kt+1 (pieces 0,1; pieces 2,3 are 128 columns on), X rows of tiles kt+2 (c) and kt+3 (n).
+  // They run past the operands after the last tile; a pointer is used only where its row is below mend.
+  const int64_t ystep = (int64_t)64 * p.ldy;
+  const T* py0 = dY + (int64_t)(mbeg + 64 + k0) * p.ldy + yc0;
+  const T* py1 = dY + (int64_t)(mbeg + 64 + k1) * p.ldy + yc1;
+  const bool carried = wgrad_p8_carried(p);
+  const int64_t xstep = carried ? (int64_t)(128 / p.T_out) * p.x_batch_stride : 0;
+  const T *px0c = zline, *px0n = zline, *px1c = zline, *px1n = zline;
+  bool xo0c = false, xo0n = false, xo1c = false, xo1n = false;
+  if (carried) {
+    px0c = x_src(mbeg + 128 + k0, xo0c) + xc0; px0n = x_src(mbeg + 192 + k0, xo0n) + xc0;
+    px1c = x_src(mbeg + 128 + k1, xo1c) + xc1; px1n = x_src(mbeg + 192 + k1, xo1n) + xc1;
+  }
 
   uint2 ya00, yb00, ya01, yb01, ya10, yb10, ya11, yb11, ya20, yb20, ya21, yb21, ya30, yb30, ya31, yb31;   // y{a,b}[ks][mi]: rows +0..3 / +4..7
   uint2 f0a0, f0b0, f0a1, f0b1, f0a2, f0b2, f0a3, f0b3;                                                   // B nq=0: [ks]
@@ -1706,20 +1765,39 @@ __global__ __launch_bounds__(PNT, 2) void gemm_wgrad_p8_kernel(const ZsGemmWgrad
     unsigned char* const dB = ldsB + st * PSTAGE;
     const int ma = mbeg + (kt + 1) * 64, mb = mbeg + (kt + 2) * 64;
     // ---- phase 1: quadrant (0,0); A0(kt+1)
-    ZS_WP_READ_A(0)
-    ZS_WP_READ_B(f0, sb0)
-    const T* s0 = y_ptr(ma + k0, yc0);
-    const T* s1 = y_ptr(ma + k1, yc1);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    ZS_WP_RB(f0, 0, sb0, 0, 512) ZS_WP_RA(0, 0, 512) ZS_WP_RB(f0, 1, sb0, 2048, 2560) ZS_WP_RA(1, 2048, 2560)
+    const bool yv0 = ma + k0 < mend, yv1 = ma + k1 < mend;
+    const T* s0 = (yv0 && ycv0) ? py0 : zline;
+    const T* s1 = (yv1 && ycv1) ? py1 : zline;
+    ZS_WP_WAIT(6)                                        // k-step 0 has landed
+    ZS_WPT(1)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    ZS_WP_QUAD(c000, c001, f0, has_a, s0, dA, s1, dA + 1024)
+    ZS_WPT(2)
+    __builtin_amdgcn_s_setprio(1);
+    ZS_WP_MMA(ya00, yb00, f0a0, f0b0, c000); ZS_WP_RB(f0, 2, sb0, 4096, 4608)
+    ZS_WP_MMA(ya01, yb01, f0a0, f0b0, c001); ZS_WP_RA(2, 4096, 4608)
+    ZS_WP_DMA(has_a, s0, dA)
+    ZS_WP_WAIT(6)                                        // 18 issued: k-step 1 has landed
+    ZS_WP_MMA(ya10, yb10, f0a1, f0b1, c000); ZS_WP_RB(f0, 3, sb0, 6144, 6656)
+    ZS_WP_MMA(ya11, yb11, f0a1, f0b1, c001); ZS_WP_RA(3, 6144, 6656)
+    ZS_WP_WAIT(6)                                        // 24 issued: k-step 2
+    ZS_WP_MMA(ya20, yb20, f0a2, f0b2, c000);
+    ZS_WP_DMA(has_a, s1, dA + 1024)
+    ZS_WP_RB(f1, 0, sb1, 0, 512) ZS_WP_RB(f1, 1, sb1, 2048, 2560)
+    ZS_WP_MMA(ya21, yb21, f0a2, f0b2, c001);
+    ZS_WP_RB(f1, 2, sb1, 4096, 4608) ZS_WP_RB(f1, 3, sb1, 6144, 6656)
+    ZS_WP_WAIT(8)                                        // 32 issued: k-step 3; the 8 reads of B(nq 1) stay in flight
+    ZS_WP_MMA(ya30, yb30, f0a3, f0b3, c000); ZS_WP_MMA(ya31, yb31, f0a3, f0b3, c001);
+    __builtin_amdgcn_s_setprio(0);
+    ZS_WPT(3)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
+    ZS_WPT(4)
     // ---- phase 2: quadrant (0,1); A1(kt+1); bias partial sums of this tile
-    ZS_WP_READ_B(f1, sb1)
-    s0 = y_ptr(ma + k0, yc0 + 128);
-    s1 = y_ptr(ma + k1, yc1 + 128);
+    s0 = (yv0 && ycv0h) ? py0 + 128 : zline;
+    s1 = (yv1 && ycv1h) ? py1 + 128 : zline;
+    py0 += ystep; py1 += ystep;
     if (do_bias) {
       u32x4_t v0, v1, v2, v3;
       const unsigned ba = bias_addr + so;
@@ -1732,41 +1810,82 @@ __global__ __launch_bounds__(PNT, 2) void gemm_wgrad_p8_kernel(const ZsGemmWgrad
         bsum[2 * (i & 3) + 1] += __uint_as_float(w[i] & 0xffff0000u);
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    ZS_WP_WAIT(0)
+    ZS_WPT(5)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    ZS_WP_QUAD(c010, c011, f1, has_a, s0, dA + 16384, s1, dA + 16384 + 1024)
+    ZS_WPT(6)
+    __builtin_amdgcn_s_setprio(1);
+    ZS_WP_MMA(ya00, yb00, f1a0, f1b0, c010); ZS_WP_MMA(ya01, yb01, f1a0, f1b0, c011);
+    ZS_WP_DMA(has_a, s0, dA + 16384)
+    ZS_WP_MMA(ya10, yb10, f1a1, f1b1, c010); ZS_WP_MMA(ya11, yb11, f1a1, f1b1, c011);
+    ZS_WP_RA(0, 8192, 8704)                              // A1 half, k-step 0
+    ZS_WP_MMA(ya20, yb20, f1a2, f1b2, c010);
+    ZS_WP_DMA(has_a, s1, dA + 16384 + 1024)
+    ZS_WP_MMA(ya21, yb21, f1a2, f1b2, c011);
+    ZS_WP_RA(1, 10240, 10752)
+    ZS_WP_MMA(ya30, yb30, f1a3, f1b3, c010); ZS_WP_MMA(ya31, yb31, f1a3, f1b3, c011);
+    ZS_WP_RA(2, 12288, 12800)
+    __builtin_amdgcn_s_setprio(0);
+    ZS_WPT(7)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
+    ZS_WPT(8)
     // ---- phase 3: quadrant (1,1); B0(kt+2)
-    ZS_WP_READ_A(8192)
     bool ok0, ok1;
-    const T* r0 = x_row(mb + k0, ok0);
-    const T* r1 = x_row(mb + k1, ok1);
-    s0 = (ok0 && xc0 < p.x_cols) ? r0 + xc0 : zline;
-    s1 = (ok1 && xc1 < p.x_cols) ? r1 + xc1 : zline;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const T *r0, *r1;                                    // rows of X for tile kt+2 at this lane's columns (pieces 0,1)
+    if (carried) {
+      ok0 = xo0c && (mb + k0 < mend); ok1 = xo1c && (mb + k1 < mend);
+      r0 = px0c; r1 = px1c;
+      const T* n0 = px0c + xstep; const T* n1 = px1c + xstep;
+      px0c = px0n; px1c = px1n; px0n = n0; px1n = n1;
+      const bool t0 = xo0c, t1 = xo1c;
+      xo0c = xo0n; xo1c = xo1n; xo0n = t0; xo1n = t1;
+    } else {
+      r0 = x_row(mb + k0, ok0) + xc0;
+      r1 = x_row(mb + k1, ok1) + xc1;
+    }
+    s0 = (ok0 && xcv0) ? r0 : zline;
+    s1 = (ok1 && xcv1) ? r1 : zline;
+    ZS_WP_RA(3, 14336, 14848)
+    ZS_WP_WAIT(4)                                        // k-steps 0..2 of A1 have landed
+    ZS_WPT(9)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    ZS_WP_QUAD(c110, c111, f1, has_b, s0, dB, s1, dB + 1024)
+    ZS_WPT(10)
+    __builtin_amdgcn_s_setprio(1);
+    ZS_WP_MMA(ya00, yb00, f1a0, f1b0, c110); ZS_WP_MMA(ya01, yb01, f1a0, f1b0, c111);
+    ZS_WP_DMA(has_b, s0, dB)
+    ZS_WP_MMA(ya10, yb10, f1a1, f1b1, c110); ZS_WP_MMA(ya11, yb11, f1a1, f1b1, c111); ZS_WP_MMA(ya20, yb20, f1a2, f1b2, c110);
+    ZS_WP_DMA(has_b, s1, dB + 1024)
+    ZS_WP_MMA(ya21, yb21, f1a2, f1b2, c111);
+    ZS_WP_WAIT(0)
+    ZS_WP_MMA(ya30, yb30, f1a3, f1b3, c110); ZS_WP_MMA(ya31, yb31, f1a3, f1b3, c111);
+    __builtin_amdgcn_s_setprio(0);
+    ZS_WPT(11)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
+    ZS_WPT(12)
     // ---- phase 4: quadrant (1,0); B1(kt+2); the counted waits for tile kt+1
-    s0 = (ok0 && xc0 + 128 < p.x_cols) ? r0 + xc0 + 128 : zline;
-    s1 = (ok1 && xc1 + 128 < p.x_cols) ? r1 + xc1 + 128 : zline;
+    s0 = (ok0 && xcv0h) ? r0 + 128 : zline;
+    s1 = (ok1 && xcv1h) ? r1 + 128 : zline;
     if (grp1) {
       if (has_b) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
+    ZS_WPT(13)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
+    ZS_WPT(14)
     ZS_WP_QUAD(c100, c101, f0, has_b, s0, dB + 16384, s1, dB + 16384 + 1024)
+    ZS_WPT(15)
     if (!grp1) {
       if (has_b) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
+    ZS_WPT(16)
   }
   if (!grp1) __builtin_amdgcn_s_barrier();          // pairs with group 1's last barrier
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1790,6 +1909,7 @@ __global__ __launch_bounds__(PNT, 2) void gemm_wgrad_p8_kernel(const ZsGemmWgrad
   // slab[split][co][tap][ci] (co < cout_r, ci < cin_r: whole tiles), staged through LDS in two 128-ci halves
   float* slab = (float*)p.workspace + (int64_t)split * cout_r * p.taps * cin_r;
   float* sC = reinterpret_cast<float*>(smem);
+  ZS_WPT(17)
 #pragma unroll 1
   for (int h = 0; h < 2; ++h) {
     if ((wc >> 1) == h) {
@@ -1817,6 +1937,15 @@ __global__ __launch_bounds__(PNT, 2) void gemm_wgrad_p8_kernel(const ZsGemmWgrad
     }
     __syncthreads();
   }
+#ifdef ZS_WGP8_PROFILE
+  ZS_WPT(18)
+  if (lane == 0 && (wave & 3) == 0) {
+#pragma unroll
+    for (int i = 0; i < 19; ++i) atomicAdd(&zs_wgp8_prof[wr][i], (unsigned long long)pc[i]);
+    atomicAdd(&zs_wgp8_prof[wr][19], (unsigned long long)nk);
+    atomicAdd(&zs_wgp8_prof[wr][20], 1ull);
+  }
+#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2294,3 +2423,16 @@ extern "C" int zs_gemm_wgrad(const ZsGemmWgrad* p, void* stream) {
   }
   return zs_check_launch("zs_gemm_wgrad.reduce");
 }
+
+#ifdef ZS_WGP8_PROFILE
+// diagnostic build only: copies out (and optionally clears) the stamps of gemm_wgrad_p8_kernel, [wave group][slot]
+extern "C" int zs_wgp8_profile_read(unsigned long long* out, int reset) {
+  if (hipDeviceSynchronize() != hipSuccess) return 1;
+  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(zs_wgp8_prof), sizeof(unsigned long long) * 48) != hipSuccess) return 1;
+  if (reset) {
+    unsigned long long z[48] = {0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(zs_wgp8_prof), z, sizeof(z)) != hipSuccess) return 1;
+  }
+  return 0;
+}
+#endif
