@@ -464,6 +464,27 @@ int zs_adam_clip(const ZsAdam* p, void* stream);
  * bytes must be a multiple of 16, both pointers 16-byte aligned. */
 int zs_host_fetch(const void* src, void* dst, size_t bytes, int32_t workgroups, void* stream);
 
+/* zs_pool_gather: one training batch out of a dataset that lies in device memory (the reference builds it on the host,
+ * dataloader.py:34-52, and copies it over, trainer.py:238-244).  pool fp32 [frames_total][F], utterances back to back; the item table
+ * of n entries: speaker int32 [n], first int64 [n] = first frame of the item's segment in the pool.  With k = *cursor, S = world * B
+ * and P = max(1, ceil(n / S) - 1), batch k serves the items
+ *   item(b) = ((k mod P) * S + rank * B + b) mod n,   b < B       (dataloader.py:48-51's sliding index and wrap rule in closed form;
+ *                                                                  the mod n only ever acts when world > 1)
+ *   x[b][t][f] = pool[first[item(b)] + t][f]   t < seg_len, f < F      x fp32 [B][seg_len][F] contiguous
+ *   c[b]       = speaker[item(b)]                                      c int64 [B]
+ * advance != 0: a one-thread launch behind the gather then does *cursor += 1, so a captured launch with frozen arguments serves
+ * the next batch at every replay.  The cursor is an int64 in device memory that the host may set (>= 0) between launches.
+ * n >= world * B is required.  The kernel trusts the table: the caller checks 0 <= first and first + seg_len <= frames_total
+ * for every entry on the host before it uploads it.  pool and x need 4-byte alignment only.  No allocation, no synchronisation. */
+typedef struct {
+  const float* pool; const int32_t* speaker; const int64_t* first;
+  int64_t* cursor;
+  int64_t n; int32_t B, seg_len, F, rank, world;
+  float* x; int64_t* c;
+  int32_t advance;
+} ZsPoolGather;
+int zs_pool_gather(const ZsPoolGather* p, void* stream);
+
 /* zs_step_counters: per-step device-side state for hipGraph replay (kernel arguments are frozen in a graph):
  * *seed += 0x9E3779B97F4A7C15, *step += 1.  Either pointer may be null. */
 int zs_step_counters(uint64_t* seed, int32_t* step, void* stream);

@@ -14,6 +14,9 @@ Vocoder of --test, --cross_test and --test_single: --gl_iters N sets the Griffin
 --gl_momentum A in [0, 1) the fast Griffin-Lim momentum (hp.gl_momentum, default 0: the reference's plain loop), e.g.
 `--gl_iters 100 --gl_momentum 0.99`.
 
+Every --train* mode takes --device_data: the training set is uploaded into GPU memory once and each batch is gathered there
+(zs_amd.pool), in the host DataLoader's order; ZS_POOL_MAX_GB caps the pool's size.
+
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
 (--train_al, --train_t, --encode, --test_asr) are not part of this build and exit with a clear error.
@@ -50,6 +53,9 @@ def build_parser():
     for flag in ['preprocess', 'train', 'train_ae', 'train_p', 'train_tgat', 'train_c', 'test', 'cross_test', 'test_encode', 'test_single',
                  'test_classify', 'load_model', 'enc_only', 'remake', 'synthetic'] + OUT_OF_SCOPE:
         p.add_argument('--' + flag, default=False, action='store_true')
+    p.add_argument('--device_data', default=False, action='store_true',
+                   help='every --train* mode: hold the training set in GPU memory and gather each batch on the device '
+                        '(zs_amd.pool; size limit ZS_POOL_MAX_GB); default: the host DataLoader')
     p.add_argument('--flag', type=str, default='train')
     p.add_argument('--g_mode', default='set_from_hps',
                    choices=['naive', 'targeted', 'targeted_residual', 'enhanced', 'spectrogram', 'tacotron', 'set_from_hps'])
@@ -139,7 +145,16 @@ def main(argv=None):
             dataset = Dataset(args.dataset_path, args.index_path, seg_len=hps.seg_len)
             sourceset = Dataset(args.dataset_path, args.index_source_path, seg_len=hps.seg_len)
             targetset = Dataset(args.dataset_path, args.index_target_path, seg_len=hps.seg_len)
-        mk = lambda ds: DataLoader(ds, hps.batch_size, rank=rank, world=world)           # disjoint per-rank shards of each global batch
+        if args.device_data:
+            # the sets the chosen modes read, uploaded once into one pool (index files over one store share their utterances)
+            import torch
+            from zs_amd.pool import DevicePool, PoolLoader
+            stage1, stage2 = args.train or args.train_ae or args.train_c, args.train or args.train_p or args.train_tgat
+            used = ([dataset] if stage1 else []) + ([sourceset, targetset] if stage2 else [])
+            pool = DevicePool(used, torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0'))))
+            mk = lambda ds: PoolLoader(pool, ds, hps.batch_size, rank=rank, world=world) if any(ds is u for u in used) else None
+        else:
+            mk = lambda ds: DataLoader(ds, hps.batch_size, rank=rank, world=world)       # disjoint per-rank shards of each global batch
         data_loader, source_loader, target_loader = mk(dataset), mk(sourceset), mk(targetset)
         os.makedirs(args.ckpt_dir, exist_ok=True)
         model_path = os.path.join(args.ckpt_dir, args.model_name)

@@ -191,11 +191,14 @@ class AEStep(object):
         return self._loss
 
     # ---- graph mode ------------------------------------------------------------------------------------------------
-    def _warm_up_or_capture(self, x_btf, c, capture):
+    def _warm_up_or_capture(self, x_btf, c, capture, prologue=None):
         """Before a shape's graphs exist: the first graph_warmup calls run the counted step eagerly on (x_btf, c) -- the launches
-        of the captured step; every buffer allocated, every workspace grown -- and return None; after them, return capture()."""
+        of the captured step; every buffer allocated, every workspace grown -- and return None; after them, return capture().
+        prologue: launches in front of an eager step (the ones capture() puts in front of the captured one, see _capture)."""
         if self._eager_calls < self.graph_warmup:
             self._eager_calls += 1
+            if prologue is not None:
+                prologue()
             self._execute(self.plan(x_btf, c, parallel.multi_rank(), True), counted=True)
             return None
         return capture()
@@ -229,11 +232,12 @@ class AEStep(object):
                                       torch.zeros(B, dtype=torch.int64, device=self.device))
         return self._statics[key]
 
-    def _capture(self, xs, cs, prefetch=()):
+    def _capture(self, xs, cs, prefetch=(), prologue=None):
         """Capture the counted step on the static inputs xs, cs: each run of consecutive 'run' actions becomes one hipGraph, a host
         action ends it.  Returns the entry whose plan is the step with every graph as a 'run' of its replay.  prefetch: (src
         pinned, dst) pairs, the H2D copy of the NEXT batch, forked at the start of the first graph and joined at its end (one
-        rank: the end of the step) -- it runs on its own stream beside the kernels of this step."""
+        rank: the end of the step) -- it runs on its own stream beside the kernels of this step.  prologue: launches captured in
+        front of the first graph's step on the step's own stream (PoolFedStep: the gather of THIS batch into xs, cs)."""
         torch.cuda.synchronize(self.device)
         graphs, plan, runs = [], [], []
         pool = None
@@ -245,6 +249,8 @@ class AEStep(object):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=pool, capture_error_mode='thread_local'):   # other threads (RCCL watchdog) may call HIP
                 fetched = self._fork_fetch(prefetch) if prefetch and not graphs else None
+                if prologue is not None and not graphs:
+                    prologue()
                 for fn in runs:
                     fn()
                 if fetched is not None:                            # the branch joins inside the graph it forked in
@@ -286,6 +292,11 @@ class AEStep(object):
         """Iterator that runs one training step per `next()` on the batches of a HOST loader (`next(loader)` -> (c int64 [B],
         x fp32 [B, T, F]) CPU tensors, the reference's DataLoader contract): see HostFedStep."""
         return HostFedStep(self, loader)
+
+    def pool_feeder(self, loader):
+        """Iterator that runs one training step per `next()` on the batches of a pool.PoolLoader, gathered on the device at the
+        head of the (captured) step: see PoolFedStep."""
+        return PoolFedStep(self, loader)
 
     def grad_norms(self):
         """Squared per-net gradient norms as device scalars (Encoder, Decoder are clipped separately).  With more than one
@@ -374,6 +385,38 @@ class HostFedStep(object):
         self.PC[k].copy_(self._next[0])
         self.P[k].copy_(self._next[1])
         self.i += 1
+        return ae._loss
+
+
+class PoolFedStep(object):
+    """The --train_ae step fed from a pool.DevicePool, the sibling of HostFedStep: the captured step begins with the gather of its
+    batch into AEStep.static_inputs and the cursor's advance (pool.PoolLoader.gather_into), on the step's own stream -- no forked
+    branch, no pinned buffer, one set of graphs -- so a replay serves the next batch and the host never waits.  The AEStep's
+    eager warm-up steps, and every step when graphs are off, run the same launches eagerly."""
+
+    def __init__(self, ae, loader):
+        self.ae, self.loader = ae, loader
+        loader.require(n_speakers=ae.Decoder.c_a)                             # an index outside the embedding tables would fault the GPU
+        self.x, self.c = ae.static_inputs(loader.batch_size, loader.seg_len, loader.F)
+        self.ent = None
+
+    def _gather(self):
+        self.loader.gather_into(self.x, self.c)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        ae = self.ae
+        if not ae.use_graph:
+            self._gather()
+            return ae.step(self.x, self.c)
+        if self.ent is None:
+            self.ent = ae._warm_up_or_capture(self.x, self.c, lambda: ae._capture(self.x, self.c, prologue=self._gather),
+                                              prologue=self._gather)
+            if self.ent is None:                                              # a warm-up step: done
+                return ae._loss
+        ae._execute(self.ent['plan'], counted=True)
         return ae._loss
 
 
@@ -708,20 +751,28 @@ class Trainer(object):
         return self.ae.step(x_btf, c, **kw)
 
     # ---- the loop (trainer.py:316-347) -----------------------------------------------------------
+    def _device_batches(self, loader, n_speakers=None, check=None):
+        """The iterator of device batches `(c, x)` over `loader`: a pool.PoolLoader serves them itself, once its whole speaker column
+        has passed the checks (host memory, before any launch); a host loader goes through a DevicePrefetcher that applies them to
+        every batch."""
+        from .pool import PoolLoader
+        if isinstance(loader, PoolLoader):
+            return loader.require(n_speakers=n_speakers, check=check)
+        from .dataloader import DevicePrefetcher
+        return DevicePrefetcher(loader, self.device, n_speakers=n_speakers, check=check)       # next batch copied under the current step
+
     def _batch(self):
         if self._prefetch is None:
-            from .dataloader import DevicePrefetcher
-            self._prefetch = DevicePrefetcher(self.data_loader, self.device, n_speakers=self.hps.n_speakers)   # next batch copied under the current step
+            self._prefetch = self._device_batches(self.data_loader, n_speakers=self.hps.n_speakers)
         return next(self._prefetch)
 
     def _duo_batch(self):
         """next(source_loader), next(target_loader) through the prefetcher (trainer.py:472-475)."""
         if getattr(self, '_duo', None) is None:
-            from .dataloader import DevicePrefetcher
             if self.source_loader is None or self.target_loader is None:
                 raise RuntimeError('patchGAN needs add_duo_loader(source_loader, target_loader)')
-            self._duo = (DevicePrefetcher(self.source_loader, self.device, n_speakers=self.hps.n_speakers),
-                         DevicePrefetcher(self.target_loader, self.device, n_speakers=self.hps.n_speakers, check=self.stage2().check_targets))
+            self._duo = (self._device_batches(self.source_loader, n_speakers=self.hps.n_speakers),
+                         self._device_batches(self.target_loader, n_speakers=self.hps.n_speakers, check=self.stage2().check_targets))
         return next(self._duo[0]), next(self._duo[1])
 
     def tclf_labels(self, c_host):
@@ -738,8 +789,7 @@ class Trainer(object):
         """next(data_loader) through a prefetcher whose check range-checks the relabelled targets of every batch on the host
         (tclf_labels, raising ValueError) before it is copied; the relabel the step uses runs on the device (TclfStep.step)."""
         if getattr(self, '_tclf_prefetch', None) is None:
-            from .dataloader import DevicePrefetcher
-            self._tclf_prefetch = DevicePrefetcher(self.data_loader, self.device, check=self.tclf_labels)
+            self._tclf_prefetch = self._device_batches(self.data_loader, check=self.tclf_labels)
         return next(self._tclf_prefetch)
 
     def _log(self, iteration, iters, fmt, info, head=()):
@@ -768,7 +818,11 @@ class Trainer(object):
     def train(self, model_path, flag='train', mode='train', target_guided=False):
         hps = self.hps
         if mode == 'pretrain_AE':                                                         # trainer.py:320-347
-            feeder = self.ae.host_feeder(self.data_loader) if self.ae.use_graph else None  # H2D of the next batch inside the graph
+            from .pool import PoolLoader
+            if isinstance(self.data_loader, PoolLoader):
+                feeder = self.ae.pool_feeder(self.data_loader.require(n_speakers=hps.n_speakers))   # the gather at the head of the step
+            else:
+                feeder = self.ae.host_feeder(self.data_loader) if self.ae.use_graph else None  # H2D of the next batch inside the graph
 
             def iteration_fn(iteration, log):
                 if feeder is not None:
