@@ -124,6 +124,25 @@ typedef struct {
   int32_t w_in, w_out, taps_h;
 } ZsGemmConv;
 int zs_gemm_conv(const ZsGemmConv* p, void* stream);
+/* zs_gemm_conv_path: the kernel a zs_gemm_conv launch of *p would take now, under the current knobs -- the same plan function the
+ * launch calls (argument checks and dispatch; tile counts below are of M = B*T_out rows by N columns).  Returns
+ * path | regs_epilogue << 8, or the negative code zs_gemm_conv would return for these arguments.  It reads the struct and the
+ * knobs only: A, W, out, ... are tested for null and alignment, never dereferenced, and no GPU call is made.
+ *   P8:      256x256 quadrant ping-pong kernel: "gemm_dma", "gemm_p8", n_pad % 256 == 0, at least "gemm_p8_min_tiles" 256x256 tiles;
+ *   RING_PP / RING: 256x128 3-stage ring, ping-pong ("gemm_pp") or lock-step: else, with "gemm_dma" and "gemm_ring", at least
+ *            "gemm_ring_min_tiles" 256x128 tiles;
+ *   DMA64:   LDS-DMA kernel, 64-row tiles: else, with "gemm_dma" and "gemm_dma64", twice the 128x128 tile count at most
+ *            "gemm_dma64_max_tiles" and, for a colsum launch, T_out | 64;
+ *   DMA128:  LDS-DMA kernel, 128x128 tiles: every other launch with "gemm_dma";   REG: register-staged 128x128 kernel ("gemm_dma" 0).
+ * regs_epilogue (bit 8): a P8 bf16 launch finishes its tile in the register epilogue, which stages the tile as bf16 BEFORE the
+ * dact_src mask / add_src (two roundings) and sums colsum over the staged bf16 values; it needs bf16 `out` (no out_f32) with
+ * out_cols % 8 == 0, 16-byte aligned out / out2 / dact_src / add_src rows, no add_f32, no out2 together with dact_src / add_src,
+ * T_out % 16 == 0 with pre_vec / vec2, (N / 2) % 8 == 0 with SPLIT2, act NONE or LRELU, T_out | 256 and no out2 with colsum.
+ * 0 on every other path and for fp32.
+ * `groups` > 1: no Python caller passes it; the library's own STEP_GEMM GRU path does (2 directions) and tests it there. */
+enum { ZS_GEMM_PATH_P8 = 0, ZS_GEMM_PATH_RING_PP = 1, ZS_GEMM_PATH_RING = 2, ZS_GEMM_PATH_DMA64 = 3, ZS_GEMM_PATH_DMA128 = 4,
+       ZS_GEMM_PATH_REG = 5 };
+int zs_gemm_conv_path(const ZsGemmConv* p);
 
 /* ---------------------------------------------------------------------------------------------
  * zs_gemm_wgrad: weight gradient of the same convolution,

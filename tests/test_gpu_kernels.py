@@ -75,16 +75,18 @@ def _ref_conv(x_btc, w, b, stride, reflect):
     return F.conv1d(xp, w3, b, stride=stride).permute(0, 2, 1)
 
 
-GEMM_KEYS = ('gemm_dma', 'gemm_ring', 'gemm_ring_min_tiles', 'gemm_pp', 'gemm_p8', 'gemm_p8_min_tiles', 'wgrad_p8')
-GEMM_VARIANTS = {'p8m16': (1, 1, 1, 1, 1, 1, 2), 'pp': (1, 1, 1, 1, 0, 200, 0), 'ring': (1, 1, 1, 0, 0, 200, 0),
-                 'dma': (1, 0, 256, 0, 0, 200, 0), 'reg': (0, 0, 256, 0, 0, 200, 0)}
+GEMM_KEYS = ('gemm_dma', 'gemm_ring', 'gemm_ring_min_tiles', 'gemm_pp', 'gemm_p8', 'gemm_p8_min_tiles', 'wgrad_p8', 'gemm_dma64')
+GEMM_VARIANTS = {'p8m16': (1, 1, 1, 1, 1, 1, 2, 1), 'pp': (1, 1, 1, 1, 0, 200, 0, 1), 'ring': (1, 1, 1, 0, 0, 200, 0, 1),
+                 'dma': (1, 0, 256, 0, 0, 200, 0, 1), 'dma128': (1, 0, 256, 0, 0, 200, 0, 0), 'reg': (0, 0, 256, 0, 0, 200, 0, 1)}
 
 
 @pytest.fixture(params=list(GEMM_VARIANTS))
 def gemm_variant(request, zs):
-    """Run a test with each conv-GEMM kernel: 256x256 quadrant ping-pong (where the packed weight has a multiple of 256 rows,
-    else it falls through to the ring), 256x128 3-stage ring with the ping-pong schedule, the same ring in lock-step,
-    128x128 LDS-DMA, 128x128 register-staged.  The 'p8m16' variant also forces the 256x256 ping-pong weight-gradient kernel
+    """Run a test with each conv-GEMM kernel instantiation (six; zs_gemm_conv_path names them): 256x256 quadrant ping-pong
+    (where the packed weight has a multiple of 256 rows, else it falls through to the ring), 256x128 3-stage ring with the
+    ping-pong schedule, the same ring in lock-step, LDS-DMA with 64-row tiles ('dma': these sizes have at most 128 tiles of
+    128x128; a colsum launch whose T_out does not divide 64 takes the 128-row tiles), LDS-DMA with 128x128 tiles ('dma128':
+    gemm_dma64 = 0), 128x128 register-staged.  The 'p8m16' variant also forces the 256x256 ping-pong weight-gradient kernel
     (bf16; wgrad_p8=2 overrides its size heuristics), the others use the 128x128 one."""
     L, _ = zs
     old = [L.set_option(k, v) for k, v in zip(GEMM_KEYS, GEMM_VARIANTS[request.param])]

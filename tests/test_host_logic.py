@@ -159,6 +159,122 @@ def test_gru_path_query_cases_independent_of_the_cu_count(lib):
     assert q(0, BF16, 4, 8, 100, 1, 1) < 0                               # H % 8 != 0 is refused by the launches too
 
 
+def test_gemm_conv_path_query(lib):
+    """zs_gemm_conv_path: the kernel a zs_gemm_conv launch would take (the launch's own plan function), under the default knobs at
+    the production shapes and with every dispatch knob flipped.  Operands are dummy aligned non-null integers: the query
+    dereferences nothing and touches no GPU."""
+    q = lib.lib().zs_gemm_conv_path
+    q.argtypes = [ctypes.c_void_p]
+    P8, RPP, RING, D64, D128, REG = (lib.ZS_GEMM_PATH_P8, lib.ZS_GEMM_PATH_RING_PP, lib.ZS_GEMM_PATH_RING, lib.ZS_GEMM_PATH_DMA64,
+                                     lib.ZS_GEMM_PATH_DMA128, lib.ZS_GEMM_PATH_REG)
+    PTR = 0x10000
+
+    def rup(x, m):
+        return (x + m - 1) // m * m
+
+    def path(B=256, T=128, N=1024, Cin=1024, k=1, dtype=lib.ZS_BF16, **kw):
+        kc = 64 if dtype == lib.ZS_BF16 else 32
+        cin_pad = rup(Cin, kc)
+        a = dict(dtype=dtype, A=PTR, lda=cin_pad, a_batch_stride=T * cin_pad, B=B, T_in=T, T_out=T, taps=k, stride=1, pad_left=k // 2,
+                 pad_mode=lib.ZS_PAD_REFLECT, gather=0, cin_pad=cin_pad, W=2 * PTR, ldw=k * cin_pad, N=N, n_pad=rup(N, 128), out=3 * PTR,
+                 ldc=rup(N, 32), out_cols=rup(N, 32), groups=1)
+        a.update(kw)
+        s = lib.STRUCTS['ZsGemmConv'](**a)
+        rc = q(ctypes.addressof(s))
+        assert rc >= 0, lib.last_error()
+        return rc & 255, rc >> 8
+
+    keys = ('gemm_dma', 'gemm_ring', 'gemm_ring_min_tiles', 'gemm_pp', 'gemm_p8', 'gemm_p8_min_tiles', 'gemm_dma64',
+            'gemm_dma64_max_tiles')
+    defaults = (1, 1, 256, 1, 1, 200, 1, 256)
+    old = {k: lib.set_option(k, v) for k, v in zip(keys, defaults)}
+    try:
+        # the bench size under the default knobs: B = 256, seg_len = 128
+        assert path(N=128, Cin=513, k=7) == (D128, 0)            # conv bank: 256 tiles of 128 x 128, one tile column
+        assert path(N=513) == (RPP, 0)                           # final linear: n_pad 640, 128 * 5 ring tiles
+        assert path(N=1024) == (P8, 1)                           # plain bf16 row output: register epilogue
+        assert path(N=1024, dtype=lib.ZS_F32) == (P8, 0)         # fp32 never takes it
+        assert path(N=1024, out_f32=1) == (P8, 0)
+        assert path(N=1024, out_cols=516, ldc=1056) == (P8, 0)
+        assert path(N=1024, pre_vec=4 * PTR, pre_vec_ld=1024, vec_idx=5 * PTR, T=24, B=2048) == (P8, 0)
+        assert path(N=1024, pre_vec=4 * PTR, pre_vec_ld=1024, vec_idx=5 * PTR, T=16, B=2048) == (P8, 1)
+        assert path(N=1024, out=3 * PTR + 8) == (P8, 0)          # rows not 16-byte aligned
+        assert path(N=1024, add_src=4 * PTR, add_ld=1024, add_f32=1) == (P8, 0)
+        assert path(N=1024, add_src=4 * PTR, add_ld=1024) == (P8, 1)
+        assert path(N=1024, act=lib.ZS_ACT_TANH) == (P8, 0)
+        assert path(N=2048, store_mode=lib.ZS_STORE_SPLIT2, out_cols=1024, ldc=1024, k=3) == (P8, 1)
+        assert path(B=1, T=129, N=1024, k=3) == (D64, 0)         # batch-1 inference: 16 tiles of 128 x 128
+        # n_pad = 384 is never P8, whatever the tile count
+        assert path(N=384, B=2048)[0] == RPP
+        lib.set_option('gemm_p8_min_tiles', 0)
+        assert path(N=384, B=1, T=64)[0] != P8 and path(N=260, B=1, T=64)[0] != P8
+        assert path(N=260, n_pad=512, B=1, T=64)[0] == P8
+        lib.set_option('gemm_p8_min_tiles', 200)
+        # the tile-count thresholds, from both sides
+        assert path(B=100, T=128, N=1024)[0] == P8               # 50 * 4 = 200 tiles of 256 x 256
+        assert path(B=99, T=128, N=1024)[0] == P8                # 12672 rows: still 50 row tiles
+        assert path(B=98, T=128, N=1024)[0] == RPP               # 49 * 4 = 196 < 200; 49 * 8 = 392 ring tiles
+        lib.set_option('gemm_p8_min_tiles', 201)
+        assert path(B=100, T=128, N=1024)[0] == RPP
+        lib.set_option('gemm_p8_min_tiles', 200)
+        lib.set_option('gemm_p8', 0)
+        assert path(N=1024) == (RPP, 0)
+        lib.set_option('gemm_pp', 0)
+        assert path(N=1024) == (RING, 0) and path(N=513) == (RING, 0)
+        lib.set_option('gemm_pp', 1)
+        assert path(B=64, T=128, N=1024)[0] == RPP               # 32 * 8 = 256 ring tiles
+        assert path(B=63, T=128, N=1024)[0] == RPP               # 8064 rows: still 32 row tiles
+        assert path(B=62, T=128, N=1024)[0] == D128              # 31 * 8 = 248 < 256; 62 * 8 128-row tiles: too many for DMA64
+        lib.set_option('gemm_ring_min_tiles', 248)
+        assert path(B=62, T=128, N=1024)[0] == RPP
+        lib.set_option('gemm_ring_min_tiles', 256)
+        lib.set_option('gemm_ring', 0)
+        assert path(N=1024) == (D128, 0) and path(N=513) == (D128, 0)
+        # 64-row tiles: twice the 128 x 128 tile count at most gemm_dma64_max_tiles
+        assert path(B=16, T=128, N=1024)[0] == D64               # 16 * 8 = 128 tiles
+        assert path(B=17, T=128, N=1024)[0] == D128              # 136 tiles
+        lib.set_option('gemm_dma64_max_tiles', 272)
+        assert path(B=17, T=128, N=1024)[0] == D64
+        lib.set_option('gemm_dma64_max_tiles', 256)
+        lib.set_option('gemm_dma64', 0)
+        assert path(B=16, T=128, N=1024)[0] == D128 and path(B=1, T=129, N=1024, k=3)[0] == D128
+        lib.set_option('gemm_dma64', 1)
+        # a colsum launch whose samples do not fit 64-row tiles is never DMA64
+        cs = dict(colsum=6 * PTR, colsum_ld=1024, gather=1, pad_left=0, pad_mode=lib.ZS_PAD_ZERO)
+        assert path(B=4, T=128, N=256, **cs)[0] == D128 and path(B=8, T=64, N=256, **cs)[0] == D64
+        assert path(B=32, T=16, N=256, **cs)[0] == D64
+        lib.set_option('gemm_ring', 1)
+        lib.set_option('gemm_dma', 0)                            # the register-staged kernel, whatever the other knobs say
+        for kw in (dict(N=1024), dict(N=513), dict(N=128, Cin=513, k=7), dict(B=1, T=129, N=1024, k=3)):
+            assert path(**kw) == (REG, 0)
+            assert path(dtype=lib.ZS_F32, **kw) == (REG, 0)
+        lib.set_option('gemm_dma', 1)
+        lib.set_option('gemm_p8', 1)
+        assert path(N=1024) == (P8, 1)
+    finally:
+        for k, v in old.items():
+            lib.set_option(k, v)
+
+    def bad(**kw):
+        a = dict(dtype=lib.ZS_BF16, A=PTR, lda=64, a_batch_stride=64 * 16, B=2, T_in=16, T_out=16, taps=1, stride=1, cin_pad=64,
+                 W=2 * PTR, ldw=64, N=64, n_pad=128, out=3 * PTR, ldc=64, out_cols=64)
+        a.update(kw)
+        s = lib.STRUCTS['ZsGemmConv'](**a)
+        rc = q(ctypes.addressof(s))
+        return rc < 0 and 'zs_gemm_conv' in lib.last_error()
+
+    assert not bad()
+    assert q(None) < 0 and 'zs_gemm_conv' in lib.last_error()
+    assert bad(A=0) and bad(W=0) and bad(out=0) and bad(dtype=7) and bad(cin_pad=48) and bad(ldw=32) and bad(n_pad=64)
+    assert bad(n_pad=192) and bad(A=PTR + 2) and bad(B=0) and bad(N=0)
+    assert bad(N=63, store_mode=lib.ZS_STORE_SPLIT2) and bad(pre_vec=4 * PTR) and bad(colsum=4 * PTR, T_out=24, T_in=24)
+    assert bad(lengths=4 * PTR, gather=1)
+    # reflect padding as long as the sample is refused with torch's message; one row shorter is accepted
+    assert bad(taps=7, pad_left=3, pad_mode=lib.ZS_PAD_REFLECT, T_in=3, T_out=3, ldw=7 * 64)
+    assert 'Padding size should be less than the corresponding input dimension' in lib.last_error()
+    assert not bad(taps=7, pad_left=3, pad_mode=lib.ZS_PAD_REFLECT, T_in=4, T_out=4, ldw=7 * 64)
+
+
 def test_no_cpu_fallback():
     import zs_amd  # noqa: F401
     from zs_amd import _lib

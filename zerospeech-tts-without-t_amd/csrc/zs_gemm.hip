@@ -905,10 +905,10 @@ template <> struct Mma16<float> {
   ZS_M16_MMA(fa31, b1, cq[3][0]); ZS_M16_MMA(fa31, b3, cq[3][1]);                \
   __builtin_amdgcn_s_setprio(0);
 
-__device__ __forceinline__ bool al16(const void* q, int64_t pitch_bytes) { return ((((uintptr_t)q) | (uintptr_t)pitch_bytes) & 15) == 0; }
+__host__ __device__ __forceinline__ bool al16(const void* q, int64_t pitch_bytes) { return ((((uintptr_t)q) | (uintptr_t)pitch_bytes) & 15) == 0; }
 
 // which problems the register epilogue of the 256x256 kernel takes (wave-uniform: depends on the launch parameters only)
-__device__ __forceinline__ bool p8_regs_epilogue_ok(const ZsGemmConv& p) {
+__host__ __device__ __forceinline__ bool p8_regs_epilogue_ok(const ZsGemmConv& p) {
   const int half = p.N >> 1;
   const bool split = (p.out && p.store_mode == ZS_STORE_SPLIT2) || (p.out2 && p.store_mode2 == ZS_STORE_SPLIT2);
   return (p.out == nullptr || (!p.out_f32 && al16(p.out, p.ldc * 2) && ((p.out_gstride * 2) & 15) == 0 && (p.out_cols & 7) == 0)) &&
@@ -2271,12 +2271,15 @@ void set_lds_attrs() {
   for (const void* f : ring) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS);
 }
 
-}  // namespace
-
-// ------------------------------------------------------------------------------------------------
-// host entry points
-// ------------------------------------------------------------------------------------------------
-extern "C" int zs_gemm_conv(const ZsGemmConv* p, void* stream) {
+// The launch plan of zs_gemm_conv: the argument checks and the dispatch rule, host arithmetic on the struct and the knobs only
+// (no operand is dereferenced, no GPU call).  zs_gemm_conv launches what it returns; zs_gemm_conv_path reports it.
+struct ConvPlan {
+  int path;        // ZS_GEMM_PATH_*
+  int regs;        // P8, bf16: the launch takes p8_regs_epilogue
+  int64_t wgs;     // grid.x: tiles of the chosen kernel
+  int groups;      // grid.z
+};
+int gemm_conv_plan(const ZsGemmConv* p, ConvPlan& pl) {
   ZS_REQUIRE(p && p->A && p->W && (p->out || p->out2), "zs_gemm_conv: null operand");
   ZS_REQUIRE(p->dtype == ZS_F32 || p->dtype == ZS_BF16, "zs_gemm_conv: bad dtype %d", p->dtype);
   const int es = p->dtype == ZS_F32 ? 4 : 2;
@@ -2315,48 +2318,82 @@ extern "C" int zs_gemm_conv(const ZsGemmConv* p, void* stream) {
              "zs_gemm_conv: colsum needs T_out (%d) to divide 128, 0 <= colsum_col0 < N and no bias / pre_vec / activation / groups", p->T_out);
   ZS_REQUIRE(!p->lengths || (p->gather == 0 && p->B < 65536 && p->T_in < 32768 && p->pad_right >= 0 && p->colsum == nullptr),
              "zs_gemm_conv: lengths (ragged batch) needs gather 0, B < 65536, T_in < 32768, pad_right >= 0 and no colsum");
-  const int groups = p->groups > 0 ? p->groups : 1;
+  pl.groups = p->groups > 0 ? p->groups : 1;
+  pl.regs = 0;
   const int64_t M = (int64_t)p->B * p->T_out;
-  const int64_t tiles = ((M + BM - 1) / BM) * ((p->N + BN - 1) / BN);
+  const int64_t ntn = (p->N + BN - 1) / BN;
+  const int64_t tiles = ((M + BM - 1) / BM) * ntn;
   ZS_REQUIRE(tiles < (1ll << 31), "zs_gemm_conv: grid too large");
-  dim3 grid((unsigned)tiles, 1, (unsigned)groups);
-  hipStream_t s = (hipStream_t)stream;
-  std::call_once(g_lds_attr_once, set_lds_attrs);
   const int use_dma = g_use_dma.get(), use_ring = g_use_ring.get(), use_p8 = g_use_p8.get(), use_pp = g_use_pp.get();
-  const int64_t ring_tiles = ((M + RBM - 1) / RBM) * ((p->N + BN - 1) / BN);
+  const int64_t ring_tiles = ((M + RBM - 1) / RBM) * ntn;
   const int64_t p8_tiles = ((M + PBM - 1) / PBM) * ((p->N + PBN - 1) / PBN);
+  const int64_t tiles64 = ((M + 63) / 64) * ntn;
   if (use_dma && use_p8 && p->n_pad % PBN == 0 && p8_tiles >= g_p8_min_tiles.get() && p8_tiles < (1ll << 31)) {
     // enough 256x256 tiles for most of the chip: quadrant ping-pong kernel
-    dim3 pgrid((unsigned)p8_tiles, 1, (unsigned)groups);
-    if (p->dtype == ZS_F32) hipLaunchKernelGGL(gemm_conv_p8m16_kernel<float>, pgrid, dim3(PNT), P8_LDS, s, *p);
-    else hipLaunchKernelGGL(gemm_conv_p8m16_kernel<bf16_t>, pgrid, dim3(PNT), P8_LDS, s, *p);
+    pl.path = ZS_GEMM_PATH_P8; pl.wgs = p8_tiles;
+    pl.regs = p->dtype == ZS_BF16 && p8_regs_epilogue_ok(*p);
   } else if (use_dma && use_ring && ring_tiles >= g_ring_min_tiles.get() && ring_tiles < (1ll << 31)) {
     // enough 256x128 tiles to give every CU one workgroup: 3-stage ring kernel
-    dim3 rgrid((unsigned)ring_tiles, 1, (unsigned)groups);
-    if (use_pp) {
-      if (p->dtype == ZS_F32) hipLaunchKernelGGL((gemm_conv_ring_kernel<float, 1>), rgrid, dim3(RNT), RING_LDS, s, *p);
-      else hipLaunchKernelGGL((gemm_conv_ring_kernel<bf16_t, 1>), rgrid, dim3(RNT), RING_LDS, s, *p);
-    } else {
-      if (p->dtype == ZS_F32) hipLaunchKernelGGL((gemm_conv_ring_kernel<float, 0>), rgrid, dim3(RNT), RING_LDS, s, *p);
-      else hipLaunchKernelGGL((gemm_conv_ring_kernel<bf16_t, 0>), rgrid, dim3(RNT), RING_LDS, s, *p);
-    }
-  } else if (use_dma) {
+    pl.path = use_pp ? ZS_GEMM_PATH_RING_PP : ZS_GEMM_PATH_RING; pl.wgs = ring_tiles;
+  } else if (use_dma && g_dma64.get() && tiles * 2 <= g_dma64_max_tiles.get() && tiles64 < (1ll << 31) &&
+             (p->colsum == nullptr || 64 % p->T_out == 0)) {
     // 64-row tiles where the 128-row grid would leave half the chip without a workgroup
-    const int64_t tiles64 = ((M + 63) / 64) * ((p->N + BN - 1) / BN);
-    if (g_dma64.get() && tiles * 2 <= g_dma64_max_tiles.get() && tiles64 < (1ll << 31) && (p->colsum == nullptr || 64 % p->T_out == 0)) {
-      dim3 g64((unsigned)tiles64, 1, (unsigned)groups);
-      const size_t lds = (2 * 64 * 128 + 2 * DTILE > EPI_LDS_BYTES / 2) ? 2 * 64 * 128 + 2 * DTILE : EPI_LDS_BYTES / 2;
-      if (p->dtype == ZS_F32) hipLaunchKernelGGL((gemm_conv_dma_kernel<float, 64>), g64, dim3(NT), lds, s, *p);
-      else hipLaunchKernelGGL((gemm_conv_dma_kernel<bf16_t, 64>), g64, dim3(NT), lds, s, *p);
-      return zs_check_launch("zs_gemm_conv");
-    }
-    const size_t lds = (4 * DTILE > EPI_LDS_BYTES) ? 4 * DTILE : EPI_LDS_BYTES;
-    if (p->dtype == ZS_F32) hipLaunchKernelGGL((gemm_conv_dma_kernel<float, 128>), grid, dim3(NT), lds, s, *p);
-    else hipLaunchKernelGGL((gemm_conv_dma_kernel<bf16_t, 128>), grid, dim3(NT), lds, s, *p);
+    pl.path = ZS_GEMM_PATH_DMA64; pl.wgs = tiles64;
   } else {
-    const size_t lds = 4 * TILE_BYTES;
-    if (p->dtype == ZS_F32) hipLaunchKernelGGL(gemm_conv_kernel<float>, grid, dim3(NT), lds, s, *p);
-    else hipLaunchKernelGGL(gemm_conv_kernel<bf16_t>, grid, dim3(NT), lds, s, *p);
+    pl.path = use_dma ? ZS_GEMM_PATH_DMA128 : ZS_GEMM_PATH_REG; pl.wgs = tiles;
+  }
+  return ZS_OK;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// host entry points
+// ------------------------------------------------------------------------------------------------
+extern "C" int zs_gemm_conv_path(const ZsGemmConv* p) {
+  ConvPlan pl;
+  const int rc = gemm_conv_plan(p, pl);
+  return rc != ZS_OK ? rc : (pl.path | pl.regs << 8);
+}
+
+extern "C" int zs_gemm_conv(const ZsGemmConv* p, void* stream) {
+  ConvPlan pl;
+  const int rc = gemm_conv_plan(p, pl);
+  if (rc != ZS_OK) return rc;
+  const dim3 grid((unsigned)pl.wgs, 1, (unsigned)pl.groups);
+  const bool f32 = p->dtype == ZS_F32;
+  hipStream_t s = (hipStream_t)stream;
+  std::call_once(g_lds_attr_once, set_lds_attrs);
+  switch (pl.path) {
+    case ZS_GEMM_PATH_P8:
+      if (f32) hipLaunchKernelGGL(gemm_conv_p8m16_kernel<float>, grid, dim3(PNT), P8_LDS, s, *p);
+      else hipLaunchKernelGGL(gemm_conv_p8m16_kernel<bf16_t>, grid, dim3(PNT), P8_LDS, s, *p);
+      break;
+    case ZS_GEMM_PATH_RING_PP:
+      if (f32) hipLaunchKernelGGL((gemm_conv_ring_kernel<float, 1>), grid, dim3(RNT), RING_LDS, s, *p);
+      else hipLaunchKernelGGL((gemm_conv_ring_kernel<bf16_t, 1>), grid, dim3(RNT), RING_LDS, s, *p);
+      break;
+    case ZS_GEMM_PATH_RING:
+      if (f32) hipLaunchKernelGGL((gemm_conv_ring_kernel<float, 0>), grid, dim3(RNT), RING_LDS, s, *p);
+      else hipLaunchKernelGGL((gemm_conv_ring_kernel<bf16_t, 0>), grid, dim3(RNT), RING_LDS, s, *p);
+      break;
+    case ZS_GEMM_PATH_DMA64: {
+      const size_t lds = (2 * 64 * 128 + 2 * DTILE > EPI_LDS_BYTES / 2) ? 2 * 64 * 128 + 2 * DTILE : EPI_LDS_BYTES / 2;
+      if (f32) hipLaunchKernelGGL((gemm_conv_dma_kernel<float, 64>), grid, dim3(NT), lds, s, *p);
+      else hipLaunchKernelGGL((gemm_conv_dma_kernel<bf16_t, 64>), grid, dim3(NT), lds, s, *p);
+      break;
+    }
+    case ZS_GEMM_PATH_DMA128: {
+      const size_t lds = (4 * DTILE > EPI_LDS_BYTES) ? 4 * DTILE : EPI_LDS_BYTES;
+      if (f32) hipLaunchKernelGGL((gemm_conv_dma_kernel<float, 128>), grid, dim3(NT), lds, s, *p);
+      else hipLaunchKernelGGL((gemm_conv_dma_kernel<bf16_t, 128>), grid, dim3(NT), lds, s, *p);
+      break;
+    }
+    default: {
+      const size_t lds = 4 * TILE_BYTES;
+      if (f32) hipLaunchKernelGGL(gemm_conv_kernel<float>, grid, dim3(NT), lds, s, *p);
+      else hipLaunchKernelGGL(gemm_conv_kernel<bf16_t>, grid, dim3(NT), lds, s, *p);
+    }
   }
   return zs_check_launch("zs_gemm_conv");
 }
