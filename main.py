@@ -17,6 +17,10 @@ Vocoder of --test, --cross_test and --test_single: --gl_iters N sets the Griffin
 Every --train* mode takes --device_data: the training set is uploaded into GPU memory once and each batch is gathered there
 (zs_amd.pool), in the host DataLoader's order; ZS_POOL_MAX_GB caps the pool's size.
 
+--resume with exactly one of --train_ae, --train_p, --train_tgat, --train_c (with or without --device_data): every checkpoint gets
+a train-state file (<ckpt_dir>/train_state/, zs_amd.resume) and the run continues bit for bit from the newest one in --ckpt_dir,
+or from iteration 0 when there is none: the same command starts a run and restarts it after an interruption.
+
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
 (--train_al, --train_t, --encode, --test_asr) are not part of this build and exit with a clear error.
@@ -56,6 +60,9 @@ def build_parser():
     p.add_argument('--device_data', default=False, action='store_true',
                    help='every --train* mode: hold the training set in GPU memory and gather each batch on the device '
                         '(zs_amd.pool; size limit ZS_POOL_MAX_GB); default: the host DataLoader')
+    p.add_argument('--resume', default=False, action='store_true',
+                   help='with one of --train_ae / --train_p / --train_tgat / --train_c: write a train-state file beside every '
+                        'checkpoint and continue from the newest one in --ckpt_dir (from iteration 0 when there is none)')
     p.add_argument('--flag', type=str, default='train')
     p.add_argument('--g_mode', default='set_from_hps',
                    choices=['naive', 'targeted', 'targeted_residual', 'enhanced', 'spectrogram', 'tacotron', 'set_from_hps'])
@@ -89,10 +96,30 @@ def build_parser():
     return p
 
 
+RESUMABLE = ['train_ae', 'train_p', 'train_tgat', 'train_c']
+
+
+def check_resume(args):
+    """--resume continues ONE stage from its own newest checkpoint: refuse, before anything is built, the chained --train, more
+    than one stage flag, and --load_model (the weights come from the checkpoint that is resumed)."""
+    if not args.resume:
+        return
+    if args.train:
+        raise ValueError('--resume continues one stage: use it with --train_ae, --train_p, --train_tgat or --train_c, not with the '
+                         'chained --train')
+    stages = [f for f in RESUMABLE if getattr(args, f)]
+    if len(stages) != 1:
+        raise ValueError('--resume needs exactly one of %s (got %s)' % (', '.join('--' + f for f in RESUMABLE),
+                                                                        ', '.join('--' + f for f in stages) or 'none'))
+    if args.load_model:
+        raise ValueError('--resume loads the newest checkpoint of its stage itself: it cannot be combined with --load_model')
+
+
 def argument_runner(argv=None):
     from zs_amd.hps import Hps, hp
     parser = build_parser()
     args = parser.parse_args(argv)
+    check_resume(args)
     if args.dataset == 'surprise':            # main.py:83-88: english -> surprise in every default path
         for action in parser._actions:
             if isinstance(action.default, str) and 'english' in action.default and \
@@ -162,14 +189,14 @@ def main(argv=None):
         if args.load_model:
             trainer.load_model(os.path.join(args.ckpt_dir, args.load_train_model_name), load_model_list=hps.load_model_list)
         if args.train or args.train_ae:
-            trainer.train(model_path, args.flag, mode='pretrain_AE')                     # stage 1: encoder-decoder reconstruction
+            trainer.train(model_path, args.flag, mode='pretrain_AE', resume=args.resume)       # stage 1: reconstruction
             trainer.reset_keep()
         if args.train or args.train_p or args.train_tgat:
             trainer.add_duo_loader(source_loader, target_loader)
-            trainer.train(model_path, args.flag, mode='patchGAN', target_guided=args.train_tgat)     # stage 2
+            trainer.train(model_path, args.flag, mode='patchGAN', target_guided=args.train_tgat, resume=args.resume)
             trainer.reset_keep()
         if args.train_c:                                  # main.py:165-167 (--train keeps the stages above)
-            trainer.train(model_path, args.flag, mode='t_classify')                      # the target speaker classifier
+            trainer.train(model_path, args.flag, mode='t_classify', resume=args.resume)        # the target speaker classifier
             trainer.reset_keep()
         if args.train and parallel.rank() == 0:
             # reference main.py:163-173 goes on to the autolocker, t_classify and Tacotron stages: outside the path this build covers

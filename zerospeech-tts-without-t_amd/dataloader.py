@@ -35,6 +35,19 @@ class DataLoader(object):
             self.index += step
         return tuple(batch_tensor)
 
+    def skip(self, k):
+        """Advance `index` as k calls of next() would (wrap rule, rank / world included) without fetching an item: the position
+        of a resumed run.  From index 0 the positions repeat with period P = max(1, ceil(n / step) - 1) (pool.batch_items)."""
+        k = int(k)
+        if k < 0:
+            raise ValueError('skip: the number of batches must be >= 0')
+        n, step = len(self.dataset), self.world * self.batch_size
+        while k > 0 and self.index != 0:                               # at most n / step times: the index then wraps to 0
+            self.index = 0 if self.index + 2 * step >= n else self.index + step
+            k -= 1
+        if k:
+            self.index = (k % max(1, -(-n // step) - 1)) * step
+
     def all(self, size=1000):
         return self._fetch(size)
 

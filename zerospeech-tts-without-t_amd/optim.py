@@ -21,6 +21,21 @@ class NetOpt(object):
         self.part = torch.zeros(1024, dtype=torch.float64, device=flat.device)
         self.reducer = parallel.GradReducer() if reduce else None
 
+    def state_dict(self):
+        """{'m', 'v': the moment buffers themselves (device), 't': the host step count}."""
+        return {'m': self.m, 'v': self.v, 't': int(self.t)}
+
+    def load_state_dict(self, sd):
+        """Restore m, v and t in place (the buffers keep their addresses: a captured step goes on reading them) and mark the
+        net's packed weights stale: the caller has just loaded its master weights."""
+        for k in ('m', 'v'):
+            if tuple(sd[k].shape) != tuple(self.m.shape):
+                raise ValueError('optimizer state: %s has %d elements, the net has %d' % (k, sd[k].numel(), self.m.numel()))
+        self.m.copy_(sd['m'])
+        self.v.copy_(sd['v'])
+        self.t = int(sd['t'])
+        self.net.mark_dirty()
+
     def sqnorm(self):
         """The squared norm of the net's gradient into self.sq, on the current stream.  Returns self.sq."""
         _, gflat = self.net.flat_params()

@@ -41,6 +41,16 @@ class PatchGANStep(object):
         self._l1part = torch.zeros(1024, dtype=torch.float32, device=dev)
         self.step_no = 0
 
+    def state_dict(self):
+        """The training state beside the weights: the two optimizers (an AutolockerStep built from a PatchGANStep shares them:
+        one step object, one state) and step_no, the counter the encoder's seeds derive from."""
+        return {'gen': self.gen_opt.state_dict(), 'patch': self.patch_opt.state_dict(), 'step_no': int(self.step_no)}
+
+    def load_state_dict(self, sd):
+        self.gen_opt.load_state_dict(sd['gen'])
+        self.patch_opt.load_state_dict(sd['patch'])
+        self.step_no = int(sd['step_no'])
+
     def check_targets(self, c_host):
         """c_host: speaker indices of a target batch, still on the HOST.  Raises like the reference's Generator embedding would
         for a speaker outside the target range (an index outside the table would read past it on the GPU)."""

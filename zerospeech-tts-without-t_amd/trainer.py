@@ -19,6 +19,7 @@ import torch
 from . import _lib as L
 from . import parallel
 from . import layers
+from . import resume as train_state                # (Trainer.train has a parameter called resume)
 from .layers import Act, join_side
 from .model import Decoder, Encoder, SpeakerClassifier, Spectrogram_Patcher
 from .patch import PatchDiscriminator, TargetClassifier
@@ -60,6 +61,28 @@ class AEStep(object):
         self._statics = {}           # (B, T, F) -> (x, c) handed out by static_inputs()
         self._eager_calls = 0
         self.graph_warmup = 2        # eager steps (same launches) before the capture
+
+    # ---- training state beside the weights --------------------------------------------------------------------------
+    def state_dict(self):
+        """Adam moments and counts of both nets, adam_step, the device words of the captured step, and which path ran: the
+        captured step draws its dropout / Gumbel seeds from _seed_dev, the eager one from adam_step."""
+        return {'enc': self.opt['enc'].state_dict(), 'dec': self.opt['dec'].state_dict(), 'adam_step': int(self.adam_step),
+                'seed_dev': self._seed_dev, 'step_dev': self._step_dev, 'use_graph': bool(self.use_graph)}
+
+    def load_state_dict(self, sd):
+        """Restore state_dict() in place, after the weights were loaded.  Raises ValueError, before anything is changed, for a
+        state saved on the other execution path."""
+        if bool(sd['use_graph']) != bool(self.use_graph):
+            raise ValueError('train state: use_graph is %r in the file, %r in this run (the captured and the eager step draw '
+                             'different random streams)' % (bool(sd['use_graph']), bool(self.use_graph)))
+        self.opt['enc'].load_state_dict(sd['enc'])
+        self.opt['dec'].load_state_dict(sd['dec'])
+        self.adam_step = int(sd['adam_step'])
+        self._seed_dev.copy_(sd['seed_dev'].view(-1))
+        self._step_dev.fill_(self.adam_step)
+        if self._eager_calls:                                # a captured step never looks at the version: re-pack now
+            self.Encoder.repack()
+            self.Decoder.repack()
 
     # ---- the step as a plan ----------------------------------------------------------------------------------------
     def l1_loss(self, de, x_btf, xdec):
@@ -434,6 +457,13 @@ class ClfStep(object):
 
     adam_step = property(lambda self: self.opt.t)
 
+    def state_dict(self):
+        """The classifier's optimizer (its count t seeds d_step); the autoencoder's state is the AEStep's own."""
+        return {'clf': self.opt.state_dict()}
+
+    def load_state_dict(self, sd):
+        self.opt.load_state_dict(sd['clf'])
+
     def _classify(self, logits_act, c, grad_scale, seed, drop_masks=None):
         """enc logits Act fp32 [B,T',n_lin] (the encoder's pre-activation: 2E, E or E^2 columns by enc_mode) -> (classifier engine,
         grad_scale * dCE/dlogits fp32 [B, n_class]); the CE loss and #correct in self.loss / self.correct."""
@@ -523,6 +553,12 @@ class TclfStep(object):
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
         self.correct = torch.zeros(1, dtype=torch.int32, device=dev)
 
+    def state_dict(self):
+        return {'clf': self.opt.state_dict()}
+
+    def load_state_dict(self, sd):
+        self.opt.load_state_dict(sd['clf'])
+
     def step(self, x_btf, c, masks=None, update=True):
         """x_btf fp32 [B, T, 513], c int64 [B] raw speaker ids on the device.  masks: optional six [B, C] Dropout2d keep masks.
         Returns (loss, n_correct) device scalars; parameter gradients are left in the classifier's flat gradient buffer."""
@@ -538,6 +574,21 @@ class TclfStep(object):
         if update:
             self.opt.step()
         return self.loss, self.correct
+
+
+class _Slot(int):
+    """Placeholder of a device tensor in the skeleton of a state tree: the index of its snapshot buffer."""
+
+
+def _fill_slots(skel, pin):
+    """The state tree of a snapshot: every _Slot of `skel` replaced by a pageable copy of its pinned buffer."""
+    if isinstance(skel, _Slot):
+        return pin[skel].clone()
+    if isinstance(skel, dict):
+        return {k: _fill_slots(v, pin) for k, v in skel.items()}
+    if isinstance(skel, list):
+        return [_fill_slots(v, pin) for v in skel]
+    return skel
 
 
 class Trainer(object):
@@ -558,6 +609,9 @@ class Trainer(object):
         self.device = torch.device(device)
         self.log_every = int(os.environ.get('ZS_LOG_EVERY', '1'))
         self.ckpt_every = int(os.environ.get('ZS_CKPT_EVERY', '1000'))     # the reference saves every 1000 iterations (trainer.py:345)
+        self._consumed = {'data': 0, 'source': 0, 'target': 0}             # batches the steps have taken from each loader (resume)
+        self._writer = None                                                # train_state.Writer of the resumable checkpoints
+        self._snap = None                                                  # their device snapshot + pinned host buffers
         self.build_model()
 
     # ---- model (trainer.py:48-98) -------------------------------------------------------------
@@ -644,10 +698,153 @@ class Trainer(object):
         all_model = {k: {n: t.detach().cpu().clone() for n, t in sd.items()} for k, sd in all_model.items()}
         new_model_path = '{}-{}-{}'.format(model_path, name, iteration)
         torch.save(all_model, new_model_path)
-        self.model_kept.append(new_model_path)
-        if len(self.model_kept) >= self.max_keep:
-            os.remove(self.model_kept[0])
-            self.model_kept.pop(0)
+        for old in train_state.roll_window(self.model_kept, new_model_path, self.max_keep):
+            train_state.remove_checkpoint(old)                                 # its train-state file, if it has one, goes with it
+
+    # ---- train state beside the checkpoint (no counterpart in the reference; see resume.py) --------
+    def _steps(self, tag=None):
+        """The step objects whose state a checkpoint of mode tag `tag` carries (None: every one that is built)."""
+        have = {'ae': self.ae, 'clf': self.clf, 's2': self.s2, 'tclf': self.tclf}
+        names = {'ae': ('ae',), 'c': ('clf',), 's1': ('ae', 'clf'), 's2': ('s2',), 'tclf': ('tclf',)}.get(tag, tuple(have))
+        return {n: have[n] for n in names if have[n] is not None}
+
+    def _state_tree(self, tag, iteration, target_guided, autolocker):
+        """The state file's dict as it stands now, its tensors still where they live (the steps' own device buffers)."""
+        st = train_state.describe(self, tag, target_guided, autolocker)
+        st.update(iteration=int(iteration), steps={n: s.state_dict() for n, s in self._steps(tag).items()},
+                  consumed=dict(self._consumed), model_kept=[os.path.basename(p) for p in self.model_kept],
+                  rng={'cpu': torch.get_rng_state(), 'cuda': torch.cuda.get_rng_state(self.device)})
+        return st
+
+    def save_state(self, path, tag=None, iteration=0, target_guided=False, autolocker=None):
+        """Write the train state (resume.py: everything but the weights) to `path`, synchronously.  tag: the mode tag it is
+        recorded under ('ae' / 'c' / 's1' / 's2' / 'tclf'; None: '' and the state of every step object that is built)."""
+        autolocker = isinstance(self.s2, AutolockerStep) if autolocker is None else autolocker
+        tree = self._state_tree(tag, iteration, target_guided, autolocker)
+        tree['tag'] = tag or ''
+        train_state.atomic_save(train_state.map_tensors(tree, lambda t: t.detach().cpu().clone()), path)
+
+    def load_state(self, path, tag=None, target_guided=None, autolocker=None, ckpt_dir=None, state=None):
+        """Restore what save_state wrote, after the weights were loaded: optimizer moments and counts, step counters, loader
+        positions, torch's RNG states and the rolling window.  tag / target_guided / autolocker: what the file must have been
+        written for (None: whatever it says).  Every recorded field is compared with this run first: ValueError naming the
+        field, before any launch.  ckpt_dir: where the window's checkpoints (recorded by file name) lie; default: the
+        directory above the state file's.  state: the file's dict, already loaded and validated (train(resume=True) reads it once).
+        Returns the file's dict."""
+        if state is not None:
+            return self._restore_state(state, ckpt_dir or os.path.dirname(os.path.dirname(os.path.abspath(path))))
+        st = torch.load(path, map_location='cpu', weights_only=True)
+        pick = lambda given, key: st.get(key) if given is None else given
+        train_state.validate(st, train_state.describe(self, pick(tag, 'tag'), pick(target_guided, 'target_guided'),
+                                                      pick(autolocker, 'autolocker')))
+        return self._restore_state(st, ckpt_dir or os.path.dirname(os.path.dirname(os.path.abspath(path))))
+
+    def _seek(self, counts):
+        """Put every loader at the position after counts[name] batches and drop the prefetchers, which run ahead of the steps:
+        they are rebuilt at the new position."""
+        self._consumed = {k: int(counts[k]) for k in ('data', 'source', 'target')}
+        for loader, k in ((self.data_loader, 'data'), (self.source_loader, 'source'), (self.target_loader, 'target')):
+            if loader is None:
+                continue
+            if hasattr(loader, 'set_cursor'):                             # pool.PoolLoader: the batch number lives on the device
+                loader.set_cursor(self._consumed[k])
+            else:
+                loader.index = 0
+                loader.skip(self._consumed[k])
+        self._prefetch = self._duo = self._tclf_prefetch = None
+
+    def _restore_state(self, st, ckpt_dir):
+        if 's2' in st['steps']:
+            self.stage2(autolocker=bool(st['autolocker']))
+        if 'tclf' in st['steps']:
+            self.tclf_step()
+        steps = self._steps()
+        for name, sd in st['steps'].items():
+            steps[name].load_state_dict(sd)
+        self._seek(st['consumed'])
+        if parallel.rank() == 0:                                          # the generator state is rank 0's; other ranks keep their own
+            torch.set_rng_state(st['rng']['cpu'])
+            torch.cuda.set_rng_state(st['rng']['cuda'], self.device)
+        self.model_kept = [os.path.join(ckpt_dir, name) for name in st['model_kept']]
+        return st
+
+    def _load_all_nets(self, ckpt_path):
+        """All six nets from a checkpoint of this build's own loop, strictly (load_model prints and goes on)."""
+        all_model = torch.load(ckpt_path, map_location='cpu', weights_only=True)
+        for key, net in zip(train_state.NET_NAMES, self.nets()):
+            net.load_state_dict({(k[7:] if k.startswith('module.') else k): v for k, v in all_model[key].items()})
+        self.sync_params()
+
+    def _reserve(self, srcs):
+        """(device snapshot buffers, pinned host buffers) for the tensors `srcs`, allocated when their shapes first appear."""
+        sig = [(tuple(s.shape), s.dtype) for s in srcs]
+        if self._snap is None or self._snap['sig'] != sig:
+            self._snap = {'sig': sig, 'dev': [torch.empty_like(s) for s in srcs],
+                          'pin': [torch.empty(s.shape, dtype=s.dtype, pin_memory=True) for s in srcs]}
+        return self._snap['dev'], self._snap['pin']
+
+    def _snapshot(self, srcs):
+        """Stream-ordered copies of the device tensors `srcs` into the reserved snapshot buffers (current stream: the next step's
+        Adam is ordered behind them) and from there to pinned host memory on the copy stream.  Returns (pinned tensors, the event
+        recorded after the last copy).  The buffers are allocated once; the caller keeps one snapshot in flight at most."""
+        dev, pin = self._reserve(srcs)
+        main, cs = torch.cuda.current_stream(self.device), layers.copy_stream(self.device)
+        for d, s in zip(dev, srcs):
+            d.copy_(s, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(main)
+        cs.wait_event(ev)
+        done = torch.cuda.Event()
+        with torch.cuda.stream(cs):
+            for p, d in zip(pin, dev):
+                p.copy_(d, non_blocking=True)
+            done.record(cs)
+        return pin, done
+
+    def _checkpoint_async(self, model_path, name, iteration, target_guided, autolocker):
+        """A resumable checkpoint off the training thread's critical path: enqueue the snapshot (_snapshot) of the six flat
+        parameter buffers and of every tensor of the state tree, then hand a worker thread the job of waiting for the event,
+        building the checkpoint dict (save_model's) and the state dict from the pinned memory and writing both."""
+        if self._writer is None:
+            self._writer = train_state.Writer()
+        self._writer.wait()                                               # one checkpoint in flight; its failure raises here
+        new_path = '{}-{}-{}'.format(model_path, name, iteration)
+        drop = train_state.roll_window(self.model_kept, new_path, self.max_keep)
+        srcs, layout, skel = self._ckpt_sources(self._state_tree(name, iteration, target_guided, autolocker))
+        pin, done = self._snapshot(srcs)
+
+        def job():
+            done.synchronize()                                            # the worker's only GPU call
+            ckpt = {key: {pre + k: pin[s][o:o + n].view(shape).clone() for k, s, o, n, shape in ents} for key, pre, ents in layout}
+            train_state.atomic_save(ckpt, new_path)
+            train_state.atomic_save(_fill_slots(skel, pin), train_state.state_path(new_path))
+            for old in drop:
+                train_state.remove_checkpoint(old)
+        self._writer.submit(job)
+
+    def _ckpt_sources(self, tree):
+        """What a resumable checkpoint copies: (srcs, layout, skel).  srcs: the device tensors (flat parameter buffers, moments, words);
+        layout: per net (checkpoint key, key prefix, [(parameter name, index into srcs, offset, numel, shape)]), in
+        state_dict order; skel: the state tree with every device tensor replaced by its index into srcs (_Slot)."""
+        srcs, layout = [], []
+        for key, net in zip(train_state.NET_NAMES, self.nets()):
+            flat, offs = net.flat_params()[0], net._zs['offsets']
+            slot, ents = len(srcs), []
+            srcs.append(flat)
+            for k, v in net.state_dict().items():
+                if k in offs:
+                    ents.append((k, slot, offs[k], v.numel(), tuple(v.shape)))
+                else:                                                     # a buffer outside the flat storage
+                    ents.append((k, len(srcs), 0, v.numel(), tuple(v.shape)))
+                    srcs.append(v.detach().reshape(-1))
+            layout.append((key, 'module.' if key in ('patch_discriminator', 'target_classifier') else '', ents))
+
+        def grab(t):
+            if t.device.type == 'cpu':
+                return t.clone()
+            srcs.append(t.detach())
+            return _Slot(len(srcs) - 1)
+        return srcs, layout, train_state.map_tensors(tree, grab)
 
     def load_model(self, model_path, load_model_list, verbose=True, clf_path=None):
         if verbose:
@@ -761,10 +958,18 @@ class Trainer(object):
         from .dataloader import DevicePrefetcher
         return DevicePrefetcher(loader, self.device, n_speakers=n_speakers, check=check)       # next batch copied under the current step
 
+    def _took(self, *loaders):
+        """Count one batch handed to a step from each named loader.  This, not the loaders' own index, is a run's position: the
+        prefetchers run one batch ahead of the steps and HostFedStep two."""
+        for name in loaders:
+            self._consumed[name] += 1
+
     def _batch(self):
         if self._prefetch is None:
             self._prefetch = self._device_batches(self.data_loader, n_speakers=self.hps.n_speakers)
-        return next(self._prefetch)
+        batch = next(self._prefetch)
+        self._took('data')
+        return batch
 
     def _duo_batch(self):
         """next(source_loader), next(target_loader) through the prefetcher (trainer.py:472-475)."""
@@ -773,7 +978,9 @@ class Trainer(object):
                 raise RuntimeError('patchGAN needs add_duo_loader(source_loader, target_loader)')
             self._duo = (self._device_batches(self.source_loader, n_speakers=self.hps.n_speakers),
                          self._device_batches(self.target_loader, n_speakers=self.hps.n_speakers, check=self.stage2().check_targets))
-        return next(self._duo[0]), next(self._duo[1])
+        pair = next(self._duo[0]), next(self._duo[1])
+        self._took('source', 'target')
+        return pair
 
     def tclf_labels(self, c_host):
         """t_classify targets of a HOST batch (tclf_labels above with this trainer's hps / g_mode); raises ValueError."""
@@ -790,7 +997,9 @@ class Trainer(object):
         (tclf_labels, raising ValueError) before it is copied; the relabel the step uses runs on the device (TclfStep.step)."""
         if getattr(self, '_tclf_prefetch', None) is None:
             self._tclf_prefetch = self._device_batches(self.data_loader, check=self.tclf_labels)
-        return next(self._tclf_prefetch)
+        batch = next(self._tclf_prefetch)
+        self._took('data')
+        return batch
 
     def _log(self, iteration, iters, fmt, info, head=()):
         """One logged record: every rank reads the GRU status word (the .item() reads that made `info` synchronised the host
@@ -802,22 +1011,79 @@ class Trainer(object):
                 for tag, value in info.items():
                     self.logger.scalar_summary(tag, value, iteration + 1)
 
-    def _loop(self, iters, model_path, ckpt_name, iteration_fn):
+    def _loop(self, iters, model_path, ckpt_name, iteration_fn, start=0, keep_state=None):
         """The loop of every mode: iteration_fn(iteration, log) runs one iteration, log = self._log bound to it at a logged
-        iteration (every log_every-th and the last) and None otherwise; rank 0 saves a checkpoint every ckpt_every iterations."""
+        iteration (every log_every-th and the last) and None otherwise; rank 0 saves a checkpoint every ckpt_every iterations.
+        start: the first iteration (a resumed run).  keep_state: None, or (target_guided, autolocker) of a resumable run: its
+        checkpoints carry a train-state file and are written by a worker thread (_checkpoint_async), which is waited for before
+        this returns and when an exception leaves the loop."""
         is_main = parallel.rank() == 0
-        for iteration in range(iters):
-            log_now = (iteration % self.log_every == 0) or (iteration + 1 == iters)
-            iteration_fn(iteration, functools.partial(self._log, iteration, iters) if log_now else None)
-            if (iteration + 1) % self.ckpt_every == 0 and is_main:
-                self.save_model(model_path, ckpt_name, iteration + 1)
+        if keep_state is not None and is_main and start < iters:
+            self._reserve(self._ckpt_sources(self._state_tree(ckpt_name, start, *keep_state))[0])     # snapshot + pinned buffers, once
+        try:
+            for iteration in range(start, iters):
+                log_now = (iteration % self.log_every == 0) or (iteration + 1 == iters)
+                iteration_fn(iteration, functools.partial(self._log, iteration, iters) if log_now else None)
+                if (iteration + 1) % self.ckpt_every == 0 and is_main:
+                    if keep_state is not None:
+                        self._checkpoint_async(model_path, ckpt_name, iteration + 1, *keep_state)
+                    else:
+                        self.save_model(model_path, ckpt_name, iteration + 1)
+                if keep_state is not None and self._writer is not None:
+                    self._writer.poll()                                                   # a failed write raises at once
+        except BaseException:
+            try:
+                self._finish_writer()
+            except Exception:                                                             # the loop's own exception is the one to report
+                pass
+            raise
+        self._finish_writer()                                                             # re-raises what the writer raised
         layers.check_status(self.device)                                                  # every rank, after the last step
         if is_main:
             print()
 
-    def train(self, model_path, flag='train', mode='train', target_guided=False):
+    def _finish_writer(self):
+        if self._writer is not None:
+            self._writer.wait()
+
+    def _resume_from(self, model_path, mode, target_guided, iters):
+        """Trainer.train(resume=True) before its loop: load the newest checkpoint of this mode's tag under model_path's directory
+        that has a train-state file (all six nets, then the state) and return its iteration; 0 when there is none; None when it
+        already is the final iteration.  Every rank reads the same files."""
+        tag, say = train_state.TAGS[mode], (print if parallel.rank() == 0 else (lambda *a: None))
+        found = train_state.find_resumable(model_path, tag)
+        if found is None:
+            say('[Trainer] - resume: no %s checkpoint with a train state beside %s, starting from iteration 0' % (tag, model_path))
+            self._seek({'data': 0, 'source': 0, 'target': 0})             # a run's position is counted from the loaders' start
+            return 0
+        ckpt, state, _ = found
+        # the file is validated against this run (ValueError) before a weight is touched or anything is launched
+        st = torch.load(state, map_location='cpu', weights_only=True)
+        train_state.validate(st, train_state.describe(self, tag, target_guided, mode == 'autolocker'))
+        self._load_all_nets(ckpt)
+        self.load_state(state, state=st)
+        it = int(st['iteration'])
+        if it >= iters:
+            say('[Trainer] - resume: %s is the final iteration (%d of %d), nothing left to train' % (ckpt, it, iters))
+            return None
+        say('[Trainer] - resume: %s, continuing at iteration %d of %d' % (ckpt, it, iters))
+        return it
+
+    def train(self, model_path, flag='train', mode='train', target_guided=False, resume=False):
+        """resume=True (not in the reference): every checkpoint gets a train-state file (resume.py) and the run continues from the
+        newest one under model_path's directory, bit for bit; without one it starts from iteration 0."""
         hps = self.hps
+        resumable = bool(resume)
+        keep_state = (bool(target_guided), mode == 'autolocker') if resumable else None
+
+        def begin(iters):
+            """The first iteration of the loop; None: the final checkpoint is already there."""
+            return self._resume_from(model_path, mode, target_guided, iters) if resumable else 0
+
         if mode == 'pretrain_AE':                                                         # trainer.py:320-347
+            start = begin(hps.enc_pretrain_iters)
+            if start is None:
+                return
             from .pool import PoolLoader
             if isinstance(self.data_loader, PoolLoader):
                 feeder = self.ae.pool_feeder(self.data_loader.require(n_speakers=hps.n_speakers))   # the gather at the head of the step
@@ -827,21 +1093,30 @@ class Trainer(object):
             def iteration_fn(iteration, log):
                 if feeder is not None:
                     loss_t = next(feeder)
+                    self._took('data')
                 else:
                     c, x = self._batch()
                     loss_t = self.ae_step(x, c)
                 if log:
                     log('pre_AE:[%06d/%06d], loss_rec=%.3f', {f'{flag}/pre_loss_rec': loss_t.item()})    # the only host sync
-            self._loop(hps.enc_pretrain_iters, model_path, 'ae', iteration_fn)
+            self._loop(hps.enc_pretrain_iters, model_path, 'ae', iteration_fn, start, keep_state)
         elif mode == 'pretrain_C':                                                        # trainer.py:349-382
+            start = begin(hps.dis_pretrain_iters)
+            if start is None:
+                return
+
             def iteration_fn(iteration, log):
                 c, x = self._batch()
                 loss_t, corr = self.clf.d_step(x, c)
                 if log:
                     log('pre_C:[%06d/%06d], loss_clf=%.2f, acc=%.2f',
                         {f'{flag}/pre_loss_clf': loss_t.item(), f'{flag}/pre_acc': corr.item() / float(c.shape[0])})
-            self._loop(hps.dis_pretrain_iters, model_path, 'c', iteration_fn)
+            self._loop(hps.dis_pretrain_iters, model_path, 'c', iteration_fn, start, keep_state)
         elif mode == 'train':                                                             # trainer.py:384-465
+            start = begin(hps.iters)
+            if start is None:
+                return
+
             def iteration_fn(iteration, log):
                 if iteration < hps.lat_sched_iters:
                     current_alpha = hps.alpha_enc * (iteration / hps.lat_sched_iters)
@@ -859,10 +1134,13 @@ class Trainer(object):
                     log('G:[%06d/%06d], loss_rec=%.3f, loss_clf=%.2f, alpha=%.2e, acc=%.2f',
                         {f'{flag}/loss_rec': l_rec.item(), f'{flag}/G_loss_clf': l_clf.item(), f'{flag}/alpha': current_alpha,
                          f'{flag}/G_acc': corr.item() / float(c.shape[0])})
-            self._loop(hps.iters, model_path, 's1', iteration_fn)
+            self._loop(hps.iters, model_path, 's1', iteration_fn, start, keep_state)
         elif mode == 'patchGAN':                                                          # trainer.py:467-560
             s2 = self.stage2()
             B = float(hps.batch_size)
+            start = begin(hps.patch_iters)
+            if start is None:
+                return
 
             def iteration_fn(iteration, log):
                 for step in range(hps.n_patch_steps):                                     # train D
@@ -879,23 +1157,29 @@ class Trainer(object):
                     log('patch_G:[%06d/%06d], loss_adv=%.2f, loss_clf=%.2f, acc=%.2f, tg_rec=%.3f',
                         {f'{flag}/loss_adv': r['loss_adv'].item(), f'{flag}/fake_loss_clf': r['fake_loss_clf'].item(),
                          f'{flag}/fake_acc': r['correct'].item() / B, f'{flag}/tg_rec': loss_rec.item() if target_guided else 0.000})
-            self._loop(hps.patch_iters, model_path, 's2', iteration_fn)
+            self._loop(hps.patch_iters, model_path, 's2', iteration_fn, start, keep_state)
         elif mode == 't_classify':                                                        # trainer.py:613-643
             if self.g_mode == 'naive':
                 self.tclf_labels(torch.zeros(0, dtype=torch.int64))                        # raises: no shift_c
+            start = begin(hps.tclf_iters)
+            if start is None:
+                return
             batch = [self._tclf_batch()]                                                  # the first batch is checked before any launch
             step = self.tclf_step()
 
             def iteration_fn(iteration, log):
-                if iteration:
+                if batch[0] is None:
                     batch[0] = self._tclf_batch()
-                c, x = batch[0]
+                (c, x), batch[0] = batch[0], None
                 _, corr = step.step(x, c)
                 if log:
                     log('Target Classifier:[%05d/%05d], acc=%.2f', {f'{flag}/acc': corr.item() / float(c.shape[0])})
-            self._loop(hps.tclf_iters, model_path, 'tclf', iteration_fn)
+            self._loop(hps.tclf_iters, model_path, 'tclf', iteration_fn, start, keep_state)
         elif mode == 'autolocker':                                                        # trainer.py:563-611
             s2 = self.stage2(autolocker=True)                                             # ValueError unless multilabel_binary
+            start = begin(hps.patch_iters)
+            if start is None:
+                return
 
             def iteration_fn(iteration, log):
                 (_, x_s), (c_t, x_t) = self._duo_batch()                                  # train G
@@ -904,6 +1188,6 @@ class Trainer(object):
                 if log:
                     log('patch_G:[%06d/%06d], re_enc=%.3f, tg_rec=%.3f',
                         {f'{flag}/re_enc': loss_reenc.item(), f'{flag}/tg_rec': loss_rec.item() if target_guided else 0.000})
-            self._loop(hps.patch_iters, model_path, 's2', iteration_fn)
+            self._loop(hps.patch_iters, model_path, 's2', iteration_fn, start, keep_state)
         else:
             raise NotImplementedError("mode %r (Tacotron) is outside the path this build covers" % mode)
