@@ -635,6 +635,36 @@ int zs_gl_deemphasis(float* wav, int64_t wav_ld, const int32_t* lengths, int32_t
  * top_db below the maximum and slices: only these few hundred values per utterance are examined on the host. */
 int zs_gl_frame_mse(const float* wav, int64_t wav_ld, const int32_t* lengths, int32_t n_utt, int32_t frame_length, int32_t hop,
                     double* mse, int64_t mse_ld, void* stream);
+/* zs_resample: band-limited sample-rate conversion of a ragged batch, the resampling inside librosa.load(sound_file, sr=hp.sr)
+ * (preprocess.py:227-258, convert.py:377,431; librosa <= 0.7: resampy 'kaiser_best', scale=False, then fix_length).  The filter is
+ * the Kaiser-windowed sinc h(u) defined in zs_amd/resample.py (64 zero crossings, 512 table steps each, linear interpolation), and
+ * with s = min(1, sr_out / sr_in):
+ *   dst[u][t] = s * sum_{m < n_in[u]} src[u][m] * h(s * (t * sr_in / sr_out - m))     t < n_out[u] = ceil(n_in[u] * sr_out / sr_in)
+ *   dst[u][t] = 0                                                                      n_out[u] <= t < dst_ld
+ * executed in polyphase form: t * sr_in = q * sr_out + r exactly (int64), H = ceil(64 / s),
+ *   dst[u][t] = sum_{j = -H..H} tap(r / g, j) * src[u][q + j],     tap(p, j) = s * h(s * (p * g / sr_out - j)),  g = gcd(sr_in, sr_out),
+ * samples outside [0, n_in[u]) counting as zero: src[u][m] is never read for m >= n_in[u] (the slack of a row may hold anything).
+ * bank: the taps, computed by the caller in fp64 and rounded once to fp32, n_tap = 2 H + 1 rows of n_phase = sr_out / g floats in
+ * OUTPUT order:   bank[(j + H) * n_phase + k] = tap((k * (sr_in / g)) mod n_phase, j)      k = t mod n_phase,
+ * so that the lanes of a wave, which take consecutive outputs t, read consecutive floats of a row at every tap (the phases of
+ * consecutive outputs are a strided permutation of 0..n_phase-1; the permutation is applied once, on the host).
+ * One workgroup per (utterance, tile of consecutive outputs), its input span staged in LDS; a thread takes up to four outputs of
+ * one phase (a multiple of n_phase apart), which share every tap it loads; fp32 FMA accumulation in the fixed order j = -H..H for
+ * every output: a launch is bitwise reproducible and a row's result does not depend on the rows around it.  n_in[u] is clamped to
+ * [0, src_ld] and n_out[u] to dst_ld on the device.
+ * Errors (nothing is launched): a null pointer with n_utt > 0; n_utt < 0 or > 65535; sr_in <= 0 or sr_out <= 0; sr_out / sr_in
+ * outside [1/32, 32]; n_tap != 2 ceil(64 / s) + 1; n_phase != sr_out / g; src_ld or dst_ld <= 0; n_in_max < 0, and with
+ * n_in_max > 0 (the host's maximum of n_in, 0 = not known): src_ld < n_in_max or dst_ld < ceil(n_in_max * sr_out / sr_in).
+ * n_utt == 0 succeeds and launches nothing. */
+typedef struct {
+  const float* src; int64_t src_ld;      /* [n_utt][src_ld] */
+  const int32_t* n_in;                   /* [n_utt], device */
+  int32_t n_utt, sr_in, sr_out;
+  const float* bank; int32_t n_phase, n_tap;
+  float* dst; int64_t dst_ld;            /* [n_utt][dst_ld], every element written */
+  int32_t n_in_max;
+} ZsResample;
+int zs_resample(const ZsResample* p, void* stream);
 
 
 /* ---------------------------------------------------------------------------------------------

@@ -12,7 +12,11 @@
 
 Vocoder of --test, --cross_test and --test_single: --gl_iters N sets the Griffin-Lim iterations (hp.n_iter, default 300),
 --gl_momentum A in [0, 1) the fast Griffin-Lim momentum (hp.gl_momentum, default 0: the reference's plain loop), e.g.
-`--gl_iters 100 --gl_momentum 0.99`.
+`--gl_iters 100 --gl_momentum 0.99`.  --out_sr N writes their wavs at N Hz instead of 16000 (hp.out_sr; band-limited resampling
+on the GPU, zs_amd.resample), e.g. `--out_sr 44100`; N / 16000 must lie within [1/32, 32].
+
+Sound files read by --preprocess, --test_single and --test_classify may have any sample rate: they are resampled to 16 kHz on
+the GPU as the reference's librosa.load does.
 
 Every --train* mode takes --device_data: the training set is uploaded into GPU memory once and each batch is gathered there
 (zs_amd.pool), in the host DataLoader's order; ZS_POOL_MAX_GB caps the pool's size.
@@ -50,6 +54,16 @@ def _gl_momentum(text):
     if not 0.0 <= a < 1.0:                    # NaN fails too
         raise argparse.ArgumentTypeError('--gl_momentum must be in [0, 1) (got %s)' % text)
     return a
+
+
+def _out_sr(text):
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('--out_sr must be a positive integer (got %s)' % text)
+    if n <= 0 or n > 32 * 16000 or 32 * n < 16000:
+        raise argparse.ArgumentTypeError('--out_sr must be a positive integer with out_sr / 16000 within [1/32, 32] (got %s)' % text)
+    return n
 
 
 def build_parser():
@@ -93,6 +107,8 @@ def build_parser():
     p.add_argument('--gl_iters', type=_gl_iters, default=None, help='Griffin-Lim iterations (hp.n_iter); default: leave hp as it is')
     p.add_argument('--gl_momentum', type=_gl_momentum, default=None,
                    help='fast Griffin-Lim momentum in [0, 1) (hp.gl_momentum); default: leave hp as it is')
+    p.add_argument('--out_sr', type=_out_sr, default=None,
+                   help='sample rate of the wavs --test / --cross_test / --test_single write (hp.out_sr); default: 16000')
     return p
 
 
@@ -131,6 +147,8 @@ def argument_runner(argv=None):
         hp.n_iter = args.gl_iters
     if args.gl_momentum is not None:
         hp.gl_momentum = args.gl_momentum
+    if args.out_sr is not None:
+        hp.out_sr = args.out_sr
     hps = Hps(args.hps_path).get_tuple()
     if args.g_mode == 'set_from_hps':
         args.g_mode = hps.g_mode

@@ -298,7 +298,7 @@ def convert(trainer, seg_len, src_speaker_spec, src_speaker, tar_speaker, utt_id
         wav_path = None
         if 'wav' in save:
             wav_path = os.path.join(result_dir, f'{tar_speaker}_{utt_id}.wav')
-            write_wav(wav_path, wav_data, hp.sr)
+            write_wav(wav_path, to_out_sr([wav_data])[0], out_rate())
         if 'enc' in save:
             write_encodings(os.path.join(result_dir, f'{src_speaker}_{utt_id}.txt'), encodings)
         return wav_path, len(converted_results)
@@ -629,6 +629,20 @@ def _finish_resynth(q, fin, defer):
     return finish if defer else finish()
 
 
+def out_rate():
+    """The sample rate of the wavs convert(), cross_test and test_single write: hp.out_sr (--out_sr), or hp.sr when it is None."""
+    return hp.sr if hp.out_sr is None else int(hp.out_sr)
+
+
+def to_out_sr(wavs):
+    """A list of hp.sr waveforms at the output rate: the very list when hp.out_sr is None or hp.sr, else resampled in one
+    zs_resample launch (zs_amd.resample)."""
+    if out_rate() == hp.sr:
+        return wavs
+    from .resample import resample_batch
+    return resample_batch(wavs, hp.sr, out_rate())
+
+
 def write_wav(path, wav, sr):
     """16-bit PCM mono wav (the reference uses soundfile.write(..., 'PCM_16'), convert.py:174)."""
     import wave
@@ -720,9 +734,9 @@ def cross_test(trainer, seg_len, data_path, speaker2id_path, result_dir, enc_onl
 
         def write(group, fin):
             encs, wavs = fin()
-            for it, e, w in zip(group, encs, wavs):
+            for it, e, w in zip(group, encs, to_out_sr(wavs)):
                 os.makedirs(it['dir'], exist_ok=True)
-                write_wav(it['wav'], w, hp.sr)
+                write_wav(it['wav'], w, out_rate())
                 write_encodings(it['txt'], e)
 
         pending = None
@@ -761,7 +775,7 @@ def test_single(trainer, seg_len, speaker2id_path, result_dir, enc_only, s_speak
     _, spec = get_spectrograms(filename)
     wav_data, encodings = convert(trainer, seg_len, src_speaker_spec=spec, src_speaker=s_speaker, tar_speaker=t_speaker, utt_id='',
                                   speaker2id=speaker2id, result_dir=result_dir, enc_only=enc_only, save=[])
-    write_wav(os.path.join(result_dir, 'result.wav'), wav_data, hp.sr)
+    write_wav(os.path.join(result_dir, 'result.wav'), to_out_sr([wav_data])[0], out_rate())
     write_encodings(os.path.join(result_dir, 'result.txt'), encodings)
     print('Testing on source speaker {} and target speaker {}, output shape: {}'.format(s_speaker, t_speaker, wav_data.shape))
     print('Comparing ASR result - skipped (the reference calls the Google Web Speech API here; no network)')
@@ -856,17 +870,20 @@ def target_classify(trainer, seg_len, synthesis_list, result_dir, flag='test', m
     """convert.py:364-414: the accuracy of the TargetClassifier on the wavs --test wrote, {result_dir}/{flag}/{tar}_{utt}.wav for
     each line of the synthesis list, over every fragment of every utterance (V001 / V002 / 'None' against the target speaker).
     All wavs go through one zs_pre_spectrogram batch, the fragments through classify_batch, the scoring through zs_tclf_score;
-    the only host synchronisation is the read of the two counts at the end.  Prints and returns the accuracy."""
-    from .preprocess import get_spectrograms_device, load_wav
+    the only host synchronisation is the read of the two counts at the end (wavs that are not at hp.sr, written by another tool
+    or with --out_sr, are resampled first, which brings them back to the host once).  Prints and returns the accuracy."""
+    from .preprocess import get_spectrograms_device, read_wav
     dir_path = os.path.join(result_dir, f'{flag}/')
     with open(synthesis_list, 'r') as f:
         lines = [l for l in f.readlines() if l.strip()]
-    wavs, tars = [], []
+    wavs, rates, tars = [], [], []
     for line in lines:
         line = line.split('\n')[0].split(' ')
         utt_id = line[0].split('/')[1].split('_')[1]
         tar_speaker = line[1]
-        wavs.append(load_wav(os.path.join(dir_path, f'{tar_speaker}_{utt_id}.wav')))
+        wav, sr = read_wav(os.path.join(dir_path, f'{tar_speaker}_{utt_id}.wav'))
+        wavs.append(wav)
+        rates.append(sr)
         tars.append(tar_speaker)
     if not getattr(trainer, 'tclf_loaded', False):
         print('[Converter] - warning: no target_classifier was loaded (hps load_model_list does not name it, or loading failed): '
@@ -875,7 +892,7 @@ def target_classify(trainer, seg_len, synthesis_list, result_dir, flag='test', m
         print('Classification Acc: {:.3f}'.format(float('nan')))
         return float('nan')
     dev = trainer.device
-    mag, frames = get_spectrograms_device(wavs, device=dev)
+    mag, frames = get_spectrograms_device(wavs, device=dev, sr=rates)      # files not at hp.sr: one resampling launch per rate
     logits, plan = classify_batch((mag, frames), trainer, seg_len, max_batch=max_batch)
     target = torch.from_numpy(tclf_targets([tars[u] for u, _ in plan])).pin_memory().to(dev, non_blocking=True)
     counts = torch.zeros(2, dtype=torch.int32, device=dev)

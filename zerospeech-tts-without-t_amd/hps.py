@@ -20,6 +20,7 @@ class ProcessingHyperparams(object):
         self.power = 1.2
         self.n_iter = 300
         self.gl_momentum = 0.0      # fast Griffin-Lim momentum alpha in [0, 1) (not in the reference; 0 = its plain loop)
+        self.out_sr = None          # sample rate of the written wavs (not in the reference; None = hp.sr; set by --out_sr)
         self.preemphasis = .97
         self.max_db = 100
         self.ref_db = 20

@@ -2,8 +2,9 @@
 
 * `get_spectrograms(sound_file)` / `get_spectrograms_batch(wavs)` -- preprocess.py:227-258: trim -> pre-emphasis -> STFT ->
   |.| -> mel(80) -> dB -> normalise, with the STFT / dB / mel product on the GPU (`zs_pre_spectrogram`, `zs_pre_mel`); the trim
-  (librosa.effects.trim defaults) is host NumPy.  Sound files are read with scipy (16-bit / float wav at hp.sr; the reference's
-  librosa.load would resample, which is not reproduced: other rates raise).
+  (librosa.effects.trim defaults) is host NumPy.  Sound files are read with scipy (`read_wav`: 8 / 16 / 32-bit PCM or float wav
+  at any rate); a file that is not at hp.sr is resampled to it on the GPU as the reference's librosa.load does (`zs_resample`,
+  zs_amd.resample: a restatement of resampy's kaiser_best, sample-level parity unpinned), a file at hp.sr is used as it is.
 * `make_dataset`, `Sampler`, `make_samples`, `preprocess` -- preprocess.py:26-225: the `{train,test}/<speaker>/<utt>/{lin,mel}`
   float32 layout and the `[{speaker, i, t}]` index JSON.  The container is HDF5 when h5py is importable (the reference's
   format); otherwise the same keys go into an .npz archive (`NpzStore`), which `dataloader.Dataset` also reads.
@@ -89,9 +90,35 @@ def _enqueue_spectrograms(wavs, do_trim, dev, with_amp):
     return mag, amp, lens
 
 
-def get_spectrograms_batch(wavs, do_trim=True, device=None):
-    """wavs: list of 1-D float arrays at hp.sr.  Returns a list of (mel [T, 80], mag [T, 513]) float32 NumPy pairs."""
+def _to_hp_sr(wavs, sr, dev):
+    """The wavs at hp.sr, in their order.  sr: None, one rate for all, or one per wav.  Entries already at hp.sr are passed through
+    untouched (None / hp.sr for all: the very list comes back); the others are grouped by rate, one zs_resample launch per distinct
+    rate, every launch enqueued before the first result is fetched, and come back to the host as float32 arrays."""
+    if sr is None:
+        return wavs
+    rates = [int(sr)] * len(wavs) if np.ndim(sr) == 0 else [int(r) for r in sr]
+    if len(rates) != len(wavs):
+        raise ValueError('sr must be one rate or one rate per wav (%d rates for %d wavs)' % (len(rates), len(wavs)))
+    if all(r == hp.sr for r in rates):
+        return wavs
+    from .resample import resample_batch
+    out = list(wavs)
+    pending = []
+    for rate in sorted({r for r in rates if r != hp.sr}):
+        idx = [i for i, r in enumerate(rates) if r == rate]
+        pending.append((idx,) + resample_batch([wavs[i] for i in idx], rate, hp.sr, device=dev, to_host=False))
+    for idx, dst, lens in pending:
+        dst_h = dst.cpu().numpy()
+        for k, i in enumerate(idx):
+            out[i] = dst_h[k, :lens[k]].copy()
+    return out
+
+
+def get_spectrograms_batch(wavs, do_trim=True, device=None, sr=None):
+    """wavs: list of 1-D float arrays at hp.sr, or at the rate(s) `sr` (an int, or one int per wav): those not at hp.sr are resampled
+    first (_to_hp_sr).  Returns a list of (mel [T, 80], mag [T, 513]) float32 NumPy pairs."""
     dev = _device_of(device)
+    wavs = _to_hp_sr(wavs, sr, dev)
     mag, amp, lens = _enqueue_spectrograms(wavs, do_trim, dev, True)
     n, T_max = mag.shape[0], mag.shape[1]
     mel = torch.zeros(n, T_max, hp.n_mels, dtype=torch.float32, device=dev)
@@ -109,31 +136,47 @@ def get_spectrograms_batch(wavs, do_trim=True, device=None):
     return out
 
 
-def get_spectrograms_device(wavs, do_trim=True, device=None):
+def get_spectrograms_device(wavs, do_trim=True, device=None, sr=None):
     """The magnitudes of get_spectrograms_batch left on the device: (mag fp32 [n, T_max, 513] on `device`, frames int64 [n] host
-    array).  Utterance i is mag[i, :frames[i]]; the rows behind it are zeros.  No mel, no host copy, no synchronisation."""
-    mag, _, lens = _enqueue_spectrograms(wavs, do_trim, _device_of(device), False)
+    array).  Utterance i is mag[i, :frames[i]]; the rows behind it are zeros.  No mel, no host copy.  No synchronisation either,
+    unless an input needs resampling (`sr` names a rate other than hp.sr): the resampled audio comes back to the host for the
+    trim, which synchronises once -- when, and only when, that is the case."""
+    dev = _device_of(device)
+    mag, _, lens = _enqueue_spectrograms(_to_hp_sr(wavs, sr, dev), do_trim, dev, False)
     return mag, 1 + lens.astype(np.int64) // hp.hop_length
 
 
-def load_wav(sound_file):
-    """16 kHz mono waveform in [-1, 1] (librosa.load(sound_file, sr=hp.sr) for files that already are at hp.sr)."""
+def read_wav(sound_file):
+    """(mono float32 waveform in [-1, 1], sample rate) of a wav file, as stored: 8-bit (unsigned), 16- and 32-bit PCM are scaled
+    by their full range, float32 / float64 are taken as they are; channels are averaged after the scaling (so an integer stereo
+    file is scaled too).  No GPU."""
     from scipy.io import wavfile
     sr, data = wavfile.read(sound_file)
-    if sr != hp.sr:
-        raise ValueError('%s is sampled at %d Hz; resampling to %d Hz (librosa.load) is not reproduced' % (sound_file, sr, hp.sr))
-    if data.ndim > 1:
-        data = data.mean(axis=1)
     if data.dtype == np.int16:
         data = data.astype(np.float32) / 32768.0
     elif data.dtype == np.int32:
         data = data.astype(np.float32) / 2147483648.0
-    return data.astype(np.float32)
+    elif data.dtype == np.uint8:
+        data = (data.astype(np.float32) - 128.0) / 128.0
+    if data.ndim > 1:
+        data = data.mean(axis=1)
+    return data.astype(np.float32), int(sr)
+
+
+def load_wav(sound_file):
+    """hp.sr (16 kHz) mono waveform in [-1, 1]: librosa.load(sound_file, sr=hp.sr).  A file at hp.sr is returned as read; any other
+    rate is resampled on the GPU (zs_amd.resample)."""
+    data, sr = read_wav(sound_file)
+    if sr == hp.sr:
+        return data
+    from .resample import resample_batch
+    return resample_batch([data], sr, hp.sr)[0]
 
 
 def get_spectrograms(sound_file):
     """preprocess.py:227-258: (mel [T, n_mels], mag [T, 1+n_fft/2]) normalised log spectrograms of a sound file."""
-    return get_spectrograms_batch([load_wav(sound_file)])[0]
+    data, sr = read_wav(sound_file)
+    return get_spectrograms_batch([data], sr=sr)[0]
 
 
 def make_dataset(grps, seg_len, root_dir, make_test=False, pad=True, batch=32):
@@ -143,7 +186,8 @@ def make_dataset(grps, seg_len, root_dir, make_test=False, pad=True, batch=32):
     print('Number of speakers: ', len({os.path.basename(f).split('_')[0] for f in filenames}))
     for lo in range(0, len(filenames), batch):
         chunk = filenames[lo:lo + batch]
-        feats = get_spectrograms_batch([load_wav(f) for f in chunk])
+        read = [read_wav(f) for f in chunk]
+        feats = get_spectrograms_batch([w for w, _ in read], sr=[r for _, r in read])     # one resampling launch per distinct rate
         for filename, (mel_spec, lin_spec) in zip(chunk, feats):
             speaker_id, segment_id = os.path.basename(filename)[:-len('.wav')].split('_')
             if pad and len(lin_spec) <= seg_len:                                       # preprocess.py:95-100
