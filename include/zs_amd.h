@@ -584,8 +584,42 @@ typedef struct {
   float preemph, ref_db, max_db;
   float* mag; int64_t mag_ld;      /* [n_utt][T_max][mag_ld], mag_ld >= 513 */
   float* amp;
+  const int32_t* start;            /* optional [n_utt], device (appended; NULL = 0 for every row): utterance u is the window
+                                      wav[u][start[u] .. start[u] + n_samples[u]) */
 } ZsPreSpec;
 int zs_pre_spectrogram(const ZsPreSpec* p, void* stream);
+/* ZsPreSpec.start: the window is the utterance, exactly as a host-sliced copy of it would be: the reflect padding and the
+ * pre-emphasis predecessor stay inside it (frame 0 / sample 0 uses w[0] of the window) and nothing outside it is read, so the
+ * bounds zs_trim leaves on the device are applied in place.  start[u] is clamped to [0, wav_ld] and the window to the row. */
+/* zs_trim: librosa.effects.trim (preprocess.py:238) for a ragged batch on the device; the definition is zs_amd.convert.trim().
+ * wav fp32 [n_utt][wav_ld], n = n_samples[u] (device, clamped to wav_ld) -> bounds int32 [n_utt][2] = (start, stop) on the device:
+ *   frames      f = 0 .. n / hop                                               (1 + n / hop of them, centred)
+ *   mse[f]      = mean_{i < frame_length} y[refl(f * hop + i - frame_length / 2)]^2, accumulated in double
+ *   refl        numpy's mode='reflect' for ANY pad width, a triangle wave: P = 2 (n - 1), m = j mod P taken non-negative,
+ *               refl(j) = m if m < n else P - m; n == 1 maps every j to 0 (so n <= frame_length / 2 is covered, which
+ *               zs_gl_frame_mse does not)
+ *   kept        10 log10(max(1e-10, mse[f])) - 10 log10(max(1e-10, max_f mse[f])) > -top_db   (both floors: an all-zero or very
+ *               quiet row keeps every frame and gives (0, n))
+ *   bounds      start = first_kept * hop, stop = min(n, (last_kept + 1) * hop); (0, 0) when no frame is kept
+ *   n <= 0      (0, 0), nothing of the row is read.  Samples at or past n_samples[u] are never read (the slack may hold anything).
+ * Two launches: one wave per (utterance, block of hop samples) writes the block's sum of squares into `work` (every sample read
+ * once; 16-byte loads where the address allows), then one workgroup per utterance forms the frame means from frame_length / hop
+ * consecutive block sums, their maximum and the bounds.  Every sum has a fixed order that depends on the row alone: a launch is
+ * bitwise reproducible and a row's bounds do not depend on the rows around it, on wav_ld or on the load width.  No atomics.
+ * work: caller-owned, 8-byte aligned, zs_trim_workspace_bytes(n_utt, wav_ld, frame_length, hop) bytes (n_utt * (wav_ld / hop +
+ * frame_length / hop) doubles; 0 for arguments zs_trim would refuse); contents on entry ignored.  No allocation, stream-ordered.
+ * Errors (nothing is launched): a null pointer with n_utt > 0; n_utt < 0 or > 65535; hop <= 0; frame_length odd or not a positive
+ * multiple of hop; wav_ld outside (0, 2^31); top_db not > 0; work_bytes too small.  n_utt == 0 succeeds and launches nothing. */
+typedef struct {
+  const float* wav; int64_t wav_ld;      /* [n_utt][wav_ld] */
+  const int32_t* n_samples;              /* [n_utt], device */
+  int32_t n_utt, frame_length, hop;
+  float top_db;
+  int32_t* bounds;                       /* [n_utt][2], device */
+  double* work; size_t work_bytes;
+} ZsTrim;
+size_t zs_trim_workspace_bytes(int32_t n_utt, int64_t wav_ld, int32_t frame_length, int32_t hop);
+int zs_trim(const ZsTrim* p, void* stream);
 /* mel[r][m] = clip((20 log10(max(1e-5, sum_k basis[m][k] amp[r][k])) - ref_db + max_db) / max_db, 1e-8, 1); basis [n_mels][513]
  * (librosa.filters.mel(sr, n_fft, n_mels), preprocess.py:243-252) */
 int zs_pre_mel(const float* amp, const float* basis, float* mel, int64_t rows, int32_t n_mels, float ref_db, float max_db, void* stream);

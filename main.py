@@ -9,14 +9,17 @@
   python main.py --train_c [--load_model] [--synthetic]    (the target speaker classifier, mode t_classify)
   python main.py --test_classify --load_tclf_model_name CKPT   (scores the wavs --test wrote; hps load_model_list must name
                                                            target_classifier)
+  python main.py --convert_dir DIR --t_speaker V001,V002 [--enc_only] [--ckpt_pth CKPT]    (every *.wav of DIR, any format and
+                                                           rate, to each target: {result_dir}/{sub_result_dir}/convert/
+                                                           {target}/{stem}.wav + .txt and convert_dir.json)
 
-Vocoder of --test, --cross_test and --test_single: --gl_iters N sets the Griffin-Lim iterations (hp.n_iter, default 300),
---gl_momentum A in [0, 1) the fast Griffin-Lim momentum (hp.gl_momentum, default 0: the reference's plain loop), e.g.
+Vocoder of --test, --cross_test, --test_single and --convert_dir: --gl_iters N sets the Griffin-Lim iterations (hp.n_iter,
+default 300), --gl_momentum A in [0, 1) the fast Griffin-Lim momentum (hp.gl_momentum, default 0: the reference's plain loop), e.g.
 `--gl_iters 100 --gl_momentum 0.99`.  --out_sr N writes their wavs at N Hz instead of 16000 (hp.out_sr; band-limited resampling
 on the GPU, zs_amd.resample), e.g. `--out_sr 44100`; N / 16000 must lie within [1/32, 32].
 
-Sound files read by --preprocess, --test_single and --test_classify may have any sample rate: they are resampled to 16 kHz on
-the GPU as the reference's librosa.load does.
+Sound files read by --preprocess, --test_single, --test_classify and --convert_dir may have any sample rate: they are resampled
+to 16 kHz on the GPU as the reference's librosa.load does.
 
 Every --train* mode takes --device_data: the training set is uploaded into GPU memory once and each batch is gathered there
 (zs_amd.pool), in the host DataLoader's order; ZS_POOL_MAX_GB caps the pool's size.
@@ -103,7 +106,10 @@ def build_parser():
     p.add_argument('--ckpt_pth', type=str, default=None)
     p.add_argument('--load_tclf_model_name', type=str, default=None)     # main.py:79: a path, used as given
     p.add_argument('--s_speaker', type=str, default='S015')
-    p.add_argument('--t_speaker', type=str, default='V002')
+    p.add_argument('--t_speaker', type=str, default='V002', help='target speaker; with --convert_dir a comma-separated list')
+    p.add_argument('--convert_dir', type=str, default=None, metavar='DIR',
+                   help='convert every *.wav of DIR (any PCM / float format, any rate) to each --t_speaker, on the GPU from the '
+                        'samples to the waveform; outputs under {result_dir}/{sub_result_dir}/convert/')
     p.add_argument('--gl_iters', type=_gl_iters, default=None, help='Griffin-Lim iterations (hp.n_iter); default: leave hp as it is')
     p.add_argument('--gl_momentum', type=_gl_momentum, default=None,
                    help='fast Griffin-Lim momentum in [0, 1) (hp.gl_momentum); default: leave hp as it is')
@@ -131,11 +137,23 @@ def check_resume(args):
         raise ValueError('--resume loads the newest checkpoint of its stage itself: it cannot be combined with --load_model')
 
 
+def convert_targets(args):
+    """--convert_dir takes --t_speaker as a comma-separated list of distinct names (--test_single keeps the single name): the
+    list, refused before anything is built when it names no speaker or one twice."""
+    names = [t.strip() for t in args.t_speaker.split(',')]
+    if not all(names):
+        raise ValueError('--convert_dir needs --t_speaker NAME[,NAME...] (got %r)' % args.t_speaker)
+    if len(set(names)) != len(names):
+        raise ValueError('--t_speaker names a speaker twice (got %r)' % args.t_speaker)
+    return names
+
+
 def argument_runner(argv=None):
     from zs_amd.hps import Hps, hp
     parser = build_parser()
     args = parser.parse_args(argv)
     check_resume(args)
+    args.t_speakers = convert_targets(args) if args.convert_dir is not None else None
     if args.dataset == 'surprise':            # main.py:83-88: english -> surprise in every default path
         for action in parser._actions:
             if isinstance(action.default, str) and 'english' in action.default and \
@@ -168,7 +186,7 @@ def main(argv=None):
     if bad:
         raise NotImplementedError('--%s is outside the stage-1 autoencoder hot path this build covers' % bad[0])
     from zs_amd import parallel
-    from zs_amd.convert import cross_test, get_trainer, target_classify, test_encode, test_from_list, test_single
+    from zs_amd.convert import convert_dir, cross_test, get_trainer, target_classify, test_encode, test_from_list, test_single
     from zs_amd.dataloader import DataLoader, Dataset, SyntheticDataset
     from zs_amd.trainer import Trainer
 
@@ -221,7 +239,7 @@ def main(argv=None):
             print("[Runner] - --train ran the pretrain_AE and patchGAN stages; the reference's autolocker / t_classify / Tacotron "
                   'stages are not part of this build and were skipped')
 
-    if args.test or args.cross_test or args.test_encode or args.test_single or args.test_classify:
+    if args.test or args.cross_test or args.test_encode or args.test_single or args.test_classify or args.convert_dir is not None:
         os.makedirs(args.result_dir, exist_ok=True)
         model_path = args.ckpt_pth if args.ckpt_pth is not None else os.path.join(args.ckpt_dir, args.load_test_model_name)
         trainer = get_trainer(args.hps_path, model_path, args.g_mode, args.enc_mode, args.load_tclf_model_name)
@@ -237,6 +255,9 @@ def main(argv=None):
             test_encode(trainer, hps.seg_len, args.test_path, args.dataset_path, result_dir, flag='test')
         if args.test_classify:                            # main.py:196-199
             target_classify(trainer, hps.seg_len, args.synthesis_list, result_dir, flag='test')
+        if args.convert_dir is not None:                  # not in the reference: a folder of sound files to the target voices
+            convert_dir(trainer, hps.seg_len, args.convert_dir, args.speaker2id_path, os.path.join(result_dir, 'convert'), args.t_speakers,
+                        args.enc_only)
 
 
 if __name__ == '__main__':

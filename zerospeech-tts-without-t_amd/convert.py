@@ -752,6 +752,200 @@ def cross_test(trainer, seg_len, data_path, speaker2id_path, result_dir, enc_onl
     return plan
 
 
+# ---------------------------------------------------------------------------------------------------
+# a folder of sound files, end to end on the device (not in the reference: its drivers read a preprocessed container)
+# ---------------------------------------------------------------------------------------------------
+
+def _wav_features(wavs, rates, dev, do_trim=True, strict=True):
+    """Sound -> spectrograms that never leave the device (preprocess.get_spectrograms_device(trim_on='device')): the list of
+    mag[i, :frames[i]] views and, per input, {'bounds': (start, stop) of the trim at hp.sr, 'frames'}.  strict=False: an input of
+    fewer than 2 samples after trimming gets None and frames 0 instead of the ValueError."""
+    from .preprocess import _spectrograms_on_device
+    mag, frames, bounds = _spectrograms_on_device(wavs, do_trim, dev, rates, strict=strict)
+    specs = [mag[i, :int(frames[i])] if frames[i] > 0 else None for i in range(len(wavs))]
+    info = [{'bounds': (int(bounds[i, 0]), int(bounds[i, 1])), 'frames': int(frames[i])} for i in range(len(wavs))]
+    return specs, info
+
+
+def convert_wavs(wavs, rates, trainer, seg_len, speakers, enc_only=True, n_iter=None, momentum=None, noise_fn=None, do_trim=True,
+                 defer=False):
+    """Waveforms in, converted waveforms out, as one enqueue: wavs is a list of 1-D float arrays at `rates` (None: hp.sr; one int,
+    or one per wav), speakers the target id of each.  Inputs not at hp.sr are resampled on the device, zs_trim finds the trim
+    bounds there, zs_pre_spectrogram reads the trimmed windows in place and resynth_batch runs on the device-resident
+    mag[i, :frames[i]]: neither the audio nor the spectrograms visit the host (one synchronisation: the n x 2 bounds).  The values
+    are those of preprocess.get_spectrograms_batch(wavs, sr=rates) followed by resynth_batch(specs, ...), bit for bit.
+    Returns (encodings, wavs, info); info[i] = {'bounds': (start, stop) of the input's trim at hp.sr, 'frames'}.  do_trim is
+    get_spectrograms' trim of the input and the vocoder's trim of the output together; defer, enc_only, n_iter, momentum and
+    noise_fn are resynth_batch's.  An input of fewer than 2 samples after trimming raises ValueError before the network is
+    enqueued."""
+    momentum = gl_momentum(momentum)
+    if len(speakers) != len(wavs):
+        raise ValueError('convert_wavs: %d target speakers for %d wavs' % (len(speakers), len(wavs)))
+    if not enc_only:
+        check_gen_targets(trainer, speakers)
+    specs, info = _wav_features(wavs, rates, trainer.device, do_trim=do_trim)
+    fin = resynth_batch(specs, trainer, seg_len, speakers, n_iter=n_iter, do_trim=do_trim, noise_fn=noise_fn, defer=True, enc_only=enc_only,
+                        momentum=momentum)
+
+    def finish():
+        encs, out = fin()
+        return encs, out, info
+    return finish if defer else finish()
+
+
+def convert_dir_plan(files, durations, targets, out_dir, batch=64, max_batch_seconds=600, max_seconds=1800):
+    """The work list of convert_dir, on the host alone: every (file, target) pair is an item.  durations[i]: seconds of files[i]
+    from its header.  Files are sorted by (duration, path) so that a group pads little and the plan does not depend on the order
+    they are listed in; a file's items are adjacent, in the order of `targets`.  A group takes items in that order while it holds
+    at most `batch` of them and at most max_batch_seconds of padded audio, counted as items x the longest (a single item above the
+    cap is a group of its own).  A file longer than max_seconds, or whose header gives no samples, goes to 'skipped' with a reason;
+    two inputs with the same stem would write the same outputs: ValueError.
+    Returns {'groups': [[item]], 'skipped': [{'file', 'reason'}]}, item = {'file', 'stem', 'target', 'duration', 'wav', 'txt'} with
+    the outputs {out_dir}/{target}/{stem}.wav and .txt."""
+    if len(files) != len(durations):
+        raise ValueError('convert_dir_plan: %d durations for %d files' % (len(durations), len(files)))
+    if batch < 1:
+        raise ValueError('convert_dir_plan: batch must be >= 1')
+    targets = list(targets)
+    if not targets or len(set(targets)) != len(targets):
+        raise ValueError('convert_dir_plan: the targets must be a non-empty list of distinct speakers (got %r)' % (targets,))
+    stems = {}
+    for f in files:
+        stem = os.path.splitext(os.path.basename(f))[0]
+        if stem in stems:
+            raise ValueError('convert_dir_plan: %s and %s would write the same outputs (stem %r)' % (stems[stem], f, stem))
+        stems[stem] = f
+    skipped, items = [], []
+    for dur, f in sorted((float(d), f) for f, d in zip(files, durations)):
+        if not dur > 0.0:
+            skipped.append({'file': f, 'reason': 'the header gives no samples'})
+            continue
+        if dur > max_seconds:
+            skipped.append({'file': f, 'reason': '%.1f s is longer than max_seconds = %g' % (dur, max_seconds)})
+            continue
+        stem = os.path.splitext(os.path.basename(f))[0]
+        for t in targets:
+            items.append({'file': f, 'stem': stem, 'target': t, 'duration': dur, 'wav': os.path.join(out_dir, t, stem + '.wav'),
+                          'txt': os.path.join(out_dir, t, stem + '.txt')})
+    groups = []
+    for it in items:                                          # ascending durations: the newest item is a group's longest
+        if groups and len(groups[-1]) < batch and (len(groups[-1]) + 1) * it['duration'] <= max_batch_seconds:
+            groups[-1].append(it)
+        else:
+            groups.append([it])
+    return {'groups': groups, 'skipped': skipped}
+
+
+def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None):
+    """Every *.wav of in_dir (any PCM / float format, any rate, channels averaged: preprocess.read_wav) to every target speaker of
+    t_speakers, on the device from the samples to the waveform: {out_dir}/{target}/{stem}.wav (PCM16 at out_rate()) and .txt (the
+    units), plus the manifest {out_dir}/convert_dir.json, which is returned.
+    The items of convert_dir_plan go through the network and the vocoder in groups; a file's features (resampling, zs_trim,
+    zs_pre_spectrogram) are computed once and shared by its targets, every item draws its own Gumbel noise as in cross_test, group
+    i + 1 is enqueued before group i is written (defer=True), and one reader thread reads the files of the next group meanwhile.
+    The targets are checked before anything is read or enqueued.  A file that cannot be read, or is too short after trimming, is
+    skipped with a printed reason and listed in the manifest; the run goes on."""
+    from concurrent.futures import ThreadPoolExecutor
+    from .preprocess import read_wav, wav_info
+    momentum = gl_momentum(momentum)
+    with open(speaker2id_path, 'r') as f_json:
+        speaker2id = json.load(f_json)
+    t_speakers = list(t_speakers)
+    missing = [t for t in t_speakers if t not in speaker2id]
+    if missing:
+        raise ValueError('convert_dir: target speaker %r is not in %s' % (missing[0], speaker2id_path))
+    if not enc_only:
+        check_gen_targets(trainer, [speaker2id[t] for t in t_speakers])
+    skipped, files, durations = [], [], []
+
+    def skip(path, reason):
+        print('[Converter] - skipped %s: %s' % (path, reason))
+        skipped.append({'input': path, 'reason': reason})
+
+    for path in sorted(glob.glob(os.path.join(in_dir, '*.wav'))):
+        try:
+            sr, n = wav_info(path)
+            if sr <= 0:
+                raise ValueError('sample rate %d' % sr)
+        except (OSError, ValueError) as e:
+            skip(path, 'cannot be read: %s' % e)
+            continue
+        files.append(path)
+        durations.append(n / float(sr))
+    plan = convert_dir_plan(files, durations, t_speakers, out_dir, batch=batch)
+    for s in plan['skipped']:
+        skip(s['file'], s['reason'])
+    groups = plan['groups']
+    print('[Converter] - %d files, %d target speakers, %d conversions in %d groups' %
+          (len(files) - len(plan['skipped']), len(t_speakers), sum(len(g) for g in groups), len(groups)))
+    os.makedirs(out_dir, exist_ok=True)
+    dev = trainer.device
+    feats = {}                                # file -> (spec on the device, rate, samples, info), None for a skipped one
+    done = []
+
+    def read(group, have):
+        out = {}
+        for path in dict.fromkeys(it['file'] for it in group):
+            if path not in have:
+                try:
+                    out[path] = read_wav(path)
+                except Exception as e:                        # scipy raises ValueError and its own warnings-as-errors for bad files
+                    out[path] = e
+        return out
+
+    def write(group, fin):
+        encs, wavs = fin()
+        for it, e, w in zip(group, encs, to_out_sr(wavs)):
+            os.makedirs(os.path.dirname(it['wav']), exist_ok=True)
+            write_wav(it['wav'], w, out_rate())
+            write_encodings(it['txt'], e)
+            done.append(it)
+
+    pending = None
+    with ThreadPoolExecutor(max_workers=1) as reader:
+        fut = reader.submit(read, groups[0], ()) if groups else None
+        for gi, group in enumerate(groups):
+            data = fut.result()
+            if gi + 1 < len(groups):                          # the next group's files are read under this group's GPU work
+                fut = reader.submit(read, groups[gi + 1], set(feats) | set(data))
+            new = [p for p, d in data.items() if not isinstance(d, Exception)]
+            for p, d in data.items():
+                if isinstance(d, Exception):
+                    skip(p, 'cannot be read: %s' % d)
+                    feats[p] = None
+            if new:
+                specs, info = _wav_features([data[p][0] for p in new], [data[p][1] for p in new], dev, strict=False)
+                for p, spec, inf in zip(new, specs, info):
+                    if spec is None:
+                        skip(p, 'utterance too short after trimming')
+                        feats[p] = None
+                    else:
+                        feats[p] = (spec, data[p][1], len(data[p][0]), inf)
+            live = [it for it in group if feats[it['file']] is not None]
+            for it in live:
+                _, it['rate'], it['samples'], inf = feats[it['file']]
+                it['bounds'], it['frames'] = list(inf['bounds']), inf['frames']
+            fin = None
+            if live:
+                fin = resynth_batch([feats[it['file']][0] for it in live], trainer, seg_len, [speaker2id[it['target']] for it in live],
+                                    n_iter=n_iter, defer=True, enc_only=enc_only, momentum=momentum)
+            later = {it['file'] for g in groups[gi + 1:gi + 2] for it in g}
+            for p in [p for p in feats if p not in later]:    # a file's items are adjacent: done with, drop its device rows
+                del feats[p]
+            if pending is not None:
+                write(*pending)
+            pending = (live, fin) if live else None
+        if pending is not None:
+            write(*pending)
+    manifest = {'in_dir': in_dir, 'out_dir': out_dir, 'targets': t_speakers, 'sr': out_rate(), 'enc_only': bool(enc_only),
+                'items': [{'input': it['file'], 'rate': it['rate'], 'samples': it['samples'], 'target': it['target'],
+                           'bounds': it['bounds'], 'frames': it['frames'], 'wav': it['wav'], 'txt': it['txt']} for it in done],
+                'skipped': skipped}
+    with open(os.path.join(out_dir, 'convert_dir.json'), 'w') as f:
+        json.dump(manifest, f, indent=1)
+    return manifest
+
+
 SINGLE_FILES = {            # convert.py:308-317: the utterances --test_single knows per source speaker
     'S015': './data/english/train/unit/S015_0361841101.wav',
     'S119': './data/english/train/unit/S119_1561145062.wav',

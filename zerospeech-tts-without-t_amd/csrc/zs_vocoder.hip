@@ -124,19 +124,24 @@ __global__ __launch_bounds__(NTV) void gl_stft_project_kernel(const ZsGlStft p) 
   }
 }
 
-// preprocess.py:227-258 (get_spectrograms) after the host-side trim: pre-emphasis y[n] - c*y[n-1], librosa.stft(n_fft 1024,
-// hop 200, hann(800) centred in the 1024 frame, center=True reflect padding), |.|, 20*log10(max(1e-5, .)), normalise and
+// preprocess.py:227-258 (get_spectrograms) after the trim (on the host, or zs_trim's bounds applied through ZsPreSpec.start):
+// pre-emphasis y[n] - c*y[n-1], librosa.stft(n_fft 1024, hop 200, hann(800) centred in the 1024 frame, center=True reflect padding), |.|, 20*log10(max(1e-5, .)), normalise and
 // clip to [1e-8, 1].  One workgroup per (utterance, frame); amp (optional) keeps the linear magnitudes for the mel product.
 __global__ __launch_bounds__(NTV) void pre_spectrogram_kernel(const ZsPreSpec p) {
   __shared__ float2 bufA[NFFT];
   __shared__ float2 bufB[NFFT];
   __shared__ float2 tw[NFFT / 2];
   const int tid = threadIdx.x, t = blockIdx.x, u = blockIdx.y;
-  const int L = p.n_samples[u];
+  int L = p.n_samples[u];
+  int64_t s0 = 0;                                                   // ZsPreSpec.start: the utterance is a window of its row
+  if (p.start) {
+    s0 = min(max((int64_t)p.start[u], (int64_t)0), p.wav_ld);
+    L = (int)min((int64_t)L, p.wav_ld - s0);
+  }
   const int T = 1 + L / HOP;                                        // librosa: 1 + len(y) // hop_length frames
   if (t >= T || L < 2) return;
   build_twiddles(tw, tid);
-  const float* w = p.wav + (int64_t)u * p.wav_ld;
+  const float* w = p.wav + (int64_t)u * p.wav_ld + s0;
   for (int n = tid; n < NFFT; n += NTV) {
     int idx = t * HOP + n - NFFT / 2;                               // np.pad(y, 512, mode='reflect') of the pre-emphasised signal
     if (idx < 0) idx = -idx;

@@ -2,7 +2,8 @@
 
 * `get_spectrograms(sound_file)` / `get_spectrograms_batch(wavs)` -- preprocess.py:227-258: trim -> pre-emphasis -> STFT ->
   |.| -> mel(80) -> dB -> normalise, with the STFT / dB / mel product on the GPU (`zs_pre_spectrogram`, `zs_pre_mel`); the trim
-  (librosa.effects.trim defaults) is host NumPy.  Sound files are read with scipy (`read_wav`: 8 / 16 / 32-bit PCM or float wav
+  (librosa.effects.trim defaults) is host NumPy, or, with get_spectrograms_device(trim_on='device'), `zs_trim` on audio that
+  stays in HBM (`trim_device`; the spectrogram kernel reads the trimmed window in place).  Sound files are read with scipy (`read_wav`: 8 / 16 / 32-bit PCM or float wav
   at any rate); a file that is not at hp.sr is resampled to it on the GPU as the reference's librosa.load does (`zs_resample`,
   zs_amd.resample: a restatement of resampy's kaiser_best, sample-level parity unpinned), a file at hp.sr is used as it is.
 * `make_dataset`, `Sampler`, `make_samples`, `preprocess` -- preprocess.py:26-225: the `{train,test}/<speaker>/<utt>/{lin,mel}`
@@ -19,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .convert import trim
+from .convert import TRIM_FRAME, TRIM_HOP, trim
 from .dataloader import NpzStore, open_store
 from .hps import hp
 
@@ -136,14 +137,133 @@ def get_spectrograms_batch(wavs, do_trim=True, device=None, sr=None):
     return out
 
 
-def get_spectrograms_device(wavs, do_trim=True, device=None, sr=None):
+def trim_device(wav, n_samples, top_db=60):
+    """librosa.effects.trim (convert.trim is the definition) of a ragged batch on the device: ONE zs_trim call on the current
+    stream, no synchronisation.  wav fp32 [n, ld] and n_samples int32 [n] are tensors on the GPU (row u holds n_samples[u] samples;
+    the slack behind them is never read).  Returns bounds int32 [n, 2] = (start, stop) on the device."""
+    if not (torch.is_tensor(wav) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.is_contiguous()):
+        raise ValueError('trim_device: wav must be a contiguous fp32 [n, ld] tensor on the GPU')
+    dev = wav.device
+    n, ld = int(wav.shape[0]), int(wav.shape[1])
+    if not (torch.is_tensor(n_samples) and n_samples.device == dev and n_samples.dtype == torch.int32 and n_samples.is_contiguous()
+            and n_samples.numel() == n):
+        raise ValueError('trim_device: n_samples must be a contiguous int32 [n] tensor on the device of wav')
+    bounds = torch.empty(n, 2, dtype=torch.int32, device=dev)
+    work = torch.empty(max(1, L.lib().zs_trim_workspace_bytes(n, ld, TRIM_FRAME, TRIM_HOP) // 8), dtype=torch.float64, device=dev)
+    L.call('zs_trim', 'ZsTrim', torch.cuda.current_stream(dev).cuda_stream, wav=L.ptr(wav), wav_ld=ld, n_samples=L.ptr(n_samples), n_utt=n,
+           frame_length=TRIM_FRAME, hop=TRIM_HOP, top_db=float(top_db), bounds=L.ptr(bounds), work=L.ptr(work), work_bytes=work.numel() * 8)
+    return bounds
+
+
+def _device_audio(wavs, sr, dev):
+    """The wavs at hp.sr as ONE padded buffer on the device, none of them coming back to the host: (wav fp32 [n, ld], lens int32 [n]
+    host array).  Entries at hp.sr go up through pinned staging; the others are resampled there, one zs_resample launch per distinct
+    rate (their lengths are resample.out_length, known on the host), and every group is copied into its rows on the device."""
+    n = len(wavs)
+    rates = [hp.sr] * n if sr is None else ([int(sr)] * n if np.ndim(sr) == 0 else [int(r) for r in sr])
+    if len(rates) != n:
+        raise ValueError('sr must be one rate or one rate per wav (%d rates for %d wavs)' % (len(rates), n))
+    ys = [np.asarray(w, dtype=np.float32) for w in wavs]
+    if any(y.ndim != 1 for y in ys):
+        raise ValueError('the wavs must be 1-D arrays')
+    lens = np.zeros(n, dtype=np.int32)
+    groups = []                                                              # (rows, device tensor [len(rows), ld_g])
+    for rate in sorted(set(rates)):
+        idx = [i for i, r in enumerate(rates) if r == rate and len(ys[i]) > 0]
+        if not idx:
+            continue
+        if rate == hp.sr:
+            glens = [len(ys[i]) for i in idx]
+            host = np.zeros((len(idx), max(glens)), dtype=np.float32)
+            for k, i in enumerate(idx):
+                host[k, :glens[k]] = ys[i]
+            part = _pinned(host, dev)
+        else:
+            from .resample import resample_batch
+            part, glens = resample_batch([ys[i] for i in idx], rate, hp.sr, device=dev, to_host=False)
+        lens[idx] = glens
+        groups.append((idx, part))
+    ld = max(1, int(lens.max()) if n else 1)
+    if len(groups) == 1 and groups[0][0] == list(range(n)):
+        return groups[0][1], lens                                           # one rate, no empty row: the buffer as it is
+    wav = torch.zeros(n, ld, dtype=torch.float32, device=dev)
+    for idx, part in groups:
+        rows = _pinned(np.asarray(idx, dtype=np.int64), dev)
+        wav[:, :part.shape[1]].index_copy_(0, rows, part)
+    return wav, lens
+
+
+def _spectrograms_on_device(wavs, do_trim, dev, sr, strict=True):
+    """get_spectrograms_device(trim_on='device'): (mag, frames int64 [n], bounds int64 [n, 2]) with the audio never back on the
+    host.  The one synchronisation is the copy of the n x 2 bounds, which sizes T_max (none at all without the trim).
+    strict=False: an utterance of fewer than 2 samples after trimming gets frames 0 and a zero row instead of the ValueError."""
+    wav, lens = _device_audio(wavs, sr, dev)
+    n, ld = int(wav.shape[0]), int(wav.shape[1])
+    ns = _pinned(lens, dev)
+    start = None
+    if do_trim:
+        bounds_d = trim_device(wav, ns)
+        bounds = bounds_d.cpu().numpy().astype(np.int64)                     # the synchronisation
+        start = bounds_d[:, 0].contiguous()
+        ns = (bounds_d[:, 1] - bounds_d[:, 0]).contiguous()
+    else:
+        bounds = np.stack([np.zeros(n, dtype=np.int64), lens.astype(np.int64)], axis=1)
+    kept = bounds[:, 1] - bounds[:, 0]
+    if strict and (kept < 2).any():
+        raise ValueError('utterance too short after trimming')
+    frames = np.where(kept < 2, 0, 1 + kept // hp.hop_length)
+    T_max = max(1, int(frames.max()))
+    mag = torch.zeros(n, T_max, 513, dtype=torch.float32, device=dev)
+    if (kept >= 2).any():
+        L.call('zs_pre_spectrogram', 'ZsPreSpec', torch.cuda.current_stream(dev).cuda_stream, wav=L.ptr(wav), wav_ld=ld,
+               n_samples=L.ptr(ns), n_utt=n, T_max=T_max, preemph=hp.preemphasis, ref_db=float(hp.ref_db), max_db=float(hp.max_db),
+               mag=L.ptr(mag), mag_ld=513, start=L.ptr(start))
+    return mag, frames, bounds
+
+
+def get_spectrograms_device(wavs, do_trim=True, device=None, sr=None, trim_on='host'):
     """The magnitudes of get_spectrograms_batch left on the device: (mag fp32 [n, T_max, 513] on `device`, frames int64 [n] host
-    array).  Utterance i is mag[i, :frames[i]]; the rows behind it are zeros.  No mel, no host copy.  No synchronisation either,
-    unless an input needs resampling (`sr` names a rate other than hp.sr): the resampled audio comes back to the host for the
-    trim, which synchronises once -- when, and only when, that is the case."""
+    array).  Utterance i is mag[i, :frames[i]]; the rows behind it are zeros.  No mel, no host copy.
+    trim_on='host' (default): the trim is host NumPy.  No synchronisation, unless an input needs resampling (`sr` names a rate
+    other than hp.sr): the resampled audio comes back to the host for the trim, which synchronises once.
+    trim_on='device': the same values, bit for bit, with the audio never back on the host -- resampled inputs stay in HBM, zs_trim
+    finds the bounds there, their n x 2 copy to the host (to size T_max) is the only synchronisation, and zs_pre_spectrogram reads
+    each trimmed window in place (ZsPreSpec.start)."""
     dev = _device_of(device)
+    if trim_on == 'device':
+        return _spectrograms_on_device(wavs, do_trim, dev, sr)[:2]
+    if trim_on != 'host':
+        raise ValueError("trim_on must be 'host' or 'device' (got %r)" % (trim_on,))
     mag, _, lens = _enqueue_spectrograms(_to_hp_sr(wavs, sr, dev), do_trim, dev, False)
     return mag, 1 + lens.astype(np.int64) // hp.hop_length
+
+
+def wav_info(sound_file):
+    """(sample rate, samples per channel) from the header of a RIFF wav file, without reading the audio.  ValueError for a file
+    that is not one."""
+    import struct
+    with open(sound_file, 'rb') as f:
+        head = f.read(12)
+        if len(head) < 12 or head[:4] != b'RIFF' or head[8:12] != b'WAVE':
+            raise ValueError('%s is not a RIFF/WAVE file' % sound_file)
+        fmt = None
+        while True:
+            ck = f.read(8)
+            if len(ck) < 8:
+                raise ValueError('%s has no data chunk' % sound_file)
+            tag, size = ck[:4], struct.unpack('<I', ck[4:])[0]
+            if tag == b'fmt ':
+                body = f.read(size + (size & 1))
+                if len(body) < 16:
+                    raise ValueError('%s has a truncated fmt chunk' % sound_file)
+                fmt = struct.unpack('<HHIIHH', body[:16])
+            elif tag == b'data':
+                if fmt is None or fmt[3] == 0 and fmt[4] == 0:
+                    raise ValueError('%s has no usable fmt chunk before its data' % sound_file)
+                block = fmt[4] if fmt[4] else max(1, fmt[1] * fmt[5] // 8)
+                return int(fmt[2]), int(size // block)
+            else:
+                f.seek(size + (size & 1), 1)
 
 
 def read_wav(sound_file):
