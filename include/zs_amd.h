@@ -66,10 +66,12 @@ const char* zs_last_error(void);
  *   "norm_lim2" (-, 64): longest T that zs_grad_combine runs in the 8 x 256 decomposition
  *   "gl_prefetch" (-, 1): Griffin-Lim waves request the next inverse frame's spectrum behind the current transform
  *   "gl_chains" (-, 3): independent launch chains of zs_griffin_lim (see there)
+ *   "adam_pack" (ZS_ADAM_PACK, 1): the counted optimizer step (NetOpt.device_step) runs zs_adam_pack; 0 = zs_adam_clip + re-pack
  * Stored values are normalised: gru_persist, gru_wide, norm_wide and gl_prefetch store v ? 1 : 0, gl_chains is clamped to [1, 4],
  * norm_lim0..2 store v, every other knob stores max(v, 0).  The knobs are process-wide atomics: they may be set from any thread; a
  * launch reads each knob once.  Returns the previous value, or ZS_EINVAL for an unknown key. */
 int zs_set_option(const char* key, int value);
+int zs_get_option(const char* key);                /* the stored value, or ZS_EINVAL for an unknown key */
 
 /* ---------------------------------------------------------------------------------------------
  * zs_gemm_conv: implicit-GEMM Conv1d / Linear / transposed-conv (data gradient) on MFMA.
@@ -475,6 +477,52 @@ typedef struct {
   int32_t max_blocks;            /* > 0: grid cap (see zs_pack_weight_batch); 0 = default */
 } ZsAdam;
 int zs_adam_clip(const ZsAdam* p, void* stream);
+
+/* zs_sqnorm_stage1: the first half of zs_sqnorm alone (per-workgroup double partials); returns how many partials it wrote
+ * (1..1024), or a negative error code.  zs_adam_pack can finish the sum itself (sq_partial). */
+int zs_sqnorm_stage1(const float* g, int64_t n, double* partial, void* stream);
+
+/* zs_adam_pack: zs_adam_clip over a net's whole flat buffer AND the re-pack of its GEMM operands, in one launch over one
+ * flat work list: every parameter is read once, updated, and its new value written to p and, rounded to the operand
+ * type, to every packed view of it -- zs_adam_clip + zs_pack_weight_batch + zs_copy_vec_batch without the re-read.  Only
+ * elements that come from a parameter are written to a view: the zero padding of an operand is written once by a full
+ * zs_pack_weight and stays.  The update is the expression zs_adam_clip compiles (bit-identical results).
+ * Jobs (sorted by `off`; together they must cover [0, a->n) exactly once -- the caller's plan checks that):
+ *   ZS_APJ_WEIGHT: the parameter W[Cout][Cin][taps] at p + off, dense (element strides (Cin*taps, taps, 1), taps <= 7).
+ *       A workgroup takes a block of 64 x 64 (taps 1) or 32 x 32|16 (bf16|fp32) x all taps (output rows x input channels)
+ *       through LDS.  co_split2: tile row n is parameter row co(n) as in ZsPackWeight (n is the row / inner index every
+ *       view is written at).  Views (n_views <= 2), for element (n, ci, j):
+ *         transpose 0: dst[(row + row_offset) * ldw + col_offset + slot(j) * inner_pad + ci], row = row_inv ? row_inv[co] : n
+ *         transpose 1: dst[(ci  + row_offset) * ldw + col_offset + slot(j) * inner_pad + n]
+ *       slot(j) = j, or with `parity` the stride-2 data gradient's tap order: j even ? j/2 : (taps+1)/2 + j/2.
+ *       row_inv (int32 [Cout], device) is the inverse of ZsPackWeight.row_perm.  dst_elems = elements of the operand type
+ *       that may be written from dst on (checked on the host against the largest index of the view).
+ *   ZS_APJ_VECTOR: Adam over [off, off + len) and up to two strided copies of the new values (re-ordered biases):
+ *       view c: dst (fp32) [i * ldw] = p[off + src_offset + i * src_stride] for i < vlen.
+ *   ZS_APJ_RANGE: plain Adam over [off, off + len), the code of zs_adam_clip.
+ * tile_start: the prefix sum of zs_adam_pack_tiles() over the jobs before this one (the caller fills it; checked).
+ * `jobs` is the list in host memory (checked on every call), `jobs_dev` the same bytes in device memory (read by the
+ * kernel: the list is too long for launch arguments); both stay alive and unchanged while launches may run or replay.
+ * sq_partial / n_partial: the partials of zs_sqnorm_stage1; every workgroup then sums them in the order of zs_sqnorm's
+ * second stage (the same float) and workgroup 0 stores it to a->sumsq; null: a->sumsq is read as zs_adam_clip reads it.
+ * a->max_blocks caps the grid as in zs_adam_clip.  dtype (ZS_F32 / ZS_BF16, of every view) is one for all jobs. */
+enum { ZS_APJ_WEIGHT = 0, ZS_APJ_VECTOR = 1, ZS_APJ_RANGE = 2 };
+typedef struct {
+  void* dst; int64_t ldw; int64_t dst_elems;
+  int32_t transpose, inner_pad, row_offset, col_offset, parity;
+  int32_t vlen, src_offset, src_stride;
+  const int32_t* row_inv;
+} ZsAdamPackView;
+typedef struct {
+  int32_t kind, dtype;
+  int64_t off, len;
+  int32_t Cout, Cin, taps, co_split2;
+  int32_t n_views, tile_start;
+  ZsAdamPackView view[2];
+} ZsAdamPackJob;
+int zs_adam_pack_tiles(const ZsAdamPackJob* job);
+int zs_adam_pack(const ZsAdam* a, const ZsAdamPackJob* jobs, const ZsAdamPackJob* jobs_dev, int32_t n, const double* sq_partial,
+                 int32_t n_partial, void* stream);
 
 /* zs_host_fetch: dst[0..bytes) = src[0..bytes) by a KERNEL that reads pinned (device-accessible) host memory over PCIe with
  * 16-byte loads, on a deliberately small grid (`workgroups`, 0 = 32; 8 loads in flight per lane cover the link's

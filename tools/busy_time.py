@@ -9,7 +9,7 @@ for r in rows:
     r['s'] = int(r['Start_Timestamp']); r['e'] = int(r['End_Timestamp'])
     r['n'] = re.sub(r'\(anonymous namespace\)::|void ', '', r['Kernel_Name']).split('(')[0]
 rows.sort(key=lambda r: r['s'])
-ad = [i for i, r in enumerate(rows) if r['n'].startswith('adam_kernel')]
+ad = [i for i, r in enumerate(rows) if r['n'].startswith(('adam_kernel', 'adam_pack_kernel'))]
 for k in ([int(sys.argv[2])] if len(sys.argv) > 2 else range(2, min(8, len(ad) // 2 - 2))):
     a, b = rows[ad[2 * k + 1]]['e'], rows[ad[2 * k + 3]]['e']
     sel = [r for r in rows if r['s'] >= a and r['e'] <= b]

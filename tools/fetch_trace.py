@@ -22,6 +22,6 @@ for f in fetch[-4:]:
         print('  before: %-36s ended %+8.3f ms' % (r['n'], (r['e'] - f['s']) / 1e6))
     for r in nxt:
         print('  after : %-36s starts %+8.3f ms after the fetch ends' % (r['n'], (r['s'] - f['e']) / 1e6))
-ad = [r for r in rows if r['n'].startswith('adam_kernel')]
+ad = [r for r in rows if r['n'].startswith(('adam_kernel', 'adam_pack_kernel'))]
 steps = [(ad[i + 2]['e'] - ad[i]['e']) / 1e6 for i in range(len(ad) - 2)][-8::2]
 print('step times (ms):', ['%.2f' % s for s in steps])

@@ -11,7 +11,7 @@ for r in rows:
     r['n'] = re.sub(r'\(anonymous namespace\)::|void ', '', r['Kernel_Name']).split('(')[0][:40]
     r['q'] = r.get('Queue_Id', r.get('Stream_Id', '?'))
 rows.sort(key=lambda r: r['s'])
-ad = [i for i, r in enumerate(rows) if r['n'].startswith('adam_kernel')]
+ad = [i for i, r in enumerate(rows) if r['n'].startswith(('adam_kernel', 'adam_pack_kernel'))]
 k = int(sys.argv[2]) if len(sys.argv) > 2 else max(1, len(ad) // 4)
 min_us = float(sys.argv[3]) if len(sys.argv) > 3 else 0.0
 a, b = rows[ad[2 * k + 1]]['e'], rows[ad[2 * k + 3]]['e']

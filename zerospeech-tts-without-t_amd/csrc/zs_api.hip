@@ -21,6 +21,13 @@ extern "C" int zs_set_option(const char* key, int value) {
   return ZS_EINVAL;
 }
 
+extern "C" int zs_get_option(const char* key) {
+  for (Knob* k = g_knobs; key && k; k = k->next)
+    if (!strcmp(k->key, key)) return k->get();
+  zs_set_error("zs_get_option: unknown key %s", key ? key : "(null)");
+  return ZS_EINVAL;
+}
+
 int zs_check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {

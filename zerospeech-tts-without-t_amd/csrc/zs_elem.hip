@@ -378,11 +378,13 @@ __global__ void sqnorm_stage2_kernel(const double* partial, int n, float* out) {
 }
 
 // ---- Adam + clip -------------------------------------------------------------------------------------
-__global__ void adam_kernel(const ZsAdam p) {
+// The update of one element: ONE function for adam_kernel and adam_pack_kernel, so that both compile the same expression.
+struct AdamCoef { float coef, step_size, bc2_sqrt, beta1, beta2, eps; };
+__device__ __forceinline__ AdamCoef adam_coef(const ZsAdam& p, const float* sumsq) {
   const float gs = p.grad_scale != 0.f ? p.grad_scale : 1.f;      // 1/world: g holds the SUM over the data-parallel ranks
   float coef = gs;
-  if (p.max_norm > 0.f && p.sumsq) {
-    const float norm = sqrtf(*p.sumsq) * gs;
+  if (p.max_norm > 0.f && sumsq) {
+    const float norm = sqrtf(*sumsq) * gs;
     coef = gs * fminf(p.max_norm / (norm + 1e-6f), 1.f);         // clip_grad_norm_
   }
   float bc1 = p.bc1, bc2 = p.bc2;
@@ -391,30 +393,196 @@ __global__ void adam_kernel(const ZsAdam p) {
     bc1 = 1.f - powf(p.beta1, t);
     bc2 = 1.f - powf(p.beta2, t);
   }
-  const float step_size = p.lr / bc1;
-  const float bc2_sqrt = sqrtf(bc2);
-  auto upd = [&](float& w, float& g, float& m, float& v) {
-    g *= coef;
-    m = m + (g - m) * (1.f - p.beta1);                           // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * p.beta2 + g * g * (1.f - p.beta2);                   // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
-    const float denom = sqrtf(v) / bc2_sqrt + p.eps;
-    w = w - step_size * (m / denom);
-  };
+  return AdamCoef{coef, p.lr / bc1, sqrtf(bc2), p.beta1, p.beta2, p.eps};
+}
+// Which products fuse with which sums is written out (and the compiler's own contraction is off inside): left to the compiler
+// it depends on the code around the call -- the 16-byte loop fused as below, the one-element loop fused nothing in m and v --
+// and a tile of zs_adam_pack must give the bits the flat loop of zs_adam_clip gives.  These are the fusions of that 16-byte
+// loop, the only one a flat parameter buffer (16-byte aligned, a multiple of 4 elements) ever ran.
+__device__ __forceinline__ void adam_upd(const AdamCoef& c, float& w, float& g, float& m, float& v) {
+#pragma clang fp contract(off)
+  const float d = __builtin_fmaf(g, c.coef, -m);                 // g - m of the scaled gradient, one rounding
+  g = g * c.coef;
+  m = __builtin_fmaf(d, 1.f - c.beta1, m);                       // exp_avg.lerp_(grad, 1 - beta1)
+  v = __builtin_fmaf(g * g, 1.f - c.beta2, v * c.beta2);         // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
+  const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
+  w = __builtin_fmaf(-c.step_size, m / denom, w);
+}
+__device__ __forceinline__ void adam_upd4(const ZsAdam& p, const AdamCoef& c, int64_t i, float4& w) {     // float4 index i
+  float4 g = reinterpret_cast<float4*>(p.g)[i], m = reinterpret_cast<float4*>(p.m)[i], v = reinterpret_cast<float4*>(p.v)[i];
+  w = reinterpret_cast<float4*>(p.p)[i];
+  adam_upd(c, w.x, g.x, m.x, v.x); adam_upd(c, w.y, g.y, m.y, v.y); adam_upd(c, w.z, g.z, m.z, v.z); adam_upd(c, w.w, g.w, m.w, v.w);
+  reinterpret_cast<float4*>(p.p)[i] = w; reinterpret_cast<float4*>(p.m)[i] = m; reinterpret_cast<float4*>(p.v)[i] = v;
+  if (p.write_clipped_grad) reinterpret_cast<float4*>(p.g)[i] = g;
+}
+__device__ __forceinline__ float adam_upd1(const ZsAdam& p, const AdamCoef& c, int64_t i) {
+  float w = p.p[i], g = p.g[i], m = p.m[i], v = p.v[i];
+  adam_upd(c, w, g, m, v);
+  p.p[i] = w; p.m[i] = m; p.v[i] = v;
+  if (p.write_clipped_grad) p.g[i] = g;
+  return w;
+}
+__device__ __forceinline__ bool adam_aligned16(const ZsAdam& p) {
+  return ((((uintptr_t)p.p) | ((uintptr_t)p.g) | ((uintptr_t)p.m) | ((uintptr_t)p.v)) & 15) == 0;
+}
+
+__global__ void adam_kernel(const ZsAdam p) {
+  const AdamCoef c = adam_coef(p, p.sumsq);
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-  const bool vec = ((((uintptr_t)p.p) | ((uintptr_t)p.g) | ((uintptr_t)p.m) | ((uintptr_t)p.v)) & 15) == 0;
-  const int64_t n4 = vec ? p.n / 4 : 0;
+  const int64_t n4 = adam_aligned16(p) ? p.n / 4 : 0;
   for (int64_t i = tid; i < n4; i += nthr) {                     // 16-byte accesses: four streams of 64 B per lane in flight
-    float4 w = reinterpret_cast<float4*>(p.p)[i], g = reinterpret_cast<float4*>(p.g)[i];
-    float4 m = reinterpret_cast<float4*>(p.m)[i], v = reinterpret_cast<float4*>(p.v)[i];
-    upd(w.x, g.x, m.x, v.x); upd(w.y, g.y, m.y, v.y); upd(w.z, g.z, m.z, v.z); upd(w.w, g.w, m.w, v.w);
-    reinterpret_cast<float4*>(p.p)[i] = w; reinterpret_cast<float4*>(p.m)[i] = m; reinterpret_cast<float4*>(p.v)[i] = v;
-    if (p.write_clipped_grad) reinterpret_cast<float4*>(p.g)[i] = g;
+    float4 w;
+    adam_upd4(p, c, i, w);
   }
-  for (int64_t i = 4 * n4 + tid; i < p.n; i += nthr) {
-    float w = p.p[i], g = p.g[i], m = p.m[i], v = p.v[i];
-    upd(w, g, m, v);
-    p.p[i] = w; p.m[i] = m; p.v[i] = v;
-    if (p.write_clipped_grad) p.g[i] = g;
+  for (int64_t i = 4 * n4 + tid; i < p.n; i += nthr) adam_upd1(p, c, i);
+}
+
+// ---- Adam + clip + re-pack in one pass (zs_adam_pack) ---------------------------------------------------
+// One flat tile list over the jobs, as pack_weight_batch_kernel walks one; the jobs live in device memory.  A weight tile is
+// CB tile rows (output channels) x IB input channels x all taps: the source run that is contiguous in memory is (ci, tap) of one
+// output channel (IB * TAPS floats), the destination runs are IB elements (transpose 0) and CB elements (transpose 1), each at
+// least 64 bytes.  The tile is kept in LDS in the operand type (the value every view stores), within PK_LDS_BYTES.
+constexpr int AP_THREADS = 256, AP_MAX_JOBS = 256, AP_RANGE_TILE = 4096, AP_VEC_TILE = 1024;
+template <typename T, int TAPS> struct ApTile {
+  static constexpr int CB = TAPS == 1 ? 64 : 32;
+  static constexpr int IB = TAPS == 1 ? 64 : (sizeof(T) == 2 ? 32 : 16);
+  static constexpr int RUN = IB * TAPS;
+  static constexpr int PITCH = RUN + (sizeof(T) == 2 ? 2 : 1);      // an odd number of 4-byte words: the transposed read walks rows
+  static_assert((size_t)CB * PITCH * sizeof(T) <= PK_LDS_BYTES, "adam_pack tile exceeds the pack kernels' LDS");
+};
+__host__ __device__ inline int ap_cb(int taps) { return taps == 1 ? 64 : 32; }
+__host__ __device__ inline int ap_ib(int taps, int dtype) { return taps == 1 ? 64 : (dtype == ZS_BF16 ? 32 : 16); }
+inline int64_t ap_tiles(const ZsAdamPackJob& j) {
+  if (j.kind == ZS_APJ_WEIGHT) {
+    const int cb = ap_cb(j.taps), ib = ap_ib(j.taps, j.dtype);
+    return (int64_t)((j.Cout + cb - 1) / cb) * ((j.Cin + ib - 1) / ib);
+  }
+  const int t = j.kind == ZS_APJ_VECTOR ? AP_VEC_TILE : AP_RANGE_TILE;
+  return (j.len + t - 1) / t;
+}
+
+template <typename T, int TAPS>
+__device__ __forceinline__ void ap_weight_tile(const ZsAdam& a, const AdamCoef& c, const ZsAdamPackJob& job, int tile, T* lds) {
+  using G = ApTile<T, TAPS>;
+  constexpr int CB = G::CB, IB = G::IB, RUN = G::RUN, PITCH = G::PITCH;
+  const int tid = threadIdx.x;
+  const int tiles_i = (job.Cin + IB - 1) / IB;
+  const int tn = tile / tiles_i, ti = tile - tn * tiles_i;
+  const int n0 = tn * CB, i0 = ti * IB;
+  const int half = job.Cout >> 1, split2 = job.co_split2;
+  const int rows = min(CB, job.Cout - n0), cis = min(IB, job.Cin - i0), runw = cis * TAPS;
+  const int64_t row_len = (int64_t)job.Cin * TAPS;
+  const int64_t base = job.off + (int64_t)i0 * TAPS;
+  auto co_of = [&](int n) { return split2 ? (n < half ? 2 * n : 2 * (n - half) + 1) : n; };
+  if (adam_aligned16(a) && ((row_len | job.off) & 3) == 0) {       // every run starts and ends on 16 bytes
+    constexpr int R4 = RUN / 4;
+    for (int e = tid; e < CB * R4; e += AP_THREADS) {
+      const int rl = e / R4, x = (e - rl * R4) * 4;
+      if (rl < rows && x < runw) {
+        float4 w;
+        adam_upd4(a, c, (base + (int64_t)co_of(n0 + rl) * row_len + x) >> 2, w);
+        T* d = lds + rl * PITCH + x;
+        Elem<T>::st(d, w.x); Elem<T>::st(d + 1, w.y); Elem<T>::st(d + 2, w.z); Elem<T>::st(d + 3, w.w);
+      }
+    }
+  } else {
+    for (int e = tid; e < CB * RUN; e += AP_THREADS) {
+      const int rl = e / RUN, x = e - rl * RUN;
+      if (rl < rows && x < runw) Elem<T>::st(lds + rl * PITCH + x, adam_upd1(a, c, base + (int64_t)co_of(n0 + rl) * row_len + x));
+    }
+  }
+  __syncthreads();
+  for (int vi = 0; vi < job.n_views; ++vi) {
+    const ZsAdamPackView& v = job.view[vi];
+    T* const dst = (T*)v.dst + v.col_offset;
+    const int ne = (TAPS + 1) / 2;
+    if (v.transpose == 0) {
+#pragma unroll 4
+      for (int e = tid; e < CB * TAPS * IB; e += AP_THREADS) {
+        const int il = e % IB, t2 = e / IB;
+        const int tap = t2 % TAPS, rl = t2 / TAPS;
+        if (rl < rows && il < cis) {
+          const int n = n0 + rl;
+          const int row = v.row_inv ? v.row_inv[co_of(n)] : n;
+          const int slot = v.parity ? ((tap & 1) ? ne + (tap >> 1) : (tap >> 1)) : tap;
+          dst[(int64_t)(row + v.row_offset) * v.ldw + slot * v.inner_pad + i0 + il] = lds[rl * PITCH + il * TAPS + tap];
+        }
+      }
+    } else {
+#pragma unroll 4
+      for (int e = tid; e < IB * TAPS * CB; e += AP_THREADS) {
+        const int nl = e % CB, t2 = e / CB;
+        const int tap = t2 % TAPS, il = t2 / TAPS;
+        if (nl < rows && il < cis) {
+          const int slot = v.parity ? ((tap & 1) ? ne + (tap >> 1) : (tap >> 1)) : tap;
+          dst[(int64_t)(i0 + il + v.row_offset) * v.ldw + slot * v.inner_pad + n0 + nl] = lds[nl * PITCH + il * TAPS + tap];
+        }
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ void ap_range_tile(const ZsAdam& a, const AdamCoef& c, const ZsAdamPackJob& job, int tile) {
+  const int64_t lo = job.off + (int64_t)tile * AP_RANGE_TILE;
+  const int cnt = (int)min((int64_t)AP_RANGE_TILE, job.off + job.len - lo);
+  const int n4 = (adam_aligned16(a) && (lo & 3) == 0) ? cnt / 4 : 0;
+  for (int i = threadIdx.x; i < n4; i += AP_THREADS) {
+    float4 w;
+    adam_upd4(a, c, (lo >> 2) + i, w);
+  }
+  for (int i = 4 * n4 + threadIdx.x; i < cnt; i += AP_THREADS) adam_upd1(a, c, lo + i);
+}
+
+__device__ __forceinline__ void ap_vector_tile(const ZsAdam& a, const AdamCoef& c, const ZsAdamPackJob& job, int tile) {
+  const int lo = tile * AP_VEC_TILE;
+  const int hi = (int)min((int64_t)lo + AP_VEC_TILE, job.len);
+  for (int e = lo + threadIdx.x; e < hi; e += AP_THREADS) {
+    const float w = adam_upd1(a, c, job.off + e);
+    for (int vi = 0; vi < job.n_views; ++vi) {
+      const ZsAdamPackView& v = job.view[vi];
+      const int r = e - v.src_offset;
+      if (r >= 0 && r % v.src_stride == 0 && r / v.src_stride < v.vlen) ((float*)v.dst)[(int64_t)(r / v.src_stride) * v.ldw] = w;
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(AP_THREADS) void adam_pack_kernel(const ZsAdam a, const ZsAdamPackJob* __restrict__ jobs, int n_jobs, int total,
+                                                                const double* __restrict__ part, int n_part) {
+  __shared__ int s_start[AP_MAX_JOBS + 1];
+  __shared__ double s_red[4];
+  __shared__ float s_sq;
+  __shared__ __align__(16) unsigned char s_tile[PK_LDS_BYTES];
+  const int tid = threadIdx.x;
+  for (int i = tid; i <= n_jobs; i += AP_THREADS) s_start[i] = i < n_jobs ? jobs[i].tile_start : total;
+  if (part) {                                                    // the second stage of zs_sqnorm: its code and order in every workgroup
+    double s = 0.0;
+    for (int i = tid; i < n_part; i += AP_THREADS) s += part[i];
+    s = wave_sum_d(s);
+    if ((tid & 63) == 0) s_red[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) {
+      s_sq = (float)(s_red[0] + s_red[1] + s_red[2] + s_red[3]);
+      if (blockIdx.x == 0 && a.sumsq) *const_cast<float*>(a.sumsq) = s_sq;
+    }
+  }
+  __syncthreads();
+  const AdamCoef c = adam_coef(a, part ? &s_sq : a.sumsq);
+  for (int g = blockIdx.x; g < total; g += gridDim.x) {
+    int lo = 0, hi = n_jobs;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_start[mid] <= g) lo = mid; else hi = mid; }
+    lo = __builtin_amdgcn_readfirstlane(lo);                     // (block-uniform: the job is read with scalar loads)
+    const ZsAdamPackJob& job = jobs[lo];
+    const int tile = g - s_start[lo];
+    if (job.kind == ZS_APJ_RANGE) ap_range_tile(a, c, job, tile);
+    else if (job.kind == ZS_APJ_VECTOR) ap_vector_tile(a, c, job, tile);
+    else {
+      T* lds = reinterpret_cast<T*>(s_tile);
+#define ZS_AP_CASE(K) case K: ap_weight_tile<T, K>(a, c, job, tile, lds); break;
+      switch (job.taps) { ZS_AP_CASE(1) ZS_AP_CASE(2) ZS_AP_CASE(3) ZS_AP_CASE(4) ZS_AP_CASE(5) ZS_AP_CASE(6) ZS_AP_CASE(7) default: break; }
+#undef ZS_AP_CASE
+    }
+    __syncthreads();
   }
 }
 
@@ -648,13 +816,19 @@ extern "C" int zs_l1_loss(const ZsL1Loss* p, void* stream) {
   return zs_check_launch("zs_l1_loss.stage2");
 }
 
-extern "C" int zs_sqnorm(const float* g, int64_t n, double* partial, float* out_sq, void* stream) {
-  ZS_REQUIRE(g && partial && out_sq && n > 0, "zs_sqnorm: bad args");
+extern "C" int zs_sqnorm_stage1(const float* g, int64_t n, double* partial, void* stream) {
+  ZS_REQUIRE(g && partial && n > 0, "zs_sqnorm: bad args");
   const unsigned nb = nblocks(n, 1024);
   hipLaunchKernelGGL(sqnorm_stage1_kernel, dim3(nb), dim3(NTE), 0, (hipStream_t)stream, g, n, partial);
   int rc = zs_check_launch("zs_sqnorm.stage1");
-  if (rc) return rc;
-  hipLaunchKernelGGL(sqnorm_stage2_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partial, (int)nb, out_sq);
+  return rc ? rc : (int)nb;
+}
+
+extern "C" int zs_sqnorm(const float* g, int64_t n, double* partial, float* out_sq, void* stream) {
+  ZS_REQUIRE(out_sq, "zs_sqnorm: bad args");
+  const int nb = zs_sqnorm_stage1(g, n, partial, stream);
+  if (nb < 0) return nb;
+  hipLaunchKernelGGL(sqnorm_stage2_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partial, nb, out_sq);
   return zs_check_launch("zs_sqnorm.stage2");
 }
 
@@ -665,6 +839,75 @@ extern "C" int zs_adam_clip(const ZsAdam* p, void* stream) {
   if (p->max_blocks > 0 && nb > (unsigned)p->max_blocks) nb = (unsigned)p->max_blocks;
   hipLaunchKernelGGL(adam_kernel, dim3(nb), dim3(NTE), 0, (hipStream_t)stream, *p);
   return zs_check_launch("zs_adam_clip");
+}
+
+// "adam_pack": read by the optimizer's host side (NetOpt.device_step), which chooses between zs_adam_pack and the separate launches
+Knob g_adam_pack("adam_pack", "ZS_ADAM_PACK", 1);
+
+static int adam_pack_check(const ZsAdam* a, const ZsAdamPackJob& j, int i) {
+  ZS_REQUIRE(j.off >= 0 && j.len > 0 && j.off + j.len <= a->n, "zs_adam_pack: job %d covers [%lld, +%lld) of %lld elements", i,
+             (long long)j.off, (long long)j.len, (long long)a->n);
+  ZS_REQUIRE(j.n_views >= 0 && j.n_views <= 2, "zs_adam_pack: job %d has %d views", i, j.n_views);
+  if (j.kind == ZS_APJ_RANGE) return ZS_OK;
+  if (j.kind == ZS_APJ_VECTOR) {
+    ZS_REQUIRE(j.len < (1ll << 30), "zs_adam_pack: vector job %d too long", i);
+    for (int k = 0; k < j.n_views; ++k) {
+      const ZsAdamPackView& v = j.view[k];
+      ZS_REQUIRE(v.dst && v.vlen > 0 && v.src_stride > 0 && v.src_offset >= 0 && v.ldw > 0 &&
+                     v.src_offset + (int64_t)(v.vlen - 1) * v.src_stride < j.len && (int64_t)(v.vlen - 1) * v.ldw < v.dst_elems,
+                 "zs_adam_pack: vector job %d, copy %d out of range", i, k);
+    }
+    return ZS_OK;
+  }
+  ZS_REQUIRE(j.kind == ZS_APJ_WEIGHT, "zs_adam_pack: job %d: bad kind %d", i, j.kind);
+  ZS_REQUIRE(j.Cout > 0 && j.Cin > 0 && j.taps >= 1 && j.taps <= PK_MAX_TAPS && (int64_t)j.Cout * j.Cin * j.taps == j.len,
+             "zs_adam_pack: weight job %d: %d x %d x %d taps over %lld elements", i, j.Cout, j.Cin, j.taps, (long long)j.len);
+  ZS_REQUIRE(!j.co_split2 || j.Cout % 2 == 0, "zs_adam_pack: SPLIT2 needs even Cout");
+  for (int k = 0; k < j.n_views; ++k) {
+    const ZsAdamPackView& v = j.view[k];
+    const int inner = v.transpose ? j.Cout : j.Cin, rows = v.transpose ? j.Cin : j.Cout;
+    ZS_REQUIRE(v.dst && v.inner_pad >= inner && v.row_offset >= 0 && v.col_offset >= 0 &&
+                   v.ldw >= (int64_t)v.col_offset + (int64_t)j.taps * v.inner_pad &&
+                   (int64_t)(rows + v.row_offset) * v.ldw <= v.dst_elems,
+               "zs_adam_pack: weight job %d, view %d: %d rows x %d taps x inner %d do not fit (ldw %lld, %lld elements)", i, k,
+               rows + v.row_offset, j.taps, v.inner_pad, (long long)v.ldw, (long long)v.dst_elems);
+    ZS_REQUIRE(!v.row_inv || (!v.transpose && !j.co_split2), "zs_adam_pack: row_inv goes with a transpose-0 view without SPLIT2");
+  }
+  return ZS_OK;
+}
+
+extern "C" int zs_adam_pack_tiles(const ZsAdamPackJob* job) {
+  ZS_REQUIRE(job && job->len > 0 && (job->kind != ZS_APJ_WEIGHT || (job->Cout > 0 && job->Cin > 0 && job->taps >= 1)),
+             "zs_adam_pack_tiles: bad job");
+  const int64_t t = ap_tiles(*job);
+  ZS_REQUIRE(t < (1ll << 30), "zs_adam_pack_tiles: too many tiles");
+  return (int)t;
+}
+
+extern "C" int zs_adam_pack(const ZsAdam* a, const ZsAdamPackJob* jobs, const ZsAdamPackJob* jobs_dev, int32_t n, const double* sq_partial,
+                            int32_t n_partial, void* stream) {
+  ZS_REQUIRE(a && a->p && a->g && a->m && a->v && a->n > 0, "zs_adam_pack: bad args");
+  ZS_REQUIRE(a->step_ptr || (a->bc1 > 0.f && a->bc2 > 0.f), "zs_adam_pack: bias corrections");
+  ZS_REQUIRE(jobs && jobs_dev && n > 0 && n <= AP_MAX_JOBS, "zs_adam_pack: 1..%d jobs", AP_MAX_JOBS);
+  ZS_REQUIRE(!sq_partial || (n_partial > 0 && n_partial <= 1024 && a->sumsq), "zs_adam_pack: 1..1024 partials and sumsq");
+  int64_t total = 0, end = 0;
+  for (int i = 0; i < n; ++i) {
+    const ZsAdamPackJob& j = jobs[i];
+    ZS_REQUIRE(j.dtype == jobs[0].dtype && (j.dtype == ZS_F32 || j.dtype == ZS_BF16), "zs_adam_pack: dtype of job %d", i);
+    int rc = adam_pack_check(a, j, i);
+    if (rc) return rc;
+    ZS_REQUIRE(j.off >= end, "zs_adam_pack: job %d overlaps its predecessor", i);       // sorted, disjoint (the plan checks the cover)
+    end = j.off + j.len;
+    ZS_REQUIRE(j.tile_start == total, "zs_adam_pack: job %d: tile_start %d, expected %lld", i, j.tile_start, (long long)total);
+    total += ap_tiles(j);
+    ZS_REQUIRE(total < (1ll << 30), "zs_adam_pack: too many tiles");
+  }
+  const unsigned gx = (unsigned)((a->max_blocks > 0 && total > a->max_blocks) ? a->max_blocks : total);
+  if (jobs[0].dtype == ZS_F32)
+    hipLaunchKernelGGL(adam_pack_kernel<float>, dim3(gx), dim3(AP_THREADS), 0, (hipStream_t)stream, *a, jobs_dev, (int)n, (int)total, sq_partial, (int)n_partial);
+  else
+    hipLaunchKernelGGL(adam_pack_kernel<bf16_t>, dim3(gx), dim3(AP_THREADS), 0, (hipStream_t)stream, *a, jobs_dev, (int)n, (int)total, sq_partial, (int)n_partial);
+  return zs_check_launch("zs_adam_pack");
 }
 
 extern "C" int zs_host_fetch(const void* src, void* dst, size_t bytes, int32_t workgroups, void* stream) {

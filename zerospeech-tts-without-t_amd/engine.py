@@ -11,7 +11,7 @@ import torch
 
 from . import _lib as L
 from .layers import (Act, ConvLayer, GruLayer, cast_rows, colsum_ok, fork_side, grad_combine, instnorm_bwd, instnorm_fwd, join_side,
-                     next_uid, rup)
+                     next_uid, pack_operands, rup, weight_operand)
 
 LRELU = L.ZS_ACT_LRELU
 
@@ -47,6 +47,16 @@ def linear_width(enc_mode, E):
     return {'multilabel_binary': 2 * E, 'binary': E * E}.get(enc_mode, E)
 
 
+def operands_of(layers):
+    """(weights, vectors): the operands() of several layers joined."""
+    w, v = [], []
+    for l in layers:
+        lw, lv = l.operands()
+        w += lw
+        v += lv
+    return w, v
+
+
 class EncoderEngine(object):
     def __init__(self, ctx, P, G, c_in, c_h1, c_h2, c_h3, enc_size, ns, dp, seg_len, enc_mode='multilabel_binary'):
         """P / G: dicts name -> fp32 parameter / gradient tensors (reference state_dict names)."""
@@ -72,14 +82,19 @@ class EncoderEngine(object):
         self.tape = None
         self.tapes = {}
         self.bank_d = None            # the bank's data-gradient operand (backward_input), packed on first use after pack()
+        self.adam_plan = None         # optim.AdamPackPlan of this engine's operands (ZsModule.adam_pack_plan)
+
+    def operands(self):
+        """(weights, vectors) of every layer (layers.weight_operand / vector_operand): the one description that pack() and the
+        fused optimizer step's plan (optim.AdamPackPlan) are built from."""
+        w, v = operands_of(self.layers + [self.gru])
+        if self.bank_d is not None:
+            w += self._bank_d_operands()
+        return w, v
 
     def pack(self):
         with L.pack_batch(self.ctx.stream):
-            for l in self.layers:
-                l.pack()
-            self.gru.pack()
-            if self.bank_d is not None:
-                self._pack_bank_d()
+            pack_operands(self.ctx, *self.operands())
 
     # ------------------------------------------------------------------------------------------
     def forward(self, x, training, noise=None, noise_kind=2, seed=0, drop_masks=None, seed_ptr=None, lengths=None, tape=None):
@@ -285,18 +300,20 @@ class EncoderEngine(object):
     # 3/3-padded domain, and one fold (zs_enc_dx_fold) that adds the padding rows back and the pass-through columns.
     BANK_PAD = 3
 
-    def _pack_bank_d(self):
+    def _bank_d_operands(self):
         """The transposed operand of the bank's 7-tap data gradient: rows = c_in (padded to 128), K = 7 slots x cp (cp = 7*c_h1
-        padded to the K chunk); slot s of kernel i (k = i + 1) holds its tap j = s - 3 + k//2 in columns [s*cp + i*c_h1, +c_h1)."""
+        padded to the K chunk); slot s of kernel i (k = i + 1) holds its tap j = s - 3 + k//2 in columns [s*cp + i*c_h1, +c_h1).
+        One single-tap column block per (kernel, tap): no whole-parameter view, so `raw` pack jobs beside the layers' own."""
         c, c1 = self.ctx, self.c1
         ld, cp = self.bank_d_ld, self.bank_d_cp
+        ops = []
         for i, l in enumerate(self.conv1s):
             k = l.k
-            for j in range(k):
-                s = j + self.BANK_PAD - k // 2
-                L.call('zs_pack_weight', 'ZsPackWeight', c.stream, dtype=c.dt, W=L.ptr(l.w, j), so=self.c_in * k, si=k, sj=1,
-                       Cout=c1, Cin=self.c_in, taps=1, transpose=1, co_split2=0, inner_pad=c1, dst=L.ptr(self.bank_d), ldw=ld,
-                       n_rows=self.bank_d_rows, n_cols=c1, row_offset=0, col_offset=s * cp + i * c1)
+            raw = [dict(dtype=c.dt, W=L.ptr(l.w, j), so=self.c_in * k, si=k, sj=1, Cout=c1, Cin=self.c_in, taps=1, transpose=1,
+                        co_split2=0, inner_pad=c1, dst=L.ptr(self.bank_d), ldw=ld, n_rows=self.bank_d_rows, n_cols=c1, row_offset=0,
+                        col_offset=(j + self.BANK_PAD - k // 2) * cp + i * c1) for j in range(k)]
+            ops.append(weight_operand(l.w, c1, self.c_in, k, (self.c_in * k, k, 1), [], raw=raw))
+        return ops
 
     def _bank_operand(self):
         if self.bank_d is None:
@@ -305,8 +322,9 @@ class EncoderEngine(object):
             self.bank_d_ld = 7 * self.bank_d_cp
             self.bank_d_rows = rup(self.c_in, 128)
             self.bank_d = torch.zeros(self.bank_d_rows * self.bank_d_ld + 512, dtype=c.tdt, device=c.device)
+            self.adam_plan = None                    # the optimizer's plan must re-pack this operand too
             with L.pack_batch(c.stream):
-                self._pack_bank_d()                  # from now on pack() re-packs it with the other operands
+                pack_operands(c, self._bank_d_operands(), [])        # from now on pack() re-packs it with the other operands
         return self.bank_d
 
     def backward_input(self, dbits=None, dlogits=None, tape=None):
@@ -364,11 +382,13 @@ class DecoderEngine(object):
             [self.dense5, self.linear]
         self.tape = None
 
+    def operands(self):
+        """(weights, vectors) of every layer: the one description of pack() and of the fused optimizer step's plan."""
+        return operands_of(self.layers + [self.gru])
+
     def pack(self):
         with L.pack_batch(self.ctx.stream):
-            for l in self.layers:
-                l.pack()
-            self.gru.pack()
+            pack_operands(self.ctx, *self.operands())
 
     def forward(self, bits, cidx, training, lengths=None):
         """bits: Act [B,T',E] (T dtype, zero padded); cidx int64 [B].  Returns x_dec Act fp32 [B, 8T', F].
@@ -633,10 +653,13 @@ class ClassifierEngine(object):
         self.layers = [l for b in self.blocks for l in b[:2]] + [self.conv9]
         self.tape = None
 
+    def operands(self):
+        """(weights, vectors) of every layer: the one description of pack() and of the fused optimizer step's plan."""
+        return operands_of(self.layers)
+
     def pack(self):
         with L.pack_batch(self.ctx.stream):
-            for l in self.layers:
-                l.pack()
+            pack_operands(self.ctx, *self.operands())
 
     def forward(self, x, training, seed=0, drop_masks=None):
         """x: Act [B, T', c_in] in the compute dtype.  Returns logits Act fp32 [B, 1, n_class]."""

@@ -212,6 +212,66 @@ class Ctx(object):
         check_status(self.device)
 
 
+# ---- packed operands as data ------------------------------------------------------------------------------------------
+# A layer describes the packed views of its parameters once (operands()); the full pack (zs_pack_weight) and the plan of the
+# fused optimizer step (zs_adam_pack, zs_amd.optim) are both built from that description.
+def weight_view(dst, transpose, inner_pad, ldw, n_rows, n_cols, dst_off=0, row_offset=0, col_offset=0, parity=False, row_perm=None):
+    """One packed view of a weight: the n_rows x n_cols block of `dst` (from element dst_off, pitch ldw) at (row_offset,
+    col_offset), as ZsPackWeight describes it.  parity: the taps in the stride-2 data gradient's order [0, 2, 4, .. | 1, 3, ..]."""
+    return dict(dst=dst, dst_off=dst_off, transpose=transpose, inner_pad=inner_pad, ldw=ldw, n_rows=n_rows, n_cols=n_cols,
+                row_offset=row_offset, col_offset=col_offset, parity=parity, row_perm=row_perm)
+
+
+def weight_operand(w, Cout, Cin, taps, strides, views, co_split2=0, raw=None):
+    """A parameter `w` [Cout, Cin, taps] (element strides so, si, sj) and its packed views.  raw: ZsPackWeight keyword sets for
+    views that are no whole-parameter view (the fused optimizer step re-packs those with zs_pack_weight behind its launch)."""
+    return dict(w=w, Cout=Cout, Cin=Cin, taps=taps, strides=tuple(strides), views=views, co_split2=int(co_split2), raw=raw or [])
+
+
+def vector_operand(src, copies):
+    """A bias `src` and its re-ordered copies: dicts(dst, dst_off, n, src_offset, src_stride), dst[dst_off + i] = src[src_offset + i * src_stride]."""
+    return dict(src=src, copies=copies)
+
+
+def pack_operands(ctx, weights, vectors):
+    """The full pack of the described operands, zero padding included (inside a pack_batch: one batched launch)."""
+    st = ctx.stream
+    for op in weights:
+        so, si, sj = op['strides']
+        common = dict(dtype=ctx.dt, so=so, si=si, Cout=op['Cout'], Cin=op['Cin'], co_split2=op['co_split2'])
+        for v in op['views']:
+            kw = dict(common, transpose=v['transpose'], inner_pad=v['inner_pad'], dst=L.ptr(v['dst'], v['dst_off']), ldw=v['ldw'],
+                      n_rows=v['n_rows'], row_offset=v['row_offset'], row_perm=L.ptr(v['row_perm']))
+            if v['parity']:
+                # stride 2: taps in parity order [j = 0, 2, 4, .. | j = 1, 3, ..] (see dgrad): two strided views of the parameter
+                ne, no = (op['taps'] + 1) // 2, op['taps'] // 2
+                L.call('zs_pack_weight', 'ZsPackWeight', st, W=L.ptr(op['w']), sj=2 * sj, taps=ne, n_cols=ne * v['inner_pad'],
+                       col_offset=v['col_offset'], **kw)
+                L.call('zs_pack_weight', 'ZsPackWeight', st, W=L.ptr(op['w'], sj), sj=2 * sj, taps=no, n_cols=no * v['inner_pad'],
+                       col_offset=v['col_offset'] + ne * v['inner_pad'], **kw)
+            else:
+                L.call('zs_pack_weight', 'ZsPackWeight', st, W=L.ptr(op['w']), sj=sj, taps=op['taps'], n_cols=v['n_cols'],
+                       col_offset=v['col_offset'], **kw)
+        for kw in op['raw']:
+            L.call('zs_pack_weight', 'ZsPackWeight', st, **kw)
+    for vc in vectors:
+        for cp in vc['copies']:
+            L.vec_copy(cp['dst'][cp['dst_off']:cp['dst_off'] + cp['n']], vc['src'][cp['src_offset']:], st, src_stride=cp['src_stride'],
+                       n=cp['n'])
+
+
+class PlanCtx(object):
+    """A context that only carries the compute dtype: layers built with it allocate on the meta device, so the packed layout of a
+    net (operands()) and the plan of its fused optimizer step can be computed from parameter shapes alone, without a GPU."""
+
+    def __init__(self, dtype='bf16'):
+        self.device = torch.device('meta')
+        self.dtype_name = dtype
+        self.dt, self.tdt = DTYPES[dtype]
+        self.es = 4 if dtype == 'fp32' else 2
+        self.kc = 128 // self.es
+
+
 class ConvLayer(object):
     """Conv1d [Cout,Cin,k] or Linear [Cout,Cin] (k=1) as packed MFMA operands.
     split2: output channels packed so that the epilogue can pixel-shuffle (see zs_amd.h)."""
@@ -247,28 +307,20 @@ class ConvLayer(object):
         """The layer of parameters name.weight / name.bias in the dicts P (values) and G (gradients)."""
         return cls(ctx, P[name + '.weight'], P[name + '.bias'], G[name + '.weight'], G[name + '.bias'], pad_mode=pad_mode, name=name, **kw)
 
-    def pack(self):
-        c = self.ctx
-        common = dict(dtype=c.dt, W=L.ptr(self.w), so=self.so, si=self.si, sj=self.sj, Cout=self.Cout, Cin=self.Cin,
-                      taps=self.k, co_split2=int(self.split2))
-        L.call('zs_pack_weight', 'ZsPackWeight', c.stream, transpose=0, inner_pad=self.cin_pad, dst=L.ptr(self.wf),
-               ldw=self.ldw, n_rows=self.n_pad, n_cols=self.ldw, **common)
-        if self.parity:
-            # stride 2: taps in parity order [j = 0, 2, 4, .. | j = 1, 3, ..] (see dgrad): two strided views of the parameter
-            ne, no = (self.k + 1) // 2, self.k // 2
-            ev = dict(common, taps=ne, sj=2 * self.sj)
-            od = dict(common, taps=no, sj=2 * self.sj, W=L.ptr(self.w, self.sj))
-            L.call('zs_pack_weight', 'ZsPackWeight', c.stream, transpose=1, inner_pad=self.cout_pad, dst=L.ptr(self.wd),
-                   ldw=self.ldw_d, n_rows=self.n_pad_d, n_cols=ne * self.cout_pad, **ev)
-            L.call('zs_pack_weight', 'ZsPackWeight', c.stream, transpose=1, inner_pad=self.cout_pad, dst=L.ptr(self.wd),
-                   ldw=self.ldw_d, n_rows=self.n_pad_d, n_cols=no * self.cout_pad, col_offset=ne * self.cout_pad, **od)
-        else:
-            L.call('zs_pack_weight', 'ZsPackWeight', c.stream, transpose=1, inner_pad=self.cout_pad, dst=L.ptr(self.wd),
-                   ldw=self.ldw_d, n_rows=self.n_pad_d, n_cols=self.ldw_d, **common)
+    def operands(self):
+        """(weights, vectors): the forward operand wf, the data-gradient operand wd and, with split2, the re-ordered bias."""
+        views = [weight_view(self.wf, 0, self.cin_pad, self.ldw, self.n_pad, self.ldw),
+                 weight_view(self.wd, 1, self.cout_pad, self.ldw_d, self.n_pad_d, self.ldw_d, parity=self.parity)]
+        w = [weight_operand(self.w, self.Cout, self.Cin, self.k, (self.so, self.si, self.sj), views, co_split2=self.split2)]
+        v = []
         if self.bias_p is not None:
             h = self.Cout // 2
-            L.vec_copy(self.bias_p[:h], self.b, c.stream, src_stride=2)
-            L.vec_copy(self.bias_p[h:], self.b[1:], c.stream, src_stride=2)
+            v = [vector_operand(self.b, [dict(dst=self.bias_p, dst_off=0, n=h, src_offset=0, src_stride=2),
+                                         dict(dst=self.bias_p, dst_off=h, n=h, src_offset=1, src_stride=2)])]
+        return w, v
+
+    def pack(self):
+        pack_operands(self.ctx, *self.operands())
 
     def bias_ptr(self):
         if self.b is None:
@@ -406,19 +458,26 @@ class Conv2dLayer(object):
     def out_hw(self, H, W):
         return (H + 2 * self.pad - self.k) // self.stride + 1, (W + 2 * self.pad - self.k) // self.stride + 1
 
-    def pack(self):
+    def operands(self):
+        """(weights, vectors).  The forward operand is a whole-parameter view; a parity class of the data gradient takes a column
+        block per kw' with its own tap stride, which is no whole-parameter view: those are `raw` pack jobs."""
         c, k = self.ctx, self.k
         common = dict(dtype=c.dt, so=self.Cin * self.taps, si=self.taps, Cout=self.Cout, Cin=self.Cin, co_split2=0)
+        views = []
         if self.wf is not None:
-            L.call('zs_pack_weight', 'ZsPackWeight', c.stream, transpose=0, inner_pad=self.cin_pad, dst=L.ptr(self.wf), ldw=self.ldw,
-                   n_rows=self.n_pad, n_cols=self.ldw, W=L.ptr(self.w), sj=1, taps=self.taps, **common)
+            views.append(weight_view(self.wf, 0, self.cin_pad, self.ldw, self.n_pad, self.ldw))
+        raw = []
         step = self.stride
         for (ph, pw), (buf, ld) in self.wd.items():
             nh, nw = self.nt[ph], self.nt[pw]
             for kwp in range(nw):                                 # real taps kw = pw + step*kw', kh = ph + step*kh'
-                L.call('zs_pack_weight', 'ZsPackWeight', c.stream, transpose=1, inner_pad=self.cout_pad, dst=L.ptr(buf), ldw=ld,
-                       n_rows=self.n_pad_d, n_cols=nh * self.cout_pad, col_offset=kwp * nh * self.cout_pad,
-                       W=L.ptr(self.w, (pw + step * kwp) * k + ph), sj=step, taps=nh, **common)
+                raw.append(dict(common, transpose=1, inner_pad=self.cout_pad, dst=L.ptr(buf), ldw=ld, n_rows=self.n_pad_d,
+                                n_cols=nh * self.cout_pad, col_offset=kwp * nh * self.cout_pad,
+                                W=L.ptr(self.w, (pw + step * kwp) * k + ph), sj=step, taps=nh))
+        return [weight_operand(self.w, self.Cout, self.Cin, self.taps, (self.Cin * self.taps, self.taps, 1), views, raw=raw)], []
+
+    def pack(self):
+        pack_operands(self.ctx, *self.operands())
 
     def fwd(self, X, H, W, out, act=L.ZS_ACT_NONE, slope=0.0, bias=True, out_f32=False):
         """X: Act [B, H*W, Cin] -> out: Act [B, Ho*Wo, Cout].  Returns (Ho, Wo)."""
@@ -618,23 +677,26 @@ class GruLayer(object):
             hc, rem = n // 96, n % 96
             self.perm = ((rem // 32) * H + hc * 32 + (rem % 32)).to(torch.int32).to(dev)
 
-    def pack(self):
+    def operands(self):
+        """(weights, vectors): per direction W_ih into wih_f (rows stacked) and wih_d (columns stacked), W_hh into whh_f (rows
+        gate-interleaved by `perm` on the fast path) and whh_t, and the biases stacked into bih / bhh."""
         c, H, Cin = self.ctx, self.H, self.Cin
+        w, v = [], []
         for d in range(2):
-            com = dict(dtype=c.dt, so=Cin, si=1, sj=0, Cout=3 * H, Cin=Cin, taps=1, co_split2=0, W=L.ptr(self.w_ih[d]))
-            L.call('zs_pack_weight', 'ZsPackWeight', c.stream, transpose=0, inner_pad=self.cin_pad, dst=L.ptr(self.wih_f),
-                   ldw=self.ih_ldw, n_rows=3 * H, n_cols=self.ih_ldw, row_offset=3 * H * d, **com)
-            L.call('zs_pack_weight', 'ZsPackWeight', c.stream, transpose=1, inner_pad=3 * H, dst=L.ptr(self.wih_d),
-                   ldw=self.ih_ldw_d, n_rows=self.ih_npad_d, n_cols=3 * H, col_offset=3 * H * d, **com)
-            com = dict(dtype=c.dt, so=H, si=1, sj=0, Cout=3 * H, Cin=H, taps=1, co_split2=0, W=L.ptr(self.w_hh[d]))
-            L.call('zs_pack_weight', 'ZsPackWeight', c.stream, transpose=0, inner_pad=rup(H, c.kc),
-                   dst=L.ptr(self.whh_f, d * self.hh_npad * self.hh_ldw), ldw=self.hh_ldw,
-                   n_rows=(3 * H if self.fast else self.hh_npad), n_cols=self.hh_ldw, row_perm=L.ptr(self.perm), **com)
-            L.call('zs_pack_weight', 'ZsPackWeight', c.stream, transpose=1, inner_pad=rup(3 * H, c.kc),
-                   dst=L.ptr(self.whh_t, d * self.hh_npad_t * self.hh_ldw_t), ldw=self.hh_ldw_t, n_rows=self.hh_npad_t,
-                   n_cols=self.hh_ldw_t, **com)
-            L.vec_copy(self.bih[3 * H * d:3 * H * (d + 1)], self.b_ih[d], c.stream)
-            L.vec_copy(self.bhh[3 * H * d:3 * H * (d + 1)], self.b_hh[d], c.stream)
+            w.append(weight_operand(self.w_ih[d], 3 * H, Cin, 1, (Cin, 1, 0), [
+                weight_view(self.wih_f, 0, self.cin_pad, self.ih_ldw, 3 * H, self.ih_ldw, row_offset=3 * H * d),
+                weight_view(self.wih_d, 1, 3 * H, self.ih_ldw_d, self.ih_npad_d, 3 * H, col_offset=3 * H * d)]))
+            w.append(weight_operand(self.w_hh[d], 3 * H, H, 1, (H, 1, 0), [
+                weight_view(self.whh_f, 0, rup(H, c.kc), self.hh_ldw, (3 * H if self.fast else self.hh_npad), self.hh_ldw,
+                            dst_off=d * self.hh_npad * self.hh_ldw, row_perm=self.perm),
+                weight_view(self.whh_t, 1, rup(3 * H, c.kc), self.hh_ldw_t, self.hh_npad_t, self.hh_ldw_t,
+                            dst_off=d * self.hh_npad_t * self.hh_ldw_t)]))
+            v.append(vector_operand(self.b_ih[d], [dict(dst=self.bih, dst_off=3 * H * d, n=3 * H, src_offset=0, src_stride=1)]))
+            v.append(vector_operand(self.b_hh[d], [dict(dst=self.bhh, dst_off=3 * H * d, n=3 * H, src_offset=0, src_stride=1)]))
+        return w, v
+
+    def pack(self):
+        pack_operands(self.ctx, *self.operands())
 
     def _work(self, B):
         n = L.lib().zs_gru_work_bytes(B, self.H)

@@ -85,7 +85,34 @@ class ZsModule(nn.Module):
             self._engine()
         else:
             z['engine'].pack()
-            z['version'] = sum(p._version for p in self.parameters())
+            self.mark_packed()
+
+    def mark_packed(self):
+        """The GEMM operands hold the current master weights (re-packed on the device, stream-ordered)."""
+        self._zs['version'] = sum(p._version for p in self.parameters())
+
+    def adam_pack_plan(self):
+        """The plan of the fused optimizer step (optim.AdamPackPlan) over this net's flat buffer and its engine's operands, or None
+        for an engine that does not describe its operands.  Built once per engine (an engine is rebuilt after a move to another
+        device or dtype) and again when the engine gains an operand; the operands have been packed in full by then."""
+        eng = self._engine()
+        if not hasattr(eng, 'operands'):
+            return None
+        if getattr(eng, 'adam_plan', None) is None:
+            from .optim import AdamPackPlan
+            eng.adam_plan = AdamPackPlan(self._zs['flat'], eng.ctx, *eng.operands())
+        return eng.adam_plan
+
+    def adam_pack_jobs(self, dtype=None):
+        """The job list of that plan from parameter shapes alone (no GPU: the layers are laid out on the meta device):
+        optim.plan_jobs' (jobs, rest_weights, rest_vectors), already checked to cover the flat buffer exactly once."""
+        from .layers import PlanCtx
+        from .optim import plan_jobs
+        flat, gflat = self.flat_params()
+        P = {k: p.data for k, p in self.named_parameters()}
+        G = {k: self.grad_view(k) for k, _ in self.named_parameters()}
+        eng = self._make_engine(PlanCtx(dtype or self._zs_dtype), P, G)
+        return plan_jobs(flat, *eng.operands())
 
     def set_compute_dtype(self, dtype):
         if dtype != self._zs_dtype:
