@@ -467,7 +467,11 @@ int zs_sqnorm(const float* g, int64_t n, double* partial, float* out_sq, void* s
  * m = m + (g-m)(1-b1); v = v*b2 + g*g*(1-b2); p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps).
  * sumsq is a device scalar (from zs_sqnorm); max_norm <= 0 disables clipping.
  * grad_scale (0 = 1): g holds grad_scale^-1 times the gradient -- the SUM over `world` data-parallel ranks with
- * grad_scale = 1/world -- so the average is never materialised: norm = grad_scale*sqrt(sumsq), g_eff = g*grad_scale*coef. */
+ * grad_scale = 1/world -- so the average is never materialised: norm = grad_scale*sqrt(sumsq), g_eff = g*grad_scale*coef.
+ * ema (optional): the exponential moving average of the weights, updated in the same pass from the new p while it is in a
+ * register: ema = fma(p_new - ema, 1 - ema_decay, ema), i.e. ema.lerp_(p, 1 - ema_decay) with p_new - ema rounded once and
+ * 1 - ema_decay formed in fp32.  It changes no bit of p, g, m or v.  ema not 16-byte aligned: the one-element loop runs
+ * (the same bits). */
 typedef struct {
   float* p; float* g; float* m; float* v; int64_t n;
   float lr, beta1, beta2, eps, bc1, bc2;
@@ -475,6 +479,8 @@ typedef struct {
   const int32_t* step_ptr;       /* optional device step count t: bc1 = 1-beta1^t, bc2 = 1-beta2^t computed on device */
   float grad_scale;
   int32_t max_blocks;            /* > 0: grid cap (see zs_pack_weight_batch); 0 = default */
+  float* ema;                    /* optional weight average, n floats indexed like p; null = off (a zeroed struct is off) */
+  float ema_decay;               /* with ema: 0 <= ema_decay < 1, else ZS_EINVAL */
 } ZsAdam;
 int zs_adam_clip(const ZsAdam* p, void* stream);
 
@@ -505,7 +511,9 @@ int zs_sqnorm_stage1(const float* g, int64_t n, double* partial, void* stream);
  * kernel: the list is too long for launch arguments); both stay alive and unchanged while launches may run or replay.
  * sq_partial / n_partial: the partials of zs_sqnorm_stage1; every workgroup then sums them in the order of zs_sqnorm's
  * second stage (the same float) and workgroup 0 stores it to a->sumsq; null: a->sumsq is read as zs_adam_clip reads it.
- * a->max_blocks caps the grid as in zs_adam_clip.  dtype (ZS_F32 / ZS_BF16, of every view) is one for all jobs. */
+ * a->max_blocks caps the grid as in zs_adam_clip.  dtype (ZS_F32 / ZS_BF16, of every view) is one for all jobs.
+ * a->ema / a->ema_decay: the weight average of zs_adam_clip, by the same device function in every kind of tile (bit-identical
+ * to zs_adam_clip's); no launch is added.  The packed views always hold the raw new p, never the average. */
 enum { ZS_APJ_WEIGHT = 0, ZS_APJ_VECTOR = 1, ZS_APJ_RANGE = 2 };
 typedef struct {
   void* dst; int64_t ldw; int64_t dst_elems;

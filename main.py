@@ -28,6 +28,13 @@ Every --train* mode takes --device_data: the training set is uploaded into GPU m
 a train-state file (<ckpt_dir>/train_state/, zs_amd.resume) and the run continues bit for bit from the newest one in --ckpt_dir,
 or from iteration 0 when there is none: the same command starts a run and restarts it after an interruption.
 
+--ema D with any --train* mode (D in [0, 1), e.g. 0.999): every optimizer keeps an exponential moving average of its net's weights,
+updated inside the Adam kernels; every checkpoint then carries `<net>_ema` entries beside the raw weights, and --resume continues the
+averages bit for bit.  --use_ema with --test, --cross_test, --test_encode, --test_single, --test_classify or --convert_dir
+converts with the averaged weights of the checkpoint; with --load_model a training run starts from them, e.g. stage 2 from the
+averaged autoencoder: `--train_tgat --load_model --use_ema --ema 0.999`.  Where a flag would have no effect (--ema without a
+training mode, --use_ema without a mode that loads a checkpoint) it is refused before anything is built.
+
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
 (--train_al, --train_t, --encode, --test_asr) are not part of this build and exit with a clear error.
@@ -67,6 +74,16 @@ def _out_sr(text):
     if n <= 0 or n > 32 * 16000 or 32 * n < 16000:
         raise argparse.ArgumentTypeError('--out_sr must be a positive integer with out_sr / 16000 within [1/32, 32] (got %s)' % text)
     return n
+
+
+def _ema(text):
+    try:
+        d = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('--ema must be a number in [0, 1) (got %s)' % text)
+    if not 0.0 <= d < 1.0:                    # NaN fails too
+        raise argparse.ArgumentTypeError('--ema must be in [0, 1) (got %s)' % text)
+    return d
 
 
 def build_parser():
@@ -113,6 +130,12 @@ def build_parser():
     p.add_argument('--gl_iters', type=_gl_iters, default=None, help='Griffin-Lim iterations (hp.n_iter); default: leave hp as it is')
     p.add_argument('--gl_momentum', type=_gl_momentum, default=None,
                    help='fast Griffin-Lim momentum in [0, 1) (hp.gl_momentum); default: leave hp as it is')
+    p.add_argument('--ema', type=_ema, default=None, metavar='D',
+                   help='every --train* mode: keep an exponential moving average of the weights with decay D in [0, 1), updated in '
+                        'the Adam kernels; checkpoints gain <net>_ema entries; default: none')
+    p.add_argument('--use_ema', default=False, action='store_true',
+                   help='load the averaged weights (<net>_ema) of the checkpoint: every --test* mode, --cross_test, --convert_dir, and '
+                        'training with --load_model')
     p.add_argument('--out_sr', type=_out_sr, default=None,
                    help='sample rate of the wavs --test / --cross_test / --test_single write (hp.out_sr); default: 16000')
     return p
@@ -137,6 +160,25 @@ def check_resume(args):
         raise ValueError('--resume loads the newest checkpoint of its stage itself: it cannot be combined with --load_model')
 
 
+TRAIN_MODES = ['train', 'train_ae', 'train_p', 'train_tgat', 'train_c']
+
+
+LOADING_MODES = ['test', 'cross_test', 'test_encode', 'test_single', 'test_classify']
+
+
+def check_ema(args):
+    """--ema averages the weights a training run updates, --use_ema chooses what a checkpoint is loaded from: each is refused,
+    before anything is built, where it would have no effect -- --ema without a --train* mode, --use_ema without a mode that loads
+    a checkpoint (a --test* mode, --cross_test, --convert_dir, or a --train* mode with --load_model)."""
+    training = any(getattr(args, f) for f in TRAIN_MODES)
+    if args.ema is not None and not training:
+        raise ValueError('--ema needs a training mode (%s)' % ', '.join('--' + f for f in TRAIN_MODES))
+    loads = any(getattr(args, f) for f in LOADING_MODES) or args.convert_dir is not None or (training and args.load_model)
+    if args.use_ema and not loads:
+        raise ValueError('--use_ema needs a mode that loads a checkpoint: %s, --convert_dir, or a training mode with --load_model'
+                         % ', '.join('--' + f for f in LOADING_MODES))
+
+
 def convert_targets(args):
     """--convert_dir takes --t_speaker as a comma-separated list of distinct names (--test_single keeps the single name): the
     list, refused before anything is built when it names no speaker or one twice."""
@@ -153,6 +195,7 @@ def argument_runner(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_resume(args)
+    check_ema(args)
     args.t_speakers = convert_targets(args) if args.convert_dir is not None else None
     if args.dataset == 'surprise':            # main.py:83-88: english -> surprise in every default path
         for action in parser._actions:
@@ -221,9 +264,10 @@ def main(argv=None):
         data_loader, source_loader, target_loader = mk(dataset), mk(sourceset), mk(targetset)
         os.makedirs(args.ckpt_dir, exist_ok=True)
         model_path = os.path.join(args.ckpt_dir, args.model_name)
-        trainer = Trainer(hps, data_loader, args.g_mode, args.enc_mode, dtype=args.dtype)
+        trainer = Trainer(hps, data_loader, args.g_mode, args.enc_mode, dtype=args.dtype, ema=args.ema)
         if args.load_model:
-            trainer.load_model(os.path.join(args.ckpt_dir, args.load_train_model_name), load_model_list=hps.load_model_list)
+            trainer.load_model(os.path.join(args.ckpt_dir, args.load_train_model_name), load_model_list=hps.load_model_list,
+                               use_ema=args.use_ema)
         if args.train or args.train_ae:
             trainer.train(model_path, args.flag, mode='pretrain_AE', resume=args.resume)       # stage 1: reconstruction
             trainer.reset_keep()
@@ -242,7 +286,7 @@ def main(argv=None):
     if args.test or args.cross_test or args.test_encode or args.test_single or args.test_classify or args.convert_dir is not None:
         os.makedirs(args.result_dir, exist_ok=True)
         model_path = args.ckpt_pth if args.ckpt_pth is not None else os.path.join(args.ckpt_dir, args.load_test_model_name)
-        trainer = get_trainer(args.hps_path, model_path, args.g_mode, args.enc_mode, args.load_tclf_model_name)
+        trainer = get_trainer(args.hps_path, model_path, args.g_mode, args.enc_mode, args.load_tclf_model_name, use_ema=args.use_ema)
         result_dir = os.path.join(args.result_dir, args.sub_result_dir)
         os.makedirs(result_dir, exist_ok=True)
         if args.test:

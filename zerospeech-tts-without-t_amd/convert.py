@@ -232,13 +232,14 @@ def encode_x(x, trainer):
     return trainer.encoder_test_step(tensor).squeeze(axis=0).transpose((1, 0))
 
 
-def get_trainer(hps_path, model_path, g_mode, enc_mode, clf_path=None):
+def get_trainer(hps_path, model_path, g_mode, enc_mode, clf_path=None, use_ema=False):
+    """use_ema: convert with the averaged weights of the checkpoint (its `<net>_ema` entries, Trainer.load_model)."""
     from .trainer import Trainer
     hps = Hps(hps_path).get_tuple()
     global MIN_LEN
     MIN_LEN = MIN_LEN if hps.enc_mode != 'gumbel_t' else hps.seg_len
     trainer = Trainer(hps, None, g_mode, enc_mode)
-    trainer.load_model(model_path, load_model_list=hps.load_model_list, clf_path=clf_path)
+    trainer.load_model(model_path, load_model_list=hps.load_model_list, clf_path=clf_path, use_ema=use_ema)
     return trainer
 
 

@@ -408,33 +408,54 @@ __device__ __forceinline__ void adam_upd(const AdamCoef& c, float& w, float& g, 
   const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
   w = __builtin_fmaf(-c.step_size, m / denom, w);
 }
+// The weight average (ZsAdam.ema): e += (w - e)(1 - decay) on the new w while it is in a register, ema.lerp_(p, 1 - decay).  ONE
+// function for every path, its fusion written out like adam_upd's: w - e is rounded once, 1 - decay is formed in fp32.
+__device__ __forceinline__ void ema_upd(float& e, float w, float decay) {
+#pragma clang fp contract(off)
+  e = __builtin_fmaf(w - e, 1.f - decay, e);
+}
+// EMA is a template parameter everywhere below: the instantiations without the average are the code without the fifth stream.
+template <bool EMA>
 __device__ __forceinline__ void adam_upd4(const ZsAdam& p, const AdamCoef& c, int64_t i, float4& w) {     // float4 index i
   float4 g = reinterpret_cast<float4*>(p.g)[i], m = reinterpret_cast<float4*>(p.m)[i], v = reinterpret_cast<float4*>(p.v)[i];
   w = reinterpret_cast<float4*>(p.p)[i];
   adam_upd(c, w.x, g.x, m.x, v.x); adam_upd(c, w.y, g.y, m.y, v.y); adam_upd(c, w.z, g.z, m.z, v.z); adam_upd(c, w.w, g.w, m.w, v.w);
   reinterpret_cast<float4*>(p.p)[i] = w; reinterpret_cast<float4*>(p.m)[i] = m; reinterpret_cast<float4*>(p.v)[i] = v;
   if (p.write_clipped_grad) reinterpret_cast<float4*>(p.g)[i] = g;
+  if constexpr (EMA) {
+    float4 e = reinterpret_cast<float4*>(p.ema)[i];
+    ema_upd(e.x, w.x, p.ema_decay); ema_upd(e.y, w.y, p.ema_decay); ema_upd(e.z, w.z, p.ema_decay); ema_upd(e.w, w.w, p.ema_decay);
+    reinterpret_cast<float4*>(p.ema)[i] = e;
+  }
 }
+template <bool EMA>
 __device__ __forceinline__ float adam_upd1(const ZsAdam& p, const AdamCoef& c, int64_t i) {
   float w = p.p[i], g = p.g[i], m = p.m[i], v = p.v[i];
   adam_upd(c, w, g, m, v);
   p.p[i] = w; p.m[i] = m; p.v[i] = v;
   if (p.write_clipped_grad) p.g[i] = g;
+  if constexpr (EMA) {
+    float e = p.ema[i];
+    ema_upd(e, w, p.ema_decay);
+    p.ema[i] = e;
+  }
   return w;
 }
+template <bool EMA>
 __device__ __forceinline__ bool adam_aligned16(const ZsAdam& p) {
-  return ((((uintptr_t)p.p) | ((uintptr_t)p.g) | ((uintptr_t)p.m) | ((uintptr_t)p.v)) & 15) == 0;
+  return ((((uintptr_t)p.p) | ((uintptr_t)p.g) | ((uintptr_t)p.m) | ((uintptr_t)p.v) | (EMA ? (uintptr_t)p.ema : 0)) & 15) == 0;
 }
 
+template <bool EMA>
 __global__ void adam_kernel(const ZsAdam p) {
   const AdamCoef c = adam_coef(p, p.sumsq);
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-  const int64_t n4 = adam_aligned16(p) ? p.n / 4 : 0;
+  const int64_t n4 = adam_aligned16<EMA>(p) ? p.n / 4 : 0;
   for (int64_t i = tid; i < n4; i += nthr) {                     // 16-byte accesses: four streams of 64 B per lane in flight
     float4 w;
-    adam_upd4(p, c, i, w);
+    adam_upd4<EMA>(p, c, i, w);
   }
-  for (int64_t i = 4 * n4 + tid; i < p.n; i += nthr) adam_upd1(p, c, i);
+  for (int64_t i = 4 * n4 + tid; i < p.n; i += nthr) adam_upd1<EMA>(p, c, i);
 }
 
 // ---- Adam + clip + re-pack in one pass (zs_adam_pack) ---------------------------------------------------
@@ -461,7 +482,7 @@ inline int64_t ap_tiles(const ZsAdamPackJob& j) {
   return (j.len + t - 1) / t;
 }
 
-template <typename T, int TAPS>
+template <typename T, int TAPS, bool EMA>
 __device__ __forceinline__ void ap_weight_tile(const ZsAdam& a, const AdamCoef& c, const ZsAdamPackJob& job, int tile, T* lds) {
   using G = ApTile<T, TAPS>;
   constexpr int CB = G::CB, IB = G::IB, RUN = G::RUN, PITCH = G::PITCH;
@@ -474,13 +495,13 @@ __device__ __forceinline__ void ap_weight_tile(const ZsAdam& a, const AdamCoef& 
   const int64_t row_len = (int64_t)job.Cin * TAPS;
   const int64_t base = job.off + (int64_t)i0 * TAPS;
   auto co_of = [&](int n) { return split2 ? (n < half ? 2 * n : 2 * (n - half) + 1) : n; };
-  if (adam_aligned16(a) && ((row_len | job.off) & 3) == 0) {       // every run starts and ends on 16 bytes
+  if (adam_aligned16<EMA>(a) && ((row_len | job.off) & 3) == 0) {       // every run starts and ends on 16 bytes
     constexpr int R4 = RUN / 4;
     for (int e = tid; e < CB * R4; e += AP_THREADS) {
       const int rl = e / R4, x = (e - rl * R4) * 4;
       if (rl < rows && x < runw) {
         float4 w;
-        adam_upd4(a, c, (base + (int64_t)co_of(n0 + rl) * row_len + x) >> 2, w);
+        adam_upd4<EMA>(a, c, (base + (int64_t)co_of(n0 + rl) * row_len + x) >> 2, w);
         T* d = lds + rl * PITCH + x;
         Elem<T>::st(d, w.x); Elem<T>::st(d + 1, w.y); Elem<T>::st(d + 2, w.z); Elem<T>::st(d + 3, w.w);
       }
@@ -488,7 +509,7 @@ __device__ __forceinline__ void ap_weight_tile(const ZsAdam& a, const AdamCoef& 
   } else {
     for (int e = tid; e < CB * RUN; e += AP_THREADS) {
       const int rl = e / RUN, x = e - rl * RUN;
-      if (rl < rows && x < runw) Elem<T>::st(lds + rl * PITCH + x, adam_upd1(a, c, base + (int64_t)co_of(n0 + rl) * row_len + x));
+      if (rl < rows && x < runw) Elem<T>::st(lds + rl * PITCH + x, adam_upd1<EMA>(a, c, base + (int64_t)co_of(n0 + rl) * row_len + x));
     }
   }
   __syncthreads();
@@ -522,22 +543,24 @@ __device__ __forceinline__ void ap_weight_tile(const ZsAdam& a, const AdamCoef& 
   }
 }
 
+template <bool EMA>
 __device__ __forceinline__ void ap_range_tile(const ZsAdam& a, const AdamCoef& c, const ZsAdamPackJob& job, int tile) {
   const int64_t lo = job.off + (int64_t)tile * AP_RANGE_TILE;
   const int cnt = (int)min((int64_t)AP_RANGE_TILE, job.off + job.len - lo);
-  const int n4 = (adam_aligned16(a) && (lo & 3) == 0) ? cnt / 4 : 0;
+  const int n4 = (adam_aligned16<EMA>(a) && (lo & 3) == 0) ? cnt / 4 : 0;
   for (int i = threadIdx.x; i < n4; i += AP_THREADS) {
     float4 w;
-    adam_upd4(a, c, (lo >> 2) + i, w);
+    adam_upd4<EMA>(a, c, (lo >> 2) + i, w);
   }
-  for (int i = 4 * n4 + threadIdx.x; i < cnt; i += AP_THREADS) adam_upd1(a, c, lo + i);
+  for (int i = 4 * n4 + threadIdx.x; i < cnt; i += AP_THREADS) adam_upd1<EMA>(a, c, lo + i);
 }
 
+template <bool EMA>
 __device__ __forceinline__ void ap_vector_tile(const ZsAdam& a, const AdamCoef& c, const ZsAdamPackJob& job, int tile) {
   const int lo = tile * AP_VEC_TILE;
   const int hi = (int)min((int64_t)lo + AP_VEC_TILE, job.len);
   for (int e = lo + threadIdx.x; e < hi; e += AP_THREADS) {
-    const float w = adam_upd1(a, c, job.off + e);
+    const float w = adam_upd1<EMA>(a, c, job.off + e);
     for (int vi = 0; vi < job.n_views; ++vi) {
       const ZsAdamPackView& v = job.view[vi];
       const int r = e - v.src_offset;
@@ -546,7 +569,7 @@ __device__ __forceinline__ void ap_vector_tile(const ZsAdam& a, const AdamCoef& 
   }
 }
 
-template <typename T>
+template <typename T, bool EMA>
 __global__ __launch_bounds__(AP_THREADS) void adam_pack_kernel(const ZsAdam a, const ZsAdamPackJob* __restrict__ jobs, int n_jobs, int total,
                                                                 const double* __restrict__ part, int n_part) {
   __shared__ int s_start[AP_MAX_JOBS + 1];
@@ -574,11 +597,11 @@ __global__ __launch_bounds__(AP_THREADS) void adam_pack_kernel(const ZsAdam a, c
     lo = __builtin_amdgcn_readfirstlane(lo);                     // (block-uniform: the job is read with scalar loads)
     const ZsAdamPackJob& job = jobs[lo];
     const int tile = g - s_start[lo];
-    if (job.kind == ZS_APJ_RANGE) ap_range_tile(a, c, job, tile);
-    else if (job.kind == ZS_APJ_VECTOR) ap_vector_tile(a, c, job, tile);
+    if (job.kind == ZS_APJ_RANGE) ap_range_tile<EMA>(a, c, job, tile);
+    else if (job.kind == ZS_APJ_VECTOR) ap_vector_tile<EMA>(a, c, job, tile);
     else {
       T* lds = reinterpret_cast<T*>(s_tile);
-#define ZS_AP_CASE(K) case K: ap_weight_tile<T, K>(a, c, job, tile, lds); break;
+#define ZS_AP_CASE(K) case K: ap_weight_tile<T, K, EMA>(a, c, job, tile, lds); break;
       switch (job.taps) { ZS_AP_CASE(1) ZS_AP_CASE(2) ZS_AP_CASE(3) ZS_AP_CASE(4) ZS_AP_CASE(5) ZS_AP_CASE(6) ZS_AP_CASE(7) default: break; }
 #undef ZS_AP_CASE
     }
@@ -835,9 +858,11 @@ extern "C" int zs_sqnorm(const float* g, int64_t n, double* partial, float* out_
 extern "C" int zs_adam_clip(const ZsAdam* p, void* stream) {
   ZS_REQUIRE(p && p->p && p->g && p->m && p->v && p->n > 0, "zs_adam_clip: bad args");
   ZS_REQUIRE(p->step_ptr || (p->bc1 > 0.f && p->bc2 > 0.f), "zs_adam_clip: bias corrections");
+  ZS_REQUIRE(!p->ema || (p->ema_decay >= 0.f && p->ema_decay < 1.f), "zs_adam_clip: ema_decay %g outside [0, 1)", (double)p->ema_decay);
   unsigned nb = nblocks((p->n + 3) / 4, 4096);
   if (p->max_blocks > 0 && nb > (unsigned)p->max_blocks) nb = (unsigned)p->max_blocks;
-  hipLaunchKernelGGL(adam_kernel, dim3(nb), dim3(NTE), 0, (hipStream_t)stream, *p);
+  if (p->ema) hipLaunchKernelGGL(adam_kernel<true>, dim3(nb), dim3(NTE), 0, (hipStream_t)stream, *p);
+  else hipLaunchKernelGGL(adam_kernel<false>, dim3(nb), dim3(NTE), 0, (hipStream_t)stream, *p);
   return zs_check_launch("zs_adam_clip");
 }
 
@@ -888,6 +913,7 @@ extern "C" int zs_adam_pack(const ZsAdam* a, const ZsAdamPackJob* jobs, const Zs
                             int32_t n_partial, void* stream) {
   ZS_REQUIRE(a && a->p && a->g && a->m && a->v && a->n > 0, "zs_adam_pack: bad args");
   ZS_REQUIRE(a->step_ptr || (a->bc1 > 0.f && a->bc2 > 0.f), "zs_adam_pack: bias corrections");
+  ZS_REQUIRE(!a->ema || (a->ema_decay >= 0.f && a->ema_decay < 1.f), "zs_adam_pack: ema_decay %g outside [0, 1)", (double)a->ema_decay);
   ZS_REQUIRE(jobs && jobs_dev && n > 0 && n <= AP_MAX_JOBS, "zs_adam_pack: 1..%d jobs", AP_MAX_JOBS);
   ZS_REQUIRE(!sq_partial || (n_partial > 0 && n_partial <= 1024 && a->sumsq), "zs_adam_pack: 1..1024 partials and sumsq");
   int64_t total = 0, end = 0;
@@ -903,10 +929,11 @@ extern "C" int zs_adam_pack(const ZsAdam* a, const ZsAdamPackJob* jobs, const Zs
     ZS_REQUIRE(total < (1ll << 30), "zs_adam_pack: too many tiles");
   }
   const unsigned gx = (unsigned)((a->max_blocks > 0 && total > a->max_blocks) ? a->max_blocks : total);
-  if (jobs[0].dtype == ZS_F32)
-    hipLaunchKernelGGL(adam_pack_kernel<float>, dim3(gx), dim3(AP_THREADS), 0, (hipStream_t)stream, *a, jobs_dev, (int)n, (int)total, sq_partial, (int)n_partial);
-  else
-    hipLaunchKernelGGL(adam_pack_kernel<bf16_t>, dim3(gx), dim3(AP_THREADS), 0, (hipStream_t)stream, *a, jobs_dev, (int)n, (int)total, sq_partial, (int)n_partial);
+#define ZS_AP_LAUNCH(T, EMA) hipLaunchKernelGGL((adam_pack_kernel<T, EMA>), dim3(gx), dim3(AP_THREADS), 0, (hipStream_t)stream, *a, jobs_dev, \
+                                               (int)n, (int)total, sq_partial, (int)n_partial)
+  if (jobs[0].dtype == ZS_F32) { if (a->ema) ZS_AP_LAUNCH(float, true); else ZS_AP_LAUNCH(float, false); }
+  else { if (a->ema) ZS_AP_LAUNCH(bf16_t, true); else ZS_AP_LAUNCH(bf16_t, false); }
+#undef ZS_AP_LAUNCH
   return zs_check_launch("zs_adam_pack");
 }
 

@@ -119,33 +119,62 @@ class AdamPackPlan(object):
                 pack_operands(self.ctx, self.rest_w, self.rest_v)
 
 
+def check_ema(decay):
+    """None (no average), or the decay of a weight average as a float: ValueError unless 0 <= decay < 1."""
+    if decay is None:
+        return None
+    decay = float(decay)
+    if not 0.0 <= decay < 1.0:                       # NaN fails too
+        raise ValueError('ema: the decay must lie in [0, 1) (got %r)' % decay)
+    return decay
+
+
 class NetOpt(object):
     """clip_grad_norm_(net, max_norm) + Adam(lr, betas) (utils.py:53-55, trainer.py:66) over ONE net's flat parameter buffer.
     step(): host step count t, bias correction computed here in double, weights re-packed lazily (mark_dirty).  device_step():
     the count read from device memory and the bias correction computed there (a captured step replays frozen arguments), weights
     re-packed at once.  reduce=True: step() first sums the gradients over ranks itself; reduce=False: the net's owner does.  The
-    buffer then holds the SUM over ranks; zs_adam_clip applies the 1/world (grad_scale)."""
+    buffer then holds the SUM over ranks; zs_adam_clip applies the 1/world (grad_scale).
+    ema: None, or the decay in [0, 1) of an exponential moving average of the weights, self.ema (fp32, the flat buffer's
+    length, a copy of the weights at first): every update, on whichever path, moves it inside the Adam launch itself
+    (ZsAdam.ema).  After the weights were loaded or broadcast: reset_ema()."""
 
-    def __init__(self, net, lr, betas=(0.5, 0.9), max_norm=0.0, reduce=True):
+    def __init__(self, net, lr, betas=(0.5, 0.9), max_norm=0.0, reduce=True, ema=None):
         self.net, self.lr, self.betas, self.max_norm, self.t = net, float(lr), betas, max_norm, 0
         flat, _ = net.flat_params()
         self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat)
+        self.ema_decay = check_ema(ema)
+        self.ema = flat.detach().clone() if self.ema_decay is not None else None
         self.sq = torch.zeros(1, dtype=torch.float32, device=flat.device)     # squared gradient norm (device scalar)
         self.part = torch.zeros(1024, dtype=torch.float64, device=flat.device)
         self.reducer = parallel.GradReducer() if reduce else None
 
+    def reset_ema(self):
+        """ema = the weights as they are now, in place (no-op without an average)."""
+        if self.ema is not None:
+            self.ema.copy_(self.net.flat_params()[0].detach())
+
     def state_dict(self):
-        """{'m', 'v': the moment buffers themselves (device), 't': the host step count}."""
-        return {'m': self.m, 'v': self.v, 't': int(self.t)}
+        """{'m', 'v': the moment buffers themselves (device), 't': the host step count} and, with an average, 'ema': its buffer."""
+        sd = {'m': self.m, 'v': self.v, 't': int(self.t)}
+        if self.ema is not None:
+            sd['ema'] = self.ema
+        return sd
 
     def load_state_dict(self, sd):
-        """Restore m, v and t in place (the buffers keep their addresses: a captured step goes on reading them) and mark the
-        net's packed weights stale: the caller has just loaded its master weights."""
-        for k in ('m', 'v'):
+        """Restore m, v, t and the average in place (the buffers keep their addresses: a captured step goes on reading them) and
+        mark the net's packed weights stale: the caller has just loaded its master weights.  ValueError, before anything is
+        changed, when the state has an average and this optimizer has none, or the other way round."""
+        if ('ema' in sd) != (self.ema is not None):
+            raise ValueError('optimizer state: ema is %s in the state, %s in this optimizer' %
+                             ('on' if 'ema' in sd else 'off', 'on' if self.ema is not None else 'off'))
+        for k in ('m', 'v') + (('ema',) if self.ema is not None else ()):
             if tuple(sd[k].shape) != tuple(self.m.shape):
                 raise ValueError('optimizer state: %s has %d elements, the net has %d' % (k, sd[k].numel(), self.m.numel()))
         self.m.copy_(sd['m'])
         self.v.copy_(sd['v'])
+        if self.ema is not None:
+            self.ema.copy_(sd['ema'])
         self.t = int(sd['t'])
         self.net.mark_dirty()
 
@@ -161,7 +190,8 @@ class NetOpt(object):
         b1, b2 = self.betas
         return dict(p=L.ptr(flat), g=L.ptr(gflat), m=L.ptr(self.m), v=L.ptr(self.v), n=flat.numel(), lr=self.lr, beta1=b1, beta2=b2,
                     eps=1e-8, bc1=bc1, bc2=bc2, sumsq=L.ptr(self.sq), max_norm=float(max_norm) if max_norm else 0.0,
-                    write_clipped_grad=0, step_ptr=step_ptr, grad_scale=1.0 / parallel.world_size())
+                    write_clipped_grad=0, step_ptr=step_ptr, grad_scale=1.0 / parallel.world_size(), ema=L.ptr(self.ema),
+                    ema_decay=self.ema_decay)
 
     def _adam(self, bc1, bc2, max_norm, step_ptr=None):
         L.call('zs_adam_clip', 'ZsAdam', torch.cuda.current_stream(self.m.device).cuda_stream,

@@ -6,6 +6,8 @@ A checkpoint `<dir>/<model_name>-<tag>-<iteration>` (the reference's dict, uncha
 weights_only=True) that holds no weights.  Its keys:
 
   version, tag, iteration, target_guided, autolocker, world, batch_size, dtype, g_mode, enc_mode, use_graph     what it belongs to
+  ema           the decay of the weight averages (Trainer(ema=...)); the key is absent when the run keeps none.  The averages
+                themselves travel in `steps`, one 'ema' buffer beside each optimizer's m and v
   flat_len      {net: length of its flat parameter buffer}
   steps         {'ae' | 'clf' | 's2' | 'tclf': that step object's state_dict()}: Adam m / v / t per stepped net and the counters
   consumed      {'data' | 'source' | 'target': batches the steps have taken from that loader}
@@ -62,10 +64,13 @@ def describe(trainer, tag, target_guided=False, autolocker=False):
     """The fields of FIELDS plus flat_len for `trainer` as it stands: what a state file written now records, and what one loaded
     now must match.  Reads attributes and buffer lengths only."""
     from . import parallel
-    return {'version': FORMAT_VERSION, 'tag': tag, 'target_guided': bool(target_guided), 'autolocker': bool(autolocker),
-            'world': int(parallel.world_size()), 'batch_size': int(trainer.hps.batch_size), 'dtype': str(trainer.dtype),
-            'g_mode': str(trainer.g_mode), 'enc_mode': str(trainer.enc_mode), 'use_graph': bool(trainer.ae.use_graph),
-            'flat_len': {name: int(net.flat_params()[0].numel()) for name, net in zip(NET_NAMES, trainer.nets())}}
+    d = {'version': FORMAT_VERSION, 'tag': tag, 'target_guided': bool(target_guided), 'autolocker': bool(autolocker),
+         'world': int(parallel.world_size()), 'batch_size': int(trainer.hps.batch_size), 'dtype': str(trainer.dtype),
+         'g_mode': str(trainer.g_mode), 'enc_mode': str(trainer.enc_mode), 'use_graph': bool(trainer.ae.use_graph),
+         'flat_len': {name: int(net.flat_params()[0].numel()) for name, net in zip(NET_NAMES, trainer.nets())}}
+    if getattr(trainer, 'ema', None) is not None:                          # recorded only when on: an EMA-off file is today's
+        d['ema'] = float(trainer.ema)
+    return d
 
 
 def validate(state, expect):
@@ -75,12 +80,24 @@ def validate(state, expect):
             raise ValueError('train state: field %r is missing' % f)
         if state[f] != expect[f]:
             raise ValueError('train state: %s is %r in the file, %r in this run' % (f, state[f], expect[f]))
+    if state.get('ema') != expect.get('ema'):                             # the decay, or None: on / off and the value must agree
+        raise ValueError('train state: ema is %r in the file, %r in this run' % (state.get('ema'), expect.get('ema')))
     have = state.get('flat_len')
     if not isinstance(have, dict):
         raise ValueError("train state: field 'flat_len' is missing")
     for name, n in expect['flat_len'].items():
         if have.get(name) != n:
             raise ValueError('train state: flat_len[%s] is %r in the file, %r in this run' % (name, have.get(name), n))
+
+
+def ema_keys(file_keys, wanted, path='checkpoint'):
+    """Which entry of a checkpoint each net is loaded from when the averaged weights are asked for (load_model(use_ema=True)):
+    {net: '<net>_ema' where the file has it, else '<net>'} for the nets `wanted`.  file_keys: the checkpoint's top-level keys.
+    ValueError naming `path` when the file has no `*_ema` entry at all: it was written without --ema."""
+    file_keys = set(file_keys)
+    if not any(k.endswith('_ema') for k in file_keys):
+        raise ValueError('use_ema: %s has no *_ema entry (it was written by a run without --ema)' % path)
+    return {net: (net + '_ema' if net + '_ema' in file_keys else net) for net in wanted}
 
 
 def roll_window(model_kept, new_path, max_keep):

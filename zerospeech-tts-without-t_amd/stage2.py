@@ -25,15 +25,15 @@ G_MODES = ('naive', 'targeted', 'targeted_residual', 'spectrogram')
 
 
 class PatchGANStep(object):
-    def __init__(self, encoder, decoder, generator, discriminator, hps, g_mode):
+    def __init__(self, encoder, decoder, generator, discriminator, hps, g_mode, ema=None):
         self.Encoder, self.Decoder, self.Generator, self.D = encoder, decoder, generator, discriminator
         self.hps, self.g_mode = hps, g_mode
         if g_mode not in G_MODES:
             raise NotImplementedError('Invalid generator mode to call gen_step()!')
         self.shift = 0 if g_mode == 'naive' else int(hps.n_speakers - hps.n_target_speakers)
         self.device = encoder.flat_params()[0].device
-        self.gen_opt = NetOpt(generator, hps.lr)
-        self.patch_opt = NetOpt(discriminator, hps.lr)
+        self.gen_opt = NetOpt(generator, hps.lr, ema=ema)                     # ema: a weight average of the generator and of the
+        self.patch_opt = NetOpt(discriminator, hps.lr, ema=ema)              # critic, moved by their own Adam launches (NetOpt)
         dev = self.device
         self.loss_clf = torch.zeros(1, dtype=torch.float32, device=dev)
         self.correct = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -193,11 +193,11 @@ class AutolockerStep(PatchGANStep):
 
     ENC_MODE = 'multilabel_binary'
 
-    def __init__(self, encoder, decoder, generator, discriminator, hps, g_mode):
+    def __init__(self, encoder, decoder, generator, discriminator, hps, g_mode, ema=None):
         mode = getattr(encoder, 'enc_mode', None)
         if mode != self.ENC_MODE:
             raise ValueError("mode 'autolocker' needs enc_mode %r (BCE on the hard units), got %r" % (self.ENC_MODE, mode))
-        super(AutolockerStep, self).__init__(encoder, decoder, generator, discriminator, hps, g_mode)
+        super(AutolockerStep, self).__init__(encoder, decoder, generator, discriminator, hps, g_mode, ema=ema)
         self.loss_reenc = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._bce_part = torch.zeros(1024, dtype=torch.float64, device=self.device)
 

@@ -23,7 +23,7 @@ from . import resume as train_state                # (Trainer.train has a parame
 from .layers import Act, join_side
 from .model import Decoder, Encoder, SpeakerClassifier, Spectrogram_Patcher
 from .patch import PatchDiscriminator, TargetClassifier
-from .optim import NetOpt, softmax_ce
+from .optim import NetOpt, check_ema, softmax_ce
 from .stage2 import AutolockerStep, PatchGANStep
 from .utils import Logger
 
@@ -44,10 +44,11 @@ class AEStep(object):
     optimizer), with the RCCL all-reduces of the gradient buckets launched eagerly between them, each as soon as its bucket is
     final."""
 
-    def __init__(self, encoder, decoder, lr=1e-4, betas=(0.5, 0.9), max_grad_norm=5.0, use_graph=None):
+    def __init__(self, encoder, decoder, lr=1e-4, betas=(0.5, 0.9), max_grad_norm=5.0, use_graph=None, ema=None):
         self.Encoder, self.Decoder = encoder, decoder
         self.adam_step = 0                   # the pair's Adam step count (on the device: _step_dev)
-        self.opt = {name: NetOpt(net, lr, betas, max_grad_norm, reduce=False) for name, net in (('enc', encoder), ('dec', decoder))}
+        self.opt = {name: NetOpt(net, lr, betas, max_grad_norm, reduce=False, ema=ema)      # ema: a weight average per net (NetOpt)
+                    for name, net in (('enc', encoder), ('dec', decoder))}
         dev = encoder.flat_params()[0].device
         self.device = dev
         self._loss = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -448,10 +449,10 @@ class ClfStep(object):
     pre-activation `enc` (CE, per-net clip, Adam betas (0.5, 0.9)); the G step trains Encoder+Decoder with
     loss_rec - alpha * loss_clf (the classifier only passes the gradient through)."""
 
-    def __init__(self, ae, classifier, lr=1e-4, betas=(0.5, 0.9), max_grad_norm=5.0):
+    def __init__(self, ae, classifier, lr=1e-4, betas=(0.5, 0.9), max_grad_norm=5.0, ema=None):
         self.ae, self.clf = ae, classifier
         self.device = ae.device
-        self.opt = NetOpt(classifier, lr, betas, max_grad_norm, reduce=False)     # reduced in d_step, even without an update
+        self.opt = NetOpt(classifier, lr, betas, max_grad_norm, reduce=False, ema=ema)     # reduced in d_step, even without an update
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.correct = torch.zeros(1, dtype=torch.int32, device=self.device)
 
@@ -546,9 +547,9 @@ class TclfStep(object):
     targets, backward to the parameters only, clip_grad_norm(max_grad_norm) + Adam(lr, betas (0.5, 0.9)).  The relabel runs on
     the device (no host sync); the targets are range-checked on the host by tclf_labels before a batch is copied over."""
 
-    def __init__(self, classifier, lr, max_grad_norm, shift):
+    def __init__(self, classifier, lr, max_grad_norm, shift, ema=None):
         self.clf, self.shift = classifier, int(shift)
-        self.opt = NetOpt(classifier, lr, betas=(0.5, 0.9), max_norm=max_grad_norm)
+        self.opt = NetOpt(classifier, lr, betas=(0.5, 0.9), max_norm=max_grad_norm, ema=ema)
         dev = classifier.flat_params()[0].device
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
         self.correct = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -592,8 +593,13 @@ def _fill_slots(skel, pin):
 
 
 class Trainer(object):
-    def __init__(self, hps, data_loader, g_mode, enc_mode, log_dir='./log/', dtype=None, device=None):
+    ema = None                             # the decay of the weight averages (__init__ sets it; the default serves a Trainer made without it)
+
+    def __init__(self, hps, data_loader, g_mode, enc_mode, log_dir='./log/', dtype=None, device=None, ema=None):
+        """ema (not in the reference): None, or the decay in [0, 1) of an exponential moving average of the weights that every
+        optimizer this trainer builds keeps beside its net (optim.NetOpt); the checkpoints then carry `<net>_ema` entries."""
         self.hps = hps
+        self.ema = check_ema(ema)
         self.data_loader = data_loader
         self._prefetch = None
         self.model_kept = []
@@ -645,8 +651,8 @@ class Trainer(object):
         self.PatchDiscriminator = PatchDiscriminator(ns=ns, n_class=(hps.n_speakers if self.g_mode == 'naive' else hps.n_target_speakers),
                                                      seg_len=hps.seg_len, dtype=dt).to(dev)
         self.TargetClassifier = TargetClassifier(ns=ns, n_class=3, seg_len=hps.seg_len, dtype=dt).to(dev)
-        self.ae = AEStep(self.Encoder, self.Decoder, lr=hps.lr, betas=(0.5, 0.9), max_grad_norm=hps.max_grad_norm)
-        self.clf = ClfStep(self.ae, self.SpeakerClassifier, lr=hps.lr, betas=(0.5, 0.9), max_grad_norm=hps.max_grad_norm)
+        self.ae = AEStep(self.Encoder, self.Decoder, lr=hps.lr, betas=(0.5, 0.9), max_grad_norm=hps.max_grad_norm, ema=self.ema)
+        self.clf = ClfStep(self.ae, self.SpeakerClassifier, lr=hps.lr, betas=(0.5, 0.9), max_grad_norm=hps.max_grad_norm, ema=self.ema)
         self.s2 = None                      # PatchGANStep, built on first use (its optimizer state is 2 x 53 M floats)
         self.source_loader = self.target_loader = None
         self.testing_shift_c = None
@@ -666,18 +672,32 @@ class Trainer(object):
         """The stage-2 step object.  autolocker=True: an AutolockerStep (raises ValueError before any launch unless enc_mode is
         multilabel_binary); a PatchGANStep built earlier hands it its optimizers (the reference has one gen_opt / patch_opt)."""
         if autolocker and not isinstance(self.s2, AutolockerStep):
-            al = AutolockerStep(self.Encoder, self.Decoder, self.Generator, self.PatchDiscriminator, self.hps, self.g_mode)
-            if self.s2 is not None:
+            al = AutolockerStep(self.Encoder, self.Decoder, self.Generator, self.PatchDiscriminator, self.hps, self.g_mode, ema=self.ema)
+            if self.s2 is not None:                 # (al's own optimizers, moments and averages included, are dropped here)
                 al.gen_opt, al.patch_opt, al.step_no = self.s2.gen_opt, self.s2.patch_opt, self.s2.step_no
             self.s2 = al
         if self.s2 is None:
-            self.s2 = PatchGANStep(self.Encoder, self.Decoder, self.Generator, self.PatchDiscriminator, self.hps, self.g_mode)
+            self.s2 = PatchGANStep(self.Encoder, self.Decoder, self.Generator, self.PatchDiscriminator, self.hps, self.g_mode, ema=self.ema)
         return self.s2
 
     def sync_params(self):
         """Data parallel: every rank starts from rank 0's weights (each process seeds torch's RNG differently, so the freshly
-        built replicas differ); the Adam moments start at zero everywhere.  Called after build_model and load_model."""
+        built replicas differ); the Adam moments start at zero everywhere.  Called after build_model and load_model.  Every
+        weight average that exists restarts from the weights (only a train state restores one that differs from them)."""
         parallel.broadcast_params(self.nets())
+        for opt in self.ema_opts().values():
+            opt.reset_ema()
+
+    def ema_opts(self):
+        """{checkpoint key of a net: its NetOpt} for every net that has a weight average now (steps built lazily count once they
+        exist), in the order of nets(); empty without ema."""
+        if self.ema is None:
+            return {}
+        s2, tclf = self.s2, self.tclf
+        opts = (('encoder', self.ae.opt['enc']), ('decoder', self.ae.opt['dec']), ('generator', s2.gen_opt if s2 is not None else None),
+                ('classifier', self.clf.opt), ('patch_discriminator', s2.patch_opt if s2 is not None else None),
+                ('target_classifier', tclf.opt if tclf is not None else None))
+        return {k: o for k, o in opts if o is not None and o.ema is not None}
 
     def reset_keep(self):
         self.model_kept = []
@@ -695,6 +715,13 @@ class Trainer(object):
             all_model['target_classifier'] = {'module.' + k: v for k, v in self.TargetClassifier.state_dict().items()}
         else:
             del all_model['classifier']
+        nets = dict(zip(train_state.NET_NAMES, self.nets()))
+        for key, opt in self.ema_opts().items():           # `<net>_ema`: the net's entry with the average in place of the weights
+            if key in all_model:
+                offs, sd = nets[key]._zs['offsets'], nets[key].state_dict()
+                pre = 'module.' if key in ('patch_discriminator', 'target_classifier') else ''
+                all_model[key + '_ema'] = {pre + k: (opt.ema[offs[k]:offs[k] + v.numel()].view(v.shape) if k in offs else v)
+                                           for k, v in sd.items()}
         all_model = {k: {n: t.detach().cpu().clone() for n, t in sd.items()} for k, sd in all_model.items()}
         new_model_path = '{}-{}-{}'.format(model_path, name, iteration)
         torch.save(all_model, new_model_path)
@@ -773,7 +800,7 @@ class Trainer(object):
         all_model = torch.load(ckpt_path, map_location='cpu', weights_only=True)
         for key, net in zip(train_state.NET_NAMES, self.nets()):
             net.load_state_dict({(k[7:] if k.startswith('module.') else k): v for k, v in all_model[key].items()})
-        self.sync_params()
+        self.sync_params()                                                # (the averages restart from these weights; load_state follows)
 
     def _reserve(self, srcs):
         """(device snapshot buffers, pinned host buffers) for the tensors `srcs`, allocated when their shapes first appear."""
@@ -825,11 +852,14 @@ class Trainer(object):
     def _ckpt_sources(self, tree):
         """What a resumable checkpoint copies: (srcs, layout, skel).  srcs: the device tensors (flat parameter buffers, moments, words);
         layout: per net (checkpoint key, key prefix, [(parameter name, index into srcs, offset, numel, shape)]), in
-        state_dict order; skel: the state tree with every device tensor replaced by its index into srcs (_Slot)."""
-        srcs, layout = [], []
+        state_dict order; skel: the state tree with every device tensor replaced by its index into srcs (_Slot).  With weight
+        averages the layout goes on with the `<net>_ema` entries: the net's entries over the average's slot -- the one the state
+        tree put it in, where the tree carries that optimizer: one copy serves the state file and the checkpoint."""
+        srcs, layout, flat_slot = [], [], {}
         for key, net in zip(train_state.NET_NAMES, self.nets()):
             flat, offs = net.flat_params()[0], net._zs['offsets']
             slot, ents = len(srcs), []
+            flat_slot[key] = slot
             srcs.append(flat)
             for k, v in net.state_dict().items():
                 if k in offs:
@@ -839,18 +869,36 @@ class Trainer(object):
                     srcs.append(v.detach().reshape(-1))
             layout.append((key, 'module.' if key in ('patch_discriminator', 'target_classifier') else '', ents))
 
+        slot_of = {}                                                      # data_ptr of a device tensor of the tree -> its slot
+
         def grab(t):
             if t.device.type == 'cpu':
                 return t.clone()
             srcs.append(t.detach())
+            slot_of[t.data_ptr()] = len(srcs) - 1
             return _Slot(len(srcs) - 1)
-        return srcs, layout, train_state.map_tensors(tree, grab)
+        skel = train_state.map_tensors(tree, grab)
+        for key, opt in self.ema_opts().items():
+            slot = slot_of.get(opt.ema.data_ptr())
+            if slot is None:                                              # a net this mode's state does not carry
+                slot = len(srcs)
+                srcs.append(opt.ema)
+            _, pre, ents = layout[train_state.NET_NAMES.index(key)]
+            layout.append((key + '_ema', pre, [(k, slot if s == flat_slot[key] else s, o, n, shape) for k, s, o, n, shape in ents]))
+        return srcs, layout, skel
 
-    def load_model(self, model_path, load_model_list, verbose=True, clf_path=None):
+    def load_model(self, model_path, load_model_list, verbose=True, clf_path=None, use_ema=False):
+        """use_ema (not in the reference): each net is taken from the file's `<net>_ema` entry, the weight average a run with
+        Trainer(ema=...) saved, where the file has one (else from `<net>`; the printed tag says which); ValueError when
+        model_path has no such entry at all -- whatever clf_path holds: that file only lends its target_classifier, averaged
+        where it has the average."""
         if verbose:
             print('[Trainer] - load model from {}'.format(model_path))
         load_model_list = load_model_list.split(', ')
         all_model = torch.load(model_path, map_location='cpu', weights_only=True)
+        src = {k: k for k in train_state.NET_NAMES}
+        if use_ema:
+            src = train_state.ema_keys(all_model.keys(), train_state.NET_NAMES, model_path)
         if verbose:
             print('[Trainer] - ', end='')
         strip = lambda sd: {(k[7:] if k.startswith('module.') else k): v for k, v in sd.items()}
@@ -862,10 +910,12 @@ class Trainer(object):
                 try:
                     if key == 'target_classifier' and clf_path is not None:        # trainer.py:157-161: taken from ANOTHER checkpoint
                         clf_model = torch.load(clf_path, map_location='cpu', weights_only=True)
-                        net.load_state_dict(strip(clf_model['target_classifier']))
-                        tag = 'target_classifier_another'
+                        avg = use_ema and 'target_classifier_ema' in clf_model
+                        net.load_state_dict(strip(clf_model['target_classifier_ema' if avg else 'target_classifier']))
+                        tag = 'target_classifier_ema_another' if avg else 'target_classifier_another'
                     else:
-                        net.load_state_dict(strip(all_model[key]))
+                        net.load_state_dict(strip(all_model[src[key]]))
+                        tag = src[key]
                     if key == 'target_classifier':
                         self.tclf_loaded = True
                     if verbose:
@@ -989,7 +1039,7 @@ class Trainer(object):
     def tclf_step(self):
         if self.tclf is None:
             self.tclf = TclfStep(self.TargetClassifier, self.hps.lr, self.hps.max_grad_norm,
-                                 self.hps.n_speakers - self.hps.n_target_speakers)
+                                 self.hps.n_speakers - self.hps.n_target_speakers, ema=self.ema)
         return self.tclf
 
     def _tclf_batch(self):
