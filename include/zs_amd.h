@@ -708,6 +708,41 @@ typedef struct {
   float* dst;
 } ZsFragGather;
 int zs_frag_gather(const ZsFragGather* p, void* stream);
+/* Bit-packed units.  A unit is one encoded frame of E columns of 0 / 1 (what write_encodings stores as a line of text); packed, it is
+ * a row of row_bytes >= (E + 7) / 8 bytes: bit j of byte k is column 8k + j (numpy.packbits(bitorder='little') along the columns),
+ * the unused high bits of the last byte zero.  `packed` is one device buffer [n_units][row_bytes] holding every utterance of a batch;
+ * start (int64 [n_frag], a row of `packed`) and len (int32 [n_frag]) are device tables planned on the host.  In both kernels one lane
+ * produces each output byte / 16-byte piece whole: no read-modify-write, no atomics, a launch is bitwise reproducible and fragment f
+ * touches its own rows only.  No allocation, no synchronisation.  n_frag == 0 succeeds and launches nothing; n_frag outside
+ * [0, ZS_UNITS_MAX_FRAG] (the fragments of a launch are strided over at most 65535 grid rows), a null operand with work to do,
+ * E <= 0, T <= 0, ld < E or row_bytes < (E + 7) / 8 launch nothing and return ZS_EINVAL.
+ *
+ * zs_units_unpack: packed units straight into the Decoder's input operand of one inference chunk (what permute + contiguous + float
+ * + zs_cast_rows(fill_cols = ld_dst) build from fp32 [B, E, T'], model/model.py:346).  dst [n_frag][T][ld_dst] of `dtype`, 16-byte
+ * aligned, ld_dst a multiple of 8, written with 16-byte stores:
+ *   dst[f][t][c] = bit(packed[start[f] + t], c) ? 1 : 0      t < len[f], c < E
+ *   dst[f][t][c] = 0                                         len[f] <= t < T, or E <= c < ld_dst
+ * An entry with len < 0, len > T, start < 0 or start + len > n_units writes a zero fragment and reads nothing (as zs_frag_gather). */
+#define ZS_UNITS_MAX_FRAG 1048576
+typedef struct {
+  int32_t dtype;
+  const uint8_t* packed; int64_t n_units; int32_t row_bytes, E;
+  const int64_t* start; const int32_t* len; int32_t n_frag, T;
+  void* dst; int64_t ld_dst;
+} ZsUnitsUnpack;
+int zs_units_unpack(const ZsUnitsUnpack* p, void* stream);
+/* zs_units_pack: the inverse, for the encoder's output rows.  src [n_frag][T][ld_src], read in place: fp32 when src_f32, else `dtype`
+ * (the engine's own `bits` buffer); 16-byte loads when src is 16-byte aligned and ld_src a multiple of 8 (4 for fp32).
+ *   packed[start[f] + t] = the bits (src[f][t][c] != 0), c < E; every byte of the row's row_bytes is written      t < len[f]
+ * Rows t >= len[f] are not read and nothing is written for them (the MIN_LEN truncation of convert.py:148-149 is a shorter len).
+ * An entry out of range (as above) reads and writes nothing. */
+typedef struct {
+  int32_t dtype, src_f32;
+  const void* src; int64_t ld_src; int32_t n_frag, T, E;
+  const int64_t* start; const int32_t* len;
+  uint8_t* packed; int64_t n_units; int32_t row_bytes;
+} ZsUnitsPack;
+int zs_units_pack(const ZsUnitsPack* p, void* stream);
 /* zs_tclf_score: the scoring loop of target_classify (convert.py:400-413) on the device.  logits fp32 [n_frag][ld] (3 valid columns),
  * target int32 [n_frag] (0 V001, 1 V002, 2 'None', -1 any other speaker: never correct):
  *   pred[f] = argmax_j logits[f][j] (first maximum, NaN as the maximum: numpy's rule; pred may be null)

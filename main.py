@@ -12,8 +12,12 @@
   python main.py --convert_dir DIR --t_speaker V001,V002 [--enc_only] [--ckpt_pth CKPT]    (every *.wav of DIR, any format and
                                                            rate, to each target: {result_dir}/{sub_result_dir}/convert/
                                                            {target}/{stem}.wav + .txt and convert_dir.json)
+  python main.py --synth_dir DIR --t_speaker V001,V002 [--enc_only] [--ckpt_pth CKPT]      (every *.txt of DIR, unit files as
+                                                           --test_encode / --convert_dir write them, spoken by each target:
+                                                           {result_dir}/{sub_result_dir}/synth/{target}/{stem}.wav and
+                                                           synth_dir.json)
 
-Vocoder of --test, --cross_test, --test_single and --convert_dir: --gl_iters N sets the Griffin-Lim iterations (hp.n_iter,
+Vocoder of --test, --cross_test, --test_single, --convert_dir and --synth_dir: --gl_iters N sets the Griffin-Lim iterations (hp.n_iter,
 default 300), --gl_momentum A in [0, 1) the fast Griffin-Lim momentum (hp.gl_momentum, default 0: the reference's plain loop), e.g.
 `--gl_iters 100 --gl_momentum 0.99`.  --out_sr N writes their wavs at N Hz instead of 16000 (hp.out_sr; band-limited resampling
 on the GPU, zs_amd.resample), e.g. `--out_sr 44100`; N / 16000 must lie within [1/32, 32].
@@ -30,7 +34,7 @@ or from iteration 0 when there is none: the same command starts a run and restar
 
 --ema D with any --train* mode (D in [0, 1), e.g. 0.999): every optimizer keeps an exponential moving average of its net's weights,
 updated inside the Adam kernels; every checkpoint then carries `<net>_ema` entries beside the raw weights, and --resume continues the
-averages bit for bit.  --use_ema with --test, --cross_test, --test_encode, --test_single, --test_classify or --convert_dir
+averages bit for bit.  --use_ema with --test, --cross_test, --test_encode, --test_single, --test_classify, --convert_dir or --synth_dir
 converts with the averaged weights of the checkpoint; with --load_model a training run starts from them, e.g. stage 2 from the
 averaged autoencoder: `--train_tgat --load_model --use_ema --ema 0.999`.  Where a flag would have no effect (--ema without a
 training mode, --use_ema without a mode that loads a checkpoint) it is refused before anything is built.
@@ -123,10 +127,13 @@ def build_parser():
     p.add_argument('--ckpt_pth', type=str, default=None)
     p.add_argument('--load_tclf_model_name', type=str, default=None)     # main.py:79: a path, used as given
     p.add_argument('--s_speaker', type=str, default='S015')
-    p.add_argument('--t_speaker', type=str, default='V002', help='target speaker; with --convert_dir a comma-separated list')
+    p.add_argument('--t_speaker', type=str, default='V002', help='target speaker; with --convert_dir / --synth_dir a comma-separated list')
     p.add_argument('--convert_dir', type=str, default=None, metavar='DIR',
                    help='convert every *.wav of DIR (any PCM / float format, any rate) to each --t_speaker, on the GPU from the '
                         'samples to the waveform; outputs under {result_dir}/{sub_result_dir}/convert/')
+    p.add_argument('--synth_dir', type=str, default=None, metavar='DIR',
+                   help='synthesise every *.txt of DIR (unit files: one line of 0 / 1 per encoded frame) in the voice of each '
+                        '--t_speaker; outputs under {result_dir}/{sub_result_dir}/synth/')
     p.add_argument('--gl_iters', type=_gl_iters, default=None, help='Griffin-Lim iterations (hp.n_iter); default: leave hp as it is')
     p.add_argument('--gl_momentum', type=_gl_momentum, default=None,
                    help='fast Griffin-Lim momentum in [0, 1) (hp.gl_momentum); default: leave hp as it is')
@@ -134,7 +141,7 @@ def build_parser():
                    help='every --train* mode: keep an exponential moving average of the weights with decay D in [0, 1), updated in '
                         'the Adam kernels; checkpoints gain <net>_ema entries; default: none')
     p.add_argument('--use_ema', default=False, action='store_true',
-                   help='load the averaged weights (<net>_ema) of the checkpoint: every --test* mode, --cross_test, --convert_dir, and '
+                   help='load the averaged weights (<net>_ema) of the checkpoint: every --test* mode, --cross_test, --convert_dir, --synth_dir, and '
                         'training with --load_model')
     p.add_argument('--out_sr', type=_out_sr, default=None,
                    help='sample rate of the wavs --test / --cross_test / --test_single write (hp.out_sr); default: 16000')
@@ -169,18 +176,19 @@ LOADING_MODES = ['test', 'cross_test', 'test_encode', 'test_single', 'test_class
 def check_ema(args):
     """--ema averages the weights a training run updates, --use_ema chooses what a checkpoint is loaded from: each is refused,
     before anything is built, where it would have no effect -- --ema without a --train* mode, --use_ema without a mode that loads
-    a checkpoint (a --test* mode, --cross_test, --convert_dir, or a --train* mode with --load_model)."""
+    a checkpoint (a --test* mode, --cross_test, --convert_dir, --synth_dir, or a --train* mode with --load_model)."""
     training = any(getattr(args, f) for f in TRAIN_MODES)
     if args.ema is not None and not training:
         raise ValueError('--ema needs a training mode (%s)' % ', '.join('--' + f for f in TRAIN_MODES))
-    loads = any(getattr(args, f) for f in LOADING_MODES) or args.convert_dir is not None or (training and args.load_model)
+    loads = any(getattr(args, f) for f in LOADING_MODES) or args.convert_dir is not None or args.synth_dir is not None or \
+        (training and args.load_model)
     if args.use_ema and not loads:
         raise ValueError('--use_ema needs a mode that loads a checkpoint: %s, --convert_dir, or a training mode with --load_model'
                          % ', '.join('--' + f for f in LOADING_MODES))
 
 
 def convert_targets(args):
-    """--convert_dir takes --t_speaker as a comma-separated list of distinct names (--test_single keeps the single name): the
+    """--convert_dir and --synth_dir take --t_speaker as a comma-separated list of distinct names (--test_single keeps the single name): the
     list, refused before anything is built when it names no speaker or one twice."""
     names = [t.strip() for t in args.t_speaker.split(',')]
     if not all(names):
@@ -196,7 +204,7 @@ def argument_runner(argv=None):
     args = parser.parse_args(argv)
     check_resume(args)
     check_ema(args)
-    args.t_speakers = convert_targets(args) if args.convert_dir is not None else None
+    args.t_speakers = convert_targets(args) if (args.convert_dir is not None or args.synth_dir is not None) else None
     if args.dataset == 'surprise':            # main.py:83-88: english -> surprise in every default path
         for action in parser._actions:
             if isinstance(action.default, str) and 'english' in action.default and \
@@ -229,7 +237,7 @@ def main(argv=None):
     if bad:
         raise NotImplementedError('--%s is outside the stage-1 autoencoder hot path this build covers' % bad[0])
     from zs_amd import parallel
-    from zs_amd.convert import convert_dir, cross_test, get_trainer, target_classify, test_encode, test_from_list, test_single
+    from zs_amd.convert import convert_dir, cross_test, get_trainer, synth_dir, target_classify, test_encode, test_from_list, test_single
     from zs_amd.dataloader import DataLoader, Dataset, SyntheticDataset
     from zs_amd.trainer import Trainer
 
@@ -283,7 +291,8 @@ def main(argv=None):
             print("[Runner] - --train ran the pretrain_AE and patchGAN stages; the reference's autolocker / t_classify / Tacotron "
                   'stages are not part of this build and were skipped')
 
-    if args.test or args.cross_test or args.test_encode or args.test_single or args.test_classify or args.convert_dir is not None:
+    if args.test or args.cross_test or args.test_encode or args.test_single or args.test_classify or args.convert_dir is not None or \
+            args.synth_dir is not None:
         os.makedirs(args.result_dir, exist_ok=True)
         model_path = args.ckpt_pth if args.ckpt_pth is not None else os.path.join(args.ckpt_dir, args.load_test_model_name)
         trainer = get_trainer(args.hps_path, model_path, args.g_mode, args.enc_mode, args.load_tclf_model_name, use_ema=args.use_ema)
@@ -302,6 +311,9 @@ def main(argv=None):
         if args.convert_dir is not None:                  # not in the reference: a folder of sound files to the target voices
             convert_dir(trainer, hps.seg_len, args.convert_dir, args.speaker2id_path, os.path.join(result_dir, 'convert'), args.t_speakers,
                         args.enc_only)
+        if args.synth_dir is not None:                    # not in the reference: a folder of unit files spoken by the target voices
+            synth_dir(trainer, hps.seg_len, args.synth_dir, args.speaker2id_path, os.path.join(result_dir, 'synth'), args.t_speakers,
+                      args.enc_only)
 
 
 if __name__ == '__main__':

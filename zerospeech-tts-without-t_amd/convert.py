@@ -6,7 +6,8 @@ call Trainer.test_step / encoder_test_step per fragment and concatenate.  spectr
 griffin_lim() run the 300-iteration Griffin-Lim on the MI355X (zs_gl_* kernels: 1024-point FFTs in LDS),
 batched over utterances by griffin_lim_batch(); `momentum` (default hp.gl_momentum = 0) selects the fast Griffin-Lim of
 Perraudin et al. (2013), as librosa / torchaudio name it; de-preemphasis on the device, librosa.effects.trim restated
-on the host (librosa itself is not required).  Utterances are independent: multi-GPU = replicas over a
+on the host (librosa itself is not required).  synth_units_batch() / synth_dir() go the other way from the unit files alone
+(bit-packed units, zs_units_unpack into the Decoder's operand; not in the reference).  Utterances are independent: multi-GPU = replicas over a
 sharded utterance list (zs_amd.parallel.shard_range), no collective.
 """
 import ctypes
@@ -279,6 +280,64 @@ def write_encodings(path, encodings):
             file.write('\n')
 
 
+def read_units(path, E):
+    """The parser of what write_encodings writes: one line of E tokens `0` / `1` per unit -> float32 [U, E].  ValueError naming the
+    file and the line for a line of another width or a token other than 0 / 1, and for a file without a line."""
+    rows = []
+    with open(path, 'r') as f:
+        for no, line in enumerate(f, 1):
+            tokens = line.split()
+            if len(tokens) != E:
+                raise ValueError('%s, line %d: %d values, expected %d' % (path, no, len(tokens), E))
+            bad = [t for t in tokens if t not in ('0', '1')]
+            if bad:
+                raise ValueError('%s, line %d: %r is not 0 or 1' % (path, no, bad[0]))
+            rows.append([t == '1' for t in tokens])
+    if not rows:
+        raise ValueError('%s: no units (the file is empty)' % path)
+    return np.asarray(rows, dtype=np.float32)
+
+
+def pack_units(units):
+    """[U, E] of 0 / 1 -> uint8 [U, (E + 7) // 8]: bit j of byte k of a row is column 8k + j (numpy.packbits(bitorder='little')
+    along the columns), the unused high bits of a row's last byte zero.  This and unpack_units are the definition zs_units_pack and
+    zs_units_unpack are tested against.  ValueError on any other value."""
+    u = np.asarray(units)
+    if u.ndim != 2:
+        raise ValueError('pack_units: units must be [U, E] (got shape %s)' % (u.shape,))
+    if not np.logical_or(u == 0, u == 1).all():
+        raise ValueError('pack_units: units must be 0 or 1')
+    return np.packbits(u != 0, axis=1, bitorder='little').reshape(u.shape[0], (u.shape[1] + 7) // 8)
+
+
+def unpack_units(packed, E):
+    """uint8 [U, (E + 7) // 8] -> float32 [U, E], the inverse of pack_units."""
+    p = np.asarray(packed)
+    if p.dtype != np.uint8 or p.ndim != 2 or p.shape[1] != (E + 7) // 8:
+        raise ValueError('unpack_units: packed must be uint8 [U, %d] for E = %d (got %s %s)' % ((E + 7) // 8, E, p.dtype, p.shape))
+    return np.unpackbits(p, axis=1, count=E, bitorder='little').astype(np.float32).reshape(p.shape[0], E)
+
+
+def unit_fragments(n_units, seg_len):
+    """The fragment rule on unit counts: the lengths, in units, of the pieces an utterance of n_units units is decoded in.  With
+    Lu = seg_len // 8: pieces of Lu while more than 2 Lu units remain, then one tail of what is left (1 .. 2 Lu units); an
+    utterance of at most 2 Lu units is one fragment.
+    These are the unit lengths fragments() and _t8 give an utterance of n >= MIN_LEN frames, for every n except
+      n = 1 (mod seg_len) with n >= 2 seg_len + 1,   and   n = 0 (mod seg_len) with n >= 3 seg_len:
+    there the reference's tail is exactly seg_len frames, Lu units, and [.., Lu, Lu] cannot be told from a tail of 2 Lu by the unit
+    count alone.  Where the rule reproduces the fragmentation, synthesis from units equals convert(); in the two exceptions it is a
+    decode of the same units with one boundary fewer."""
+    n, Lu = int(n_units), int(seg_len) // 8
+    if n < 1 or Lu < 1:
+        raise ValueError('unit_fragments: need n_units >= 1 and seg_len >= 8 (got %d, %d)' % (n, seg_len))
+    out = []
+    while n > 2 * Lu:
+        out.append(Lu)
+        n -= Lu
+    out.append(n)
+    return out
+
+
 def convert(trainer, seg_len, src_speaker_spec, src_speaker, tar_speaker, utt_id, speaker2id, result_dir, enc_only=True,
             save=['wav', 'enc']):
     src_speaker_spec, PADDED = _pad_min(src_speaker_spec)
@@ -377,7 +436,7 @@ def _t8(n):
 class _Enqueued(object):
     """What _enqueue_encode leaves behind: nothing here has been waited for.  With the generator (enc_only=False), `conv` holds
     the converted spectrograms [n_utt, T_max, 513] fp32 on the device (amplitudes when de-normalised) and `ulens` their frames."""
-    __slots__ = ('n_utt', 'chunks', 'enc_host', 'dec_dev', 'dec_host', 'enc_done', 'dev', 'conv', 'ulens')
+    __slots__ = ('n_utt', 'chunks', 'enc_host', 'dec_dev', 'dec_host', 'enc_done', 'dev', 'conv', 'ulens', 'units_host', 'uoffs')
 
 
 GEN_COMBINE = {'naive': 1, 'targeted': 1, 'spectrogram': 1, 'targeted_residual': 2}     # zs_gen_scatter modes (trainer.py:206-213)
@@ -401,12 +460,61 @@ def check_gen_targets(trainer, speakers):
     return shift
 
 
-def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host, enc_only=True, denorm=False):
+def _decode_chunk(trainer, ci, utts, lens_p, decode_speakers, enc_only, gen_plan, rows):
+    """The decode half of one chunk, shared by _enqueue_encode and synth_units_batch: the Decoder and, with the generator
+    (enc_only=False), the generator and zs_gen_scatter into gen_plan's buffer.  utts: the utterance of each fragment; lens_p: encoded
+    frames per fragment of a ragged chunk, None for a plain one; rows(ch, lens_p) -> (bits, x_dec) as Decoder.forward_rows returns
+    them; gen_plan = (conv, dsts, shift, denorm).  Returns a copy of the decoded rows [n, 8 T', 513] (enc_only), else None."""
+    dev = trainer.device
+    ch = torch.tensor([decode_speakers[u] for u in utts], dtype=torch.int64).to(dev, non_blocking=True)
+    # the engines directly (the modules would clone their outputs): x_dec and the generator's rows are read in place
+    bits, xr = rows(ch, lens_p)
+    if enc_only:
+        return xr.valid().clone(memory_format=torch.contiguous_format)
+    conv, dsts, shift, denorm = gen_plan
+    gen = trainer.Generator._engine()
+    cg = (ch - shift) if shift else ch                                       # trainer.py:207-213
+    if trainer.g_mode == 'spectrogram':                                      # G(x_dec, c - shift), T = 8 T' frames per sample
+        m = gen.forward(xr, cg, False, lengths=([8 * n for n in lens_p] if lens_p is not None else None))
+    else:                                                                    # G(enc, c [- shift]) on the decoder's own input
+        m = gen.forward(bits, cg, False, lengths=lens_p)
+    dst = dsts[ci]
+    if dst.numel() != xr.B * xr.T or m.B * m.T != xr.B * xr.T:
+        raise L.ZsError('conversion chunk %d: %d destination rows for %d output rows' % (ci, dst.numel(), xr.B * xr.T))
+    L.call('zs_gen_scatter', 'ZsGenScatter', torch.cuda.current_stream(dev).cuda_stream, xd=xr.ptr(), ld_xd=xr.ld, m=m.ptr(),
+           ld_m=m.ld, dst=L.ptr(dst), rows=dst.numel(), amp=L.ptr(conv), amp_ld=conv.shape[2], amp_rows=conv.shape[0] * conv.shape[1],
+           mode=GEN_COMBINE[trainer.g_mode], denorm=int(denorm))
+    return None
+
+
+def _plan_pack(items, chunks, n_utt, dev):
+    """Where zs_units_pack puts every fragment's units: utterance u's units are its fragments' in fragment order, the utterances back
+    to back in one buffer.  Returns (row offsets of the utterances [n_utt + 1], per chunk the device tables (start int64, len int32));
+    len is the MIN_LEN truncation where an item carries one.  All tables go to the device in one copy each."""
+    n_of = {(u, k): (trunc if trunc is not None else _t8(b - a)) for (u, k, a, b, trunc) in items}
+    at, counts = {}, [0] * n_utt
+    for (u, k) in sorted(n_of):
+        at[(u, k)] = counts[u]
+        counts[u] += n_of[(u, k)]
+    uoffs = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+    starts = np.array([uoffs[u] + at[(u, k)] for chunk, _ in chunks for (u, k, _, _, _) in chunk], dtype=np.int64)
+    lens = np.array([n_of[(u, k)] for chunk, _ in chunks for (u, k, _, _, _) in chunk], dtype=np.int32)
+    sizes = [len(chunk) for chunk, _ in chunks]
+    st_d = torch.split(torch.from_numpy(starts).to(dev, non_blocking=True), sizes)
+    ln_d = torch.split(torch.from_numpy(lens).to(dev, non_blocking=True), sizes)
+    return uoffs, list(zip(st_d, ln_d))
+
+
+def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host, enc_only=True, denorm=False, pack=False):
     """Fragment rule + every Encoder / Decoder launch of a batch of utterances, WITHOUT a host synchronisation: the caller decides
     what else to put on the stream (the vocoder) before it waits.
     enc_only=False (decode_speakers required): the stage-2 generator as well, and zs_gen_scatter writes every chunk's converted rows
     into q.conv right behind it (de-normalised when `denorm`): the engines reuse their output buffers for the next chunk of the
-    same shape."""
+    same shape.
+    pack: zs_units_pack writes every chunk's units, bit-packed, to their utterance's place in one device buffer, and ONE copy
+    brings them to the host (q.units_host, q.uoffs) instead of a fp32 copy per chunk."""
+    if pack and trainer.enc_mode == 'continues':
+        raise ValueError("enc_mode 'continues' has no units to pack (its encodings are not 0 / 1)")
     if not enc_only:
         if decode_speakers is None:
             raise ValueError('conversion with the generator (enc_only=False) needs the target speakers')
@@ -442,11 +550,15 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
     zero_row = int(offs[-1])
     q = _Enqueued()
     q.n_utt, q.dev, q.chunks, q.enc_host, q.dec_dev, q.dec_host = len(specs), dev, [], [], [], []
-    q.conv = q.ulens = None
+    q.conv = q.ulens = q.units_host = q.uoffs = None
+    gen_plan = None
     if not enc_only:
         q.conv, q.ulens, dsts = _plan_scatter(items, chunks, len(specs), denorm, dev)
-        gen = trainer.Generator._engine()
-        mode = GEN_COMBINE[trainer.g_mode]
+        gen_plan = (q.conv, dsts, shift, denorm)
+    if pack:
+        q.uoffs, pack_tabs = _plan_pack(items, chunks, len(specs), dev)
+        row_bytes = (enc.enc_size + 7) // 8
+        units_dev = torch.empty(int(q.uoffs[-1]), row_bytes, dtype=torch.uint8, device=dev)
     for ci, (chunk, ragged) in enumerate(chunks):
         lens = [b - a for (_, _, a, b, _) in chunk]
         Tm = max(lens)
@@ -457,43 +569,37 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
         G = noise_fn(len(chunk), _t8(Tm), enc.enc_size) if noise_fn is not None else None
         act, _ = enc(x.permute(0, 2, 1), G=G, lengths=(lens if ragged else None))
         xd = None
-        if decode_speakers is not None and enc_only:
-            ch = torch.tensor([decode_speakers[u] for (u, _, _, _, _) in chunk], dtype=torch.int64)
-            lens_p = [_t8(n) for n in lens]
-            xd = dec(act, ch.to(dev, non_blocking=True), lengths=(lens_p if ragged else None)).permute(0, 2, 1).contiguous()
-        elif not enc_only:
-            # the engines directly (the modules would clone their outputs): x_dec and the generator's rows are read in place
-            ch = torch.tensor([decode_speakers[u] for (u, _, _, _, _) in chunk], dtype=torch.int64).to(dev, non_blocking=True)
-            lens_p = [_t8(n) for n in lens]
-            bits, xr = dec.forward_rows(act, ch, lengths=(lens_p if ragged else None))
-            cg = (ch - shift) if shift else ch                                   # trainer.py:207-213
-            if trainer.g_mode == 'spectrogram':                                  # G(x_dec, c - shift), T = 8 T' frames per sample
-                m = gen.forward(xr, cg, False, lengths=([8 * n for n in lens_p] if ragged else None))
-            else:                                                                # G(enc, c [- shift]) on the decoder's own input
-                m = gen.forward(bits, cg, False, lengths=(lens_p if ragged else None))
-            dst = dsts[ci]
-            if dst.numel() != xr.B * xr.T or m.B * m.T != xr.B * xr.T:
-                raise L.ZsError('conversion chunk %d: %d destination rows for %d output rows' % (ci, dst.numel(), xr.B * xr.T))
-            L.call('zs_gen_scatter', 'ZsGenScatter', torch.cuda.current_stream(dev).cuda_stream, xd=xr.ptr(), ld_xd=xr.ld, m=m.ptr(),
-                   ld_m=m.ld, dst=L.ptr(dst), rows=dst.numel(), amp=L.ptr(q.conv), amp_ld=q.conv.shape[2],
-                   amp_rows=q.conv.shape[0] * q.conv.shape[1], mode=mode, denorm=int(denorm))
+        if decode_speakers is not None:
+            xd = _decode_chunk(trainer, ci, [it[0] for it in chunk], ([_t8(n) for n in lens] if ragged else None), decode_speakers,
+                               enc_only, gen_plan, lambda ch, lens_p: dec.forward_rows(act, ch, lengths=lens_p))
         q.chunks.append((chunk, lens))
-        q.enc_host.append(_to_host(act.permute(0, 2, 1).contiguous()))
+        if pack:                                              # the engine's own bits buffer, read in place
+            bits = enc._last_bits
+            L.call('zs_units_pack', 'ZsUnitsPack', torch.cuda.current_stream(dev).cuda_stream, dtype=enc._zs['ctx'].dt, src_f32=0,
+                   src=bits.ptr(), ld_src=bits.ld, n_frag=len(chunk), T=bits.T, E=enc.enc_size, start=L.ptr(pack_tabs[ci][0]),
+                   len=L.ptr(pack_tabs[ci][1]), packed=L.ptr(units_dev), n_units=units_dev.shape[0], row_bytes=row_bytes)
+            q.enc_host.append(None)
+        else:
+            q.enc_host.append(_to_host(act.permute(0, 2, 1).contiguous()))
         q.dec_dev.append(xd)
         q.dec_host.append(_to_host(xd) if (xd is not None and dec_to_host) else None)
+    if pack:
+        q.units_host = _to_host(units_dev)
     q.enc_done = torch.cuda.Event()
     q.enc_done.record(torch.cuda.current_stream(dev))
     return q
 
 
-def _plan_scatter(items, chunks, n_utt, denorm, dev):
+def _plan_scatter(items, chunks, n_utt, denorm, dev, rows_of=None):
     """The converted spectrograms' buffer [n_utt, T_max, 513] and, per chunk, the destination row of each of its output rows
     (b*T + t -> u*T_max + frame, -1 past a fragment's 8 T' rows): utterance u's frames are its fragments' rows in fragment order.
     The padding rows (frames past an utterance's length) are filled here, once: what the per-utterance path gives them,
-    (denorm of) zero.  All destination tables go to the device in one copy."""
+    (denorm of) zero.  All destination tables go to the device in one copy.
+    rows_of(n): the output rows of a fragment of n = b - a (default: n frames in, 8 * _t8(n) rows out)."""
+    rows_of = rows_of or (lambda n: 8 * _t8(n))
     out_rows = {}
     for (u, k, a, b, _) in items:
-        out_rows[(u, k)] = 8 * _t8(b - a)
+        out_rows[(u, k)] = rows_of(b - a)
     start, ulens = {}, [0] * n_utt
     for (u, k) in sorted(out_rows):
         start[(u, k)] = ulens[u]
@@ -501,7 +607,7 @@ def _plan_scatter(items, chunks, n_utt, denorm, dev):
     Tm = max(ulens)
     tables = []
     for chunk, _ in chunks:
-        T = 8 * _t8(max(b - a for (_, _, a, b, _) in chunk))
+        T = rows_of(max(b - a for (_, _, a, b, _) in chunk))
         d = np.full((len(chunk), T), -1, dtype=np.int32)
         for i, (u, k, _, _, _) in enumerate(chunk):
             n = out_rows[(u, k)]
@@ -525,8 +631,9 @@ def _assemble(q, want_dec):
     """Per-utterance encodings (and decoded spectrograms: 'host', 'device' or None) from the chunk outputs, in fragment order.
     The caller has waited for the copies."""
     enc_out, dec_out = {}, {}
+    units = q.units_host.numpy() if q.units_host is not None else None      # packed: one buffer, utterance by utterance
     for ci, (chunk, lens) in enumerate(q.chunks):
-        e = q.enc_host[ci].numpy()
+        e = q.enc_host[ci].numpy() if units is None else None
         xd = None
         if want_dec == 'host':
             xd = q.dec_host[ci].numpy()
@@ -534,7 +641,7 @@ def _assemble(q, want_dec):
             xd = q.dec_dev[ci]
         for i, (u, k, _, _, trunc) in enumerate(chunk):
             tp = _t8(lens[i])
-            enc_out[(u, k)] = e[i][:trunc] if trunc is not None else e[i][:tp]
+            enc_out[(u, k)] = None if units is not None else (e[i][:trunc] if trunc is not None else e[i][:tp])
             if xd is not None:
                 dec_out[(u, k)] = xd[i][:8 * tp]
     by_utt = {}
@@ -543,14 +650,14 @@ def _assemble(q, want_dec):
     encs, decs = [], ([] if want_dec else None)
     for u in range(q.n_utt):
         ks = sorted(by_utt[u])
-        encs.append(np.concatenate([enc_out[(u, k)] for k in ks], axis=0))
+        encs.append(np.concatenate([enc_out[(u, k)] for k in ks], axis=0) if units is None else units[q.uoffs[u]:q.uoffs[u + 1]].copy())
         if decs is not None:
             parts = [dec_out[(u, k)] for k in ks]
             decs.append(np.concatenate(parts, axis=0) if want_dec == 'host' else (parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)))
     return encs, decs
 
 
-def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, max_batch=256, to_host=True, enc_only=True):
+def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, max_batch=256, to_host=True, enc_only=True, packed=False):
     """Batched encode()/convert() for many utterances: the same fragments the reference would send through the network one by
     one (convert.py:151-165), as a few large batches on the GPU.
     specs: list of [T_i, 513] arrays (host arrays, or torch tensors already on the device).  decode_speakers: optional list of
@@ -560,8 +667,12 @@ def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, m
     longest member).  Returns (encodings list, decoded list or None); to_host=False leaves the decoded spectrograms on the
     device (torch tensors [T_out, 513]) for spectrogram2wav_batch.
     enc_only=False: convert() with the stage-2 generator (trainer.py:198-213) -- the decoded list holds the CONVERTED spectrograms
-    (normalised, as test_step returns them), bit for bit the concatenated per-fragment test_step outputs given the same noise."""
-    q = _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host=to_host, enc_only=enc_only)
+    (normalised, as test_step returns them), bit for bit the concatenated per-fragment test_step outputs given the same noise.
+    packed=True: the encodings come back bit-packed, uint8 [U_i, (E + 7) // 8] as pack_units defines them -- zs_units_pack writes
+    every fragment's units to its utterance's place in one device buffer and one D2H copy of E / 8 bytes per unit replaces the
+    per-chunk fp32 copies of 4 E bytes per unit (ValueError for enc_mode 'continues', whose encodings are not units)."""
+    q = _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host=to_host, enc_only=enc_only,
+                        pack=packed)
     conv_h = _to_host(q.conv) if (q.conv is not None and to_host) else None
     torch.cuda.current_stream(q.dev).synchronize()
     from . import layers
@@ -591,6 +702,14 @@ def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, 
         q = _enqueue_encode(specs, trainer, seg_len, speakers, noise_fn, max_batch, dec_to_host=False, enc_only=False, denorm=True)
         return _finish_resynth(q, _enqueue_vocoder(q.conv, q.ulens, n_iter, do_trim, q.dev, amplitudes=True, momentum=momentum), defer)
     q = _enqueue_encode(specs, trainer, seg_len, speakers, noise_fn, max_batch, dec_to_host=False)
+    t, ulens = _gather_decoded(q, [[8 * _t8(n) for n in lens] for _, lens in q.chunks])
+    return _finish_resynth(q, _enqueue_vocoder(t, ulens, n_iter, do_trim, q.dev, momentum=momentum), defer)
+
+
+def _gather_decoded(q, out_rows):
+    """The vocoder's padded input [n_utt, T_max, 513] fp32 from the decoded chunks q.dec_dev, by one index kernel on the device:
+    utterance u's frames are its fragments' rows in fragment order, zeros behind them.  out_rows[ci][i]: the valid output rows of
+    fragment i of chunk ci.  Returns (t, frames per utterance)."""
     dev = q.dev
     # row table of all decoded fragments + a zero row; utterance u's frames are its fragments' rows in order
     bases, total = [], 0
@@ -601,7 +720,7 @@ def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, 
     for ci, (chunk, lens) in enumerate(q.chunks):
         ld = q.dec_dev[ci].shape[1]
         for i, (u, k, _, _, _) in enumerate(chunk):
-            frag_rows.setdefault(u, []).append((k, bases[ci] + i * ld, 8 * _t8(lens[i])))
+            frag_rows.setdefault(u, []).append((k, bases[ci] + i * ld, out_rows[ci][i]))
     ulens = []
     for u in range(q.n_utt):
         frag_rows[u].sort()
@@ -614,8 +733,7 @@ def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, 
             idx[u, at:at + n] = np.arange(r0, r0 + n)
             at += n
     table = torch.cat([x.reshape(-1, x.shape[2]) for x in q.dec_dev] + [torch.zeros(1, q.dec_dev[0].shape[2], dtype=q.dec_dev[0].dtype, device=dev)], dim=0)
-    t = table[torch.from_numpy(idx).to(dev, non_blocking=True)].float()                               # [n, Tm, 513]
-    return _finish_resynth(q, _enqueue_vocoder(t, ulens, n_iter, do_trim, dev, momentum=momentum), defer)
+    return table[torch.from_numpy(idx).to(dev, non_blocking=True)].float(), ulens                     # [n, Tm, 513]
 
 
 def _finish_resynth(q, fin, defer):
@@ -627,6 +745,113 @@ def _finish_resynth(q, fin, defer):
             from . import layers
             layers.check_status(q.dev)                        # synchronises, clears the word and raises
         return encs, wavs
+    return finish if defer else finish()
+
+
+def _check_units(units, E, packed):
+    """The utterances of synth_units_batch as packed rows (uint8 [U_i, (E + 7) // 8]), checked on the host: ValueError for a width
+    other than E, a value other than 0 / 1 (packed: a bit set above column E) and an utterance of fewer than 2 units."""
+    row_bytes = (E + 7) // 8
+    out = []
+    for i, u in enumerate(units):
+        a = np.asarray(u.cpu() if torch.is_tensor(u) else u)
+        if packed:
+            if a.dtype != np.uint8 or a.ndim != 2 or a.shape[1] != row_bytes:
+                raise ValueError("utterance %d: packed units must be uint8 [U, %d] for the Decoder's %d columns (got %s %s)" %
+                                 (i, row_bytes, E, a.dtype, a.shape))
+            if E % 8 and (a[:, -1] >> (E % 8)).any():
+                raise ValueError('utterance %d: packed units have a bit set above column %d' % (i, E))
+        else:
+            if a.ndim != 2 or a.shape[1] != E:
+                raise ValueError("utterance %d: units must be [U, %d], the Decoder's input width (got shape %s)" % (i, E, a.shape))
+            try:
+                a = pack_units(a)
+            except ValueError:
+                raise ValueError('utterance %d: units must be 0 or 1' % i)
+        if a.shape[0] < 2:
+            raise ValueError('utterance %d has fewer than 2 units (the Decoder needs two rows; the one-unit files written for inputs '
+                             'shorter than MIN_LEN frames were decoded from two units and cannot be reproduced)' % i)
+        out.append(np.ascontiguousarray(a))
+    return out
+
+
+def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=None, do_trim=True, max_batch=256, defer=False,
+                      momentum=None, packed=False, want_specs=False):
+    """Speech from units: what resynth_batch does behind its encoder, from the units alone.  units: a list of [U_i, E] arrays of
+    0 / 1 as encode_batch returns them (what read_units parses from a --test_encode file); packed=True: a list of uint8
+    [U_i, (E + 7) // 8] arrays (pack_units, encode_batch(packed=True)).  speakers: the target id of each.
+    Every utterance goes to the device once, bit-packed, in one buffer; unit_fragments cuts each into the pieces the Decoder runs
+    on -- pieces of exactly seg_len // 8 units as plain batches, the rest as ragged batches, longest first, as _enqueue_encode
+    batches them -- zs_units_unpack writes each chunk's Decoder operand, the decode half is _enqueue_encode's own (_decode_chunk:
+    with enc_only=False the stage-2 generator and zs_gen_scatter), and the vocoder follows on the same stream.
+    Returns (specs or None, wavs): wavs as resynth_batch returns them; specs (want_specs=True) the normalised spectrograms
+    [8 U_i, 513] the vocoder was given.  defer=True returns the function that waits for this batch and returns that pair.
+    Where unit_fragments reproduces the fragmentation of the frames (see there) the result is resynth_batch's / convert()'s.
+    Refused before anything is enqueued: enc_mode 'continues' (its files are not units), a width other than the Decoder's c_in, a
+    value other than 0 / 1, fewer than 2 units (ValueError); a speaker the Decoder or the generator cannot take
+    (check_gen_targets)."""
+    momentum = gl_momentum(momentum)
+    if trainer.enc_mode == 'continues':
+        raise ValueError("enc_mode 'continues' has no units: its encodings are real-valued and cannot be synthesised from unit files")
+    if len(speakers) != len(units) or not len(units):
+        raise ValueError('synth_units_batch: %d target speakers for %d utterances' % (len(speakers), len(units)))
+    dec = trainer.Decoder
+    E, row_bytes = int(dec.c_in), (int(dec.c_in) + 7) // 8
+    rows = _check_units(units, E, packed)
+    bad = [int(c) for c in speakers if not 0 <= int(c) < int(dec.c_a)]
+    if bad:
+        raise ValueError('speaker id %d is outside [0, n_speakers = %d)' % (bad[0], dec.c_a))
+    shift = 0 if enc_only else check_gen_targets(trainer, speakers)
+    trainer.set_eval()
+    dev = trainer.device
+    Lu = int(seg_len) // 8
+    items = []                                            # (utt, order, first unit, stop, None): the item layout of _enqueue_encode
+    for u, r in enumerate(rows):
+        a = 0
+        for k, n in enumerate(unit_fragments(len(r), seg_len)):
+            items.append((u, k, a, a + n, None))
+            a += n
+    full = [it for it in items if it[3] - it[2] == Lu]
+    rest = sorted((it for it in items if it[3] - it[2] != Lu), key=lambda it: it[2] - it[3])           # longest first
+    chunks = [(full[lo:lo + max_batch], None) for lo in range(0, len(full), max_batch)]
+    chunks += [(rest[lo:lo + max_batch], True) for lo in range(0, len(rest), max_batch)]
+    # every utterance goes to the device once: E / 8 bytes per unit, one pinned buffer, one copy; the fragments are row ranges of it
+    uoffs = np.concatenate(([0], np.cumsum([len(r) for r in rows]))).astype(np.int64)
+    host = torch.empty(int(uoffs[-1]), row_bytes, dtype=torch.uint8, pin_memory=True)
+    np.concatenate(rows, axis=0, out=host.numpy())
+    packed_dev = host.to(dev, non_blocking=True)
+    sizes = [len(chunk) for chunk, _ in chunks]
+    starts = np.array([uoffs[u] + a for chunk, _ in chunks for (u, _, a, _, _) in chunk], dtype=np.int64)
+    counts = np.array([b - a for chunk, _ in chunks for (_, _, a, b, _) in chunk], dtype=np.int32)
+    st_d = torch.split(torch.from_numpy(starts).to(dev, non_blocking=True), sizes)
+    ln_d = torch.split(torch.from_numpy(counts).to(dev, non_blocking=True), sizes)
+    q = _Enqueued()
+    q.n_utt, q.dev, q.chunks, q.dec_dev = len(rows), dev, [], []
+    denorm = not want_specs                               # the vocoder de-normalises (the same device function) when the rows are wanted
+    gen_plan = None
+    if not enc_only:
+        q.conv, q.ulens, dsts = _plan_scatter(items, chunks, len(rows), denorm, dev, rows_of=lambda n: 8 * n)
+        gen_plan = (q.conv, dsts, shift, denorm)
+    for ci, (chunk, ragged) in enumerate(chunks):
+        lens = [b - a for (_, _, a, b, _) in chunk]
+        xd = _decode_chunk(trainer, ci, [it[0] for it in chunk], (lens if ragged else None), speakers, enc_only, gen_plan,
+                           lambda ch, lens_p: dec.forward_units(packed_dev, st_d[ci], ln_d[ci], len(chunk), max(lens), ch, lengths=lens_p))
+        q.chunks.append((chunk, lens))
+        q.dec_dev.append(xd)
+    if enc_only:
+        t, ulens = _gather_decoded(q, [[8 * n for n in lens] for _, lens in q.chunks])
+    else:
+        t, ulens = q.conv, q.ulens
+    spec_h = _to_host(t) if want_specs else None
+    fin = _enqueue_vocoder(t, ulens, n_iter, do_trim, dev, amplitudes=(denorm and not enc_only), momentum=momentum)
+
+    def finish():
+        wavs = fin()
+        if fin.status:                                        # a persistent GRU pass timed out before this batch's end
+            from . import layers
+            layers.check_status(dev)                          # synchronises, clears the word and raises
+        specs = [spec_h.numpy()[u, :n].copy() for u, n in enumerate(ulens)] if spec_h is not None else None
+        return specs, wavs
     return finish if defer else finish()
 
 
@@ -943,6 +1168,115 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
                            'bounds': it['bounds'], 'frames': it['frames'], 'wav': it['wav'], 'txt': it['txt']} for it in done],
                 'skipped': skipped}
     with open(os.path.join(out_dir, 'convert_dir.json'), 'w') as f:
+        json.dump(manifest, f, indent=1)
+    return manifest
+
+
+# ---------------------------------------------------------------------------------------------------
+# a folder of unit files to speech (not in the reference, whose drivers always start from the spectrogram)
+# ---------------------------------------------------------------------------------------------------
+
+def synth_dir_plan(files, n_units, targets, out_dir, batch=64, max_batch_units=6000):
+    """The work list of synth_dir, on the host alone: every (file, target) pair is an item.  n_units[i]: the units of files[i].
+    Files are sorted by (units, path) so that a group pads little and the plan does not depend on the order they are listed in; a
+    file's items are adjacent, in the order of `targets`.  A group takes items in that order while it holds at most `batch` of them
+    and at most max_batch_units of padded length, counted as items x the longest (a single item above the cap is a group of its
+    own; 6000 units are the 600 s of convert_dir_plan).  A file of fewer than 2 units goes to 'skipped' with a reason; two inputs
+    with the same stem would write the same outputs: ValueError.
+    Returns {'groups': [[item]], 'skipped': [{'file', 'reason'}]}, item = {'file', 'stem', 'target', 'units', 'wav'} with the output
+    {out_dir}/{target}/{stem}.wav."""
+    if len(files) != len(n_units):
+        raise ValueError('synth_dir_plan: %d unit counts for %d files' % (len(n_units), len(files)))
+    if batch < 1:
+        raise ValueError('synth_dir_plan: batch must be >= 1')
+    targets = list(targets)
+    if not targets or len(set(targets)) != len(targets):
+        raise ValueError('synth_dir_plan: the targets must be a non-empty list of distinct speakers (got %r)' % (targets,))
+    stems = {}
+    for f in files:
+        stem = os.path.splitext(os.path.basename(f))[0]
+        if stem in stems:
+            raise ValueError('synth_dir_plan: %s and %s would write the same outputs (stem %r)' % (stems[stem], f, stem))
+        stems[stem] = f
+    skipped, items = [], []
+    for n, f in sorted((int(n), f) for f, n in zip(files, n_units)):
+        if n < 2:
+            skipped.append({'file': f, 'reason': '%d unit%s: fewer than 2 units' % (n, '' if n == 1 else 's')})
+            continue
+        stem = os.path.splitext(os.path.basename(f))[0]
+        for t in targets:
+            items.append({'file': f, 'stem': stem, 'target': t, 'units': n, 'wav': os.path.join(out_dir, t, stem + '.wav')})
+    groups = []
+    for it in items:                                          # ascending lengths: the newest item is a group's longest
+        if groups and len(groups[-1]) < batch and (len(groups[-1]) + 1) * it['units'] <= max_batch_units:
+            groups[-1].append(it)
+        else:
+            groups.append([it])
+    return {'groups': groups, 'skipped': skipped}
+
+
+def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None):
+    """Every *.txt of in_dir -- unit files as write_encodings writes them (--test_encode, --test, --convert_dir, encode_batch), one
+    line of 0 / 1 per unit -- spoken in the voice of every target speaker of t_speakers: {out_dir}/{target}/{stem}.wav (PCM16 at
+    out_rate()), plus the manifest {out_dir}/synth_dir.json, which is returned.
+    The files are parsed and bit-packed on the host (E / 8 bytes per unit), the items of synth_dir_plan go through
+    synth_units_batch in groups, and group i + 1 is enqueued before group i is written (defer=True).  The targets are checked
+    before anything is read or enqueued.  A file that cannot be read as units of the Decoder's width, or holds fewer than 2
+    units, is skipped with a printed reason and listed in the manifest; the run goes on."""
+    momentum = gl_momentum(momentum)
+    with open(speaker2id_path, 'r') as f_json:
+        speaker2id = json.load(f_json)
+    t_speakers = list(t_speakers)
+    missing = [t for t in t_speakers if t not in speaker2id]
+    if missing:
+        raise ValueError('synth_dir: target speaker %r is not in %s' % (missing[0], speaker2id_path))
+    if trainer.enc_mode == 'continues':
+        raise ValueError("enc_mode 'continues' has no units: its encodings are real-valued and cannot be synthesised from unit files")
+    if not enc_only:
+        check_gen_targets(trainer, [speaker2id[t] for t in t_speakers])
+    E = int(trainer.Decoder.c_in)
+    skipped, units = [], {}
+
+    def skip(path, reason):
+        print('[Synthesiser] - skipped %s: %s' % (path, reason))
+        skipped.append({'input': path, 'reason': reason})
+
+    for path in sorted(glob.glob(os.path.join(in_dir, '*.txt'))):
+        try:
+            units[path] = pack_units(read_units(path, E))
+        except (OSError, ValueError) as e:
+            skip(path, 'cannot be read: %s' % e)
+    files = sorted(units)
+    plan = synth_dir_plan(files, [len(units[f]) for f in files], t_speakers, out_dir, batch=batch)
+    for s in plan['skipped']:
+        skip(s['file'], s['reason'])
+    groups = plan['groups']
+    print('[Synthesiser] - %d unit files, %d target speakers, %d syntheses in %d groups' %
+          (len(files) - len(plan['skipped']), len(t_speakers), sum(len(g) for g in groups), len(groups)))
+    os.makedirs(out_dir, exist_ok=True)
+    done = []
+
+    def write(group, fin):
+        _, wavs = fin()
+        for it, w in zip(group, to_out_sr(wavs)):
+            os.makedirs(os.path.dirname(it['wav']), exist_ok=True)
+            write_wav(it['wav'], w, out_rate())
+            done.append(it)
+
+    pending = None
+    for group in groups:
+        fin = synth_units_batch([units[it['file']] for it in group], trainer, seg_len, [speaker2id[it['target']] for it in group],
+                                enc_only=enc_only, n_iter=n_iter, defer=True, momentum=momentum, packed=True)
+        if pending is not None:
+            write(*pending)
+        pending = (group, fin)
+    if pending is not None:
+        write(*pending)
+    manifest = {'in_dir': in_dir, 'out_dir': out_dir, 'targets': t_speakers, 'sr': out_rate(), 'enc_only': bool(enc_only),
+                'items': [{'input': it['file'], 'units': it['units'], 'fragments': unit_fragments(it['units'], seg_len),
+                           'target': it['target'], 'wav': it['wav']} for it in done],
+                'skipped': skipped}
+    with open(os.path.join(out_dir, 'synth_dir.json'), 'w') as f:
         json.dump(manifest, f, indent=1)
     return manifest
 

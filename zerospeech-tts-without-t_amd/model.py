@@ -286,6 +286,21 @@ class Decoder(ZsModule):
         cidx = c.detach().to(xb.device, torch.int64).contiguous()
         return bits, eng.forward(bits, cidx, self.training, lengths=lengths)
 
+    def forward_units(self, packed, start, length, B, T0, c, lengths=None):
+        """forward_rows() from bit-packed units (convert.pack_units): zs_units_unpack writes the chunk's operand [B, T0, c_in] from
+        rows start[b] .. start[b] + length[b] of `packed` (uint8 [n_units, row_bytes] on the device; start int64 [B] and length
+        int32 [B] device tables), zeros behind each fragment's rows.  The same buffer, and then the same launches, as forward_rows."""
+        eng = self._engine()
+        ctx = eng.ctx
+        E = self.c_in
+        if packed.dtype != torch.uint8 or packed.dim() != 2 or packed.shape[1] < (E + 7) // 8 or not packed.is_contiguous():
+            raise ValueError('Decoder.forward_units: packed must be contiguous uint8 [n_units, >= %d]' % ((E + 7) // 8))
+        bits = ctx.act('d_in_%d_%d_%d' % (eng.uid, B, T0), B, T0, E)
+        L.call('zs_units_unpack', 'ZsUnitsUnpack', ctx.stream, dtype=ctx.dt, packed=L.ptr(packed), n_units=packed.shape[0],
+               row_bytes=packed.shape[1], E=E, start=L.ptr(start), len=L.ptr(length), n_frag=B, T=T0, dst=bits.ptr(), ld_dst=bits.ld)
+        cidx = c.detach().to(packed.device, torch.int64).contiguous()
+        return bits, eng.forward(bits, cidx, self.training, lengths=lengths)
+
 
 class Spectrogram_Patcher(ZsModule):
     """model/model.py:505-549: the stage-2 generator of g_mode 'spectrogram', a post-filter on the decoder's output spectrogram
