@@ -173,6 +173,23 @@ typedef struct {
 } ZsGemmWgrad;
 size_t zs_gemm_wgrad_workspace_bytes(const ZsGemmWgrad* p);
 int zs_gemm_wgrad(const ZsGemmWgrad* p, void* stream);
+/* zs_gemm_wgrad_path: the kernels a zs_gemm_wgrad launch of *p would take now, under the current knobs -- the same plan function
+ * the launch calls (argument checks, K-loop kernel, split-K plan, slab reduce).  Returns kernel | reduce << 8, or the negative code
+ * zs_gemm_wgrad would return for these arguments (the workspace SIZE is checked by the launch only: ask
+ * zs_gemm_wgrad_workspace_bytes); *splits and *rows_per_split (each may be null) receive the split-K plan: split k sums output rows
+ * [k * rows_per_split, min(M, (k + 1) * rows_per_split)), M = B*T_out, an empty range gives a slab of zeros.  It reads the struct
+ * and the knobs only: dY, X, dW, workspace are tested for null and alignment, never dereferenced, and no GPU call is made.
+ *   P8:   gemm_wgrad_p8_kernel, 256x256 tiles, bf16: "wgrad_p8" 2; or "wgrad_p8" 1, padded / real output area of the 256-wide
+ *         tiles at most "wgrad_p8_waste" / 100, M >= 2048 and (256x256 tiles x taps) * M >= 131072;  rows_per_split % 64 == 0
+ *   DMA:  gemm_wgrad_dma_kernel, 128x128 tiles, bf16: every other bf16 launch with "wgrad_dma";  rows_per_split % 32 == 0
+ *   REG:  gemm_wgrad_kernel, 128x128 tiles: fp32 always, bf16 with "wgrad_dma" 0;  rows_per_split % 32 == 0
+ * splits: p->splits when > 0, else the plan's choice (under "wgrad_alone", "wgrad_wgs", "wgrad_wgs128*", "wgrad_slab_cost*").
+ * reduce (bit 8): 1 = wgrad_reduce_taps_kernel (stores in dW order): "wgrad_reduce_taps", 1 < taps <= 256, si == taps and
+ * sj == 1 (a Conv1d weight; so may exceed Cin*taps); 0 = wgrad_reduce_kernel (any so / si / sj).
+ * Columns [Cout, y_cols) of dY and [Cin, x_cols) of X are read by the K-loop kernels and may hold anything (a neighbouring
+ * problem's data, NaN): they reach only slab rows / columns from which neither reduce stores anything. */
+enum { ZS_WGRAD_PATH_P8 = 0, ZS_WGRAD_PATH_DMA = 1, ZS_WGRAD_PATH_REG = 2 };
+int zs_gemm_wgrad_path(const ZsGemmWgrad* p, int32_t* splits, int32_t* rows_per_split);
 
 /* ---------------------------------------------------------------------------------------------
  * zs_pack_weight: fp32 parameter (PyTorch layout, strides so/si/sj as above) -> GEMM operand.

@@ -275,6 +275,187 @@ def test_gemm_conv_path_query(lib):
     assert not bad(taps=7, pad_left=3, pad_mode=lib.ZS_PAD_REFLECT, T_in=4, T_out=4, ldw=7 * 64)
 
 
+class _WgradQuery(object):
+    """zs_gemm_wgrad_path on structs with dummy aligned non-null operands (nothing is dereferenced, no GPU is touched), and the
+    split-K rule of the plan restated."""
+
+    def __init__(self, lib):
+        self.lib, self.L = lib, lib.lib()
+        self.P8, self.DMA, self.REG = lib.ZS_WGRAD_PATH_P8, lib.ZS_WGRAD_PATH_DMA, lib.ZS_WGRAD_PATH_REG
+        self.PTR = 0x10000
+
+    @staticmethod
+    def rup(x, m):
+        return (x + m - 1) // m * m
+
+    def struct(self, B=64, T=128, Cout=1024, Cin=1024, k=1, dtype=None, conv=True, **kw):
+        lib, rup, PTR = self.lib, self.rup, self.PTR
+        dtype = lib.ZS_BF16 if dtype is None else dtype
+        es = 2 if dtype == lib.ZS_BF16 else 4
+        a = dict(dtype=dtype, dY=PTR, ldy=rup(Cout, 32), y_cols=rup(Cout, 16 // es), X=2 * PTR, ldx=rup(Cin, 32), x_batch_stride=T * rup(Cin, 32),
+                 x_cols=rup(Cin, 16 // es), B=B, T_in=T, T_out=T, taps=k, stride=1, pad_left=k // 2, pad_mode=lib.ZS_PAD_REFLECT, Cout=Cout,
+                 Cin=Cin, dW=3 * PTR, so=Cin * k, si=k if conv else 1, sj=1 if conv else Cin, workspace=4 * PTR)
+        a.update(kw)
+        return lib.STRUCTS['ZsGemmWgrad'](**a)
+
+    def path(self, **kw):
+        """(kernel, reduce, splits, rows per split); the workspace size and the rounding of rows per split follow the reported plan."""
+        rup = self.rup
+        s = self.struct(**kw)
+        k, r, sp, rps = self.lib.wgrad_path(s)
+        tile = 256 if k == self.P8 else 128
+        need = sp * (rup(s.Cout, tile) * s.taps * rup(s.Cin, tile) + rup(s.Cout, tile)) * 4
+        assert self.L.zs_gemm_wgrad_workspace_bytes(ctypes.byref(s)) == need, kw
+        assert rps % (64 if k == self.P8 else 32) == 0 and rps == rup(-(-s.B * s.T_out // sp), 64 if k == self.P8 else 32), kw
+        return k, r, sp, rps
+
+    @staticmethod
+    def plan128(M, tiles, target=448):
+        return max(1, min(-(-target // tiles), -(-M // 256), 1024))
+
+    @staticmethod
+    def plan256(M, tiles, wgs=256, slab=13):
+        kt, best, bs = -(-M // 64), 1e30, 1
+        for sp in range(1, 65):
+            if sp * 4 > kt:
+                break
+            cost = -(-tiles * sp // wgs) * (-(-kt // sp) + slab)
+            if cost < best - 1e-9:
+                best, bs = cost, sp
+        return bs
+
+
+@pytest.fixture
+def wgrad_query(lib):
+    """A _WgradQuery under the documented defaults of every weight-gradient knob; the knobs are restored afterwards."""
+    keys = ('wgrad_p8', 'wgrad_dma', 'wgrad_reduce_taps', 'wgrad_alone', 'wgrad_p8_waste', 'wgrad_wgs', 'wgrad_wgs128', 'wgrad_slab_cost',
+            'wgrad_wgs128_alone', 'wgrad_slab_cost_alone')
+    defaults = (1, 1, 1, 0, 135, 256, 448, 13, 448, 13)
+    old = {k: lib.set_option(k, v) for k, v in zip(keys, defaults)}
+    try:
+        yield _WgradQuery(lib)
+    finally:
+        for k, v in old.items():
+            lib.set_option(k, v)
+
+
+def test_gemm_wgrad_path_dispatch(lib, wgrad_query):
+    """zs_gemm_wgrad_path (the launch's own plan function): the K-loop kernel under wgrad_p8 0 / 1 / 2, wgrad_dma and wgrad_p8_waste,
+    both P8 thresholds from both sides, fp32 never P8 or DMA; the taps-reduce condition under wgrad_reduce_taps."""
+    q = wgrad_query
+    path, P8, DMA, REG, F32, BF16 = q.path, q.P8, q.DMA, q.REG, lib.ZS_F32, lib.ZS_BF16
+    # the P8 rule: bf16, M >= 2048, (256 x 256 tiles x taps) * M >= 16 * 8192, padding waste at most wgrad_p8_waste / 100
+    assert path()[:2] == (P8, 0)                                             # M 8192, 16 tiles
+    assert path(B=1, T=8191)[0] == DMA and path(B=1, T=8192)[0] == P8        # t256 * M from both sides
+    assert path(B=1, T=2047, Cout=2048, Cin=2048, k=3)[0] == DMA             # M from both sides (192 tiles)
+    assert path(B=1, T=2048, Cout=2048, Cin=2048, k=3)[:2] == (P8, 1)
+    assert path(dtype=F32)[0] == REG and path(B=1, T=2048, Cout=2048, Cin=2048, k=3, dtype=F32)[:2] == (REG, 1)
+    big = dict(B=1024, T=128)                                                # M 131072: one tile is enough
+    assert path(Cout=200, Cin=256, **big)[0] == P8                           # waste 1.28
+    assert path(Cout=180, Cin=256, **big)[0] == DMA                          # waste 1.42
+    lib.set_option('wgrad_p8_waste', 143)
+    assert path(Cout=180, Cin=256, **big)[0] == P8
+    lib.set_option('wgrad_p8_waste', 135)
+    lib.set_option('wgrad_p8', 0)
+    assert path()[0] == DMA and path(dtype=F32)[0] == REG
+    lib.set_option('wgrad_dma', 0)
+    assert path()[0] == REG and path(Cout=8, Cin=8, B=1, T=21)[0] == REG
+    lib.set_option('wgrad_p8', 2)                                            # forced: any bf16 shape, never fp32
+    assert path(Cout=8, Cin=8, B=1, T=21)[0] == P8 and path(Cout=180, Cin=256)[0] == P8
+    assert path(Cout=8, Cin=8, B=1, T=21, dtype=F32)[0] == REG and path(dtype=F32)[0] == REG
+    lib.set_option('wgrad_dma', 1)
+    assert path(dtype=F32)[0] == REG                                         # fp32 never takes the LDS-DMA kernel either
+    lib.set_option('wgrad_p8', 0)
+    assert path(Cout=8, Cin=8, B=1, T=21, dtype=F32)[0] == REG and path(Cout=8, Cin=8, B=1, T=21)[0] == DMA
+    # the taps reduce: a Conv1d weight (si == taps, sj == 1) with 1 < taps <= 256, whatever so
+    for dt in (BF16, F32):
+        assert path(k=3, dtype=dt)[1] == 1 and path(k=1, dtype=dt)[1] == 0
+        assert path(k=3, dtype=dt, so=3 * 1024 + 40)[1] == 1
+        assert path(k=3, dtype=dt, conv=False)[1] == 0                       # [co][tap][ci]: si 1, sj Cin
+        assert path(k=3, dtype=dt, si=4)[1] == 0 and path(k=3, dtype=dt, sj=0)[1] == 0
+        assert path(k=256, Cout=8, Cin=8, B=1, T=300, dtype=dt)[1] == 1 and path(k=257, Cout=8, Cin=8, B=1, T=300, dtype=dt)[1] == 0
+    lib.set_option('wgrad_reduce_taps', 0)
+    assert path(k=3)[1] == 0
+    lib.set_option('wgrad_reduce_taps', 1)
+
+
+def test_gemm_wgrad_path_splits(lib, wgrad_query):
+    """Explicit splits with rows per split rounded to 32 (64 for P8), and splits = 0 against the split-K rule restated in
+    _WgradQuery, under wgrad_alone and the workgroup / slab-cost knobs; the workspace size agrees with every reported plan."""
+    q = wgrad_query
+    path, plan128, plan256, P8, F32 = q.path, q.plan128, q.plan256, q.P8, lib.ZS_F32
+    # explicit splits: rows per split rounded up to 32 (64 for P8), also where trailing splits get no rows
+    assert path(B=1, T=200, splits=3)[2:] == (3, 96) and path(B=1, T=21, splits=5)[2:] == (5, 32)
+    assert path(B=1, T=640, splits=7, dtype=F32)[2:] == (7, 96)
+    lib.set_option('wgrad_p8', 2)
+    assert path(B=1, T=200, splits=3)[2:] == (3, 128) and path(B=1, T=21, splits=5)[2:] == (5, 64)
+    assert path(B=1, T=640, splits=7)[2:] == (7, 128)                        # splits 5 and 6 start at rows 640 and 768: empty
+    # splits = 0: the plan's choice, restated above
+    lib.set_option('wgrad_p8', 1)
+    for alone in (0, 1):
+        lib.set_option('wgrad_alone', alone)
+        assert path(Cout=128, Cin=513, k=5)[2:] == (18, 480)                 # 25 tiles of 128 x 128: ceil(448 / 25)
+        assert path(Cout=128, Cin=513, k=5, B=1, T=700)[2] == 3              # at most one split per 256 rows
+        assert path(Cout=64, Cin=25, B=1 << 14, T=128, dtype=F32, conv=False)[2] == 448
+        assert path(B=256, Cout=1024, Cin=1024)[2] == plan256(256 * 128, 16) and path(B=256)[0] == P8
+        assert path(B=256, Cout=2048, Cin=1024, k=3)[2] == plan256(256 * 128, 96)
+    lib.set_option('wgrad_wgs128_alone', 768)
+    lib.set_option('wgrad_slab_cost_alone', 40)
+    lib.set_option('wgrad_wgs', 128)
+    for alone in (0, 1):
+        lib.set_option('wgrad_alone', alone)
+        assert path(Cout=128, Cin=513, k=5)[2] == plan128(8192, 25, 768 if alone else 448) == (31 if alone else 18)
+        assert path(B=256)[2] == plan256(256 * 128, 16, wgs=128, slab=40 if alone else 13)
+    lib.set_option('wgrad_wgs128', 0)                                        # 0: the built-in target
+    lib.set_option('wgrad_alone', 0)
+    assert path(Cout=128, Cin=513, k=5)[2] == 18
+
+
+def test_gemm_wgrad_path_errors(lib, wgrad_query):
+    """Every argument error comes back from zs_gemm_wgrad_path as the code and the text the launch itself gives (the launch
+    returns before any GPU call); the workspace size is the launch's check alone."""
+    q = wgrad_query
+    L, struct, PTR, F32 = q.L, q.struct, q.PTR, lib.ZS_F32
+    # every argument error: the code and the text of the launch itself
+    launch = L.zs_gemm_wgrad
+    launch.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+
+    def bad(text, **kw):
+        small = dict(B=2, T=16, Cout=64, Cin=64)
+        small.update(kw)
+        s = struct(**small)
+        rc = L.zs_gemm_wgrad_path(ctypes.addressof(s), None, None)
+        e1 = lib.last_error()
+        if rc >= 0:
+            return False
+        assert launch(ctypes.addressof(s), None) == rc == lib.ZS_EINVAL and lib.last_error() == e1 and text in e1, (kw, rc, e1)
+        return True
+
+    assert not bad('')
+    assert L.zs_gemm_wgrad_path(None, None, None) == lib.ZS_EINVAL and launch(None, None) == lib.ZS_EINVAL
+    for f in ('dY', 'X', 'dW', 'workspace'):
+        assert bad('null operand', **{f: 0})
+    assert bad('workspace must be 16-byte aligned', workspace=4 * PTR + 8)
+    assert bad('bad dtype', dtype=7)
+    for f in ('B', 'T_in', 'T_out', 'Cout', 'Cin', 'taps', 'stride'):
+        assert bad('bad sizes', **{f: 0}), f
+    for kw in (dict(dY=PTR + 2), dict(X=2 * PTR + 8), dict(ldy=68), dict(ldx=68), dict(x_batch_stride=16 * 64 + 4), dict(y_cols=60, Cout=60),
+               dict(x_cols=60, Cin=60), dict(dtype=F32, ldy=66), dict(dtype=F32, x_cols=62, Cin=60)):
+        assert bad('16-byte aligned', **kw), kw
+    assert not bad('', dtype=F32, ldy=68, x_cols=60, Cin=60)                     # fp32: multiples of 4 elements
+    for kw in (dict(y_cols=72), dict(x_cols=72), dict(y_cols=56), dict(x_cols=56), dict(Cout=65, y_cols=64, ldy=64), dict(Cin=65, x_cols=64, ldx=64)):
+        assert bad('column bounds', **kw), kw
+    assert bad('SPLIT2 needs even Cout', Cout=63, y_cols=64, co_split2=1) and not bad('', Cout=62, y_cols=64, co_split2=1)
+    g2 = dict(T=24, k=9, w_in=6, w_out=6, taps_h=3)
+    assert not bad('', **g2)
+    for kw in (dict(w_in=-1), dict(w_out=0), dict(taps_h=0), dict(taps_h=2), dict(w_in=5), dict(w_out=5)):
+        assert bad('2-D geometry', **dict(g2, **kw)), kw
+    # the report does not look at the workspace size; the launch does, after the plan
+    s = struct(B=2, T=16, Cout=64, Cin=64, workspace_bytes=16)
+    assert L.zs_gemm_wgrad_path(ctypes.addressof(s), None, None) >= 0
+    assert launch(ctypes.addressof(s), None) == lib.ZS_EWORKSPACE and 'workspace 16 <' in lib.last_error()
+
+
 def test_no_cpu_fallback():
     import zs_amd  # noqa: F401
     from zs_amd import _lib

@@ -2345,6 +2345,57 @@ int gemm_conv_plan(const ZsGemmConv* p, ConvPlan& pl) {
   return ZS_OK;
 }
 
+// The launch plan of zs_gemm_wgrad, as gemm_conv_plan above: the argument checks, the K-loop kernel and split-K plan (wgrad_plan)
+// and the slab reduce with its grid, host arithmetic on the struct and the knobs only.  zs_gemm_wgrad launches what it returns (and
+// checks the workspace size against it); zs_gemm_wgrad_path reports it.
+struct WgradLaunch {
+  WgradPlan w;
+  int kernel;          // ZS_WGRAD_PATH_*
+  int reduce_taps;     // 1: wgrad_reduce_taps_kernel, 0: wgrad_reduce_kernel
+  int64_t wgs;         // grid.x of the K-loop kernel: tiles x splits
+  int c4n, nblk;       // wgrad_reduce_taps_kernel: float4 columns per workgroup, ci blocks per co
+  int nmain, nbias;    // reduce grid: workgroups of the dW sums, trailing workgroups of the bias sums (one lane per co)
+};
+int gemm_wgrad_plan(const ZsGemmWgrad* p, WgradLaunch& pl) {
+  ZS_REQUIRE(p && p->dY && p->X && p->dW && p->workspace, "zs_gemm_wgrad: null operand");
+  ZS_REQUIRE(aligned16(p->workspace), "zs_gemm_wgrad: workspace must be 16-byte aligned");
+  ZS_REQUIRE(p->dtype == ZS_F32 || p->dtype == ZS_BF16, "zs_gemm_wgrad: bad dtype");
+  const int es = p->dtype == ZS_F32 ? 4 : 2;
+  ZS_REQUIRE(p->B > 0 && p->T_in > 0 && p->T_out > 0 && p->Cout > 0 && p->Cin > 0 && p->taps > 0 && p->stride > 0,
+             "zs_gemm_wgrad: bad sizes");
+  ZS_REQUIRE(aligned16(p->dY) && aligned16(p->X) && (p->ldy * es) % 16 == 0 && (p->ldx * es) % 16 == 0 &&
+                 (p->x_batch_stride * es) % 16 == 0 && (p->y_cols * es) % 16 == 0 && (p->x_cols * es) % 16 == 0,
+             "zs_gemm_wgrad: operands must be 16-byte aligned");
+  ZS_REQUIRE(p->y_cols <= p->ldy && p->x_cols <= p->ldx && p->Cout <= p->y_cols && p->Cin <= p->x_cols, "zs_gemm_wgrad: column bounds");
+  ZS_REQUIRE(!p->co_split2 || p->Cout % 2 == 0, "zs_gemm_wgrad: SPLIT2 needs even Cout");
+  ZS_REQUIRE(p->w_in == 0 || (p->w_in > 0 && p->w_out > 0 && p->taps_h > 0 && p->taps % p->taps_h == 0 && p->T_in % p->w_in == 0 &&
+                              p->T_out % p->w_out == 0 && (int64_t)p->T_out * p->w_out < (1ll << 32)),
+             "zs_gemm_wgrad: 2-D geometry (w_in %d, w_out %d, taps_h %d, taps %d, T_in %d, T_out %d)", p->w_in, p->w_out, p->taps_h, p->taps,
+             p->T_in, p->T_out);
+  pl.w = wgrad_plan(p);
+  const WgradPlan& w = pl.w;
+  pl.kernel = w.p8 ? ZS_WGRAD_PATH_P8 : (w.dma ? ZS_WGRAD_PATH_DMA : ZS_WGRAD_PATH_REG);
+  pl.wgs = (int64_t)w.co_tiles * p->taps * w.ci_tiles * w.splits;
+  // (the two grid checks used to follow the workspace-size check of the launch: a call with an oversized grid AND too small a
+  //  workspace now comes back as ZS_EINVAL, not ZS_EWORKSPACE; no valid call is affected)
+  ZS_REQUIRE(pl.wgs < (1ll << 31), "zs_gemm_wgrad: grid too large");
+  pl.nbias = p->db ? (p->Cout + 255) / 256 : 0;                  // trailing workgroups: the bias sums, one lane per co
+  pl.reduce_taps = g_wgrad_reduce_taps.get() && p->taps > 1 && p->taps <= 256 && p->si == p->taps && p->sj == 1;
+  pl.c4n = pl.nblk = 0;
+  if (pl.reduce_taps) {
+    pl.c4n = 256 / p->taps;                                      // ci per workgroup: 4 * c4n, so that c4n * taps <= 256 items
+    pl.nblk = (p->Cin + 4 * pl.c4n - 1) / (4 * pl.c4n);
+    ZS_REQUIRE((int64_t)p->Cout * pl.nblk + pl.nbias < (1ll << 31), "zs_gemm_wgrad: reduce grid too large");
+    pl.nmain = p->Cout * pl.nblk;
+  } else {
+    const int64_t relems = (int64_t)p->Cout * p->taps * ((p->Cin + 3) / 4);
+    const int64_t nmain = (relems + 255) / 256;
+    ZS_REQUIRE(nmain + pl.nbias < (1ll << 31), "zs_gemm_wgrad: reduce grid too large");
+    pl.nmain = (int)nmain;
+  }
+  return ZS_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -2404,24 +2455,21 @@ extern "C" size_t zs_gemm_wgrad_workspace_bytes(const ZsGemmWgrad* p) {
   return (size_t)w.splits * ((size_t)w.cout_r * p->taps * w.cin_r + w.cout_r) * sizeof(float);
 }
 
+extern "C" int zs_gemm_wgrad_path(const ZsGemmWgrad* p, int32_t* splits, int32_t* rows_per_split) {
+  WgradLaunch pl;
+  const int rc = gemm_wgrad_plan(p, pl);
+  if (rc != ZS_OK) return rc;
+  if (splits) *splits = pl.w.splits;
+  if (rows_per_split) *rows_per_split = pl.w.rows_per_split;
+  return pl.kernel | pl.reduce_taps << 8;
+}
+
 extern "C" int zs_gemm_wgrad(const ZsGemmWgrad* p, void* stream) {
-  ZS_REQUIRE(p && p->dY && p->X && p->dW && p->workspace, "zs_gemm_wgrad: null operand");
-  ZS_REQUIRE(aligned16(p->workspace), "zs_gemm_wgrad: workspace must be 16-byte aligned");
-  ZS_REQUIRE(p->dtype == ZS_F32 || p->dtype == ZS_BF16, "zs_gemm_wgrad: bad dtype");
-  const int es = p->dtype == ZS_F32 ? 4 : 2;
-  ZS_REQUIRE(p->B > 0 && p->T_in > 0 && p->T_out > 0 && p->Cout > 0 && p->Cin > 0 && p->taps > 0 && p->stride > 0,
-             "zs_gemm_wgrad: bad sizes");
-  ZS_REQUIRE(aligned16(p->dY) && aligned16(p->X) && (p->ldy * es) % 16 == 0 && (p->ldx * es) % 16 == 0 &&
-                 (p->x_batch_stride * es) % 16 == 0 && (p->y_cols * es) % 16 == 0 && (p->x_cols * es) % 16 == 0,
-             "zs_gemm_wgrad: operands must be 16-byte aligned");
-  ZS_REQUIRE(p->y_cols <= p->ldy && p->x_cols <= p->ldx && p->Cout <= p->y_cols && p->Cin <= p->x_cols, "zs_gemm_wgrad: column bounds");
-  ZS_REQUIRE(!p->co_split2 || p->Cout % 2 == 0, "zs_gemm_wgrad: SPLIT2 needs even Cout");
-  ZS_REQUIRE(p->w_in == 0 || (p->w_in > 0 && p->w_out > 0 && p->taps_h > 0 && p->taps % p->taps_h == 0 && p->T_in % p->w_in == 0 &&
-                              p->T_out % p->w_out == 0 && (int64_t)p->T_out * p->w_out < (1ll << 32)),
-             "zs_gemm_wgrad: 2-D geometry (w_in %d, w_out %d, taps_h %d, taps %d, T_in %d, T_out %d)", p->w_in, p->w_out, p->taps_h, p->taps,
-             p->T_in, p->T_out);
-  const WgradPlan w = wgrad_plan(p);
-  const int splits = w.splits, co_tiles = w.co_tiles, ci_tiles = w.ci_tiles, cout_r = w.cout_r, cin_r = w.cin_r;
+  WgradLaunch pl;
+  int rc = gemm_wgrad_plan(p, pl);
+  if (rc != ZS_OK) return rc;
+  const WgradPlan& w = pl.w;
+  const int splits = w.splits, ci_tiles = w.ci_tiles, cout_r = w.cout_r, cin_r = w.cin_r;
   const int rows_per_split = w.rows_per_split;
   const size_t need = (size_t)splits * ((size_t)cout_r * p->taps * cin_r + cout_r) * sizeof(float);
   if (p->workspace_bytes < need) {
@@ -2429,35 +2477,26 @@ extern "C" int zs_gemm_wgrad(const ZsGemmWgrad* p, void* stream) {
     return ZS_EWORKSPACE;
   }
   hipStream_t s = (hipStream_t)stream;
-  ZS_REQUIRE((int64_t)co_tiles * p->taps * ci_tiles * splits < (1ll << 31), "zs_gemm_wgrad: grid too large");
-  dim3 grid((unsigned)(co_tiles * p->taps * ci_tiles * splits), 1, 1);
+  const dim3 grid((unsigned)pl.wgs, 1, 1);
   std::call_once(g_lds_attr_once, set_lds_attrs);
-  if (w.p8) {
+  if (pl.kernel == ZS_WGRAD_PATH_P8) {
     hipLaunchKernelGGL(gemm_wgrad_p8_kernel, grid, dim3(PNT), P8_LDS, s, *p, ci_tiles, rows_per_split, cout_r, cin_r);
   } else if (p->dtype == ZS_F32) {
     const size_t lds = (4 * WK * WFrag<float>::PITCHW > EPI_LDS_BYTES) ? 4 * WK * WFrag<float>::PITCHW : EPI_LDS_BYTES;
     hipLaunchKernelGGL(gemm_wgrad_kernel<float>, grid, dim3(NT), lds, s, *p, ci_tiles, rows_per_split, cout_r, cin_r);
-  } else if (w.dma) {
+  } else if (pl.kernel == ZS_WGRAD_PATH_DMA) {
     hipLaunchKernelGGL(gemm_wgrad_dma_kernel, grid, dim3(NT), WD_LDS, s, *p, ci_tiles, rows_per_split, cout_r, cin_r);
   } else {
     const size_t lds = (4 * WK * WFrag<bf16_t>::PITCHW > EPI_LDS_BYTES) ? 4 * WK * WFrag<bf16_t>::PITCHW : EPI_LDS_BYTES;
     hipLaunchKernelGGL(gemm_wgrad_kernel<bf16_t>, grid, dim3(NT), lds, s, *p, ci_tiles, rows_per_split, cout_r, cin_r);
   }
-  int rc = zs_check_launch("zs_gemm_wgrad");
+  rc = zs_check_launch("zs_gemm_wgrad");
   if (rc) return rc;
-  const int nbias = p->db ? (p->Cout + 255) / 256 : 0;          // trailing workgroups: the bias sums, one lane per co
-  if (g_wgrad_reduce_taps.get() && p->taps > 1 && p->taps <= 256 && p->si == p->taps && p->sj == 1) {
-    const int c4n = 256 / p->taps;                               // ci per workgroup: 4 * c4n, so that c4n * taps <= 256 items
-    const int nblk = (p->Cin + 4 * c4n - 1) / (4 * c4n);
-    ZS_REQUIRE((int64_t)p->Cout * nblk + nbias < (1ll << 31), "zs_gemm_wgrad: reduce grid too large");
-    const int nmain = p->Cout * nblk;
-    hipLaunchKernelGGL(wgrad_reduce_taps_kernel, dim3((unsigned)(nmain + nbias)), dim3(256), 0, s, *p, splits, cout_r, cin_r, c4n, nblk, nmain);
-  } else {
-    const int64_t relems = (int64_t)p->Cout * p->taps * ((p->Cin + 3) / 4);
-    const int64_t nmain = (relems + 255) / 256;
-    ZS_REQUIRE(nmain + nbias < (1ll << 31), "zs_gemm_wgrad: reduce grid too large");
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(nmain + nbias)), dim3(256), 0, s, *p, splits, cout_r, cin_r, (int)nmain);
-  }
+  if (pl.reduce_taps)
+    hipLaunchKernelGGL(wgrad_reduce_taps_kernel, dim3((unsigned)(pl.nmain + pl.nbias)), dim3(256), 0, s, *p, splits, cout_r, cin_r, pl.c4n, pl.nblk,
+                       pl.nmain);
+  else
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(pl.nmain + pl.nbias)), dim3(256), 0, s, *p, splits, cout_r, cin_r, pl.nmain);
   return zs_check_launch("zs_gemm_wgrad.reduce");
 }
 
