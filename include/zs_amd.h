@@ -1003,6 +1003,39 @@ typedef struct {
 } ZsEncDxFold;
 int zs_enc_dx_fold(const ZsEncDxFold* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * zs_eval_accum: one held-out validation batch added into device-resident tables (zs_amd.validation).  No host
+ * synchronisation, no gradient, no allocation; the host reads the tables once, after the last batch.
+ * Reconstruction error per speaker.  x_dec fp32 [B*T][ld_dec], x fp32 [B*T][ldx] (F valid columns each; the padding columns
+ * are never read), c int64 [B]:
+ *   s_b = sum_{t, f} |x_dec - x|       the difference in fp32, the sum in double: ZS_EVAL_PARTS workgroups per sample, each
+ *                                      over a fixed share of the rows in a fixed order, their partials summed in order
+ *   for b = 0 .. B-1 in this order:    spk_sum[c[b]] += s_b (double),  spk_cnt[c[b]] += 1
+ * There is no floating-point atomic: the same launch on the same tables gives the same bits.  A c[b] outside [0, n_speakers) is
+ * never used as an index: the sample is skipped and *bad += 1.  work: scratch of >= B * ZS_EVAL_PARTS doubles.
+ * 16-byte loads of four columns need 4-byte alignment only; columns F - F % 4 .. F - 1 are read one by one.
+ * Unit statistics (bits_f32 == null skips them and leaves ones / flips / rows / pairs alone).  bits_f32 fp32 [B*T4][E], dense, the
+ * 0 / 1 units the encoder writes (a unit is set when its value != 0):
+ *   ones[j]  += #{rows with unit j set}
+ *   flips[j] += #{(b, t), t + 1 < T4 : unit j of rows (b, t) and (b, t + 1) differs}      (never across two samples)
+ *   *rows += B * T4,  *pairs += B * (T4 - 1)
+ * added with integer atomics (integer sums do not depend on the order).
+ * ZS_EINVAL (nothing launched): a null struct or required pointer (x_dec, x, c, work, spk_sum, spk_cnt, bad; with bits_f32 also
+ * ones, flips, rows, pairs), B, T or F <= 0, T * F >= 2^31, ld_dec < F, ldx < F, n_speakers <= 0 or > 2^24, with bits_f32 T4 <= 0 or
+ * E <= 0. */
+#define ZS_EVAL_PARTS 8
+typedef struct {
+  const float* x_dec; int64_t ld_dec;
+  const float* x; int64_t ldx;
+  const int64_t* c;
+  int32_t B, T, F, n_speakers;
+  double* work;
+  double* spk_sum; int64_t* spk_cnt; uint64_t* bad;
+  const float* bits_f32; int32_t T4, E;
+  uint64_t* ones; uint64_t* flips; uint64_t* rows; uint64_t* pairs;
+} ZsEvalAccum;
+int zs_eval_accum(const ZsEvalAccum* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,19 @@ converts with the averaged weights of the checkpoint; with --load_model a traini
 averaged autoencoder: `--train_tgat --load_model --use_ema --ema 0.999`.  Where a flag would have no effect (--ema without a
 training mode, --use_ema without a mode that loads a checkpoint) it is refused before anything is built.
 
+--valid_every N with --train_ae or --train (zs_amd.validation): after every N-th iteration of the pretrain_AE stage, and after its
+last one, the autoencoder is run forward on a held-out set that lies in GPU memory -- --valid_batches M batches (default 8) of
+hps.batch_size segments, always the same data with the same noise -- and the reconstruction loss (overall, over the target speakers,
+the worst speaker), the entropy, dead count and flip rate of the unit bits are logged, printed and appended, with the per-speaker
+table, to <ckpt_dir>/valid.jsonl; the checkpoint with the lowest loss so far is kept as <model_name>-ae-best, outside the
+max_to_keep window.  The set: --valid_index_path PATH (an index JSON as --preprocess writes, over --dataset_path, group --valid_flag,
+default train), or --valid_holdout K (every K-th utterance of --index_path leaves the training set and becomes the validation
+set), or, with --synthetic and neither, a synthetic set of its own.  The training run computes bit for bit what it computes without
+validation, and --resume continues the records and the best value; a run without --resume starts from iteration 0 and so
+empties an existing valid.jsonl in --ckpt_dir and overwrites -ae-best, as it overwrites the numbered checkpoints:
+  python main.py --train_ae --synthetic --valid_every 1000
+  python main.py --train_ae --valid_every 1000 --valid_holdout 20 --resume --ema 0.999
+
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
 (--train_al, --train_t, --encode, --test_asr) are not part of this build and exit with a clear error.
@@ -88,6 +101,9 @@ def _ema(text):
     if not 0.0 <= d < 1.0:                    # NaN fails too
         raise argparse.ArgumentTypeError('--ema must be in [0, 1) (got %s)' % text)
     return d
+
+
+VALID_BATCHES = 8
 
 
 def build_parser():
@@ -143,6 +159,18 @@ def build_parser():
     p.add_argument('--use_ema', default=False, action='store_true',
                    help='load the averaged weights (<net>_ema) of the checkpoint: every --test* mode, --cross_test, --convert_dir, --synth_dir, and '
                         'training with --load_model')
+    p.add_argument('--valid_every', type=int, default=None, metavar='N',
+                   help='--train_ae / --train: validate the autoencoder on a held-out set after every N-th pretrain_AE iteration and '
+                        'the last; records in <ckpt_dir>/valid.jsonl, best checkpoint <model_name>-ae-best (a run without --resume starts both '
+                        'anew: an existing valid.jsonl in --ckpt_dir is emptied, -ae-best overwritten); default: never')
+    p.add_argument('--valid_batches', type=int, default=None, metavar='M',
+                   help='with --valid_every: batches of hps.batch_size segments in the validation set (default %d)' % VALID_BATCHES)
+    p.add_argument('--valid_index_path', type=str, default=None,
+                   help='with --valid_every: index JSON of the validation set over --dataset_path (its first M * batch_size entries)')
+    p.add_argument('--valid_holdout', type=int, default=None, metavar='K',
+                   help='with --valid_every: hold every K-th utterance (K >= 2) of --index_path out of training as the validation set')
+    p.add_argument('--valid_flag', type=str, default=None,
+                   help="with --valid_index_path: the group of --dataset_path its entries lie in (default 'train')")
     p.add_argument('--out_sr', type=_out_sr, default=None,
                    help='sample rate of the wavs --test / --cross_test / --test_single write (hp.out_sr); default: 16000')
     return p
@@ -204,6 +232,8 @@ def argument_runner(argv=None):
     args = parser.parse_args(argv)
     check_resume(args)
     check_ema(args)
+    from zs_amd.validation import check_flags
+    check_flags(args)
     args.t_speakers = convert_targets(args) if (args.convert_dir is not None or args.synth_dir is not None) else None
     if args.dataset == 'surprise':            # main.py:83-88: english -> surprise in every default path
         for action in parser._actions:
@@ -230,6 +260,39 @@ def argument_runner(argv=None):
     return args, hps
 
 
+def training_sets(args, hps, world=1):
+    """(dataset, sourceset, targetset, valid) of a --train* run: the three sets the loaders are built over and the ValidConfig of
+    --valid_every (None without it).  --valid_holdout takes every K-th utterance of --index_path out of `dataset` (the stage-2
+    sets are not touched); the validation set is read, and checked (ValueError), here."""
+    from zs_amd.dataloader import Dataset, SyntheticDataset
+    n_syn = max(4 * hps.batch_size * world, 64)
+    validset = None
+    if args.synthetic:
+        dataset = SyntheticDataset(n_syn, seg_len=hps.seg_len, n_speakers=hps.n_speakers)
+        sourceset = SyntheticDataset(n_syn, seg_len=hps.seg_len, n_speakers=max(1, hps.n_speakers - hps.n_target_speakers), seed=1)
+        targetset = SyntheticDataset(n_syn, seg_len=hps.seg_len, n_speakers=hps.n_target_speakers, seed=2,
+                                     speaker_offset=hps.n_speakers - hps.n_target_speakers)
+    else:
+        dataset = Dataset(args.dataset_path, args.index_path, seg_len=hps.seg_len)
+        sourceset = Dataset(args.dataset_path, args.index_source_path, seg_len=hps.seg_len)
+        targetset = Dataset(args.dataset_path, args.index_target_path, seg_len=hps.seg_len)
+        if args.valid_every is not None and args.valid_holdout is not None:      # every K-th utterance leaves the training set
+            from zs_amd import validation
+            kept, held = validation.holdout_split(dataset.indexes, args.valid_holdout)
+            dataset = Dataset(args.dataset_path, args.index_path, seg_len=hps.seg_len, indexes=kept)
+            validset = Dataset(args.dataset_path, args.index_path, seg_len=hps.seg_len, indexes=held)
+    valid = None
+    if args.valid_every is not None:
+        from zs_amd.validation import ValidConfig, ValidSet
+        M = args.valid_batches if args.valid_batches is not None else VALID_BATCHES
+        if args.valid_index_path is not None:
+            validset = Dataset(args.dataset_path, args.valid_index_path, dset=args.valid_flag or 'train', seg_len=hps.seg_len)
+        elif validset is None:
+            validset = SyntheticDataset(M * hps.batch_size, seg_len=hps.seg_len, n_speakers=hps.n_speakers, seed=3)
+        valid = ValidConfig(args.valid_every, M, ValidSet.from_dataset(validset, M, hps.batch_size, hps.n_speakers), args.valid_holdout)
+    return dataset, sourceset, targetset, valid
+
+
 def main(argv=None):
     import zs_amd  # noqa: F401
     args, hps = argument_runner(argv)
@@ -238,7 +301,7 @@ def main(argv=None):
         raise NotImplementedError('--%s is outside the stage-1 autoencoder hot path this build covers' % bad[0])
     from zs_amd import parallel
     from zs_amd.convert import convert_dir, cross_test, get_trainer, synth_dir, target_classify, test_encode, test_from_list, test_single
-    from zs_amd.dataloader import DataLoader, Dataset, SyntheticDataset
+    from zs_amd.dataloader import DataLoader
     from zs_amd.trainer import Trainer
 
     if args.preprocess:                                   # main.py:113-126
@@ -249,16 +312,7 @@ def main(argv=None):
 
     if args.train or args.train_ae or args.train_p or args.train_tgat or args.train_c:   # main.py:129-171
         rank, world, _ = parallel.init_from_env()
-        n_syn = max(4 * hps.batch_size * world, 64)
-        if args.synthetic:
-            dataset = SyntheticDataset(n_syn, seg_len=hps.seg_len, n_speakers=hps.n_speakers)
-            sourceset = SyntheticDataset(n_syn, seg_len=hps.seg_len, n_speakers=max(1, hps.n_speakers - hps.n_target_speakers), seed=1)
-            targetset = SyntheticDataset(n_syn, seg_len=hps.seg_len, n_speakers=hps.n_target_speakers, seed=2,
-                                         speaker_offset=hps.n_speakers - hps.n_target_speakers)
-        else:
-            dataset = Dataset(args.dataset_path, args.index_path, seg_len=hps.seg_len)
-            sourceset = Dataset(args.dataset_path, args.index_source_path, seg_len=hps.seg_len)
-            targetset = Dataset(args.dataset_path, args.index_target_path, seg_len=hps.seg_len)
+        dataset, sourceset, targetset, valid = training_sets(args, hps, world)   # (ValueError of the validation set: before the trainer and any pool)
         if args.device_data:
             # the sets the chosen modes read, uploaded once into one pool (index files over one store share their utterances)
             import torch
@@ -272,7 +326,7 @@ def main(argv=None):
         data_loader, source_loader, target_loader = mk(dataset), mk(sourceset), mk(targetset)
         os.makedirs(args.ckpt_dir, exist_ok=True)
         model_path = os.path.join(args.ckpt_dir, args.model_name)
-        trainer = Trainer(hps, data_loader, args.g_mode, args.enc_mode, dtype=args.dtype, ema=args.ema)
+        trainer = Trainer(hps, data_loader, args.g_mode, args.enc_mode, dtype=args.dtype, ema=args.ema, valid=valid)
         if args.load_model:
             trainer.load_model(os.path.join(args.ckpt_dir, args.load_train_model_name), load_model_list=hps.load_model_list,
                                use_ema=args.use_ema)

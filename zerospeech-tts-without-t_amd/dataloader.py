@@ -164,10 +164,15 @@ def open_store(path, mode='r'):
 class Dataset(torch.utils.data.Dataset):
     """HDF5- (or .npz-) backed segments, dataloader.py:56-78 (layout `{dset}/{speaker}/{utt}/lin|mel`)."""
 
-    def __init__(self, h5_path, index_path, dset='train', seg_len=64, load_mel=False):
+    def __init__(self, h5_path, index_path, dset='train', seg_len=64, load_mel=False, indexes=None):
+        """indexes (not in the reference): the index entries themselves, used in place of the file at index_path (a part of
+        an index file, e.g. validation.holdout_split's)."""
         self.dataset = open_store(h5_path, 'r')         # HDF5 (h5py) or the .npz container written by zs_amd.preprocess
-        with open(index_path) as f_index:
-            self.indexes = json.load(f_index)
+        if indexes is not None:
+            self.indexes = list(indexes)
+        else:
+            with open(index_path) as f_index:
+                self.indexes = json.load(f_index)
         self.indexer = namedtuple('index', ['speaker', 'i', 't'])
         self.seg_len, self.dset, self.load_mel = seg_len, dset, load_mel
 

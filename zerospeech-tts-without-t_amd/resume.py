@@ -12,6 +12,9 @@ weights_only=True) that holds no weights.  Its keys:
   steps         {'ae' | 'clf' | 's2' | 'tclf': that step object's state_dict()}: Adam m / v / t per stepped net and the counters
   consumed      {'data' | 'source' | 'target': batches the steps have taken from that loader}
   rng           {'cpu': torch.get_rng_state(), 'cuda': torch.cuda.get_rng_state(device)}
+  valid         {'every', 'batches', 'digest', 'holdout'} of the held-out validation (validation.py) of a pretrain_AE run; the key, and
+                best_loss / best_iteration (the lowest validation loss so far and its iteration) beside it, are absent when the run
+                does not validate
   model_kept    the rolling window of checkpoints (Trainer.model_kept) after this checkpoint, as file names in the checkpoint's
                 directory: a copied or moved directory resumes
 
@@ -70,6 +73,9 @@ def describe(trainer, tag, target_guided=False, autolocker=False):
          'flat_len': {name: int(net.flat_params()[0].numel()) for name, net in zip(NET_NAMES, trainer.nets())}}
     if getattr(trainer, 'ema', None) is not None:                          # recorded only when on: an EMA-off file is today's
         d['ema'] = float(trainer.ema)
+    if tag == 'ae' and getattr(trainer, 'valid', None) is not None:        # recorded only when on, as ema
+        from . import validation
+        d['valid'] = validation.describe(trainer.valid)
     return d
 
 
@@ -82,6 +88,8 @@ def validate(state, expect):
             raise ValueError('train state: %s is %r in the file, %r in this run' % (f, state[f], expect[f]))
     if state.get('ema') != expect.get('ema'):                             # the decay, or None: on / off and the value must agree
         raise ValueError('train state: ema is %r in the file, %r in this run' % (state.get('ema'), expect.get('ema')))
+    from . import validation
+    validation.validate(state.get('valid'), expect.get('valid'))         # on / off, every, batches, the set's digest, the holdout K
     have = state.get('flat_len')
     if not isinstance(have, dict):
         raise ValueError("train state: field 'flat_len' is missing")

@@ -20,6 +20,7 @@ from . import _lib as L
 from . import parallel
 from . import layers
 from . import resume as train_state                # (Trainer.train has a parameter called resume)
+from . import validation
 from .layers import Act, join_side
 from .model import Decoder, Encoder, SpeakerClassifier, Spectrogram_Patcher
 from .patch import PatchDiscriminator, TargetClassifier
@@ -262,6 +263,11 @@ class AEStep(object):
         pinned, dst) pairs, the H2D copy of the NEXT batch, forked at the start of the first graph and joined at its end (one
         rank: the end of the step) -- it runs on its own stream beside the kernels of this step.  prologue: launches captured in
         front of the first graph's step on the step's own stream (PoolFedStep: the gather of THIS batch into xs, cs)."""
+        graphs, plan = self._capture_plan(self.plan(xs, cs, parallel.multi_rank(), True), prefetch, prologue)
+        return {'graphs': graphs, 'plan': plan, 'x': xs, 'c': cs}
+
+    def _capture_plan(self, acts, prefetch=(), prologue=None):
+        """Capture any plan (the step's, or ValidStep's forward-only one) as _capture describes; returns (graphs, captured plan)."""
         torch.cuda.synchronize(self.device)
         graphs, plan, runs = [], [], []
         pool = None
@@ -284,14 +290,14 @@ class AEStep(object):
             plan.append(('run', g.replay))
             del runs[:]
 
-        for a in self.plan(xs, cs, parallel.multi_rank(), True):
+        for a in acts:
             if a[0] == 'run':
                 runs.append(a[1])
             else:
                 close()
                 plan.append(a)
         close()
-        return {'graphs': graphs, 'plan': plan, 'x': xs, 'c': cs}
+        return graphs, plan
 
     def _fork_fetch(self, pairs):
         """Inside a capture: copy each pinned src to its device dst by zs_host_fetch kernel nodes (they read the pinned buffers over
@@ -335,6 +341,74 @@ class AEStep(object):
         self.opt['enc'].adam(self.adam_step)
         self.opt['dec'].adam(self.adam_step)
         self._step_dev.fill_(self.adam_step)
+
+
+class ValidStep(object):
+    """Held-out validation of an AEStep's Encoder / Decoder pair (validation.py): a forward-only plan beside AEStep.plan, run by
+    the AEStep's own executors (eager, capture, replay).
+
+    Batch m of the M-batch pass: Encoder forward with training=False on its own tape key ('valid': buffers of its own), its Gumbel
+    noise from the counter-hash stream seeded VALID_SEED + m (a host constant of the plan; 'continues' draws none); Decoder
+    forward with training=False (the decoder's buffers are shared with the training step, which rewrites every one of them before
+    it reads it); zs_eval_accum into one device table.  The plan reads inputs of its own (the whole set lies in HBM: the training
+    step's static inputs may already hold the prefetched next batch) and writes scalars of its own: it launches no
+    zs_step_counters, touches none of _seed_dev, _step_dev, adam_step, _loss, _lpart, xdec, and draws nothing from torch's
+    generators, so the training run computes bit for bit what it computes without validation.  run() ends with the one D2H copy
+    of the table (under 20 KB), the only host synchronisation of a validation.  (The engines' forward also makes its tape the
+    'latest forward' one that backward* default to; every training step forwards before it backpropagates, so none ever reads it.)  With graphs on, the first run() is eager (every
+    buffer allocated) and the second captures the M-batch pass into one hipGraph that later ones replay."""
+
+    def __init__(self, ae, vset, batches, n_speakers):
+        self.ae, dev = ae, ae.device
+        self.M, self.n_speakers = int(batches), int(n_speakers)
+        self.x = vset.x[:self.M].to(dev, torch.float32).contiguous()          # [M, B, T, F]
+        self.c = vset.c[:self.M].to(dev, torch.int64).contiguous()            # [M, B]
+        if int(self.c.min()) < 0 or int(self.c.max()) >= self.n_speakers:    # (zs_eval_accum would skip them; the decoder's embedding lookup would not)
+            raise ValueError('validation set: speaker id outside [0, %d)' % self.n_speakers)
+        _, self.B, self.T, self.F = self.x.shape
+        enc = ae.Encoder
+        self.units = enc.enc_mode != 'continues'
+        self.E = enc.enc_size if self.units else 0
+        self.layout, total = validation.table_layout(self.n_speakers, self.E)
+        self.table = torch.zeros(total, dtype=torch.int64, device=dev)
+        self.work = torch.zeros(self.B * L.ZS_EVAL_PARTS, dtype=torch.float64, device=dev)
+        self._captured = None
+        self._runs = 0
+
+    def _word(self, name):
+        return L.ptr(self.table, self.layout[name][0])
+
+    def _batch(self, m):
+        ae = self.ae
+        ee, de = ae.Encoder._engine(), ae.Decoder._engine()
+        x, c = self.x[m], self.c[m]
+        bits, bits_f32, _ = ee.forward(x, False, noise_kind=2, seed=validation.VALID_SEED + m, tape='valid')
+        xdec = de.forward(bits, c, False)
+        if xdec.T != self.T:
+            raise ValueError('validation: the decoder returns %d frames for segments of %d' % (xdec.T, self.T))
+        u = self.units
+        L.call('zs_eval_accum', 'ZsEvalAccum', de.ctx.stream, x_dec=xdec.ptr(), ld_dec=xdec.ld, x=L.ptr(x), ldx=self.F, c=L.ptr(c),
+               B=self.B, T=self.T, F=self.F, n_speakers=self.n_speakers, work=L.ptr(self.work), spk_sum=self._word('spk_sum'),
+               spk_cnt=self._word('spk_cnt'), bad=self._word('bad'), bits_f32=L.ptr(bits_f32) if u else None,
+               T4=bits_f32.shape[1], E=bits_f32.shape[2], ones=self._word('ones') if u else None,
+               flips=self._word('flips') if u else None, rows=self._word('rows') if u else None, pairs=self._word('pairs') if u else None)
+
+    def plan(self):
+        return [('run', self.table.zero_)] + [('run', functools.partial(self._batch, m)) for m in range(self.M)]
+
+    def run(self):
+        """One validation on the current weights.  Returns validation.split_table's dict of host arrays."""
+        ae = self.ae
+        ae.Encoder._engine(); ae.Decoder._engine()                            # (a re-pack after load_state_dict stays outside the capture)
+        if ae.use_graph and self._runs >= 1:
+            if self._captured is None:
+                self._captured = ae._capture_plan(self.plan())
+            ae._execute(self._captured[1])
+        else:
+            ae._execute(self.plan())
+        self._runs += 1
+        host = self.table.cpu().numpy()                                       # the only host sync of a validation
+        return validation.split_table(host, self.n_speakers, self.E)
 
 
 class HostFedStep(object):
@@ -595,11 +669,20 @@ def _fill_slots(skel, pin):
 class Trainer(object):
     ema = None                             # the decay of the weight averages (__init__ sets it; the default serves a Trainer made without it)
 
-    def __init__(self, hps, data_loader, g_mode, enc_mode, log_dir='./log/', dtype=None, device=None, ema=None):
-        """ema (not in the reference): None, or the decay in [0, 1) of an exponential moving average of the weights that every
+    valid = None                           # the ValidConfig of the held-out validation (__init__ sets it)
+    _best_due = False
+
+    def __init__(self, hps, data_loader, g_mode, enc_mode, log_dir='./log/', dtype=None, device=None, ema=None, valid=None):
+        """valid (not in the reference): None, or a validation.ValidConfig: train(mode='pretrain_AE') then validates on its set
+        every `every` iterations and after the last one (ValidStep), logs and records the result and keeps the best checkpoint.
+        ema (not in the reference): None, or the decay in [0, 1) of an exponential moving average of the weights that every
         optimizer this trainer builds keeps beside its net (optim.NetOpt); the checkpoints then carry `<net>_ema` entries."""
         self.hps = hps
         self.ema = check_ema(ema)
+        self.valid = validation.check_config(valid, hps) if valid is not None else None
+        self._vstep = None                                                 # ValidStep, built on first use
+        self.best_loss = self.best_iteration = None                        # the lowest valid_loss_rec so far and its iteration
+        self._best_due = False                                             # the next periodic resumable checkpoint also writes -ae-best
         self.data_loader = data_loader
         self._prefetch = None
         self.model_kept = []
@@ -703,7 +786,8 @@ class Trainer(object):
         self.model_kept = []
 
     # ---- checkpoints (trainer.py:103-168) -----------------------------------------------------
-    def save_model(self, model_path, name, iteration, model_all=True):
+    def _model_dict(self, model_all=True):
+        """The checkpoint dict (the reference's, plus `<net>_ema` entries with weight averages) as CPU tensors."""
         all_model = {
             'encoder': self.Encoder.state_dict(),
             'decoder': self.Decoder.state_dict(),
@@ -722,9 +806,11 @@ class Trainer(object):
                 pre = 'module.' if key in ('patch_discriminator', 'target_classifier') else ''
                 all_model[key + '_ema'] = {pre + k: (opt.ema[offs[k]:offs[k] + v.numel()].view(v.shape) if k in offs else v)
                                            for k, v in sd.items()}
-        all_model = {k: {n: t.detach().cpu().clone() for n, t in sd.items()} for k, sd in all_model.items()}
+        return {k: {n: t.detach().cpu().clone() for n, t in sd.items()} for k, sd in all_model.items()}
+
+    def save_model(self, model_path, name, iteration, model_all=True):
         new_model_path = '{}-{}-{}'.format(model_path, name, iteration)
-        torch.save(all_model, new_model_path)
+        torch.save(self._model_dict(model_all), new_model_path)
         for old in train_state.roll_window(self.model_kept, new_model_path, self.max_keep):
             train_state.remove_checkpoint(old)                                 # its train-state file, if it has one, goes with it
 
@@ -741,6 +827,8 @@ class Trainer(object):
         st.update(iteration=int(iteration), steps={n: s.state_dict() for n, s in self._steps(tag).items()},
                   consumed=dict(self._consumed), model_kept=[os.path.basename(p) for p in self.model_kept],
                   rng={'cpu': torch.get_rng_state(), 'cuda': torch.cuda.get_rng_state(self.device)})
+        if 'valid' in st:                                                 # (describe: a validating pretrain_AE run)
+            st.update(best_loss=self.best_loss, best_iteration=self.best_iteration)
         return st
 
     def save_state(self, path, tag=None, iteration=0, target_guided=False, autolocker=None):
@@ -793,6 +881,8 @@ class Trainer(object):
             torch.set_rng_state(st['rng']['cpu'])
             torch.cuda.set_rng_state(st['rng']['cuda'], self.device)
         self.model_kept = [os.path.join(ckpt_dir, name) for name in st['model_kept']]
+        if 'valid' in st:
+            self.best_loss, self.best_iteration = st.get('best_loss'), st.get('best_iteration')
         return st
 
     def _load_all_nets(self, ckpt_path):
@@ -828,15 +918,19 @@ class Trainer(object):
             done.record(cs)
         return pin, done
 
-    def _checkpoint_async(self, model_path, name, iteration, target_guided, autolocker):
+    def _checkpoint_async(self, model_path, name, iteration, target_guided, autolocker, best=False):
         """A resumable checkpoint off the training thread's critical path: enqueue the snapshot (_snapshot) of the six flat
         parameter buffers and of every tensor of the state tree, then hand a worker thread the job of waiting for the event,
-        building the checkpoint dict (save_model's) and the state dict from the pinned memory and writing both."""
+        building the checkpoint dict (save_model's) and the state dict from the pinned memory and writing both.
+        best: the snapshot written to validation.best_path(model_path) alone: no state file, not in the rolling window (it takes
+        the state tree's tensors along so that the one set of snapshot buffers serves both kinds).  A periodic checkpoint whose
+        iteration's validation was a new best (_best_due) writes the best file too, from its one snapshot."""
         if self._writer is None:
             self._writer = train_state.Writer()
         self._writer.wait()                                               # one checkpoint in flight; its failure raises here
-        new_path = '{}-{}-{}'.format(model_path, name, iteration)
-        drop = train_state.roll_window(self.model_kept, new_path, self.max_keep)
+        new_path = validation.best_path(model_path) if best else '{}-{}-{}'.format(model_path, name, iteration)
+        drop = [] if best else train_state.roll_window(self.model_kept, new_path, self.max_keep)
+        also_best, self._best_due = (not best) and self._best_due, False
         srcs, layout, skel = self._ckpt_sources(self._state_tree(name, iteration, target_guided, autolocker))
         pin, done = self._snapshot(srcs)
 
@@ -844,7 +938,10 @@ class Trainer(object):
             done.synchronize()                                            # the worker's only GPU call
             ckpt = {key: {pre + k: pin[s][o:o + n].view(shape).clone() for k, s, o, n, shape in ents} for key, pre, ents in layout}
             train_state.atomic_save(ckpt, new_path)
-            train_state.atomic_save(_fill_slots(skel, pin), train_state.state_path(new_path))
+            if also_best:
+                train_state.atomic_save(ckpt, validation.best_path(model_path))
+            if not best:
+                train_state.atomic_save(_fill_slots(skel, pin), train_state.state_path(new_path))
             for old in drop:
                 train_state.remove_checkpoint(old)
         self._writer.submit(job)
@@ -1092,6 +1189,41 @@ class Trainer(object):
         if is_main:
             print()
 
+    def valid_step(self):
+        if self._vstep is None:
+            self._vstep = ValidStep(self.ae, self.valid.set, self.valid.batches, self.hps.n_speakers)
+        return self._vstep
+
+    def validate(self, iteration, model_path=None, flag='train', keep_state=None):
+        """One held-out validation of the autoencoder's raw weights (with --ema too: validating the averages would need an operand
+        re-pack round trip) after `iteration` iterations.  Every rank runs it, on the same set with the same noise, so all
+        ranks agree without communication; rank 0 logs the record, prints one line, appends it to <ckpt_dir>/valid.jsonl and,
+        when valid_loss_rec is lower than every earlier one, writes <model_path>-ae-best through the path the run's periodic
+        checkpoints take (save_model's dict; the writer thread when resumable).  Returns the record."""
+        hps = self.hps
+        vs = self.valid_step()
+        rec = validation.finish(vs.run(), vs.T, vs.F, units=vs.units,
+                                target_ids=range(hps.n_speakers - hps.n_target_speakers, hps.n_speakers))
+        layers.check_status(self.device)                                  # (run() synchronised: a timed-out GRU pass raises here)
+        if parallel.rank() != 0:
+            return rec
+        for k in validation.SCALARS:
+            if rec.get(k) is not None:
+                self.logger.scalar_summary('%s/%s' % (flag, k), rec[k], iteration)
+        print(validation.line(iteration, rec).ljust(60))                  # a line of its own: the loop's \r lines overwrite each other
+        if model_path is not None:
+            validation.append_record(validation.record_path(model_path), iteration, rec)
+        if self.best_loss is None or rec['valid_loss_rec'] < self.best_loss:
+            self.best_loss, self.best_iteration = rec['valid_loss_rec'], int(iteration)
+            if model_path is not None:
+                if keep_state is not None and iteration % self.ckpt_every == 0:
+                    self._best_due = True                                 # this iteration's periodic checkpoint writes it, from its one snapshot
+                elif keep_state is not None:
+                    self._checkpoint_async(model_path, 'ae', iteration, *keep_state, best=True)
+                else:
+                    train_state.atomic_save(self._model_dict(), validation.best_path(model_path))
+        return rec
+
     def _finish_writer(self):
         if self._writer is not None:
             self._writer.wait()
@@ -1102,7 +1234,10 @@ class Trainer(object):
         already is the final iteration.  Every rank reads the same files."""
         tag, say = train_state.TAGS[mode], (print if parallel.rank() == 0 else (lambda *a: None))
         found = train_state.find_resumable(model_path, tag)
+        records = validation.record_path(model_path) if (self.valid is not None and tag == 'ae' and parallel.rank() == 0) else None
         if found is None:
+            if records is not None:
+                validation.truncate_records(records, 0)
             say('[Trainer] - resume: no %s checkpoint with a train state beside %s, starting from iteration 0' % (tag, model_path))
             self._seek({'data': 0, 'source': 0, 'target': 0})             # a run's position is counted from the loaders' start
             return 0
@@ -1110,6 +1245,8 @@ class Trainer(object):
         # the file is validated against this run (ValueError) before a weight is touched or anything is launched
         st = torch.load(state, map_location='cpu', weights_only=True)
         train_state.validate(st, train_state.describe(self, tag, target_guided, mode == 'autolocker'))
+        if records is not None:                                           # the records behind the restart point are written again
+            validation.truncate_records(records, int(st['iteration']))
         self._load_all_nets(ckpt)
         self.load_state(state, state=st)
         it = int(st['iteration'])
@@ -1140,6 +1277,10 @@ class Trainer(object):
             else:
                 feeder = self.ae.host_feeder(self.data_loader) if self.ae.use_graph else None  # H2D of the next batch inside the graph
 
+            vcfg, iters = self.valid, hps.enc_pretrain_iters
+            if vcfg is not None and not resumable and parallel.rank() == 0:
+                validation.truncate_records(validation.record_path(model_path), 0)              # a run from iteration 0: its own records
+
             def iteration_fn(iteration, log):
                 if feeder is not None:
                     loss_t = next(feeder)
@@ -1149,6 +1290,8 @@ class Trainer(object):
                     loss_t = self.ae_step(x, c)
                 if log:
                     log('pre_AE:[%06d/%06d], loss_rec=%.3f', {f'{flag}/pre_loss_rec': loss_t.item()})    # the only host sync
+                if vcfg is not None and ((iteration + 1) % vcfg.every == 0 or iteration + 1 == iters):
+                    self.validate(iteration + 1, model_path, flag, keep_state)                 # before this iteration's checkpoint
             self._loop(hps.enc_pretrain_iters, model_path, 'ae', iteration_fn, start, keep_state)
         elif mode == 'pretrain_C':                                                        # trainer.py:349-382
             start = begin(hps.dis_pretrain_iters)
