@@ -760,6 +760,57 @@ typedef struct {
   uint8_t* packed; int64_t n_units; int32_t row_bytes;
 } ZsUnitsPack;
 int zs_units_pack(const ZsUnitsPack* p, void* stream);
+/* Voice adaptation (zs_amd/voice.py): the five embedding rows of a new speaker are fitted to a few utterances with every other weight
+ * frozen.  The utterances' spectrograms lie in device memory as a pool (zs_pool_gather's layout) and their units, encoded once, as
+ * bit-packed rows (zs_units_unpack's layout).
+ *
+ * zs_voice_gather: one adaptation batch per call, behind a device cursor -- zs_pool_gather and zs_units_unpack in one kernel, with the
+ * item chosen on the device, so that a captured call serves the next batch at every replay (zs_units_unpack alone reads its `start`
+ * table through launch arguments that a graph freezes).  pool fp32 [frames_total][F]; packed uint8 [n_units][row_bytes]; the item
+ * table of n >= 1 entries, planned on the host: first int64 [n] = first frame of the segment in the pool (a multiple of 8 is what
+ * the planner makes; the kernel does not need it) and ufirst int64 [n] = the row of `packed` that holds the unit of that frame.  With
+ * k = *cursor:
+ *   item(b)       = (k * B + b) mod n                                          b < B
+ *   x[b][t][f]    = pool[first[item(b)] + t][f]                                t < seg_len, f < F; x fp32 [B][seg_len][F] contiguous
+ *   bits[b][u][c] = bit(packed[ufirst[item(b)] + u], c) ? 1 : 0                u < seg_len / 8, c < E
+ *   bits[b][u][c] = 0                                                          E <= c < ld_bits
+ * bits [B][seg_len / 8][ld_bits] of `dtype` (ZS_F32 / ZS_BF16) is the Decoder's input operand: 16-byte aligned, ld_bits a multiple
+ * of 8, written with 16-byte stores.  advance != 0: a one-thread launch behind the gather then does *cursor += 1.  One lane produces
+ * each output piece whole: no atomics, no read-modify-write, a call is bitwise reproducible.  pool and x need 4-byte alignment only
+ * (F = 513); first, ufirst and cursor 8-byte.  The kernel trusts the table: the caller checks 0 <= first, first + seg_len <=
+ * frames_total, 0 <= ufirst and ufirst + seg_len / 8 <= n_units for every entry on the host before it uploads it.  A null operand,
+ * B, F, E or n <= 0, seg_len <= 0 or no multiple of 8, ld_bits < E or no multiple of 8, row_bytes < (E + 7) / 8, a dtype other than
+ * the two or a misaligned pointer return ZS_EINVAL and launch nothing.  No allocation, no synchronisation. */
+typedef struct {
+  int32_t dtype;
+  const float* pool; const uint8_t* packed; int32_t row_bytes;
+  const int64_t* first; const int64_t* ufirst; int64_t n;
+  int64_t* cursor;
+  int32_t B, seg_len, F, E;
+  float* x; void* bits; int64_t ld_bits;
+  int32_t advance;
+} ZsVoiceGather;
+int zs_voice_gather(const ZsVoiceGather* p, void* stream);
+/* zs_voice_adam: the end of an adaptation step in one launch -- the five zs_emb_scatter (all samples to row 0), zs_sqnorm and
+ * zs_adam_clip over the five rows.  emb_sum fp32 [5][B][C], contiguous: the decoder's per-sample embedding sums (slots 0..4 of
+ * DecoderEngine's buffer).  With i = k * C + c over the 5 C elements:
+ *   g[i]   = sum_b emb_sum[k][b][c], an fp32 sum in ascending b from 0.f (the order and the bits of zs_emb_scatter);  g fp32 [5][C]
+ *   *sumsq = (float) sum_i (double) g[i]^2, in a fixed order
+ *   row[k][c], m[i], v[i]: the update of zs_adam_clip (the same device function: bit-identical to zs_adam_clip over p = row k,
+ *   g, m, v given this *sumsq), with max_norm <= 0 = no clipping and step_ptr (optional device step count t, else bc1 / bc2) as there.
+ * row: five device pointers to C floats each (the rows need not be adjacent); m, v fp32 [5][C].  One workgroup: the work is
+ * 5 B C floats read once (320 KB at B = 16, C = 1024).  No atomics, no host synchronisation, capturable.  A null operand, B or
+ * C <= 0, 5 C > ZS_VOICE_ADAM_MAX, or bias corrections <= 0 without step_ptr return ZS_EINVAL and launch nothing. */
+#define ZS_VOICE_ROWS 5
+#define ZS_VOICE_ADAM_MAX 65536
+typedef struct {
+  const float* emb_sum; int32_t B, C;
+  float* row[5]; float* m; float* v; float* g;
+  float lr, beta1, beta2, eps, bc1, bc2;
+  float* sumsq; float max_norm;
+  const int32_t* step_ptr;
+} ZsVoiceAdam;
+int zs_voice_adam(const ZsVoiceAdam* p, void* stream);
 /* zs_tclf_score: the scoring loop of target_classify (convert.py:400-413) on the device.  logits fp32 [n_frag][ld] (3 valid columns),
  * target int32 [n_frag] (0 V001, 1 V002, 2 'None', -1 any other speaker: never correct):
  *   pred[f] = argmax_j logits[f][j] (first maximum, NaN as the maximum: numpy's rule; pred may be null)

@@ -52,6 +52,19 @@ empties an existing valid.jsonl in --ckpt_dir and overwrites -ae-best, as it ove
   python main.py --train_ae --synthetic --valid_every 1000
   python main.py --train_ae --valid_every 1000 --valid_holdout 20 --resume --ema 0.999
 
+--adapt_voice NAME --adapt_dir DIR --ckpt_pth CKPT (zs_amd.voice): enrol a voice that was not in the training run.  The *.wav of DIR
+(read as --convert_dir reads them) are encoded once by the frozen Encoder, and the five embedding rows through which the Decoder sees
+a speaker are fitted to them -- random seg_len-frame segments, the L1 reconstruction loss, Adam(lr hps.lr or --adapt_lr, betas
+(0.5, 0.9)) and the run's gradient clip over the five rows, every other weight frozen -- for --adapt_iters iterations (default 500),
+starting from the rows of speaker --adapt_init or, without it, from the mean of each table.  The result is {voice_dir}/NAME.voice.npz
+(--voice_dir, default {ckpt_dir}/voices); no checkpoint, hps or speaker2id file is written, and the same command on the same files
+gives the same rows bit for bit.  --voice NAME=FILE (repeatable) with --convert_dir or --synth_dir and --enc_only appends such voices
+to the Decoder's tables, and --t_speaker may then name them (speaker2id is looked up first).  Voices convert through the autoencoder
+alone: the stage-2 Generator has rows for its trained target speakers only, so --voice without --enc_only is refused, as is every
+other combination without effect, before anything is built:
+  python main.py --adapt_voice ANNA --adapt_dir wavs/ --ckpt_pth CKPT --adapt_init V001
+  python main.py --convert_dir in/ --enc_only --voice ANNA=ckpt_english/voices/ANNA.voice.npz --t_speaker ANNA,V001 --ckpt_pth CKPT
+
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
 (--train_al, --train_t, --encode, --test_asr) are not part of this build and exit with a clear error.
@@ -171,6 +184,17 @@ def build_parser():
                    help='with --valid_every: hold every K-th utterance (K >= 2) of --index_path out of training as the validation set')
     p.add_argument('--valid_flag', type=str, default=None,
                    help="with --valid_index_path: the group of --dataset_path its entries lie in (default 'train')")
+    p.add_argument('--adapt_voice', type=str, default=None, metavar='NAME',
+                   help='enrol a new target voice NAME from the *.wav of --adapt_dir: fit its five Decoder embedding rows with every '
+                        'other weight frozen and write {voice_dir}/NAME.voice.npz')
+    p.add_argument('--adapt_dir', type=str, default=None, metavar='DIR', help='with --adapt_voice: the folder of its utterances')
+    p.add_argument('--adapt_iters', type=int, default=None, metavar='N', help='with --adapt_voice: iterations (default 500)')
+    p.add_argument('--adapt_init', type=str, default=None, metavar='SPEAKER',
+                   help="with --adapt_voice: start from this speaker's rows (default: the mean of each table's rows)")
+    p.add_argument('--adapt_lr', type=float, default=None, metavar='LR', help='with --adapt_voice: learning rate (default hps.lr)')
+    p.add_argument('--voice_dir', type=str, default=None, metavar='DIR', help='with --adapt_voice: where the voice file goes (default {ckpt_dir}/voices)')
+    p.add_argument('--voice', action='append', default=None, metavar='NAME=FILE',
+                   help='with --convert_dir / --synth_dir and --enc_only: register the voice file FILE as target speaker NAME (repeatable)')
     p.add_argument('--out_sr', type=_out_sr, default=None,
                    help='sample rate of the wavs --test / --cross_test / --test_single write (hp.out_sr); default: 16000')
     return p
@@ -209,10 +233,73 @@ def check_ema(args):
     if args.ema is not None and not training:
         raise ValueError('--ema needs a training mode (%s)' % ', '.join('--' + f for f in TRAIN_MODES))
     loads = any(getattr(args, f) for f in LOADING_MODES) or args.convert_dir is not None or args.synth_dir is not None or \
-        (training and args.load_model)
+        (training and args.load_model) or getattr(args, 'adapt_voice', None) is not None
     if args.use_ema and not loads:
         raise ValueError('--use_ema needs a mode that loads a checkpoint: %s, --convert_dir, or a training mode with --load_model'
                          % ', '.join('--' + f for f in LOADING_MODES))
+
+
+def voice_files(args):
+    """--voice NAME=FILE ... as {name: file}, in order; ValueError for an entry of another form or a name given twice."""
+    specs = getattr(args, 'voice', None) or []
+    if not specs:
+        return {}
+    from zs_amd.voice import parse_voices
+    return parse_voices(specs)
+
+
+def check_voice(args, speaker2id=None):
+    """--adapt_voice and --voice are refused, before anything is built, where they cannot do what they say: --adapt_voice without
+    --adapt_dir, with a --train* mode, with any mode that converts or tests (a command adapts OR uses a voice) or under a multi-rank launch; --voice without --convert_dir / --synth_dir or without --enc_only
+    (voices convert through the autoencoder alone); a name that is a speaker of speaker2id already or is given twice; an --adapt_init
+    that is no such speaker; --adapt_iters < 1; and enc_mode 'continues', which has no units to cache (checked once --enc_mode is
+    known: argument_runner calls this again after reading hps).  speaker2id: the table, read from --speaker2id_path when None
+    and the file exists."""
+    adapt, voices = getattr(args, 'adapt_voice', None), voice_files(args)
+    if adapt is None:
+        for flag in ('adapt_dir', 'adapt_iters', 'adapt_init', 'adapt_lr', 'voice_dir'):
+            if getattr(args, flag, None) is not None:
+                raise ValueError('--%s needs --adapt_voice' % flag)
+    if adapt is None and not voices:
+        return
+    if speaker2id is None and os.path.exists(args.speaker2id_path):
+        import json
+        with open(args.speaker2id_path, 'r') as f:
+            speaker2id = json.load(f)
+    speaker2id = speaker2id or {}
+    if adapt is not None:
+        if not adapt.strip() or adapt != adapt.strip() or any(ch in adapt for ch in ',=/\\'):
+            raise ValueError("--adapt_voice needs a name without ',', '=', '/' or surrounding blanks (got %r)" % adapt)
+        if args.adapt_dir is None:
+            raise ValueError('--adapt_voice needs --adapt_dir DIR, the folder of the voice\'s utterances')
+        modes = [f for f in TRAIN_MODES if getattr(args, f)]
+        if modes:
+            raise ValueError('--adapt_voice fits a voice to a finished checkpoint: it cannot be combined with --%s' % modes[0])
+        if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+            raise ValueError('--adapt_voice runs on one GPU: start it without a multi-rank launcher (WORLD_SIZE = %s)' % os.environ['WORLD_SIZE'])
+        others = [f for f in LOADING_MODES if getattr(args, f)] + [f for f in ('convert_dir', 'synth_dir') if getattr(args, f) is not None]
+        if voices or others:
+            raise ValueError('--adapt_voice writes a voice and does nothing else: run --%s as a command of its own'
+                             % (others[0] if others else 'voice'))
+        if adapt in speaker2id:
+            raise ValueError('--adapt_voice %r is a speaker of %s already' % (adapt, args.speaker2id_path))
+        if args.adapt_init is not None and args.adapt_init not in speaker2id:
+            raise ValueError('--adapt_init %r is not in %s' % (args.adapt_init, args.speaker2id_path))
+        if args.adapt_iters is not None and args.adapt_iters < 1:
+            raise ValueError('--adapt_iters must be >= 1 (got %d)' % args.adapt_iters)
+        if args.adapt_lr is not None and not args.adapt_lr > 0.0:
+            raise ValueError('--adapt_lr must be > 0 (got %r)' % args.adapt_lr)
+    if voices:
+        if args.convert_dir is None and args.synth_dir is None:
+            raise ValueError('--voice needs --convert_dir or --synth_dir')
+        if not args.enc_only:
+            raise ValueError('--voice needs --enc_only: voices convert through the autoencoder alone (the stage-2 generator has rows '
+                             'for its trained target speakers only)')
+        for name in voices:
+            if name in speaker2id:
+                raise ValueError('--voice %r is a speaker of %s already' % (name, args.speaker2id_path))
+    if args.enc_mode == 'continues':
+        raise ValueError("enc_mode 'continues' has no units to cache: voices need a discrete encoder mode")
 
 
 def convert_targets(args):
@@ -232,6 +319,7 @@ def argument_runner(argv=None):
     args = parser.parse_args(argv)
     check_resume(args)
     check_ema(args)
+    check_voice(args)
     from zs_amd.validation import check_flags
     check_flags(args)
     args.t_speakers = convert_targets(args) if (args.convert_dir is not None or args.synth_dir is not None) else None
@@ -253,6 +341,7 @@ def argument_runner(argv=None):
         args.g_mode = hps.g_mode
     if args.enc_mode == 'set_from_hps':
         args.enc_mode = hps.enc_mode
+    check_voice(args)                         # again, now that enc_mode is known
     print('[Runner] - Generation mode: ', 'autoencoder only' if args.enc_only else 'with generator')
     print('[Runner] - Generator mode: ', args.g_mode)
     print('[Runner] - Encoder mode: ', args.enc_mode)
@@ -345,6 +434,20 @@ def main(argv=None):
             print("[Runner] - --train ran the pretrain_AE and patchGAN stages; the reference's autolocker / t_classify / Tacotron "
                   'stages are not part of this build and were skipped')
 
+    if args.adapt_voice is not None:                      # not in the reference: enrol a new target voice (zs_amd.voice)
+        import json
+        from zs_amd import voice
+        model_path = args.ckpt_pth if args.ckpt_pth is not None else os.path.join(args.ckpt_dir, args.load_test_model_name)
+        trainer = get_trainer(args.hps_path, model_path, args.g_mode, args.enc_mode, use_ema=args.use_ema)
+        speaker2id = {}
+        if os.path.exists(args.speaker2id_path):
+            with open(args.speaker2id_path, 'r') as f_json:
+                speaker2id = json.load(f_json)
+        voice.adapt(trainer, hps.seg_len, args.adapt_dir, args.adapt_voice,
+                    args.voice_dir if args.voice_dir is not None else os.path.join(args.ckpt_dir, 'voices'), speaker2id=speaker2id,
+                    iters=(args.adapt_iters if args.adapt_iters is not None else voice.ADAPT_ITERS), init=args.adapt_init,
+                    lr=args.adapt_lr)
+
     if args.test or args.cross_test or args.test_encode or args.test_single or args.test_classify or args.convert_dir is not None or \
             args.synth_dir is not None:
         os.makedirs(args.result_dir, exist_ok=True)
@@ -352,6 +455,10 @@ def main(argv=None):
         trainer = get_trainer(args.hps_path, model_path, args.g_mode, args.enc_mode, args.load_tclf_model_name, use_ema=args.use_ema)
         result_dir = os.path.join(args.result_dir, args.sub_result_dir)
         os.makedirs(result_dir, exist_ok=True)
+        voices = None
+        if args.voice:                                    # --voice NAME=FILE: rows appended to the Decoder's tables (zs_amd.voice)
+            from zs_amd.voice import add_voices
+            voices = add_voices(trainer, voice_files(args))
         if args.test:
             test_from_list(trainer, hps.seg_len, args.synthesis_list, args.dataset_path, args.speaker2id_path, result_dir, args.enc_only)
         if args.cross_test:                               # main.py:188-189
@@ -364,10 +471,10 @@ def main(argv=None):
             target_classify(trainer, hps.seg_len, args.synthesis_list, result_dir, flag='test')
         if args.convert_dir is not None:                  # not in the reference: a folder of sound files to the target voices
             convert_dir(trainer, hps.seg_len, args.convert_dir, args.speaker2id_path, os.path.join(result_dir, 'convert'), args.t_speakers,
-                        args.enc_only)
+                        args.enc_only, voices=voices)
         if args.synth_dir is not None:                    # not in the reference: a folder of unit files spoken by the target voices
             synth_dir(trainer, hps.seg_len, args.synth_dir, args.speaker2id_path, os.path.join(result_dir, 'synth'), args.t_speakers,
-                      args.enc_only)
+                      args.enc_only, voices=voices)
 
 
 if __name__ == '__main__':

@@ -1062,7 +1062,29 @@ def convert_dir_plan(files, durations, targets, out_dir, batch=64, max_batch_sec
     return {'groups': groups, 'skipped': skipped}
 
 
-def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None):
+def _target_table(who, trainer, speaker2id, voices, t_speakers, enc_only, speaker2id_path):
+    """The name -> Decoder row table of a folder driver: speaker2id, then the registered voices (zs_amd.voice.add_voices: {name:
+    row}; a name in both keeps its speaker2id row).  ValueError for a target in neither, and for voices with the generator."""
+    if voices:
+        if not enc_only:
+            raise ValueError('%s: voices convert through the autoencoder alone (enc_only): the stage-2 generator has rows for its '
+                             'trained target speakers only' % who)
+    missing = [t for t in t_speakers if t not in speaker2id and t not in (voices or {})]
+    if missing:
+        raise ValueError('%s: target speaker %r is not in %s%s' % (who, missing[0], speaker2id_path,
+                                                                   ' nor a registered voice' if voices else ''))
+    if voices:
+        from .voice import resolve_speaker
+        speaker2id = dict(speaker2id, **{t: resolve_speaker(t, speaker2id, voices) for t in t_speakers})
+    n_rows = int(trainer.Decoder.c_a)
+    bad = [t for t in t_speakers if not 0 <= int(speaker2id[t]) < n_rows] if voices else []
+    if bad:
+        raise ValueError('%s: target %r is row %d of a Decoder with %d rows' % (who, bad[0], int(speaker2id[bad[0]]), n_rows))
+    return speaker2id
+
+
+def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None,
+                voices=None):
     """Every *.wav of in_dir (any PCM / float format, any rate, channels averaged: preprocess.read_wav) to every target speaker of
     t_speakers, on the device from the samples to the waveform: {out_dir}/{target}/{stem}.wav (PCM16 at out_rate()) and .txt (the
     units), plus the manifest {out_dir}/convert_dir.json, which is returned.
@@ -1070,16 +1092,16 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
     zs_pre_spectrogram) are computed once and shared by its targets, every item draws its own Gumbel noise as in cross_test, group
     i + 1 is enqueued before group i is written (defer=True), and one reader thread reads the files of the next group meanwhile.
     The targets are checked before anything is read or enqueued.  A file that cannot be read, or is too short after trimming, is
-    skipped with a printed reason and listed in the manifest; the run goes on."""
+    skipped with a printed reason and listed in the manifest; the run goes on.
+    voices: {name: Decoder row} of voices registered with zs_amd.voice.add_voices (enc_only alone): t_speakers may name them, and
+    the manifest then lists them under 'voices'."""
     from concurrent.futures import ThreadPoolExecutor
     from .preprocess import read_wav, wav_info
     momentum = gl_momentum(momentum)
     with open(speaker2id_path, 'r') as f_json:
         speaker2id = json.load(f_json)
     t_speakers = list(t_speakers)
-    missing = [t for t in t_speakers if t not in speaker2id]
-    if missing:
-        raise ValueError('convert_dir: target speaker %r is not in %s' % (missing[0], speaker2id_path))
+    speaker2id = _target_table('convert_dir', trainer, speaker2id, voices, t_speakers, enc_only, speaker2id_path)
     if not enc_only:
         check_gen_targets(trainer, [speaker2id[t] for t in t_speakers])
     skipped, files, durations = [], [], []
@@ -1167,6 +1189,8 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
                 'items': [{'input': it['file'], 'rate': it['rate'], 'samples': it['samples'], 'target': it['target'],
                            'bounds': it['bounds'], 'frames': it['frames'], 'wav': it['wav'], 'txt': it['txt']} for it in done],
                 'skipped': skipped}
+    if voices:
+        manifest['voices'] = {t: int(voices[t]) for t in t_speakers if t in voices and speaker2id[t] == voices[t]}
     with open(os.path.join(out_dir, 'convert_dir.json'), 'w') as f:
         json.dump(manifest, f, indent=1)
     return manifest
@@ -1215,21 +1239,20 @@ def synth_dir_plan(files, n_units, targets, out_dir, batch=64, max_batch_units=6
     return {'groups': groups, 'skipped': skipped}
 
 
-def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None):
+def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None, voices=None):
     """Every *.txt of in_dir -- unit files as write_encodings writes them (--test_encode, --test, --convert_dir, encode_batch), one
     line of 0 / 1 per unit -- spoken in the voice of every target speaker of t_speakers: {out_dir}/{target}/{stem}.wav (PCM16 at
     out_rate()), plus the manifest {out_dir}/synth_dir.json, which is returned.
     The files are parsed and bit-packed on the host (E / 8 bytes per unit), the items of synth_dir_plan go through
     synth_units_batch in groups, and group i + 1 is enqueued before group i is written (defer=True).  The targets are checked
     before anything is read or enqueued.  A file that cannot be read as units of the Decoder's width, or holds fewer than 2
-    units, is skipped with a printed reason and listed in the manifest; the run goes on."""
+    units, is skipped with a printed reason and listed in the manifest; the run goes on.
+    voices: as convert_dir's."""
     momentum = gl_momentum(momentum)
     with open(speaker2id_path, 'r') as f_json:
         speaker2id = json.load(f_json)
     t_speakers = list(t_speakers)
-    missing = [t for t in t_speakers if t not in speaker2id]
-    if missing:
-        raise ValueError('synth_dir: target speaker %r is not in %s' % (missing[0], speaker2id_path))
+    speaker2id = _target_table('synth_dir', trainer, speaker2id, voices, t_speakers, enc_only, speaker2id_path)
     if trainer.enc_mode == 'continues':
         raise ValueError("enc_mode 'continues' has no units: its encodings are real-valued and cannot be synthesised from unit files")
     if not enc_only:
@@ -1276,6 +1299,8 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
                 'items': [{'input': it['file'], 'units': it['units'], 'fragments': unit_fragments(it['units'], seg_len),
                            'target': it['target'], 'wav': it['wav']} for it in done],
                 'skipped': skipped}
+    if voices:
+        manifest['voices'] = {t: int(voices[t]) for t in t_speakers if t in voices and speaker2id[t] == voices[t]}
     with open(os.path.join(out_dir, 'synth_dir.json'), 'w') as f:
         json.dump(manifest, f, indent=1)
     return manifest

@@ -459,13 +459,16 @@ class DecoderEngine(object):
         self.tape = tp
         return xdec
 
-    def backward(self, dlogit, need_dbits=True):
+    def backward(self, dlogit, need_dbits=True, param_grads=True):
         """dlogit: Act [B,T,F] gradient w.r.t. the pre-sigmoid output.  Fills (overwrites) every decoder parameter
-        gradient.  Returns dbits Act [B,T',E]."""
-        self.backward_head(dlogit)
-        return self.backward_convs(need_dbits)
+        gradient.  Returns dbits Act [B,T',E].
+        param_grads=False (voice adaptation, zs_amd.voice): the data-gradient chain alone -- the same launches on the main stream,
+        which leave the per-sample embedding sums in self._embsum (slots 0..4: emb1..emb5, fp32 [B, c_h] each) -- without any
+        weight-gradient launch, side stream or zs_emb_scatter: no gradient buffer is written."""
+        self.backward_head(dlogit, param_grads)
+        return self.backward_convs(need_dbits, param_grads)
 
-    def backward_head(self, dlogit):
+    def backward_head(self, dlogit, param_grads=True):
         """linear, dense5, the GRU and the two dense blocks: the gradients of dense1 .. linear (a contiguous range of the flat
         gradient buffer) are final when this returns and the side streams have been joined -- data parallel training starts their
         all-reduce here, under the conv blocks' backward (trainer.AEStep)."""
@@ -478,7 +481,8 @@ class DecoderEngine(object):
         ed, er = self.e_dense, self.e_rnn
         self._embsum = c.f32('d_embsum' + tag, 6 * B * ch)      # slots 0..4: per-sample sums for emb1..emb5; 5: column sums of dz5
         self._embsum.zero_()
-        self.linear.wgrad(dlogit, h5)
+        if param_grads:
+            self.linear.wgrad(dlogit, h5)
         dz5 = c.act('d_dz5' + tag, B, T, ch)
         # the embedding parts of the k = 1 data gradients (per-sample column sums) come out of the GEMM epilogues when whole
         # samples fit a tile (ZsGemmConv.colsum); otherwise a zs_grad_combine pass over the gradient computes them
@@ -490,7 +494,8 @@ class DecoderEngine(object):
         # GEMM that produces it) times the block, a B-row GEMM, instead of a third of dense5's data gradient
         thin5 = fuse and ch % 128 == 0 and os.environ.get('ZS_THIN_EMB5', '1') == '1'
         self.linear.dgrad(dlogit, T, dz5, dact_src=h5, slope=ns, colsum=(slot(5) if thin5 else None), colsum_post=True)
-        self.dense5.wgrad(dz5, cat3)
+        if param_grads:
+            self.dense5.wgrad(dz5, cat3)
         dcat3 = c.act('d_dcat3' + tag, B, T, 3 * ch)
         if thin5:
             self.dense5.dgrad(dz5, T, dcat3, n_cols=2 * ch)
@@ -510,23 +515,26 @@ class DecoderEngine(object):
         gpv = Act(gp.t, B, T, ch, gp.ld)
         dx = c.act('d_dxA' + tag, B, T, ch)
         if fuse:                                                                                     # out+emb5 (:353)
-            self.gru.bwd(dcat3, ch, cat3, ch, tp['gates'], tp['gru_in'], dgi, dgh, dx, add_src=dcat3.sub(0, ch), colsum=slot(er))
+            self.gru.bwd(dcat3, ch, cat3, ch, tp['gates'], tp['gru_in'], dgi, dgh, dx, add_src=dcat3.sub(0, ch), colsum=slot(er),
+                         param_grads=param_grads)
         else:
-            self.gru.bwd(dcat3, ch, cat3, ch, tp['gates'], tp['gru_in'], dgi, dgh, gpv)
+            self.gru.bwd(dcat3, ch, cat3, ch, tp['gates'], tp['gru_in'], dgi, dgh, gpv, param_grads=param_grads)
             grad_combine(c, gpv, T, 0, 0, self.pad_mode, ch, dx, ns, emb_sum=esum(er), res_mode=L.ZS_RES_IDENTITY, res=dcat3.sub(0, ch))
         for j in (1, 0):
             la, lb = self.dense[j]
             xin, xe, y1, y1e, y2, stt = tp['dense'][j]
             dz2 = c.act('d_dz2%d' % j + tag, B, T, ch)           # unique per block: read later by the side-stream wgrad
             instnorm_bwd(c, dx, y2, *stt, dz2, ns)
-            lb.wgrad(dz2, y1e)
+            if param_grads:
+                lb.wgrad(dz2, y1e)
             dz1 = c.act('d_dz1%d' % j + tag, B, T, ch)
             if fuse:
                 lb.dgrad(dz2, T, dz1, dact_src=y1, slope=ns, colsum=slot(ed))
             else:
                 lb.dgrad(dz2, T, gpv)
                 grad_combine(c, gpv, T, 0, 0, self.pad_mode, ch, dz1, ns, emb_sum=esum(ed), dact=y1)
-            la.wgrad(dz1, xe)
+            if param_grads:
+                la.wgrad(dz1, xe)
             dn = c.act('d_dxD%d' % j + tag, B, T, ch)
             if fuse:
                 la.dgrad(dz1, T, dn, add_src=dx, colsum=slot(ed))
@@ -536,8 +544,8 @@ class DecoderEngine(object):
             dx = dn
         self._bw = (dx, gp, tag)
 
-    def backward_convs(self, need_dbits=True):
-        """The three conv blocks, the embeddings and input_emb.  Returns dbits."""
+    def backward_convs(self, need_dbits=True, param_grads=True):
+        """The three conv blocks, the embeddings and input_emb.  Returns dbits.  param_grads: see backward()."""
         c, ns, ch, tp = self.ctx, self.ns, self.ch, self.tape
         dx, gp, tag = self._bw
         B, T0 = tp['B'], tp['T0']
@@ -548,12 +556,14 @@ class DecoderEngine(object):
             T2 = 2 * Ti
             dzb = c.act('d_dzb%d' % i + tag, B, T2, ch)
             instnorm_bwd(c, dx, yb, *stt, dzb, ns)
-            lb.wgrad(dzb, s)
+            if param_grads:
+                lb.wgrad(dzb, s)
             gp2 = Act(gp.t, B, T2 + 2, ch, gp.ld)
             lb.dgrad(dzb, T2, gp2)
             dza = c.act('d_dza%d' % i + tag, B, Ti, 2 * ch)
             grad_combine(c, gp2, T2, 1, 1, self.pad_mode, ch, dza, ns, emb_sum=esum, dact=ya, unshuffle=1)   # pixel_shuffle^T, +emb (:323-324)
-            la.wgrad(dza, xe)
+            if param_grads:
+                la.wgrad(dza, xe)
             gp1 = Act(gp.t, B, Ti + 2, ch, gp.ld)
             la.dgrad(dza, Ti, gp1)
             dn = c.act('d_dxC%d' % i + tag, B, Ti, ch)
@@ -561,13 +571,14 @@ class DecoderEngine(object):
                          res=dx)                                                                # x+emb (:319) and upsample(x) (:329)
             dx = dn
         # nn.Embedding backward, fixed sample order.  Only the optimizer needs these: off the main chain, side by side
-        sts = fork_side(c.device) if c.overlap_wgrad else None
-        for k in range(5):
+        sts = fork_side(c.device) if (c.overlap_wgrad and param_grads) else None
+        for k in (range(5) if param_grads else ()):
             st_k = sts[k % len(sts)].cuda_stream if sts is not None else c.stream
             L.call('zs_emb_scatter', 'ZsEmbScatter', st_k, emb_sum=L.ptr(self._embsum, k * B * ch), emb_ld=ch,
                    idx=L.ptr(tp['cidx']), B=B, demb=L.ptr(self.gemb[k]), demb_ld=ch, n_rows=self.n_spk, C=ch, accumulate=0)
         bits = tp['bits']
-        self.input_emb.wgrad(dx, bits)
+        if param_grads:
+            self.input_emb.wgrad(dx, bits)
         dbits = None
         if need_dbits:
             dbits = c.act('d_dbits' + tag, B, T0, self.E)
