@@ -60,6 +60,10 @@ const char* zs_last_error(void);
  *   "gru_persist" (ZS_GRU_PERSIST, 1): one persistent launch per GRU pass where H allows and the grid fits one workgroup per CU
  *   "gru_wide" (ZS_GRU_WIDE, 1): bf16, H in {128, 256, 512}: the persistent kernels' 16-row x 64-unit tiling
  *   "gru_spin_limit" (ZS_GRU_SPIN_LIMIT, 2097152): granule sweeps a persistent GRU wave waits for its group (see ZsGruFwd.status); 0 = timeout
+ *   "gru_xcd_groups" (ZS_GRU_XCD_GROUPS, 1): WIDE hand-off BPTT launches whose (row groups x 2) is a multiple of 8 order their grid
+ *       so that the H/64 workgroups of a group share an XCD (placement only, bit-identical results); 0 = unit chunk fastest
+ *   "gru_solo_max_h" (ZS_GRU_SOLO_MAX_H, 128): WIDE launches with H = 128 <= this run the one-workgroup kernels (see zs_gru_solo); 0 = the
+ *       hand-off kernels.  Not planned while "gru_spin_limit" is 0: that setting exists to force the hand-off's timeout
  *   "norm_wide" (-, 1): InstanceNorm kernels in 8 row groups x 256 channels for short bf16 samples
  *   "norm_lim0" (-, 64): longest T that zs_instnorm_fwd runs in the 8 x 256 decomposition
  *   "norm_lim1" (-, 32): longest T that zs_instnorm_bwd runs in the 8 x 256 decomposition
@@ -460,6 +464,13 @@ int zs_gru_bwd(const ZsGruBwd* p, void* stream);
  * dout_col, ldd and ldgh multiples of 8, dout, out, gates, dgi, dgh 16-byte aligned (zs_gru_fwd / zs_gru_bwd test it themselves). */
 enum { ZS_GRU_PATH_WIDE = 0, ZS_GRU_PATH_PERSIST = 1, ZS_GRU_PATH_STEP_FUSED = 2, ZS_GRU_PATH_STEP_GEMM = 3 };
 int zs_gru_path(int32_t pass, int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t whh_interleaved, int32_t wide_aligned);
+/* zs_gru_solo: 1 when that launch would run the one-workgroup variant of WIDE now, else 0; negative on bad arguments (the arguments
+ * and the plan function of zs_gru_path, whose value the variant does not change).  H = 128 only: W_hh of one direction (96 KB in
+ * bf16) fits the registers of ONE workgroup, which then owns all units of its 16 batch rows: h_{t-1} goes through LDS and nothing
+ * is handed between CUs.  Such a launch issues no memset, neither reads nor writes `work` (zs_gru_check keeps reporting what was
+ * there), cannot time out and never touches `status`; its results are bit-equal to the hand-off kernels'.  Needs WIDE, H <=
+ * "gru_solo_max_h" and "gru_spin_limit" != 0. */
+int zs_gru_solo(int32_t pass, int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t whh_interleaved, int32_t wide_aligned);
 
 /* ---------------------------------------------------------------------------------------------
  * zs_l1_loss: loss = mean|x_dec - x| over rows*F (trainer.py:328) and the gradient w.r.t. the

@@ -798,6 +798,7 @@ struct GruPersistBwdArgs {
   unsigned* status;              // sticky status word (bit 1 = BPTT timeout), see GruPersistArgs
   unsigned spin_limit;
   int B, T, H, rows_pad;
+  int xcd_groups;                // WIDE: grid = (row group * 2 + direction, unit chunk): the members of a group share blockIdx % 8
 };
 
 // Tiling: 64 hidden units x 16 rows per workgroup (forward: 32 x 32): the BPTT sweep reads all 3H columns of its rows, so fewer
@@ -972,9 +973,12 @@ __global__ __launch_bounds__(256) void gru_wide_bwd_kernel(const GruPersistBwdAr
   __shared__ __attribute__((aligned(16))) bf16_t out_s[2][4][16][64];               // dr_pre, dz_pre, dn_pre, dn_pre*r of the step
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q = lane >> 4, r = lane & 15;
-  const int d = blockIdx.z, T_ = a.T;
-  const int m0 = blockIdx.y * 16;
-  const int u_wg = blockIdx.x * 64;
+  // Placement, for speed only (nothing below depends on it).  Workgroups are dealt round-robin over the 8 XCDs in linear block
+  // order, so with the unit chunk as blockIdx.x the H/64 members of a group sit on different XCDs.  With xcd_groups the grid is
+  // (row group * 2 + direction, unit chunk) and its x extent a multiple of 8: all members of a group share blockIdx % 8.
+  const int d = a.xcd_groups ? (int)(blockIdx.x & 1) : (int)blockIdx.z, T_ = a.T;
+  const int m0 = (a.xcd_groups ? (int)(blockIdx.x >> 1) : (int)blockIdx.y) * 16;
+  const int u_wg = (a.xcd_groups ? (int)blockIdx.y : (int)blockIdx.x) * 64;
   const int ul = wave * 16 + r;
   const int unit = u_wg + ul;
   constexpr int gpr = 3 * H / 2;                        // granules per row
@@ -1149,12 +1153,270 @@ __global__ __launch_bounds__(256) void gru_wide_bwd_kernel(const GruPersistBwdAr
   __syncthreads();
   copy_out((T_ - 1) & 1, T_ - 1);
 #ifdef ZS_GRU_PROFILE
-  if (blockIdx.x == 2 && blockIdx.y == 3 && d == 0 && tid == 0) {
+  if (u_wg == 128 && m0 == 48 && d == 0 && tid == 0) {
     long long* o = reinterpret_cast<long long*>(a.err) + 8;        // header bytes 64..
     for (int k = 0; k < 5; ++k) o[k] = pc[k];
   }
 #endif
 #undef ZS_PT
+}
+
+// ------------------------------------------------------------------------------------------------
+// "Solo" persistent recurrence (bf16, H = 128): the wide kernels with the exchange taken out.  W_hh of one direction is 96 KB, 24
+// 16-byte fragments (96 VGPRs) per lane of ONE workgroup, so a workgroup owns all 128 units of its 16 batch rows and nothing ever
+// leaves the CU: h_{s-1} (BPTT: dgh_{s-1}) goes through the two LDS images, a step has one barrier, and there is no exchange
+// buffer, no memset in front of the launch, no sc1 sweep, no spin, no error word and no co-residency requirement.  Wave w owns units
+// 32w .. 32w+31 as two 16-unit MFMA tiles that share the A fragments read from the image.  Every accumulator chain keeps the wide
+// kernel's order (forward: one chain per gate, k-steps ascending; BPTT: three chains by gate block, (acc0 + acc1) + acc2) and the
+// gate math is the same expressions, so every output is bit-equal to the wide path's (tests/test_gpu_gru_solo.py).
+// Staging as in the wide kernels: gate inputs / tape fetched one step ahead as 16-byte loads, outputs leave as 16-byte stores one
+// step later.  The BPTT takes dr_pre, dz_pre and dn_pre*r of a step from the image it has just written (they ARE dgh of the step)
+// and stages only dn_pre beside it: with four staged arrays of 128 units the kernel would need 105 KB of LDS.
+// ------------------------------------------------------------------------------------------------
+constexpr int SOLO_H = 128;
+constexpr int SOLO_KS = SOLO_H / 32;
+// Row pitch of the staging arrays in elements: 8 more than H, so that the rows 4q + i a wave touches in one 2-byte access (q = lane >> 4)
+// start 16 banks apart instead of in the same bank; a multiple of 8 keeps the 16-byte transfers aligned.
+constexpr int SOLO_HP = SOLO_H + 8;
+
+__global__ __launch_bounds__(256) void gru_solo_fwd_kernel(const GruPersistArgs a) {
+  constexpr int H = SOLO_H, KS = SOLO_KS;
+  constexpr int PITCH = H * 2 + 16;                     // bytes per row of the LDS image
+  __shared__ __attribute__((aligned(16))) unsigned char himg[2][16 * PITCH];      // h_{s-1}, by step parity
+  __shared__ __attribute__((aligned(16))) bf16_t gi_s[2][16][3][SOLO_HP];          // gate inputs of the step, by step parity
+  __shared__ __attribute__((aligned(16))) bf16_t out_s[2][5][16][SOLO_HP];         // h, r, z, n, hn of the step, by step parity
+  __shared__ __attribute__((aligned(16))) bf16_t bc_s[16][SOLO_HP];                // broadcast values (constant over time)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int q = lane >> 4, r = lane & 15;
+  const int d = blockIdx.z, T_ = a.T;
+  const int m0 = blockIdx.y * 16;
+
+  // W_hh rows of this wave: packed (gate-interleaved per 32 units) row of (gate g, unit 32 w + 16 tl + r) = 96 w + 32 g + 16 tl + r
+  uint4 fb[2][KS][3];
+  {
+    const bf16_t* Wb = (const bf16_t*)a.whh + (int64_t)d * a.w_gstride + (int64_t)(wave * 96 + r) * a.ldw + q * 8;
+#pragma unroll
+    for (int tl = 0; tl < 2; ++tl)
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+        for (int g = 0; g < 3; ++g) fb[tl][ks][g] = *reinterpret_cast<const uint4*>(Wb + (int64_t)(32 * g + 16 * tl) * a.ldw + ks * 32);
+  }
+  const float* bh = a.bhh + (int64_t)d * a.bhh_gstride;
+  int unit[2];
+  float b_r[2], b_z[2], b_n[2];
+#pragma unroll
+  for (int tl = 0; tl < 2; ++tl) {
+    unit[tl] = wave * 32 + tl * 16 + r;                 // this lane's units (accumulator layout)
+    b_r[tl] = bh[unit[tl]]; b_z[tl] = bh[H + unit[tl]]; b_n[tl] = bh[2 * H + unit[tl]];
+  }
+  // cooperative 16-byte transfers (8 units each).  gate inputs: 16 rows x 3 gates x 16 chunks = 768 (thread: tid + 256 k, k < 3);
+  // outputs: 6 arrays (h, r, z, n, hn, broadcast) x 16 rows x 16 chunks = 1536 (thread: tid + 256 k, k < 6)
+  auto gi_src = [&](int id, int t) -> const bf16_t* {
+    const int row = id / 48, rem = id - row * 48, g = rem >> 4, c = rem & 15;
+    const int b = min(m0 + row, a.B - 1);
+    return (const bf16_t*)a.gi + ((int64_t)b * T_ + t) * a.ldgi + (int64_t)d * 3 * H + g * H + 8 * c;
+  };
+  auto gi_dst = [&](int par, int id) -> uint4* {
+    const int row = id / 48, rem = id - row * 48, g = rem >> 4, c = rem & 15;
+    return reinterpret_cast<uint4*>(&gi_s[par][row][g][8 * c]);
+  };
+  auto copy_out = [&](int par, int t) {                 // staged outputs of one step -> global, 16-byte stores
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {                       // k IS the array: 256 chunks each
+      const int row = tid >> 4, c = tid & 15;
+      const int b = m0 + row;
+      if (b >= a.B) continue;
+      if (k == 0) {
+        *reinterpret_cast<uint4*>((bf16_t*)a.out + ((int64_t)b * T_ + t) * a.ldo + a.out_col + d * H + 8 * c) =
+            *reinterpret_cast<const uint4*>(&out_s[par][0][row][8 * c]);
+      } else if (k < 5) {
+        if (a.gates)
+          *reinterpret_cast<uint4*>((bf16_t*)a.gates + (((int64_t)b * T_ + t) * 2 + d) * 4 * H + (k - 1) * H + 8 * c) =
+              *reinterpret_cast<const uint4*>(&out_s[par][k][row][8 * c]);
+      } else if (a.bcast_vec) {
+        *reinterpret_cast<uint4*>((bf16_t*)a.out + ((int64_t)b * T_ + t) * a.ldo + a.bcast_col + d * H + 8 * c) =
+            *reinterpret_cast<const uint4*>(&bc_s[row][8 * c]);
+      }
+    }
+  };
+  float hp[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  if (a.bcast_vec) {
+#pragma unroll
+    for (int tl = 0; tl < 2; ++tl)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int b = min(m0 + 4 * q + i, a.B - 1);
+        bc_s[4 * q + i][unit[tl]] = f2bf(a.bcast_vec[a.bcast_idx[b] * a.bcast_ld + d * H + unit[tl]]);
+      }
+  }
+  const bool fwd_t = d == 0 || a.dir1_forward;         // this direction walks t = 0 .. T-1
+  // gate inputs of step 0 (later steps: fetched one step ahead)
+  uint4 gq0 = *reinterpret_cast<const uint4*>(gi_src(tid, fwd_t ? 0 : T_ - 1));
+  uint4 gq1 = *reinterpret_cast<const uint4*>(gi_src(tid + 256, fwd_t ? 0 : T_ - 1));
+  uint4 gq2 = *reinterpret_cast<const uint4*>(gi_src(tid + 512, fwd_t ? 0 : T_ - 1));
+
+  for (int s = 0; s < T_; ++s) {
+    const unsigned char* const img = &himg[s & 1][0];
+    f32x4_t acc[2][3];
+#pragma unroll
+    for (int tl = 0; tl < 2; ++tl)
+#pragma unroll
+      for (int g = 0; g < 3; ++g) acc[tl][g] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    *gi_dst(s & 1, tid) = gq0; *gi_dst(s & 1, tid + 256) = gq1; *gi_dst(s & 1, tid + 512) = gq2;
+    __syncthreads();                                     // images of h_{s-1} and of this step's gate inputs are complete
+    if (s > 0) copy_out((s - 1) & 1, fwd_t ? s - 1 : T_ - s);       // the previous step's outputs leave as 16-byte stores
+    if (s + 1 < T_) {                                    // next step's gate inputs: in flight under this step
+      const int tn = fwd_t ? s + 1 : T_ - 2 - s;
+      gq0 = *reinterpret_cast<const uint4*>(gi_src(tid, tn));
+      gq1 = *reinterpret_cast<const uint4*>(gi_src(tid + 256, tn));
+      gq2 = *reinterpret_cast<const uint4*>(gi_src(tid + 512, tn));
+    }
+    if (s > 0) {
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        const uint4 fa = *reinterpret_cast<const uint4*>(img + r * PITCH + q * 16 + ks * 64);
+#pragma unroll
+        for (int tl = 0; tl < 2; ++tl)
+#pragma unroll
+          for (int g = 0; g < 3; ++g) Frag16<bf16_t>::mma(fa, fb[tl][ks][g], acc[tl][g]);
+      }
+    }
+    // gate math: lane owns (row 4q + i, unit[tl]) for i < 4
+    unsigned char* const nimg = &himg[(s + 1) & 1][0];
+#pragma unroll
+    for (int tl = 0; tl < 2; ++tl) {
+      const int ul = unit[tl];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float gi_r = bf2f(gi_s[s & 1][4 * q + i][0][ul]), gi_z = bf2f(gi_s[s & 1][4 * q + i][1][ul]), gi_n = bf2f(gi_s[s & 1][4 * q + i][2][ul]);
+        const float rg = 1.f / (1.f + expf(-(gi_r + (acc[tl][0][i] + b_r[tl]))));
+        const float zg = 1.f / (1.f + expf(-(gi_z + (acc[tl][1][i] + b_z[tl]))));
+        const float hn = acc[tl][2][i] + b_n[tl];
+        const float ng = tanhf(gi_n + rg * hn);
+        // h = (1 - z) n + z h_prev with the fusion gru_wide_fwd_kernel<4> is compiled with, stated: the product (1 - z) n
+        // rounded, then ONE fma.  Left to the compiler this kernel gets the other fusion (z h_prev rounded first, as the <8>
+        // and <16> instantiations do) and h differs from the hand-off kernel's in the last bit of one element in a few.
+        const float hv = __builtin_fmaf(zg, hp[tl][i], (1.f - zg) * ng);
+        hp[tl][i] = hv;
+        const bf16_t hb = f2bf(hv);
+        if (s + 1 < T_) *reinterpret_cast<bf16_t*>(nimg + (4 * q + i) * PITCH + ul * 2) = hb;    // h_s for the next step's product
+        out_s[s & 1][0][4 * q + i][ul] = hb;
+        out_s[s & 1][1][4 * q + i][ul] = f2bf(rg); out_s[s & 1][2][4 * q + i][ul] = f2bf(zg);
+        out_s[s & 1][3][4 * q + i][ul] = f2bf(ng); out_s[s & 1][4][4 * q + i][ul] = f2bf(hn);
+      }
+    }
+  }
+  __syncthreads();
+  copy_out((T_ - 1) & 1, fwd_t ? T_ - 1 : 0);
+}
+
+__global__ __launch_bounds__(256) void gru_solo_bwd_kernel(const GruPersistBwdArgs a) {
+  constexpr int H = SOLO_H, KS = SOLO_KS;
+  constexpr int PITCH = 3 * H * 2 + 16;                 // bytes per row of the LDS image of dgh
+  __shared__ __attribute__((aligned(16))) unsigned char gimg[2][16 * PITCH];       // dgh of the previous BPTT step, by step parity
+  __shared__ __attribute__((aligned(16))) bf16_t in_s[2][6][16][SOLO_HP];           // r, z, n, hn, dout, h_prev of the step
+  __shared__ __attribute__((aligned(16))) bf16_t dn_s[2][16][SOLO_HP];              // dn_pre of the step (dr_pre, dz_pre, dn_pre*r: gimg)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int q = lane >> 4, r = lane & 15;
+  const int d = blockIdx.z, T_ = a.T;
+  const int m0 = blockIdx.y * 16;
+
+  uint4 fb[2][3 * KS];                                   // rows (unit) of W_hh^T, K = 3H contiguous
+  int unit[2];
+#pragma unroll
+  for (int tl = 0; tl < 2; ++tl) {
+    unit[tl] = wave * 32 + tl * 16 + r;
+    const bf16_t* Wb = (const bf16_t*)a.whh_t + (int64_t)d * a.w_gstride + (int64_t)unit[tl] * a.ldw + q * 8;
+#pragma unroll
+    for (int kk = 0; kk < 3 * KS; ++kk) fb[tl][kk] = *reinterpret_cast<const uint4*>(Wb + kk * 32);
+  }
+  // cooperative 16-byte transfers (8 units each): 6 input arrays x 16 rows x 16 chunks = 1536 = 6 per thread (k IS the array);
+  // outputs likewise (dgi: dr, dz, dn ; dgh: dr, dz, dn*r)
+  const int x_row = tid >> 4, x_c = tid & 15;
+  auto in_src = [&](int arr, int s_) -> const bf16_t* {
+    const int b = min(m0 + x_row, a.B - 1);
+    const int t = d == 0 ? T_ - 1 - s_ : s_;
+    if (arr < 4) return (const bf16_t*)a.gates + (((int64_t)b * T_ + t) * 2 + d) * 4 * H + arr * H + 8 * x_c;
+    if (arr == 4) return (const bf16_t*)a.dout + ((int64_t)b * T_ + t) * a.ldd + a.dout_col + d * H + 8 * x_c;
+    const int tp = s_ < T_ - 1 ? (d == 0 ? t - 1 : t + 1) : t;            // last BPTT step: h_prev = 0 (zeroed below)
+    return (const bf16_t*)a.out + ((int64_t)b * T_ + tp) * a.ldo + a.out_col + d * H + 8 * x_c;
+  };
+  auto copy_out = [&](int s_) {                          // image (s_ + 1) & 1 holds dgh of BPTT step s_
+    const int t = d == 0 ? T_ - 1 - s_ : s_;
+    const int b = m0 + x_row;
+    if (b >= a.B) return;
+    const unsigned char* const grow = &gimg[(s_ + 1) & 1][0] + x_row * PITCH;
+#pragma unroll
+    for (int arr = 0; arr < 6; ++arr) {                  // arr 0..2: dgi r, z, n ; 3..5: dgh r, z, n
+      const int g = arr < 3 ? arr : arr - 3;
+      bf16_t* base = arr < 3 ? (bf16_t*)a.dgi + ((int64_t)b * T_ + t) * a.ldgi : (bf16_t*)a.dgh + ((int64_t)b * T_ + t) * a.ldgh;
+      const uint4 v = arr == 2 ? *reinterpret_cast<const uint4*>(&dn_s[s_ & 1][x_row][8 * x_c])
+                               : *reinterpret_cast<const uint4*>(grow + (g * H + 8 * x_c) * 2);
+      *reinterpret_cast<uint4*>(base + (int64_t)d * 3 * H + g * H + 8 * x_c) = v;
+    }
+  };
+  uint4 gq[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) gq[k] = *reinterpret_cast<const uint4*>(in_src(k, 0));
+  float dhd[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};      // direct carry dh * z of the previous BPTT step
+
+  for (int s = 0; s < T_; ++s) {
+    const unsigned char* const img = &gimg[s & 1][0];
+    f32x4_t acc[2][3];
+#pragma unroll
+    for (int tl = 0; tl < 2; ++tl)
+#pragma unroll
+      for (int g = 0; g < 3; ++g) acc[tl][g] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      uint4 v = gq[k];
+      if (k == 5 && s == T_ - 1) v = make_uint4(0, 0, 0, 0);                  // h_prev of the first time step is h0 = 0
+      *reinterpret_cast<uint4*>(&in_s[s & 1][k][x_row][8 * x_c]) = v;
+    }
+    __syncthreads();                                     // images of dgh_{s-1} and of this step's operands are complete
+    if (s > 0) copy_out(s - 1);
+    if (s + 1 < T_) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) gq[k] = *reinterpret_cast<const uint4*>(in_src(k, s + 1));
+    }
+    if (s > 0) {
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)                    // the three accumulator chains (gate blocks of K) interleaved
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+          const uint4 fa = *reinterpret_cast<const uint4*>(img + r * PITCH + q * 16 + (g * KS + ks) * 64);
+#pragma unroll
+          for (int tl = 0; tl < 2; ++tl) Frag16<bf16_t>::mma(fa, fb[tl][g * KS + ks], acc[tl][g]);
+        }
+    }
+    unsigned char* const nimg = &gimg[(s + 1) & 1][0];
+#pragma unroll
+    for (int tl = 0; tl < 2; ++tl) {
+      const int ul = unit[tl];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = 4 * q + i;
+        const float r_ = bf2f(in_s[s & 1][0][row][ul]), z_ = bf2f(in_s[s & 1][1][row][ul]), n_ = bf2f(in_s[s & 1][2][row][ul]);
+        const float hn_ = bf2f(in_s[s & 1][3][row][ul]), do_ = bf2f(in_s[s & 1][4][row][ul]), hp_ = bf2f(in_s[s & 1][5][row][ul]);
+        float dh = do_ + dhd[tl][i];
+        if (s > 0) dh += (acc[tl][0][i] + acc[tl][1][i]) + acc[tl][2][i];
+        const float dn = dh * (1.f - z_);
+        const float dz = dh * (hp_ - n_);
+        dhd[tl][i] = dh * z_;
+        const float dn_pre = dn * (1.f - n_ * n_);
+        const float dr_pre = dn_pre * hn_ * r_ * (1.f - r_);
+        const float dz_pre = dz * z_ * (1.f - z_);
+        const float dnr = dn_pre * r_;
+        // dgh of this step: the next step's product reads it, and copy_out takes the outputs from it
+        bf16_t* irow = reinterpret_cast<bf16_t*>(nimg + row * PITCH);
+        irow[ul] = f2bf(dr_pre); irow[H + ul] = f2bf(dz_pre); irow[2 * H + ul] = f2bf(dnr);
+        dn_s[s & 1][row][ul] = f2bf(dn_pre);
+      }
+    }
+  }
+  __syncthreads();
+  copy_out(T_ - 1);
 }
 
 inline unsigned gate_blocks(int64_t total) {
@@ -1173,6 +1435,8 @@ size_t gru_hx_bytes(int B, int H, int es) {
 Knob g_gru_persist("gru_persist", "ZS_GRU_PERSIST", 1, knob_flag);
 Knob g_gru_wide("gru_wide", "ZS_GRU_WIDE", 1, knob_flag);         // the 16-row x 64-unit tiling of the persistent kernels
 Knob g_gru_spin_limit("gru_spin_limit", "ZS_GRU_SPIN_LIMIT", (int)GRU_SPIN_LIMIT);   // tests force a timeout with 0
+Knob g_gru_xcd_groups("gru_xcd_groups", "ZS_GRU_XCD_GROUPS", 1);   // gru_wide_bwd_kernel: the members of a hand-off group on one XCD
+Knob g_gru_solo_max_h("gru_solo_max_h", "ZS_GRU_SOLO_MAX_H", SOLO_H);      // largest H the one-workgroup kernels take; 0 = never
 // workgroups that are certainly co-resident: one per CU
 int64_t gru_resident_limit() {
   static std::atomic<int> cus{0};
@@ -1199,36 +1463,41 @@ bool gru_wide_aligned(const ZsGruBwd* p) {
 // How one GRU pass runs (the paths are ZS_GRU_PATH_* in zs_amd.h).  WIDE: one persistent launch of 16-row x 64-unit tiles (bf16,
 // H in {128, 256, 512}).  PERSIST: one persistent launch of 32 x 32 (forward) / 16 x 64 K-split (BPTT) tiles.  STEP_FUSED: one
 // rowblock_gemm_kernel launch per step, recurrent product and gate math fused.  STEP_GEMM: zs_gemm_conv and a gate kernel per step.
+// `solo` is a variant inside WIDE: H = 128 runs gru_solo_*_kernel, one workgroup per (16 rows, direction) and no hand-off.
 struct GruPlan {
   int path;              // ZS_GRU_PATH_*
   int per;               // PERSIST: the kernel's PER (forward) / PERB (BPTT)
   int rb;                // row blocks of the grid (grid.y); 0 for STEP_GEMM
   unsigned spin_limit;
+  bool solo;             // WIDE only: the one-workgroup kernels (no exchange buffer, no memset, no error word)
 };
 
 // The one plan of both passes (pass 0: zs_gru_fwd, 1: zs_gru_bwd); the launches and zs_gru_path call it.  It reads the GRU knobs
 // once.  The forward's persistent and fused paths need W_hh interleaved (the BPTT reads the transposed packing and ignores it).
 GruPlan gru_plan(int pass, int dtype, int B, int T, int H, bool whh_interleaved, bool wide_aligned) {
   const bool bwd = pass != 0;
-  if (H % 32 != 0 || (!bwd && !whh_interleaved)) return {ZS_GRU_PATH_STEP_GEMM, 0, 0, 0};
+  if (H % 32 != 0 || (!bwd && !whh_interleaved)) return {ZS_GRU_PATH_STEP_GEMM, 0, 0, 0, false};
   const bool persist = g_gru_persist.get() != 0 && T > 1, wide = g_gru_wide.get() != 0;
   const unsigned spin = (unsigned)g_gru_spin_limit.get();
   const int nrb16 = (B + 15) / 16, nrb = (B + 16 * RB - 1) / (16 * RB);
   const int kstep = dtype == ZS_F32 ? 16 : 32;
   if (persist && wide && dtype == ZS_BF16 && (H == 128 || H == 256 || H == 512) && (int64_t)(H / 64) * nrb16 * 2 <= gru_resident_limit() &&
-      wide_aligned)
-    return {ZS_GRU_PATH_WIDE, 0, nrb16, spin};
+      wide_aligned) {
+    // "gru_spin_limit" 0 is how a caller forces the hand-off's timeout: such a launch keeps the hand-off kernels
+    const bool solo = H == SOLO_H && H <= g_gru_solo_max_h.get() && spin != 0;
+    return {ZS_GRU_PATH_WIDE, 0, nrb16, spin, solo};
+  }
   if (!bwd) {
     const int per = (H % (4 * kstep) == 0) ? H / (4 * kstep) : 0;
     if (persist && (per == 1 || per == 2 || per == 4) && (int64_t)(H / 32) * nrb * 2 <= gru_resident_limit())
-      return {ZS_GRU_PATH_PERSIST, per, nrb, spin};
-    return {ZS_GRU_PATH_STEP_FUSED, 0, nrb, spin};
+      return {ZS_GRU_PATH_PERSIST, per, nrb, spin, false};
+    return {ZS_GRU_PATH_STEP_FUSED, 0, nrb, spin, false};
   }
   // both persistent BPTT tilings: 16 rows x 64 units per workgroup
   const int perb = ((3 * H) % (4 * kstep) == 0 && H % (16 * BNT) == 0) ? (3 * H) / (4 * kstep) : 0;
   if (persist && (perb == 3 || perb == 6 || perb == 12) && (int64_t)(H / (16 * BNT)) * nrb16 * 2 <= gru_resident_limit())
-    return {ZS_GRU_PATH_PERSIST, perb, nrb16, spin};
-  return {ZS_GRU_PATH_STEP_FUSED, 0, nrb, spin};
+    return {ZS_GRU_PATH_PERSIST, perb, nrb16, spin, false};
+  return {ZS_GRU_PATH_STEP_FUSED, 0, nrb, spin, false};
 }
 
 GruPlan gru_fwd_plan(const ZsGruFwd* p) {
@@ -1270,6 +1539,13 @@ extern "C" int zs_gru_path(int32_t pass, int32_t dtype, int32_t B, int32_t T, in
   return pl.path | (pl.per << 8);
 }
 
+extern "C" int zs_gru_solo(int32_t pass, int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t whh_interleaved, int32_t wide_aligned) {
+  ZS_REQUIRE(pass == 0 || pass == 1, "zs_gru_solo: pass 0 (zs_gru_fwd) or 1 (zs_gru_bwd)");
+  ZS_REQUIRE(dtype == ZS_F32 || dtype == ZS_BF16, "zs_gru_solo: bad dtype");
+  ZS_REQUIRE(B > 0 && T > 0 && H > 0 && H % 8 == 0, "zs_gru_solo: sizes");
+  return gru_plan(pass, dtype, B, T, H, whh_interleaved != 0, wide_aligned != 0).solo ? 1 : 0;
+}
+
 extern "C" int zs_gru_fwd(const ZsGruFwd* p, void* stream) {
   ZS_REQUIRE(p && p->gi && p->whh && p->bhh && p->out && p->work, "zs_gru_fwd: null operand");
   ZS_REQUIRE(p->dtype == ZS_F32 || p->dtype == ZS_BF16, "zs_gru_fwd: bad dtype");
@@ -1306,6 +1582,10 @@ extern "C" int zs_gru_fwd(const ZsGruFwd* p, void* stream) {
     a.B = B; a.T = T; a.H = H; a.rows_pad = pl.path == ZS_GRU_PATH_WIDE ? pl.rb * 16 : pl.rb * 16 * RB;
     a.bcast_vec = p->bcast_vec; a.bcast_ld = p->bcast_ld; a.bcast_idx = p->bcast_idx; a.bcast_col = p->bcast_col;
     a.dir1_forward = p->dir1_forward != 0;
+    if (pl.solo) {                                       // nothing is exchanged: the work buffer is neither zeroed nor touched
+      hipLaunchKernelGGL(gru_solo_fwd_kernel, dim3(1, pl.rb, 2), dim3(256), 0, (hipStream_t)stream, a);
+      return zs_check_launch("zs_gru_fwd.solo");
+    }
     if (hipMemsetAsync(p->work, 0, GRU_WORK_HDR + gru_hx_bytes(B, H, es), (hipStream_t)stream) != hipSuccess) {
       zs_set_error("zs_gru_fwd: memset failed");
       return ZS_ELAUNCH;
@@ -1402,12 +1682,19 @@ extern "C" int zs_gru_bwd(const ZsGruBwd* p, void* stream) {
     a.err = reinterpret_cast<unsigned*>(p->work);
     a.status = p->status; a.spin_limit = pl.spin_limit;
     a.B = B; a.T = T; a.H = H; a.rows_pad = pl.rb * 16;
+    if (pl.solo) {
+      hipLaunchKernelGGL(gru_solo_bwd_kernel, dim3(1, pl.rb, 2), dim3(256), 0, (hipStream_t)stream, a);
+      return zs_check_launch("zs_gru_bwd.solo");
+    }
     if (hipMemsetAsync(p->work, 0, GRU_WORK_HDR + gru_hx_bytes(B, 3 * H, es), (hipStream_t)stream) != hipSuccess) {
       zs_set_error("zs_gru_bwd: memset failed");
       return ZS_ELAUNCH;
     }
     if (pl.path == ZS_GRU_PATH_WIDE) {
       dim3 wgrid(H / 64, pl.rb, 2);
+      // same-XCD groups where the grid allows it (the forward kernel is slower so placed, DESIGN 27, and keeps its grid)
+      a.xcd_groups = g_gru_xcd_groups.get() != 0 && (pl.rb * 2) % 8 == 0;
+      if (a.xcd_groups) wgrid = dim3(pl.rb * 2, H / 64, 1);
       if (H == 512) hipLaunchKernelGGL(gru_wide_bwd_kernel<16>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
       else if (H == 256) hipLaunchKernelGGL(gru_wide_bwd_kernel<8>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
       else hipLaunchKernelGGL(gru_wide_bwd_kernel<4>, wgrid, dim3(256), 0, (hipStream_t)stream, a);
