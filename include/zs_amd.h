@@ -1098,6 +1098,53 @@ typedef struct {
 } ZsEvalAccum;
 int zs_eval_accum(const ZsEvalAccum* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Unit codebook (zs_amd.codebook): K codewords of E bits, fitted by k-modes over bit-packed units; a unit is snapped to its nearest
+ * codeword in Hamming distance.  Rows and bit order are zs_units_pack's (convert.pack_units): `units` uint8 [n][row_bytes], `code`
+ * uint8 [K][code_bytes], bit j of byte b is column 8b + j.  Only the (E + 7) / 8 bytes of a row that carry columns are read or
+ * written: bits at columns >= E of the last of them are ignored on input (units and codewords) and zero on output, and the bytes
+ * of a pitch behind them are never touched.  Everything is integer, so every result is bitwise reproducible.
+ * Limits: 1 <= E <= ZS_CODE_MAX_E, 1 <= K <= ZS_CODE_MAX_K, row_bytes and code_bytes >= (E + 7) / 8, 0 <= n < 2^40.  n == 0 succeeds
+ * and launches nothing.  A null struct, K < 1, K > ZS_CODE_MAX_K, E < 1, E > ZS_CODE_MAX_E, n < 0, a pitch too small or a null
+ * operand with work to do return ZS_EINVAL and launch nothing.  No allocation, no synchronisation; launches are stream-ordered.
+ *
+ * zs_code_assign: for every unit the codeword of least Hamming distance over the columns < E; ties go to the lowest index.
+ *   idx[i]     = that codeword                                   (int32 [n], optional)
+ *   dist[i]    = its distance                                    (int32 [n], optional)
+ *   snapped[i] = code[idx[i]], bits >= E zero                    (uint8 [n][row_bytes], optional; may be `units` itself: in place)
+ *   *total    += sum_i dist[i]                                   (int64, optional)
+ * One unit row per lane in registers (two above ZS_CODE_BIG_N rows); the codewords go through LDS ZS_CODE_TILE_WORDS dwords at a
+ * time, a codeword padded to the next power of two of its dwords, i.e. ZS_CODE_TILE_WORDS / pow2(ceil(E / 32)) codewords per pass.
+ * Below ZS_CODE_SPLIT_N rows the 16 waves of a workgroup share 64 units and a sixteenth of every pass each. */
+#define ZS_CODE_MAX_E 1024
+#define ZS_CODE_MAX_K 65536
+#define ZS_CODE_TILE_WORDS 4096
+#define ZS_CODE_BIG_N 262144
+#define ZS_CODE_SPLIT_N 65536
+typedef struct {
+  const uint8_t* units; int64_t n; int32_t row_bytes;
+  const uint8_t* code; int32_t K, code_bytes, E;
+  int32_t* idx; int32_t* dist; uint8_t* snapped; int64_t* total;
+} ZsCodeAssign;
+int zs_code_assign(const ZsCodeAssign* p, void* stream);
+/* zs_code_accum: the votes of one k-modes iteration.  For every unit i with 0 <= idx[i] < K:
+ *   cnt[idx[i]] += 1,   ones[idx[i]][j] += bit j of unit i  (j < E)          cnt int32 [K], ones int32 [K][E], dense
+ * An idx[i] outside [0, K) is never used as an index: the unit is skipped and *bad += 1 (int32).  Integer atomics, privatised: a
+ * workgroup keeps the counters of a tile of codewords in LDS over its slice of the units and adds the non-zero ones at the end. */
+typedef struct {
+  const uint8_t* units; const int32_t* idx; int64_t n; int32_t row_bytes, K, E;
+  int32_t* cnt; int32_t* ones; int32_t* bad;
+} ZsCodeAccum;
+int zs_code_accum(const ZsCodeAccum* p, void* stream);
+/* zs_code_update: majority vote.  For every k with cnt[k] > 0, bit j < E of code[k] becomes 1 if 2 ones[k][j] > cnt[k], 0 if
+ * 2 ones[k][j] < cnt[k], and stays if they are equal; cnt[k] <= 0 leaves every byte of code[k] as it is.
+ * *changed += #{k : code[k] differs from before in a column < E}  (int32). */
+typedef struct {
+  uint8_t* code; int32_t K, code_bytes, E;
+  const int32_t* cnt; const int32_t* ones; int32_t* changed;
+} ZsCodeUpdate;
+int zs_code_update(const ZsCodeUpdate* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

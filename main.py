@@ -65,6 +65,16 @@ other combination without effect, before anything is built:
   python main.py --adapt_voice ANNA --adapt_dir wavs/ --ckpt_pth CKPT --adapt_init V001
   python main.py --convert_dir in/ --enc_only --voice ANNA=ckpt_english/voices/ANNA.voice.npz --t_speaker ANNA,V001 --ckpt_pth CKPT
 
+--fit_codebook K --fit_dir DIR [--codebook_out FILE] [--codebook_iters N] [--codebook_seed S] (zs_amd.codebook), with --ckpt_pth or
+the usual model flags and --use_ema: the *.wav of DIR (read as --convert_dir reads them) are encoded, the *.txt unit files of DIR are
+added, and K codewords are fitted to all their units by k-modes on the GPU; the codebook goes to FILE (default
+{ckpt_dir}/codebooks/K<K>.codebook.npz) with a fit_codebook.json beside it.  --codebook FILE with --convert_dir, --synth_dir or
+--test_encode snaps every unit to its nearest codeword before it is written and before the Decoder sees it: unit files become
+sequences over at most K symbols, each gets a sibling <name>.idx.txt with one codeword index per line, and convert_dir.json /
+synth_dir.json gain a 'codebook' entry (--synth_dir also writes the snapped units beside each wav):
+  python main.py --fit_codebook 1024 --fit_dir wavs/ --ckpt_pth CKPT
+  python main.py --convert_dir in/ --t_speaker V001 --ckpt_pth CKPT --codebook ckpt_english/codebooks/K1024.codebook.npz
+
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
 (--train_al, --train_t, --encode, --test_asr) are not part of this build and exit with a clear error.
@@ -116,7 +126,28 @@ def _ema(text):
     return d
 
 
+def _codebook_k(text):
+    try:
+        k = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('--fit_codebook must be an integer in [1, 65536] (got %s)' % text)
+    if not 1 <= k <= 65536:
+        raise argparse.ArgumentTypeError('--fit_codebook must be in [1, 65536] (got %s)' % text)
+    return k
+
+
+def _codebook_iters(text):
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('--codebook_iters must be a positive integer (got %s)' % text)
+    if n < 1:
+        raise argparse.ArgumentTypeError('--codebook_iters must be >= 1 (got %s)' % text)
+    return n
+
+
 VALID_BATCHES = 8
+CODEBOOK_ITERS = 20
 
 
 def build_parser():
@@ -195,6 +226,18 @@ def build_parser():
     p.add_argument('--voice_dir', type=str, default=None, metavar='DIR', help='with --adapt_voice: where the voice file goes (default {ckpt_dir}/voices)')
     p.add_argument('--voice', action='append', default=None, metavar='NAME=FILE',
                    help='with --convert_dir / --synth_dir and --enc_only: register the voice file FILE as target speaker NAME (repeatable)')
+    p.add_argument('--fit_codebook', type=_codebook_k, default=None, metavar='K',
+                   help='fit a codebook of K codewords (k-modes in Hamming distance, on the GPU) to the units of --fit_dir and write '
+                        'it to --codebook_out')
+    p.add_argument('--fit_dir', type=str, default=None, metavar='DIR',
+                   help='with --fit_codebook: the folder of *.wav (encoded as --convert_dir reads them) and *.txt unit files')
+    p.add_argument('--codebook_out', type=str, default=None, metavar='FILE',
+                   help='with --fit_codebook: where the codebook goes (default {ckpt_dir}/codebooks/K<K>.codebook.npz)')
+    p.add_argument('--codebook_iters', type=_codebook_iters, default=None, metavar='N',
+                   help='with --fit_codebook: k-modes iterations at most (default %d)' % CODEBOOK_ITERS)
+    p.add_argument('--codebook_seed', type=int, default=None, metavar='S', help='with --fit_codebook: seed of the starting codewords (default 0)')
+    p.add_argument('--codebook', type=str, default=None, metavar='FILE',
+                   help='with --convert_dir / --synth_dir / --test_encode: snap every unit to its nearest codeword of this codebook')
     p.add_argument('--out_sr', type=_out_sr, default=None,
                    help='sample rate of the wavs --test / --cross_test / --test_single write (hp.out_sr); default: 16000')
     return p
@@ -233,7 +276,8 @@ def check_ema(args):
     if args.ema is not None and not training:
         raise ValueError('--ema needs a training mode (%s)' % ', '.join('--' + f for f in TRAIN_MODES))
     loads = any(getattr(args, f) for f in LOADING_MODES) or args.convert_dir is not None or args.synth_dir is not None or \
-        (training and args.load_model) or getattr(args, 'adapt_voice', None) is not None
+        (training and args.load_model) or getattr(args, 'adapt_voice', None) is not None or \
+        getattr(args, 'fit_codebook', None) is not None
     if args.use_ema and not loads:
         raise ValueError('--use_ema needs a mode that loads a checkpoint: %s, --convert_dir, or a training mode with --load_model'
                          % ', '.join('--' + f for f in LOADING_MODES))
@@ -302,6 +346,23 @@ def check_voice(args, speaker2id=None):
         raise ValueError("enc_mode 'continues' has no units to cache: voices need a discrete encoder mode")
 
 
+def check_codebook(parser, args):
+    """The codebook flags that cannot do what they say are argparse errors: --fit_codebook without --fit_dir (and the reverse), its
+    options without it, --fit_codebook beside a --train* mode, and --codebook without a mode that takes it."""
+    if args.fit_codebook is not None and args.fit_dir is None:
+        parser.error('--fit_codebook needs --fit_dir DIR, the folder whose units are clustered')
+    if args.fit_codebook is None:
+        for flag in ('fit_dir', 'codebook_out', 'codebook_iters', 'codebook_seed'):
+            if getattr(args, flag) is not None:
+                parser.error('--%s needs --fit_codebook' % flag)
+    elif any(getattr(args, f) for f in TRAIN_MODES):
+        parser.error('--fit_codebook fits a codebook to a finished checkpoint: it cannot be combined with a --train* mode')
+    if args.codebook is not None and not (args.convert_dir is not None or args.synth_dir is not None or args.test_encode):
+        parser.error('--codebook needs --convert_dir, --synth_dir or --test_encode')
+    if args.codebook is not None and args.fit_codebook is not None:
+        parser.error('--codebook uses a codebook and --fit_codebook writes one: run them as two commands')
+
+
 def convert_targets(args):
     """--convert_dir and --synth_dir take --t_speaker as a comma-separated list of distinct names (--test_single keeps the single name): the
     list, refused before anything is built when it names no speaker or one twice."""
@@ -317,6 +378,7 @@ def argument_runner(argv=None):
     from zs_amd.hps import Hps, hp
     parser = build_parser()
     args = parser.parse_args(argv)
+    check_codebook(parser, args)
     check_resume(args)
     check_ema(args)
     check_voice(args)
@@ -448,6 +510,15 @@ def main(argv=None):
                     iters=(args.adapt_iters if args.adapt_iters is not None else voice.ADAPT_ITERS), init=args.adapt_init,
                     lr=args.adapt_lr)
 
+    if args.fit_codebook is not None:                     # not in the reference: a unit codebook over a folder (zs_amd.codebook)
+        from zs_amd import codebook as zcb
+        model_path = args.ckpt_pth if args.ckpt_pth is not None else os.path.join(args.ckpt_dir, args.load_test_model_name)
+        trainer = get_trainer(args.hps_path, model_path, args.g_mode, args.enc_mode, use_ema=args.use_ema)
+        zcb.fit_dir(trainer, hps.seg_len, args.fit_dir, args.fit_codebook,
+                    args.codebook_out if args.codebook_out is not None else zcb.default_path(args.ckpt_dir, args.fit_codebook),
+                    iters=(args.codebook_iters if args.codebook_iters is not None else CODEBOOK_ITERS),
+                    seed=(args.codebook_seed if args.codebook_seed is not None else 0))
+
     if args.test or args.cross_test or args.test_encode or args.test_single or args.test_classify or args.convert_dir is not None or \
             args.synth_dir is not None:
         os.makedirs(args.result_dir, exist_ok=True)
@@ -455,6 +526,10 @@ def main(argv=None):
         trainer = get_trainer(args.hps_path, model_path, args.g_mode, args.enc_mode, args.load_tclf_model_name, use_ema=args.use_ema)
         result_dir = os.path.join(args.result_dir, args.sub_result_dir)
         os.makedirs(result_dir, exist_ok=True)
+        cb = None
+        if args.codebook is not None:                     # a malformed file or another width: ValueError before anything is enqueued
+            from zs_amd.codebook import Codebook
+            cb = Codebook.load(args.codebook, E=int(trainer.Decoder.c_in))
         voices = None
         if args.voice:                                    # --voice NAME=FILE: rows appended to the Decoder's tables (zs_amd.voice)
             from zs_amd.voice import add_voices
@@ -466,15 +541,15 @@ def main(argv=None):
         if args.test_single:                              # main.py:190-191
             test_single(trainer, hps.seg_len, args.speaker2id_path, args.result_dir, args.enc_only, args.s_speaker, args.t_speaker)
         if args.test_encode:
-            test_encode(trainer, hps.seg_len, args.test_path, args.dataset_path, result_dir, flag='test')
+            test_encode(trainer, hps.seg_len, args.test_path, args.dataset_path, result_dir, flag='test', codebook=cb)
         if args.test_classify:                            # main.py:196-199
             target_classify(trainer, hps.seg_len, args.synthesis_list, result_dir, flag='test')
         if args.convert_dir is not None:                  # not in the reference: a folder of sound files to the target voices
             convert_dir(trainer, hps.seg_len, args.convert_dir, args.speaker2id_path, os.path.join(result_dir, 'convert'), args.t_speakers,
-                        args.enc_only, voices=voices)
+                        args.enc_only, voices=voices, codebook=cb, codebook_file=args.codebook)
         if args.synth_dir is not None:                    # not in the reference: a folder of unit files spoken by the target voices
             synth_dir(trainer, hps.seg_len, args.synth_dir, args.speaker2id_path, os.path.join(result_dir, 'synth'), args.t_speakers,
-                      args.enc_only, voices=voices)
+                      args.enc_only, voices=voices, codebook=cb, codebook_file=args.codebook)
 
 
 if __name__ == '__main__':

@@ -1,0 +1,345 @@
+"""Unit codebook: K codewords of E bits fitted by k-modes over bit-packed units (convert.pack_units' rows), and the snap of every
+unit to its nearest codeword in Hamming distance.  One trained model then serves any point of the bitrate / quality
+trade-off: unit files become sequences over at most K symbols, and a snapped unit is still a line of 0 / 1.
+
+The work is three HIP entry points (csrc/zs_codebook.hip): zs_code_assign (nearest codeword, the hot call), zs_code_accum and
+zs_code_update (the votes and the majority rule of one k-modes iteration).  Everything is integer: a fit is bitwise reproducible and
+equals tests/codebook_ref.py, the numpy definition, codeword for codeword.  Not in the reference, which changes the size of the
+symbol inventory only by retraining with another enc_size."""
+import json
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+FORMAT_VERSION = 1
+MAX_K = L.ENUMS['ZS_CODE_MAX_K']
+MAX_E = L.ENUMS['ZS_CODE_MAX_E']
+
+
+def row_bytes(E):
+    return (int(E) + 7) // 8
+
+
+def assign_tile(E):
+    """Codewords zs_code_assign stages in LDS per pass at width E (a K above it crosses a tile boundary)."""
+    words, w = (int(E) + 31) // 32, 1
+    while w < words:
+        w *= 2
+    return L.ENUMS['ZS_CODE_TILE_WORDS'] // w
+
+
+def refuse_continues(enc_mode):
+    if enc_mode == 'continues':
+        raise ValueError("enc_mode 'continues' has no units to pack (its encodings are not 0 / 1): there is nothing a codebook could snap")
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _check_rows(t, E, what):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 2 or t.shape[1] < row_bytes(E) or not t.is_contiguous():
+        raise ValueError('%s must be a contiguous uint8 device tensor [n, >= %d] for E = %d' % (what, row_bytes(E), E))
+
+
+def assign(units, code, E, idx=None, dist=None, snapped=None, total=None):
+    """zs_code_assign on the current stream.  units uint8 [n, row_bytes], code uint8 [K, code_bytes] (device); every output optional:
+    idx / dist int32 [n], snapped uint8 like units (may be units itself), total int64 [1] (added to)."""
+    _check_rows(units, E, 'units')
+    _check_rows(code, E, 'code')
+    if snapped is not None and (snapped.shape != units.shape or snapped.dtype != torch.uint8 or not snapped.is_contiguous()):
+        raise ValueError('snapped must have the shape and pitch of units')
+    L.call('zs_code_assign', 'ZsCodeAssign', _stream(units.device), units=L.ptr(units), n=units.shape[0], row_bytes=units.shape[1],
+           code=L.ptr(code), K=code.shape[0], code_bytes=code.shape[1], E=int(E), idx=L.ptr(idx), dist=L.ptr(dist), snapped=L.ptr(snapped),
+           total=L.ptr(total))
+
+
+def usage(idx, K=None):
+    """(symbols used, entropy of the index histogram in bits per unit), on the host in double from a bincount."""
+    i = np.asarray(idx.cpu() if torch.is_tensor(idx) else idx).reshape(-1).astype(np.int64)
+    if i.size == 0:
+        return 0, 0.0
+    if (i < 0).any() or (K is not None and (i >= K).any()):
+        raise ValueError('usage: an index outside [0, K)')
+    return usage_counts(np.bincount(i, minlength=(K or 0)))
+
+
+def usage_counts(counts):
+    """usage() from the histogram itself (counts[k] = units of codeword k)."""
+    c = np.asarray(counts, dtype=np.float64).reshape(-1)
+    if (c < 0).any():
+        raise ValueError('usage_counts: a negative count')
+    if c.sum() == 0:
+        return 0, 0.0
+    p = c[c > 0] / c.sum()
+    return int(len(p)), float(max(0.0, -(p * np.log2(p)).sum()))
+
+
+class Codebook(object):
+    """K codewords of E bits: `packed` uint8 [K, (E + 7) // 8] on the host (bits at columns >= E zero), and `meta`: enc_mode, n_units,
+    seed and the per-iteration history [(total distance, changed, empties)] of the fit."""
+
+    def __init__(self, packed, E, meta=None):
+        E = int(E)
+        if not 1 <= E <= MAX_E:
+            raise ValueError('codebook: E must be in [1, %d] (got %d)' % (MAX_E, E))
+        p = np.asarray(packed)
+        if p.dtype != np.uint8 or p.ndim != 2 or p.shape[1] != row_bytes(E):
+            raise ValueError('codebook: packed must be uint8 [K, %d] for E = %d (got %s %s)' % (row_bytes(E), E, p.dtype, p.shape))
+        if not 1 <= p.shape[0] <= MAX_K:
+            raise ValueError('codebook: K must be in [1, %d] (got %d)' % (MAX_K, p.shape[0]))
+        if E % 8 and (p[:, -1] >> (E % 8)).any():
+            raise ValueError('codebook: packed has a bit set above column %d' % E)
+        self.K, self.E, self.packed, self.meta = int(p.shape[0]), E, np.ascontiguousarray(p), dict(meta or {})
+        self._dev = {}
+
+    def save(self, path):
+        with open(path, 'wb') as f:
+            np.savez(f, format_version=np.int64(FORMAT_VERSION), K=np.int64(self.K), E=np.int64(self.E), packed=self.packed,
+                     meta=np.array(json.dumps(self.meta)))
+
+    @classmethod
+    def load(cls, path, E=None):
+        """ValueError naming the field for a malformed file, and for a width other than E (the Decoder's c_in) when E is given."""
+        try:
+            z = np.load(path, allow_pickle=False)
+            d = {k: z[k] for k in z.files}
+        except Exception as e:
+            raise ValueError('%s is not a codebook file: %s' % (path, e))
+        for k in ('format_version', 'K', 'E', 'packed', 'meta'):
+            if k not in d:
+                raise ValueError('%s: codebook field %r is missing' % (path, k))
+        for k in ('format_version', 'K', 'E'):
+            if d[k].shape != () or d[k].dtype.kind not in 'iu':
+                raise ValueError('%s: codebook field %r must be one integer' % (path, k))
+        if int(d['format_version']) != FORMAT_VERSION:
+            raise ValueError('%s: codebook field format_version is %d, this build reads %d' % (path, int(d['format_version']), FORMAT_VERSION))
+        try:
+            meta = json.loads(str(d['meta']))
+            if not isinstance(meta, dict):
+                raise ValueError('not an object')
+        except ValueError as e:
+            raise ValueError('%s: codebook field meta is not a json object (%s)' % (path, e))
+        try:
+            cb = cls(d['packed'], int(d['E']), meta)
+        except ValueError as e:
+            raise ValueError('%s: codebook field packed / E: %s' % (path, e))
+        if cb.K != int(d['K']):
+            raise ValueError('%s: codebook field K is %d but packed has %d rows' % (path, int(d['K']), cb.K))
+        if E is not None:
+            cb.check_width(E, path)
+        return cb
+
+    def check_width(self, E, where='codebook'):
+        if int(E) != self.E:
+            raise ValueError("%s: codebook field E is %d, the Decoder's input width (c_in) is %d" % (where, self.E, int(E)))
+
+    def to(self, dev):
+        dev = torch.device(dev)
+        t = self._dev.get(dev)
+        if t is None:
+            t = self._dev[dev] = torch.from_numpy(self.packed).to(dev)
+        return t
+
+    def snap_(self, units_dev, idx=None, dist=None, total=None):
+        """Every row of units_dev replaced by its codeword, in place (one zs_code_assign on the current stream, no synchronisation)."""
+        assign(units_dev, self.to(units_dev.device), self.E, idx=idx, dist=dist, snapped=units_dev, total=total)
+
+    def snap(self, units_dev):
+        """(idx int32 [n], snapped uint8 like units_dev), both on the device."""
+        _check_rows(units_dev, self.E, 'units')
+        idx = torch.empty(units_dev.shape[0], dtype=torch.int32, device=units_dev.device)
+        snapped = units_dev.clone()                                # the bytes of a pitch behind the columns come along
+        assign(units_dev, self.to(units_dev.device), self.E, idx=idx, snapped=snapped)
+        return idx, snapped
+
+    def snap_host(self, packed):
+        """Host rows uint8 [n, (E + 7) // 8] -> (idx int32 [n], snapped) as numpy arrays (one round trip through the device)."""
+        idx, s = self.snap(torch.from_numpy(np.ascontiguousarray(packed)).cuda())
+        return idx.cpu().numpy(), s.cpu().numpy()
+
+
+def _mask_rows(rows, E):
+    """The columns < E of packed rows: [n, (E + 7) // 8], the bits above E zero (a numpy array or a tensor)."""
+    rows = rows[:, :row_bytes(E)]
+    rows = rows.clone() if torch.is_tensor(rows) else np.array(rows, dtype=np.uint8)
+    if E % 8:
+        rows[:, -1] &= (1 << (E % 8)) - 1
+    return rows
+
+
+def init_rows(packed, K, seed, E=None):
+    """The indices of the K starting codewords: numpy.random.RandomState(seed).permutation(n) walked in order, the first K indices
+    whose rows are pairwise different (over the columns < E; E defaults to every bit of a row).  ValueError saying how many distinct
+    rows there are when they are fewer than K.  packed: host array or device tensor [n, row_bytes]; of a device tensor only the
+    rows looked at come to the host."""
+    n = int(packed.shape[0])
+    E = 8 * int(packed.shape[1]) if E is None else int(E)
+    K = int(K)
+    perm = np.random.RandomState(seed).permutation(n)
+    seen, out, at, step = set(), [], 0, max(4096, 4 * K)
+    while at < n:
+        sel = perm[at:at + step]
+        if torch.is_tensor(packed):
+            rows = _mask_rows(packed[torch.from_numpy(sel).to(packed.device)], E).cpu().numpy()
+        else:
+            rows = _mask_rows(np.asarray(packed)[sel], E)
+        for i, r in zip(sel, rows):
+            key = r.tobytes()
+            if key not in seen:
+                seen.add(key)
+                out.append(int(i))
+                if len(out) == K:
+                    return np.asarray(out, dtype=np.int64)
+        at += step
+        step *= 4
+    raise ValueError('init_rows: the units hold %d distinct rows, fewer than K = %d' % (len(seen), K))
+
+
+def fit(units_dev, K, iters=20, seed=0, E=None, enc_mode='multilabel_binary', on_iter=None):
+    """k-modes over units_dev (uint8 [n, row_bytes] on the device, left unchanged) -> Codebook.  Per iteration zs_code_assign,
+    zs_code_accum, zs_code_update and ONE small D2H copy of (total, changed, bad, cnt) -- a synchronisation; fitting is not a captured
+    path.  Empty clusters, in increasing k, take the units of largest distance (ties to the lowest unit index, each unit once),
+    decided on the host from one D2H of dist in the iterations that have empties.  `changed` counts the codewords that differ from
+    the iteration's start, reseeds included; the fit stops at changed == 0 or after `iters`.  The total distance never rises from
+    one iteration to the next (assignment minimises per unit, the vote per bit, a tie keeps the bit, a reseed zeroes one unit's
+    distance): RuntimeError if it does.  on_iter(i, packed codebook on the host) is called after every iteration."""
+    refuse_continues(enc_mode)
+    K, iters = int(K), int(iters)
+    if not 1 <= K <= MAX_K:
+        raise ValueError('fit: K must be in [1, %d] (got %d)' % (MAX_K, K))
+    if iters < 1:
+        raise ValueError('fit: iters must be >= 1 (got %d)' % iters)
+    E = 8 * int(units_dev.shape[1]) if E is None else int(E)
+    if not 1 <= E <= MAX_E:
+        raise ValueError('fit: E must be in [1, %d] (got %d)' % (MAX_E, E))
+    _check_rows(units_dev, E, 'units')
+    n, dev, nb = int(units_dev.shape[0]), units_dev.device, row_bytes(E)
+    if n >= 2 ** 31:
+        raise ValueError('fit: %d units, the counters are int32' % n)
+    first = init_rows(units_dev, K, seed, E)
+    code = _mask_rows(units_dev[torch.from_numpy(first).to(dev)], E).contiguous()
+    st = _stream(dev)
+    stats = torch.empty(4 + K, dtype=torch.int32, device=dev)     # total (int64) | changed | bad | cnt [K]: one copy per iteration
+    ones = torch.empty(K, E, dtype=torch.int32, device=dev)
+    idx = torch.empty(n, dtype=torch.int32, device=dev)
+    dist = torch.empty(n, dtype=torch.int32, device=dev)
+    history = []
+    for it in range(iters):
+        stats.zero_()
+        ones.zero_()
+        start = code.clone()
+        assign(units_dev, code, E, idx=idx, dist=dist, total=stats[0:2])
+        L.call('zs_code_accum', 'ZsCodeAccum', st, units=L.ptr(units_dev), idx=L.ptr(idx), n=n, row_bytes=units_dev.shape[1], K=K, E=E,
+               cnt=L.ptr(stats, 4), ones=L.ptr(ones), bad=L.ptr(stats, 3))
+        L.call('zs_code_update', 'ZsCodeUpdate', st, code=L.ptr(code), K=K, code_bytes=nb, E=E, cnt=L.ptr(stats, 4), ones=L.ptr(ones),
+               changed=L.ptr(stats, 2))
+        h = stats.cpu().numpy()                                   # the synchronisation of this iteration
+        total, changed, bad, cnt = int(h[0:2].view(np.int64)[0]), int(h[2]), int(h[3]), h[4:]
+        if bad:
+            raise RuntimeError('fit: zs_code_assign gave %d indices outside [0, %d)' % (bad, K))
+        empties = np.flatnonzero(cnt == 0)
+        if len(empties):
+            order = np.argsort(-dist.cpu().numpy().astype(np.int64), kind='stable')[:len(empties)]
+            code[torch.from_numpy(empties).to(dev)] = _mask_rows(units_dev[torch.from_numpy(order).to(dev)], E)
+            changed = int((code != start).any(dim=1).sum().item())
+        if history and total > history[-1][0]:
+            raise RuntimeError('fit: the total distance rose from %d to %d in iteration %d' % (history[-1][0], total, it))
+        history.append((total, changed, int(len(empties))))
+        if on_iter is not None:
+            on_iter(it, code.cpu().numpy())
+        if changed == 0:
+            break
+    return Codebook(code.cpu().numpy(), E, {'enc_mode': enc_mode, 'n_units': n, 'seed': int(seed), 'history': [list(x) for x in history]})
+
+
+def default_path(ckpt_dir, K):
+    """{ckpt_dir}/codebooks/K<K>.codebook.npz"""
+    import os
+    return os.path.join(ckpt_dir, 'codebooks', 'K%d.codebook.npz' % int(K))
+
+
+def fit_dir(trainer, seg_len, in_dir, K, out_path, iters=20, seed=0, batch=64):
+    """--fit_codebook: a codebook of K codewords over the units of a folder.  The *.wav of in_dir are read and encoded as convert_dir
+    reads them (any rate, the same trimming, the same skip list), in the groups of convert_dir_plan, through
+    encode_batch(packed=True) with the packed units left on the device; the *.txt unit files of in_dir (read_units) are added.
+    Writes the codebook to out_path and fit_codebook.json beside it (files used and skipped, n_units, the history, symbols used and
+    the entropy of the final assignment); returns (Codebook, that report)."""
+    import glob
+    import os
+    from . import convert as cv
+    from .preprocess import read_wav, wav_info
+    refuse_continues(trainer.enc_mode)
+    K = int(K)
+    if not 1 <= K <= MAX_K:
+        raise ValueError('--fit_codebook: K must be in [1, %d] (got %d)' % (MAX_K, K))
+    E, dev = int(trainer.Decoder.c_in), trainer.device
+    used, skipped, parts = [], [], []
+
+    def skip(path, reason):
+        print('[Codebook] - skipped %s: %s' % (path, reason))
+        skipped.append({'input': path, 'reason': reason})
+
+    files, durations = [], []
+    for path in sorted(glob.glob(os.path.join(in_dir, '*.wav'))):
+        try:
+            sr, n = wav_info(path)
+            if sr <= 0:
+                raise ValueError('sample rate %d' % sr)
+        except (OSError, ValueError) as e:
+            skip(path, 'cannot be read: %s' % e)
+            continue
+        files.append(path)
+        durations.append(n / float(sr))
+    plan = cv.convert_dir_plan(files, durations, ['-'], in_dir, batch=batch) if files else {'groups': [], 'skipped': []}
+    for s in plan['skipped']:
+        skip(s['file'], s['reason'])
+    for group in plan['groups']:
+        wavs, rates, paths = [], [], []
+        for it in group:
+            try:
+                w, r = read_wav(it['file'])
+            except Exception as e:
+                skip(it['file'], 'cannot be read: %s' % e)
+                continue
+            wavs.append(w)
+            rates.append(r)
+            paths.append(it['file'])
+        if not wavs:
+            continue
+        specs, _ = cv._wav_features(wavs, rates, dev, strict=False)
+        for p, s in zip(paths, specs):
+            if s is None:
+                skip(p, 'utterance too short after trimming')
+        live = [(p, s) for p, s in zip(paths, specs) if s is not None]
+        if live:
+            units, _ = cv.encode_batch([s for _, s in live], trainer, seg_len, packed=True, units_on_device=True)
+            parts += units
+            used += [{'input': p, 'units': int(u.shape[0])} for (p, _), u in zip(live, units)]
+    for path in sorted(glob.glob(os.path.join(in_dir, '*.txt'))):
+        if path.endswith('.idx.txt'):
+            continue
+        try:
+            u = cv.pack_units(cv.read_units(path, E))
+        except (OSError, ValueError) as e:
+            skip(path, 'cannot be read: %s' % e)
+            continue
+        parts.append(torch.from_numpy(u).to(dev))
+        used.append({'input': path, 'units': int(u.shape[0])})
+    if not parts:
+        raise ValueError('--fit_codebook: %s holds no usable *.wav or *.txt unit file' % in_dir)
+    units_dev = torch.cat(parts, dim=0).contiguous()
+    cb = fit(units_dev, K, iters=iters, seed=seed, E=E, enc_mode=trainer.enc_mode)
+    idx, _ = cb.snap(units_dev)
+    n_used, entropy = usage(idx, K)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    cb.save(out_path)
+    report = {'codebook': out_path, 'K': K, 'E': E, 'in_dir': in_dir, 'files': used, 'skipped': skipped, 'n_units': int(units_dev.shape[0]),
+              'seed': int(seed), 'history': cb.meta['history'], 'symbols_used': n_used, 'entropy_bits_per_unit': entropy}
+    with open(os.path.join(os.path.dirname(os.path.abspath(out_path)), 'fit_codebook.json'), 'w') as f:
+        json.dump(report, f, indent=1)
+    print('[Codebook] - K = %d over %d units of %d files: %d iterations, total distance %d, %d symbols used, %.3f bits per unit -> %s' %
+          (K, units_dev.shape[0], len(used), len(cb.meta['history']), cb.meta['history'][-1][0], n_used, entropy, out_path))
+    return cb, report

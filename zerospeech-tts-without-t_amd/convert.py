@@ -436,7 +436,8 @@ def _t8(n):
 class _Enqueued(object):
     """What _enqueue_encode leaves behind: nothing here has been waited for.  With the generator (enc_only=False), `conv` holds
     the converted spectrograms [n_utt, T_max, 513] fp32 on the device (amplitudes when de-normalised) and `ulens` their frames."""
-    __slots__ = ('n_utt', 'chunks', 'enc_host', 'dec_dev', 'dec_host', 'enc_done', 'dev', 'conv', 'ulens', 'units_host', 'uoffs')
+    __slots__ = ('n_utt', 'chunks', 'enc_host', 'dec_dev', 'dec_host', 'enc_done', 'dev', 'conv', 'ulens', 'units_host', 'uoffs',
+                 'units_dev', 'unpack_E', 'idx_host', 'cb_total')
 
 
 GEN_COMBINE = {'naive': 1, 'targeted': 1, 'spectrogram': 1, 'targeted_residual': 2}     # zs_gen_scatter modes (trainer.py:206-213)
@@ -505,14 +506,46 @@ def _plan_pack(items, chunks, n_utt, dev):
     return uoffs, list(zip(st_d, ln_d))
 
 
-def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host, enc_only=True, denorm=False, pack=False):
+def _plan_dense(chunks, dev):
+    """The tables of the chunk-local packed buffers a codebook snaps for the Decoder: fragment i of a chunk whose longest member
+    encodes to Tp frames owns rows [i Tp, i Tp + _t8(n_i)) -- every encoded frame, without the MIN_LEN truncation of _plan_pack,
+    because the Decoder reads both units of an input shorter than MIN_LEN.  Per chunk (start int64, len int32) on the device."""
+    starts, lens, sizes = [], [], []
+    for chunk, _ in chunks:
+        Tp = _t8(max(b - a for (_, _, a, b, _) in chunk))
+        starts += [i * Tp for i in range(len(chunk))]
+        lens += [_t8(b - a) for (_, _, a, b, _) in chunk]
+        sizes.append(len(chunk))
+    st_d = torch.split(torch.from_numpy(np.array(starts, dtype=np.int64)).to(dev, non_blocking=True), sizes)
+    ln_d = torch.split(torch.from_numpy(np.array(lens, dtype=np.int32)).to(dev, non_blocking=True), sizes)
+    return list(zip(st_d, ln_d))
+
+
+def _check_codebook(codebook, trainer):
+    """A codebook is refused before anything is enqueued for enc_mode 'continues' and for a width other than the Decoder's c_in."""
+    from .codebook import refuse_continues
+    refuse_continues(trainer.enc_mode)
+    codebook.check_width(int(trainer.Decoder.c_in))
+
+
+def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host, enc_only=True, denorm=False, pack=False,
+                    codebook=None):
     """Fragment rule + every Encoder / Decoder launch of a batch of utterances, WITHOUT a host synchronisation: the caller decides
     what else to put on the stream (the vocoder) before it waits.
     enc_only=False (decode_speakers required): the stage-2 generator as well, and zs_gen_scatter writes every chunk's converted rows
     into q.conv right behind it (de-normalised when `denorm`): the engines reuse their output buffers for the next chunk of the
     same shape.
     pack: zs_units_pack writes every chunk's units, bit-packed, to their utterance's place in one device buffer, and ONE copy
-    brings them to the host (q.units_host, q.uoffs) instead of a fp32 copy per chunk."""
+    brings them to the host (q.units_host, q.uoffs) instead of a fp32 copy per chunk.
+    codebook (zs_amd.codebook.Codebook; implies pack): every unit is snapped to its nearest codeword.  A chunk's units go encoder ->
+    chunk-local packed rows -> zs_code_assign in place -> Decoder.forward_units, so the Decoder and the generator read the snapped
+    units of every encoded frame; the utterance buffer is snapped once, in place, behind the last chunk (the same rows, the same
+    codewords) with the index of every unit (q.idx_host) and the summed distance (q.cb_total)."""
+    if codebook is not None:
+        _check_codebook(codebook, trainer)
+        if int(trainer.Encoder.enc_size) != codebook.E:
+            raise ValueError("codebook field E is %d, the Encoder's enc_size is %d" % (codebook.E, int(trainer.Encoder.enc_size)))
+        pack = True
     if pack and trainer.enc_mode == 'continues':
         raise ValueError("enc_mode 'continues' has no units to pack (its encodings are not 0 / 1)")
     if not enc_only:
@@ -550,7 +583,7 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
     zero_row = int(offs[-1])
     q = _Enqueued()
     q.n_utt, q.dev, q.chunks, q.enc_host, q.dec_dev, q.dec_host = len(specs), dev, [], [], [], []
-    q.conv = q.ulens = q.units_host = q.uoffs = None
+    q.conv = q.ulens = q.units_host = q.uoffs = q.units_dev = q.unpack_E = q.idx_host = q.cb_total = None
     gen_plan = None
     if not enc_only:
         q.conv, q.ulens, dsts = _plan_scatter(items, chunks, len(specs), denorm, dev)
@@ -559,6 +592,7 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
         q.uoffs, pack_tabs = _plan_pack(items, chunks, len(specs), dev)
         row_bytes = (enc.enc_size + 7) // 8
         units_dev = torch.empty(int(q.uoffs[-1]), row_bytes, dtype=torch.uint8, device=dev)
+    dense_tabs = _plan_dense(chunks, dev) if (codebook is not None and decode_speakers is not None) else None
     for ci, (chunk, ragged) in enumerate(chunks):
         lens = [b - a for (_, _, a, b, _) in chunk]
         Tm = max(lens)
@@ -570,8 +604,20 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
         act, _ = enc(x.permute(0, 2, 1), G=G, lengths=(lens if ragged else None))
         xd = None
         if decode_speakers is not None:
+            rows_fn = lambda ch, lens_p: dec.forward_rows(act, ch, lengths=lens_p)
+            if codebook is not None:                          # the Decoder's operand from the chunk's own snapped rows
+                bits, Tp = enc._last_bits, int(act.shape[2])
+                if Tp != _t8(Tm):
+                    raise L.ZsError('conversion chunk %d: %d encoded frames where the plan has %d' % (ci, Tp, _t8(Tm)))
+                st_c, ln_c = dense_tabs[ci]
+                snapped = torch.empty(len(chunk) * Tp, row_bytes, dtype=torch.uint8, device=dev)
+                L.call('zs_units_pack', 'ZsUnitsPack', torch.cuda.current_stream(dev).cuda_stream, dtype=enc._zs['ctx'].dt, src_f32=0,
+                       src=bits.ptr(), ld_src=bits.ld, n_frag=len(chunk), T=bits.T, E=enc.enc_size, start=L.ptr(st_c), len=L.ptr(ln_c),
+                       packed=L.ptr(snapped), n_units=snapped.shape[0], row_bytes=row_bytes)
+                codebook.snap_(snapped)                       # rows behind a fragment's len are snapped too and never read
+                rows_fn = lambda ch, lens_p: dec.forward_units(snapped, st_c, ln_c, len(chunk), Tp, ch, lengths=lens_p)
             xd = _decode_chunk(trainer, ci, [it[0] for it in chunk], ([_t8(n) for n in lens] if ragged else None), decode_speakers,
-                               enc_only, gen_plan, lambda ch, lens_p: dec.forward_rows(act, ch, lengths=lens_p))
+                               enc_only, gen_plan, rows_fn)
         q.chunks.append((chunk, lens))
         if pack:                                              # the engine's own bits buffer, read in place
             bits = enc._last_bits
@@ -583,7 +629,13 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
             q.enc_host.append(_to_host(act.permute(0, 2, 1).contiguous()))
         q.dec_dev.append(xd)
         q.dec_host.append(_to_host(xd) if (xd is not None and dec_to_host) else None)
+    if codebook is not None:
+        idx_dev = torch.empty(units_dev.shape[0], dtype=torch.int32, device=dev)
+        total = torch.zeros(1, dtype=torch.int64, device=dev)
+        codebook.snap_(units_dev, idx=idx_dev, total=total)
+        q.idx_host, q.cb_total = _to_host(idx_dev), _to_host(total)
     if pack:
+        q.units_dev = units_dev
         q.units_host = _to_host(units_dev)
     q.enc_done = torch.cuda.Event()
     q.enc_done.record(torch.cuda.current_stream(dev))
@@ -650,14 +702,26 @@ def _assemble(q, want_dec):
     encs, decs = [], ([] if want_dec else None)
     for u in range(q.n_utt):
         ks = sorted(by_utt[u])
-        encs.append(np.concatenate([enc_out[(u, k)] for k in ks], axis=0) if units is None else units[q.uoffs[u]:q.uoffs[u + 1]].copy())
+        if units is None:
+            encs.append(np.concatenate([enc_out[(u, k)] for k in ks], axis=0))
+        elif q.unpack_E is not None:                          # packed on the way (a codebook), plain rows for the caller
+            encs.append(unpack_units(units[q.uoffs[u]:q.uoffs[u + 1]], q.unpack_E))
+        else:
+            encs.append(units[q.uoffs[u]:q.uoffs[u + 1]].copy())
         if decs is not None:
             parts = [dec_out[(u, k)] for k in ks]
             decs.append(np.concatenate(parts, axis=0) if want_dec == 'host' else (parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)))
     return encs, decs
 
 
-def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, max_batch=256, to_host=True, enc_only=True, packed=False):
+def _unit_indices(q):
+    """Per utterance the codeword index of every returned unit (int32 [U_i]) and the summed distance; the copies have been waited for."""
+    idx = q.idx_host.numpy()
+    return [idx[q.uoffs[u]:q.uoffs[u + 1]].copy() for u in range(q.n_utt)], int(q.cb_total.numpy()[0])
+
+
+def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, max_batch=256, to_host=True, enc_only=True, packed=False,
+                 codebook=None, want_idx=False, units_on_device=False):
     """Batched encode()/convert() for many utterances: the same fragments the reference would send through the network one by
     one (convert.py:151-165), as a few large batches on the GPU.
     specs: list of [T_i, 513] arrays (host arrays, or torch tensors already on the device).  decode_speakers: optional list of
@@ -670,22 +734,41 @@ def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, m
     (normalised, as test_step returns them), bit for bit the concatenated per-fragment test_step outputs given the same noise.
     packed=True: the encodings come back bit-packed, uint8 [U_i, (E + 7) // 8] as pack_units defines them -- zs_units_pack writes
     every fragment's units to its utterance's place in one device buffer and one D2H copy of E / 8 bytes per unit replaces the
-    per-chunk fp32 copies of 4 E bytes per unit (ValueError for enc_mode 'continues', whose encodings are not units)."""
+    per-chunk fp32 copies of 4 E bytes per unit (ValueError for enc_mode 'continues', whose encodings are not units).
+    units_on_device=True (with packed): the packed encodings are returned as device tensors, views of the one uint8 buffer.
+    codebook: a zs_amd.codebook.Codebook -- every unit is snapped to its nearest codeword before the Decoder and the generator see
+    it and before it is returned (under the same truncation rules, in the form `packed` asks for); want_idx=True appends the list
+    of codeword indices, int32 [U_i] per utterance, to the result."""
+    if want_idx and codebook is None:
+        raise ValueError('encode_batch: want_idx needs a codebook')
+    if units_on_device and not packed:
+        raise ValueError('encode_batch: units_on_device needs packed=True')
     q = _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host=to_host, enc_only=enc_only,
-                        pack=packed)
+                        pack=packed, codebook=codebook)
+    if codebook is not None and not packed:
+        q.unpack_E = codebook.E
+    out = _encode_result(q, decode_speakers, to_host, enc_only, units_on_device)
+    return out + (_unit_indices(q)[0],) if want_idx else out
+
+
+def _encode_result(q, decode_speakers, to_host, enc_only, units_on_device):
+    """encode_batch's wait and assembly: (encodings, decoded or converted spectrograms or None)."""
     conv_h = _to_host(q.conv) if (q.conv is not None and to_host) else None
     torch.cuda.current_stream(q.dev).synchronize()
     from . import layers
     layers.check_status(q.dev)                                # synchronised: a timed-out GRU pass raises here
+    if units_on_device:
+        encs_dev = [q.units_dev[q.uoffs[u]:q.uoffs[u + 1]] for u in range(q.n_utt)]
     if enc_only:
-        return _assemble(q, None if decode_speakers is None else ('host' if to_host else 'device'))
+        encs, decs = _assemble(q, None if decode_speakers is None else ('host' if to_host else 'device'))
+        return (encs_dev if units_on_device else encs), decs
     encs, _ = _assemble(q, None)
     conv = conv_h.numpy() if to_host else q.conv
-    return encs, [conv[u, :n] for u, n in enumerate(q.ulens)]
+    return (encs_dev if units_on_device else encs), [conv[u, :n] for u, n in enumerate(q.ulens)]
 
 
 def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, noise_fn=None, max_batch=256, defer=False, enc_only=True,
-                  momentum=None):
+                  momentum=None, codebook=None, want_idx=False):
     """test_encode + convert(enc_only) + spectrogram2wav for a batch of utterances as ONE enqueue (convert.py:151-165, 55-62):
     the fragments' Encoder / Decoder launches, the gather of the decoded fragments into the vocoder's padded [n, T_max, 513]
     input (one index kernel on the device), de-normalisation, the Griffin-Lim loop, de-emphasis, the trim statistics and the
@@ -696,14 +779,23 @@ def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, 
     batch run under the GPU work of the next.
     enc_only=False: convert() with the stage-2 generator; zs_gen_scatter writes each chunk's de-normalised converted rows straight
     into the vocoder's input, so the gather / combine / de-normalisation passes below do not exist on that path.
-    momentum: the vocoder's fast Griffin-Lim momentum (see griffin_lim_batch; None: hp.gl_momentum)."""
+    momentum: the vocoder's fast Griffin-Lim momentum (see griffin_lim_batch; None: hp.gl_momentum).
+    codebook: as encode_batch's -- the Decoder, the generator and the returned encodings see the snapped units; want_idx=True
+    makes the result (encodings, wavs, codeword indices int32 [U_i] per utterance, summed Hamming distance of the snap)."""
     momentum = gl_momentum(momentum)
+    if want_idx and codebook is None:
+        raise ValueError('resynth_batch: want_idx needs a codebook')
     if not enc_only:
-        q = _enqueue_encode(specs, trainer, seg_len, speakers, noise_fn, max_batch, dec_to_host=False, enc_only=False, denorm=True)
-        return _finish_resynth(q, _enqueue_vocoder(q.conv, q.ulens, n_iter, do_trim, q.dev, amplitudes=True, momentum=momentum), defer)
-    q = _enqueue_encode(specs, trainer, seg_len, speakers, noise_fn, max_batch, dec_to_host=False)
-    t, ulens = _gather_decoded(q, [[8 * _t8(n) for n in lens] for _, lens in q.chunks])
-    return _finish_resynth(q, _enqueue_vocoder(t, ulens, n_iter, do_trim, q.dev, momentum=momentum), defer)
+        q = _enqueue_encode(specs, trainer, seg_len, speakers, noise_fn, max_batch, dec_to_host=False, enc_only=False, denorm=True,
+                            codebook=codebook)
+        fin = _enqueue_vocoder(q.conv, q.ulens, n_iter, do_trim, q.dev, amplitudes=True, momentum=momentum)
+    else:
+        q = _enqueue_encode(specs, trainer, seg_len, speakers, noise_fn, max_batch, dec_to_host=False, codebook=codebook)
+        t, ulens = _gather_decoded(q, [[8 * _t8(n) for n in lens] for _, lens in q.chunks])
+        fin = _enqueue_vocoder(t, ulens, n_iter, do_trim, q.dev, momentum=momentum)
+    if codebook is not None:
+        q.unpack_E = codebook.E
+    return _finish_resynth(q, fin, defer, want_idx)
 
 
 def _gather_decoded(q, out_rows):
@@ -736,7 +828,7 @@ def _gather_decoded(q, out_rows):
     return table[torch.from_numpy(idx).to(dev, non_blocking=True)].float(), ulens                     # [n, Tm, 513]
 
 
-def _finish_resynth(q, fin, defer):
+def _finish_resynth(q, fin, defer, want_idx=False):
     def finish():
         q.enc_done.synchronize()                              # the encodings are on the host; the vocoder is still running
         encs, _ = _assemble(q, None)
@@ -744,7 +836,7 @@ def _finish_resynth(q, fin, defer):
         if fin.status:                                        # a persistent GRU pass timed out before this batch's end
             from . import layers
             layers.check_status(q.dev)                        # synchronises, clears the word and raises
-        return encs, wavs
+        return (encs, wavs) + _unit_indices(q) if want_idx else (encs, wavs)
     return finish if defer else finish()
 
 
@@ -776,7 +868,7 @@ def _check_units(units, E, packed):
 
 
 def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=None, do_trim=True, max_batch=256, defer=False,
-                      momentum=None, packed=False, want_specs=False):
+                      momentum=None, packed=False, want_specs=False, codebook=None, want_idx=False):
     """Speech from units: what resynth_batch does behind its encoder, from the units alone.  units: a list of [U_i, E] arrays of
     0 / 1 as encode_batch returns them (what read_units parses from a --test_encode file); packed=True: a list of uint8
     [U_i, (E + 7) // 8] arrays (pack_units, encode_batch(packed=True)).  speakers: the target id of each.
@@ -789,8 +881,13 @@ def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=N
     Where unit_fragments reproduces the fragmentation of the frames (see there) the result is resynth_batch's / convert()'s.
     Refused before anything is enqueued: enc_mode 'continues' (its files are not units), a width other than the Decoder's c_in, a
     value other than 0 / 1, fewer than 2 units (ValueError); a speaker the Decoder or the generator cannot take
-    (check_gen_targets)."""
+    (check_gen_targets).
+    codebook: a zs_amd.codebook.Codebook -- the one device buffer is snapped once, in place, before the first chunk, so every
+    fragment is decoded from snapped units; want_idx=True appends (codeword indices int32 [U_i] per utterance, summed Hamming
+    distance of the snap) to the result."""
     momentum = gl_momentum(momentum)
+    if want_idx and codebook is None:
+        raise ValueError('synth_units_batch: want_idx needs a codebook')
     if trainer.enc_mode == 'continues':
         raise ValueError("enc_mode 'continues' has no units: its encodings are real-valued and cannot be synthesised from unit files")
     if len(speakers) != len(units) or not len(units):
@@ -798,6 +895,8 @@ def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=N
     dec = trainer.Decoder
     E, row_bytes = int(dec.c_in), (int(dec.c_in) + 7) // 8
     rows = _check_units(units, E, packed)
+    if codebook is not None:
+        _check_codebook(codebook, trainer)
     bad = [int(c) for c in speakers if not 0 <= int(c) < int(dec.c_a)]
     if bad:
         raise ValueError('speaker id %d is outside [0, n_speakers = %d)' % (bad[0], dec.c_a))
@@ -820,6 +919,13 @@ def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=N
     host = torch.empty(int(uoffs[-1]), row_bytes, dtype=torch.uint8, pin_memory=True)
     np.concatenate(rows, axis=0, out=host.numpy())
     packed_dev = host.to(dev, non_blocking=True)
+    idx_h = total_h = None
+    if codebook is not None:
+        idx_dev = torch.empty(packed_dev.shape[0], dtype=torch.int32, device=dev)
+        total = torch.zeros(1, dtype=torch.int64, device=dev)
+        codebook.snap_(packed_dev, idx=idx_dev, total=total)
+        if want_idx:
+            idx_h, total_h = _to_host(idx_dev), _to_host(total)
     sizes = [len(chunk) for chunk, _ in chunks]
     starts = np.array([uoffs[u] + a for chunk, _ in chunks for (u, _, a, _, _) in chunk], dtype=np.int64)
     counts = np.array([b - a for chunk, _ in chunks for (_, _, a, b, _) in chunk], dtype=np.int32)
@@ -851,6 +957,8 @@ def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=N
             from . import layers
             layers.check_status(dev)                          # synchronises, clears the word and raises
         specs = [spec_h.numpy()[u, :n].copy() for u, n in enumerate(ulens)] if spec_h is not None else None
+        if want_idx:                                          # copied before the vocoder, which fin() has waited for
+            return specs, wavs, [idx_h.numpy()[uoffs[u]:uoffs[u + 1]].copy() for u in range(len(rows))], int(total_h.numpy()[0])
         return specs, wavs
     return finish if defer else finish()
 
@@ -994,7 +1102,7 @@ def _wav_features(wavs, rates, dev, do_trim=True, strict=True):
 
 
 def convert_wavs(wavs, rates, trainer, seg_len, speakers, enc_only=True, n_iter=None, momentum=None, noise_fn=None, do_trim=True,
-                 defer=False):
+                 defer=False, codebook=None):
     """Waveforms in, converted waveforms out, as one enqueue: wavs is a list of 1-D float arrays at `rates` (None: hp.sr; one int,
     or one per wav), speakers the target id of each.  Inputs not at hp.sr are resampled on the device, zs_trim finds the trim
     bounds there, zs_pre_spectrogram reads the trimmed windows in place and resynth_batch runs on the device-resident
@@ -1002,16 +1110,18 @@ def convert_wavs(wavs, rates, trainer, seg_len, speakers, enc_only=True, n_iter=
     are those of preprocess.get_spectrograms_batch(wavs, sr=rates) followed by resynth_batch(specs, ...), bit for bit.
     Returns (encodings, wavs, info); info[i] = {'bounds': (start, stop) of the input's trim at hp.sr, 'frames'}.  do_trim is
     get_spectrograms' trim of the input and the vocoder's trim of the output together; defer, enc_only, n_iter, momentum and
-    noise_fn are resynth_batch's.  An input of fewer than 2 samples after trimming raises ValueError before the network is
-    enqueued."""
+    noise_fn and codebook are resynth_batch's.  An input of fewer than 2 samples after trimming raises ValueError before the network
+    is enqueued."""
     momentum = gl_momentum(momentum)
     if len(speakers) != len(wavs):
         raise ValueError('convert_wavs: %d target speakers for %d wavs' % (len(speakers), len(wavs)))
+    if codebook is not None:
+        _check_codebook(codebook, trainer)
     if not enc_only:
         check_gen_targets(trainer, speakers)
     specs, info = _wav_features(wavs, rates, trainer.device, do_trim=do_trim)
     fin = resynth_batch(specs, trainer, seg_len, speakers, n_iter=n_iter, do_trim=do_trim, noise_fn=noise_fn, defer=True, enc_only=enc_only,
-                        momentum=momentum)
+                        momentum=momentum, codebook=codebook)
 
     def finish():
         encs, out = fin()
@@ -1062,6 +1172,37 @@ def convert_dir_plan(files, durations, targets, out_dir, batch=64, max_batch_sec
     return {'groups': groups, 'skipped': skipped}
 
 
+def write_indices(path, idx):
+    """The sibling of a unit file under a codebook: one codeword index per line, one line per unit."""
+    with open(path, 'w') as f:
+        for i in idx:
+            f.write('%d\n' % int(i))
+
+
+def idx_path(txt):
+    """<name>.txt -> <name>.idx.txt"""
+    return os.path.splitext(txt)[0] + '.idx.txt'
+
+
+class _CodebookStats(object):
+    """What a folder driver reports about a codebook run: the histogram of the indices written and the summed distance."""
+
+    def __init__(self, codebook, file):
+        self.cb, self.file, self.hist, self.total = codebook, file, np.zeros(codebook.K, dtype=np.int64), 0
+
+    def add(self, idxs, total):
+        for i in idxs:
+            self.hist += np.bincount(i, minlength=self.cb.K)
+        self.total += int(total)
+
+    def manifest(self):
+        from .codebook import usage_counts
+        n = int(self.hist.sum())
+        used, ent = usage_counts(self.hist)
+        return {'file': self.file, 'K': self.cb.K, 'symbols_used': used, 'entropy_bits_per_unit': ent,
+                'mean_distance': (self.total / float(n)) if n else 0.0}
+
+
 def _target_table(who, trainer, speaker2id, voices, t_speakers, enc_only, speaker2id_path):
     """The name -> Decoder row table of a folder driver: speaker2id, then the registered voices (zs_amd.voice.add_voices: {name:
     row}; a name in both keeps its speaker2id row).  ValueError for a target in neither, and for voices with the generator."""
@@ -1084,7 +1225,7 @@ def _target_table(who, trainer, speaker2id, voices, t_speakers, enc_only, speake
 
 
 def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None,
-                voices=None):
+                voices=None, codebook=None, codebook_file=None):
     """Every *.wav of in_dir (any PCM / float format, any rate, channels averaged: preprocess.read_wav) to every target speaker of
     t_speakers, on the device from the samples to the waveform: {out_dir}/{target}/{stem}.wav (PCM16 at out_rate()) and .txt (the
     units), plus the manifest {out_dir}/convert_dir.json, which is returned.
@@ -1094,10 +1235,17 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
     The targets are checked before anything is read or enqueued.  A file that cannot be read, or is too short after trimming, is
     skipped with a printed reason and listed in the manifest; the run goes on.
     voices: {name: Decoder row} of voices registered with zs_amd.voice.add_voices (enc_only alone): t_speakers may name them, and
-    the manifest then lists them under 'voices'."""
+    the manifest then lists them under 'voices'.
+    codebook: a zs_amd.codebook.Codebook (codebook_file: where it came from) -- the units are snapped as resynth_batch snaps them,
+    every .txt gets a sibling .idx.txt (one codeword index per line) and the manifest the entry 'codebook': {file, K, symbols_used,
+    entropy_bits_per_unit, mean_distance} over the units written."""
     from concurrent.futures import ThreadPoolExecutor
     from .preprocess import read_wav, wav_info
     momentum = gl_momentum(momentum)
+    stats = None
+    if codebook is not None:
+        _check_codebook(codebook, trainer)
+        stats = _CodebookStats(codebook, codebook_file)
     with open(speaker2id_path, 'r') as f_json:
         speaker2id = json.load(f_json)
     t_speakers = list(t_speakers)
@@ -1142,11 +1290,16 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
         return out
 
     def write(group, fin):
-        encs, wavs = fin()
-        for it, e, w in zip(group, encs, to_out_sr(wavs)):
+        res = fin()
+        encs, wavs = res[0], res[1]
+        if stats is not None:
+            stats.add(res[2], res[3])
+        for i, (it, e, w) in enumerate(zip(group, encs, to_out_sr(wavs))):
             os.makedirs(os.path.dirname(it['wav']), exist_ok=True)
             write_wav(it['wav'], w, out_rate())
             write_encodings(it['txt'], e)
+            if stats is not None:
+                write_indices(idx_path(it['txt']), res[2][i])
             done.append(it)
 
     pending = None
@@ -1176,7 +1329,8 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
             fin = None
             if live:
                 fin = resynth_batch([feats[it['file']][0] for it in live], trainer, seg_len, [speaker2id[it['target']] for it in live],
-                                    n_iter=n_iter, defer=True, enc_only=enc_only, momentum=momentum)
+                                    n_iter=n_iter, defer=True, enc_only=enc_only, momentum=momentum, codebook=codebook,
+                                    want_idx=codebook is not None)
             later = {it['file'] for g in groups[gi + 1:gi + 2] for it in g}
             for p in [p for p in feats if p not in later]:    # a file's items are adjacent: done with, drop its device rows
                 del feats[p]
@@ -1189,6 +1343,8 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
                 'items': [{'input': it['file'], 'rate': it['rate'], 'samples': it['samples'], 'target': it['target'],
                            'bounds': it['bounds'], 'frames': it['frames'], 'wav': it['wav'], 'txt': it['txt']} for it in done],
                 'skipped': skipped}
+    if stats is not None:
+        manifest['codebook'] = stats.manifest()
     if voices:
         manifest['voices'] = {t: int(voices[t]) for t in t_speakers if t in voices and speaker2id[t] == voices[t]}
     with open(os.path.join(out_dir, 'convert_dir.json'), 'w') as f:
@@ -1239,7 +1395,8 @@ def synth_dir_plan(files, n_units, targets, out_dir, batch=64, max_batch_units=6
     return {'groups': groups, 'skipped': skipped}
 
 
-def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None, voices=None):
+def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None, voices=None,
+              codebook=None, codebook_file=None):
     """Every *.txt of in_dir -- unit files as write_encodings writes them (--test_encode, --test, --convert_dir, encode_batch), one
     line of 0 / 1 per unit -- spoken in the voice of every target speaker of t_speakers: {out_dir}/{target}/{stem}.wav (PCM16 at
     out_rate()), plus the manifest {out_dir}/synth_dir.json, which is returned.
@@ -1247,7 +1404,9 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
     synth_units_batch in groups, and group i + 1 is enqueued before group i is written (defer=True).  The targets are checked
     before anything is read or enqueued.  A file that cannot be read as units of the Decoder's width, or holds fewer than 2
     units, is skipped with a printed reason and listed in the manifest; the run goes on.
-    voices: as convert_dir's."""
+    voices: as convert_dir's.
+    codebook: as convert_dir's -- the units of every file are snapped before they are spoken, and what was spoken is written beside
+    each wav: {stem}.txt (the snapped units) and {stem}.idx.txt (one codeword index per line); the manifest gains 'codebook'."""
     momentum = gl_momentum(momentum)
     with open(speaker2id_path, 'r') as f_json:
         speaker2id = json.load(f_json)
@@ -1258,6 +1417,10 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
     if not enc_only:
         check_gen_targets(trainer, [speaker2id[t] for t in t_speakers])
     E = int(trainer.Decoder.c_in)
+    stats = None
+    if codebook is not None:
+        _check_codebook(codebook, trainer)
+        stats = _CodebookStats(codebook, codebook_file)
     skipped, units = [], {}
 
     def skip(path, reason):
@@ -1280,16 +1443,24 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
     done = []
 
     def write(group, fin):
-        _, wavs = fin()
-        for it, w in zip(group, to_out_sr(wavs)):
+        res = fin()
+        wavs = res[1]
+        if stats is not None:
+            stats.add(res[2], res[3])
+        for i, (it, w) in enumerate(zip(group, to_out_sr(wavs))):
             os.makedirs(os.path.dirname(it['wav']), exist_ok=True)
             write_wav(it['wav'], w, out_rate())
+            if stats is not None:                             # what was spoken: the codewords of the file's units
+                txt = os.path.splitext(it['wav'])[0] + '.txt'
+                write_encodings(txt, unpack_units(codebook.packed[res[2][i]], E))
+                write_indices(idx_path(txt), res[2][i])
             done.append(it)
 
     pending = None
     for group in groups:
         fin = synth_units_batch([units[it['file']] for it in group], trainer, seg_len, [speaker2id[it['target']] for it in group],
-                                enc_only=enc_only, n_iter=n_iter, defer=True, momentum=momentum, packed=True)
+                                enc_only=enc_only, n_iter=n_iter, defer=True, momentum=momentum, packed=True, codebook=codebook,
+                                want_idx=codebook is not None)
         if pending is not None:
             write(*pending)
         pending = (group, fin)
@@ -1299,6 +1470,8 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
                 'items': [{'input': it['file'], 'units': it['units'], 'fragments': unit_fragments(it['units'], seg_len),
                            'target': it['target'], 'wav': it['wav']} for it in done],
                 'skipped': skipped}
+    if stats is not None:
+        manifest['codebook'] = stats.manifest()
     if voices:
         manifest['voices'] = {t: int(voices[t]) for t in t_speakers if t in voices and speaker2id[t] == voices[t]}
     with open(os.path.join(out_dir, 'synth_dir.json'), 'w') as f:
@@ -1336,8 +1509,11 @@ def test_single(trainer, seg_len, speaker2id_path, result_dir, enc_only, s_speak
     return wav_data, encodings
 
 
-def test_encode(trainer, seg_len, test_path, data_path, result_dir, flag='test'):
-    """convert.py:342-360."""
+def test_encode(trainer, seg_len, test_path, data_path, result_dir, flag='test', codebook=None):
+    """convert.py:342-360.  codebook (not in the reference): every file's units are snapped to their codewords before they are
+    written, and each .txt gets a sibling .idx.txt with one codeword index per line."""
+    if codebook is not None:
+        _check_codebook(codebook, trainer)
     files = sorted(glob.glob(os.path.join(test_path, '*.wav')))
     feeds = [{'s_id': f.split('/')[-1].split('_')[0], 'utt_id': f.split('/')[-1].split('_')[1].split('.')[0]} for f in files]
     print('[Tester] - Number of files to encoded: ', len(feeds))
@@ -1345,8 +1521,15 @@ def test_encode(trainer, seg_len, test_path, data_path, result_dir, flag='test')
     os.makedirs(dir_path, exist_ok=True)
     with _open_h5(data_path) as f_h5:
         for feed in feeds:
-            encode(f_h5[f"test/{feed['s_id']}/{feed['utt_id']}/lin"][()], trainer, seg_len, s_speaker=feed['s_id'],
-                   utt_id=feed['utt_id'], result_dir=dir_path)
+            if codebook is None:
+                encode(f_h5[f"test/{feed['s_id']}/{feed['utt_id']}/lin"][()], trainer, seg_len, s_speaker=feed['s_id'],
+                       utt_id=feed['utt_id'], result_dir=dir_path)
+                continue
+            units = encode(f_h5[f"test/{feed['s_id']}/{feed['utt_id']}/lin"][()], trainer, seg_len, save=False)
+            idx, snapped = codebook.snap_host(pack_units(units))
+            txt = os.path.join(dir_path, f"{feed['s_id']}_{feed['utt_id']}.txt")
+            write_encodings(txt, unpack_units(snapped, codebook.E))
+            write_indices(idx_path(txt), idx)
 
 
 # ---------------------------------------------------------------------------------------------------
