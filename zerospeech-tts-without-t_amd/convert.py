@@ -14,6 +14,7 @@ import ctypes
 import glob
 import json
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -150,7 +151,7 @@ def trim_bounds(mse, n, top_db=60, hop_length=TRIM_HOP):
 
 def _enqueue_vocoder(t, lens, n_iter, do_trim, dev, amplitudes=False, momentum=None):
     """t: normalised magnitudes [n, T_max, 513] fp32 on the device (amplitudes=True: already de-normalised, e.g. by
-    zs_gen_scatter).  Enqueues convert.py:55-62 and returns the function that waits for it and cuts the waveforms
+    zs_gen_scatter).  Enqueues convert.py:55-62 and returns the _VocoderWait that waits for it and cuts the waveforms
     (librosa.effects.trim restated on device-computed frame statistics)."""
     st = torch.cuda.current_stream(dev).cuda_stream
     if amplitudes:
@@ -173,23 +174,34 @@ def _enqueue_vocoder(t, lens, n_iter, do_trim, dev, amplitudes=False, momentum=N
     st_h = _to_host(layers.device_status(dev))                # the sticky GRU status word as of this batch (checked by the caller)
     done = torch.cuda.Event()
     done.record(torch.cuda.current_stream(dev))
+    return _VocoderWait(done, st_h, w_h, mse_h, lens, do_trim)
 
-    def finish():
-        done.synchronize()                                    # this batch's copies only: later batches may already be enqueued
-        finish.status = int(st_h[0])
-        w = w_h.numpy()
+
+class _VocoderWait(object):
+    """What _enqueue_vocoder returns: the call waits for the batch and cuts its waveforms; `status` is then the sticky GRU status
+    word as of the batch.  An object, not a closure that names itself to carry `status`: that closure is a reference cycle, and
+    the pinned buffers it holds (64 MB for 64 utterances) waited for the garbage collector instead of going back to the pool with
+    the result -- the next batches then paid for fresh pinned memory or not, by when a collection happened to run."""
+    __slots__ = ('done', 'st_h', 'w_h', 'mse_h', 'lens', 'do_trim', 'status')
+
+    def __init__(self, done, st_h, w_h, mse_h, lens, do_trim):
+        self.done, self.st_h, self.w_h, self.mse_h, self.lens, self.do_trim, self.status = done, st_h, w_h, mse_h, lens, do_trim, None
+
+    def __call__(self):
+        self.done.synchronize()                               # this batch's copies only: later batches may already be enqueued
+        self.status = int(self.st_h[0])
+        w = self.w_h.numpy()
         out = []
-        for i, T in enumerate(lens):
+        for i, T in enumerate(self.lens):
             y = w[i, :200 * (T - 1)]
-            if do_trim:
-                if mse_h is not None:
-                    a, b = trim_bounds(mse_h[i, :1 + len(y) // TRIM_HOP].numpy(), len(y))
+            if self.do_trim:
+                if self.mse_h is not None:
+                    a, b = trim_bounds(self.mse_h[i, :1 + len(y) // TRIM_HOP].numpy(), len(y))
                     y = y[a:b]
                 else:
                     y, _ = trim(y)
             out.append(np.asarray(y, dtype=np.float32))
         return out
-    return finish
 
 
 def spectrogram2wav_batch(mags_tf, n_iter=None, do_trim=True, momentum=None):
@@ -434,13 +446,158 @@ def _t8(n):
 
 
 class _Enqueued(object):
-    """What _enqueue_encode leaves behind: nothing here has been waited for.  With the generator (enc_only=False), `conv` holds
-    the converted spectrograms [n_utt, T_max, 513] fp32 on the device (amplitudes when de-normalised) and `ulens` their frames."""
+    """What _enqueue_encode and synth_units_batch leave behind: nothing here has been waited for, and a slot its producer has
+    nothing for is None.  With the generator (enc_only=False), `conv` holds the converted spectrograms [n_utt, T_max, 513] fp32 on
+    the device (amplitudes when de-normalised) and `ulens` their frames."""
     __slots__ = ('n_utt', 'chunks', 'enc_host', 'dec_dev', 'dec_host', 'enc_done', 'dev', 'conv', 'ulens', 'units_host', 'uoffs',
                  'units_dev', 'unpack_E', 'idx_host', 'cb_total')
 
+    def __init__(self):
+        for slot in self.__slots__:
+            setattr(self, slot, None)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the plans of a batch: host code alone (numpy in, numpy out; tests/test_convert_plan_host.py), uploaded by _upload_tables
+# ---------------------------------------------------------------------------------------------------
+
+class _Item(namedtuple('_Item', 'u k a b trunc')):
+    """One fragment: rows [a, b) of utterance u (frames for _enqueue_encode, units for synth_units_batch), the k-th of its
+    utterance; trunc: the units returned for an input that was padded to MIN_LEN, else None."""
+    __slots__ = ()
+
+    @property
+    def n(self):
+        return self.b - self.a
+
+
+def _frame_items(u, n_frames, seg_len, was_padded):
+    """The items of utterance u of n_frames >= MIN_LEN frames (after _pad_min): one when it is at most seg_len, else fragments()."""
+    if n_frames <= seg_len:
+        return [_Item(u, 0, 0, n_frames, (MIN_LEN // 8) if was_padded else None)]
+    return [_Item(u, k, a, b, None) for k, (a, b) in enumerate(fragments(n_frames, seg_len))]
+
+
+def _unit_items(u, n_units, seg_len):
+    """The items of utterance u of n_units units: the pieces of unit_fragments, back to back."""
+    ends = np.cumsum(unit_fragments(n_units, seg_len)).tolist()
+    return [_Item(u, k, a, b, None) for k, (a, b) in enumerate(zip([0] + ends[:-1], ends))]
+
+
+def _split_chunks(items, full_len, max_batch):
+    """Two kinds of batches instead of one per distinct length (the fragment rule leaves ~60 tail lengths per 64 utterances):
+    the fragments of exactly full_len as plain batches, everything else (tails of seg_len .. 2 seg_len - 2 frames, short
+    utterances) as RAGGED batches padded to their longest member, with per-sample lengths: the kernels pad / normalise / run the
+    reverse GRU at each sample's own end, so a fragment's result does not depend on what it is batched with.
+    Returns [(items, ragged)], ragged None for a plain chunk and True for a ragged one, each of at most max_batch items."""
+    full = [it for it in items if it.n == full_len]
+    rest = sorted((it for it in items if it.n != full_len), key=lambda it: -it.n)                       # longest first
+    chunks = [(full[lo:lo + max_batch], None) for lo in range(0, len(full), max_batch)]
+    return chunks + [(rest[lo:lo + max_batch], True) for lo in range(0, len(rest), max_batch)]
+
+
+def _flat(chunks):
+    return [it for chunk, _ in chunks for it in chunk]
+
+
+def _fragment_layout(items, counts, n_utt):
+    """THE layout of every per-utterance buffer: utterance u's rows are its fragments' rows in fragment order.  counts[i]: the rows
+    of items[i] (in any order).  Returns (the first row of each item within its utterance, the rows of each utterance)."""
+    at, totals = [0] * len(items), [0] * n_utt
+    for i in sorted(range(len(items)), key=lambda i: items[i][:2]):
+        at[i] = totals[items[i].u]
+        totals[items[i].u] += counts[i]
+    return at, totals
+
+
+def _pack_tables(chunks, n_utt):
+    """Where zs_units_pack puts every fragment's units: utterance u's units are its fragments' in fragment order, the utterances back
+    to back in one buffer.  Returns (row offsets of the utterances int64 [n_utt + 1], and over all fragments in chunk order: start
+    int64, len int32); len is the MIN_LEN truncation where an item carries one."""
+    flat = _flat(chunks)
+    lens = [it.trunc if it.trunc is not None else _t8(it.n) for it in flat]
+    at, counts = _fragment_layout(flat, lens, n_utt)
+    uoffs = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+    starts = np.array([uoffs[it.u] + s for it, s in zip(flat, at)], dtype=np.int64)
+    return uoffs, starts, np.array(lens, dtype=np.int32)
+
+
+def _dense_tables(chunks):
+    """The tables of the chunk-local packed buffers a codebook snaps for the Decoder: fragment i of a chunk whose longest member
+    encodes to Tp frames owns rows [i Tp, i Tp + _t8(n_i)) -- every encoded frame, without the MIN_LEN truncation of _pack_tables,
+    because the Decoder reads both units of an input shorter than MIN_LEN.  Over all fragments in chunk order (start int64, len int32)."""
+    starts, lens = [], []
+    for chunk, _ in chunks:
+        Tp = _t8(max(it.n for it in chunk))
+        starts += [i * Tp for i in range(len(chunk))]
+        lens += [_t8(it.n) for it in chunk]
+    return np.array(starts, dtype=np.int64), np.array(lens, dtype=np.int32)
+
+
+def _unit_tables(chunks, uoffs):
+    """Where zs_units_unpack finds every fragment in synth_units_batch's one packed buffer (utterance u's units from row uoffs[u]):
+    over all fragments in chunk order (start int64, len int32)."""
+    flat = _flat(chunks)
+    return np.array([uoffs[it.u] + it.a for it in flat], dtype=np.int64), np.array([it.n for it in flat], dtype=np.int32)
+
+
+def _scatter_tables(chunks, n_utt, rows_of=None):
+    """Per chunk, the destination row of each of its output rows in the converted spectrograms' buffer [n_utt, T_max, 513]
+    (b*T + t -> u*T_max + frame, -1 past a fragment's own rows): utterance u's frames are its fragments' rows in fragment order.
+    rows_of(n): the output rows of a fragment of n = b - a (default: n frames in, 8 * _t8(n) rows out).
+    Returns (T_max, frames per utterance, the chunk tables int32 flat, the padding rows int32: frames past an utterance's length)."""
+    rows_of = rows_of or (lambda n: 8 * _t8(n))
+    flat = _flat(chunks)
+    out_rows = [rows_of(it.n) for it in flat]
+    start, ulens = _fragment_layout(flat, out_rows, n_utt)
+    Tm = max(ulens)
+    tables, at = [], 0
+    for chunk, _ in chunks:
+        T = rows_of(max(it.n for it in chunk))
+        d = np.full((len(chunk), T), -1, dtype=np.int32)
+        for i, it in enumerate(chunk):
+            r0, n = it.u * Tm + start[at + i], out_rows[at + i]
+            d[i, :n] = np.arange(r0, r0 + n, dtype=np.int32)
+        at += len(chunk)
+        tables.append(d.reshape(-1))
+    pad = np.concatenate([np.arange(u * Tm + ulens[u], (u + 1) * Tm, dtype=np.int32) for u in range(n_utt)])
+    return Tm, ulens, tables, pad
+
+
+def _gather_index(chunks, out_rows, shapes, n_utt):
+    """The row index of the vocoder's padded input [n_utt, T_max] into the decoded chunks laid end to end with one zero row behind
+    them: utterance u's frames are its fragments' rows in fragment order, the zero row behind them.  out_rows[ci][i]: the valid
+    output rows of fragment i of chunk ci; shapes[ci]: (fragments, rows per fragment) of its decoded buffer.
+    Returns (index int64 [n_utt, T_max], frames per utterance, the zero row)."""
+    flat, first, total = _flat(chunks), [], 0
+    for (chunk, _), (n_frag, ld) in zip(chunks, shapes):
+        first += [total + i * ld for i in range(len(chunk))]
+        total += n_frag * ld
+    counts = [n for rows in out_rows for n in rows]
+    at, ulens = _fragment_layout(flat, counts, n_utt)
+    idx = np.full((n_utt, max(ulens)), total, dtype=np.int64)
+    for it, r0, n, s in zip(flat, first, counts, at):
+        idx[it.u, s:s + n] = np.arange(r0, r0 + n)
+    return idx, ulens, total
+
+
+def _upload_tables(starts, lens, chunks, dev):
+    """The (start int64, len int32) tables of a plan, over all fragments in chunk order, to the device in one copy each; returns
+    per chunk its views (start, len)."""
+    sizes = [len(chunk) for chunk, _ in chunks]
+    st_d = torch.split(torch.from_numpy(starts).to(dev, non_blocking=True), sizes)
+    ln_d = torch.split(torch.from_numpy(lens).to(dev, non_blocking=True), sizes)
+    return list(zip(st_d, ln_d))
+
 
 GEN_COMBINE = {'naive': 1, 'targeted': 1, 'spectrogram': 1, 'targeted_residual': 2}     # zs_gen_scatter modes (trainer.py:206-213)
+
+
+def _check_speaker_range(speakers, n_spk):
+    """An id outside a speaker embedding table would be read past on the GPU."""
+    bad = [int(s) for s in speakers if not 0 <= int(s) < n_spk]
+    if bad:
+        raise ValueError('speaker id %d is outside [0, n_speakers = %d)' % (bad[0], n_spk))
 
 
 def check_gen_targets(trainer, speakers):
@@ -450,9 +607,7 @@ def check_gen_targets(trainer, speakers):
     if trainer.g_mode not in GEN_COMBINE:
         raise NotImplementedError('g_mode %r has no batched conversion path' % trainer.g_mode)
     n_spk = int(trainer.hps.n_speakers)
-    bad = [int(s) for s in speakers if not 0 <= int(s) < n_spk]
-    if bad:
-        raise ValueError('speaker id %d is outside [0, n_speakers = %d)' % (bad[0], n_spk))
+    _check_speaker_range(speakers, n_spk)
     if trainer.g_mode == 'naive':
         return 0
     shift = n_spk - int(trainer.hps.n_target_speakers)
@@ -488,44 +643,29 @@ def _decode_chunk(trainer, ci, utts, lens_p, decode_speakers, enc_only, gen_plan
     return None
 
 
-def _plan_pack(items, chunks, n_utt, dev):
-    """Where zs_units_pack puts every fragment's units: utterance u's units are its fragments' in fragment order, the utterances back
-    to back in one buffer.  Returns (row offsets of the utterances [n_utt + 1], per chunk the device tables (start int64, len int32));
-    len is the MIN_LEN truncation where an item carries one.  All tables go to the device in one copy each."""
-    n_of = {(u, k): (trunc if trunc is not None else _t8(b - a)) for (u, k, a, b, trunc) in items}
-    at, counts = {}, [0] * n_utt
-    for (u, k) in sorted(n_of):
-        at[(u, k)] = counts[u]
-        counts[u] += n_of[(u, k)]
-    uoffs = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
-    starts = np.array([uoffs[u] + at[(u, k)] for chunk, _ in chunks for (u, k, _, _, _) in chunk], dtype=np.int64)
-    lens = np.array([n_of[(u, k)] for chunk, _ in chunks for (u, k, _, _, _) in chunk], dtype=np.int32)
-    sizes = [len(chunk) for chunk, _ in chunks]
-    st_d = torch.split(torch.from_numpy(starts).to(dev, non_blocking=True), sizes)
-    ln_d = torch.split(torch.from_numpy(lens).to(dev, non_blocking=True), sizes)
-    return uoffs, list(zip(st_d, ln_d))
-
-
-def _plan_dense(chunks, dev):
-    """The tables of the chunk-local packed buffers a codebook snaps for the Decoder: fragment i of a chunk whose longest member
-    encodes to Tp frames owns rows [i Tp, i Tp + _t8(n_i)) -- every encoded frame, without the MIN_LEN truncation of _plan_pack,
-    because the Decoder reads both units of an input shorter than MIN_LEN.  Per chunk (start int64, len int32) on the device."""
-    starts, lens, sizes = [], [], []
-    for chunk, _ in chunks:
-        Tp = _t8(max(b - a for (_, _, a, b, _) in chunk))
-        starts += [i * Tp for i in range(len(chunk))]
-        lens += [_t8(b - a) for (_, _, a, b, _) in chunk]
-        sizes.append(len(chunk))
-    st_d = torch.split(torch.from_numpy(np.array(starts, dtype=np.int64)).to(dev, non_blocking=True), sizes)
-    ln_d = torch.split(torch.from_numpy(np.array(lens, dtype=np.int32)).to(dev, non_blocking=True), sizes)
-    return list(zip(st_d, ln_d))
-
-
 def _check_codebook(codebook, trainer):
     """A codebook is refused before anything is enqueued for enc_mode 'continues' and for a width other than the Decoder's c_in."""
     from .codebook import refuse_continues
     refuse_continues(trainer.enc_mode)
     codebook.check_width(int(trainer.Decoder.c_in))
+
+
+def _launch_units_pack(enc, n_frag, tabs, packed, dev):
+    """zs_units_pack of the Encoder's last chunk -- the engine's own bits buffer, read in place -- into the rows tabs = (start, len)
+    give each of its n_frag fragments in `packed` (uint8 [n_units, row_bytes])."""
+    bits = enc._last_bits
+    L.call('zs_units_pack', 'ZsUnitsPack', torch.cuda.current_stream(dev).cuda_stream, dtype=enc._zs['ctx'].dt, src_f32=0,
+           src=bits.ptr(), ld_src=bits.ld, n_frag=n_frag, T=bits.T, E=enc.enc_size, start=L.ptr(tabs[0]), len=L.ptr(tabs[1]),
+           packed=L.ptr(packed), n_units=packed.shape[0], row_bytes=packed.shape[1])
+
+
+def _snap_units(codebook, packed, dev, to_host):
+    """Snaps the packed units of a whole batch in place, once.  Returns the pinned host copies (codeword index of every unit int32,
+    summed distance int64 [1]) when to_host, else (None, None); nothing is waited for."""
+    idx_dev = torch.empty(packed.shape[0], dtype=torch.int32, device=dev)
+    total = torch.zeros(1, dtype=torch.int64, device=dev)
+    codebook.snap_(packed, idx=idx_dev, total=total)
+    return (_to_host(idx_dev), _to_host(total)) if to_host else (None, None)
 
 
 def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host, enc_only=True, denorm=False, pack=False,
@@ -555,8 +695,7 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
     trainer.set_eval()
     enc, dec = trainer.Encoder, trainer.Decoder
     dev = trainer.device
-    items = []                                            # (utt, order, start, stop, truncate)
-    padded = []
+    items, padded = [], []
     for u, spec in enumerate(specs):
         if torch.is_tensor(spec) and spec.is_cuda:
             was_padded = spec.shape[0] < MIN_LEN
@@ -565,40 +704,29 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
         else:
             spec, was_padded = _pad_min(np.asarray(spec, dtype=np.float32))
         padded.append(spec)
-        if len(spec) <= seg_len:
-            items.append((u, 0, 0, len(spec), (MIN_LEN // 8) if was_padded else None))
-        else:
-            for k, (a, b) in enumerate(fragments(len(spec), seg_len)):
-                items.append((u, k, a, b, None))
-    # Two kinds of batches instead of one per distinct length (the fragment rule leaves ~60 tail lengths per 64 utterances):
-    # the full seg_len fragments as plain batches, everything else (tails of seg_len .. 2 seg_len - 2 frames, short utterances)
-    # as RAGGED batches padded to their longest member, with per-sample lengths: the kernels pad / normalise / run the reverse
-    # GRU at each sample's own end, so a fragment's result does not depend on what it is batched with.
-    full = [it for it in items if it[3] - it[2] == seg_len]
-    rest = sorted((it for it in items if it[3] - it[2] != seg_len), key=lambda it: it[2] - it[3])      # longest first
-    chunks = [(full[lo:lo + max_batch], None) for lo in range(0, len(full), max_batch)]
-    chunks += [(rest[lo:lo + max_batch], True) for lo in range(0, len(rest), max_batch)]
+        items += _frame_items(u, len(spec), seg_len, was_padded)
+    chunks = _split_chunks(items, seg_len, max_batch)
     # every utterance goes to the device once, whole; the fragments are gathered there (row index tables, a few hundred KB)
     rows, offs = _stage_rows(padded, dev)
     zero_row = int(offs[-1])
     q = _Enqueued()
     q.n_utt, q.dev, q.chunks, q.enc_host, q.dec_dev, q.dec_host = len(specs), dev, [], [], [], []
-    q.conv = q.ulens = q.units_host = q.uoffs = q.units_dev = q.unpack_E = q.idx_host = q.cb_total = None
     gen_plan = None
     if not enc_only:
-        q.conv, q.ulens, dsts = _plan_scatter(items, chunks, len(specs), denorm, dev)
+        q.conv, q.ulens, dsts = _plan_scatter(chunks, len(specs), denorm, dev)
         gen_plan = (q.conv, dsts, shift, denorm)
     if pack:
-        q.uoffs, pack_tabs = _plan_pack(items, chunks, len(specs), dev)
+        q.uoffs, starts, counts = _pack_tables(chunks, len(specs))
+        pack_tabs = _upload_tables(starts, counts, chunks, dev)
         row_bytes = (enc.enc_size + 7) // 8
         units_dev = torch.empty(int(q.uoffs[-1]), row_bytes, dtype=torch.uint8, device=dev)
-    dense_tabs = _plan_dense(chunks, dev) if (codebook is not None and decode_speakers is not None) else None
+    dense_tabs = _upload_tables(*_dense_tables(chunks), chunks, dev) if (codebook is not None and decode_speakers is not None) else None
     for ci, (chunk, ragged) in enumerate(chunks):
-        lens = [b - a for (_, _, a, b, _) in chunk]
+        lens = [it.n for it in chunk]
         Tm = max(lens)
         idx = np.full((len(chunk), Tm), zero_row, dtype=np.int64)
-        for i, (u, _, a, b, _) in enumerate(chunk):
-            idx[i, :b - a] = np.arange(offs[u] + a, offs[u] + b)
+        for i, it in enumerate(chunk):
+            idx[i, :it.n] = np.arange(offs[it.u] + it.a, offs[it.u] + it.b)
         x = rows[torch.from_numpy(idx).to(dev, non_blocking=True)]                                     # [n, Tm, 513]
         G = noise_fn(len(chunk), _t8(Tm), enc.enc_size) if noise_fn is not None else None
         act, _ = enc(x.permute(0, 2, 1), G=G, lengths=(lens if ragged else None))
@@ -606,34 +734,26 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
         if decode_speakers is not None:
             rows_fn = lambda ch, lens_p: dec.forward_rows(act, ch, lengths=lens_p)
             if codebook is not None:                          # the Decoder's operand from the chunk's own snapped rows
-                bits, Tp = enc._last_bits, int(act.shape[2])
+                Tp = int(act.shape[2])
                 if Tp != _t8(Tm):
                     raise L.ZsError('conversion chunk %d: %d encoded frames where the plan has %d' % (ci, Tp, _t8(Tm)))
                 st_c, ln_c = dense_tabs[ci]
                 snapped = torch.empty(len(chunk) * Tp, row_bytes, dtype=torch.uint8, device=dev)
-                L.call('zs_units_pack', 'ZsUnitsPack', torch.cuda.current_stream(dev).cuda_stream, dtype=enc._zs['ctx'].dt, src_f32=0,
-                       src=bits.ptr(), ld_src=bits.ld, n_frag=len(chunk), T=bits.T, E=enc.enc_size, start=L.ptr(st_c), len=L.ptr(ln_c),
-                       packed=L.ptr(snapped), n_units=snapped.shape[0], row_bytes=row_bytes)
+                _launch_units_pack(enc, len(chunk), (st_c, ln_c), snapped, dev)
                 codebook.snap_(snapped)                       # rows behind a fragment's len are snapped too and never read
                 rows_fn = lambda ch, lens_p: dec.forward_units(snapped, st_c, ln_c, len(chunk), Tp, ch, lengths=lens_p)
-            xd = _decode_chunk(trainer, ci, [it[0] for it in chunk], ([_t8(n) for n in lens] if ragged else None), decode_speakers,
+            xd = _decode_chunk(trainer, ci, [it.u for it in chunk], ([_t8(n) for n in lens] if ragged else None), decode_speakers,
                                enc_only, gen_plan, rows_fn)
         q.chunks.append((chunk, lens))
-        if pack:                                              # the engine's own bits buffer, read in place
-            bits = enc._last_bits
-            L.call('zs_units_pack', 'ZsUnitsPack', torch.cuda.current_stream(dev).cuda_stream, dtype=enc._zs['ctx'].dt, src_f32=0,
-                   src=bits.ptr(), ld_src=bits.ld, n_frag=len(chunk), T=bits.T, E=enc.enc_size, start=L.ptr(pack_tabs[ci][0]),
-                   len=L.ptr(pack_tabs[ci][1]), packed=L.ptr(units_dev), n_units=units_dev.shape[0], row_bytes=row_bytes)
+        if pack:
+            _launch_units_pack(enc, len(chunk), pack_tabs[ci], units_dev, dev)
             q.enc_host.append(None)
         else:
             q.enc_host.append(_to_host(act.permute(0, 2, 1).contiguous()))
         q.dec_dev.append(xd)
         q.dec_host.append(_to_host(xd) if (xd is not None and dec_to_host) else None)
     if codebook is not None:
-        idx_dev = torch.empty(units_dev.shape[0], dtype=torch.int32, device=dev)
-        total = torch.zeros(1, dtype=torch.int64, device=dev)
-        codebook.snap_(units_dev, idx=idx_dev, total=total)
-        q.idx_host, q.cb_total = _to_host(idx_dev), _to_host(total)
+        q.idx_host, q.cb_total = _snap_units(codebook, units_dev, dev, to_host=True)
     if pack:
         q.units_dev = units_dev
         q.units_host = _to_host(units_dev)
@@ -642,30 +762,11 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
     return q
 
 
-def _plan_scatter(items, chunks, n_utt, denorm, dev, rows_of=None):
-    """The converted spectrograms' buffer [n_utt, T_max, 513] and, per chunk, the destination row of each of its output rows
-    (b*T + t -> u*T_max + frame, -1 past a fragment's 8 T' rows): utterance u's frames are its fragments' rows in fragment order.
-    The padding rows (frames past an utterance's length) are filled here, once: what the per-utterance path gives them,
-    (denorm of) zero.  All destination tables go to the device in one copy.
-    rows_of(n): the output rows of a fragment of n = b - a (default: n frames in, 8 * _t8(n) rows out)."""
-    rows_of = rows_of or (lambda n: 8 * _t8(n))
-    out_rows = {}
-    for (u, k, a, b, _) in items:
-        out_rows[(u, k)] = rows_of(b - a)
-    start, ulens = {}, [0] * n_utt
-    for (u, k) in sorted(out_rows):
-        start[(u, k)] = ulens[u]
-        ulens[u] += out_rows[(u, k)]
-    Tm = max(ulens)
-    tables = []
-    for chunk, _ in chunks:
-        T = rows_of(max(b - a for (_, _, a, b, _) in chunk))
-        d = np.full((len(chunk), T), -1, dtype=np.int32)
-        for i, (u, k, _, _, _) in enumerate(chunk):
-            n = out_rows[(u, k)]
-            d[i, :n] = np.arange(u * Tm + start[(u, k)], u * Tm + start[(u, k)] + n, dtype=np.int32)
-        tables.append(d.reshape(-1))
-    pad = np.concatenate([np.arange(u * Tm + ulens[u], (u + 1) * Tm, dtype=np.int32) for u in range(n_utt)])
+def _plan_scatter(chunks, n_utt, denorm, dev, rows_of=None):
+    """The converted spectrograms' buffer [n_utt, T_max, 513] and, per chunk, the device table of _scatter_tables (rows_of: see
+    there).  The padding rows (frames past an utterance's length) are filled here, once: what the per-utterance path gives them,
+    (denorm of) zero.  All destination tables go to the device in one copy.  Returns (buffer, frames per utterance, tables)."""
+    Tm, ulens, tables, pad = _scatter_tables(chunks, n_utt, rows_of)
     sizes = [len(t) for t in tables] + [len(pad)]
     if n_utt * Tm >= 2 ** 31:
         raise ValueError('converted batch too large: %d rows' % (n_utt * Tm))
@@ -691,11 +792,11 @@ def _assemble(q, want_dec):
             xd = q.dec_host[ci].numpy()
         elif want_dec == 'device':
             xd = q.dec_dev[ci]
-        for i, (u, k, _, _, trunc) in enumerate(chunk):
+        for i, it in enumerate(chunk):
             tp = _t8(lens[i])
-            enc_out[(u, k)] = None if units is not None else (e[i][:trunc] if trunc is not None else e[i][:tp])
+            enc_out[(it.u, it.k)] = None if units is not None else (e[i][:it.trunc] if it.trunc is not None else e[i][:tp])
             if xd is not None:
-                dec_out[(u, k)] = xd[i][:8 * tp]
+                dec_out[(it.u, it.k)] = xd[i][:8 * tp]
     by_utt = {}
     for (u, k) in enc_out:
         by_utt.setdefault(u, []).append(k)
@@ -714,10 +815,11 @@ def _assemble(q, want_dec):
     return encs, decs
 
 
-def _unit_indices(q):
-    """Per utterance the codeword index of every returned unit (int32 [U_i]) and the summed distance; the copies have been waited for."""
-    idx = q.idx_host.numpy()
-    return [idx[q.uoffs[u]:q.uoffs[u + 1]].copy() for u in range(q.n_utt)], int(q.cb_total.numpy()[0])
+def _unit_indices(idx_host, cb_total, uoffs):
+    """Per utterance the codeword index of every returned unit (int32 [U_i]) and the summed distance, from _snap_units' host copies
+    (which have been waited for) and the utterances' row offsets."""
+    idx = idx_host.numpy()
+    return [idx[uoffs[u]:uoffs[u + 1]].copy() for u in range(len(uoffs) - 1)], int(cb_total.numpy()[0])
 
 
 def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, max_batch=256, to_host=True, enc_only=True, packed=False,
@@ -748,7 +850,7 @@ def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, m
     if codebook is not None and not packed:
         q.unpack_E = codebook.E
     out = _encode_result(q, decode_speakers, to_host, enc_only, units_on_device)
-    return out + (_unit_indices(q)[0],) if want_idx else out
+    return out + (_unit_indices(q.idx_host, q.cb_total, q.uoffs)[0],) if want_idx else out
 
 
 def _encode_result(q, decode_speakers, to_host, enc_only, units_on_device):
@@ -803,27 +905,7 @@ def _gather_decoded(q, out_rows):
     utterance u's frames are its fragments' rows in fragment order, zeros behind them.  out_rows[ci][i]: the valid output rows of
     fragment i of chunk ci.  Returns (t, frames per utterance)."""
     dev = q.dev
-    # row table of all decoded fragments + a zero row; utterance u's frames are its fragments' rows in order
-    bases, total = [], 0
-    for ci, (chunk, lens) in enumerate(q.chunks):
-        bases.append(total)
-        total += q.dec_dev[ci].shape[0] * q.dec_dev[ci].shape[1]
-    frag_rows = {}
-    for ci, (chunk, lens) in enumerate(q.chunks):
-        ld = q.dec_dev[ci].shape[1]
-        for i, (u, k, _, _, _) in enumerate(chunk):
-            frag_rows.setdefault(u, []).append((k, bases[ci] + i * ld, out_rows[ci][i]))
-    ulens = []
-    for u in range(q.n_utt):
-        frag_rows[u].sort()
-        ulens.append(sum(n for (_, _, n) in frag_rows[u]))
-    Tm = max(ulens)
-    idx = np.full((q.n_utt, Tm), total, dtype=np.int64)
-    for u in range(q.n_utt):
-        at = 0
-        for (_, r0, n) in frag_rows[u]:
-            idx[u, at:at + n] = np.arange(r0, r0 + n)
-            at += n
+    idx, ulens, _ = _gather_index(q.chunks, out_rows, [(x.shape[0], x.shape[1]) for x in q.dec_dev], q.n_utt)
     table = torch.cat([x.reshape(-1, x.shape[2]) for x in q.dec_dev] + [torch.zeros(1, q.dec_dev[0].shape[2], dtype=q.dec_dev[0].dtype, device=dev)], dim=0)
     return table[torch.from_numpy(idx).to(dev, non_blocking=True)].float(), ulens                     # [n, Tm, 513]
 
@@ -836,7 +918,7 @@ def _finish_resynth(q, fin, defer, want_idx=False):
         if fin.status:                                        # a persistent GRU pass timed out before this batch's end
             from . import layers
             layers.check_status(q.dev)                        # synchronises, clears the word and raises
-        return (encs, wavs) + _unit_indices(q) if want_idx else (encs, wavs)
+        return (encs, wavs) + _unit_indices(q.idx_host, q.cb_total, q.uoffs) if want_idx else (encs, wavs)
     return finish if defer else finish()
 
 
@@ -897,23 +979,12 @@ def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=N
     rows = _check_units(units, E, packed)
     if codebook is not None:
         _check_codebook(codebook, trainer)
-    bad = [int(c) for c in speakers if not 0 <= int(c) < int(dec.c_a)]
-    if bad:
-        raise ValueError('speaker id %d is outside [0, n_speakers = %d)' % (bad[0], dec.c_a))
+    _check_speaker_range(speakers, int(dec.c_a))
     shift = 0 if enc_only else check_gen_targets(trainer, speakers)
     trainer.set_eval()
     dev = trainer.device
-    Lu = int(seg_len) // 8
-    items = []                                            # (utt, order, first unit, stop, None): the item layout of _enqueue_encode
-    for u, r in enumerate(rows):
-        a = 0
-        for k, n in enumerate(unit_fragments(len(r), seg_len)):
-            items.append((u, k, a, a + n, None))
-            a += n
-    full = [it for it in items if it[3] - it[2] == Lu]
-    rest = sorted((it for it in items if it[3] - it[2] != Lu), key=lambda it: it[2] - it[3])           # longest first
-    chunks = [(full[lo:lo + max_batch], None) for lo in range(0, len(full), max_batch)]
-    chunks += [(rest[lo:lo + max_batch], True) for lo in range(0, len(rest), max_batch)]
+    items = [it for u, r in enumerate(rows) for it in _unit_items(u, len(r), seg_len)]
+    chunks = _split_chunks(items, int(seg_len) // 8, max_batch)
     # every utterance goes to the device once: E / 8 bytes per unit, one pinned buffer, one copy; the fragments are row ranges of it
     uoffs = np.concatenate(([0], np.cumsum([len(r) for r in rows]))).astype(np.int64)
     host = torch.empty(int(uoffs[-1]), row_bytes, dtype=torch.uint8, pin_memory=True)
@@ -921,27 +992,19 @@ def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=N
     packed_dev = host.to(dev, non_blocking=True)
     idx_h = total_h = None
     if codebook is not None:
-        idx_dev = torch.empty(packed_dev.shape[0], dtype=torch.int32, device=dev)
-        total = torch.zeros(1, dtype=torch.int64, device=dev)
-        codebook.snap_(packed_dev, idx=idx_dev, total=total)
-        if want_idx:
-            idx_h, total_h = _to_host(idx_dev), _to_host(total)
-    sizes = [len(chunk) for chunk, _ in chunks]
-    starts = np.array([uoffs[u] + a for chunk, _ in chunks for (u, _, a, _, _) in chunk], dtype=np.int64)
-    counts = np.array([b - a for chunk, _ in chunks for (_, _, a, b, _) in chunk], dtype=np.int32)
-    st_d = torch.split(torch.from_numpy(starts).to(dev, non_blocking=True), sizes)
-    ln_d = torch.split(torch.from_numpy(counts).to(dev, non_blocking=True), sizes)
+        idx_h, total_h = _snap_units(codebook, packed_dev, dev, to_host=want_idx)
     q = _Enqueued()
     q.n_utt, q.dev, q.chunks, q.dec_dev = len(rows), dev, [], []
+    tabs = _upload_tables(*_unit_tables(chunks, uoffs), chunks, dev)
     denorm = not want_specs                               # the vocoder de-normalises (the same device function) when the rows are wanted
     gen_plan = None
     if not enc_only:
-        q.conv, q.ulens, dsts = _plan_scatter(items, chunks, len(rows), denorm, dev, rows_of=lambda n: 8 * n)
+        q.conv, q.ulens, dsts = _plan_scatter(chunks, len(rows), denorm, dev, rows_of=lambda n: 8 * n)
         gen_plan = (q.conv, dsts, shift, denorm)
     for ci, (chunk, ragged) in enumerate(chunks):
-        lens = [b - a for (_, _, a, b, _) in chunk]
-        xd = _decode_chunk(trainer, ci, [it[0] for it in chunk], (lens if ragged else None), speakers, enc_only, gen_plan,
-                           lambda ch, lens_p: dec.forward_units(packed_dev, st_d[ci], ln_d[ci], len(chunk), max(lens), ch, lengths=lens_p))
+        lens = [it.n for it in chunk]
+        xd = _decode_chunk(trainer, ci, [it.u for it in chunk], (lens if ragged else None), speakers, enc_only, gen_plan,
+                           lambda ch, lens_p: dec.forward_units(packed_dev, tabs[ci][0], tabs[ci][1], len(chunk), max(lens), ch, lengths=lens_p))
         q.chunks.append((chunk, lens))
         q.dec_dev.append(xd)
     if enc_only:
@@ -957,9 +1020,8 @@ def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=N
             from . import layers
             layers.check_status(dev)                          # synchronises, clears the word and raises
         specs = [spec_h.numpy()[u, :n].copy() for u, n in enumerate(ulens)] if spec_h is not None else None
-        if want_idx:                                          # copied before the vocoder, which fin() has waited for
-            return specs, wavs, [idx_h.numpy()[uoffs[u]:uoffs[u + 1]].copy() for u in range(len(rows))], int(total_h.numpy()[0])
-        return specs, wavs
+        # the indices were copied before the vocoder, which fin() has waited for
+        return (specs, wavs) + _unit_indices(idx_h, total_h, uoffs) if want_idx else (specs, wavs)
     return finish if defer else finish()
 
 
@@ -1021,6 +1083,20 @@ def store_keys(store, prefix):
     return sorted(store[prefix].keys())
 
 
+def _run_deferred(groups, enqueue, write):
+    """The serving loop of every driver: group i + 1 is enqueued before group i is written, so the host's share of one group (the
+    wait, the assembly, the files) runs under the GPU work of the next.  enqueue(group) puts a group on the stream and returns
+    the arguments of write for it, or None for a group with nothing to write."""
+    pending = None
+    for group in groups:
+        enqueued = enqueue(group)
+        if pending is not None:
+            write(*pending)
+        pending = enqueued
+    if pending is not None:
+        write(*pending)
+
+
 def cross_test_plan(keys, flag, result_dir):
     """The work list of cross_test (convert.py:268-300): every utterance of every source speaker to every target speaker.
     keys(prefix) lists the names under a container prefix (store_keys).  Sources: the speakers under test/ (flag 'test') or the
@@ -1073,16 +1149,12 @@ def cross_test(trainer, seg_len, data_path, speaker2id_path, result_dir, enc_onl
                 write_wav(it['wav'], w, out_rate())
                 write_encodings(it['txt'], e)
 
-        pending = None
-        for group in groups:
+        def enqueue(group):
             specs = [np.asarray(f_h5[it['key']][()], dtype=np.float32) for it in group]
-            fin = resynth_batch(specs, trainer, seg_len, [speaker2id[it['tar']] for it in group], n_iter=n_iter, defer=True,
-                                enc_only=enc_only, momentum=momentum)
-            if pending is not None:
-                write(*pending)
-            pending = (group, fin)
-        if pending is not None:
-            write(*pending)
+            return group, resynth_batch(specs, trainer, seg_len, [speaker2id[it['tar']] for it in group], n_iter=n_iter, defer=True,
+                                        enc_only=enc_only, momentum=momentum)
+
+        _run_deferred(groups, enqueue, write)
     return plan
 
 
@@ -1129,6 +1201,38 @@ def convert_wavs(wavs, rates, trainer, seg_len, speakers, enc_only=True, n_iter=
     return finish if defer else finish()
 
 
+def _dir_plan(who, files, sizes, sizes_name, targets, batch, cap, reject, item):
+    """The grouping convert_dir_plan and synth_dir_plan share: files sorted by (size, path), reject(size) -> the reason a file is
+    skipped for or None, item(file, stem, target, size) for every target of a file that stays, then greedily groups of at most
+    `batch` items and at most `cap` of padded size, items x the longest."""
+    if len(files) != len(sizes):
+        raise ValueError('%s: %d %s for %d files' % (who, len(sizes), sizes_name, len(files)))
+    if batch < 1:
+        raise ValueError('%s: batch must be >= 1' % who)
+    targets = list(targets)
+    if not targets or len(set(targets)) != len(targets):
+        raise ValueError('%s: the targets must be a non-empty list of distinct speakers (got %r)' % (who, targets))
+    stems = {}
+    for f in files:
+        stem = os.path.splitext(os.path.basename(f))[0]
+        if stem in stems:
+            raise ValueError('%s: %s and %s would write the same outputs (stem %r)' % (who, stems[stem], f, stem))
+        stems[stem] = f
+    skipped, groups = [], []
+    for size, f in sorted(zip(sizes, files)):
+        reason = reject(size)
+        if reason is not None:
+            skipped.append({'file': f, 'reason': reason})
+            continue
+        stem = os.path.splitext(os.path.basename(f))[0]
+        for t in targets:                                     # ascending sizes: the newest item is a group's longest
+            if groups and len(groups[-1]) < batch and (len(groups[-1]) + 1) * size <= cap:
+                groups[-1].append(item(f, stem, t, size))
+            else:
+                groups.append([item(f, stem, t, size)])
+    return {'groups': groups, 'skipped': skipped}
+
+
 def convert_dir_plan(files, durations, targets, out_dir, batch=64, max_batch_seconds=600, max_seconds=1800):
     """The work list of convert_dir, on the host alone: every (file, target) pair is an item.  durations[i]: seconds of files[i]
     from its header.  Files are sorted by (duration, path) so that a group pads little and the plan does not depend on the order
@@ -1138,38 +1242,16 @@ def convert_dir_plan(files, durations, targets, out_dir, batch=64, max_batch_sec
     two inputs with the same stem would write the same outputs: ValueError.
     Returns {'groups': [[item]], 'skipped': [{'file', 'reason'}]}, item = {'file', 'stem', 'target', 'duration', 'wav', 'txt'} with
     the outputs {out_dir}/{target}/{stem}.wav and .txt."""
-    if len(files) != len(durations):
-        raise ValueError('convert_dir_plan: %d durations for %d files' % (len(durations), len(files)))
-    if batch < 1:
-        raise ValueError('convert_dir_plan: batch must be >= 1')
-    targets = list(targets)
-    if not targets or len(set(targets)) != len(targets):
-        raise ValueError('convert_dir_plan: the targets must be a non-empty list of distinct speakers (got %r)' % (targets,))
-    stems = {}
-    for f in files:
-        stem = os.path.splitext(os.path.basename(f))[0]
-        if stem in stems:
-            raise ValueError('convert_dir_plan: %s and %s would write the same outputs (stem %r)' % (stems[stem], f, stem))
-        stems[stem] = f
-    skipped, items = [], []
-    for dur, f in sorted((float(d), f) for f, d in zip(files, durations)):
+    def reject(dur):
         if not dur > 0.0:
-            skipped.append({'file': f, 'reason': 'the header gives no samples'})
-            continue
+            return 'the header gives no samples'
         if dur > max_seconds:
-            skipped.append({'file': f, 'reason': '%.1f s is longer than max_seconds = %g' % (dur, max_seconds)})
-            continue
-        stem = os.path.splitext(os.path.basename(f))[0]
-        for t in targets:
-            items.append({'file': f, 'stem': stem, 'target': t, 'duration': dur, 'wav': os.path.join(out_dir, t, stem + '.wav'),
-                          'txt': os.path.join(out_dir, t, stem + '.txt')})
-    groups = []
-    for it in items:                                          # ascending durations: the newest item is a group's longest
-        if groups and len(groups[-1]) < batch and (len(groups[-1]) + 1) * it['duration'] <= max_batch_seconds:
-            groups[-1].append(it)
-        else:
-            groups.append([it])
-    return {'groups': groups, 'skipped': skipped}
+            return '%.1f s is longer than max_seconds = %g' % (dur, max_seconds)
+
+    def item(f, stem, t, dur):
+        return {'file': f, 'stem': stem, 'target': t, 'duration': dur, 'wav': os.path.join(out_dir, t, stem + '.wav'),
+                'txt': os.path.join(out_dir, t, stem + '.txt')}
+    return _dir_plan('convert_dir_plan', files, [float(d) for d in durations], 'durations', targets, batch, max_batch_seconds, reject, item)
 
 
 def write_indices(path, idx):
@@ -1203,9 +1285,11 @@ class _CodebookStats(object):
                 'mean_distance': (self.total / float(n)) if n else 0.0}
 
 
-def _target_table(who, trainer, speaker2id, voices, t_speakers, enc_only, speaker2id_path):
-    """The name -> Decoder row table of a folder driver: speaker2id, then the registered voices (zs_amd.voice.add_voices: {name:
-    row}; a name in both keeps its speaker2id row).  ValueError for a target in neither, and for voices with the generator."""
+def _target_table(who, trainer, speaker2id_path, voices, t_speakers, enc_only):
+    """The name -> Decoder row table of a folder driver: the speaker2id file, then the registered voices (zs_amd.voice.add_voices:
+    {name: row}; a name in both keeps its speaker2id row).  ValueError for a target in neither, and for voices with the generator."""
+    with open(speaker2id_path, 'r') as f_json:
+        speaker2id = json.load(f_json)
     if voices:
         if not enc_only:
             raise ValueError('%s: voices convert through the autoencoder alone (enc_only): the stage-2 generator has rows for its '
@@ -1222,6 +1306,38 @@ def _target_table(who, trainer, speaker2id, voices, t_speakers, enc_only, speake
     if bad:
         raise ValueError('%s: target %r is row %d of a Decoder with %d rows' % (who, bad[0], int(speaker2id[bad[0]]), n_rows))
     return speaker2id
+
+
+def _codebook_stats(codebook, trainer, file):
+    """A folder driver's codebook, checked before anything is read: its _CodebookStats, or None without a codebook."""
+    if codebook is None:
+        return None
+    _check_codebook(codebook, trainer)
+    return _CodebookStats(codebook, file)
+
+
+def _skip_log(tag):
+    """(the manifest's 'skipped' list, skip(path, reason): prints the reason under [tag] and lists the input there)."""
+    skipped = []
+
+    def skip(path, reason):
+        print('[%s] - skipped %s: %s' % (tag, path, reason))
+        skipped.append({'input': path, 'reason': reason})
+    return skipped, skip
+
+
+def _write_manifest(path, in_dir, out_dir, t_speakers, enc_only, items, skipped, stats, voices, speaker2id):
+    """The manifest of a folder driver, written to `path` and returned: the run's fields, the driver's own `items`, what was
+    skipped, and 'codebook' / 'voices' when the run had them."""
+    manifest = {'in_dir': in_dir, 'out_dir': out_dir, 'targets': t_speakers, 'sr': out_rate(), 'enc_only': bool(enc_only),
+                'items': items, 'skipped': skipped}
+    if stats is not None:
+        manifest['codebook'] = stats.manifest()
+    if voices:
+        manifest['voices'] = {t: int(voices[t]) for t in t_speakers if t in voices and speaker2id[t] == voices[t]}
+    with open(path, 'w') as f:
+        json.dump(manifest, f, indent=1)
+    return manifest
 
 
 def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None,
@@ -1242,22 +1358,13 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
     from concurrent.futures import ThreadPoolExecutor
     from .preprocess import read_wav, wav_info
     momentum = gl_momentum(momentum)
-    stats = None
-    if codebook is not None:
-        _check_codebook(codebook, trainer)
-        stats = _CodebookStats(codebook, codebook_file)
-    with open(speaker2id_path, 'r') as f_json:
-        speaker2id = json.load(f_json)
+    stats = _codebook_stats(codebook, trainer, codebook_file)
     t_speakers = list(t_speakers)
-    speaker2id = _target_table('convert_dir', trainer, speaker2id, voices, t_speakers, enc_only, speaker2id_path)
+    speaker2id = _target_table('convert_dir', trainer, speaker2id_path, voices, t_speakers, enc_only)
     if not enc_only:
         check_gen_targets(trainer, [speaker2id[t] for t in t_speakers])
-    skipped, files, durations = [], [], []
-
-    def skip(path, reason):
-        print('[Converter] - skipped %s: %s' % (path, reason))
-        skipped.append({'input': path, 'reason': reason})
-
+    skipped, skip = _skip_log('Converter')
+    files, durations = [], []
     for path in sorted(glob.glob(os.path.join(in_dir, '*.wav'))):
         try:
             sr, n = wav_info(path)
@@ -1302,10 +1409,12 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
                 write_indices(idx_path(it['txt']), res[2][i])
             done.append(it)
 
-    pending = None
     with ThreadPoolExecutor(max_workers=1) as reader:
         fut = reader.submit(read, groups[0], ()) if groups else None
-        for gi, group in enumerate(groups):
+
+        def enqueue(numbered):
+            nonlocal fut
+            gi, group = numbered
             data = fut.result()
             if gi + 1 < len(groups):                          # the next group's files are read under this group's GPU work
                 fut = reader.submit(read, groups[gi + 1], set(feats) | set(data))
@@ -1334,22 +1443,13 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
             later = {it['file'] for g in groups[gi + 1:gi + 2] for it in g}
             for p in [p for p in feats if p not in later]:    # a file's items are adjacent: done with, drop its device rows
                 del feats[p]
-            if pending is not None:
-                write(*pending)
-            pending = (live, fin) if live else None
-        if pending is not None:
-            write(*pending)
-    manifest = {'in_dir': in_dir, 'out_dir': out_dir, 'targets': t_speakers, 'sr': out_rate(), 'enc_only': bool(enc_only),
-                'items': [{'input': it['file'], 'rate': it['rate'], 'samples': it['samples'], 'target': it['target'],
-                           'bounds': it['bounds'], 'frames': it['frames'], 'wav': it['wav'], 'txt': it['txt']} for it in done],
-                'skipped': skipped}
-    if stats is not None:
-        manifest['codebook'] = stats.manifest()
-    if voices:
-        manifest['voices'] = {t: int(voices[t]) for t in t_speakers if t in voices and speaker2id[t] == voices[t]}
-    with open(os.path.join(out_dir, 'convert_dir.json'), 'w') as f:
-        json.dump(manifest, f, indent=1)
-    return manifest
+            return (live, fin) if live else None
+
+        _run_deferred(enumerate(groups), enqueue, write)
+    items = [{'input': it['file'], 'rate': it['rate'], 'samples': it['samples'], 'target': it['target'], 'bounds': it['bounds'],
+              'frames': it['frames'], 'wav': it['wav'], 'txt': it['txt']} for it in done]
+    return _write_manifest(os.path.join(out_dir, 'convert_dir.json'), in_dir, out_dir, t_speakers, enc_only, items, skipped, stats,
+                           voices, speaker2id)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1365,34 +1465,13 @@ def synth_dir_plan(files, n_units, targets, out_dir, batch=64, max_batch_units=6
     with the same stem would write the same outputs: ValueError.
     Returns {'groups': [[item]], 'skipped': [{'file', 'reason'}]}, item = {'file', 'stem', 'target', 'units', 'wav'} with the output
     {out_dir}/{target}/{stem}.wav."""
-    if len(files) != len(n_units):
-        raise ValueError('synth_dir_plan: %d unit counts for %d files' % (len(n_units), len(files)))
-    if batch < 1:
-        raise ValueError('synth_dir_plan: batch must be >= 1')
-    targets = list(targets)
-    if not targets or len(set(targets)) != len(targets):
-        raise ValueError('synth_dir_plan: the targets must be a non-empty list of distinct speakers (got %r)' % (targets,))
-    stems = {}
-    for f in files:
-        stem = os.path.splitext(os.path.basename(f))[0]
-        if stem in stems:
-            raise ValueError('synth_dir_plan: %s and %s would write the same outputs (stem %r)' % (stems[stem], f, stem))
-        stems[stem] = f
-    skipped, items = [], []
-    for n, f in sorted((int(n), f) for f, n in zip(files, n_units)):
+    def reject(n):
         if n < 2:
-            skipped.append({'file': f, 'reason': '%d unit%s: fewer than 2 units' % (n, '' if n == 1 else 's')})
-            continue
-        stem = os.path.splitext(os.path.basename(f))[0]
-        for t in targets:
-            items.append({'file': f, 'stem': stem, 'target': t, 'units': n, 'wav': os.path.join(out_dir, t, stem + '.wav')})
-    groups = []
-    for it in items:                                          # ascending lengths: the newest item is a group's longest
-        if groups and len(groups[-1]) < batch and (len(groups[-1]) + 1) * it['units'] <= max_batch_units:
-            groups[-1].append(it)
-        else:
-            groups.append([it])
-    return {'groups': groups, 'skipped': skipped}
+            return '%d unit%s: fewer than 2 units' % (n, '' if n == 1 else 's')
+
+    def item(f, stem, t, n):
+        return {'file': f, 'stem': stem, 'target': t, 'units': n, 'wav': os.path.join(out_dir, t, stem + '.wav')}
+    return _dir_plan('synth_dir_plan', files, [int(n) for n in n_units], 'unit counts', targets, batch, max_batch_units, reject, item)
 
 
 def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None, voices=None,
@@ -1408,25 +1487,16 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
     codebook: as convert_dir's -- the units of every file are snapped before they are spoken, and what was spoken is written beside
     each wav: {stem}.txt (the snapped units) and {stem}.idx.txt (one codeword index per line); the manifest gains 'codebook'."""
     momentum = gl_momentum(momentum)
-    with open(speaker2id_path, 'r') as f_json:
-        speaker2id = json.load(f_json)
     t_speakers = list(t_speakers)
-    speaker2id = _target_table('synth_dir', trainer, speaker2id, voices, t_speakers, enc_only, speaker2id_path)
+    speaker2id = _target_table('synth_dir', trainer, speaker2id_path, voices, t_speakers, enc_only)
     if trainer.enc_mode == 'continues':
         raise ValueError("enc_mode 'continues' has no units: its encodings are real-valued and cannot be synthesised from unit files")
     if not enc_only:
         check_gen_targets(trainer, [speaker2id[t] for t in t_speakers])
     E = int(trainer.Decoder.c_in)
-    stats = None
-    if codebook is not None:
-        _check_codebook(codebook, trainer)
-        stats = _CodebookStats(codebook, codebook_file)
-    skipped, units = [], {}
-
-    def skip(path, reason):
-        print('[Synthesiser] - skipped %s: %s' % (path, reason))
-        skipped.append({'input': path, 'reason': reason})
-
+    stats = _codebook_stats(codebook, trainer, codebook_file)
+    skipped, skip = _skip_log('Synthesiser')
+    units = {}
     for path in sorted(glob.glob(os.path.join(in_dir, '*.txt'))):
         try:
             units[path] = pack_units(read_units(path, E))
@@ -1456,27 +1526,16 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
                 write_indices(idx_path(txt), res[2][i])
             done.append(it)
 
-    pending = None
-    for group in groups:
-        fin = synth_units_batch([units[it['file']] for it in group], trainer, seg_len, [speaker2id[it['target']] for it in group],
-                                enc_only=enc_only, n_iter=n_iter, defer=True, momentum=momentum, packed=True, codebook=codebook,
-                                want_idx=codebook is not None)
-        if pending is not None:
-            write(*pending)
-        pending = (group, fin)
-    if pending is not None:
-        write(*pending)
-    manifest = {'in_dir': in_dir, 'out_dir': out_dir, 'targets': t_speakers, 'sr': out_rate(), 'enc_only': bool(enc_only),
-                'items': [{'input': it['file'], 'units': it['units'], 'fragments': unit_fragments(it['units'], seg_len),
-                           'target': it['target'], 'wav': it['wav']} for it in done],
-                'skipped': skipped}
-    if stats is not None:
-        manifest['codebook'] = stats.manifest()
-    if voices:
-        manifest['voices'] = {t: int(voices[t]) for t in t_speakers if t in voices and speaker2id[t] == voices[t]}
-    with open(os.path.join(out_dir, 'synth_dir.json'), 'w') as f:
-        json.dump(manifest, f, indent=1)
-    return manifest
+    def enqueue(group):
+        return group, synth_units_batch([units[it['file']] for it in group], trainer, seg_len, [speaker2id[it['target']] for it in group],
+                                        enc_only=enc_only, n_iter=n_iter, defer=True, momentum=momentum, packed=True, codebook=codebook,
+                                        want_idx=codebook is not None)
+
+    _run_deferred(groups, enqueue, write)
+    items = [{'input': it['file'], 'units': it['units'], 'fragments': unit_fragments(it['units'], seg_len), 'target': it['target'],
+              'wav': it['wav']} for it in done]
+    return _write_manifest(os.path.join(out_dir, 'synth_dir.json'), in_dir, out_dir, t_speakers, enc_only, items, skipped, stats, voices,
+                           speaker2id)
 
 
 SINGLE_FILES = {            # convert.py:308-317: the utterances --test_single knows per source speaker
