@@ -1145,6 +1145,77 @@ typedef struct {
 } ZsCodeUpdate;
 int zs_code_update(const ZsCodeUpdate* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Vector codebook (zs_amd.vq): K real-valued codewords of E columns for enc_mode 'continues', fitted by k-means over encoder rows; an
+ * encoded frame is snapped to its nearest codeword in Euclidean distance and a unit file is the sequence of indices.  `code` is fp32
+ * [K][ld_code], `cnorm` fp32 [K] (the squared norms, kept by the caller / zs_vq_update).  Limits: 1 <= K <= ZS_CODE_MAX_K,
+ * 1 <= E <= ZS_CODE_MAX_E, 0 <= n < 2^31, every leading dimension >= E.  A null struct, a K, E or n outside its range, a leading
+ * dimension below E, a null operand with work to do or an operand not aligned to its element return ZS_EINVAL and launch nothing;
+ * n == 0 (n_frag == 0) succeeds and launches nothing.  Caller-owned buffers, no allocation, no synchronisation, stream-ordered.
+ *
+ * zs_vq_assign: x [n][ld_x] of `dtype` (fp32 when src_f32), read in place (the encoder's own output rows of a chunk are such an
+ * operand, as for zs_units_pack).  The score of row i against codeword k is
+ *   s(i, k) = cnorm[k] - 2 sum_j x[i][j] code[k][j]
+ * with exact fp32 operands (bf16 widened), the products and the sum in fp32 on v_mfma_f32_32x32x2_f32, one rounding for the
+ * subtraction.  idx[i] is the k of least computed score, ties to the lowest k.  Every output is optional:
+ *   idx[i]   = that k                                            (int32 [n])
+ *   dist[i]  = max(0, |x_i|^2 + s(i, idx[i])), |x_i|^2 in fp32   (fp32 [n])
+ *   *moved  += #{i : idx[i] differs from the value found in idx[i] on entry}     (int32; when count_moved, which needs idx and moved)
+ * Two decompositions with bitwise equal results (one pair's score does not depend on where the codeword sits):
+ *   rows   a workgroup owns 128 rows and walks the codewords ZS_VQ_TILE_K at a time with a running best per row;
+ *   split  below ZS_VQ_SPLIT_N rows, when `work` is given and K > ZS_VQ_TILE_K: the codeword tiles are dealt to about
+ *          ZS_VQ_SPLIT_WGS workgroups in all, whose (orderable score, k) words meet by a 64-bit minimum in `work` (order-independent),
+ *          and a second launch writes the outputs.  `work` is 8-byte aligned and holds ZS_VQ_WORK_BYTES (12 bytes per row is what is
+ *          asked for); work == NULL selects `rows` at any n.
+ * Results are bitwise equal from run to run. */
+#define ZS_VQ_TILE_K 128
+#define ZS_VQ_SPLIT_N 32768
+#define ZS_VQ_SPLIT_WGS 512
+#define ZS_VQ_WORK_BYTES 393216
+typedef struct {
+  int32_t dtype, src_f32;
+  const void* x; int64_t n, ld_x;
+  const float* code; int64_t ld_code; const float* cnorm; int32_t K, E;
+  int32_t* idx; float* dist; int32_t* moved; int32_t count_moved;
+  void* work; int64_t work_bytes;
+} ZsVqAssign;
+int zs_vq_assign(const ZsVqAssign* p, void* stream);
+/* zs_vq_accum: the sums of one k-means iteration, in fixed point.  x fp32 [n][ld_x].  For every row i with 0 <= idx[i] < K:
+ *   cnt[idx[i]] += 1,   sum[idx[i]][j] += q(x[i][j])  (j < E)                  cnt int32 [K], sum int64 [K][E], dense
+ *   q(v) = (int64) rint(v 2^shift), the product exact in double, half to even; -64 <= shift <= 62
+ * Integer sums do not depend on the order of the adds.  An idx[i] outside [0, K) is never used as an index: the row is skipped and
+ * *bad += 1 (int32).  Privatised as zs_code_accum: a workgroup keeps the sums of a tile of codewords in LDS over its slice of the rows. */
+typedef struct {
+  const float* x; const int32_t* idx; int64_t n, ld_x; int32_t K, E, shift;
+  int32_t* cnt; int64_t* sum; int32_t* bad;
+} ZsVqAccum;
+int zs_vq_accum(const ZsVqAccum* p, void* stream);
+/* zs_vq_update: the means.  For every k with cnt[k] > 0 and j < E
+ *   code[k][j] = (float)((double)sum[k][j] / (double)cnt[k] * 2^-shift)
+ * (int64 -> double to nearest even, an IEEE division, an exact scaling, one rounding to fp32); cnt[k] <= 0 leaves the row as it is.
+ * cnorm[k] is rewritten for EVERY k as the fp32 rounding of sum_j code[k][j]^2 accumulated in double.
+ * *changed += #{k : code[k] differs bitwise from before}  (int32). */
+typedef struct {
+  float* code; int64_t ld_code; float* cnorm; int32_t K, E, shift;
+  const int32_t* cnt; const int64_t* sum; int32_t* changed;
+} ZsVqUpdate;
+int zs_vq_update(const ZsVqUpdate* p, void* stream);
+/* zs_vq_gather: indices straight into the Decoder's input operand of one inference chunk (zs_units_unpack for codewords).  idx int32
+ * [n_idx] holds every utterance of a batch; start (int64 [n_frag], an entry of idx) and len (int32 [n_frag]) are device tables.
+ * dst [n_frag][T][ld_dst] of `dtype`, 16-byte aligned, ld_dst a multiple of 8, written with 16-byte stores:
+ *   dst[f][t][c] = cast(code[idx[start[f] + t]][c])             t < len[f], c < E      (round to nearest even)
+ *   dst[f][t][c] = 0                                             len[f] <= t < T, or E <= c < ld_dst
+ * An entry with len < 0, len > T, start < 0 or start + len > n_idx writes a zero fragment and reads nothing; an idx outside [0, K)
+ * writes a zero row and *bad += 1 (int32).  n_frag in [0, ZS_UNITS_MAX_FRAG]. */
+typedef struct {
+  int32_t dtype;
+  const int32_t* idx; int64_t n_idx;
+  const float* code; int64_t ld_code; int32_t K, E;
+  const int64_t* start; const int32_t* len; int32_t n_frag, T;
+  void* dst; int64_t ld_dst; int32_t* bad;
+} ZsVqGather;
+int zs_vq_gather(const ZsVqGather* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,14 @@ sequences over at most K symbols, each gets a sibling <name>.idx.txt with one co
 synth_dir.json gain a 'codebook' entry (--synth_dir also writes the snapped units beside each wav):
   python main.py --fit_codebook 1024 --fit_dir wavs/ --ckpt_pth CKPT
   python main.py --convert_dir in/ --t_speaker V001 --ckpt_pth CKPT --codebook ckpt_english/codebooks/K1024.codebook.npz
+With --enc_mode continues the same flags take the vector path (zs_amd.vq): --fit_codebook fits K real-valued codewords to the
+encoder's rows of the *.wav of DIR by k-means (default {ckpt_dir}/codebooks/K<K>.vq.npz; *.txt are ignored), --codebook FILE.vq.npz
+snaps every encoded frame to its nearest codeword in Euclidean distance before the Decoder sees it and writes <name>.idx.txt, and
+--synth_dir --codebook FILE.vq.npz speaks the *.idx.txt files of a folder (one integer per line).  The file's kind and the model's
+enc_mode must agree:
+  python main.py --enc_mode continues --fit_codebook 1024 --fit_dir wavs/ --ckpt_pth CKPT
+  python main.py --enc_mode continues --convert_dir in/ --t_speaker V001 --ckpt_pth CKPT --codebook ckpt_english/codebooks/K1024.vq.npz
+  python main.py --enc_mode continues --synth_dir idx/ --t_speaker V001 --ckpt_pth CKPT --codebook ckpt_english/codebooks/K1024.vq.npz
 
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
@@ -227,17 +235,19 @@ def build_parser():
     p.add_argument('--voice', action='append', default=None, metavar='NAME=FILE',
                    help='with --convert_dir / --synth_dir and --enc_only: register the voice file FILE as target speaker NAME (repeatable)')
     p.add_argument('--fit_codebook', type=_codebook_k, default=None, metavar='K',
-                   help='fit a codebook of K codewords (k-modes in Hamming distance, on the GPU) to the units of --fit_dir and write '
-                        'it to --codebook_out')
+                   help='fit a codebook of K codewords to the units of --fit_dir on the GPU and write it to --codebook_out: k-modes in '
+                        "Hamming distance, or for enc_mode 'continues' k-means over the encoder's vectors (a vector codebook)")
     p.add_argument('--fit_dir', type=str, default=None, metavar='DIR',
                    help='with --fit_codebook: the folder of *.wav (encoded as --convert_dir reads them) and *.txt unit files')
     p.add_argument('--codebook_out', type=str, default=None, metavar='FILE',
-                   help='with --fit_codebook: where the codebook goes (default {ckpt_dir}/codebooks/K<K>.codebook.npz)')
+                   help="with --fit_codebook: where the codebook goes (default {ckpt_dir}/codebooks/K<K>.codebook.npz, K<K>.vq.npz for "
+                        "enc_mode 'continues')")
     p.add_argument('--codebook_iters', type=_codebook_iters, default=None, metavar='N',
                    help='with --fit_codebook: k-modes iterations at most (default %d)' % CODEBOOK_ITERS)
     p.add_argument('--codebook_seed', type=int, default=None, metavar='S', help='with --fit_codebook: seed of the starting codewords (default 0)')
     p.add_argument('--codebook', type=str, default=None, metavar='FILE',
-                   help='with --convert_dir / --synth_dir / --test_encode: snap every unit to its nearest codeword of this codebook')
+                   help='with --convert_dir / --synth_dir / --test_encode: snap every unit to its nearest codeword of this codebook; a '
+                        "vector codebook (FILE.vq.npz, enc_mode 'continues') writes <name>.idx.txt index files, and --synth_dir reads them")
     p.add_argument('--out_sr', type=_out_sr, default=None,
                    help='sample rate of the wavs --test / --cross_test / --test_single write (hp.out_sr); default: 16000')
     return p
@@ -514,6 +524,8 @@ def main(argv=None):
         from zs_amd import codebook as zcb
         model_path = args.ckpt_pth if args.ckpt_pth is not None else os.path.join(args.ckpt_dir, args.load_test_model_name)
         trainer = get_trainer(args.hps_path, model_path, args.g_mode, args.enc_mode, use_ema=args.use_ema)
+        if trainer.enc_mode == 'continues':               # real-valued encodings: a vector codebook, k-means (zs_amd.vq)
+            from zs_amd import vq as zcb
         zcb.fit_dir(trainer, hps.seg_len, args.fit_dir, args.fit_codebook,
                     args.codebook_out if args.codebook_out is not None else zcb.default_path(args.ckpt_dir, args.fit_codebook),
                     iters=(args.codebook_iters if args.codebook_iters is not None else CODEBOOK_ITERS),
@@ -528,8 +540,8 @@ def main(argv=None):
         os.makedirs(result_dir, exist_ok=True)
         cb = None
         if args.codebook is not None:                     # a malformed file or another width: ValueError before anything is enqueued
-            from zs_amd.codebook import Codebook
-            cb = Codebook.load(args.codebook, E=int(trainer.Decoder.c_in))
+            from zs_amd.vq import load_codebook       # the file's kind and the model's enc_mode choose the path
+            cb = load_codebook(args.codebook, trainer.enc_mode, E=int(trainer.Decoder.c_in))
         voices = None
         if args.voice:                                    # --voice NAME=FILE: rows appended to the Decoder's tables (zs_amd.voice)
             from zs_amd.voice import add_voices

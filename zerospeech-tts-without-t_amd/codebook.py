@@ -261,21 +261,15 @@ def default_path(ckpt_dir, K):
     return os.path.join(ckpt_dir, 'codebooks', 'K%d.codebook.npz' % int(K))
 
 
-def fit_dir(trainer, seg_len, in_dir, K, out_path, iters=20, seed=0, batch=64):
-    """--fit_codebook: a codebook of K codewords over the units of a folder.  The *.wav of in_dir are read and encoded as convert_dir
-    reads them (any rate, the same trimming, the same skip list), in the groups of convert_dir_plan, through
-    encode_batch(packed=True) with the packed units left on the device; the *.txt unit files of in_dir (read_units) are added.
-    Writes the codebook to out_path and fit_codebook.json beside it (files used and skipped, n_units, the history, symbols used and
-    the entropy of the final assignment); returns (Codebook, that report)."""
+def encode_dir(trainer, seg_len, in_dir, batch, encode):
+    """The *.wav of in_dir read and encoded as convert_dir reads them (any rate, the same trimming, the same skip list), in the groups
+    of convert_dir_plan; encode(specs) -> one device tensor of rows per utterance.  Shared by the two fit_dir (this module's and
+    zs_amd.vq's).  Returns (used [{'input', 'units'}], skipped [{'input', 'reason'}], the device tensors, skip(path, reason))."""
     import glob
     import os
     from . import convert as cv
     from .preprocess import read_wav, wav_info
-    refuse_continues(trainer.enc_mode)
-    K = int(K)
-    if not 1 <= K <= MAX_K:
-        raise ValueError('--fit_codebook: K must be in [1, %d] (got %d)' % (MAX_K, K))
-    E, dev = int(trainer.Decoder.c_in), trainer.device
+    dev = trainer.device
     used, skipped, parts = [], [], []
 
     def skip(path, reason):
@@ -315,9 +309,28 @@ def fit_dir(trainer, seg_len, in_dir, K, out_path, iters=20, seed=0, batch=64):
                 skip(p, 'utterance too short after trimming')
         live = [(p, s) for p, s in zip(paths, specs) if s is not None]
         if live:
-            units, _ = cv.encode_batch([s for _, s in live], trainer, seg_len, packed=True, units_on_device=True)
+            units = encode([s for _, s in live])
             parts += units
             used += [{'input': p, 'units': int(u.shape[0])} for (p, _), u in zip(live, units)]
+    return used, skipped, parts, skip
+
+
+def fit_dir(trainer, seg_len, in_dir, K, out_path, iters=20, seed=0, batch=64):
+    """--fit_codebook: a codebook of K codewords over the units of a folder.  The *.wav of in_dir are read and encoded as convert_dir
+    reads them (any rate, the same trimming, the same skip list), in the groups of convert_dir_plan, through
+    encode_batch(packed=True) with the packed units left on the device; the *.txt unit files of in_dir (read_units) are added.
+    Writes the codebook to out_path and fit_codebook.json beside it (files used and skipped, n_units, the history, symbols used and
+    the entropy of the final assignment); returns (Codebook, that report)."""
+    import glob
+    import os
+    from . import convert as cv
+    refuse_continues(trainer.enc_mode)
+    K = int(K)
+    if not 1 <= K <= MAX_K:
+        raise ValueError('--fit_codebook: K must be in [1, %d] (got %d)' % (MAX_K, K))
+    E, dev = int(trainer.Decoder.c_in), trainer.device
+    used, skipped, parts, skip = encode_dir(trainer, seg_len, in_dir, batch,
+                                            lambda specs: cv.encode_batch(specs, trainer, seg_len, packed=True, units_on_device=True)[0])
     for path in sorted(glob.glob(os.path.join(in_dir, '*.txt'))):
         if path.endswith('.idx.txt'):
             continue

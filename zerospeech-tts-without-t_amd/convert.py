@@ -450,7 +450,7 @@ class _Enqueued(object):
     nothing for is None.  With the generator (enc_only=False), `conv` holds the converted spectrograms [n_utt, T_max, 513] fp32 on
     the device (amplitudes when de-normalised) and `ulens` their frames."""
     __slots__ = ('n_utt', 'chunks', 'enc_host', 'dec_dev', 'dec_host', 'enc_done', 'dev', 'conv', 'ulens', 'units_host', 'uoffs',
-                 'units_dev', 'unpack_E', 'idx_host', 'cb_total')
+                 'units_dev', 'unpack_E', 'idx_host', 'cb_total', 'vq', 'enc_dev')
 
     def __init__(self):
         for slot in self.__slots__:
@@ -646,8 +646,32 @@ def _decode_chunk(trainer, ci, utts, lens_p, decode_speakers, enc_only, gen_plan
 def _check_codebook(codebook, trainer):
     """A codebook is refused before anything is enqueued for enc_mode 'continues' and for a width other than the Decoder's c_in."""
     from .codebook import refuse_continues
-    refuse_continues(trainer.enc_mode)
+    if _is_vq(codebook):                                      # a vector codebook serves 'continues' and no other mode
+        if trainer.enc_mode != 'continues':
+            raise ValueError("a vector codebook serves enc_mode 'continues': this model's enc_mode is %r" % trainer.enc_mode)
+    else:
+        refuse_continues(trainer.enc_mode)
     codebook.check_width(int(trainer.Decoder.c_in))
+
+
+def _is_vq(codebook):
+    return codebook is not None and getattr(codebook, 'kind', None) == 'vector'
+
+
+def _vq_index_map(chunks, n_utt):
+    """Where the returned units of a batch lie in the chunks' index buffers laid end to end (chunk ci: len(chunk) x Tp rows, Tp the
+    encoded frames of its longest member): utterance u's units are its fragments' in fragment order, under the MIN_LEN truncation of
+    _pack_tables.  Returns (row offsets of the utterances int64 [n_utt + 1], the source row of every unit int64)."""
+    uoffs, starts, lens = _pack_tables(chunks, n_utt)
+    src = np.empty(int(uoffs[-1]), dtype=np.int64)
+    j, base = 0, 0
+    for chunk, _ in chunks:
+        Tp = _t8(max(it.n for it in chunk))
+        for i in range(len(chunk)):
+            src[starts[j]:starts[j] + lens[j]] = np.arange(base + i * Tp, base + i * Tp + lens[j])
+            j += 1
+        base += len(chunk) * Tp
+    return uoffs, src
 
 
 def _launch_units_pack(enc, n_frag, tabs, packed, dev):
@@ -669,7 +693,7 @@ def _snap_units(codebook, packed, dev, to_host):
 
 
 def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host, enc_only=True, denorm=False, pack=False,
-                    codebook=None):
+                    codebook=None, rows_on_device=False):
     """Fragment rule + every Encoder / Decoder launch of a batch of utterances, WITHOUT a host synchronisation: the caller decides
     what else to put on the stream (the vocoder) before it waits.
     enc_only=False (decode_speakers required): the stage-2 generator as well, and zs_gen_scatter writes every chunk's converted rows
@@ -680,12 +704,18 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
     codebook (zs_amd.codebook.Codebook; implies pack): every unit is snapped to its nearest codeword.  A chunk's units go encoder ->
     chunk-local packed rows -> zs_code_assign in place -> Decoder.forward_units, so the Decoder and the generator read the snapped
     units of every encoded frame; the utterance buffer is snapped once, in place, behind the last chunk (the same rows, the same
-    codewords) with the index of every unit (q.idx_host) and the summed distance (q.cb_total)."""
+    codewords) with the index of every unit (q.idx_host) and the summed distance (q.cb_total).
+    codebook a zs_amd.vq.VectorCodebook (enc_mode 'continues'; nothing is packed): a chunk goes encoder -> zs_vq_assign over the
+    chunk's rows, read in place from the engine's output -> zs_vq_gather (Decoder.forward_indices) -> the Decoder's launches; the
+    chunks' indices are brought into utterance order on the device (_vq_index_map) and copied once (q.idx_host), with the summed
+    squared distance of the returned units (q.cb_total, a double), and the encodings returned are the codewords of the indices.
+    rows_on_device: the fp32 encodings stay on the device (q.enc_dev, one tensor per chunk) instead of being copied to the host."""
+    vq = _is_vq(codebook)
     if codebook is not None:
         _check_codebook(codebook, trainer)
         if int(trainer.Encoder.enc_size) != codebook.E:
             raise ValueError("codebook field E is %d, the Encoder's enc_size is %d" % (codebook.E, int(trainer.Encoder.enc_size)))
-        pack = True
+        pack = pack or not vq
     if pack and trainer.enc_mode == 'continues':
         raise ValueError("enc_mode 'continues' has no units to pack (its encodings are not 0 / 1)")
     if not enc_only:
@@ -721,6 +751,14 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
         row_bytes = (enc.enc_size + 7) // 8
         units_dev = torch.empty(int(q.uoffs[-1]), row_bytes, dtype=torch.uint8, device=dev)
     dense_tabs = _upload_tables(*_dense_tables(chunks), chunks, dev) if (codebook is not None and decode_speakers is not None) else None
+    if vq:                                                    # a vector codebook ('continues'): indices, not packed rows
+        from . import vq as zvq
+        code_d, cnorm_d = codebook.to(dev)
+        vq_work, vq_idx, vq_dist = zvq.workspace(dev), [], []
+        vq_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        q.vq = codebook
+        q.uoffs, vq_src = _vq_index_map(chunks, len(specs))
+        vq_src = torch.from_numpy(vq_src).to(dev, non_blocking=True)
     for ci, (chunk, ragged) in enumerate(chunks):
         lens = [it.n for it in chunk]
         Tm = max(lens)
@@ -731,9 +769,24 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
         G = noise_fn(len(chunk), _t8(Tm), enc.enc_size) if noise_fn is not None else None
         act, _ = enc(x.permute(0, 2, 1), G=G, lengths=(lens if ragged else None))
         xd = None
+        if vq:                                                # encoder -> zs_vq_assign over the chunk's rows, read in place
+            bits = enc._last_bits
+            Tp = int(bits.T)
+            if Tp != _t8(Tm) or int(bits.B) != len(chunk):
+                raise L.ZsError('conversion chunk %d: %d x %d encoded frames where the plan has %d x %d' % (ci, bits.B, Tp, len(chunk), _t8(Tm)))
+            idx_c = torch.empty(len(chunk) * Tp, dtype=torch.int32, device=dev)
+            dist_c = torch.empty(len(chunk) * Tp, dtype=torch.float32, device=dev)
+            L.call('zs_vq_assign', 'ZsVqAssign', torch.cuda.current_stream(dev).cuda_stream, dtype=enc._zs['ctx'].dt, src_f32=0, x=bits.ptr(),
+                   n=len(chunk) * Tp, ld_x=bits.ld, code=L.ptr(code_d), ld_code=codebook.E, cnorm=L.ptr(cnorm_d), K=codebook.K, E=codebook.E,
+                   idx=L.ptr(idx_c), dist=L.ptr(dist_c), work=L.ptr(vq_work), work_bytes=vq_work.numel() * 8)
+            vq_idx.append(idx_c)
+            vq_dist.append(dist_c)
         if decode_speakers is not None:
             rows_fn = lambda ch, lens_p: dec.forward_rows(act, ch, lengths=lens_p)
-            if codebook is not None:                          # the Decoder's operand from the chunk's own snapped rows
+            if vq:                                            # -> zs_vq_gather: the Decoder's operand from the chunk's own indices
+                st_c, ln_c = dense_tabs[ci]
+                rows_fn = lambda ch, lens_p: dec.forward_indices(idx_c, code_d, st_c, ln_c, len(chunk), Tp, ch, vq_bad, lengths=lens_p)
+            if codebook is not None and not vq:               # the Decoder's operand from the chunk's own snapped rows
                 Tp = int(act.shape[2])
                 if Tp != _t8(Tm):
                     raise L.ZsError('conversion chunk %d: %d encoded frames where the plan has %d' % (ci, Tp, _t8(Tm)))
@@ -748,11 +801,20 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
         if pack:
             _launch_units_pack(enc, len(chunk), pack_tabs[ci], units_dev, dev)
             q.enc_host.append(None)
+        elif vq:                                              # the encodings returned are the codewords of the indices
+            q.enc_host.append(None)
+        elif rows_on_device:                                  # the fp32 rows stay where they are (q.enc_dev): no copy to the host
+            q.enc_host.append(None)
+            q.enc_dev = (q.enc_dev or []) + [act.permute(0, 2, 1).contiguous()]
         else:
             q.enc_host.append(_to_host(act.permute(0, 2, 1).contiguous()))
         q.dec_dev.append(xd)
         q.dec_host.append(_to_host(xd) if (xd is not None and dec_to_host) else None)
-    if codebook is not None:
+    if vq:                                                    # the chunks' indices into utterance order, then one copy
+        idx_all, dist_all = (torch.cat(vq_idx), torch.cat(vq_dist)) if len(vq_idx) > 1 else (vq_idx[0], vq_dist[0])
+        q.idx_host = _to_host(idx_all[vq_src])
+        q.cb_total = _to_host(dist_all[vq_src].sum(dtype=torch.float64).reshape(1))
+    elif codebook is not None:
         q.idx_host, q.cb_total = _snap_units(codebook, units_dev, dev, to_host=True)
     if pack:
         q.units_dev = units_dev
@@ -785,8 +847,9 @@ def _assemble(q, want_dec):
     The caller has waited for the copies."""
     enc_out, dec_out = {}, {}
     units = q.units_host.numpy() if q.units_host is not None else None      # packed: one buffer, utterance by utterance
+    vq_idx = q.idx_host.numpy() if q.vq is not None else None              # a vector codebook: the codewords of the indices
     for ci, (chunk, lens) in enumerate(q.chunks):
-        e = q.enc_host[ci].numpy() if units is None else None
+        e = q.enc_host[ci].numpy() if (units is None and vq_idx is None) else None
         xd = None
         if want_dec == 'host':
             xd = q.dec_host[ci].numpy()
@@ -794,7 +857,7 @@ def _assemble(q, want_dec):
             xd = q.dec_dev[ci]
         for i, it in enumerate(chunk):
             tp = _t8(lens[i])
-            enc_out[(it.u, it.k)] = None if units is not None else (e[i][:it.trunc] if it.trunc is not None else e[i][:tp])
+            enc_out[(it.u, it.k)] = None if e is None else (e[i][:it.trunc] if it.trunc is not None else e[i][:tp])
             if xd is not None:
                 dec_out[(it.u, it.k)] = xd[i][:8 * tp]
     by_utt = {}
@@ -803,7 +866,9 @@ def _assemble(q, want_dec):
     encs, decs = [], ([] if want_dec else None)
     for u in range(q.n_utt):
         ks = sorted(by_utt[u])
-        if units is None:
+        if vq_idx is not None:
+            encs.append(q.vq.vectors[vq_idx[q.uoffs[u]:q.uoffs[u + 1]]])
+        elif units is None:
             encs.append(np.concatenate([enc_out[(u, k)] for k in ks], axis=0))
         elif q.unpack_E is not None:                          # packed on the way (a codebook), plain rows for the caller
             encs.append(unpack_units(units[q.uoffs[u]:q.uoffs[u + 1]], q.unpack_E))
@@ -818,8 +883,22 @@ def _assemble(q, want_dec):
 def _unit_indices(idx_host, cb_total, uoffs):
     """Per utterance the codeword index of every returned unit (int32 [U_i]) and the summed distance, from _snap_units' host copies
     (which have been waited for) and the utterances' row offsets."""
-    idx = idx_host.numpy()
-    return [idx[uoffs[u]:uoffs[u + 1]].copy() for u in range(len(uoffs) - 1)], int(cb_total.numpy()[0])
+    idx, total = idx_host.numpy(), cb_total.numpy()[0]
+    return [idx[uoffs[u]:uoffs[u + 1]].copy() for u in range(len(uoffs) - 1)], (float(total) if total.dtype.kind == 'f' else int(total))
+
+
+def encode_rows_on_device(specs, trainer, seg_len, noise_fn=None, max_batch=256):
+    """encode_batch's encodings as fp32 device tensors [U_i, E], one per utterance, under the same fragment and truncation rules:
+    the encoder's rows never visit the host (what a vector codebook is fitted to, zs_amd.vq.fit_dir)."""
+    q = _enqueue_encode(specs, trainer, seg_len, None, noise_fn, max_batch, dec_to_host=False, rows_on_device=True)
+    torch.cuda.current_stream(q.dev).synchronize()
+    from . import layers
+    layers.check_status(q.dev)
+    parts = {}
+    for (chunk, lens), e in zip(q.chunks, q.enc_dev):
+        for i, it in enumerate(chunk):
+            parts[(it.u, it.k)] = e[i][:(it.trunc if it.trunc is not None else _t8(lens[i]))]
+    return [torch.cat([parts[k] for k in sorted(k for k in parts if k[0] == u)], dim=0) for u in range(q.n_utt)]
 
 
 def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, max_batch=256, to_host=True, enc_only=True, packed=False,
@@ -840,14 +919,15 @@ def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, m
     units_on_device=True (with packed): the packed encodings are returned as device tensors, views of the one uint8 buffer.
     codebook: a zs_amd.codebook.Codebook -- every unit is snapped to its nearest codeword before the Decoder and the generator see
     it and before it is returned (under the same truncation rules, in the form `packed` asks for); want_idx=True appends the list
-    of codeword indices, int32 [U_i] per utterance, to the result."""
+    of codeword indices, int32 [U_i] per utterance, to the result.  For enc_mode 'continues' a zs_amd.vq.VectorCodebook: every encoded
+    frame is snapped to its nearest codeword in Euclidean distance and the encodings returned are those codewords, fp32 [U_i, E]."""
     if want_idx and codebook is None:
         raise ValueError('encode_batch: want_idx needs a codebook')
     if units_on_device and not packed:
         raise ValueError('encode_batch: units_on_device needs packed=True')
     q = _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host=to_host, enc_only=enc_only,
                         pack=packed, codebook=codebook)
-    if codebook is not None and not packed:
+    if codebook is not None and not packed and not _is_vq(codebook):
         q.unpack_E = codebook.E
     out = _encode_result(q, decode_speakers, to_host, enc_only, units_on_device)
     return out + (_unit_indices(q.idx_host, q.cb_total, q.uoffs)[0],) if want_idx else out
@@ -883,7 +963,8 @@ def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, 
     into the vocoder's input, so the gather / combine / de-normalisation passes below do not exist on that path.
     momentum: the vocoder's fast Griffin-Lim momentum (see griffin_lim_batch; None: hp.gl_momentum).
     codebook: as encode_batch's -- the Decoder, the generator and the returned encodings see the snapped units; want_idx=True
-    makes the result (encodings, wavs, codeword indices int32 [U_i] per utterance, summed Hamming distance of the snap)."""
+    makes the result (encodings, wavs, codeword indices int32 [U_i] per utterance, summed Hamming distance of the snap -- under a
+    vector codebook, enc_mode 'continues', the summed squared Euclidean distance, a float)."""
     momentum = gl_momentum(momentum)
     if want_idx and codebook is None:
         raise ValueError('resynth_batch: want_idx needs a codebook')
@@ -895,7 +976,7 @@ def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, 
         q = _enqueue_encode(specs, trainer, seg_len, speakers, noise_fn, max_batch, dec_to_host=False, codebook=codebook)
         t, ulens = _gather_decoded(q, [[8 * _t8(n) for n in lens] for _, lens in q.chunks])
         fin = _enqueue_vocoder(t, ulens, n_iter, do_trim, q.dev, momentum=momentum)
-    if codebook is not None:
+    if codebook is not None and not _is_vq(codebook):
         q.unpack_E = codebook.E
     return _finish_resynth(q, fin, defer, want_idx)
 
@@ -993,26 +1074,8 @@ def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=N
     idx_h = total_h = None
     if codebook is not None:
         idx_h, total_h = _snap_units(codebook, packed_dev, dev, to_host=want_idx)
-    q = _Enqueued()
-    q.n_utt, q.dev, q.chunks, q.dec_dev = len(rows), dev, [], []
-    tabs = _upload_tables(*_unit_tables(chunks, uoffs), chunks, dev)
-    denorm = not want_specs                               # the vocoder de-normalises (the same device function) when the rows are wanted
-    gen_plan = None
-    if not enc_only:
-        q.conv, q.ulens, dsts = _plan_scatter(chunks, len(rows), denorm, dev, rows_of=lambda n: 8 * n)
-        gen_plan = (q.conv, dsts, shift, denorm)
-    for ci, (chunk, ragged) in enumerate(chunks):
-        lens = [it.n for it in chunk]
-        xd = _decode_chunk(trainer, ci, [it.u for it in chunk], (lens if ragged else None), speakers, enc_only, gen_plan,
-                           lambda ch, lens_p: dec.forward_units(packed_dev, tabs[ci][0], tabs[ci][1], len(chunk), max(lens), ch, lengths=lens_p))
-        q.chunks.append((chunk, lens))
-        q.dec_dev.append(xd)
-    if enc_only:
-        t, ulens = _gather_decoded(q, [[8 * n for n in lens] for _, lens in q.chunks])
-    else:
-        t, ulens = q.conv, q.ulens
-    spec_h = _to_host(t) if want_specs else None
-    fin = _enqueue_vocoder(t, ulens, n_iter, do_trim, dev, amplitudes=(denorm and not enc_only), momentum=momentum)
+    fin, spec_h, ulens = _enqueue_synth(trainer, seg_len, chunks, uoffs, speakers, enc_only, shift, n_iter, do_trim, momentum, want_specs,
+                                        lambda tab, B, T0, ch, lens_p: dec.forward_units(packed_dev, tab[0], tab[1], B, T0, ch, lengths=lens_p))
 
     def finish():
         wavs = fin()
@@ -1022,6 +1085,110 @@ def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=N
         specs = [spec_h.numpy()[u, :n].copy() for u, n in enumerate(ulens)] if spec_h is not None else None
         # the indices were copied before the vocoder, which fin() has waited for
         return (specs, wavs) + _unit_indices(idx_h, total_h, uoffs) if want_idx else (specs, wavs)
+    return finish if defer else finish()
+
+
+def _enqueue_synth(trainer, seg_len, chunks, uoffs, speakers, enc_only, shift, n_iter, do_trim, momentum, want_specs, operand):
+    """The decode half and the vocoder of a batch of unit (or index) sequences, shared by synth_units_batch and synth_index_batch:
+    operand(tab, B, T0, ch, lens_p) -> (bits, x_dec) builds and decodes one chunk's operand from its (start, len) device tables over
+    the batch's one buffer.  Returns (the vocoder's finish function, the pinned copy of the spectrograms or None, frames per
+    utterance); nothing is waited for."""
+    dev, n_utt = trainer.device, len(uoffs) - 1
+    q = _Enqueued()
+    q.n_utt, q.dev, q.chunks, q.dec_dev = n_utt, dev, [], []
+    tabs = _upload_tables(*_unit_tables(chunks, uoffs), chunks, dev)
+    denorm = not want_specs                               # the vocoder de-normalises (the same device function) when the rows are wanted
+    gen_plan = None
+    if not enc_only:
+        q.conv, q.ulens, dsts = _plan_scatter(chunks, n_utt, denorm, dev, rows_of=lambda n: 8 * n)
+        gen_plan = (q.conv, dsts, shift, denorm)
+    for ci, (chunk, ragged) in enumerate(chunks):
+        lens = [it.n for it in chunk]
+        xd = _decode_chunk(trainer, ci, [it.u for it in chunk], (lens if ragged else None), speakers, enc_only, gen_plan,
+                           lambda ch, lens_p: operand(tabs[ci], len(chunk), max(lens), ch, lens_p))
+        q.chunks.append((chunk, lens))
+        q.dec_dev.append(xd)
+    if enc_only:
+        t, ulens = _gather_decoded(q, [[8 * n for n in lens] for _, lens in q.chunks])
+    else:
+        t, ulens = q.conv, q.ulens
+    spec_h = _to_host(t) if want_specs else None
+    fin = _enqueue_vocoder(t, ulens, n_iter, do_trim, dev, amplitudes=(denorm and not enc_only), momentum=momentum)
+    return fin, spec_h, ulens
+
+
+def read_indices(path, K):
+    """The parser of what write_indices writes: one integer in [0, K) per line -> int32 [U].  ValueError naming the file and the line
+    for anything else, and for a file without a line."""
+    out = []
+    with open(path, 'r') as f:
+        for no, line in enumerate(f, 1):
+            tokens = line.split()
+            if len(tokens) != 1:
+                raise ValueError('%s, line %d: %d values, expected one index' % (path, no, len(tokens)))
+            try:
+                k = int(tokens[0], 10)
+            except ValueError:
+                raise ValueError('%s, line %d: %r is not an integer' % (path, no, tokens[0]))
+            if not 0 <= k < K:
+                raise ValueError('%s, line %d: index %d is outside [0, K = %d)' % (path, no, k, K))
+            out.append(k)
+    if not out:
+        raise ValueError('%s: no indices (the file is empty)' % path)
+    return np.asarray(out, dtype=np.int32)
+
+
+def synth_index_batch(idx_lists, trainer, seg_len, speakers, codebook, enc_only=True, n_iter=None, do_trim=True, max_batch=256, defer=False,
+                      momentum=None, want_specs=False):
+    """Speech from codeword indices: synth_units_batch for enc_mode 'continues' under a vector codebook (zs_amd.vq.VectorCodebook).
+    idx_lists: one integer sequence per utterance (what resynth_batch(want_idx=True) returns, what read_indices parses from an
+    .idx.txt file).  Every index goes to the device once, in one int32 buffer; unit_fragments cuts each utterance as
+    synth_units_batch cuts it, zs_vq_gather writes each chunk's Decoder operand from the codewords, and the decode half and the
+    vocoder are synth_units_batch's own.  Returns (specs or None, wavs); defer=True returns the function that waits for them.
+    Refused before anything is enqueued: a codebook that is no vector codebook (for 'continues' in synth_units_batch's words), a
+    width other than the Decoder's c_in, an index outside [0, K), fewer than 2 indices (ValueError); a speaker the Decoder or the
+    generator cannot take."""
+    momentum = gl_momentum(momentum)
+    if not _is_vq(codebook):
+        if trainer.enc_mode == 'continues':
+            raise ValueError("enc_mode 'continues' has no units: its encodings are real-valued and cannot be synthesised from unit files")
+        raise ValueError('synth_index_batch: the codebook must be a vector codebook (zs_amd.vq.VectorCodebook)')
+    _check_codebook(codebook, trainer)
+    if len(speakers) != len(idx_lists) or not len(idx_lists):
+        raise ValueError('synth_index_batch: %d target speakers for %d utterances' % (len(speakers), len(idx_lists)))
+    rows = []
+    for i, seq in enumerate(idx_lists):
+        a = np.asarray(seq.cpu() if torch.is_tensor(seq) else seq)
+        if a.ndim != 1 or a.dtype.kind not in 'iu':
+            raise ValueError('utterance %d: indices must be a 1-D integer sequence (got %s %s)' % (i, a.dtype, a.shape))
+        if a.shape[0] < 2:
+            raise ValueError('utterance %d has fewer than 2 indices (the Decoder needs two rows)' % i)
+        if (a < 0).any() or (a >= codebook.K).any():
+            raise ValueError('utterance %d: an index is outside [0, K = %d)' % (i, codebook.K))
+        rows.append(a.astype(np.int32))
+    dec = trainer.Decoder
+    _check_speaker_range(speakers, int(dec.c_a))
+    shift = 0 if enc_only else check_gen_targets(trainer, speakers)
+    trainer.set_eval()
+    dev = trainer.device
+    items = [it for u, r in enumerate(rows) for it in _unit_items(u, len(r), seg_len)]
+    chunks = _split_chunks(items, int(seg_len) // 8, max_batch)
+    uoffs = np.concatenate(([0], np.cumsum([len(r) for r in rows]))).astype(np.int64)
+    host = torch.empty(int(uoffs[-1]), dtype=torch.int32, pin_memory=True)
+    np.concatenate(rows, axis=0, out=host.numpy())
+    idx_dev = host.to(dev, non_blocking=True)                 # the one H2D copy of the batch
+    code_d, _ = codebook.to(dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    fin, spec_h, ulens = _enqueue_synth(trainer, seg_len, chunks, uoffs, speakers, enc_only, shift, n_iter, do_trim, momentum, want_specs,
+                                        lambda tab, B, T0, ch, lens_p: dec.forward_indices(idx_dev, code_d, tab[0], tab[1], B, T0, ch, bad,
+                                                                                           lengths=lens_p))
+
+    def finish():
+        wavs = fin()
+        if fin.status:
+            from . import layers
+            layers.check_status(dev)
+        return ([spec_h.numpy()[u, :n].copy() for u, n in enumerate(ulens)] if spec_h is not None else None), wavs
     return finish if defer else finish()
 
 
@@ -1275,7 +1442,7 @@ class _CodebookStats(object):
     def add(self, idxs, total):
         for i in idxs:
             self.hist += np.bincount(i, minlength=self.cb.K)
-        self.total += int(total)
+        self.total += total                                   # int (Hamming) or float (squared Euclidean, a vector codebook)
 
     def manifest(self):
         from .codebook import usage_counts
@@ -1354,7 +1521,8 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
     the manifest then lists them under 'voices'.
     codebook: a zs_amd.codebook.Codebook (codebook_file: where it came from) -- the units are snapped as resynth_batch snaps them,
     every .txt gets a sibling .idx.txt (one codeword index per line) and the manifest the entry 'codebook': {file, K, symbols_used,
-    entropy_bits_per_unit, mean_distance} over the units written."""
+    entropy_bits_per_unit, mean_distance} over the units written.  A zs_amd.vq.VectorCodebook for enc_mode 'continues': the same
+    outputs, the .idx.txt being the unit file (the .txt holds what write_encodings writes for real-valued rows)."""
     from concurrent.futures import ThreadPoolExecutor
     from .preprocess import read_wav, wav_info
     momentum = gl_momentum(momentum)
@@ -1485,11 +1653,15 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
     units, is skipped with a printed reason and listed in the manifest; the run goes on.
     voices: as convert_dir's.
     codebook: as convert_dir's -- the units of every file are snapped before they are spoken, and what was spoken is written beside
-    each wav: {stem}.txt (the snapped units) and {stem}.idx.txt (one codeword index per line); the manifest gains 'codebook'."""
+    each wav: {stem}.txt (the snapped units) and {stem}.idx.txt (one codeword index per line); the manifest gains 'codebook'.
+    A zs_amd.vq.VectorCodebook (enc_mode 'continues', refused without one): the *.idx.txt of in_dir are read instead (read_indices:
+    one integer in [0, K) per line), <name>.idx.txt is spoken as {stem}.wav through synth_index_batch, and the indices spoken are
+    written beside each wav as {stem}.idx.txt."""
     momentum = gl_momentum(momentum)
     t_speakers = list(t_speakers)
     speaker2id = _target_table('synth_dir', trainer, speaker2id_path, voices, t_speakers, enc_only)
-    if trainer.enc_mode == 'continues':
+    vq = _is_vq(codebook)                                     # a vector codebook: the *.idx.txt index files of a 'continues' model
+    if trainer.enc_mode == 'continues' and not vq:
         raise ValueError("enc_mode 'continues' has no units: its encodings are real-valued and cannot be synthesised from unit files")
     if not enc_only:
         check_gen_targets(trainer, [speaker2id[t] for t in t_speakers])
@@ -1497,9 +1669,9 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
     stats = _codebook_stats(codebook, trainer, codebook_file)
     skipped, skip = _skip_log('Synthesiser')
     units = {}
-    for path in sorted(glob.glob(os.path.join(in_dir, '*.txt'))):
+    for path in sorted(glob.glob(os.path.join(in_dir, '*.idx.txt' if vq else '*.txt'))):
         try:
-            units[path] = pack_units(read_units(path, E))
+            units[path] = read_indices(path, codebook.K) if vq else pack_units(read_units(path, E))
         except (OSError, ValueError) as e:
             skip(path, 'cannot be read: %s' % e)
     files = sorted(units)
@@ -1507,6 +1679,10 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
     for s in plan['skipped']:
         skip(s['file'], s['reason'])
     groups = plan['groups']
+    if vq:                                                    # <name>.idx.txt speaks as <name>.wav
+        for it in (it for g in groups for it in g):
+            it['stem'] = it['stem'][:-len('.idx')]
+            it['wav'] = os.path.join(out_dir, it['target'], it['stem'] + '.wav')
     print('[Synthesiser] - %d unit files, %d target speakers, %d syntheses in %d groups' %
           (len(files) - len(plan['skipped']), len(t_speakers), sum(len(g) for g in groups), len(groups)))
     os.makedirs(out_dir, exist_ok=True)
@@ -1515,18 +1691,25 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
     def write(group, fin):
         res = fin()
         wavs = res[1]
-        if stats is not None:
+        if vq:                                                # what was spoken: the file's own indices, nothing was snapped
+            stats.add([units[it['file']] for it in group], 0.0)
+        elif stats is not None:
             stats.add(res[2], res[3])
         for i, (it, w) in enumerate(zip(group, to_out_sr(wavs))):
             os.makedirs(os.path.dirname(it['wav']), exist_ok=True)
             write_wav(it['wav'], w, out_rate())
-            if stats is not None:                             # what was spoken: the codewords of the file's units
+            if vq:
+                write_indices(os.path.splitext(it['wav'])[0] + '.idx.txt', units[it['file']])
+            elif stats is not None:                           # what was spoken: the codewords of the file's units
                 txt = os.path.splitext(it['wav'])[0] + '.txt'
                 write_encodings(txt, unpack_units(codebook.packed[res[2][i]], E))
                 write_indices(idx_path(txt), res[2][i])
             done.append(it)
 
     def enqueue(group):
+        if vq:
+            return group, synth_index_batch([units[it['file']] for it in group], trainer, seg_len, [speaker2id[it['target']] for it in group],
+                                            codebook, enc_only=enc_only, n_iter=n_iter, defer=True, momentum=momentum)
         return group, synth_units_batch([units[it['file']] for it in group], trainer, seg_len, [speaker2id[it['target']] for it in group],
                                         enc_only=enc_only, n_iter=n_iter, defer=True, momentum=momentum, packed=True, codebook=codebook,
                                         want_idx=codebook is not None)
@@ -1570,7 +1753,8 @@ def test_single(trainer, seg_len, speaker2id_path, result_dir, enc_only, s_speak
 
 def test_encode(trainer, seg_len, test_path, data_path, result_dir, flag='test', codebook=None):
     """convert.py:342-360.  codebook (not in the reference): every file's units are snapped to their codewords before they are
-    written, and each .txt gets a sibling .idx.txt with one codeword index per line."""
+    written, and each .txt gets a sibling .idx.txt with one codeword index per line.  Under a zs_amd.vq.VectorCodebook ('continues')
+    the .txt is written as without a codebook and the .idx.txt holds the nearest codeword of every encoded frame."""
     if codebook is not None:
         _check_codebook(codebook, trainer)
     files = sorted(glob.glob(os.path.join(test_path, '*.wav')))
@@ -1585,8 +1769,13 @@ def test_encode(trainer, seg_len, test_path, data_path, result_dir, flag='test',
                        utt_id=feed['utt_id'], result_dir=dir_path)
                 continue
             units = encode(f_h5[f"test/{feed['s_id']}/{feed['utt_id']}/lin"][()], trainer, seg_len, save=False)
-            idx, snapped = codebook.snap_host(pack_units(units))
             txt = os.path.join(dir_path, f"{feed['s_id']}_{feed['utt_id']}.txt")
+            if _is_vq(codebook):                              # 'continues': the .txt as without a codebook, the indices beside it
+                idx, _ = codebook.snap(torch.from_numpy(np.ascontiguousarray(units, dtype=np.float32)).to(trainer.device))
+                write_encodings(txt, units)
+                write_indices(idx_path(txt), idx.cpu().numpy())
+                continue
+            idx, snapped = codebook.snap_host(pack_units(units))
             write_encodings(txt, unpack_units(snapped, codebook.E))
             write_indices(idx_path(txt), idx)
 

@@ -301,6 +301,24 @@ class Decoder(ZsModule):
         cidx = c.detach().to(packed.device, torch.int64).contiguous()
         return bits, eng.forward(bits, cidx, self.training, lengths=lengths)
 
+    def forward_indices(self, idx, code, start, length, B, T0, c, bad, lengths=None):
+        """forward_rows() from codeword indices (zs_amd.vq): zs_vq_gather writes the chunk's operand [B, T0, c_in] from the codewords
+        code[idx[start[b]] .. idx[start[b] + length[b] - 1]] (idx int32 [n_idx], code fp32 [K, c_in], start int64 [B], length int32
+        [B], all on the device), zeros behind each fragment's rows; bad int32 [1] counts the indices outside [0, K).  The same
+        buffer, and then the same launches, as forward_rows."""
+        eng = self._engine()
+        ctx = eng.ctx
+        E = self.c_in
+        if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous():
+            raise ValueError('Decoder.forward_indices: idx must be contiguous int32 [n_idx]')
+        if code.dtype != torch.float32 or code.dim() != 2 or code.shape[1] != E or not code.is_contiguous():
+            raise ValueError('Decoder.forward_indices: code must be contiguous fp32 [K, %d]' % E)
+        bits = ctx.act('d_in_%d_%d_%d' % (eng.uid, B, T0), B, T0, E)
+        L.call('zs_vq_gather', 'ZsVqGather', ctx.stream, dtype=ctx.dt, idx=L.ptr(idx), n_idx=idx.numel(), code=L.ptr(code), ld_code=E,
+               K=code.shape[0], E=E, start=L.ptr(start), len=L.ptr(length), n_frag=B, T=T0, dst=bits.ptr(), ld_dst=bits.ld, bad=L.ptr(bad))
+        cidx = c.detach().to(idx.device, torch.int64).contiguous()
+        return bits, eng.forward(bits, cidx, self.training, lengths=lengths)
+
 
 class Spectrogram_Patcher(ZsModule):
     """model/model.py:505-549: the stage-2 generator of g_mode 'spectrogram', a post-filter on the decoder's output spectrogram
