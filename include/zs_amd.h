@@ -1216,6 +1216,77 @@ typedef struct {
 } ZsVqGather;
 int zs_vq_gather(const ZsVqGather* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Training through the vector codebook (zs_amd.vq_train): the straight-through quantiser between the 'continues' Encoder and
+ * the Decoder, its commitment term and the exponential moving average that moves the codebook after the encoder.  One training
+ * iteration is zs_vq_assign (above, unchanged) -> zs_vq_commit -> zs_vq_accum (above, unchanged) -> zs_vq_ema in the forward and
+ * zs_vq_st_bwd in the backward.  `code` fp32 [K][ld_code] and the limits on K, E, n and the leading dimensions are the vector
+ * codebook's (above).  A null struct, a K, E or n outside its range, a leading dimension below E, a null operand with work to do or a
+ * misaligned operand return ZS_EINVAL and launch nothing; n == 0 succeeds and launches nothing.  Caller-owned buffers, no allocation,
+ * no synchronisation, stream-ordered; no launch argument depends on the iteration, so a captured graph replays them.  No float
+ * atomics: every result is bitwise equal from run to run.
+ *
+ * zs_vq_commit: the Decoder's operand and the commitment loss.  z [n][ld_z] of `dtype` (the encoder's rows, read in place, any
+ * alignment of its element), idx int32 [n].  q [n][ld_q] of `dtype`, 16-byte aligned, ld_q a multiple of 8, written with 16-byte stores:
+ *   q[i][j]      = cast(code[idx[i]][j])   j < E (round to nearest even);   0 for E <= j < ld_q
+ *   z_f32[i][j]  = (float) z[i][j]         j < E      (fp32 [n][ld_zf], optional: the operand zs_vq_accum wants when z is bf16)
+ *   idx_acc[i]   = idx[i], or -1 when row i has an element that is not of magnitude < ZS_VQ_MAX_ABS (NaN included): zs_vq_accum
+ *                  then leaves the row out, so its int64 sums cannot overflow under vq_shift(n, ZS_VQ_MAX_ABS); *over += 1 for
+ *                  such a row.  (int32 [n], optional, must not overlap idx; over int32, optional)
+ *   *loss        = (float)(scale * sum_ij ((double) z[i][j] - (double) code[idx[i]][j])^2)   (optional; needs partial)
+ * The sum: every lane adds its terms in double in a fixed order, a workgroup's lanes are summed in a fixed tree into
+ * partial[workgroup] (double [ZS_VQ_COMMIT_PARTS]) and a second launch of one workgroup adds the partials in a fixed order.
+ * An idx[i] outside [0, K) is never used as an index: q[i] is a zero row, the row is left out of the loss, idx_acc[i] = -1 and
+ * *bad += 1 (int32, required).  A row is owned by a team of 2^t <= 64 lanes of one wave, one 16-byte piece of q per lane and round. */
+#define ZS_VQ_COMMIT_PARTS 1024
+#define ZS_VQ_MAX_ABS 65536
+typedef struct {
+  int32_t dtype;
+  const void* z; int64_t n, ld_z;
+  const int32_t* idx;
+  const float* code; int64_t ld_code; int32_t K, E;
+  void* q; int64_t ld_q;
+  float* z_f32; int64_t ld_zf;
+  int32_t* idx_acc;
+  double scale; double* partial; float* loss;
+  int32_t* bad; int32_t* over;
+} ZsVqCommit;
+int zs_vq_commit(const ZsVqCommit* p, void* stream);
+/* zs_vq_st_bwd: the straight-through gradient plus the commitment term's.  dq, dz [n][ld] of `dtype`, 16-byte aligned, both leading
+ * dimensions multiples of 8; z [n][ld_z] of `dtype`; g fp32 (2 beta / (n E), rounded once by the caller):
+ *   dz[i][j] = cast(dq[i][j] + g * (z[i][j] - code[idx[i]][j]))   j < E;    0 for E <= j < ld_dz
+ * The subtraction, the product and the sum are three fp32 operations, each rounded once (no fused multiply-add), then one cast.
+ * dz == dq (with ld_dz == ld_dq) updates in place; any other overlap is undefined.  The codeword row is read again, so the forward
+ * keeps no residual.  An idx[i] outside [0, K) is never used as an index: dz[i] = dq[i] and *bad += 1 (int32, required). */
+typedef struct {
+  int32_t dtype;
+  const void* dq; int64_t n, ld_dq;
+  const void* z; int64_t ld_z;
+  const int32_t* idx;
+  const float* code; int64_t ld_code; int32_t K, E;
+  float g;
+  void* dz; int64_t ld_dz;
+  int32_t* bad;
+} ZsVqStBwd;
+int zs_vq_st_bwd(const ZsVqStBwd* p, void* stream);
+/* zs_vq_ema: the codebook follows the encoder.  cnt int32 [K] and sum int64 [K][E] as zs_vq_accum left them (shift: its shift);
+ * N fp32 [K], m fp32 [K][E] dense; decay a double in [0, 1).  For every k, in IEEE double with one rounding per stored fp32:
+ *   N[k]       = (float)(decay N[k]    + (1 - decay) cnt[k])
+ *   m[k][j]    = (float)(decay m[k][j] + (1 - decay) (double) sum[k][j] 2^-shift)
+ *   code[k][j] = (float)((double) m[k][j] / (double) N[k])      when the new N[k] >= 1e-3; else the row stays as it is
+ * (no fused multiply-add; int64 -> double to nearest even; 1 - decay in double).  cnorm[k] is rewritten for EVERY k exactly as
+ * zs_vq_update writes it: lane t of 256 adds code[k][j]^2, j = t, t + 256, .., in double, the 64 lanes of a wave are added
+ * pairwise at distances 32, 16, .., 1, and the four waves' sums left to right.  *used += #{k : cnt[k] > 0} (int32, optional).
+ * Nothing is summed across k.  One workgroup per codeword. */
+typedef struct {
+  const int32_t* cnt; const int64_t* sum; int32_t K, E, shift;
+  double decay;
+  float* N; float* m;
+  float* code; int64_t ld_code; float* cnorm;
+  int32_t* used;
+} ZsVqEma;
+int zs_vq_ema(const ZsVqEma* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,15 @@ enc_mode must agree:
   python main.py --enc_mode continues --convert_dir in/ --t_speaker V001 --ckpt_pth CKPT --codebook ckpt_english/codebooks/K1024.vq.npz
   python main.py --enc_mode continues --synth_dir idx/ --t_speaker V001 --ckpt_pth CKPT --codebook ckpt_english/codebooks/K1024.vq.npz
 
+--vq_train FILE.vq.npz with --train_ae and --enc_mode continues (zs_amd.vq_train): the autoencoder is trained through that vector
+codebook -- every encoder row of a batch is snapped to its nearest codeword in front of the Decoder, whose input gradient passes
+straight through; --vq_beta B (default 0.25, in (0, 10]) weighs the commitment term that keeps the encoder near its codewords, and the
+codebook follows the encoder by an exponential moving average of decay --vq_decay D (default 0.99, in [0, 1)).  The log gains loss_vq,
+the share of codewords used and the perplexity; every checkpoint gets <checkpoint>.vq.npz beside it, the file --codebook reads.
+--ema, --device_data and --load_model combine with it; --resume, --valid_every, a multi-rank launch and every other --train* mode are
+refused before anything is built:
+  python main.py --enc_mode continues --train_ae --load_model --vq_train ckpt_english/codebooks/K1024.vq.npz
+
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
 (--train_al, --train_t, --encode, --test_asr) are not part of this build and exit with a clear error.
@@ -248,6 +257,13 @@ def build_parser():
     p.add_argument('--codebook', type=str, default=None, metavar='FILE',
                    help='with --convert_dir / --synth_dir / --test_encode: snap every unit to its nearest codeword of this codebook; a '
                         "vector codebook (FILE.vq.npz, enc_mode 'continues') writes <name>.idx.txt index files, and --synth_dir reads them")
+    p.add_argument('--vq_train', type=str, default=None, metavar='FILE',
+                   help="with --train_ae and enc_mode 'continues': train through the vector codebook FILE.vq.npz (straight-through "
+                        'quantiser, commitment term, codebook by exponential moving average); every checkpoint gets a '
+                        '<checkpoint>.vq.npz beside it, the file --codebook reads')
+    p.add_argument('--vq_beta', type=float, default=None, metavar='B', help='with --vq_train: commitment weight in (0, 10] (default 0.25)')
+    p.add_argument('--vq_decay', type=float, default=None, metavar='D',
+                   help="with --vq_train: decay of the codebook's moving average in [0, 1) (default 0.99)")
     p.add_argument('--out_sr', type=_out_sr, default=None,
                    help='sample rate of the wavs --test / --cross_test / --test_single write (hp.out_sr); default: 16000')
     return p
@@ -373,6 +389,16 @@ def check_codebook(parser, args):
         parser.error('--codebook uses a codebook and --fit_codebook writes one: run them as two commands')
 
 
+def check_vq_train(args, enc_mode=None, c_in=None):
+    """--vq_train, --vq_beta and --vq_decay are refused, before anything is built, where they cannot do what they say
+    (zs_amd.vq_train.check_vq_train): without --train_ae or beside another --train* mode, under a multi-rank launch, with --resume
+    or --valid_every, the two options without --vq_train or out of range; and, once enc_mode is known (argument_runner calls
+    this again after reading hps), an enc_mode other than 'continues', a bit codebook or a width other than the Decoder's c_in.
+    Returns the loaded codebook on that second call (None without --vq_train)."""
+    from zs_amd.vq_train import check_vq_train as check
+    return check(args, enc_mode, c_in)
+
+
 def convert_targets(args):
     """--convert_dir and --synth_dir take --t_speaker as a comma-separated list of distinct names (--test_single keeps the single name): the
     list, refused before anything is built when it names no speaker or one twice."""
@@ -394,7 +420,8 @@ def argument_runner(argv=None):
     check_voice(args)
     from zs_amd.validation import check_flags
     check_flags(args)
-    args.t_speakers = convert_targets(args) if (args.convert_dir is not None or args.synth_dir is not None) else None
+    check_vq_train(args)
+    args.t_speakers =convert_targets(args) if (args.convert_dir is not None or args.synth_dir is not None) else None
     if args.dataset == 'surprise':            # main.py:83-88: english -> surprise in every default path
         for action in parser._actions:
             if isinstance(action.default, str) and 'english' in action.default and \
@@ -414,6 +441,7 @@ def argument_runner(argv=None):
     if args.enc_mode == 'set_from_hps':
         args.enc_mode = hps.enc_mode
     check_voice(args)                         # again, now that enc_mode is known
+    args.vq_codebook = check_vq_train(args, args.enc_mode, hps.enc_size)      # (the file is read here: a bit codebook or another width)
     print('[Runner] - Generation mode: ', 'autoencoder only' if args.enc_only else 'with generator')
     print('[Runner] - Generator mode: ', args.g_mode)
     print('[Runner] - Encoder mode: ', args.enc_mode)
@@ -487,7 +515,12 @@ def main(argv=None):
         data_loader, source_loader, target_loader = mk(dataset), mk(sourceset), mk(targetset)
         os.makedirs(args.ckpt_dir, exist_ok=True)
         model_path = os.path.join(args.ckpt_dir, args.model_name)
-        trainer = Trainer(hps, data_loader, args.g_mode, args.enc_mode, dtype=args.dtype, ema=args.ema, valid=valid)
+        vq_train = None
+        if args.vq_codebook is not None:                  # --vq_train: the --train_ae loop runs through this codebook (zs_amd.vq_train)
+            from zs_amd.vq_train import BETA, DECAY
+            vq_train = (args.vq_codebook, args.vq_beta if args.vq_beta is not None else BETA,
+                        args.vq_decay if args.vq_decay is not None else DECAY)
+        trainer = Trainer(hps, data_loader, args.g_mode, args.enc_mode, dtype=args.dtype, ema=args.ema, valid=valid, vq_train=vq_train)
         if args.load_model:
             trainer.load_model(os.path.join(args.ckpt_dir, args.load_train_model_name), load_model_list=hps.load_model_list,
                                use_ema=args.use_ema)

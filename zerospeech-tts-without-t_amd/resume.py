@@ -118,11 +118,11 @@ def roll_window(model_kept, new_path, max_keep):
 
 
 def remove_checkpoint(path):
-    """Remove a checkpoint file and, where there is one, its state file."""
+    """Remove a checkpoint file and, where there is one, its state file and the codebook --vq_train wrote beside it."""
     os.remove(path)
-    side = state_path(path)
-    if os.path.exists(side):
-        os.remove(side)
+    for side in (state_path(path), path + '.vq.npz'):
+        if os.path.exists(side):
+            os.remove(side)
 
 
 def map_tensors(tree, fn):

@@ -45,8 +45,11 @@ class AEStep(object):
     optimizer), with the RCCL all-reduces of the gradient buckets launched eagerly between them, each as soon as its bucket is
     final."""
 
-    def __init__(self, encoder, decoder, lr=1e-4, betas=(0.5, 0.9), max_grad_norm=5.0, use_graph=None, ema=None):
+    def __init__(self, encoder, decoder, lr=1e-4, betas=(0.5, 0.9), max_grad_norm=5.0, use_graph=None, ema=None, vq=None):
+        """vq (not in the reference): None, or a vq_train.VqBottleneck: the step then quantises the encoder's rows in front of the
+        Decoder and hands the Decoder's input gradient through it; its loss_vq stays beside loss_rec, in vq.loss."""
         self.Encoder, self.Decoder = encoder, decoder
+        self.vq = vq
         self.adam_step = 0                   # the pair's Adam step count (on the device: _step_dev)
         self.opt = {name: NetOpt(net, lr, betas, max_grad_norm, reduce=False, ema=ema)      # ema: a weight average per net (NetOpt)
                     for name, net in (('enc', encoder), ('dec', decoder))}
@@ -115,6 +118,9 @@ class AEStep(object):
         streams) are done, so with layers.MULTI_STREAM its clip + Adam + re-pack run on a third stream under the encoder's backward."""
         enc, dec = self.Encoder, self.Decoder
         dev = self.device
+        vq = self.vq
+        if vq is not None and multi:
+            raise ValueError("AEStep: the vector-codebook bottleneck runs on one rank (its counts and sums would need an all-reduce)")
         if counted:
             seed = parallel.rank()
         seed_ptr = L.ptr(self._seed_dev) if counted else None
@@ -128,6 +134,8 @@ class AEStep(object):
             ee, de = enc._engine(), dec._engine()
             bits, _, _ = ee.forward(x_btf, True, noise=noise, noise_kind=noise_kind, seed=seed, drop_masks=drop_masks,
                                     seed_ptr=seed_ptr)
+            if vq is not None:
+                bits = vq.forward(bits)                                                   # the Decoder reads the codewords
             return self.l1_loss(de, x_btf, de.forward(bits, c, True))
 
         def update(name):
@@ -174,7 +182,7 @@ class AEStep(object):
                 self.opt['dec'].device_step(L.ptr(self._step_dev))
 
         def enc_bwd():
-            enc._engine().backward(st['dbits'])
+            enc._engine().backward(st['dbits'] if vq is None else vq.backward(st['dbits']))
             join_side(dev)
 
         def join_dec_update():
@@ -670,16 +678,25 @@ class Trainer(object):
     ema = None                             # the decay of the weight averages (__init__ sets it; the default serves a Trainer made without it)
 
     valid = None                           # the ValidConfig of the held-out validation (__init__ sets it)
+    vq = None                              # the vq_train.VqBottleneck of a run that trains through its codebook (build_model sets it)
+    vq_train = None
     _best_due = False
 
-    def __init__(self, hps, data_loader, g_mode, enc_mode, log_dir='./log/', dtype=None, device=None, ema=None, valid=None):
-        """valid (not in the reference): None, or a validation.ValidConfig: train(mode='pretrain_AE') then validates on its set
+    def __init__(self, hps, data_loader, g_mode, enc_mode, log_dir='./log/', dtype=None, device=None, ema=None, valid=None,
+                 vq_train=None):
+        """vq_train (not in the reference): None, or (vq.VectorCodebook, beta, decay): train(mode='pretrain_AE') then trains through
+        that codebook (vq_train.VqBottleneck inside the AEStep), logs loss_vq, the codewords used and the perplexity, and
+        writes <checkpoint>.vq.npz beside every checkpoint.  Every other mode runs without the quantiser.
+        valid (not in the reference): None, or a validation.ValidConfig: train(mode='pretrain_AE') then validates on its set
         every `every` iterations and after the last one (ValidStep), logs and records the result and keeps the best checkpoint.
         ema (not in the reference): None, or the decay in [0, 1) of an exponential moving average of the weights that every
         optimizer this trainer builds keeps beside its net (optim.NetOpt); the checkpoints then carry `<net>_ema` entries."""
         self.hps = hps
         self.ema = check_ema(ema)
         self.valid = validation.check_config(valid, hps) if valid is not None else None
+        self.vq_train = vq_train
+        if vq_train is not None and enc_mode != 'continues':
+            raise ValueError("vq_train needs enc_mode 'continues': this model's enc_mode is %r" % enc_mode)
         self._vstep = None                                                 # ValidStep, built on first use
         self.best_loss = self.best_iteration = None                        # the lowest valid_loss_rec so far and its iteration
         self._best_due = False                                             # the next periodic resumable checkpoint also writes -ae-best
@@ -735,6 +752,11 @@ class Trainer(object):
                                                      seg_len=hps.seg_len, dtype=dt).to(dev)
         self.TargetClassifier = TargetClassifier(ns=ns, n_class=3, seg_len=hps.seg_len, dtype=dt).to(dev)
         self.ae = AEStep(self.Encoder, self.Decoder, lr=hps.lr, betas=(0.5, 0.9), max_grad_norm=hps.max_grad_norm, ema=self.ema)
+        if self.vq_train is not None:                   # the --train_ae loop alone: train() hands it to the AEStep for that mode
+            from .vq_train import VqBottleneck, encoded_rows
+            cb, beta, decay = self.vq_train
+            cb.check_width(hps.enc_size, 'vq_train')
+            self.vq = VqBottleneck(cb, beta, decay, encoded_rows(hps.batch_size, hps.seg_len), layers.Ctx(dev, dt))
         self.clf = ClfStep(self.ae, self.SpeakerClassifier, lr=hps.lr, betas=(0.5, 0.9), max_grad_norm=hps.max_grad_norm, ema=self.ema)
         self.s2 = None                      # PatchGANStep, built on first use (its optimizer state is 2 x 53 M floats)
         self.source_loader = self.target_loader = None
@@ -1158,9 +1180,10 @@ class Trainer(object):
                 for tag, value in info.items():
                     self.logger.scalar_summary(tag, value, iteration + 1)
 
-    def _loop(self, iters, model_path, ckpt_name, iteration_fn, start=0, keep_state=None):
+    def _loop(self, iters, model_path, ckpt_name, iteration_fn, start=0, keep_state=None, after_save=None):
         """The loop of every mode: iteration_fn(iteration, log) runs one iteration, log = self._log bound to it at a logged
-        iteration (every log_every-th and the last) and None otherwise; rank 0 saves a checkpoint every ckpt_every iterations.
+        iteration (every log_every-th and the last) and None otherwise; rank 0 saves a checkpoint every ckpt_every iterations
+        and then calls after_save(checkpoint path, iteration), when given.
         start: the first iteration (a resumed run).  keep_state: None, or (target_guided, autolocker) of a resumable run: its
         checkpoints carry a train-state file and are written by a worker thread (_checkpoint_async), which is waited for before
         this returns and when an exception leaves the loop."""
@@ -1176,6 +1199,8 @@ class Trainer(object):
                         self._checkpoint_async(model_path, ckpt_name, iteration + 1, *keep_state)
                     else:
                         self.save_model(model_path, ckpt_name, iteration + 1)
+                    if after_save is not None:
+                        after_save('{}-{}-{}'.format(model_path, ckpt_name, iteration + 1), iteration + 1)
                 if keep_state is not None and self._writer is not None:
                     self._writer.poll()                                                   # a failed write raises at once
         except BaseException:
@@ -1288,11 +1313,37 @@ class Trainer(object):
                 else:
                     c, x = self._batch()
                     loss_t = self.ae_step(x, c)
-                if log:
+                if log and bn is not None:
+                    info = {f'{flag}/pre_loss_rec': loss_t.item()}                             # (the host sync)
+                    s = bn.stats()                                                             # raises for a row left out of the average
+                    info.update({f'{flag}/pre_loss_vq': s['loss_vq'], f'{flag}/vq_used': s['used'] / float(s['K']),
+                                 f'{flag}/vq_perplexity': s['perplexity']})
+                    log('pre_AE:[%06d/%06d], loss_rec=%.3f, loss_vq=%.4f, used=%.3f, perplexity=%.1f', info)
+                elif log:
                     log('pre_AE:[%06d/%06d], loss_rec=%.3f', {f'{flag}/pre_loss_rec': loss_t.item()})    # the only host sync
                 if vcfg is not None and ((iteration + 1) % vcfg.every == 0 or iteration + 1 == iters):
                     self.validate(iteration + 1, model_path, flag, keep_state)                 # before this iteration's checkpoint
-            self._loop(hps.enc_pretrain_iters, model_path, 'ae', iteration_fn, start, keep_state)
+
+            def save_codebook(path, iteration):
+                """<checkpoint>.vq.npz beside the checkpoint: the file --codebook reads (vq.VectorCodebook.save, format unchanged)."""
+                s = bn.stats()
+                bn.to_codebook({'trained_iterations': int(iteration), 'beta': bn.beta, 'decay': bn.decay, 'used': s['used']}).save(
+                    ckpt_path(path))
+
+            bn = self.vq
+            if bn is not None:
+                from .vq_train import ckpt_path
+                if resumable or vcfg is not None or parallel.multi_rank():
+                    raise ValueError('vq_train cannot be combined with resume, validation or several ranks')
+                self.ae.vq = bn
+                self.ae._graphs.clear()                                                        # (a step captured without the quantiser)
+            try:
+                self._loop(hps.enc_pretrain_iters, model_path, 'ae', iteration_fn, start, keep_state,
+                           after_save=(save_codebook if bn is not None else None))
+            finally:
+                if bn is not None:
+                    self.ae.vq = None
+                    self.ae._graphs.clear()
         elif mode == 'pretrain_C':                                                        # trainer.py:349-382
             start = begin(hps.dis_pretrain_iters)
             if start is None:
