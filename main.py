@@ -553,16 +553,15 @@ def main(argv=None):
                     iters=(args.adapt_iters if args.adapt_iters is not None else voice.ADAPT_ITERS), init=args.adapt_init,
                     lr=args.adapt_lr)
 
-    if args.fit_codebook is not None:                     # not in the reference: a unit codebook over a folder (zs_amd.codebook)
-        from zs_amd import codebook as zcb
+    if args.fit_codebook is not None:                     # not in the reference: a codebook over a folder (zs_amd.codebook, zs_amd.vq)
+        from zs_amd.vq import kind_for                    # the model's enc_mode chooses the kind: bits (k-modes) or vectors (k-means)
         model_path = args.ckpt_pth if args.ckpt_pth is not None else os.path.join(args.ckpt_dir, args.load_test_model_name)
         trainer = get_trainer(args.hps_path, model_path, args.g_mode, args.enc_mode, use_ema=args.use_ema)
-        if trainer.enc_mode == 'continues':               # real-valued encodings: a vector codebook, k-means (zs_amd.vq)
-            from zs_amd import vq as zcb
-        zcb.fit_dir(trainer, hps.seg_len, args.fit_dir, args.fit_codebook,
-                    args.codebook_out if args.codebook_out is not None else zcb.default_path(args.ckpt_dir, args.fit_codebook),
-                    iters=(args.codebook_iters if args.codebook_iters is not None else CODEBOOK_ITERS),
-                    seed=(args.codebook_seed if args.codebook_seed is not None else 0))
+        kind = kind_for(trainer.enc_mode)
+        kind.fit_dir(trainer, hps.seg_len, args.fit_dir, args.fit_codebook,
+                     args.codebook_out if args.codebook_out is not None else kind.default_path(args.ckpt_dir, args.fit_codebook),
+                     iters=(args.codebook_iters if args.codebook_iters is not None else CODEBOOK_ITERS),
+                     seed=(args.codebook_seed if args.codebook_seed is not None else 0))
 
     if args.test or args.cross_test or args.test_encode or args.test_single or args.test_classify or args.convert_dir is not None or \
             args.synth_dir is not None:

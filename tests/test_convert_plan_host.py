@@ -1,6 +1,6 @@
 """The plans of batched conversion without a GPU: the index tables _enqueue_encode, _gather_decoded and synth_units_batch upload are
 built by host functions that return numpy arrays (convert._scatter_tables, _pack_tables, _dense_tables, _gather_index, _unit_tables,
-all on convert._fragment_layout).  An off-by-one here is an out-of-bounds write on the device, so every table is checked against
+all on convert._fragment_layout, and _vq_index_map on _pack_tables).  An off-by-one here is an out-of-bounds write on the device, so every table is checked against
 values derived from fragments(), _t8 and the per-utterance rule of convert() alone."""
 import os
 import sys
@@ -128,6 +128,28 @@ def test_pack_tables(max_batch):
     order = np.argsort(starts)
     assert starts[order][0] == 0 and np.array_equal((starts + lens)[order][:-1], starts[order][1:])      # no gap, no overlap
     assert (starts + lens)[order][-1] == uoffs[-1]
+
+
+@pytest.mark.parametrize('max_batch', MAX_BATCH)
+def test_vq_index_map(max_batch):
+    """The table that gives every returned unit of a vector-codebook batch its index: src[uoffs[u]:uoffs[u + 1]] are the rows of the
+    chunks' index buffers (chunk by chunk, len(chunk) x _t8(longest member) rows each) that hold utterance u's frames."""
+    _, chunks = _frame_chunks(max_batch)
+    uoffs, src = cv._vq_index_map(chunks, len(FRAMES))
+    assert np.array_equal(uoffs, cv._pack_tables(chunks, len(FRAMES))[0]) and uoffs.dtype == np.int64
+    assert src.dtype == np.int64 and src.shape == (uoffs[-1],)
+    label, base = {}, 0                                              # every row of the buffers, end to end: (utterance, fragment, frame)
+    for chunk, _ in chunks:
+        Tp = cv._t8(max(b - a for a, b in (RULE[it.u][it.k] for it in chunk)))
+        for i, it in enumerate(chunk):
+            label.update({base + i * Tp + t: (it.u, it.k, t) for t in range(Tp)})
+        base += len(chunk) * Tp
+    assert src.min() >= 0 and src.max() < base and len(set(src.tolist())) == len(src)          # inside the buffers, no index twice
+    want = [[cv._t8(b - a) for a, b in frs] for frs in RULE]
+    want[0] = [cv.MIN_LEN // 8]                                      # the 5-frame utterance: the truncation of convert()
+    assert FRAMES[0] < cv.MIN_LEN
+    for u, counts in enumerate(want):                                # exactly the frames of utterance u, in fragment order
+        assert [label[r] for r in src[uoffs[u]:uoffs[u + 1]]] == [(u, k, t) for k, n in enumerate(counts) for t in range(n)]
 
 
 @pytest.mark.parametrize('max_batch', MAX_BATCH)

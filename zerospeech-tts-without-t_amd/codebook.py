@@ -77,9 +77,150 @@ def usage_counts(counts):
     return int(len(p)), float(max(0.0, -(p * np.log2(p)).sum()))
 
 
-class Codebook(object):
+def read_npz(path):
+    """The fields of a codebook file of either kind; ValueError for anything numpy cannot read as one."""
+    try:
+        z = np.load(path, allow_pickle=False)
+        return {k: z[k] for k in z.files}
+    except Exception as e:
+        raise ValueError('%s is not a codebook file: %s' % (path, e))
+
+
+def reseed_rows(cnt, dist):
+    """(the empty k in increasing order, the rows they take): the rows of largest dist, ties to the lowest row, each row once."""
+    empties = np.flatnonzero(np.asarray(cnt) == 0)
+    order = np.argsort(-np.asarray(dist, dtype=np.float64), kind='stable')[:len(empties)]
+    return empties, order
+
+
+def first_distinct(n, K, seed, rows_at, nouns):
+    """The walk of both init_rows: numpy.random.RandomState(seed).permutation(n) in growing slices, the first K indices whose rows
+    are pairwise different.  rows_at(sel) -> the host rows of the indices sel, compared by their bytes; nouns: what the error calls
+    the input and a row of it."""
+    K = int(K)
+    perm = np.random.RandomState(seed).permutation(n)
+    seen, out, at, step = set(), [], 0, max(4096, 4 * K)
+    while at < n:
+        sel = perm[at:at + step]
+        for i, r in zip(sel, rows_at(sel)):
+            key = r.tobytes()
+            if key not in seen:
+                seen.add(key)
+                out.append(int(i))
+                if len(out) == K:
+                    return np.asarray(out, dtype=np.int64)
+        at += step
+        step *= 4
+    raise ValueError('init_rows: the %s hold %d distinct %s, fewer than K = %d' % (nouns[0], len(seen), nouns[1], K))
+
+
+class CodebookFile(object):
+    """What the two kinds of codebook share: the file (fields format_version, K, E, meta and the kind's payload; `kind` where the
+    kind has one), the width check, the per-device upload and the fit over a folder.  A kind supplies `label` (what messages call
+    it), `payload` (the field and attribute of its codewords), `_from_payload` (the check of that payload: its constructor) and
+    what fit_dir names below."""
+    kind = None
+
+    def save(self, path):
+        fields = {'kind': np.array(self.kind)} if self.kind else {}              # in the order the file lists them
+        fields.update(format_version=np.int64(FORMAT_VERSION), K=np.int64(self.K), E=np.int64(self.E))
+        fields[self.payload] = getattr(self, self.payload)
+        fields['meta'] = np.array(json.dumps(self.meta))
+        with open(path, 'wb') as f:
+            np.savez(f, **fields)
+
+    @classmethod
+    def load(cls, path, E=None):
+        """ValueError naming the field for a malformed file, and for a width other than E (the Decoder's c_in) when E is given."""
+        return cls.from_fields(read_npz(path), path, E)
+
+    @classmethod
+    def from_fields(cls, d, path, E=None):
+        """load() of fields already read (read_npz)."""
+        where = '%s: %s field' % (path, cls.label)
+        for k in (('kind',) if cls.kind else ()) + ('format_version', 'K', 'E', cls.payload, 'meta'):
+            if k not in d:
+                raise ValueError('%s %r is missing' % (where, k))
+        if cls.kind and (d['kind'].shape != () or d['kind'].dtype.kind != 'U' or str(d['kind']) != cls.kind):
+            raise ValueError("%s kind must be '%s'" % (where, cls.kind))
+        for k in ('format_version', 'K', 'E'):
+            if d[k].shape != () or d[k].dtype.kind not in 'iu':
+                raise ValueError('%s %r must be one integer' % (where, k))
+        if int(d['format_version']) != FORMAT_VERSION:
+            raise ValueError('%s format_version is %d, this build reads %d' % (where, int(d['format_version']), FORMAT_VERSION))
+        try:
+            meta = json.loads(str(d['meta']))
+            if not isinstance(meta, dict):
+                raise ValueError('not an object')
+        except ValueError as e:
+            raise ValueError('%s meta is not a json object (%s)' % (where, e))
+        try:
+            cb = cls._from_payload(d[cls.payload], int(d['E']), meta)
+        except ValueError as e:
+            raise ValueError('%s %s: %s' % (where, cls._payload_error, e))
+        if cb.K != int(d['K']):
+            raise ValueError('%s K is %d but %s has %d rows' % (where, int(d['K']), cls.payload, cb.K))
+        if cb.E != int(d['E']):
+            raise ValueError('%s E is %d but %s has %d columns' % (where, int(d['E']), cls.payload, cb.E))
+        if E is not None:
+            cb.check_width(E, path)
+        return cb
+
+    def check_width(self, E, where='codebook'):
+        if int(E) != self.E:
+            raise ValueError("%s: codebook field E is %d, the Decoder's input width (c_in) is %d" % (where, self.E, int(E)))
+
+    def to(self, dev):
+        """The codewords on the device (what the kind's _upload gives), uploaded once."""
+        dev = torch.device(dev)
+        t = self._dev.get(dev)
+        if t is None:
+            t = self._dev[dev] = self._upload(dev)
+        return t
+
+    @classmethod
+    def default_path(cls, ckpt_dir, K):
+        import os
+        return os.path.join(ckpt_dir, 'codebooks', 'K%d.%s' % (int(K), cls.suffix))
+
+    @classmethod
+    def fit_dir(cls, trainer, seg_len, in_dir, K, out_path, iters, seed=0, batch=64):
+        """--fit_codebook: a codebook of this kind of K codewords over a folder.  The kind's _dir_rows reads and encodes the folder
+        (-> files used, files skipped, device tensors of rows), its _fit clusters them and its _indices gives the final assignment.
+        Writes the codebook to out_path and fit_codebook.json beside it (files used and skipped, n_units, the history, symbols used
+        and the entropy of the final assignment); returns (the codebook, that report)."""
+        import os
+        cls.check_mode(trainer.enc_mode)
+        K = int(K)
+        if not 1 <= K <= MAX_K:
+            raise ValueError('--fit_codebook: K must be in [1, %d] (got %d)' % (MAX_K, K))
+        E = int(trainer.Decoder.c_in)
+        used, skipped, parts = cls._dir_rows(trainer, seg_len, in_dir, batch, E)
+        if not parts:
+            raise ValueError('--fit_codebook: %s holds no usable %s' % (in_dir, cls._dir_files))
+        rows_dev = torch.cat(parts, dim=0).contiguous()
+        cb = cls._fit(rows_dev, K, iters, seed, E, trainer.enc_mode)
+        cb.check_width(E, out_path)
+        n_used, entropy = usage(cb._indices(rows_dev), K)
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        cb.save(out_path)
+        report = {'codebook': out_path}
+        if cls.kind:
+            report['kind'] = cls.kind
+        report.update({'K': K, 'E': E, 'in_dir': in_dir, 'files': used, 'skipped': skipped, 'n_units': int(rows_dev.shape[0]),
+                       'seed': int(seed), 'history': cb.meta['history'], 'symbols_used': n_used, 'entropy_bits_per_unit': entropy})
+        with open(os.path.join(os.path.dirname(os.path.abspath(out_path)), 'fit_codebook.json'), 'w') as f:
+            json.dump(report, f, indent=1)
+        print(cls._fit_line % (K, rows_dev.shape[0], len(used), len(cb.meta['history']), cb.meta['history'][-1][0], n_used, entropy, out_path))
+        return cb, report
+
+
+class Codebook(CodebookFile):
     """K codewords of E bits: `packed` uint8 [K, (E + 7) // 8] on the host (bits at columns >= E zero), and `meta`: enc_mode, n_units,
     seed and the per-iteration history [(total distance, changed, empties)] of the fit."""
+    label, payload, suffix, _payload_error = 'codebook', 'packed', 'codebook.npz', 'packed / E'
+    _dir_files = '*.wav or *.txt unit file'
+    _fit_line = '[Codebook] - K = %d over %d units of %d files: %d iterations, total distance %d, %d symbols used, %.3f bits per unit -> %s'
 
     def __init__(self, packed, E, meta=None):
         E = int(E)
@@ -95,53 +236,47 @@ class Codebook(object):
         self.K, self.E, self.packed, self.meta = int(p.shape[0]), E, np.ascontiguousarray(p), dict(meta or {})
         self._dev = {}
 
-    def save(self, path):
-        with open(path, 'wb') as f:
-            np.savez(f, format_version=np.int64(FORMAT_VERSION), K=np.int64(self.K), E=np.int64(self.E), packed=self.packed,
-                     meta=np.array(json.dumps(self.meta)))
+    @classmethod
+    def _from_payload(cls, packed, E, meta):
+        return cls(packed, E, meta)
+
+    check_mode = staticmethod(refuse_continues)               # a bit codebook serves every enc_mode but 'continues'
+
+    def _upload(self, dev):
+        return torch.from_numpy(self.packed).to(dev)
 
     @classmethod
-    def load(cls, path, E=None):
-        """ValueError naming the field for a malformed file, and for a width other than E (the Decoder's c_in) when E is given."""
-        try:
-            z = np.load(path, allow_pickle=False)
-            d = {k: z[k] for k in z.files}
-        except Exception as e:
-            raise ValueError('%s is not a codebook file: %s' % (path, e))
-        for k in ('format_version', 'K', 'E', 'packed', 'meta'):
-            if k not in d:
-                raise ValueError('%s: codebook field %r is missing' % (path, k))
-        for k in ('format_version', 'K', 'E'):
-            if d[k].shape != () or d[k].dtype.kind not in 'iu':
-                raise ValueError('%s: codebook field %r must be one integer' % (path, k))
-        if int(d['format_version']) != FORMAT_VERSION:
-            raise ValueError('%s: codebook field format_version is %d, this build reads %d' % (path, int(d['format_version']), FORMAT_VERSION))
-        try:
-            meta = json.loads(str(d['meta']))
-            if not isinstance(meta, dict):
-                raise ValueError('not an object')
-        except ValueError as e:
-            raise ValueError('%s: codebook field meta is not a json object (%s)' % (path, e))
-        try:
-            cb = cls(d['packed'], int(d['E']), meta)
-        except ValueError as e:
-            raise ValueError('%s: codebook field packed / E: %s' % (path, e))
-        if cb.K != int(d['K']):
-            raise ValueError('%s: codebook field K is %d but packed has %d rows' % (path, int(d['K']), cb.K))
-        if E is not None:
-            cb.check_width(E, path)
-        return cb
+    def _dir_rows(cls, trainer, seg_len, in_dir, batch, E):
+        """The *.wav of in_dir through encode_batch(packed=True) with the packed units left on the device, and the *.txt unit files
+        of in_dir (read_units) behind them."""
+        import glob
+        import os
+        from . import convert as cv
+        used, skipped, parts, skip = encode_dir(trainer, seg_len, in_dir, batch,
+                                                lambda specs: cv.encode_batch(specs, trainer, seg_len, packed=True, units_on_device=True)[0])
+        for path in sorted(glob.glob(os.path.join(in_dir, '*.txt'))):
+            if path.endswith('.idx.txt'):
+                continue
+            try:
+                u = cv.pack_units(cv.read_units(path, E))
+            except (OSError, ValueError) as e:
+                skip(path, 'cannot be read: %s' % e)
+                continue
+            parts.append(torch.from_numpy(u).to(trainer.device))
+            used.append({'input': path, 'units': int(u.shape[0])})
+        return used, skipped, parts
 
-    def check_width(self, E, where='codebook'):
-        if int(E) != self.E:
-            raise ValueError("%s: codebook field E is %d, the Decoder's input width (c_in) is %d" % (where, self.E, int(E)))
+    @classmethod
+    def _fit(cls, units_dev, K, iters, seed, E, enc_mode):
+        return fit(units_dev, K, iters=iters, seed=seed, E=E, enc_mode=enc_mode)
 
-    def to(self, dev):
-        dev = torch.device(dev)
-        t = self._dev.get(dev)
-        if t is None:
-            t = self._dev[dev] = torch.from_numpy(self.packed).to(dev)
-        return t
+    def _indices(self, units_dev):
+        return self.snap(units_dev)[0]
+
+    def units(self):
+        """What batched conversion and the folder drivers do with units under this codebook (convert._BitUnits)."""
+        from .convert import _BitUnits
+        return _BitUnits(self)
 
     def snap_(self, units_dev, idx=None, dist=None, total=None):
         """Every row of units_dev replaced by its codeword, in place (one zs_code_assign on the current stream, no synchronisation)."""
@@ -175,27 +310,13 @@ def init_rows(packed, K, seed, E=None):
     whose rows are pairwise different (over the columns < E; E defaults to every bit of a row).  ValueError saying how many distinct
     rows there are when they are fewer than K.  packed: host array or device tensor [n, row_bytes]; of a device tensor only the
     rows looked at come to the host."""
-    n = int(packed.shape[0])
     E = 8 * int(packed.shape[1]) if E is None else int(E)
-    K = int(K)
-    perm = np.random.RandomState(seed).permutation(n)
-    seen, out, at, step = set(), [], 0, max(4096, 4 * K)
-    while at < n:
-        sel = perm[at:at + step]
+
+    def rows_at(sel):
         if torch.is_tensor(packed):
-            rows = _mask_rows(packed[torch.from_numpy(sel).to(packed.device)], E).cpu().numpy()
-        else:
-            rows = _mask_rows(np.asarray(packed)[sel], E)
-        for i, r in zip(sel, rows):
-            key = r.tobytes()
-            if key not in seen:
-                seen.add(key)
-                out.append(int(i))
-                if len(out) == K:
-                    return np.asarray(out, dtype=np.int64)
-        at += step
-        step *= 4
-    raise ValueError('init_rows: the units hold %d distinct rows, fewer than K = %d' % (len(seen), K))
+            return _mask_rows(packed[torch.from_numpy(sel).to(packed.device)], E).cpu().numpy()
+        return _mask_rows(np.asarray(packed)[sel], E)
+    return first_distinct(int(packed.shape[0]), K, seed, rows_at, ('units', 'rows'))
 
 
 def fit(units_dev, K, iters=20, seed=0, E=None, enc_mode='multilabel_binary', on_iter=None):
@@ -240,9 +361,8 @@ def fit(units_dev, K, iters=20, seed=0, E=None, enc_mode='multilabel_binary', on
         total, changed, bad, cnt = int(h[0:2].view(np.int64)[0]), int(h[2]), int(h[3]), h[4:]
         if bad:
             raise RuntimeError('fit: zs_code_assign gave %d indices outside [0, %d)' % (bad, K))
-        empties = np.flatnonzero(cnt == 0)
+        empties, order = reseed_rows(cnt, dist.cpu().numpy()) if (cnt == 0).any() else ((), ())
         if len(empties):
-            order = np.argsort(-dist.cpu().numpy().astype(np.int64), kind='stable')[:len(empties)]
             code[torch.from_numpy(empties).to(dev)] = _mask_rows(units_dev[torch.from_numpy(order).to(dev)], E)
             changed = int((code != start).any(dim=1).sum().item())
         if history and total > history[-1][0]:
@@ -257,36 +377,19 @@ def fit(units_dev, K, iters=20, seed=0, E=None, enc_mode='multilabel_binary', on
 
 def default_path(ckpt_dir, K):
     """{ckpt_dir}/codebooks/K<K>.codebook.npz"""
-    import os
-    return os.path.join(ckpt_dir, 'codebooks', 'K%d.codebook.npz' % int(K))
+    return Codebook.default_path(ckpt_dir, K)
 
 
 def encode_dir(trainer, seg_len, in_dir, batch, encode):
     """The *.wav of in_dir read and encoded as convert_dir reads them (any rate, the same trimming, the same skip list), in the groups
-    of convert_dir_plan; encode(specs) -> one device tensor of rows per utterance.  Shared by the two fit_dir (this module's and
-    zs_amd.vq's).  Returns (used [{'input', 'units'}], skipped [{'input', 'reason'}], the device tensors, skip(path, reason))."""
-    import glob
-    import os
+    of convert_dir_plan; encode(specs) -> one device tensor of rows per utterance.  What the _dir_rows of both kinds of
+    codebook read a folder with.  Returns (used [{'input', 'units'}], skipped [{'input', 'reason'}], the device tensors, skip(path, reason))."""
     from . import convert as cv
-    from .preprocess import read_wav, wav_info
+    from .preprocess import read_wav
     dev = trainer.device
-    used, skipped, parts = [], [], []
-
-    def skip(path, reason):
-        print('[Codebook] - skipped %s: %s' % (path, reason))
-        skipped.append({'input': path, 'reason': reason})
-
-    files, durations = [], []
-    for path in sorted(glob.glob(os.path.join(in_dir, '*.wav'))):
-        try:
-            sr, n = wav_info(path)
-            if sr <= 0:
-                raise ValueError('sample rate %d' % sr)
-        except (OSError, ValueError) as e:
-            skip(path, 'cannot be read: %s' % e)
-            continue
-        files.append(path)
-        durations.append(n / float(sr))
+    used, parts = [], []
+    skipped, skip = cv._skip_log('Codebook')
+    files, durations = cv._scan_wavs(in_dir, skip)
     plan = cv.convert_dir_plan(files, durations, ['-'], in_dir, batch=batch) if files else {'groups': [], 'skipped': []}
     for s in plan['skipped']:
         skip(s['file'], s['reason'])
@@ -316,43 +419,7 @@ def encode_dir(trainer, seg_len, in_dir, batch, encode):
 
 
 def fit_dir(trainer, seg_len, in_dir, K, out_path, iters=20, seed=0, batch=64):
-    """--fit_codebook: a codebook of K codewords over the units of a folder.  The *.wav of in_dir are read and encoded as convert_dir
-    reads them (any rate, the same trimming, the same skip list), in the groups of convert_dir_plan, through
-    encode_batch(packed=True) with the packed units left on the device; the *.txt unit files of in_dir (read_units) are added.
-    Writes the codebook to out_path and fit_codebook.json beside it (files used and skipped, n_units, the history, symbols used and
-    the entropy of the final assignment); returns (Codebook, that report)."""
-    import glob
-    import os
-    from . import convert as cv
-    refuse_continues(trainer.enc_mode)
-    K = int(K)
-    if not 1 <= K <= MAX_K:
-        raise ValueError('--fit_codebook: K must be in [1, %d] (got %d)' % (MAX_K, K))
-    E, dev = int(trainer.Decoder.c_in), trainer.device
-    used, skipped, parts, skip = encode_dir(trainer, seg_len, in_dir, batch,
-                                            lambda specs: cv.encode_batch(specs, trainer, seg_len, packed=True, units_on_device=True)[0])
-    for path in sorted(glob.glob(os.path.join(in_dir, '*.txt'))):
-        if path.endswith('.idx.txt'):
-            continue
-        try:
-            u = cv.pack_units(cv.read_units(path, E))
-        except (OSError, ValueError) as e:
-            skip(path, 'cannot be read: %s' % e)
-            continue
-        parts.append(torch.from_numpy(u).to(dev))
-        used.append({'input': path, 'units': int(u.shape[0])})
-    if not parts:
-        raise ValueError('--fit_codebook: %s holds no usable *.wav or *.txt unit file' % in_dir)
-    units_dev = torch.cat(parts, dim=0).contiguous()
-    cb = fit(units_dev, K, iters=iters, seed=seed, E=E, enc_mode=trainer.enc_mode)
-    idx, _ = cb.snap(units_dev)
-    n_used, entropy = usage(idx, K)
-    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-    cb.save(out_path)
-    report = {'codebook': out_path, 'K': K, 'E': E, 'in_dir': in_dir, 'files': used, 'skipped': skipped, 'n_units': int(units_dev.shape[0]),
-              'seed': int(seed), 'history': cb.meta['history'], 'symbols_used': n_used, 'entropy_bits_per_unit': entropy}
-    with open(os.path.join(os.path.dirname(os.path.abspath(out_path)), 'fit_codebook.json'), 'w') as f:
-        json.dump(report, f, indent=1)
-    print('[Codebook] - K = %d over %d units of %d files: %d iterations, total distance %d, %d symbols used, %.3f bits per unit -> %s' %
-          (K, units_dev.shape[0], len(used), len(cb.meta['history']), cb.meta['history'][-1][0], n_used, entropy, out_path))
-    return cb, report
+    """--fit_codebook: a codebook of K codewords over the units of a folder (CodebookFile.fit_dir).  The *.wav of in_dir are read and
+    encoded as convert_dir reads them (any rate, the same trimming, the same skip list), in the groups of convert_dir_plan; the *.txt
+    unit files of in_dir are added.  Returns (Codebook, the report written to fit_codebook.json)."""
+    return Codebook.fit_dir(trainer, seg_len, in_dir, K, out_path, iters, seed, batch)

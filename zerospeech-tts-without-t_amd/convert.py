@@ -450,7 +450,7 @@ class _Enqueued(object):
     nothing for is None.  With the generator (enc_only=False), `conv` holds the converted spectrograms [n_utt, T_max, 513] fp32 on
     the device (amplitudes when de-normalised) and `ulens` their frames."""
     __slots__ = ('n_utt', 'chunks', 'enc_host', 'dec_dev', 'dec_host', 'enc_done', 'dev', 'conv', 'ulens', 'units_host', 'uoffs',
-                 'units_dev', 'unpack_E', 'idx_host', 'cb_total', 'vq', 'enc_dev')
+                 'units_dev', 'idx_host', 'cb_total', 'cb', 'enc_dev')
 
     def __init__(self):
         for slot in self.__slots__:
@@ -644,18 +644,10 @@ def _decode_chunk(trainer, ci, utts, lens_p, decode_speakers, enc_only, gen_plan
 
 
 def _check_codebook(codebook, trainer):
-    """A codebook is refused before anything is enqueued for enc_mode 'continues' and for a width other than the Decoder's c_in."""
-    from .codebook import refuse_continues
-    if _is_vq(codebook):                                      # a vector codebook serves 'continues' and no other mode
-        if trainer.enc_mode != 'continues':
-            raise ValueError("a vector codebook serves enc_mode 'continues': this model's enc_mode is %r" % trainer.enc_mode)
-    else:
-        refuse_continues(trainer.enc_mode)
+    """A codebook is refused before anything is enqueued for an enc_mode its kind does not serve (a vector codebook serves
+    'continues' and no other mode) and for a width other than the Decoder's c_in."""
+    codebook.check_mode(trainer.enc_mode)
     codebook.check_width(int(trainer.Decoder.c_in))
-
-
-def _is_vq(codebook):
-    return codebook is not None and getattr(codebook, 'kind', None) == 'vector'
 
 
 def _vq_index_map(chunks, n_utt):
@@ -692,6 +684,153 @@ def _snap_units(codebook, packed, dev, to_host):
     return (_to_host(idx_dev), _to_host(total)) if to_host else (None, None)
 
 
+_NO_UNITS = "enc_mode 'continues' has no units: its encodings are real-valued and cannot be synthesised from unit files"
+
+
+class _Units(object):
+    """What conversion does with units under a codebook of one kind (the codebook's units() hands one out per batch or folder run):
+    the three points of a batch of _enqueue_encode (plan, operand, finish), the encodings _assemble returns, and what the folder
+    drivers read, speak and write.  _BitUnits and _VectorUnits answer the same calls."""
+
+    def __init__(self, codebook):
+        self.cb = codebook
+
+    def check_speakable(self, enc_mode):
+        pass
+
+    def spoken_stem(self, stem):
+        """The stem of the wav a unit file of that stem speaks as."""
+        return stem
+
+
+class _BitUnits(_Units):
+    """Under a bit codebook (zs_amd.codebook.Codebook).  codebook None: plain unit files, which synth_dir reads and speaks as it does
+    under a bit codebook."""
+    packs = True                                  # the batch's units are bit-packed: a bit codebook implies pack
+    unit_glob = '*.txt'
+
+    def plan(self, q, chunks, decoding, want_packed):
+        """Before the chunk loop: the chunk-local tables the Decoder's operands are packed by."""
+        self.want_packed = want_packed
+        self.dense = _upload_tables(*_dense_tables(chunks), chunks, q.dev) if decoding else None
+
+    def operand(self, ci, chunk, Tm, enc, act, dec, dev):
+        """Behind the encoder's launches of chunk ci: the chunk's units -> chunk-local packed rows -> zs_code_assign in place.
+        Returns rows(ch, lens_p) for _decode_chunk: the Decoder's operand from the snapped rows; None when nothing is decoded."""
+        if self.dense is None:
+            return None
+        Tp = int(act.shape[2])
+        if Tp != _t8(Tm):
+            raise L.ZsError('conversion chunk %d: %d encoded frames where the plan has %d' % (ci, Tp, _t8(Tm)))
+        st_c, ln_c = self.dense[ci]
+        snapped = torch.empty(len(chunk) * Tp, (enc.enc_size + 7) // 8, dtype=torch.uint8, device=dev)
+        _launch_units_pack(enc, len(chunk), (st_c, ln_c), snapped, dev)
+        self.cb.snap_(snapped)                                # rows behind a fragment's len are snapped too and never read
+        return lambda ch, lens_p: dec.forward_units(snapped, st_c, ln_c, len(chunk), Tp, ch, lengths=lens_p)
+
+    def finish(self, q, units_dev):
+        """Behind the last chunk: the utterance buffer snapped once, in place (the same rows, the same codewords)."""
+        q.idx_host, q.cb_total = _snap_units(self.cb, units_dev, q.dev, to_host=True)
+
+    def encodings(self, q, u):
+        """Utterance u's snapped units, in the form the caller asked for."""
+        rows = q.units_host.numpy()[q.uoffs[u]:q.uoffs[u + 1]]
+        return rows.copy() if self.want_packed else unpack_units(rows, self.cb.E)
+
+    def check_speakable(self, enc_mode):
+        if enc_mode == 'continues':
+            raise ValueError(_NO_UNITS)
+
+    def read_unit_file(self, path, E):
+        return pack_units(read_units(path, E))
+
+    def speak(self, units, trainer, seg_len, speakers, **kw):
+        return synth_units_batch(units, trainer, seg_len, speakers, packed=True, codebook=self.cb, want_idx=self.cb is not None, **kw)
+
+    def spoken(self, res, units):
+        """(the indices spoken per utterance, the summed distance) of a batch speak() has finished (res) from `units`."""
+        return res[2], res[3]
+
+    def write_spoken(self, base, idx, E):
+        """What was spoken, beside the wav: the codewords of the file's units and their indices."""
+        write_encodings(base + '.txt', unpack_units(self.cb.packed[idx], E))
+        write_indices(base + '.idx.txt', idx)
+
+    def write_encoded(self, txt, units, dev):
+        """--test_encode: the snapped units as the .txt, their indices beside it."""
+        idx, snapped = self.cb.snap_host(pack_units(units))
+        write_encodings(txt, unpack_units(snapped, self.cb.E))
+        write_indices(idx_path(txt), idx)
+
+
+class _VectorUnits(_Units):
+    """Under a vector codebook (zs_amd.vq.VectorCodebook, enc_mode 'continues'): nothing is packed, the units are codeword indices
+    and the unit files are <name>.idx.txt."""
+    packs = False
+    unit_glob = '*.idx.txt'
+
+    def plan(self, q, chunks, decoding, want_packed):
+        """Before the chunk loop: the codebook and the workspace on the device, and where the returned units will lie."""
+        from .vq import workspace
+        self.dense = _upload_tables(*_dense_tables(chunks), chunks, q.dev) if decoding else None
+        self.code, self.cnorm = self.cb.to(q.dev)
+        self.work, self.idx, self.dist = workspace(q.dev), [], []
+        self.bad = torch.zeros(1, dtype=torch.int32, device=q.dev)
+        q.uoffs, src = _vq_index_map(chunks, q.n_utt)
+        self.src = torch.from_numpy(src).to(q.dev, non_blocking=True)
+
+    def operand(self, ci, chunk, Tm, enc, act, dec, dev):
+        """Behind the encoder's launches of chunk ci: zs_vq_assign over the chunk's rows, read in place from the engine's output.
+        Returns rows(ch, lens_p) for _decode_chunk: zs_vq_gather builds the Decoder's operand from the chunk's own indices."""
+        from .vq import launch_assign
+        bits = enc._last_bits
+        Tp = int(bits.T)
+        if Tp != _t8(Tm) or int(bits.B) != len(chunk):
+            raise L.ZsError('conversion chunk %d: %d x %d encoded frames where the plan has %d x %d' % (ci, bits.B, Tp, len(chunk), _t8(Tm)))
+        idx_c = torch.empty(len(chunk) * Tp, dtype=torch.int32, device=dev)
+        dist_c = torch.empty(len(chunk) * Tp, dtype=torch.float32, device=dev)
+        launch_assign(torch.cuda.current_stream(dev).cuda_stream, enc._zs['ctx'].dt, bits.ptr(), len(chunk) * Tp, bits.ld, self.code,
+                      self.cnorm, idx=idx_c, dist=dist_c, work=self.work)
+        self.idx.append(idx_c)
+        self.dist.append(dist_c)
+        if self.dense is None:
+            return None
+        st_c, ln_c = self.dense[ci]
+        return lambda ch, lens_p: dec.forward_indices(idx_c, self.code, st_c, ln_c, len(chunk), Tp, ch, self.bad, lengths=lens_p)
+
+    def finish(self, q, units_dev):
+        """Behind the last chunk: the chunks' indices into utterance order, then one copy.  The batch's device buffers go with it."""
+        idx_all, dist_all = (torch.cat(self.idx), torch.cat(self.dist)) if len(self.idx) > 1 else (self.idx[0], self.dist[0])
+        q.idx_host = _to_host(idx_all[self.src])
+        q.cb_total = _to_host(dist_all[self.src].sum(dtype=torch.float64).reshape(1))
+        self.idx = self.dist = self.work = self.src = self.dense = None
+
+    def encodings(self, q, u):
+        """Utterance u's encodings: the codewords of its indices."""
+        return self.cb.vectors[q.idx_host.numpy()[q.uoffs[u]:q.uoffs[u + 1]]]
+
+    def read_unit_file(self, path, E):
+        return read_indices(path, self.cb.K)
+
+    def spoken_stem(self, stem):
+        return stem[:-len('.idx')]                            # <name>.idx.txt speaks as <name>.wav
+
+    def speak(self, units, trainer, seg_len, speakers, **kw):
+        return synth_index_batch(units, trainer, seg_len, speakers, self.cb, **kw)
+
+    def spoken(self, res, units):
+        return units, 0.0                                     # the file's own indices: nothing was snapped
+
+    def write_spoken(self, base, idx, E):
+        write_indices(base + '.idx.txt', idx)
+
+    def write_encoded(self, txt, units, dev):
+        """--test_encode: the .txt as without a codebook, the nearest codeword of every encoded frame beside it."""
+        idx, _ = self.cb.snap(torch.from_numpy(np.ascontiguousarray(units, dtype=np.float32)).to(dev))
+        write_encodings(txt, units)
+        write_indices(idx_path(txt), idx.cpu().numpy())
+
+
 def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host, enc_only=True, denorm=False, pack=False,
                     codebook=None, rows_on_device=False):
     """Fragment rule + every Encoder / Decoder launch of a batch of utterances, WITHOUT a host synchronisation: the caller decides
@@ -710,12 +849,13 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
     chunks' indices are brought into utterance order on the device (_vq_index_map) and copied once (q.idx_host), with the summed
     squared distance of the returned units (q.cb_total, a double), and the encodings returned are the codewords of the indices.
     rows_on_device: the fp32 encodings stay on the device (q.enc_dev, one tensor per chunk) instead of being copied to the host."""
-    vq = _is_vq(codebook)
+    side = None                                               # what the codebook's kind does to this batch (_BitUnits, _VectorUnits)
     if codebook is not None:
         _check_codebook(codebook, trainer)
         if int(trainer.Encoder.enc_size) != codebook.E:
             raise ValueError("codebook field E is %d, the Encoder's enc_size is %d" % (codebook.E, int(trainer.Encoder.enc_size)))
-        pack = pack or not vq
+        side, want_packed = codebook.units(), pack
+        pack = pack or side.packs
     if pack and trainer.enc_mode == 'continues':
         raise ValueError("enc_mode 'continues' has no units to pack (its encodings are not 0 / 1)")
     if not enc_only:
@@ -750,15 +890,8 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
         pack_tabs = _upload_tables(starts, counts, chunks, dev)
         row_bytes = (enc.enc_size + 7) // 8
         units_dev = torch.empty(int(q.uoffs[-1]), row_bytes, dtype=torch.uint8, device=dev)
-    dense_tabs = _upload_tables(*_dense_tables(chunks), chunks, dev) if (codebook is not None and decode_speakers is not None) else None
-    if vq:                                                    # a vector codebook ('continues'): indices, not packed rows
-        from . import vq as zvq
-        code_d, cnorm_d = codebook.to(dev)
-        vq_work, vq_idx, vq_dist = zvq.workspace(dev), [], []
-        vq_bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        q.vq = codebook
-        q.uoffs, vq_src = _vq_index_map(chunks, len(specs))
-        vq_src = torch.from_numpy(vq_src).to(dev, non_blocking=True)
+    if side is not None:
+        side.plan(q, chunks, decode_speakers is not None, want_packed)
     for ci, (chunk, ragged) in enumerate(chunks):
         lens = [it.n for it in chunk]
         Tm = max(lens)
@@ -769,39 +902,18 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
         G = noise_fn(len(chunk), _t8(Tm), enc.enc_size) if noise_fn is not None else None
         act, _ = enc(x.permute(0, 2, 1), G=G, lengths=(lens if ragged else None))
         xd = None
-        if vq:                                                # encoder -> zs_vq_assign over the chunk's rows, read in place
-            bits = enc._last_bits
-            Tp = int(bits.T)
-            if Tp != _t8(Tm) or int(bits.B) != len(chunk):
-                raise L.ZsError('conversion chunk %d: %d x %d encoded frames where the plan has %d x %d' % (ci, bits.B, Tp, len(chunk), _t8(Tm)))
-            idx_c = torch.empty(len(chunk) * Tp, dtype=torch.int32, device=dev)
-            dist_c = torch.empty(len(chunk) * Tp, dtype=torch.float32, device=dev)
-            L.call('zs_vq_assign', 'ZsVqAssign', torch.cuda.current_stream(dev).cuda_stream, dtype=enc._zs['ctx'].dt, src_f32=0, x=bits.ptr(),
-                   n=len(chunk) * Tp, ld_x=bits.ld, code=L.ptr(code_d), ld_code=codebook.E, cnorm=L.ptr(cnorm_d), K=codebook.K, E=codebook.E,
-                   idx=L.ptr(idx_c), dist=L.ptr(dist_c), work=L.ptr(vq_work), work_bytes=vq_work.numel() * 8)
-            vq_idx.append(idx_c)
-            vq_dist.append(dist_c)
-        if decode_speakers is not None:
+        if side is not None:                                  # the snap of the chunk, and the Decoder's operand from what it gave
+            rows_fn = side.operand(ci, chunk, Tm, enc, act, dec, dev)
+        else:
             rows_fn = lambda ch, lens_p: dec.forward_rows(act, ch, lengths=lens_p)
-            if vq:                                            # -> zs_vq_gather: the Decoder's operand from the chunk's own indices
-                st_c, ln_c = dense_tabs[ci]
-                rows_fn = lambda ch, lens_p: dec.forward_indices(idx_c, code_d, st_c, ln_c, len(chunk), Tp, ch, vq_bad, lengths=lens_p)
-            if codebook is not None and not vq:               # the Decoder's operand from the chunk's own snapped rows
-                Tp = int(act.shape[2])
-                if Tp != _t8(Tm):
-                    raise L.ZsError('conversion chunk %d: %d encoded frames where the plan has %d' % (ci, Tp, _t8(Tm)))
-                st_c, ln_c = dense_tabs[ci]
-                snapped = torch.empty(len(chunk) * Tp, row_bytes, dtype=torch.uint8, device=dev)
-                _launch_units_pack(enc, len(chunk), (st_c, ln_c), snapped, dev)
-                codebook.snap_(snapped)                       # rows behind a fragment's len are snapped too and never read
-                rows_fn = lambda ch, lens_p: dec.forward_units(snapped, st_c, ln_c, len(chunk), Tp, ch, lengths=lens_p)
+        if decode_speakers is not None:
             xd = _decode_chunk(trainer, ci, [it.u for it in chunk], ([_t8(n) for n in lens] if ragged else None), decode_speakers,
                                enc_only, gen_plan, rows_fn)
         q.chunks.append((chunk, lens))
         if pack:
             _launch_units_pack(enc, len(chunk), pack_tabs[ci], units_dev, dev)
             q.enc_host.append(None)
-        elif vq:                                              # the encodings returned are the codewords of the indices
+        elif side is not None:                                # the encodings returned come from the codebook (side.encodings)
             q.enc_host.append(None)
         elif rows_on_device:                                  # the fp32 rows stay where they are (q.enc_dev): no copy to the host
             q.enc_host.append(None)
@@ -810,12 +922,9 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
             q.enc_host.append(_to_host(act.permute(0, 2, 1).contiguous()))
         q.dec_dev.append(xd)
         q.dec_host.append(_to_host(xd) if (xd is not None and dec_to_host) else None)
-    if vq:                                                    # the chunks' indices into utterance order, then one copy
-        idx_all, dist_all = (torch.cat(vq_idx), torch.cat(vq_dist)) if len(vq_idx) > 1 else (vq_idx[0], vq_dist[0])
-        q.idx_host = _to_host(idx_all[vq_src])
-        q.cb_total = _to_host(dist_all[vq_src].sum(dtype=torch.float64).reshape(1))
-    elif codebook is not None:
-        q.idx_host, q.cb_total = _snap_units(codebook, units_dev, dev, to_host=True)
+    if side is not None:                                      # the index of every returned unit and the summed distance
+        side.finish(q, units_dev if pack else None)
+        q.cb = side
     if pack:
         q.units_dev = units_dev
         q.units_host = _to_host(units_dev)
@@ -847,9 +956,8 @@ def _assemble(q, want_dec):
     The caller has waited for the copies."""
     enc_out, dec_out = {}, {}
     units = q.units_host.numpy() if q.units_host is not None else None      # packed: one buffer, utterance by utterance
-    vq_idx = q.idx_host.numpy() if q.vq is not None else None              # a vector codebook: the codewords of the indices
     for ci, (chunk, lens) in enumerate(q.chunks):
-        e = q.enc_host[ci].numpy() if (units is None and vq_idx is None) else None
+        e = q.enc_host[ci].numpy() if q.enc_host[ci] is not None else None
         xd = None
         if want_dec == 'host':
             xd = q.dec_host[ci].numpy()
@@ -866,12 +974,10 @@ def _assemble(q, want_dec):
     encs, decs = [], ([] if want_dec else None)
     for u in range(q.n_utt):
         ks = sorted(by_utt[u])
-        if vq_idx is not None:
-            encs.append(q.vq.vectors[vq_idx[q.uoffs[u]:q.uoffs[u + 1]]])
+        if q.cb is not None:                                  # a codebook: what its kind returns for the snapped units
+            encs.append(q.cb.encodings(q, u))
         elif units is None:
             encs.append(np.concatenate([enc_out[(u, k)] for k in ks], axis=0))
-        elif q.unpack_E is not None:                          # packed on the way (a codebook), plain rows for the caller
-            encs.append(unpack_units(units[q.uoffs[u]:q.uoffs[u + 1]], q.unpack_E))
         else:
             encs.append(units[q.uoffs[u]:q.uoffs[u + 1]].copy())
         if decs is not None:
@@ -927,8 +1033,6 @@ def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, m
         raise ValueError('encode_batch: units_on_device needs packed=True')
     q = _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host=to_host, enc_only=enc_only,
                         pack=packed, codebook=codebook)
-    if codebook is not None and not packed and not _is_vq(codebook):
-        q.unpack_E = codebook.E
     out = _encode_result(q, decode_speakers, to_host, enc_only, units_on_device)
     return out + (_unit_indices(q.idx_host, q.cb_total, q.uoffs)[0],) if want_idx else out
 
@@ -976,8 +1080,6 @@ def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, 
         q = _enqueue_encode(specs, trainer, seg_len, speakers, noise_fn, max_batch, dec_to_host=False, codebook=codebook)
         t, ulens = _gather_decoded(q, [[8 * _t8(n) for n in lens] for _, lens in q.chunks])
         fin = _enqueue_vocoder(t, ulens, n_iter, do_trim, q.dev, momentum=momentum)
-    if codebook is not None and not _is_vq(codebook):
-        q.unpack_E = codebook.E
     return _finish_resynth(q, fin, defer, want_idx)
 
 
@@ -991,14 +1093,20 @@ def _gather_decoded(q, out_rows):
     return table[torch.from_numpy(idx).to(dev, non_blocking=True)].float(), ulens                     # [n, Tm, 513]
 
 
+def _wait_vocoder(fin, dev):
+    """The wavs of a batch, waited for; a persistent GRU pass that timed out before the batch's end raises here."""
+    wavs = fin()
+    if fin.status:
+        from . import layers
+        layers.check_status(dev)                              # synchronises, clears the word and raises
+    return wavs
+
+
 def _finish_resynth(q, fin, defer, want_idx=False):
     def finish():
         q.enc_done.synchronize()                              # the encodings are on the host; the vocoder is still running
         encs, _ = _assemble(q, None)
-        wavs = fin()
-        if fin.status:                                        # a persistent GRU pass timed out before this batch's end
-            from . import layers
-            layers.check_status(q.dev)                        # synchronises, clears the word and raises
+        wavs = _wait_vocoder(fin, q.dev)
         return (encs, wavs) + _unit_indices(q.idx_host, q.cb_total, q.uoffs) if want_idx else (encs, wavs)
     return finish if defer else finish()
 
@@ -1052,39 +1160,51 @@ def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=N
     if want_idx and codebook is None:
         raise ValueError('synth_units_batch: want_idx needs a codebook')
     if trainer.enc_mode == 'continues':
-        raise ValueError("enc_mode 'continues' has no units: its encodings are real-valued and cannot be synthesised from unit files")
-    if len(speakers) != len(units) or not len(units):
-        raise ValueError('synth_units_batch: %d target speakers for %d utterances' % (len(speakers), len(units)))
+        raise ValueError(_NO_UNITS)
     dec = trainer.Decoder
-    E, row_bytes = int(dec.c_in), (int(dec.c_in) + 7) // 8
-    rows = _check_units(units, E, packed)
-    if codebook is not None:
-        _check_codebook(codebook, trainer)
-    _check_speaker_range(speakers, int(dec.c_a))
+
+    def check_rows():
+        rows = _check_units(units, int(dec.c_in), packed)
+        if codebook is not None:
+            _check_codebook(codebook, trainer)
+        return rows
+
+    def operand(packed_dev, dev):                             # the snap of the one buffer, then zs_units_unpack per chunk
+        idx_h = total_h = None
+        if codebook is not None:
+            idx_h, total_h = _snap_units(codebook, packed_dev, dev, to_host=want_idx)
+        return (lambda tab, B, T0, ch, lens_p: dec.forward_units(packed_dev, tab[0], tab[1], B, T0, ch, lengths=lens_p)), idx_h, total_h
+    return _synth_batch('synth_units_batch', units, check_rows, operand, trainer, seg_len, speakers, enc_only, n_iter, do_trim, max_batch,
+                        defer, momentum, want_specs)
+
+
+def _synth_batch(who, units, check_rows, operand, trainer, seg_len, speakers, enc_only, n_iter, do_trim, max_batch, defer, momentum,
+                 want_specs):
+    """The one driver of synth_units_batch and synth_index_batch.  check_rows() -> the utterances as host arrays of one dtype and
+    row shape (ValueError for what cannot be spoken); they go to the device once, in one pinned buffer and one copy, and
+    unit_fragments cuts each into the row ranges the Decoder runs on.  operand(buffer, dev) -> (the function _enqueue_synth builds a
+    chunk's Decoder operand with, and the pinned codeword indices and summed distance of a snap, or None, None)."""
+    if len(speakers) != len(units) or not len(units):
+        raise ValueError('%s: %d target speakers for %d utterances' % (who, len(speakers), len(units)))
+    rows = check_rows()
+    _check_speaker_range(speakers, int(trainer.Decoder.c_a))
     shift = 0 if enc_only else check_gen_targets(trainer, speakers)
     trainer.set_eval()
     dev = trainer.device
     items = [it for u, r in enumerate(rows) for it in _unit_items(u, len(r), seg_len)]
     chunks = _split_chunks(items, int(seg_len) // 8, max_batch)
-    # every utterance goes to the device once: E / 8 bytes per unit, one pinned buffer, one copy; the fragments are row ranges of it
     uoffs = np.concatenate(([0], np.cumsum([len(r) for r in rows]))).astype(np.int64)
-    host = torch.empty(int(uoffs[-1]), row_bytes, dtype=torch.uint8, pin_memory=True)
+    host = torch.empty((int(uoffs[-1]),) + rows[0].shape[1:], dtype=torch.from_numpy(rows[0]).dtype, pin_memory=True)
     np.concatenate(rows, axis=0, out=host.numpy())
-    packed_dev = host.to(dev, non_blocking=True)
-    idx_h = total_h = None
-    if codebook is not None:
-        idx_h, total_h = _snap_units(codebook, packed_dev, dev, to_host=want_idx)
+    chunk_operand, idx_h, total_h = operand(host.to(dev, non_blocking=True), dev)     # the one H2D copy of the batch
     fin, spec_h, ulens = _enqueue_synth(trainer, seg_len, chunks, uoffs, speakers, enc_only, shift, n_iter, do_trim, momentum, want_specs,
-                                        lambda tab, B, T0, ch, lens_p: dec.forward_units(packed_dev, tab[0], tab[1], B, T0, ch, lengths=lens_p))
+                                        chunk_operand)
 
     def finish():
-        wavs = fin()
-        if fin.status:                                        # a persistent GRU pass timed out before this batch's end
-            from . import layers
-            layers.check_status(dev)                          # synchronises, clears the word and raises
+        wavs = _wait_vocoder(fin, dev)
         specs = [spec_h.numpy()[u, :n].copy() for u, n in enumerate(ulens)] if spec_h is not None else None
         # the indices were copied before the vocoder, which fin() has waited for
-        return (specs, wavs) + _unit_indices(idx_h, total_h, uoffs) if want_idx else (specs, wavs)
+        return (specs, wavs) + _unit_indices(idx_h, total_h, uoffs) if idx_h is not None else (specs, wavs)
     return finish if defer else finish()
 
 
@@ -1149,47 +1269,32 @@ def synth_index_batch(idx_lists, trainer, seg_len, speakers, codebook, enc_only=
     width other than the Decoder's c_in, an index outside [0, K), fewer than 2 indices (ValueError); a speaker the Decoder or the
     generator cannot take."""
     momentum = gl_momentum(momentum)
-    if not _is_vq(codebook):
+    if getattr(codebook, 'kind', None) != 'vector':
         if trainer.enc_mode == 'continues':
-            raise ValueError("enc_mode 'continues' has no units: its encodings are real-valued and cannot be synthesised from unit files")
+            raise ValueError(_NO_UNITS)
         raise ValueError('synth_index_batch: the codebook must be a vector codebook (zs_amd.vq.VectorCodebook)')
     _check_codebook(codebook, trainer)
-    if len(speakers) != len(idx_lists) or not len(idx_lists):
-        raise ValueError('synth_index_batch: %d target speakers for %d utterances' % (len(speakers), len(idx_lists)))
-    rows = []
-    for i, seq in enumerate(idx_lists):
-        a = np.asarray(seq.cpu() if torch.is_tensor(seq) else seq)
-        if a.ndim != 1 or a.dtype.kind not in 'iu':
-            raise ValueError('utterance %d: indices must be a 1-D integer sequence (got %s %s)' % (i, a.dtype, a.shape))
-        if a.shape[0] < 2:
-            raise ValueError('utterance %d has fewer than 2 indices (the Decoder needs two rows)' % i)
-        if (a < 0).any() or (a >= codebook.K).any():
-            raise ValueError('utterance %d: an index is outside [0, K = %d)' % (i, codebook.K))
-        rows.append(a.astype(np.int32))
     dec = trainer.Decoder
-    _check_speaker_range(speakers, int(dec.c_a))
-    shift = 0 if enc_only else check_gen_targets(trainer, speakers)
-    trainer.set_eval()
-    dev = trainer.device
-    items = [it for u, r in enumerate(rows) for it in _unit_items(u, len(r), seg_len)]
-    chunks = _split_chunks(items, int(seg_len) // 8, max_batch)
-    uoffs = np.concatenate(([0], np.cumsum([len(r) for r in rows]))).astype(np.int64)
-    host = torch.empty(int(uoffs[-1]), dtype=torch.int32, pin_memory=True)
-    np.concatenate(rows, axis=0, out=host.numpy())
-    idx_dev = host.to(dev, non_blocking=True)                 # the one H2D copy of the batch
-    code_d, _ = codebook.to(dev)
-    bad = torch.zeros(1, dtype=torch.int32, device=dev)
-    fin, spec_h, ulens = _enqueue_synth(trainer, seg_len, chunks, uoffs, speakers, enc_only, shift, n_iter, do_trim, momentum, want_specs,
-                                        lambda tab, B, T0, ch, lens_p: dec.forward_indices(idx_dev, code_d, tab[0], tab[1], B, T0, ch, bad,
-                                                                                           lengths=lens_p))
 
-    def finish():
-        wavs = fin()
-        if fin.status:
-            from . import layers
-            layers.check_status(dev)
-        return ([spec_h.numpy()[u, :n].copy() for u, n in enumerate(ulens)] if spec_h is not None else None), wavs
-    return finish if defer else finish()
+    def check_rows():
+        rows = []
+        for i, seq in enumerate(idx_lists):
+            a = np.asarray(seq.cpu() if torch.is_tensor(seq) else seq)
+            if a.ndim != 1 or a.dtype.kind not in 'iu':
+                raise ValueError('utterance %d: indices must be a 1-D integer sequence (got %s %s)' % (i, a.dtype, a.shape))
+            if a.shape[0] < 2:
+                raise ValueError('utterance %d has fewer than 2 indices (the Decoder needs two rows)' % i)
+            if (a < 0).any() or (a >= codebook.K).any():
+                raise ValueError('utterance %d: an index is outside [0, K = %d)' % (i, codebook.K))
+            rows.append(a.astype(np.int32))
+        return rows
+
+    def operand(idx_dev, dev):                                # zs_vq_gather per chunk, from the one index buffer and the codewords
+        code_d, _ = codebook.to(dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        return (lambda tab, B, T0, ch, lens_p: dec.forward_indices(idx_dev, code_d, tab[0], tab[1], B, T0, ch, bad, lengths=lens_p)), None, None
+    return _synth_batch('synth_index_batch', idx_lists, check_rows, operand, trainer, seg_len, speakers, enc_only, n_iter, do_trim, max_batch,
+                        defer, momentum, want_specs)
 
 
 def out_rate():
@@ -1493,6 +1598,23 @@ def _skip_log(tag):
     return skipped, skip
 
 
+def _scan_wavs(in_dir, skip):
+    """(the *.wav of in_dir whose header can be read, sorted; their durations in seconds); skip(path, reason) takes the others."""
+    from .preprocess import wav_info
+    files, durations = [], []
+    for path in sorted(glob.glob(os.path.join(in_dir, '*.wav'))):
+        try:
+            sr, n = wav_info(path)
+            if sr <= 0:
+                raise ValueError('sample rate %d' % sr)
+        except (OSError, ValueError) as e:
+            skip(path, 'cannot be read: %s' % e)
+            continue
+        files.append(path)
+        durations.append(n / float(sr))
+    return files, durations
+
+
 def _write_manifest(path, in_dir, out_dir, t_speakers, enc_only, items, skipped, stats, voices, speaker2id):
     """The manifest of a folder driver, written to `path` and returned: the run's fields, the driver's own `items`, what was
     skipped, and 'codebook' / 'voices' when the run had them."""
@@ -1524,7 +1646,7 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
     entropy_bits_per_unit, mean_distance} over the units written.  A zs_amd.vq.VectorCodebook for enc_mode 'continues': the same
     outputs, the .idx.txt being the unit file (the .txt holds what write_encodings writes for real-valued rows)."""
     from concurrent.futures import ThreadPoolExecutor
-    from .preprocess import read_wav, wav_info
+    from .preprocess import read_wav
     momentum = gl_momentum(momentum)
     stats = _codebook_stats(codebook, trainer, codebook_file)
     t_speakers = list(t_speakers)
@@ -1532,17 +1654,7 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
     if not enc_only:
         check_gen_targets(trainer, [speaker2id[t] for t in t_speakers])
     skipped, skip = _skip_log('Converter')
-    files, durations = [], []
-    for path in sorted(glob.glob(os.path.join(in_dir, '*.wav'))):
-        try:
-            sr, n = wav_info(path)
-            if sr <= 0:
-                raise ValueError('sample rate %d' % sr)
-        except (OSError, ValueError) as e:
-            skip(path, 'cannot be read: %s' % e)
-            continue
-        files.append(path)
-        durations.append(n / float(sr))
+    files, durations = _scan_wavs(in_dir, skip)
     plan = convert_dir_plan(files, durations, t_speakers, out_dir, batch=batch)
     for s in plan['skipped']:
         skip(s['file'], s['reason'])
@@ -1660,18 +1772,17 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
     momentum = gl_momentum(momentum)
     t_speakers = list(t_speakers)
     speaker2id = _target_table('synth_dir', trainer, speaker2id_path, voices, t_speakers, enc_only)
-    vq = _is_vq(codebook)                                     # a vector codebook: the *.idx.txt index files of a 'continues' model
-    if trainer.enc_mode == 'continues' and not vq:
-        raise ValueError("enc_mode 'continues' has no units: its encodings are real-valued and cannot be synthesised from unit files")
+    side = codebook.units() if codebook is not None else _BitUnits(None)      # which files are read, and how they are spoken and written
+    side.check_speakable(trainer.enc_mode)                    # 'continues' speaks from the index files of a vector codebook alone
     if not enc_only:
         check_gen_targets(trainer, [speaker2id[t] for t in t_speakers])
     E = int(trainer.Decoder.c_in)
     stats = _codebook_stats(codebook, trainer, codebook_file)
     skipped, skip = _skip_log('Synthesiser')
     units = {}
-    for path in sorted(glob.glob(os.path.join(in_dir, '*.idx.txt' if vq else '*.txt'))):
+    for path in sorted(glob.glob(os.path.join(in_dir, side.unit_glob))):
         try:
-            units[path] = read_indices(path, codebook.K) if vq else pack_units(read_units(path, E))
+            units[path] = side.read_unit_file(path, E)
         except (OSError, ValueError) as e:
             skip(path, 'cannot be read: %s' % e)
     files = sorted(units)
@@ -1679,10 +1790,9 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
     for s in plan['skipped']:
         skip(s['file'], s['reason'])
     groups = plan['groups']
-    if vq:                                                    # <name>.idx.txt speaks as <name>.wav
-        for it in (it for g in groups for it in g):
-            it['stem'] = it['stem'][:-len('.idx')]
-            it['wav'] = os.path.join(out_dir, it['target'], it['stem'] + '.wav')
+    for it in (it for g in groups for it in g):
+        it['stem'] = side.spoken_stem(it['stem'])
+        it['wav'] = os.path.join(out_dir, it['target'], it['stem'] + '.wav')
     print('[Synthesiser] - %d unit files, %d target speakers, %d syntheses in %d groups' %
           (len(files) - len(plan['skipped']), len(t_speakers), sum(len(g) for g in groups), len(groups)))
     os.makedirs(out_dir, exist_ok=True)
@@ -1690,29 +1800,19 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
 
     def write(group, fin):
         res = fin()
-        wavs = res[1]
-        if vq:                                                # what was spoken: the file's own indices, nothing was snapped
-            stats.add([units[it['file']] for it in group], 0.0)
-        elif stats is not None:
-            stats.add(res[2], res[3])
-        for i, (it, w) in enumerate(zip(group, to_out_sr(wavs))):
+        if stats is not None:
+            idxs, total = side.spoken(res, [units[it['file']] for it in group])
+            stats.add(idxs, total)
+        for i, (it, w) in enumerate(zip(group, to_out_sr(res[1]))):
             os.makedirs(os.path.dirname(it['wav']), exist_ok=True)
             write_wav(it['wav'], w, out_rate())
-            if vq:
-                write_indices(os.path.splitext(it['wav'])[0] + '.idx.txt', units[it['file']])
-            elif stats is not None:                           # what was spoken: the codewords of the file's units
-                txt = os.path.splitext(it['wav'])[0] + '.txt'
-                write_encodings(txt, unpack_units(codebook.packed[res[2][i]], E))
-                write_indices(idx_path(txt), res[2][i])
+            if stats is not None:                             # what was spoken, beside the wav
+                side.write_spoken(os.path.splitext(it['wav'])[0], idxs[i], E)
             done.append(it)
 
     def enqueue(group):
-        if vq:
-            return group, synth_index_batch([units[it['file']] for it in group], trainer, seg_len, [speaker2id[it['target']] for it in group],
-                                            codebook, enc_only=enc_only, n_iter=n_iter, defer=True, momentum=momentum)
-        return group, synth_units_batch([units[it['file']] for it in group], trainer, seg_len, [speaker2id[it['target']] for it in group],
-                                        enc_only=enc_only, n_iter=n_iter, defer=True, momentum=momentum, packed=True, codebook=codebook,
-                                        want_idx=codebook is not None)
+        return group, side.speak([units[it['file']] for it in group], trainer, seg_len, [speaker2id[it['target']] for it in group],
+                                 enc_only=enc_only, n_iter=n_iter, defer=True, momentum=momentum)
 
     _run_deferred(groups, enqueue, write)
     items = [{'input': it['file'], 'units': it['units'], 'fragments': unit_fragments(it['units'], seg_len), 'target': it['target'],
@@ -1770,14 +1870,7 @@ def test_encode(trainer, seg_len, test_path, data_path, result_dir, flag='test',
                 continue
             units = encode(f_h5[f"test/{feed['s_id']}/{feed['utt_id']}/lin"][()], trainer, seg_len, save=False)
             txt = os.path.join(dir_path, f"{feed['s_id']}_{feed['utt_id']}.txt")
-            if _is_vq(codebook):                              # 'continues': the .txt as without a codebook, the indices beside it
-                idx, _ = codebook.snap(torch.from_numpy(np.ascontiguousarray(units, dtype=np.float32)).to(trainer.device))
-                write_encodings(txt, units)
-                write_indices(idx_path(txt), idx.cpu().numpy())
-                continue
-            idx, snapped = codebook.snap_host(pack_units(units))
-            write_encodings(txt, unpack_units(snapped, codebook.E))
-            write_indices(idx_path(txt), idx)
+            codebook.units().write_encoded(txt, units, trainer.device)
 
 
 # ---------------------------------------------------------------------------------------------------

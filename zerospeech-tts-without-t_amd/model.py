@@ -273,51 +273,57 @@ class Decoder(ZsModule):
         _, xdec = self.forward_rows(x, c, lengths=lengths)
         return xdec.valid().permute(0, 2, 1).clone()
 
+    def _forward_operand(self, B, T0, E, fill, c, dev, lengths):
+        """The shared tail of forward_rows, forward_units and forward_indices: the engine's operand buffer [B, T0, E], filled by
+        fill(ctx, bits) (what it returns is kept alive until the engine's launches are enqueued), the speaker index tensor and the
+        engine.  Returns (bits, x_dec)."""
+        eng = self._engine()
+        ctx = eng.ctx
+        bits = ctx.act('d_in_%d_%d_%d' % (eng.uid, B, T0), B, T0, E)
+        keep = fill(ctx, bits)  # noqa: F841
+        cidx = c.detach().to(dev, torch.int64).contiguous()
+        return bits, eng.forward(bits, cidx, self.training, lengths=lengths)
+
     def forward_rows(self, x, c, lengths=None):
         """forward() without the copy out: (bits, x_dec), the input as the engine reads it (Act [B, T', c_in], compute dtype) and
         the output rows (Act fp32 [B, 8T', c_out]).  Both live in the engine's buffers, which the next forward of the same shape
         overwrites."""
-        eng = self._engine()
-        ctx = eng.ctx
-        xb = x.detach().permute(0, 2, 1).contiguous().float()
-        B, T0, E = xb.shape
-        bits = ctx.act('d_in_%d_%d_%d' % (eng.uid, B, T0), B, T0, E)
-        cast_rows(ctx, L.ptr(xb), E, bits)
-        cidx = c.detach().to(xb.device, torch.int64).contiguous()
-        return bits, eng.forward(bits, cidx, self.training, lengths=lengths)
+        B, E, T0 = x.shape
+
+        def fill(ctx, bits):
+            xb = x.detach().permute(0, 2, 1).contiguous().float()
+            cast_rows(ctx, L.ptr(xb), E, bits)
+            return xb
+        return self._forward_operand(B, T0, E, fill, c, x.device, lengths)
 
     def forward_units(self, packed, start, length, B, T0, c, lengths=None):
         """forward_rows() from bit-packed units (convert.pack_units): zs_units_unpack writes the chunk's operand [B, T0, c_in] from
         rows start[b] .. start[b] + length[b] of `packed` (uint8 [n_units, row_bytes] on the device; start int64 [B] and length
         int32 [B] device tables), zeros behind each fragment's rows.  The same buffer, and then the same launches, as forward_rows."""
-        eng = self._engine()
-        ctx = eng.ctx
         E = self.c_in
         if packed.dtype != torch.uint8 or packed.dim() != 2 or packed.shape[1] < (E + 7) // 8 or not packed.is_contiguous():
             raise ValueError('Decoder.forward_units: packed must be contiguous uint8 [n_units, >= %d]' % ((E + 7) // 8))
-        bits = ctx.act('d_in_%d_%d_%d' % (eng.uid, B, T0), B, T0, E)
-        L.call('zs_units_unpack', 'ZsUnitsUnpack', ctx.stream, dtype=ctx.dt, packed=L.ptr(packed), n_units=packed.shape[0],
-               row_bytes=packed.shape[1], E=E, start=L.ptr(start), len=L.ptr(length), n_frag=B, T=T0, dst=bits.ptr(), ld_dst=bits.ld)
-        cidx = c.detach().to(packed.device, torch.int64).contiguous()
-        return bits, eng.forward(bits, cidx, self.training, lengths=lengths)
+
+        def fill(ctx, bits):
+            L.call('zs_units_unpack', 'ZsUnitsUnpack', ctx.stream, dtype=ctx.dt, packed=L.ptr(packed), n_units=packed.shape[0],
+                   row_bytes=packed.shape[1], E=E, start=L.ptr(start), len=L.ptr(length), n_frag=B, T=T0, dst=bits.ptr(), ld_dst=bits.ld)
+        return self._forward_operand(B, T0, E, fill, c, packed.device, lengths)
 
     def forward_indices(self, idx, code, start, length, B, T0, c, bad, lengths=None):
         """forward_rows() from codeword indices (zs_amd.vq): zs_vq_gather writes the chunk's operand [B, T0, c_in] from the codewords
         code[idx[start[b]] .. idx[start[b] + length[b] - 1]] (idx int32 [n_idx], code fp32 [K, c_in], start int64 [B], length int32
         [B], all on the device), zeros behind each fragment's rows; bad int32 [1] counts the indices outside [0, K).  The same
         buffer, and then the same launches, as forward_rows."""
-        eng = self._engine()
-        ctx = eng.ctx
+        from .vq import launch_gather
         E = self.c_in
         if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous():
             raise ValueError('Decoder.forward_indices: idx must be contiguous int32 [n_idx]')
         if code.dtype != torch.float32 or code.dim() != 2 or code.shape[1] != E or not code.is_contiguous():
             raise ValueError('Decoder.forward_indices: code must be contiguous fp32 [K, %d]' % E)
-        bits = ctx.act('d_in_%d_%d_%d' % (eng.uid, B, T0), B, T0, E)
-        L.call('zs_vq_gather', 'ZsVqGather', ctx.stream, dtype=ctx.dt, idx=L.ptr(idx), n_idx=idx.numel(), code=L.ptr(code), ld_code=E,
-               K=code.shape[0], E=E, start=L.ptr(start), len=L.ptr(length), n_frag=B, T=T0, dst=bits.ptr(), ld_dst=bits.ld, bad=L.ptr(bad))
-        cidx = c.detach().to(idx.device, torch.int64).contiguous()
-        return bits, eng.forward(bits, cidx, self.training, lengths=lengths)
+
+        def fill(ctx, bits):
+            launch_gather(ctx.stream, ctx.dt, idx, code, start, length, B, T0, bits.ptr(), bits.ld, bad)
+        return self._forward_operand(B, T0, E, fill, c, idx.device, lengths)
 
 
 class Spectrogram_Patcher(ZsModule):

@@ -695,8 +695,9 @@ class Trainer(object):
         self.ema = check_ema(ema)
         self.valid = validation.check_config(valid, hps) if valid is not None else None
         self.vq_train = vq_train
-        if vq_train is not None and enc_mode != 'continues':
-            raise ValueError("vq_train needs enc_mode 'continues': this model's enc_mode is %r" % enc_mode)
+        if vq_train is not None:
+            from .vq import VectorCodebook
+            VectorCodebook.check_mode(enc_mode, "vq_train needs enc_mode 'continues'")
         self._vstep = None                                                 # ValidStep, built on first use
         self.best_loss = self.best_iteration = None                        # the lowest valid_loss_rec so far and its iteration
         self._best_due = False                                             # the next periodic resumable checkpoint also writes -ae-best

@@ -6,26 +6,21 @@ The work is four HIP entry points (csrc/zs_vq.hip): zs_vq_assign (nearest codewo
 epilogue, the hot call), zs_vq_accum and zs_vq_update (the fixed-point sums and the means of one k-means iteration) and zs_vq_gather
 (indices -> the Decoder's input operand).  The sums are int64, so a fit is bitwise reproducible.  tests/vq_ref.py is the numpy
 definition.  Not in the reference, which has no codebook of any kind."""
-import json
 from fractions import Fraction
 
 import numpy as np
 import torch
 
 from . import _lib as L
-from .codebook import Codebook, refuse_continues, usage  # noqa: F401  (usage: the histogram statistics are the bit codebook's)
+from .codebook import (FORMAT_VERSION, Codebook, CodebookFile, _stream, encode_dir, first_distinct, read_npz,  # noqa: F401
+                       reseed_rows, usage)       # (the file format, reseed_rows and usage are one rule for both kinds of codebook)
 
-FORMAT_VERSION = 1
 MAX_K = L.ENUMS['ZS_CODE_MAX_K']
 MAX_E = L.ENUMS['ZS_CODE_MAX_E']
 TILE_K = L.ENUMS['ZS_VQ_TILE_K']
 SPLIT_N = L.ENUMS['ZS_VQ_SPLIT_N']
 WORK_BYTES = L.ENUMS['ZS_VQ_WORK_BYTES']
 MAX_SHIFT = 30
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def host_cnorm(vectors):
@@ -61,6 +56,15 @@ def _check_x(x, E, what='x'):
         raise ValueError('%s must be an fp32 or bf16 device tensor [n, >= %d] with unit column stride' % (what, E))
 
 
+def launch_assign(stream, dt, x, n, ld_x, code, cnorm, E=None, idx=None, dist=None, moved=None, work=None):
+    """THE zs_vq_assign launch: n rows of the compute dtype dt at the device pointer x, ld_x elements apart, against code fp32 [K, E]
+    and cnorm fp32 [K] (tensors).  Outputs and workspace as assign() describes them."""
+    L.call('zs_vq_assign', 'ZsVqAssign', stream, dtype=dt, src_f32=0, x=x, n=n, ld_x=ld_x, code=L.ptr(code), ld_code=code.stride(0),
+           cnorm=L.ptr(cnorm), K=code.shape[0], E=(int(code.shape[1]) if E is None else int(E)), idx=L.ptr(idx), dist=L.ptr(dist),
+           moved=L.ptr(moved), count_moved=int(moved is not None), work=L.ptr(work),
+           work_bytes=(0 if work is None else work.numel() * work.element_size()))
+
+
 def assign(x, code, cnorm, idx=None, dist=None, moved=None, work=None, E=None):
     """zs_vq_assign on the current stream.  x fp32 / bf16 [n, >= E] (rows at stride(0)), code fp32 [K, E], cnorm fp32 [K]; every output
     optional: idx int32 [n], dist fp32 [n], moved int32 [1] (added to: the rows whose idx changes).  work: workspace(dev), or None for
@@ -68,25 +72,33 @@ def assign(x, code, cnorm, idx=None, dist=None, moved=None, work=None, E=None):
     E = int(code.shape[1]) if E is None else int(E)
     _check_x(x, E)
     n = int(x.shape[0])
-    L.call('zs_vq_assign', 'ZsVqAssign', _stream(x.device), dtype=(L.ZS_F32 if x.dtype == torch.float32 else L.ZS_BF16), src_f32=0,
-           x=L.ptr(x), n=n, ld_x=(x.stride(0) if n > 1 else max(int(x.shape[1]), E)), code=L.ptr(code), ld_code=code.stride(0),
-           cnorm=L.ptr(cnorm), K=code.shape[0], E=E, idx=L.ptr(idx), dist=L.ptr(dist), moved=L.ptr(moved),
-           count_moved=int(moved is not None), work=L.ptr(work), work_bytes=(0 if work is None else work.numel() * work.element_size()))
+    launch_assign(_stream(x.device), (L.ZS_F32 if x.dtype == torch.float32 else L.ZS_BF16), L.ptr(x), n,
+                  (x.stride(0) if n > 1 else max(int(x.shape[1]), E)), code, cnorm, E=E, idx=idx, dist=dist, moved=moved, work=work)
+
+
+def launch_gather(stream, dt, idx, code, start, length, n_frag, T, dst, ld_dst, bad, E=None):
+    """THE zs_vq_gather launch: the operand [n_frag, T, ld_dst] of the compute dtype dt at the device pointer dst from idx int32
+    [n_idx], code fp32 [K, E] and the device tables start int64 / length int32 [n_frag]; bad int32 [1] is added to."""
+    L.call('zs_vq_gather', 'ZsVqGather', stream, dtype=dt, idx=L.ptr(idx), n_idx=idx.numel(), code=L.ptr(code), ld_code=code.stride(0),
+           K=code.shape[0], E=(int(code.shape[1]) if E is None else int(E)), start=L.ptr(start), len=L.ptr(length), n_frag=n_frag,
+           T=int(T), dst=dst, ld_dst=ld_dst, bad=L.ptr(bad))
 
 
 def gather(idx, code, start, length, T, dst, bad, E=None):
     """zs_vq_gather on the current stream: dst [n_frag, T, ld] (fp32 / bf16, contiguous) from idx int32 [n_idx] and the device tables
     start int64 / length int32 [n_frag]; bad int32 [1] is added to."""
-    E = int(code.shape[1]) if E is None else int(E)
-    L.call('zs_vq_gather', 'ZsVqGather', _stream(dst.device), dtype=(L.ZS_F32 if dst.dtype == torch.float32 else L.ZS_BF16), idx=L.ptr(idx),
-           n_idx=idx.numel(), code=L.ptr(code), ld_code=code.stride(0), K=code.shape[0], E=E, start=L.ptr(start), len=L.ptr(length),
-           n_frag=start.numel(), T=int(T), dst=L.ptr(dst), ld_dst=dst.shape[-1], bad=L.ptr(bad))
+    launch_gather(_stream(dst.device), (L.ZS_F32 if dst.dtype == torch.float32 else L.ZS_BF16), idx, code, start, length, start.numel(), T,
+                  L.ptr(dst), dst.shape[-1], bad, E=E)
 
 
-class VectorCodebook(object):
+class VectorCodebook(CodebookFile):
     """K codewords of E real columns: `vectors` fp32 [K, E] and `cnorm` fp32 [K] (the squared norms, summed in double) on the host, and
     `meta`: enc_mode, n_rows, seed, shift and the per-iteration history [(sum of distances, moved, empties)] of the fit."""
     kind = 'vector'
+    label, payload, suffix, _payload_error = 'vector codebook', 'vectors', 'vq.npz', 'vectors'
+    _dir_files = '*.wav'
+    _fit_line = ('[Codebook] - K = %d vectors over %d rows of %d files: %d iterations, summed distance %.6g, %d symbols used, '
+                 '%.3f bits per unit -> %s')
 
     def __init__(self, vectors, meta=None):
         v = np.asarray(vectors)
@@ -102,58 +114,24 @@ class VectorCodebook(object):
         self.cnorm = host_cnorm(self.vectors)
         self._dev = {}
 
-    def save(self, path):
-        with open(path, 'wb') as f:
-            np.savez(f, kind=np.array('vector'), format_version=np.int64(FORMAT_VERSION), K=np.int64(self.K), E=np.int64(self.E),
-                     vectors=self.vectors, meta=np.array(json.dumps(self.meta)))
-
     @classmethod
-    def load(cls, path, E=None):
-        """ValueError naming the field for a malformed file, and for a width other than E (the Decoder's c_in) when E is given."""
-        return cls._from_fields(_read_npz(path), path, E)
+    def _from_payload(cls, vectors, E, meta):
+        return cls(vectors, meta)                                  # the file's E is compared with the columns behind this
 
-    @classmethod
-    def _from_fields(cls, d, path, E=None):
-        for k in ('kind', 'format_version', 'K', 'E', 'vectors', 'meta'):
-            if k not in d:
-                raise ValueError('%s: vector codebook field %r is missing' % (path, k))
-        if d['kind'].shape != () or d['kind'].dtype.kind != 'U' or str(d['kind']) != 'vector':
-            raise ValueError("%s: vector codebook field kind must be 'vector'" % path)
-        for k in ('format_version', 'K', 'E'):
-            if d[k].shape != () or d[k].dtype.kind not in 'iu':
-                raise ValueError('%s: vector codebook field %r must be one integer' % (path, k))
-        if int(d['format_version']) != FORMAT_VERSION:
-            raise ValueError('%s: vector codebook field format_version is %d, this build reads %d' %
-                             (path, int(d['format_version']), FORMAT_VERSION))
-        try:
-            meta = json.loads(str(d['meta']))
-            if not isinstance(meta, dict):
-                raise ValueError('not an object')
-        except ValueError as e:
-            raise ValueError('%s: vector codebook field meta is not a json object (%s)' % (path, e))
-        try:
-            cb = cls(d['vectors'], meta)
-        except ValueError as e:
-            raise ValueError('%s: vector codebook field vectors: %s' % (path, e))
-        if cb.K != int(d['K']):
-            raise ValueError('%s: vector codebook field K is %d but vectors has %d rows' % (path, int(d['K']), cb.K))
-        if cb.E != int(d['E']):
-            raise ValueError('%s: vector codebook field E is %d but vectors has %d columns' % (path, int(d['E']), cb.E))
-        if E is not None:
-            cb.check_width(E, path)
-        return cb
+    @staticmethod
+    def check_mode(enc_mode, who="a vector codebook serves enc_mode 'continues'"):
+        """A vector codebook serves enc_mode 'continues' and no other mode; `who`: the caller's own opening of the refusal."""
+        if enc_mode != 'continues':
+            raise ValueError("%s: this model's enc_mode is %r" % (who, enc_mode))
 
-    def check_width(self, E, where='codebook'):
-        if int(E) != self.E:
-            raise ValueError("%s: codebook field E is %d, the Decoder's input width (c_in) is %d" % (where, self.E, int(E)))
+    def _upload(self, dev):
+        """(vectors, cnorm) on the device."""
+        return torch.from_numpy(self.vectors).to(dev), torch.from_numpy(self.cnorm).to(dev)
 
-    def to(self, dev):
-        """(vectors, cnorm) on the device, uploaded once."""
-        dev = torch.device(dev)
-        t = self._dev.get(dev)
-        if t is None:
-            t = self._dev[dev] = (torch.from_numpy(self.vectors).to(dev), torch.from_numpy(self.cnorm).to(dev))
-        return t
+    def units(self):
+        """What batched conversion and the folder drivers do with units under this codebook (convert._VectorUnits)."""
+        from .convert import _VectorUnits
+        return _VectorUnits(self)
 
     def snap(self, x_dev, work=None):
         """(idx int32 [n], dist fp32 [n]) of the rows of x_dev (fp32 / bf16 [n, >= E]), on the device."""
@@ -163,53 +141,43 @@ class VectorCodebook(object):
         assign(x_dev, code, cn, idx=idx, dist=dist, work=work)
         return idx, dist
 
+    @classmethod
+    def _dir_rows(cls, trainer, seg_len, in_dir, batch, E):
+        """The *.wav of in_dir as the encoder's fp32 rows, left on the device (convert.encode_rows_on_device).  *.txt files are
+        ignored: what write_encodings writes for 'continues' carries no encoding."""
+        from . import convert as cv
+        return encode_dir(trainer, seg_len, in_dir, batch, lambda specs: cv.encode_rows_on_device(specs, trainer, seg_len))[:3]
 
-def _read_npz(path):
-    try:
-        z = np.load(path, allow_pickle=False)
-        return {k: z[k] for k in z.files}
-    except Exception as e:
-        raise ValueError('%s is not a codebook file: %s' % (path, e))
+    @classmethod
+    def _fit(cls, x_dev, K, iters, seed, E, enc_mode):
+        return fit_vectors(x_dev, K, iters=iters, seed=seed, enc_mode=enc_mode)
+
+    def _indices(self, x_dev):
+        return self.snap(x_dev, work=(workspace(x_dev.device) if x_dev.shape[0] < SPLIT_N else None))[0]
+
+
+def kind_for(enc_mode):
+    """The codebook class that serves enc_mode: VectorCodebook for 'continues', the bit Codebook for every other mode."""
+    return VectorCodebook if enc_mode == 'continues' else Codebook
 
 
 def load_codebook(path, enc_mode, E=None):
     """The codebook of a file, by the file's own fields: a VectorCodebook (field kind == 'vector') serves enc_mode 'continues' and no
     other mode; a bit Codebook serves every other mode and is refused for 'continues' in the bit codebook's own words."""
-    d = _read_npz(path)
+    d = read_npz(path)
     if 'kind' in d or 'vectors' in d:
-        if enc_mode != 'continues':
-            raise ValueError("%s is a vector codebook (kind 'vector'), which serves enc_mode 'continues': this model's enc_mode is %r" %
-                             (path, enc_mode))
-        return VectorCodebook._from_fields(d, path, E)
-    refuse_continues(enc_mode)
-    return Codebook.load(path, E=E)
+        VectorCodebook.check_mode(enc_mode, "%s is a vector codebook (kind 'vector'), which serves enc_mode 'continues'" % path)
+        return VectorCodebook.from_fields(d, path, E)
+    Codebook.check_mode(enc_mode)
+    return Codebook.from_fields(d, path, E)
 
 
 def init_rows(x, K, seed):
     """codebook.init_rows' rule over fp32 rows: the first K pairwise different rows along RandomState(seed).permutation(n)."""
-    n, K = int(x.shape[0]), int(K)
-    perm = np.random.RandomState(seed).permutation(n)
-    seen, out, at, step = set(), [], 0, max(4096, 4 * K)
-    while at < n:
-        sel = perm[at:at + step]
+    def rows_at(sel):
         rows = x[torch.from_numpy(sel).to(x.device)].cpu().numpy() if torch.is_tensor(x) else np.asarray(x)[sel]
-        for i, r in zip(sel, np.ascontiguousarray(rows, dtype=np.float32)):
-            key = r.tobytes()
-            if key not in seen:
-                seen.add(key)
-                out.append(int(i))
-                if len(out) == K:
-                    return np.asarray(out, dtype=np.int64)
-        at += step
-        step *= 4
-    raise ValueError('init_rows: the rows hold %d distinct vectors, fewer than K = %d' % (len(seen), K))
-
-
-def reseed_rows(cnt, dist):
-    """(the empty k in increasing order, the rows they take): the rows of largest dist, ties to the lowest row, each row once."""
-    empties = np.flatnonzero(np.asarray(cnt) == 0)
-    order = np.argsort(-np.asarray(dist, dtype=np.float64), kind='stable')[:len(empties)]
-    return empties, order
+        return np.ascontiguousarray(rows, dtype=np.float32)
+    return first_distinct(int(x.shape[0]), K, seed, rows_at, ('rows', 'vectors'))
 
 
 def fit_vectors(x_dev, K, iters=40, seed=0, on_iter=None, enc_mode='continues'):
@@ -274,41 +242,12 @@ def fit_vectors(x_dev, K, iters=40, seed=0, on_iter=None, enc_mode='continues'):
 
 
 def fit_dir(trainer, seg_len, in_dir, K, out_path, iters=40, seed=0, batch=64):
-    """--fit_codebook for a 'continues' model: a vector codebook of K codewords over the encoder rows of a folder.  The *.wav of
-    in_dir are read and encoded as codebook.fit_dir reads them (the same plan, trimming and skip list); the encoder's fp32 rows stay
-    on the device (convert.encode_rows_on_device).  *.txt files are ignored: what write_encodings writes for 'continues' carries no
-    encoding.  Writes the codebook to out_path and the same fit_codebook.json beside it (symbols used and entropy through
-    codebook.usage); returns (VectorCodebook, that report)."""
-    import os
-    from . import convert as cv
-    from .codebook import encode_dir
-    if trainer.enc_mode != 'continues':
-        raise ValueError("a vector codebook serves enc_mode 'continues': this model's enc_mode is %r" % trainer.enc_mode)
-    K = int(K)
-    if not 1 <= K <= MAX_K:
-        raise ValueError('--fit_codebook: K must be in [1, %d] (got %d)' % (MAX_K, K))
-    E = int(trainer.Decoder.c_in)
-    used, skipped, parts, _ = encode_dir(trainer, seg_len, in_dir, batch, lambda specs: cv.encode_rows_on_device(specs, trainer, seg_len))
-    if not parts:
-        raise ValueError('--fit_codebook: %s holds no usable *.wav' % in_dir)
-    x_dev = torch.cat(parts, dim=0).contiguous()
-    cb = fit_vectors(x_dev, K, iters=iters, seed=seed, enc_mode=trainer.enc_mode)
-    cb.check_width(E, out_path)
-    idx, _ = cb.snap(x_dev, work=(workspace(x_dev.device) if x_dev.shape[0] < SPLIT_N else None))
-    n_used, entropy = usage(idx, K)
-    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-    cb.save(out_path)
-    report = {'codebook': out_path, 'kind': 'vector', 'K': K, 'E': E, 'in_dir': in_dir, 'files': used, 'skipped': skipped,
-              'n_units': int(x_dev.shape[0]), 'seed': int(seed), 'history': cb.meta['history'], 'symbols_used': n_used,
-              'entropy_bits_per_unit': entropy}
-    with open(os.path.join(os.path.dirname(os.path.abspath(out_path)), 'fit_codebook.json'), 'w') as f:
-        json.dump(report, f, indent=1)
-    print('[Codebook] - K = %d vectors over %d rows of %d files: %d iterations, summed distance %.6g, %d symbols used, %.3f bits per unit '
-          '-> %s' % (K, x_dev.shape[0], len(used), len(cb.meta['history']), cb.meta['history'][-1][0], n_used, entropy, out_path))
-    return cb, report
+    """--fit_codebook for a 'continues' model: a vector codebook of K codewords over the encoder rows of a folder
+    (CodebookFile.fit_dir).  The *.wav of in_dir are read and encoded as codebook.fit_dir reads them (the same plan, trimming and
+    skip list); *.txt files are ignored.  Returns (VectorCodebook, the report written to fit_codebook.json)."""
+    return VectorCodebook.fit_dir(trainer, seg_len, in_dir, K, out_path, iters, seed, batch)
 
 
 def default_path(ckpt_dir, K):
     """{ckpt_dir}/codebooks/K<K>.vq.npz"""
-    import os
-    return os.path.join(ckpt_dir, 'codebooks', 'K%d.vq.npz' % int(K))
+    return VectorCodebook.default_path(ckpt_dir, K)

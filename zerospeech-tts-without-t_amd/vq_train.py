@@ -107,9 +107,7 @@ class VqBottleneck(object):
         self.code_live.copy_(self.code)                          # the codebook the step before left
         self.cnorm_live.copy_(self.cnorm)
         self.acc.zero_()
-        L.call('zs_vq_assign', 'ZsVqAssign', st, dtype=ctx.dt, src_f32=0, x=bits.ptr(), n=n, ld_x=bits.ld, code=L.ptr(self.code_live),
-               ld_code=E, cnorm=L.ptr(self.cnorm_live), K=K, E=E, idx=L.ptr(self.idx), work=L.ptr(self.work),
-               work_bytes=(0 if self.work is None else vq.WORK_BYTES))
+        vq.launch_assign(st, ctx.dt, bits.ptr(), n, bits.ld, self.code_live, self.cnorm_live, idx=self.idx, work=self.work)
         q = ctx.act('vq_q_%d_%d' % (bits.B, bits.T), bits.B, bits.T, E)
         zf = self.z_f32
         L.call('zs_vq_commit', 'ZsVqCommit', st, dtype=ctx.dt, z=bits.ptr(), n=n, ld_z=bits.ld, idx=L.ptr(self.idx),
@@ -197,8 +195,7 @@ def check_vq_train(args, enc_mode=None, c_in=None):
         check_decay(args.vq_decay)
     if enc_mode is None:
         return None
-    if enc_mode != 'continues':
-        raise ValueError("--vq_train needs enc_mode 'continues': this model's enc_mode is %r" % enc_mode)
+    vq.VectorCodebook.check_mode(enc_mode, "--vq_train needs enc_mode 'continues'")
     try:
         return vq.load_codebook(path, enc_mode, E=c_in)
     except ValueError as e:
