@@ -1219,8 +1219,8 @@ int zs_vq_gather(const ZsVqGather* p, void* stream);
 /* ---------------------------------------------------------------------------------------------
  * Training through the vector codebook (zs_amd.vq_train): the straight-through quantiser between the 'continues' Encoder and
  * the Decoder, its commitment term and the exponential moving average that moves the codebook after the encoder.  One training
- * iteration is zs_vq_assign (above, unchanged) -> zs_vq_commit -> zs_vq_accum (above, unchanged) -> zs_vq_ema in the forward and
- * zs_vq_st_bwd in the backward.  `code` fp32 [K][ld_code] and the limits on K, E, n and the leading dimensions are the vector
+ * iteration is zs_vq_assign (above, unchanged) -> zs_vq_commit -> zs_vq_accum (above, unchanged) -> zs_vq_ema (-> zs_vq_restart when
+ * dead codewords are restarted) in the forward and zs_vq_st_bwd in the backward.  `code` fp32 [K][ld_code] and the limits on K, E, n and the leading dimensions are the vector
  * codebook's (above).  A null struct, a K, E or n outside its range, a leading dimension below E, a null operand with work to do or a
  * misaligned operand return ZS_EINVAL and launch nothing; n == 0 succeeds and launches nothing.  Caller-owned buffers, no allocation,
  * no synchronisation, stream-ordered; no launch argument depends on the iteration, so a captured graph replays them.  No float
@@ -1286,6 +1286,34 @@ typedef struct {
   int32_t* used;
 } ZsVqEma;
 int zs_vq_ema(const ZsVqEma* p, void* stream);
+/* zs_vq_restart: dead codewords go back onto this step's encoder rows, directly behind zs_vq_ema on the same stream.
+ * x fp32 [n][ld_x] (the rows zs_vq_accum read), idx_acc int32 [n] (optional: zs_vq_commit's), cnt int32 [K] (zs_vq_accum's), and
+ * N, m [K][E] dense, code [K][ld_code], cnorm as zs_vq_ema just left them.  thresh fp32 in (0, 1); 1 <= stride <= n.
+ *   dead(k)  = cnt[k] == 0 && N[k] < thresh            (fp32 comparison: NaN and equality are not dead)
+ *   j(k)     = #{k' < k : dead(k')}
+ *   start    = mix64(seed + *seed_ptr + 0x5651524553544152) mod n      (unsigned 64-bit, wrapping; seed_ptr optional)
+ *   mix64(z) : z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *   r(k)     = (start + (j(k) mod n) * stride) mod n
+ * For every dead k: when idx_acc is given and idx_acc[r(k)] < 0 the codeword stays and *skipped += 1; else code[k][j] = m[k][j] =
+ * x[r(k)][j] for j < E, N[k] = 1, cnorm[k] = the double sum of squares in zs_vq_ema's order rounded once, and *restarted += 1
+ * (both int32, required).  Columns E <= j < ld_code are not touched.  work int32 [K + 2], required, undefined afterwards.  Two
+ * launches: one workgroup ranks the K flags into work, then one workgroup per dead codeword (at most 1024, striding) copies its row;
+ * with nothing dead the second reads one word per workgroup and writes nothing.  n == 0 succeeds and launches nothing; a thresh
+ * outside (0, 1) or a stride outside [1, n] is ZS_EINVAL as the cases above are.  No float atomics. */
+typedef struct {
+  float thresh;
+  const float* x; int64_t n, ld_x;
+  const int32_t* idx_acc;
+  const int32_t* cnt; int32_t K, E;
+  float* N; float* m;
+  float* code; int64_t ld_code; float* cnorm;
+  uint64_t seed;
+  const uint64_t* seed_ptr;
+  int32_t stride;
+  int32_t* work;
+  int32_t* restarted; int32_t* skipped;
+} ZsVqRestart;
+int zs_vq_restart(const ZsVqRestart* p, void* stream);
 
 #ifdef __cplusplus
 }

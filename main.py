@@ -88,6 +88,8 @@ codebook -- every encoder row of a batch is snapped to its nearest codeword in f
 straight through; --vq_beta B (default 0.25, in (0, 10]) weighs the commitment term that keeps the encoder near its codewords, and the
 codebook follows the encoder by an exponential moving average of decay --vq_decay D (default 0.99, in [0, 1)).  The log gains loss_vq,
 the share of codewords used and the perplexity; every checkpoint gets <checkpoint>.vq.npz beside it, the file --codebook reads.
+--vq_restart T (in (0, 1); off by default) puts a codeword that took no row of the batch and whose averaged count fell below T back
+onto one of the batch's encoder rows, on the device inside the step; the log then ends with the restarts so far.
 --ema, --device_data and --load_model combine with it; --resume, --valid_every, a multi-rank launch and every other --train* mode are
 refused before anything is built:
   python main.py --enc_mode continues --train_ae --load_model --vq_train ckpt_english/codebooks/K1024.vq.npz
@@ -264,6 +266,9 @@ def build_parser():
     p.add_argument('--vq_beta', type=float, default=None, metavar='B', help='with --vq_train: commitment weight in (0, 10] (default 0.25)')
     p.add_argument('--vq_decay', type=float, default=None, metavar='D',
                    help="with --vq_train: decay of the codebook's moving average in [0, 1) (default 0.99)")
+    p.add_argument('--vq_restart', type=float, default=None, metavar='T',
+                   help='with --vq_train: a codeword that took no row of the batch and whose averaged count fell below T, in (0, 1), '
+                        "is put back onto one of the batch's encoder rows (default: dead codewords stay where they are)")
     p.add_argument('--out_sr', type=_out_sr, default=None,
                    help='sample rate of the wavs --test / --cross_test / --test_single write (hp.out_sr); default: 16000')
     return p
@@ -390,7 +395,7 @@ def check_codebook(parser, args):
 
 
 def check_vq_train(args, enc_mode=None, c_in=None):
-    """--vq_train, --vq_beta and --vq_decay are refused, before anything is built, where they cannot do what they say
+    """--vq_train, --vq_beta, --vq_decay and --vq_restart are refused, before anything is built, where they cannot do what they say
     (zs_amd.vq_train.check_vq_train): without --train_ae or beside another --train* mode, under a multi-rank launch, with --resume
     or --valid_every, the two options without --vq_train or out of range; and, once enc_mode is known (argument_runner calls
     this again after reading hps), an enc_mode other than 'continues', a bit codebook or a width other than the Decoder's c_in.
@@ -520,6 +525,8 @@ def main(argv=None):
             from zs_amd.vq_train import BETA, DECAY
             vq_train = (args.vq_codebook, args.vq_beta if args.vq_beta is not None else BETA,
                         args.vq_decay if args.vq_decay is not None else DECAY)
+            if args.vq_restart is not None:
+                vq_train += (args.vq_restart,)
         trainer = Trainer(hps, data_loader, args.g_mode, args.enc_mode, dtype=args.dtype, ema=args.ema, valid=valid, vq_train=vq_train)
         if args.load_model:
             trainer.load_model(os.path.join(args.ckpt_dir, args.load_train_model_name), load_model_list=hps.load_model_list,

@@ -7,7 +7,14 @@
             step's dtype): HIP events around a replayed graph of launches
   parent    (--parent DIR, a built tree of the parent commit) `bench.py --gpus 1 --steps 20 --warmup 5` in each tree, a fresh process
             per run, alternating, three runs each: the headline path launches nothing new, so the two ranges must overlap
-    python tools/vq_train_bench.py [--parent DIR] [--rounds 7] [--steps 10] [--dtype bf16] [--out profiles/vq_train_step_ms.json]"""
+    python tools/vq_train_bench.py [--parent DIR] [--rounds 7] [--steps 10] [--dtype bf16] [--out profiles/vq_train_step_ms.json]
+With --restart T the same job measures the restart of dead codewords instead -> profiles/vq_restart_step_ms.json:
+  step      the replayed step with the bottleneck, without and with restart=T, alternating as above; the figures of the bottleneck
+            (used, perplexity, restarts, dead) at the end of those ~100 steps and again after --long steps in all
+  kernels   zs_vq_ema alone, zs_vq_restart alone with nothing dead, and with all but one codeword dead (each launch behind a fill that
+            makes them dead again; the fill alone is timed beside it)
+  parent    as above
+    python tools/vq_train_bench.py --restart 0.01 [--decay 0.99] [--long 1000] [--parent DIR]"""
 import argparse
 import json
 import os
@@ -57,7 +64,7 @@ def _batch(kind, B, T, F, g):
     return x.clamp(1e-3, 0.999)
 
 
-def _pair(hps, dtype, dev, B, with_vq, kind):
+def _pair(hps, dtype, dev, B, with_vq, kind, restart=None, decay=None):
     """An Encoder / Decoder pair of the run's sizes and its captured AEStep on one batch."""
     import torch
     from zs_amd import layers
@@ -78,7 +85,10 @@ def _pair(hps, dtype, dev, B, with_vq, kind):
         rows = z.reshape(-1, hps.enc_size)
         pick = torch.randint(0, rows.shape[0], (K,), generator=g).to(dev)
         code = (rows[pick] + 0.05 * rows.std() * torch.randn(K, hps.enc_size, device=dev)).float().cpu().numpy()
-        bn = VqBottleneck(VectorCodebook(code, {'enc_mode': 'continues'}), rows=encoded_rows(B, hps.seg_len), ctx=layers.Ctx(dev, dtype))
+        more = {} if restart is None else {'restart': restart}
+        if decay is not None:
+            more['decay'] = decay
+        bn = VqBottleneck(VectorCodebook(code, {'enc_mode': 'continues'}), rows=encoded_rows(B, hps.seg_len), ctx=layers.Ctx(dev, dtype), **more)
     ae = AEStep(enc, dec, lr=hps.lr, max_grad_norm=hps.max_grad_norm, use_graph=True, vq=bn)
     for _ in range(ae.graph_warmup + 2):                          # the eager warm-up steps, the capture, one replay
         ae.step(x, c)
@@ -94,6 +104,9 @@ def step(args, out):
     hps = Hps(os.path.join(HERE, 'hps', 'zerospeech_english_1024.json')).get_tuple()
     out['step'] = {}
     for kind, B in (('formants', 16), ('formants', 256), ('noise', 16), ('noise', 256)):
+        if args.restart is not None:
+            restart_step(args, out, hps, dev, kind, B)
+            continue
         runs = {'off': _pair(hps, args.dtype, dev, B, False, kind), 'vq_K1024': _pair(hps, args.dtype, dev, B, True, kind)}
 
         def timed(name):
@@ -129,6 +142,100 @@ def step(args, out):
         print('[vq_train_bench] step %s B %d: %s' % (kind, B, json.dumps(rec)), file=sys.stderr, flush=True)
         del runs, bn
         torch.cuda.empty_cache()
+
+
+def restart_step(args, out, hps, dev, kind, B):
+    """The replayed step with the bottleneck, without and with restart, and what the codebook looks like afterwards."""
+    import torch
+    runs = {'vq_K1024': _pair(hps, args.dtype, dev, B, True, kind, decay=args.decay),
+            'vq_restart': _pair(hps, args.dtype, dev, B, True, kind, restart=args.restart, decay=args.decay)}
+    done = {k: v[0].graph_warmup + 2 for k, v in runs.items()}
+
+    def timed(name):
+        ae, x, c, _ = runs[name]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            ae.step(x, c)
+        torch.cuda.synchronize()
+        done[name] += args.steps
+        return (time.perf_counter() - t0) * 1e3 / args.steps
+    ms = {k: [] for k in runs}
+    names = tuple(runs)
+    for r in range(-1, args.rounds):
+        for name in (names if r % 2 == 0 else names[::-1]):
+            t = timed(name)
+            if r >= 0:
+                ms[name].append(t)
+    rec = {k: _stats(v) for k, v in ms.items()}
+    rec.update(rows=runs['vq_K1024'][3].rows, K=K, E=hps.enc_size, steps_per_round=args.steps, restart=args.restart, decay=runs['vq_K1024'][3].decay,
+               restart_minus_plain_ms=round(rec['vq_restart']['median_ms'] - rec['vq_K1024']['median_ms'], 4))
+    for name, (ae, x, c, bn) in runs.items():
+        rec[name]['after_%d_steps' % done[name]] = bn.stats()
+        while done[name] < args.long:
+            ae.step(x, c)
+            done[name] += 1
+        rec[name]['after_%d_steps' % done[name]] = bn.stats()
+    out['step']['%s_B%d' % (kind, B)] = rec
+    print('[vq_train_bench] restart step %s B %d: %s' % (kind, B, json.dumps(rec)), file=sys.stderr, flush=True)
+    del runs
+    torch.cuda.empty_cache()
+
+
+def restart_kernels(args, out):
+    """zs_vq_ema and zs_vq_restart alone at K = E = 1024 and 256 / 4096 rows: HIP events around a replayed graph of launches."""
+    import torch
+    from zs_amd import _lib as L
+    from zs_amd.vq_train import restart_stride
+    dev = torch.device('cuda:0')
+    E = 1024
+    g = torch.Generator().manual_seed(0)
+    code = torch.randn(K, E, generator=g).to(dev)
+    out['kernels'] = {}
+    for n, calls in ((256, 40), (4096, 20)):
+        x = torch.randn(n, E, generator=g).to(dev)
+        ia = (torch.arange(n, dtype=torch.int32) % K).to(dev)
+        cnt, sums = torch.zeros(K, dtype=torch.int32, device=dev), torch.zeros(K, E, dtype=torch.int64, device=dev)
+        N, m, code2, cn2 = torch.ones(K, device=dev), code.clone(), code.clone(), (code.double() ** 2).sum(1).float()
+        cnt_live = torch.ones(K, dtype=torch.int32, device=dev)
+        cnt_dead = torch.zeros(K, dtype=torch.int32, device=dev)
+        cnt_dead[0] = 1
+        work, stat = torch.zeros(K + 2, dtype=torch.int32, device=dev), torch.zeros(4, dtype=torch.int32, device=dev)
+        seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        st = lambda: torch.cuda.current_stream().cuda_stream
+        restart = lambda c: L.call('zs_vq_restart', 'ZsVqRestart', st(), thresh=args.restart, x=L.ptr(x), n=n, ld_x=E, idx_acc=L.ptr(ia),
+                                   cnt=L.ptr(c), K=K, E=E, N=L.ptr(N), m=L.ptr(m), code=L.ptr(code2), ld_code=E, cnorm=L.ptr(cn2), seed=1,
+                                   seed_ptr=L.ptr(seed_dev), stride=restart_stride(n), work=L.ptr(work), restarted=L.ptr(stat),
+                                   skipped=L.ptr(stat, 1))
+        kill = lambda: N.fill_(0.5 * args.restart)
+        fns = {
+            'zs_vq_ema': lambda: L.call('zs_vq_ema', 'ZsVqEma', st(), cnt=L.ptr(cnt), sum=L.ptr(sums), K=K, E=E, shift=20, decay=0.99, N=L.ptr(N),
+                                        m=L.ptr(m), code=L.ptr(code2), ld_code=E, cnorm=L.ptr(cn2), used=L.ptr(stat, 3)),
+            'zs_vq_restart_nothing_dead': lambda: restart(cnt_live),
+            'fill_N_alone': kill,
+            'fill_N_then_zs_vq_restart_all_but_one_dead': lambda: (kill(), restart(cnt_dead)),
+        }
+        rec = {'n': n, 'K': K, 'E': E, 'launches_per_replay': calls}
+        for name, fn in fns.items():
+            if name == 'zs_vq_restart_nothing_dead':
+                N.fill_(1.0)                                      # (zs_vq_ema let it decay)
+                stat.zero_()
+            fn()
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                for _ in range(calls):
+                    fn()
+            graph.replay()
+            rec[name] = _events(graph.replay, per=calls)
+            if name == 'zs_vq_restart_nothing_dead':
+                assert int(stat[0]) == 0 and int(stat[1]) == 0
+        assert int(stat[0]) == (K - 1) * (1 + calls * 8) and int(stat[1]) == 0, stat      # (the eager call, one replay, seven timed ones)
+        rec['restart_all_but_one_dead_minus_fill_us'] = round(rec['fill_N_then_zs_vq_restart_all_but_one_dead']['median_us'] -
+                                                              rec['fill_N_alone']['median_us'], 2)
+        rec['nothing_dead_not_above_ema'] = rec['zs_vq_restart_nothing_dead']['median_us'] <= rec['zs_vq_ema']['median_us']
+        out['kernels']['rows%d' % n] = rec
+        print('[vq_train_bench] restart kernels rows %d: %s' % (n, json.dumps(rec)), file=sys.stderr, flush=True)
 
 
 def kernels(args, out):
@@ -214,8 +321,13 @@ def main():
     p.add_argument('--steps', type=int, default=10, help='replays per timed round')
     p.add_argument('--dtype', default='bf16')
     p.add_argument('--only', default=None, choices=['step', 'kernels', 'parent'])
-    p.add_argument('--out', default=os.path.join(HERE, 'profiles', 'vq_train_step_ms.json'))
+    p.add_argument('--restart', type=float, default=None, metavar='T', help='measure zs_vq_restart at this threshold (DESIGN 32) instead')
+    p.add_argument('--decay', type=float, default=None, help='with --restart: the decay of the codebook\'s average (default: the run\'s, 0.99)')
+    p.add_argument('--long', type=int, default=1000, help='with --restart: steps in all before the second look at the codebook')
+    p.add_argument('--out', default=None)
     args = p.parse_args()
+    if args.out is None:
+        args.out = os.path.join(HERE, 'profiles', 'vq_train_step_ms.json' if args.restart is None else 'vq_restart_step_ms.json')
     if args.rounds < 5:
         p.error('--rounds must be at least 5')
     sys.path.insert(0, HERE)
@@ -230,7 +342,7 @@ def main():
             out = dict(json.load(f), **out)
     if args.parent is not None and args.only in (None, 'parent'):  # first, while this process holds no GPU memory
         bench_against_parent(args, out)
-    for name, part in (('kernels', kernels), ('step', step)):
+    for name, part in (('kernels', kernels if args.restart is None else restart_kernels), ('step', step)):
         if args.only in (None, name):
             part(args, out)
     text = json.dumps(out, indent=1)

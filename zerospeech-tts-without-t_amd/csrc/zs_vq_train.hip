@@ -8,6 +8,8 @@
 //                       a workgroup's sum goes to partial[workgroup] and vq_commit_finish_kernel adds the partials.
 //   vq_st_bwd_kernel    one lane per 16-byte piece of dz, grid-stride.
 //   vq_ema_kernel       one workgroup per codeword, as vq_update_kernel (the same order of the norm's sum).
+//   vq_restart_*        zs_vq_restart: one workgroup ranks the dead codewords, then one workgroup per dead codeword copies
+//                       an encoder row over it, as vq_ema_kernel is laid out.
 #include "zs_common.h"
 
 // the definitions are stated operation by operation (a rounding each): nothing in this file may be fused into a multiply-add
@@ -219,6 +221,97 @@ __global__ void __launch_bounds__(VT_NT) vq_ema_kernel(const ZsVqEma p, const do
   }
 }
 
+// ---- restart of dead codewords ---------------------------------------------------------------------------------------------
+constexpr int VR_MAX_WG = 1024;                                   // workgroups of the copy: more dead codewords than that stride
+
+// One workgroup ranks the K flags: a coalesced pass leaves them as 64-bit ballots in LDS (K / 64 <= 1024 words), lane t owns the
+// contiguous words [t wp, (t + 1) wp), counts them, the counts are scanned over the wave and then over the four waves, and every lane
+// writes the k of its dead codewords to work[rank].  work[K] = the number of dead codewords.
+__global__ void __launch_bounds__(VT_NT) vq_restart_rank_kernel(const ZsVqRestart p) {
+  __shared__ unsigned long long s_bits[ZS_CODE_MAX_K / 64];
+  __shared__ int s_wave[VT_NT / 64];
+  const int tid = threadIdx.x, lane = tid & 63;
+#pragma unroll 4
+  for (int base = 0; base < p.K; base += VT_NT) {                 // (the same trip count for every lane: the ballot sees whole waves)
+    const int k = base + tid;
+    bool dead = false;
+    if (k < p.K) {
+      const int c = p.cnt[k];
+      const float n = p.N[k];
+      dead = c == 0 && n < p.thresh;                              // (NaN: not below)
+    }
+    const unsigned long long b = __ballot(dead);
+    if (lane == 0) s_bits[(base >> 6) + (tid >> 6)] = b;
+  }
+  __syncthreads();
+  const int words = (p.K + 63) >> 6, wp = (words + VT_NT - 1) / VT_NT;
+  const int lo = tid * wp < words ? tid * wp : words, hi = lo + wp < words ? lo + wp : words;
+  int mine = 0;
+  for (int w = lo; w < hi; ++w) mine += __popcll(s_bits[w]);
+  int inc = mine;                                                 // inclusive over the wave
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += v;
+  }
+  if (lane == 63) s_wave[tid >> 6] = inc;
+  __syncthreads();
+  int rank = inc - mine;
+  for (int w = 0; w < (tid >> 6); ++w) rank += s_wave[w];
+  for (int w = lo; w < hi; ++w) {
+    unsigned long long b = s_bits[w];
+    while (b) {
+      p.work[rank++] = (w << 6) + (__ffsll(b) - 1);
+      b &= b - 1;
+    }
+  }
+  if (tid == VT_NT - 1) p.work[p.K] = rank;                       // (the last lane's rank behind its own words: all of them)
+}
+
+__device__ __forceinline__ uint64_t vr_mix64(uint64_t z) {
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27; z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z;
+}
+
+// One workgroup per dead codeword, laid out as vq_ema_kernel (the same order of the norm's sum).
+__global__ void __launch_bounds__(VT_NT) vq_restart_copy_kernel(const ZsVqRestart p) {
+  __shared__ double s_part[VT_NT / 64];
+  const int tid = threadIdx.x;
+  const int dead = p.work[p.K];
+  if ((int)blockIdx.x >= dead) return;                            // the usual case: nothing is written
+  const uint64_t n = (uint64_t)p.n;
+  const uint64_t start = vr_mix64(p.seed + (p.seed_ptr ? *p.seed_ptr : 0ull) + 0x5651524553544152ull) % n;
+  for (int j = blockIdx.x; j < dead; j += gridDim.x) {
+    const int k = p.work[j];
+    const int64_t r = (int64_t)((start + ((uint64_t)j % n) * (uint64_t)p.stride) % n);
+    if (p.idx_acc && p.idx_acc[r] < 0) {                          // left out of the average for its magnitude (the whole workgroup agrees)
+      if (tid == 0) atomicAdd(p.skipped, 1);
+      continue;
+    }
+    const float* xr = p.x + r * p.ld_x;
+    float* row = p.code + (int64_t)k * p.ld_code;
+    float* m = p.m + (int64_t)k * p.E;
+    double sq = 0.0;
+    for (int e = tid; e < p.E; e += VT_NT) {
+      const float v = xr[e];
+      row[e] = v;
+      m[e] = v;
+      sq += (double)v * (double)v;
+    }
+    sq = wave_sum_d(sq);
+    if ((tid & 63) == 0) s_part[tid >> 6] = sq;
+    __syncthreads();
+    if (tid == 0) {
+      p.N[k] = 1.f;
+      p.cnorm[k] = (float)(s_part[0] + s_part[1] + s_part[2] + s_part[3]);
+      atomicAdd(p.restarted, 1);
+    }
+    __syncthreads();                                              // s_part is written again in the next round
+  }
+}
+
 inline bool misaligned(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; }
 
 const char* vt_shape(int K, int E, int64_t n, int64_t ld_a, int64_t ld_b, int64_t ld_c) {
@@ -305,4 +398,22 @@ extern "C" int zs_vq_ema(const ZsVqEma* p, void* stream) {
                  !misaligned(p->cnorm, 4) && !misaligned(p->used, 4), "zs_vq_ema: an operand is not aligned to its element");
   hipLaunchKernelGGL(vq_ema_kernel, dim3((unsigned)p->K), dim3(VT_NT), 0, (hipStream_t)stream, *p, 1.0 - p->decay, ldexp(1.0, -p->shift));
   return zs_check_launch("zs_vq_ema");
+}
+
+extern "C" int zs_vq_restart(const ZsVqRestart* p, void* stream) {
+  ZS_REQUIRE(p, "zs_vq_restart: null argument");
+  const char* why = vt_shape(p->K, p->E, p->n, p->ld_x, p->ld_code, p->E);
+  ZS_REQUIRE(!why, "zs_vq_restart: %s (n %lld, K %d, E %d, ld_x %lld, ld_code %lld)", why, (long long)p->n, p->K, p->E, (long long)p->ld_x,
+             (long long)p->ld_code);
+  ZS_REQUIRE(p->thresh > 0.f && p->thresh < 1.f, "zs_vq_restart: thresh must be in (0, 1) (got %g)", (double)p->thresh);
+  if (p->n == 0) return ZS_OK;
+  ZS_REQUIRE(p->stride >= 1 && p->stride <= p->n, "zs_vq_restart: stride must be in [1, n] (got %d, n %lld)", p->stride, (long long)p->n);
+  ZS_REQUIRE(p->x && p->cnt && p->N && p->m && p->code && p->cnorm && p->work && p->restarted && p->skipped, "zs_vq_restart: null operand");
+  ZS_REQUIRE(!misaligned(p->x, 4) && !misaligned(p->idx_acc, 4) && !misaligned(p->cnt, 4) && !misaligned(p->N, 4) && !misaligned(p->m, 4) &&
+                 !misaligned(p->code, 4) && !misaligned(p->cnorm, 4) && !misaligned(p->seed_ptr, 8) && !misaligned(p->work, 4) &&
+                 !misaligned(p->restarted, 4) && !misaligned(p->skipped, 4), "zs_vq_restart: an operand is not aligned to its element");
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(vq_restart_rank_kernel, dim3(1), dim3(VT_NT), 0, st, *p);
+  hipLaunchKernelGGL(vq_restart_copy_kernel, dim3((unsigned)(p->K < VR_MAX_WG ? p->K : VR_MAX_WG)), dim3(VT_NT), 0, st, *p);
+  return zs_check_launch("zs_vq_restart");
 }

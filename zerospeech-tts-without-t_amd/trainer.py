@@ -135,7 +135,7 @@ class AEStep(object):
             bits, _, _ = ee.forward(x_btf, True, noise=noise, noise_kind=noise_kind, seed=seed, drop_masks=drop_masks,
                                     seed_ptr=seed_ptr)
             if vq is not None:
-                bits = vq.forward(bits)                                                   # the Decoder reads the codewords
+                bits = vq.forward(bits, seed, seed_ptr)                                   # the Decoder reads the codewords
             return self.l1_loss(de, x_btf, de.forward(bits, c, True))
 
         def update(name):
@@ -686,7 +686,8 @@ class Trainer(object):
                  vq_train=None):
         """vq_train (not in the reference): None, or (vq.VectorCodebook, beta, decay): train(mode='pretrain_AE') then trains through
         that codebook (vq_train.VqBottleneck inside the AEStep), logs loss_vq, the codewords used and the perplexity, and
-        writes <checkpoint>.vq.npz beside every checkpoint.  Every other mode runs without the quantiser.
+        writes <checkpoint>.vq.npz beside every checkpoint.  Every other mode runs without the quantiser.  A fourth element is the
+        threshold below which dead codewords are restarted; the log and the file's meta then carry the restarts.
         valid (not in the reference): None, or a validation.ValidConfig: train(mode='pretrain_AE') then validates on its set
         every `every` iterations and after the last one (ValidStep), logs and records the result and keeps the best checkpoint.
         ema (not in the reference): None, or the decay in [0, 1) of an exponential moving average of the weights that every
@@ -755,9 +756,10 @@ class Trainer(object):
         self.ae = AEStep(self.Encoder, self.Decoder, lr=hps.lr, betas=(0.5, 0.9), max_grad_norm=hps.max_grad_norm, ema=self.ema)
         if self.vq_train is not None:                   # the --train_ae loop alone: train() hands it to the AEStep for that mode
             from .vq_train import VqBottleneck, encoded_rows
-            cb, beta, decay = self.vq_train
+            cb, beta, decay = self.vq_train[:3]
+            restart = self.vq_train[3] if len(self.vq_train) > 3 else None      # the threshold of zs_vq_restart
             cb.check_width(hps.enc_size, 'vq_train')
-            self.vq = VqBottleneck(cb, beta, decay, encoded_rows(hps.batch_size, hps.seg_len), layers.Ctx(dev, dt))
+            self.vq = VqBottleneck(cb, beta, decay, encoded_rows(hps.batch_size, hps.seg_len), layers.Ctx(dev, dt), restart=restart)
         self.clf = ClfStep(self.ae, self.SpeakerClassifier, lr=hps.lr, betas=(0.5, 0.9), max_grad_norm=hps.max_grad_norm, ema=self.ema)
         self.s2 = None                      # PatchGANStep, built on first use (its optimizer state is 2 x 53 M floats)
         self.source_loader = self.target_loader = None
@@ -1319,7 +1321,11 @@ class Trainer(object):
                     s = bn.stats()                                                             # raises for a row left out of the average
                     info.update({f'{flag}/pre_loss_vq': s['loss_vq'], f'{flag}/vq_used': s['used'] / float(s['K']),
                                  f'{flag}/vq_perplexity': s['perplexity']})
-                    log('pre_AE:[%06d/%06d], loss_rec=%.3f, loss_vq=%.4f, used=%.3f, perplexity=%.1f', info)
+                    line = 'pre_AE:[%06d/%06d], loss_rec=%.3f, loss_vq=%.4f, used=%.3f, perplexity=%.1f'
+                    if bn.restart is not None:
+                        info[f'{flag}/vq_restarts'] = s['restarts']
+                        line += ', restarts=%d'
+                    log(line, info)
                 elif log:
                     log('pre_AE:[%06d/%06d], loss_rec=%.3f', {f'{flag}/pre_loss_rec': loss_t.item()})    # the only host sync
                 if vcfg is not None and ((iteration + 1) % vcfg.every == 0 or iteration + 1 == iters):
@@ -1328,8 +1334,7 @@ class Trainer(object):
             def save_codebook(path, iteration):
                 """<checkpoint>.vq.npz beside the checkpoint: the file --codebook reads (vq.VectorCodebook.save, format unchanged)."""
                 s = bn.stats()
-                bn.to_codebook({'trained_iterations': int(iteration), 'beta': bn.beta, 'decay': bn.decay, 'used': s['used']}).save(
-                    ckpt_path(path))
+                bn.to_codebook(bn.ckpt_meta(iteration, s)).save(ckpt_path(path))
 
             bn = self.vq
             if bn is not None:

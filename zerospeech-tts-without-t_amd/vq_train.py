@@ -6,7 +6,9 @@ average of the counts and sums of the rows each codeword took (zs_vq_accum, zs_v
 The codebook receives no gradient.  Step t quantises, and takes its gradient, against the codebook step t - 1 left: the average is
 written to the `next` copy and becomes the live one at the head of the next forward.  Everything is enqueued on the current stream
 with launch arguments that do not change between iterations, so the captured step replays it; nothing adds floats atomically, so a
-run is bitwise reproducible.  tests/vq_train_ref.py is the numpy definition.  Not in the reference, which has no codebook."""
+run is bitwise reproducible.  tests/vq_train_ref.py is the numpy definition.  Not in the reference, which has no codebook.
+`--vq_restart T`: a codeword that took no row of the step and whose averaged count fell below T is put back onto one of
+the step's encoder rows by zs_vq_restart, behind the average; tests/vq_restart_ref.py is its definition."""
 import numpy as np
 import torch
 
@@ -34,6 +36,27 @@ def check_decay(decay):
     return d
 
 
+def check_restart(v):
+    t = float(v)
+    if not (0.0 < t < 1.0):                    # NaN fails too
+        raise ValueError('--vq_restart must be in (0, 1) (got %r)' % (v,))
+    return t
+
+
+def restart_stride(n):
+    """The step between the rows that consecutive dead codewords take (zs_vq_restart): the largest s with
+    1 <= s <= max(1, floor(0.6180339887 n)) and gcd(s, n) == 1, so that up to n dead codewords take n distinct rows spread over
+    the batch."""
+    from math import gcd
+    n = int(n)
+    if n < 1:
+        raise ValueError('restart_stride: n must be at least 1 (got %d)' % n)
+    s = max(1, int(0.6180339887 * n))
+    while gcd(s, n) != 1:
+        s -= 1
+    return s
+
+
 def encoded_rows(batch_size, seg_len):
     """Rows of the encoder's output for a batch of seg_len-frame segments: three stride-2 convs, each rounding up."""
     t = int(seg_len)
@@ -57,7 +80,9 @@ class VqBottleneck(object):
     codebook: the vq.VectorCodebook the run starts from (code = vectors, N = 1, m = code); ctx: a layers.Ctx (device, compute dtype
     and the buffer of q)."""
 
-    def __init__(self, codebook, beta=BETA, decay=DECAY, rows=0, ctx=None):
+    def __init__(self, codebook, beta=BETA, decay=DECAY, rows=0, ctx=None, restart=None):
+        """restart: None, or the threshold in (0, 1) below which a codeword that took no row this step is put back onto one of the
+        step's encoder rows (zs_vq_restart)."""
         if not isinstance(codebook, vq.VectorCodebook):
             raise ValueError('VqBottleneck: a vector codebook (vq.VectorCodebook) is needed')
         self.beta, self.decay = check_beta(beta), check_decay(decay)
@@ -89,16 +114,22 @@ class VqBottleneck(object):
         self.sums = self.acc[self._sum_at:].view(K, E)
         self.partial = torch.zeros(PARTS, dtype=torch.float64, device=dev)
         self.loss = torch.zeros(1, **f32)                        # loss_vq of the last step
-        self.stat = torch.zeros(4, dtype=torch.int32, device=dev)      # sticky: bad idx (commit) | rows above MAX_ABS | bad idx (backward)
+        # sticky: bad idx (commit) | rows above MAX_ABS | bad idx (backward) | with restart: codewords restarted so far | restarts skipped
+        self.stat = torch.zeros(4 if restart is None else 5, dtype=torch.int32, device=dev)
         self.work = vq.workspace(dev) if n < vq.SPLIT_N else None
         self.z_f32 = torch.zeros(n, E, **f32) if ctx.tdt != torch.float32 else None
+        self.restart = None if restart is None else check_restart(restart)
+        if self.restart is not None:
+            self.stride = restart_stride(n)                      # a host constant of the plan
+            self.rwork = torch.zeros(K + 2, dtype=torch.int32, device=dev)
         self.steps = 0
         self._bits = None
 
     # ---- the step ----------------------------------------------------------------------------------------------------------------------
-    def forward(self, bits):
+    def forward(self, bits, seed=0, seed_ptr=None):
         """bits: the Act [B, T', E] EncoderEngine.forward returns.  Enqueues assign, commit, accum and the codebook's average;
-        returns q, an Act the DecoderEngine takes as it takes bits."""
+        returns q, an Act the DecoderEngine takes as it takes bits.  (seed, seed_ptr): the pair the encoder's forward of this step
+        was given; with restart on, the rows that dead codewords take follow it."""
         ctx, K, E, n = self.ctx, self.K, self.E, self.rows
         if bits.rows != n or bits.C != E or bits.t.dtype != ctx.tdt:
             raise ValueError('VqBottleneck: built for %d rows of %d columns of %s, got %d rows of %d of %s' %
@@ -120,6 +151,12 @@ class VqBottleneck(object):
         L.call('zs_vq_ema', 'ZsVqEma', st, cnt=L.ptr(self.cnt), sum=L.ptr(self.sums), K=K, E=E, shift=self.shift, decay=self.decay,
                N=L.ptr(self.N), m=L.ptr(self.m), code=L.ptr(self.code), ld_code=E, cnorm=L.ptr(self.cnorm),
                used=L.ptr(self.acc.view(torch.int32)))
+        if self.restart is not None:
+            L.call('zs_vq_restart', 'ZsVqRestart', st, thresh=self.restart, x=(L.ptr(zf) if zf is not None else bits.ptr()), n=n,
+                   ld_x=(E if zf is not None else bits.ld), idx_acc=L.ptr(self.idx_acc), cnt=L.ptr(self.cnt), K=K, E=E, N=L.ptr(self.N),
+                   m=L.ptr(self.m), code=L.ptr(self.code), ld_code=E, cnorm=L.ptr(self.cnorm), seed=int(seed or 0) % (1 << 64),
+                   seed_ptr=seed_ptr, stride=self.stride, work=L.ptr(self.rwork), restarted=L.ptr(self.stat, 3),
+                   skipped=L.ptr(self.stat, 4))
         self._bits = bits
         self.steps += 1
         return q
@@ -147,7 +184,10 @@ class VqBottleneck(object):
         head = self.acc[:self._sum_at].cpu().numpy()
         cnt = head[self._cnt_at:].view(np.int32)[:self.K]
         used = int(head[:1].view(np.int32)[0])
-        return {'loss_vq': float(self.loss.item()), 'used': used, 'K': self.K, 'perplexity': perplexity(cnt)}
+        out = {'loss_vq': float(self.loss.item()), 'used': used, 'K': self.K, 'perplexity': perplexity(cnt)}
+        if self.restart is not None:
+            out.update(restarts=int(stat[3]), skipped=int(stat[4]), dead=int((self.N < self.restart).sum().item()))
+        return out
 
     def state_dict(self):
         return {'code': self.code, 'cnorm': self.cnorm, 'N': self.N, 'm': self.m}
@@ -159,6 +199,13 @@ class VqBottleneck(object):
                 raise ValueError('VqBottleneck: state %r has shape %s, this bottleneck %s' % (k, tuple(src.shape), tuple(dst.shape)))
         for k in ('code', 'cnorm', 'N', 'm'):
             getattr(self, k).copy_(torch.as_tensor(sd[k]).to(torch.float32))
+
+    def ckpt_meta(self, iteration, s):
+        """The meta fields of <checkpoint>.vq.npz after `iteration` iterations; s: stats()."""
+        meta = {'trained_iterations': int(iteration), 'beta': self.beta, 'decay': self.decay, 'used': s['used']}
+        if self.restart is not None:
+            meta.update(restart=self.restart, restarts=s['restarts'])
+        return meta
 
     def to_codebook(self, meta=None):
         """The codebook as the last step left it: a vq.VectorCodebook whose meta is the starting file's plus `meta`."""
@@ -174,7 +221,7 @@ def check_vq_train(args, enc_mode=None, c_in=None):
     import os
     path = getattr(args, 'vq_train', None)
     if path is None:
-        for flag in ('vq_beta', 'vq_decay'):
+        for flag in ('vq_beta', 'vq_decay', 'vq_restart'):
             if getattr(args, flag, None) is not None:
                 raise ValueError('--%s needs --vq_train' % flag)
         return None
@@ -193,6 +240,8 @@ def check_vq_train(args, enc_mode=None, c_in=None):
         check_beta(args.vq_beta)
     if getattr(args, 'vq_decay', None) is not None:
         check_decay(args.vq_decay)
+    if getattr(args, 'vq_restart', None) is not None:
+        check_restart(args.vq_restart)
     if enc_mode is None:
         return None
     vq.VectorCodebook.check_mode(enc_mode, "--vq_train needs enc_mode 'continues'")
