@@ -99,7 +99,6 @@ def zs():
     import zs_amd  # noqa: F401
     from zs_amd import _lib, layers
     _lib.lib()
-    _lib.lib().zs_gemm_conv_path.argtypes = [ctypes.c_void_p]
     t0 = time.time()
     yield _lib, layers
     print('\n[gemm] wall time of this module %.1f s; worst fraction of the bound per (family, path, dtype):' % (time.time() - t0))

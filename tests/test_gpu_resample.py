@@ -131,7 +131,6 @@ def test_argument_errors_launch_nothing(dev):
     n_in = torch.tensor([1000, 500], dtype=torch.int32, device=dev)
     dst = torch.full((2, 400), SENTINEL, dtype=torch.float32, device=dev)
     fn = L.lib().zs_resample
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     st = torch.cuda.current_stream(dev).cuda_stream
     good = dict(src=L.ptr(src), src_ld=1000, n_in=L.ptr(n_in), n_utt=2, sr_in=sr_in, sr_out=sr_out, bank=L.ptr(bank), n_phase=pl.n_phase,
                 n_tap=pl.n_tap, dst=L.ptr(dst), dst_ld=400, n_in_max=1000)

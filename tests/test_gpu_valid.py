@@ -63,7 +63,6 @@ def _struct(t, xdec, x, c, n_spk, bits, F, over=()):
 def _call(s):
     from zs_amd import _lib as L
     fn = L.lib().zs_eval_accum
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     return fn(ctypes.addressof(s), torch.cuda.current_stream().cuda_stream)
 
 
@@ -171,7 +170,6 @@ def test_eval_accum_refuses_malformed_structs(dev):
     xdec, x, c, n_spk, bits, F = _inputs(dev, 'odd_F_ordered_pass')
     t = _Tables(dev, 5, n_spk, 10)
     fn = L.lib().zs_eval_accum
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     assert fn(None, None) == L.ZS_EINVAL
     for over in (dict(x_dec=0), dict(x=0), dict(c=0), dict(work=0), dict(spk_sum=0), dict(spk_cnt=0), dict(bad=0), dict(B=0), dict(B=-1),
                  dict(T=0), dict(F=0), dict(F=-3), dict(ld_dec=F - 1), dict(ldx=F - 1), dict(n_speakers=0), dict(n_speakers=-2),

@@ -55,6 +55,77 @@ def test_struct_layouts_match_the_c_compiler(lib, tmp_path):
             assert ctypes.sizeof(lib.STRUCTS[k]) == int(v), k
 
 
+def _c_kind(ct):
+    """'<size><p|f|i|u>' of a ctypes type: pointer (c_void_p and c_char_p alike), floating, signed, unsigned."""
+    if ct in (ctypes.c_void_p, ctypes.c_char_p):
+        k = 'p'
+    elif ct in (ctypes.c_float, ctypes.c_double):
+        k = 'f'
+    else:
+        k = 'i' if ct(-1).value < 0 else 'u'
+    return '%d%s' % (ctypes.sizeof(ct), k)
+
+
+def test_function_signatures_match_the_cxx_compiler(lib, tmp_path):
+    """The function-side twin of the layout test: g++ prints the size and kind of the return type and of every parameter of each
+    declared function; the restype / argtypes that lib() set on the loaded library must say the same, for every function."""
+    src = ('#include <cstdio>\n#include <type_traits>\n#include "%s"\n'
+           'template <class T> void one() {\n'
+           '  std::printf(" %%zu%%c", sizeof(T), std::is_pointer<T>::value ? \'p\' : std::is_floating_point<T>::value ? \'f\' :\n'
+           '              std::is_signed<T>::value ? \'i\' : \'u\');\n}\n'
+           'template <class R, class... A> void show(const char* name, R (*)(A...)) {\n'
+           '  std::printf("%%s", name); one<R>(); int order[] = {0, (one<A>(), 0)...}; (void)order; std::printf("\\n");\n}\n'
+           'int main() {\n' % lib.HEADER)
+    # (a null pointer of the function's type: the program reads declarations only and links against nothing)
+    src += ''.join('  show("%s", (decltype(&%s))0);\n' % (f, f) for f in lib.FUNCTIONS) + '  return 0;\n}\n'
+    c = tmp_path / 'sig.cpp'
+    c.write_text(src)
+    subprocess.check_call(['g++', '-std=c++11', str(c), '-o', str(tmp_path / 'sig')])
+    L, seen = lib.lib(), []
+    for line in subprocess.check_output([str(tmp_path / 'sig')]).decode().splitlines():
+        name, ret = line.split()[:2]
+        fn = getattr(L, name)
+        assert fn.argtypes is not None, '%s: no argtypes declared' % name
+        assert [_c_kind(fn.restype)] + [_c_kind(a) for a in fn.argtypes] == [ret] + line.split()[2:], line
+        seen.append(name)
+    assert seen == lib.FUNCTIONS and len(seen) >= 92
+
+
+@pytest.mark.parametrize('proto, named', [
+    ('short zs_bad(int32_t a);', 'zs_bad.*short'),                       # a return type with no mapping
+    ('int zs_bad(int32_t a, long double b);', 'zs_bad.*long double'),    # a parameter type with no mapping
+    ('unsigned long zs_bad(void);', "zs_bad.*'unsigned long'"),          # a type of several words is named whole
+    ('int zs_bad(void (*cb)(int), void* stream);', 'zs_bad'),            # a declaration the prototype pattern cannot read
+])
+def test_header_parse_is_strict(lib, tmp_path, proto, named):
+    hdr = open(lib.HEADER).read()
+    same = tmp_path / 'same.h'
+    same.write_text(hdr)
+    parsed = lib.parse_header(str(same))
+    assert parsed[1] == lib.FUNCTIONS == list(parsed[4]) and len(lib.FUNCTIONS) >= 92
+    bad = tmp_path / 'bad.h'
+    bad.write_text(hdr.replace('int zs_abi_version(void);', 'int zs_abi_version(void);\n' + proto))
+    with pytest.raises(ValueError, match=named):
+        lib.parse_header(str(bad))
+
+
+def test_a_64_bit_address_survives_a_positional_entry_point(lib):
+    """zs_gemm_conv_path reads the struct and dereferences none of its operands.  The struct's address goes in as a plain integer
+    above 2^32, with no signature set by this test: the header's declaration alone must carry all 64 bits of it."""
+    T, C = 128, 1024
+    s = lib.STRUCTS['ZsGemmConv'](dtype=lib.ZS_BF16, A=0x10000, lda=C, a_batch_stride=T * C, B=256, T_in=T, T_out=T, taps=1, stride=1,
+                                  pad_mode=lib.ZS_PAD_REFLECT, cin_pad=C, W=0x20000, ldw=C, N=C, n_pad=C, out=0x30000, ldc=C, out_cols=C,
+                                  groups=1)
+    addr = ctypes.addressof(s)
+    assert type(addr) is int and addr >> 32, hex(addr)
+    rc = lib.lib().zs_gemm_conv_path(addr)
+    assert rc >= 0, lib.last_error()
+    assert rc & 255 in (lib.ZS_GEMM_PATH_P8, lib.ZS_GEMM_PATH_RING_PP, lib.ZS_GEMM_PATH_RING, lib.ZS_GEMM_PATH_DMA64,
+                        lib.ZS_GEMM_PATH_DMA128, lib.ZS_GEMM_PATH_REG) and rc >> 8 in (0, 1)
+    s.n_pad = 192                                              # the same route gives an argument error as its ZS_E* code
+    assert lib.lib().zs_gemm_conv_path(addr) == lib.ZS_EINVAL
+
+
 def test_invalid_calls_return_errors_not_crashes(lib):
     with pytest.raises(lib.ZsError, match='null operand'):
         lib.call('zs_gemm_conv', 'ZsGemmConv', 0, dtype=0)
@@ -164,7 +235,6 @@ def test_gemm_conv_path_query(lib):
     the production shapes and with every dispatch knob flipped.  Operands are dummy aligned non-null integers: the query
     dereferences nothing and touches no GPU."""
     q = lib.lib().zs_gemm_conv_path
-    q.argtypes = [ctypes.c_void_p]
     P8, RPP, RING, D64, D128, REG = (lib.ZS_GEMM_PATH_P8, lib.ZS_GEMM_PATH_RING_PP, lib.ZS_GEMM_PATH_RING, lib.ZS_GEMM_PATH_DMA64,
                                      lib.ZS_GEMM_PATH_DMA128, lib.ZS_GEMM_PATH_REG)
     PTR = 0x10000
@@ -418,7 +488,6 @@ def test_gemm_wgrad_path_errors(lib, wgrad_query):
     L, struct, PTR, F32 = q.L, q.struct, q.PTR, lib.ZS_F32
     # every argument error: the code and the text of the launch itself
     launch = L.zs_gemm_wgrad
-    launch.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 
     def bad(text, **kw):
         small = dict(B=2, T=16, Cout=64, Cin=64)

@@ -586,11 +586,11 @@ def wgrad_call(ctx, kw, sid=None):
     for k, v in kw.items():
         if v is not None:
             setattr(s, k, v)
-    need = L.lib().zs_gemm_wgrad_workspace_bytes(ctypes.byref(s))
+    need = L.lib().zs_gemm_wgrad_workspace_bytes(ctypes.addressof(s))
     stream, ws = side_launch(ctx, sid, need)
     s.workspace = ws.data_ptr()
     s.workspace_bytes = ws.numel()
-    L.check(L.lib().zs_gemm_wgrad(ctypes.byref(s), ctypes.c_void_p(stream)), 'zs_gemm_wgrad')
+    L.check(L.lib().zs_gemm_wgrad(ctypes.addressof(s), stream), 'zs_gemm_wgrad')
 
 
 # The norm-family launches of the engines.  An optional operand left at None leaves its struct fields zero (absent).
