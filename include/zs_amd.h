@@ -1315,6 +1315,49 @@ typedef struct {
 } ZsVqRestart;
 int zs_vq_restart(const ZsVqRestart* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Residual vector codebook (zs_amd.rvq): S codebooks of K codewords each, stage s quantising what stage s - 1 left over,
+ * 2 <= S <= ZS_RVQ_MAX_S in a file (the kernels take S = 1 too).  The search of every stage is zs_vq_assign (above, unchanged); the two
+ * entry points here are the glue around it.  The limits on K, E, n and the leading dimensions are the vector codebook's.  A null struct,
+ * a K, E, n, S or s_use outside its range, a leading dimension below E, a null operand with work to do or a misaligned operand return
+ * ZS_EINVAL and launch nothing; n == 0 (n_frag == 0) succeeds and launches nothing.  Caller-owned buffers, no allocation, no
+ * synchronisation, stream-ordered; no float atomics and no fused multiply-add: every result is bitwise equal from run to run.
+ *
+ * zs_rvq_residual: what a stage leaves over.  x [n][ld_x] of `dtype` (fp32 when src_f32; aligned to its element), idx int32 [n],
+ * code fp32 [K][ld_code]; r fp32 [n][ld_r], ld_r >= E:
+ *   r[i][j] = (float) x[i][j] - code[idx[i]][j]        j < E       (one IEEE fp32 subtraction; bf16 widened exactly)
+ * Columns E <= j < ld_r are not touched.  An idx[i] outside [0, K) is never used as an index: r[i] = (float) x[i] and *bad += 1
+ * (int32, required).  r == x is allowed when x is fp32 and ld_r == ld_x (every lane reads the piece it writes); any other overlap is
+ * undefined.  A row is owned by a team of 2^t <= 64 lanes of one wave, four columns per lane and round, with 16-byte loads and
+ * stores where the operand is 16-byte aligned (x bf16: 8) and its leading dimension a multiple of 4, element by element otherwise. */
+#define ZS_RVQ_MAX_S 8
+typedef struct {
+  int32_t dtype, src_f32;
+  const void* x; int64_t n, ld_x;
+  const int32_t* idx;
+  const float* code; int64_t ld_code; int32_t K, E;
+  float* r; int64_t ld_r;
+  int32_t* bad;
+} ZsRvqResidual;
+int zs_rvq_residual(const ZsRvqResidual* p, void* stream);
+/* zs_rvq_gather: S planes of indices straight into the Decoder's input operand of one inference chunk (zs_vq_gather for a sum of
+ * codewords).  idx int32 [S][ld_idx]: plane s holds stage s of every frame of the batch, n_idx <= ld_idx entries of it; code fp32
+ * [S][K][ld_code], the codebooks plane_code elements apart (>= (K - 1) ld_code + E); the first s_use stages are used, 1 <= s_use <= S
+ * <= ZS_RVQ_MAX_S.  start, len, n_frag, T, dst, ld_dst and bad exactly as in ZsVqGather:
+ *   dst[f][t][c] = cast(((code[0][k_0][c] + code[1][k_1][c]) + ..) + code[s_use - 1][k_{s_use - 1}][c])     t < len[f], c < E
+ *                  with k_s = idx[s][start[f] + t]; fp32 adds in increasing s, each rounded once, then one cast (to nearest even)
+ *   dst[f][t][c] = 0                                             len[f] <= t < T, or E <= c < ld_dst
+ * A frame with any of its s_use indices outside [0, K) writes a zero row and *bad += 1 (once per frame); no index of such a frame is
+ * used as an index, and the planes s >= s_use are not read.  With S = s_use = 1 the operand is zs_vq_gather's, bit for bit. */
+typedef struct {
+  int32_t dtype;
+  const int32_t* idx; int64_t n_idx, ld_idx; int32_t S, s_use;
+  const float* code; int64_t ld_code, plane_code; int32_t K, E;
+  const int64_t* start; const int32_t* len; int32_t n_frag, T;
+  void* dst; int64_t ld_dst; int32_t* bad;
+} ZsRvqGather;
+int zs_rvq_gather(const ZsRvqGather* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,16 @@ onto one of the batch's encoder rows, on the device inside the step; the log the
 refused before anything is built:
   python main.py --enc_mode continues --train_ae --load_model --vq_train ckpt_english/codebooks/K1024.vq.npz
 
+--fit_codebook K --rvq S with --enc_mode continues (zs_amd.rvq): a residual codebook of S stages (2 to 8) of K codewords each, stage s
+fitted to what stage s - 1 left over; the file (default {ckpt_dir}/codebooks/K<K>x<S>.rvq.npz) gives a frame S indices, S log2 K bits,
+and its first s of them are a valid coarser description.  --codebook FILE.rvq.npz takes it wherever a vector codebook goes, and
+--rvq_stages s uses its first s stages: --convert_dir and --test_encode write <name>.idx.txt with s indices per line (default: all
+S), --synth_dir speaks the first s columns of every *.idx.txt (default: the columns a file has) and refuses a file with fewer.
+--vq_train refuses a residual codebook, as every flag here is refused without its companion, before anything is built:
+  python main.py --enc_mode continues --fit_codebook 1024 --rvq 4 --fit_dir wavs/ --ckpt_pth CKPT
+  python main.py --enc_mode continues --convert_dir in/ --t_speaker V001 --ckpt_pth CKPT --codebook ckpt_english/codebooks/K1024x4.rvq.npz
+  python main.py --enc_mode continues --synth_dir idx/ --t_speaker V001 --ckpt_pth CKPT --codebook ckpt_english/codebooks/K1024x4.rvq.npz --rvq_stages 2
+
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
 (--train_al, --train_t, --encode, --test_asr) are not part of this build and exit with a clear error.
@@ -163,6 +173,26 @@ def _codebook_iters(text):
     if n < 1:
         raise argparse.ArgumentTypeError('--codebook_iters must be >= 1 (got %s)' % text)
     return n
+
+
+def _rvq(text):
+    try:
+        s = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('--rvq must be an integer in [2, 8] (got %s)' % text)
+    if not 2 <= s <= 8:
+        raise argparse.ArgumentTypeError('--rvq must be in [2, 8] (got %s)' % text)
+    return s
+
+
+def _rvq_stages(text):
+    try:
+        s = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('--rvq_stages must be an integer in [1, 8] (got %s)' % text)
+    if not 1 <= s <= 8:
+        raise argparse.ArgumentTypeError('--rvq_stages must be in [1, 8] (got %s)' % text)
+    return s
 
 
 VALID_BATCHES = 8
@@ -259,6 +289,12 @@ def build_parser():
     p.add_argument('--codebook', type=str, default=None, metavar='FILE',
                    help='with --convert_dir / --synth_dir / --test_encode: snap every unit to its nearest codeword of this codebook; a '
                         "vector codebook (FILE.vq.npz, enc_mode 'continues') writes <name>.idx.txt index files, and --synth_dir reads them")
+    p.add_argument('--rvq', type=_rvq, default=None, metavar='S',
+                   help="with --fit_codebook and enc_mode 'continues': fit a residual codebook of S stages of K codewords each, S in "
+                        '[2, 8] (default file {ckpt_dir}/codebooks/K<K>x<S>.rvq.npz)')
+    p.add_argument('--rvq_stages', type=_rvq_stages, default=None, metavar='s',
+                   help='with --codebook FILE.rvq.npz: use the first s stages of the residual codebook (default: all of them for '
+                        "--convert_dir and --test_encode, a unit file's own columns for --synth_dir)")
     p.add_argument('--vq_train', type=str, default=None, metavar='FILE',
                    help="with --train_ae and enc_mode 'continues': train through the vector codebook FILE.vq.npz (straight-through "
                         'quantiser, commitment term, codebook by exponential moving average); every checkpoint gets a '
@@ -394,6 +430,36 @@ def check_codebook(parser, args):
         parser.error('--codebook uses a codebook and --fit_codebook writes one: run them as two commands')
 
 
+def check_rvq(args, enc_mode=None):
+    """--rvq and --rvq_stages are refused, before anything is built, where they cannot do what they say: --rvq without --fit_codebook,
+    --rvq_stages without --codebook; and, once enc_mode is known (argument_runner calls this again after reading hps), --rvq for an
+    enc_mode other than 'continues', --rvq_stages for a file that is no residual codebook or has fewer stages, and a residual
+    codebook for an enc_mode other than 'continues' (the file's fields are read here)."""
+    rvq, stages = getattr(args, 'rvq', None), getattr(args, 'rvq_stages', None)
+    if rvq is not None and getattr(args, 'fit_codebook', None) is None:
+        raise ValueError('--rvq needs --fit_codebook K: it sets the stages of the residual codebook that is fitted')
+    if stages is not None and getattr(args, 'codebook', None) is None:
+        raise ValueError('--rvq_stages needs --codebook FILE.rvq.npz: it chooses how many stages of that residual codebook are used')
+    if enc_mode is None:
+        return
+    if rvq is not None and enc_mode != 'continues':
+        raise ValueError("--rvq fits a residual codebook, which serves enc_mode 'continues': this model's enc_mode is %r" % enc_mode)
+    path = getattr(args, 'codebook', None)
+    if path is None or (stages is None and not path.endswith('.rvq.npz')):      # (every other file is read where it always was)
+        return
+    from zs_amd.codebook import read_npz
+    d = read_npz(path)
+    residual = 'kind' in d and d['kind'].shape == () and str(d['kind']) == 'residual'
+    if residual:
+        from zs_amd.rvq import ResidualCodebook
+        ResidualCodebook.check_mode(enc_mode, "--codebook %s is a residual codebook (kind 'residual'), which serves enc_mode 'continues'" % path)
+    if stages is not None:
+        if not residual:
+            raise ValueError('--rvq_stages needs a residual codebook (FILE.rvq.npz): %s is none' % path)
+        if 'S' in d and d['S'].shape == () and d['S'].dtype.kind in 'iu' and stages > int(d['S']):
+            raise ValueError('--rvq_stages %d: %s has S = %d stages' % (stages, path, int(d['S'])))
+
+
 def check_vq_train(args, enc_mode=None, c_in=None):
     """--vq_train, --vq_beta, --vq_decay and --vq_restart are refused, before anything is built, where they cannot do what they say
     (zs_amd.vq_train.check_vq_train): without --train_ae or beside another --train* mode, under a multi-rank launch, with --resume
@@ -426,6 +492,7 @@ def argument_runner(argv=None):
     from zs_amd.validation import check_flags
     check_flags(args)
     check_vq_train(args)
+    check_rvq(args)
     args.t_speakers =convert_targets(args) if (args.convert_dir is not None or args.synth_dir is not None) else None
     if args.dataset == 'surprise':            # main.py:83-88: english -> surprise in every default path
         for action in parser._actions:
@@ -447,6 +514,7 @@ def argument_runner(argv=None):
         args.enc_mode = hps.enc_mode
     check_voice(args)                         # again, now that enc_mode is known
     args.vq_codebook = check_vq_train(args, args.enc_mode, hps.enc_size)      # (the file is read here: a bit codebook or another width)
+    check_rvq(args, args.enc_mode)            # again, now that enc_mode is known (a residual codebook's fields are read here)
     print('[Runner] - Generation mode: ', 'autoencoder only' if args.enc_only else 'with generator')
     print('[Runner] - Generator mode: ', args.g_mode)
     print('[Runner] - Encoder mode: ', args.enc_mode)
@@ -564,11 +632,18 @@ def main(argv=None):
         from zs_amd.vq import kind_for                    # the model's enc_mode chooses the kind: bits (k-modes) or vectors (k-means)
         model_path = args.ckpt_pth if args.ckpt_pth is not None else os.path.join(args.ckpt_dir, args.load_test_model_name)
         trainer = get_trainer(args.hps_path, model_path, args.g_mode, args.enc_mode, use_ema=args.use_ema)
-        kind = kind_for(trainer.enc_mode)
-        kind.fit_dir(trainer, hps.seg_len, args.fit_dir, args.fit_codebook,
-                     args.codebook_out if args.codebook_out is not None else kind.default_path(args.ckpt_dir, args.fit_codebook),
-                     iters=(args.codebook_iters if args.codebook_iters is not None else CODEBOOK_ITERS),
-                     seed=(args.codebook_seed if args.codebook_seed is not None else 0))
+        iters = args.codebook_iters if args.codebook_iters is not None else CODEBOOK_ITERS
+        seed = args.codebook_seed if args.codebook_seed is not None else 0
+        if args.rvq is not None:                          # --rvq S: S stages of K codewords, fitted greedily (zs_amd.rvq)
+            from zs_amd import rvq
+            rvq.fit_dir(trainer, hps.seg_len, args.fit_dir, args.fit_codebook, args.rvq,
+                        args.codebook_out if args.codebook_out is not None else
+                        rvq.ResidualCodebook.default_path(args.ckpt_dir, args.fit_codebook, args.rvq), iters=iters, seed=seed)
+        else:
+            kind = kind_for(trainer.enc_mode)
+            kind.fit_dir(trainer, hps.seg_len, args.fit_dir, args.fit_codebook,
+                         args.codebook_out if args.codebook_out is not None else kind.default_path(args.ckpt_dir, args.fit_codebook),
+                         iters=iters, seed=seed)
 
     if args.test or args.cross_test or args.test_encode or args.test_single or args.test_classify or args.convert_dir is not None or \
             args.synth_dir is not None:
@@ -581,6 +656,8 @@ def main(argv=None):
         if args.codebook is not None:                     # a malformed file or another width: ValueError before anything is enqueued
             from zs_amd.vq import load_codebook       # the file's kind and the model's enc_mode choose the path
             cb = load_codebook(args.codebook, trainer.enc_mode, E=int(trainer.Decoder.c_in))
+            if args.rvq_stages is not None:               # (check_rvq has seen that the file is a residual codebook of that many stages)
+                cb = cb.with_stages(args.rvq_stages)
         voices = None
         if args.voice:                                    # --voice NAME=FILE: rows appended to the Decoder's tables (zs_amd.voice)
             from zs_amd.voice import add_voices

@@ -115,7 +115,7 @@ def first_distinct(n, K, seed, rows_at, nouns):
 
 
 class CodebookFile(object):
-    """What the two kinds of codebook share: the file (fields format_version, K, E, meta and the kind's payload; `kind` where the
+    """What the kinds of codebook (bits, vectors, zs_amd.rvq's stages of vectors) share: the file (fields format_version, K, E, meta and the kind's payload; `kind` where the
     kind has one), the width check, the per-device upload and the fit over a folder.  A kind supplies `label` (what messages call
     it), `payload` (the field and attribute of its codewords), `_from_payload` (the check of that payload: its constructor) and
     what fit_dir names below."""
@@ -184,9 +184,10 @@ class CodebookFile(object):
         return os.path.join(ckpt_dir, 'codebooks', 'K%d.%s' % (int(K), cls.suffix))
 
     @classmethod
-    def fit_dir(cls, trainer, seg_len, in_dir, K, out_path, iters, seed=0, batch=64):
+    def fit_dir(cls, trainer, seg_len, in_dir, K, out_path, iters, seed=0, batch=64, **fit_kw):
         """--fit_codebook: a codebook of this kind of K codewords over a folder.  The kind's _dir_rows reads and encodes the folder
-        (-> files used, files skipped, device tensors of rows), its _fit clusters them and its _indices gives the final assignment.
+        (-> files used, files skipped, device tensors of rows), its _fit clusters them (fit_kw: what else that kind's fit takes) and
+        its _indices gives the final assignment; a kind with more to say answers _usage, _report_extra and _fit_summary itself.
         Writes the codebook to out_path and fit_codebook.json beside it (files used and skipped, n_units, the history, symbols used
         and the entropy of the final assignment); returns (the codebook, that report)."""
         import os
@@ -199,9 +200,9 @@ class CodebookFile(object):
         if not parts:
             raise ValueError('--fit_codebook: %s holds no usable %s' % (in_dir, cls._dir_files))
         rows_dev = torch.cat(parts, dim=0).contiguous()
-        cb = cls._fit(rows_dev, K, iters, seed, E, trainer.enc_mode)
+        cb = cls._fit(rows_dev, K, iters, seed, E, trainer.enc_mode, **fit_kw)
         cb.check_width(E, out_path)
-        n_used, entropy = usage(cb._indices(rows_dev), K)
+        n_used, entropy = cb._usage(rows_dev)
         os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
         cb.save(out_path)
         report = {'codebook': out_path}
@@ -209,10 +210,23 @@ class CodebookFile(object):
             report['kind'] = cls.kind
         report.update({'K': K, 'E': E, 'in_dir': in_dir, 'files': used, 'skipped': skipped, 'n_units': int(rows_dev.shape[0]),
                        'seed': int(seed), 'history': cb.meta['history'], 'symbols_used': n_used, 'entropy_bits_per_unit': entropy})
+        report.update(cb._report_extra())
         with open(os.path.join(os.path.dirname(os.path.abspath(out_path)), 'fit_codebook.json'), 'w') as f:
             json.dump(report, f, indent=1)
-        print(cls._fit_line % (K, rows_dev.shape[0], len(used), len(cb.meta['history']), cb.meta['history'][-1][0], n_used, entropy, out_path))
+        print(cb._fit_summary(K, rows_dev.shape[0], len(used), n_used, entropy, out_path))
         return cb, report
+
+    def _usage(self, rows_dev):
+        """(symbols used, entropy in bits per unit) of the final assignment of the fit rows."""
+        return usage(self._indices(rows_dev), self.K)
+
+    def _report_extra(self):
+        """What fit_codebook.json holds for this kind beyond the shared fields."""
+        return {}
+
+    def _fit_summary(self, K, n_rows, n_files, n_used, entropy, out_path):
+        """The line fit_dir prints."""
+        return self._fit_line % (K, n_rows, n_files, len(self.meta['history']), self.meta['history'][-1][0], n_used, entropy, out_path)
 
 
 class Codebook(CodebookFile):

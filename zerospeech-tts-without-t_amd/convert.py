@@ -690,7 +690,7 @@ _NO_UNITS = "enc_mode 'continues' has no units: its encodings are real-valued an
 class _Units(object):
     """What conversion does with units under a codebook of one kind (the codebook's units() hands one out per batch or folder run):
     the three points of a batch of _enqueue_encode (plan, operand, finish), the encodings _assemble returns, and what the folder
-    drivers read, speak and write.  _BitUnits and _VectorUnits answer the same calls."""
+    drivers read, speak and write.  _BitUnits, _VectorUnits and _ResidualUnits answer the same calls."""
 
     def __init__(self, codebook):
         self.cb = codebook
@@ -701,6 +701,10 @@ class _Units(object):
     def spoken_stem(self, stem):
         """The stem of the wav a unit file of that stem speaks as."""
         return stem
+
+    def write_idx(self, path, idx):
+        """An utterance's codeword indices as the .idx.txt beside its unit file."""
+        write_indices(path, idx)
 
 
 class _BitUnits(_Units):
@@ -829,6 +833,107 @@ class _VectorUnits(_Units):
         idx, _ = self.cb.snap(torch.from_numpy(np.ascontiguousarray(units, dtype=np.float32)).to(dev))
         write_encodings(txt, units)
         write_indices(idx_path(txt), idx.cpu().numpy())
+
+
+class _ResidualUnits(_VectorUnits):
+    """Under a residual codebook (zs_amd.rvq.ResidualCodebook, enc_mode 'continues'): the units of a frame are the indices of its
+    first s' stages, one row of s' columns, and the unit files are <name>.idx.txt with that row per line.  stages: s' (None: every
+    stage for conversion, a file's own columns for synthesis)."""
+
+    def __init__(self, codebook, stages=None):
+        from .rvq import check_stages
+        super(_ResidualUnits, self).__init__(codebook)
+        self.stages = None if stages is None else check_stages(stages, codebook.S, '--rvq_stages')
+        self.s_use = codebook.S if self.stages is None else self.stages
+
+    def plan(self, q, chunks, decoding, want_packed):
+        """_VectorUnits.plan, and the one fp32 residual buffer of the batch: the rows of its largest chunk."""
+        super(_ResidualUnits, self).plan(q, chunks, decoding, want_packed)
+        rows = max(len(chunk) * _t8(max(it.n for it in chunk)) for chunk, _ in chunks)
+        self.resid = torch.empty(rows if self.s_use > 1 else 0, self.cb.E, dtype=torch.float32, device=q.dev)
+
+    def operand(self, ci, chunk, Tm, enc, act, dec, dev):
+        """Behind the encoder's launches of chunk ci: stage 0 is zs_vq_assign over the chunk's rows, read in place from the engine's
+        output; zs_rvq_residual writes what it leaves into the fp32 buffer, and every further stage assigns on that buffer and
+        subtracts in place.  Returns rows(ch, lens_p) for _decode_chunk: zs_rvq_gather builds the Decoder's operand from the planes."""
+        from .rvq import launch_residual
+        from .vq import launch_assign
+        bits = enc._last_bits
+        Tp = int(bits.T)
+        if Tp != _t8(Tm) or int(bits.B) != len(chunk):
+            raise L.ZsError('conversion chunk %d: %d x %d encoded frames where the plan has %d x %d' % (ci, bits.B, Tp, len(chunk), _t8(Tm)))
+        n, E, s_use = len(chunk) * Tp, self.cb.E, self.s_use
+        st, dt = torch.cuda.current_stream(dev).cuda_stream, enc._zs['ctx'].dt
+        idx_c = torch.empty(s_use, n, dtype=torch.int32, device=dev)
+        dist_c = torch.empty(s_use, n, dtype=torch.float32, device=dev)
+        launch_assign(st, dt, bits.ptr(), n, bits.ld, self.code[0], self.cnorm[0], idx=idx_c[0], dist=dist_c[0], work=self.work)
+        r = L.ptr(self.resid)
+        for s in range(1, s_use):
+            if s == 1:
+                launch_residual(st, dt, 0, bits.ptr(), n, bits.ld, idx_c[0], self.code[0], r, E, self.bad)
+            else:
+                launch_residual(st, L.ZS_F32, 1, r, n, E, idx_c[s - 1], self.code[s - 1], r, E, self.bad)
+            launch_assign(st, L.ZS_F32, r, n, E, self.code[s], self.cnorm[s], idx=idx_c[s], dist=dist_c[s], work=self.work)
+        self.idx.append(idx_c)
+        self.dist.append(dist_c)
+        if self.dense is None:
+            return None
+        st_c, ln_c = self.dense[ci]
+        return lambda ch, lens_p: dec.forward_index_planes(idx_c, s_use, self.code, st_c, ln_c, len(chunk), Tp, ch, self.bad, lengths=lens_p)
+
+    def finish(self, q, units_dev):
+        """Behind the last chunk: the planes into utterance order (_vq_index_map), then one copy: q.idx_host int32 [units, s'], a row per
+        frame, and q.cb_total double [s'], the summed squared distance left behind every stage (the last: that of the units written)."""
+        idx_all, dist_all = (torch.cat(self.idx, dim=1), torch.cat(self.dist, dim=1)) if len(self.idx) > 1 else (self.idx[0], self.dist[0])
+        q.idx_host = _to_host(idx_all[:, self.src].t().contiguous())
+        q.cb_total = _to_host(dist_all[:, self.src].sum(dim=1, dtype=torch.float64))
+        self.idx = self.dist = self.work = self.src = self.dense = self.resid = None
+
+    def encodings(self, q, u):
+        """Utterance u's encodings: the sums of the codewords of its indices (ResidualCodebook.reconstruct)."""
+        return self.cb.reconstruct(q.idx_host.numpy()[q.uoffs[u]:q.uoffs[u + 1]].T)
+
+    def read_unit_file(self, path, E):
+        """int32 [U, c] of the file, cut to the first s' columns when s' is given; a file of fewer columns is refused."""
+        rows = read_index_rows(path, self.cb.K, self.cb.S)
+        if self.stages is not None and rows.shape[1] < self.stages:
+            raise ValueError('%s holds c = %d indices per line, fewer than the s = %d stages asked for (--rvq_stages)'
+                             % (path, rows.shape[1], self.stages))
+        return rows if self.stages is None else np.ascontiguousarray(rows[:, :self.stages])
+
+    def speak(self, units, trainer, seg_len, speakers, **kw):
+        """synth_index_batch with the planes operand.  Files of different widths (no s' given: each speaks with its own columns) go
+        through it width by width, and the results come back in the order given."""
+        widths = sorted({int(u.shape[1]) for u in units})
+        if len(widths) == 1:
+            return synth_index_batch(units, trainer, seg_len, speakers, self.cb, **kw)
+        parts = []
+        for c in widths:
+            sel = [i for i, u in enumerate(units) if u.shape[1] == c]
+            parts.append((sel, synth_index_batch([units[i] for i in sel], trainer, seg_len, [speakers[i] for i in sel], self.cb, **kw)))
+
+        def finish():
+            specs, wavs = [None] * len(units), [None] * len(units)
+            for sel, res in parts:
+                res = res() if callable(res) else res
+                for j, i in enumerate(sel):
+                    wavs[i] = res[1][j]
+                    if res[0] is not None:
+                        specs[i] = res[0][j]
+            return (specs if any(s is not None for s in specs) else None), wavs
+        return finish if kw.get('defer') else finish()
+
+    def write_idx(self, path, idx):
+        write_index_rows(path, idx)
+
+    def write_spoken(self, base, idx, E):
+        write_index_rows(base + '.idx.txt', idx)
+
+    def write_encoded(self, txt, units, dev):
+        """--test_encode: the .txt as without a codebook, the s' indices of every encoded frame beside it."""
+        idx, _ = self.cb.snap(torch.from_numpy(np.ascontiguousarray(units, dtype=np.float32)).to(dev), stages=self.s_use)
+        write_encodings(txt, units)
+        write_index_rows(idx_path(txt), idx.t().cpu().numpy())
 
 
 def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host, enc_only=True, denorm=False, pack=False,
@@ -990,6 +1095,8 @@ def _unit_indices(idx_host, cb_total, uoffs):
     """Per utterance the codeword index of every returned unit (int32 [U_i]) and the summed distance, from _snap_units' host copies
     (which have been waited for) and the utterances' row offsets."""
     idx, total = idx_host.numpy(), cb_total.numpy()[0]
+    if cb_total.numel() > 1:                                  # a residual codebook: [U_i, s'] indices, the distance left behind every stage
+        return [idx[uoffs[u]:uoffs[u + 1]].copy() for u in range(len(uoffs) - 1)], cb_total.numpy().astype(np.float64)
     return [idx[uoffs[u]:uoffs[u + 1]].copy() for u in range(len(uoffs) - 1)], (float(total) if total.dtype.kind == 'f' else int(total))
 
 
@@ -1267,9 +1374,13 @@ def synth_index_batch(idx_lists, trainer, seg_len, speakers, codebook, enc_only=
     vocoder are synth_units_batch's own.  Returns (specs or None, wavs); defer=True returns the function that waits for them.
     Refused before anything is enqueued: a codebook that is no vector codebook (for 'continues' in synth_units_batch's words), a
     width other than the Decoder's c_in, an index outside [0, K), fewer than 2 indices (ValueError); a speaker the Decoder or the
-    generator cannot take."""
+    generator cannot take.
+    Under a zs_amd.rvq.ResidualCodebook an utterance is integers [U_i, c], a row of c <= S indices per frame and the same c for the
+    whole batch (what read_index_rows parses): the rows go to the device once, are transposed there into c planes, and zs_rvq_gather
+    (Decoder.forward_index_planes) writes each chunk's operand as the sum of the c stages' codewords.  The driver is the same."""
     momentum = gl_momentum(momentum)
-    if getattr(codebook, 'kind', None) != 'vector':
+    planes = getattr(codebook, 'kind', None) == 'residual'    # a zs_amd.rvq.ResidualCodebook: [U_i, c] rows, c <= S the same for all
+    if getattr(codebook, 'kind', None) != 'vector' and not planes:
         if trainer.enc_mode == 'continues':
             raise ValueError(_NO_UNITS)
         raise ValueError('synth_index_batch: the codebook must be a vector codebook (zs_amd.vq.VectorCodebook)')
@@ -1280,18 +1391,27 @@ def synth_index_batch(idx_lists, trainer, seg_len, speakers, codebook, enc_only=
         rows = []
         for i, seq in enumerate(idx_lists):
             a = np.asarray(seq.cpu() if torch.is_tensor(seq) else seq)
-            if a.ndim != 1 or a.dtype.kind not in 'iu':
+            if planes:
+                if a.ndim != 2 or a.dtype.kind not in 'iu' or not 1 <= a.shape[1] <= codebook.S:
+                    raise ValueError('utterance %d: indices must be integers [U, 1 .. S = %d] (got %s %s)' % (i, codebook.S, a.dtype, a.shape))
+                if rows and a.shape[1] != rows[0].shape[1]:
+                    raise ValueError('utterance %d has %d indices per frame where utterance 0 has %d' % (i, a.shape[1], rows[0].shape[1]))
+            elif a.ndim != 1 or a.dtype.kind not in 'iu':
                 raise ValueError('utterance %d: indices must be a 1-D integer sequence (got %s %s)' % (i, a.dtype, a.shape))
             if a.shape[0] < 2:
                 raise ValueError('utterance %d has fewer than 2 indices (the Decoder needs two rows)' % i)
             if (a < 0).any() or (a >= codebook.K).any():
                 raise ValueError('utterance %d: an index is outside [0, K = %d)' % (i, codebook.K))
-            rows.append(a.astype(np.int32))
+            rows.append(np.ascontiguousarray(a.astype(np.int32)))
         return rows
 
     def operand(idx_dev, dev):                                # zs_vq_gather per chunk, from the one index buffer and the codewords
         code_d, _ = codebook.to(dev)
         bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        if planes:                                            # zs_rvq_gather: the batch's rows [n, c] as c planes, every column used
+            idx_p = idx_dev.t().contiguous()
+            return (lambda tab, B, T0, ch, lens_p: dec.forward_index_planes(idx_p, idx_p.shape[0], code_d, tab[0], tab[1], B, T0, ch, bad,
+                                                                            lengths=lens_p)), None, None
         return (lambda tab, B, T0, ch, lens_p: dec.forward_indices(idx_dev, code_d, tab[0], tab[1], B, T0, ch, bad, lengths=lens_p)), None, None
     return _synth_batch('synth_index_batch', idx_lists, check_rows, operand, trainer, seg_len, speakers, enc_only, n_iter, do_trim, max_batch,
                         defer, momentum, want_specs)
@@ -1533,28 +1653,83 @@ def write_indices(path, idx):
             f.write('%d\n' % int(i))
 
 
+def write_index_rows(path, rows):
+    """The unit file under a residual codebook: one line per frame, its c indices separated by one blank (rows: integers [U, c])."""
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[1] < 1 or rows.dtype.kind not in 'iu':
+        raise ValueError('write_index_rows: rows must be integers [U, c >= 1] (got %s %s)' % (rows.dtype, rows.shape))
+    with open(path, 'w') as f:
+        for r in rows:
+            f.write(' '.join('%d' % int(k) for k in r) + '\n')
+
+
+def read_index_rows(path, K, S):
+    """The parser of what write_index_rows writes: c integers in [0, K) per line, 1 <= c <= S, the same c on every line -> int32
+    [U, c].  ValueError naming the file and the line for anything else, and for a file without a line."""
+    out, c = [], None
+    with open(path, 'r') as f:
+        for no, line in enumerate(f, 1):
+            tokens = line.split()
+            if c is None:
+                if not 1 <= len(tokens) <= S:
+                    raise ValueError('%s, line %d: %d values, expected 1 to S = %d indices' % (path, no, len(tokens), S))
+                c = len(tokens)
+            elif len(tokens) != c:
+                raise ValueError('%s, line %d: %d values where line 1 has %d' % (path, no, len(tokens), c))
+            row = []
+            for tok in tokens:
+                try:
+                    k = int(tok, 10)
+                except ValueError:
+                    raise ValueError('%s, line %d: %r is not an integer' % (path, no, tok))
+                if not 0 <= k < K:
+                    raise ValueError('%s, line %d: index %d is outside [0, K = %d)' % (path, no, k, K))
+                row.append(k)
+            out.append(row)
+    if not out:
+        raise ValueError('%s: no indices (the file is empty)' % path)
+    return np.asarray(out, dtype=np.int32)
+
+
 def idx_path(txt):
     """<name>.txt -> <name>.idx.txt"""
     return os.path.splitext(txt)[0] + '.idx.txt'
 
 
 class _CodebookStats(object):
-    """What a folder driver reports about a codebook run: the histogram of the indices written and the summed distance."""
+    """What a folder driver reports about a codebook run: the histogram of the indices written and the summed distance.  Under a
+    residual codebook a histogram and a distance per stage."""
 
     def __init__(self, codebook, file):
-        self.cb, self.file, self.hist, self.total = codebook, file, np.zeros(codebook.K, dtype=np.int64), 0
+        self.cb, self.file, self.total = codebook, file, 0
+        self.hist = np.zeros((getattr(codebook, 'S', 1), codebook.K), dtype=np.int64)
 
     def add(self, idxs, total):
         for i in idxs:
-            self.hist += np.bincount(i, minlength=self.cb.K)
-        self.total += total                                   # int (Hamming) or float (squared Euclidean, a vector codebook)
+            i = np.asarray(i)
+            planes = i[:, None] if i.ndim == 1 else i         # [U] or, under a residual codebook, [U, s']
+            for s in range(planes.shape[1]):
+                self.hist[s] += np.bincount(planes[:, s], minlength=self.cb.K)
+        self.total = self.total + total                       # int (Hamming), float (squared Euclidean) or, residual, a float per stage
 
     def manifest(self):
         from .codebook import usage_counts
-        n = int(self.hist.sum())
-        used, ent = usage_counts(self.hist)
-        return {'file': self.file, 'K': self.cb.K, 'symbols_used': used, 'entropy_bits_per_unit': ent,
-                'mean_distance': (self.total / float(n)) if n else 0.0}
+        n = int(self.hist[0].sum())
+        used, ent = usage_counts(self.hist[0])
+        out = {'file': self.file, 'K': self.cb.K, 'symbols_used': used, 'entropy_bits_per_unit': ent}
+        if getattr(self.cb, 'kind', None) != 'residual':
+            out['mean_distance'] = (self.total / float(n)) if n else 0.0
+            return out
+        live = [s for s in range(self.hist.shape[0]) if self.hist[s].sum()]
+        totals = np.broadcast_to(np.asarray(self.total, dtype=np.float64).reshape(-1), (len(live),)) if live else np.zeros(0)
+        stages = []
+        for s, t in zip(live, totals):
+            u, e = usage_counts(self.hist[s])
+            stages.append({'symbols_used': u, 'entropy_bits_per_unit': e, 'mean_distance': float(t) / float(self.hist[s].sum())})
+        out.update({'S': self.cb.S, 'stages': stages, 'symbols_used': max([st['symbols_used'] for st in stages] or [0]),
+                    'entropy_bits_per_unit': float(sum(st['entropy_bits_per_unit'] for st in stages)),
+                    'mean_distance': stages[-1]['mean_distance'] if stages else 0.0})
+        return out
 
 
 def _target_table(who, trainer, speaker2id_path, voices, t_speakers, enc_only):
@@ -1644,11 +1819,14 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
     codebook: a zs_amd.codebook.Codebook (codebook_file: where it came from) -- the units are snapped as resynth_batch snaps them,
     every .txt gets a sibling .idx.txt (one codeword index per line) and the manifest the entry 'codebook': {file, K, symbols_used,
     entropy_bits_per_unit, mean_distance} over the units written.  A zs_amd.vq.VectorCodebook for enc_mode 'continues': the same
-    outputs, the .idx.txt being the unit file (the .txt holds what write_encodings writes for real-valued rows)."""
+    outputs, the .idx.txt being the unit file (the .txt holds what write_encodings writes for real-valued rows).  A
+    zs_amd.rvq.ResidualCodebook: the .idx.txt holds one line of s' indices per frame (write_index_rows), s' the stages the codebook
+    was told to use (with_stages; default all), and the manifest's 'codebook' entry gains 'S' and per-stage figures under 'stages'."""
     from concurrent.futures import ThreadPoolExecutor
     from .preprocess import read_wav
     momentum = gl_momentum(momentum)
     stats = _codebook_stats(codebook, trainer, codebook_file)
+    side = codebook.units() if codebook is not None else None    # how this kind of codebook writes an utterance's indices
     t_speakers = list(t_speakers)
     speaker2id = _target_table('convert_dir', trainer, speaker2id_path, voices, t_speakers, enc_only)
     if not enc_only:
@@ -1686,7 +1864,7 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
             write_wav(it['wav'], w, out_rate())
             write_encodings(it['txt'], e)
             if stats is not None:
-                write_indices(idx_path(it['txt']), res[2][i])
+                side.write_idx(idx_path(it['txt']), res[2][i])
             done.append(it)
 
     with ThreadPoolExecutor(max_workers=1) as reader:

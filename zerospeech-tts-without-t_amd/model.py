@@ -325,6 +325,21 @@ class Decoder(ZsModule):
             launch_gather(ctx.stream, ctx.dt, idx, code, start, length, B, T0, bits.ptr(), bits.ld, bad)
         return self._forward_operand(B, T0, E, fill, c, idx.device, lengths)
 
+    def forward_index_planes(self, idx, s_use, code, start, length, B, T0, c, bad, lengths=None):
+        """forward_indices() under a residual codebook (zs_amd.rvq): zs_rvq_gather writes the chunk's operand [B, T0, c_in] as the sum,
+        in fp32 in increasing stage, of the first s_use stages' codewords (idx int32 [S, n_idx]: a plane per stage, rows a multiple of
+        n_idx apart; code fp32 [S, K, c_in]); a frame with a used index outside [0, K) is a zero row, counted once in bad."""
+        from .rvq import launch_gather
+        E = self.c_in
+        if idx.dtype != torch.int32 or idx.dim() != 2 or idx.stride(1) != 1 or (idx.shape[0] > 1 and idx.stride(0) < idx.shape[1]):
+            raise ValueError('Decoder.forward_index_planes: idx must be int32 [S, n_idx] with unit column stride')
+        if code.dtype != torch.float32 or code.dim() != 3 or code.shape[2] != E or code.shape[0] < int(s_use) or not code.is_contiguous():
+            raise ValueError('Decoder.forward_index_planes: code must be contiguous fp32 [>= %d stages, K, %d]' % (int(s_use), E))
+
+        def fill(ctx, bits):
+            launch_gather(ctx.stream, ctx.dt, idx, s_use, code, start, length, B, T0, bits.ptr(), bits.ld, bad)
+        return self._forward_operand(B, T0, E, fill, c, idx.device, lengths)
+
 
 class Spectrogram_Patcher(ZsModule):
     """model/model.py:505-549: the stage-2 generator of g_mode 'spectrogram', a post-filter on the decoder's output spectrogram

@@ -163,8 +163,13 @@ def kind_for(enc_mode):
 
 def load_codebook(path, enc_mode, E=None):
     """The codebook of a file, by the file's own fields: a VectorCodebook (field kind == 'vector') serves enc_mode 'continues' and no
-    other mode; a bit Codebook serves every other mode and is refused for 'continues' in the bit codebook's own words."""
+    other mode, as does a zs_amd.rvq.ResidualCodebook (field kind == 'residual': S stages of vectors); a bit Codebook serves every other
+    mode and is refused for 'continues' in the bit codebook's own words."""
     d = read_npz(path)
+    if 'kind' in d and d['kind'].shape == () and d['kind'].dtype.kind == 'U' and str(d['kind']) == 'residual':
+        from .rvq import ResidualCodebook                         # S stages of vectors (zs_amd.rvq): 'continues' and no other mode
+        ResidualCodebook.check_mode(enc_mode, "%s is a residual codebook (kind 'residual'), which serves enc_mode 'continues'" % path)
+        return ResidualCodebook.from_fields(d, path, E)
     if 'kind' in d or 'vectors' in d:
         VectorCodebook.check_mode(enc_mode, "%s is a vector codebook (kind 'vector'), which serves enc_mode 'continues'" % path)
         return VectorCodebook.from_fields(d, path, E)

@@ -246,9 +246,13 @@ def check_vq_train(args, enc_mode=None, c_in=None):
         return None
     vq.VectorCodebook.check_mode(enc_mode, "--vq_train needs enc_mode 'continues'")
     try:
-        return vq.load_codebook(path, enc_mode, E=c_in)
+        cb = vq.load_codebook(path, enc_mode, E=c_in)
     except ValueError as e:
         raise ValueError('--vq_train: %s' % e)
+    if cb.kind == 'residual':
+        raise ValueError("--vq_train: %s is a residual codebook (kind 'residual'): training through a residual codebook is not "
+                         'supported, --vq_train takes a vector codebook (FILE.vq.npz)' % path)
+    return cb
 
 
 def ckpt_path(checkpoint):
