@@ -1358,6 +1358,75 @@ typedef struct {
 } ZsRvqGather;
 int zs_rvq_gather(const ZsRvqGather* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Training through the residual codebook (zs_amd.rvq_train): the per-stage glue of the S-stage straight-through quantiser.
+ * One training iteration is, for every stage s in increasing order, zs_vq_assign -> zs_rvq_commit -> zs_vq_accum -> zs_vq_ema
+ * (-> zs_vq_restart), all but the second unchanged, then zs_rvq_loss and zs_rvq_gather (above, unchanged: the Decoder's operand) in
+ * the forward and zs_rvq_st_bwd in the backward.  The limits on K, E, n and the leading dimensions are the vector codebook's.  A null
+ * struct, a K, E, n or S outside its range, a leading dimension below E, a null operand with work to do, a misaligned operand or a
+ * forbidden overlap return ZS_EINVAL and launch nothing; n == 0 succeeds and launches nothing.  Caller-owned buffers, no allocation, no
+ * synchronisation, stream-ordered; no launch argument depends on the iteration, so a captured graph replays them.  No float atomics
+ * and no fused multiply-add: every result is bitwise equal from run to run.
+ *
+ * zs_rvq_commit: what stage s leaves over, and everything the step wants of it, in one pass over the row.  x [n][ld_x] of `dtype`
+ * (fp32 when src_f32; aligned to its element) is r_s, the stage's input: the encoder's rows at stage 0, the fp32 residual behind it.
+ * idx int32 [n] (zs_vq_assign's of this stage), code fp32 [K][ld_code].  With ok(i) = 0 <= idx[i] < K:
+ *   r[i][j]      = (float) x[i][j] - code[idx[i]][j]      j < E   (fp32 [n][ld_r]; one IEEE fp32 subtraction, bf16 widened exactly)
+ *   x_f32[i][j]  = (float) x[i][j]                        j < E   (fp32 [n][ld_xf], optional: the operand zs_vq_accum wants of bf16 rows)
+ *   idx_acc[i]   = idx[i], or -1 when !ok(i) or row i of x has an element that is not of magnitude < ZS_VQ_MAX_ABS (NaN included);
+ *                  *over += 1 for such a row of x                                      (int32 [n], required; over int32, required)
+ *   a[i][j]      = r[i][j]            when `first`;   a[i][j] + r[i][j] otherwise (read, one fp32 add, written)   (fp32 [n][ld_a])
+ *   partial[w]   = the sum over the rows of workgroup w of (double) r[i][j] * (double) r[i][j], the STORED fp32 residual: every lane
+ *                  adds its terms in double in a fixed order, the 64 lanes of a wave are added pairwise at distances 32, .., 1 and the
+ *                  four waves left to right; partial[w] = 0 for the launch's workgroup count <= w < ZS_VQ_COMMIT_PARTS
+ *                  (double [ZS_VQ_COMMIT_PARTS], required: zs_rvq_loss reads all of them)
+ * Columns E <= j of r, x_f32 and a are not touched.  A row with !ok(i) is never used as an index: r[i] = (float) x[i], it adds nothing
+ * to partial, a[i] = 0 when `first` and is left as it is otherwise, idx_acc[i] = -1 and *bad += 1 (int32, required).  r, x_f32 and a
+ * must not be x or each other.  A row is owned by a team of 2^t <= 64 lanes of one wave, four columns per lane and round, with 16-byte
+ * loads and stores where the operand is 16-byte aligned (x bf16: 8) and its leading dimension a multiple of 4, element by element
+ * otherwise; the magnitude check is an OR over the team. */
+typedef struct {
+  int32_t dtype, src_f32, first;
+  const void* x; int64_t n, ld_x;
+  const int32_t* idx;
+  const float* code; int64_t ld_code; int32_t K, E;
+  float* r; int64_t ld_r;
+  float* x_f32; int64_t ld_xf;
+  int32_t* idx_acc;
+  float* a; int64_t ld_a;
+  double* partial;
+  int32_t* bad; int32_t* over;
+} ZsRvqCommit;
+int zs_rvq_commit(const ZsRvqCommit* p, void* stream);
+/* zs_rvq_loss: the commitment loss of the S stages from zs_rvq_commit's partials.  partial double [S][ZS_VQ_COMMIT_PARTS] dense,
+ * 1 <= S <= ZS_RVQ_MAX_S; loss fp32 [1 + S].  d_s = the sum of partial[s][.]: lane t of 256 adds partial[s][t], [t + 256], .. in
+ * double, a wave's lanes are added pairwise at distances 32, .., 1 and the four waves left to right.
+ *   loss[1 + s] = (float)(scale * d_s)
+ *   loss[0]     = (float)(scale * (((d_0 + d_1) + ..) + d_{S-1}))         (doubles, in increasing s; scale = beta / (n E), a double)
+ * One workgroup.  It has no n: it always launches. */
+typedef struct {
+  const double* partial; int32_t S;
+  double scale;
+  float* loss;
+} ZsRvqLoss;
+int zs_rvq_loss(const ZsRvqLoss* p, void* stream);
+/* zs_rvq_st_bwd: the straight-through gradient plus the commitment terms' of every stage.  dq, dz [n][ld] of `dtype`, 16-byte
+ * aligned, both leading dimensions multiples of 8; a fp32 [n][ld_a] as the last zs_rvq_commit left it (r_1 + .. + r_S added in
+ * increasing stage); g fp32 (2 beta / (n E), rounded once by the caller):
+ *   dz[i][j] = cast(dq[i][j] + g * a[i][j])      j < E;    0 for E <= j < ld_dz
+ * The product and the sum are two fp32 operations, each rounded once (no fused multiply-add), then one cast (to nearest even).  With
+ * S = 1 this is zs_vq_st_bwd's value bit for bit.  dz == dq (with ld_dz == ld_dq) updates in place; any other overlap is undefined.
+ * One lane per 16-byte piece of dz, grid-stride; a is read with 16-byte loads when it is 16-byte aligned and ld_a a multiple of 4. */
+typedef struct {
+  int32_t dtype;
+  const void* dq; int64_t n, ld_dq;
+  const float* a; int64_t ld_a;
+  int32_t E;
+  float g;
+  void* dz; int64_t ld_dz;
+} ZsRvqStBwd;
+int zs_rvq_st_bwd(const ZsRvqStBwd* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,16 @@ S), --synth_dir speaks the first s columns of every *.idx.txt (default: the colu
   python main.py --enc_mode continues --convert_dir in/ --t_speaker V001 --ckpt_pth CKPT --codebook ckpt_english/codebooks/K1024x4.rvq.npz
   python main.py --enc_mode continues --synth_dir idx/ --t_speaker V001 --ckpt_pth CKPT --codebook ckpt_english/codebooks/K1024x4.rvq.npz --rvq_stages 2
 
+--rvq_train FILE.rvq.npz with --train_ae and --enc_mode continues (zs_amd.rvq_train): the autoencoder is trained through that residual
+codebook -- stage 0 snaps every encoder row of a batch, stage s what stage s - 1 left over, the Decoder reads the sum of the S
+codewords exactly as --convert_dir --codebook FILE.rvq.npz builds it, and its input gradient passes straight through; every stage
+commits its input to its codeword (--vq_beta) and every stage's codebook follows its own input rows by the moving average of
+--vq_train (--vq_decay, --vq_restart: the three options serve either flag).  The log gains loss_vq and every stage's share of
+codewords used and perplexity; every checkpoint gets <checkpoint>.rvq.npz beside it, the file --codebook ... --rvq_stages s reads.
+--ema, --device_data and --load_model combine with it; --vq_train, --resume, --valid_every, a multi-rank launch, every other --train*
+mode and a file that is no residual codebook are refused before anything is built:
+  python main.py --enc_mode continues --train_ae --load_model --rvq_train ckpt_english/codebooks/K1024x4.rvq.npz
+
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
 (--train_al, --train_t, --encode, --test_asr) are not part of this build and exit with a clear error.
@@ -299,12 +309,17 @@ def build_parser():
                    help="with --train_ae and enc_mode 'continues': train through the vector codebook FILE.vq.npz (straight-through "
                         'quantiser, commitment term, codebook by exponential moving average); every checkpoint gets a '
                         '<checkpoint>.vq.npz beside it, the file --codebook reads')
-    p.add_argument('--vq_beta', type=float, default=None, metavar='B', help='with --vq_train: commitment weight in (0, 10] (default 0.25)')
+    p.add_argument('--rvq_train', type=str, default=None, metavar='FILE',
+                   help="with --train_ae and enc_mode 'continues': train through the residual codebook FILE.rvq.npz (every stage a "
+                        'straight-through quantiser of what the stage before left over, with its own commitment term and moving '
+                        'average); every checkpoint gets a <checkpoint>.rvq.npz beside it, the file --codebook and --rvq_stages read')
+    p.add_argument('--vq_beta', type=float, default=None, metavar='B',
+                   help='with --vq_train or --rvq_train: commitment weight in (0, 10] (default 0.25)')
     p.add_argument('--vq_decay', type=float, default=None, metavar='D',
-                   help="with --vq_train: decay of the codebook's moving average in [0, 1) (default 0.99)")
+                   help="with --vq_train or --rvq_train: decay of the codebook's moving average in [0, 1) (default 0.99)")
     p.add_argument('--vq_restart', type=float, default=None, metavar='T',
-                   help='with --vq_train: a codeword that took no row of the batch and whose averaged count fell below T, in (0, 1), '
-                        "is put back onto one of the batch's encoder rows (default: dead codewords stay where they are)")
+                   help='with --vq_train or --rvq_train: a codeword that took no row of the batch and whose averaged count fell below '
+                        "T, in (0, 1), is put back onto one of the rows its stage quantised (default: dead codewords stay where they are)")
     p.add_argument('--out_sr', type=_out_sr, default=None,
                    help='sample rate of the wavs --test / --cross_test / --test_single write (hp.out_sr); default: 16000')
     return p
@@ -470,6 +485,16 @@ def check_vq_train(args, enc_mode=None, c_in=None):
     return check(args, enc_mode, c_in)
 
 
+def check_rvq_train(args, enc_mode=None, c_in=None):
+    """--rvq_train is refused, before anything is built and naming the flag, where it cannot do what it says
+    (zs_amd.rvq_train.check_rvq_train): beside --vq_train, without --train_ae or beside another --train* mode, under a multi-rank
+    launch, with --resume or --valid_every, its options out of range; and, once enc_mode is known (argument_runner calls this again
+    after reading hps), an enc_mode other than 'continues', a file that is no residual codebook or a width other than the Decoder's
+    c_in.  Returns the loaded codebook on that second call (None without --rvq_train)."""
+    from zs_amd.rvq_train import check_rvq_train as check
+    return check(args, enc_mode, c_in)
+
+
 def convert_targets(args):
     """--convert_dir and --synth_dir take --t_speaker as a comma-separated list of distinct names (--test_single keeps the single name): the
     list, refused before anything is built when it names no speaker or one twice."""
@@ -492,6 +517,7 @@ def argument_runner(argv=None):
     from zs_amd.validation import check_flags
     check_flags(args)
     check_vq_train(args)
+    check_rvq_train(args)
     check_rvq(args)
     args.t_speakers =convert_targets(args) if (args.convert_dir is not None or args.synth_dir is not None) else None
     if args.dataset == 'surprise':            # main.py:83-88: english -> surprise in every default path
@@ -514,6 +540,8 @@ def argument_runner(argv=None):
         args.enc_mode = hps.enc_mode
     check_voice(args)                         # again, now that enc_mode is known
     args.vq_codebook = check_vq_train(args, args.enc_mode, hps.enc_size)      # (the file is read here: a bit codebook or another width)
+    if args.vq_codebook is None:              # --rvq_train: the same slot, a residual codebook in it (the Trainer picks by its kind)
+        args.vq_codebook = check_rvq_train(args, args.enc_mode, hps.enc_size)
     check_rvq(args, args.enc_mode)            # again, now that enc_mode is known (a residual codebook's fields are read here)
     print('[Runner] - Generation mode: ', 'autoencoder only' if args.enc_only else 'with generator')
     print('[Runner] - Generator mode: ', args.g_mode)
@@ -589,7 +617,7 @@ def main(argv=None):
         os.makedirs(args.ckpt_dir, exist_ok=True)
         model_path = os.path.join(args.ckpt_dir, args.model_name)
         vq_train = None
-        if args.vq_codebook is not None:                  # --vq_train: the --train_ae loop runs through this codebook (zs_amd.vq_train)
+        if args.vq_codebook is not None:                  # --vq_train / --rvq_train: the --train_ae loop runs through this codebook
             from zs_amd.vq_train import BETA, DECAY
             vq_train = (args.vq_codebook, args.vq_beta if args.vq_beta is not None else BETA,
                         args.vq_decay if args.vq_decay is not None else DECAY)

@@ -118,9 +118,9 @@ def roll_window(model_kept, new_path, max_keep):
 
 
 def remove_checkpoint(path):
-    """Remove a checkpoint file and, where there is one, its state file and the codebook --vq_train wrote beside it."""
+    """Remove a checkpoint file and, where there is one, its state file and the codebook --vq_train or --rvq_train wrote beside it."""
     os.remove(path)
-    for side in (state_path(path), path + '.vq.npz'):
+    for side in (state_path(path), path + '.vq.npz', path + '.rvq.npz'):
         if os.path.exists(side):
             os.remove(side)
 

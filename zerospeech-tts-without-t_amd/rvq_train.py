@@ -1,0 +1,238 @@
+"""Training a 'continues' model through its residual codebook: `--rvq_train FILE.rvq.npz` puts the S-stage quantiser of
+zs_amd.rvq between the Encoder and the Decoder of the --train_ae step.  Stage 0 snaps every encoder row to its nearest codeword, stage
+s what stage s - 1 left over (zs_vq_assign, unchanged); the Decoder reads the sum of the S codewords exactly as conversion builds it
+(zs_rvq_gather, unchanged) and hands its input gradient straight through; every stage commits its input to its codeword,
+loss_vq = beta * mean sum_s r_{s+1}^2, whose gradient is 2 beta / (n E) (r_1 + .. + r_S); and every stage's codebook follows its own
+input rows by the exponential moving average of vq_train (zs_vq_accum, zs_vq_ema and, with --vq_restart, zs_vq_restart, all
+unchanged).  The glue on the step's critical path is csrc/zs_rvq_train.hip: zs_rvq_commit (one launch per stage: the residual, the sum
+of the residuals, the index zs_vq_accum reads and the loss's partial sums in one pass over the row), zs_rvq_loss and zs_rvq_st_bwd.
+Step t reads, in every stage, the codebook step t - 1 left: the averages are written to the `next` copies, which become the live ones at
+the head of the next forward.  Everything is enqueued on the current stream with launch arguments that do not change between
+iterations, so the captured step replays it; nothing adds floats atomically, so a run is bitwise reproducible.
+tests/rvq_train_ref.py is the numpy definition.  Not in the reference, which has no codebook."""
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import rvq, vq
+from .vq_train import BETA, DECAY, MAX_ABS, PARTS, check_beta, check_decay, check_restart, perplexity, restart_stride
+
+GOLDEN = 0x9E3779B97F4A7C15        # stage s restarts with the seed (seed + s GOLDEN) mod 2^64
+
+
+class RvqBottleneck(object):
+    """The device state (per stage code, cnorm, N, m) and the plan's buffers of the S-stage quantiser for `rows` encoder rows per
+    step: vq_train.VqBottleneck's interface.  codebook: the rvq.ResidualCodebook the run starts from (code = vectors, N = 1,
+    m = code); ctx: a layers.Ctx (device, compute dtype and the buffer of q)."""
+    kind = 'residual'
+
+    def __init__(self, codebook, beta=BETA, decay=DECAY, rows=0, ctx=None, restart=None):
+        """restart: None, or the threshold in (0, 1) below which a codeword of any stage that took no row this step is put back onto
+        one of the rows that stage quantised (zs_vq_restart)."""
+        if not isinstance(codebook, rvq.ResidualCodebook):
+            raise ValueError('RvqBottleneck: a residual codebook (rvq.ResidualCodebook) is needed')
+        self.beta, self.decay = check_beta(beta), check_decay(decay)
+        self.rows = int(rows)
+        if not 1 <= self.rows < 2 ** 31:
+            raise ValueError('RvqBottleneck: rows must be in [1, 2^31) (got %d)' % self.rows)
+        self.ctx, self.base = ctx, codebook
+        self.S, self.K, self.E = codebook.S, codebook.K, codebook.E
+        dev = self.device = ctx.device
+        S, K, E, n = self.S, self.K, self.E, self.rows
+        self.shift = vq.vq_shift(n, MAX_ABS)                     # one host constant: a row above MAX_ABS is left out in every stage
+        self.scale = self.beta / (float(n) * E)                  # loss_vq = scale * sum_s sum r_{s+1}^2
+        self.g = float(np.float32(2.0 * self.beta / (float(n) * E)))
+        f32 = dict(dtype=torch.float32, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        # the state: what the last step left (`code`, `cnorm` are the `next` copies the averages write)
+        self.code = torch.from_numpy(codebook.vectors).to(dev).contiguous()          # [S, K, E]
+        self.cnorm = torch.from_numpy(codebook.cnorm).to(dev).contiguous()           # [S, K]
+        self.N = torch.ones(S, K, **f32)
+        self.m = self.code.clone()
+        # the live copies: what this step's assigns, commits and gather read
+        self.code_live, self.cnorm_live = self.code.clone(), self.cnorm.clone()
+        self.idx = torch.zeros(S, n, **i32)                      # the planes zs_rvq_gather reads
+        self.idx_acc = torch.zeros(S, n, **i32)
+        # zeroed at the head of every step, per stage: (used | accum's own bad count) | cnt int32 [K] | sum int64 [K][E]
+        self._cnt_at = 1
+        self._sum_at = 1 + (K + 1) // 2
+        self.acc = torch.zeros(S, self._sum_at + K * E, dtype=torch.int64, device=dev)
+        self.cnt = [self.acc[s, self._cnt_at:self._sum_at].view(torch.int32)[:K] for s in range(S)]
+        self.sums = [self.acc[s, self._sum_at:].view(K, E) for s in range(S)]
+        self.partial = torch.zeros(S, PARTS, dtype=torch.float64, device=dev)
+        self.loss = torch.zeros(1 + S, **f32)                    # loss_vq of the last step, then every stage's share of it
+        # sticky: bad idx (commit) | rows above MAX_ABS | bad frames (gather) | codewords restarted so far | restarts skipped
+        self.stat = torch.zeros(5, **i32)
+        self.work = vq.workspace(dev) if n < vq.SPLIT_N else None
+        # two fp32 [n, E] buffers in ping-pong: stage s reads r_s in one and writes r_{s+1} to the other; the fp32 copy of bf16
+        # rows is the first one's first content.  zs_vq_accum, the average and the restart of stage s read r_s behind the commit
+        # of stage s and in front of the commit of stage s + 1, which overwrites it: stream order keeps that safe.
+        self.res = [torch.zeros(n, E, **f32), torch.zeros(n, E, **f32)]
+        self.a = torch.zeros(n, E, **f32)                        # r_1 + .. + r_S, what the backward reads
+        self.restart = None if restart is None else check_restart(restart)
+        if self.restart is not None:
+            self.stride = restart_stride(n)                      # a host constant of the plan
+            self.rwork = torch.zeros(K + 2, **i32)
+        self._frag = {}                                          # (B, T') -> the device table of zs_rvq_gather
+        self.steps = 0
+        self._bits = None
+
+    def _table(self, B, T):
+        """start[b] = b T', len[b] = T': the batch as the B fragments of zs_rvq_gather (built once per shape, before any capture)."""
+        tab = self._frag.get((B, T))
+        if tab is None:
+            tab = self._frag[(B, T)] = (torch.arange(B, dtype=torch.int64, device=self.device) * T,
+                                        torch.full((B,), T, dtype=torch.int32, device=self.device))
+        return tab
+
+    # ---- the step ----------------------------------------------------------------------------------------------------------------------
+    def forward(self, bits, seed=0, seed_ptr=None):
+        """bits: the Act [B, T', E] EncoderEngine.forward returns.  Enqueues, per stage, assign, commit, accum and the codebook's
+        average (and the restart), then the loss and the gather; returns q, an Act the DecoderEngine takes as it takes bits.
+        (seed, seed_ptr): the pair the encoder's forward of this step was given; with restart on, the rows that dead codewords take
+        follow it."""
+        ctx, S, K, E, n = self.ctx, self.S, self.K, self.E, self.rows
+        if bits.rows != n or bits.C != E or bits.t.dtype != ctx.tdt:
+            raise ValueError('RvqBottleneck: built for %d rows of %d columns of %s, got %d rows of %d of %s' %
+                             (n, E, ctx.tdt, bits.rows, bits.C, bits.t.dtype))
+        st = ctx.stream
+        start, length = self._table(bits.B, bits.T)
+        self.code_live.copy_(self.code)                          # the codebooks the step before left
+        self.cnorm_live.copy_(self.cnorm)
+        self.acc.zero_()
+        wide = ctx.tdt != torch.float32                          # the rows need an fp32 copy for zs_vq_accum
+        acc32 = self.acc.view(torch.int32)
+        for s in range(S):
+            code, cn = self.code_live[s], self.cnorm_live[s]
+            if s == 0:
+                x, ld_x, f32 = bits.ptr(), bits.ld, 0
+                rows32, ld32 = (L.ptr(self.res[0]), E) if wide else (x, ld_x)
+            else:
+                x = rows32 = L.ptr(self.res[s & 1])
+                ld_x = ld32 = E
+                f32 = 1
+            vq.launch_assign(st, (L.ZS_F32 if f32 else ctx.dt), x, n, ld_x, code, cn, idx=self.idx[s], work=self.work)
+            L.call('zs_rvq_commit', 'ZsRvqCommit', st, dtype=ctx.dt, src_f32=f32, first=int(s == 0), x=x, n=n, ld_x=ld_x,
+                   idx=L.ptr(self.idx[s]), code=L.ptr(code), ld_code=E, K=K, E=E, r=L.ptr(self.res[(s + 1) & 1]), ld_r=E,
+                   x_f32=(L.ptr(self.res[0]) if s == 0 and wide else None), ld_xf=(E if s == 0 and wide else 0),
+                   idx_acc=L.ptr(self.idx_acc[s]), a=L.ptr(self.a), ld_a=E, partial=L.ptr(self.partial[s]), bad=L.ptr(self.stat),
+                   over=L.ptr(self.stat, 1))
+            head = s * self.acc.stride(0) * 2                    # this stage's (used | bad) words, in int32 elements
+            L.call('zs_vq_accum', 'ZsVqAccum', st, x=rows32, idx=L.ptr(self.idx_acc[s]), n=n, ld_x=ld32, K=K, E=E, shift=self.shift,
+                   cnt=L.ptr(self.cnt[s]), sum=L.ptr(self.sums[s]), bad=L.ptr(acc32, head + 1))
+            L.call('zs_vq_ema', 'ZsVqEma', st, cnt=L.ptr(self.cnt[s]), sum=L.ptr(self.sums[s]), K=K, E=E, shift=self.shift,
+                   decay=self.decay, N=L.ptr(self.N[s]), m=L.ptr(self.m[s]), code=L.ptr(self.code[s]), ld_code=E,
+                   cnorm=L.ptr(self.cnorm[s]), used=L.ptr(acc32, head))
+            if self.restart is not None:
+                L.call('zs_vq_restart', 'ZsVqRestart', st, thresh=self.restart, x=rows32, n=n, ld_x=ld32, idx_acc=L.ptr(self.idx_acc[s]),
+                       cnt=L.ptr(self.cnt[s]), K=K, E=E, N=L.ptr(self.N[s]), m=L.ptr(self.m[s]), code=L.ptr(self.code[s]), ld_code=E,
+                       cnorm=L.ptr(self.cnorm[s]), seed=(int(seed or 0) + s * GOLDEN) % (1 << 64), seed_ptr=seed_ptr,
+                       stride=self.stride, work=L.ptr(self.rwork), restarted=L.ptr(self.stat, 3), skipped=L.ptr(self.stat, 4))
+        L.call('zs_rvq_loss', 'ZsRvqLoss', st, partial=L.ptr(self.partial), S=S, scale=self.scale, loss=L.ptr(self.loss))
+        q = ctx.act('rvq_q_%d_%d' % (bits.B, bits.T), bits.B, bits.T, E)
+        rvq.launch_gather(st, ctx.dt, self.idx, S, self.code_live, start, length, bits.B, bits.T, q.ptr(), q.ld, self.stat[2:])
+        self._bits = bits
+        self.steps += 1
+        return q
+
+    def backward(self, dbits):
+        """dbits: the Act [B, T', E] the Decoder's backward returns (d loss / d q).  Returns d loss / d z, written in place."""
+        if self._bits is None or dbits.rows != self.rows or dbits.C != self.E:
+            raise ValueError('RvqBottleneck.backward: no forward of %d rows before it' % dbits.rows)
+        L.call('zs_rvq_st_bwd', 'ZsRvqStBwd', self.ctx.stream, dtype=self.ctx.dt, dq=dbits.ptr(), n=self.rows, ld_dq=dbits.ld,
+               a=L.ptr(self.a), ld_a=self.E, E=self.E, g=self.g, dz=dbits.ptr(), ld_dz=dbits.ld)
+        return dbits
+
+    # ---- host side ---------------------------------------------------------------------------------------------------------------------
+    def stats(self):
+        """The last step's figures, read from the device (a synchronisation: call where the host syncs anyway): loss_vq, K, S and
+        `stages`, per stage dict(loss_vq, used, perplexity); `used` is the list of the stages' counts.  RuntimeError when a row was
+        left out of an average because an element reached ZS_VQ_MAX_ABS, or an index was outside [0, K)."""
+        stat = self.stat.cpu().numpy()
+        if stat[1]:
+            raise RuntimeError('--rvq_train: %d rows of a stage held a value of magnitude >= %g (or not finite) and were left out of '
+                               "that stage's average" % (int(stat[1]), MAX_ABS))
+        if stat[0] or stat[2]:
+            raise RuntimeError('--rvq_train: zs_vq_assign gave %d indices outside [0, %d)' % (int(stat[0]) + int(stat[2]), self.K))
+        head = self.acc[:, :self._sum_at].cpu().numpy()
+        loss = self.loss.cpu().numpy()
+        stages = []
+        for s in range(self.S):
+            cnt = head[s, self._cnt_at:].view(np.int32)[:self.K]
+            stages.append({'loss_vq': float(loss[1 + s]), 'used': int(head[s, :1].view(np.int32)[0]), 'perplexity': perplexity(cnt)})
+        out = {'loss_vq': float(loss[0]), 'K': self.K, 'S': self.S, 'stages': stages, 'used': [st['used'] for st in stages],
+               'perplexity': [st['perplexity'] for st in stages]}
+        if self.restart is not None:
+            out.update(restarts=int(stat[3]), skipped=int(stat[4]), dead=[int(v) for v in (self.N < self.restart).sum(1).cpu()])
+        return out
+
+    def state_dict(self):
+        return {'code': self.code, 'cnorm': self.cnorm, 'N': self.N, 'm': self.m}
+
+    def load_state_dict(self, sd):
+        for k in ('code', 'cnorm', 'N', 'm'):
+            dst, src = getattr(self, k), torch.as_tensor(sd[k])
+            if tuple(src.shape) != tuple(dst.shape):
+                raise ValueError('RvqBottleneck: state %r has shape %s, this bottleneck %s' % (k, tuple(src.shape), tuple(dst.shape)))
+        for k in ('code', 'cnorm', 'N', 'm'):
+            getattr(self, k).copy_(torch.as_tensor(sd[k]).to(torch.float32))
+
+    def ckpt_meta(self, iteration, s):
+        """The meta fields of <checkpoint>.rvq.npz after `iteration` iterations; s: stats()."""
+        meta = {'trained_iterations': int(iteration), 'beta': self.beta, 'decay': self.decay, 'used': list(s['used'])}
+        if self.restart is not None:
+            meta.update(restart=self.restart, restarts=s['restarts'])
+        return meta
+
+    def to_codebook(self, meta=None):
+        """The codebooks as the last step left them: an rvq.ResidualCodebook whose meta is the starting file's plus `meta`."""
+        out = dict(self.base.meta)
+        out.update(meta or {})
+        return rvq.ResidualCodebook(self.code.cpu().numpy(), out)
+
+
+def check_rvq_train(args, enc_mode=None, c_in=None):
+    """--rvq_train is refused, before anything is built, where it cannot do what it says.  Called before hps is read (enc_mode None:
+    the flag combinations) and again once enc_mode and the Decoder's width are known: then the file is read, and the loaded
+    ResidualCodebook returned (None without --rvq_train).  --vq_beta, --vq_decay and --vq_restart serve --vq_train or --rvq_train;
+    without either, vq_train.check_vq_train refuses them."""
+    import os
+    path = getattr(args, 'rvq_train', None)
+    if path is None:
+        return None
+    if getattr(args, 'vq_train', None) is not None:
+        raise ValueError('--rvq_train cannot be combined with --vq_train: a run trains through one codebook, a residual one '
+                         '(--rvq_train FILE.rvq.npz) or a vector one (--vq_train FILE.vq.npz)')
+    others = [f for f in ('train', 'train_p', 'train_tgat', 'train_c') if getattr(args, f, False)]
+    if others or not getattr(args, 'train_ae', False):
+        raise ValueError('--rvq_train trains the autoencoder through its residual codebook: it needs --train_ae and no other --train* '
+                         'mode' + (' (got --%s)' % others[0] if others else ''))
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise ValueError("--rvq_train runs on one GPU: every stage's counts and sums would need an all-reduce (WORLD_SIZE = %s)"
+                         % os.environ['WORLD_SIZE'])
+    if getattr(args, 'resume', False):
+        raise ValueError('--rvq_train cannot be combined with --resume: the train-state file does not carry the codebooks')
+    if getattr(args, 'valid_every', None) is not None:
+        raise ValueError('--rvq_train cannot be combined with --valid_every: the validation step does not quantise')
+    if getattr(args, 'vq_beta', None) is not None:
+        check_beta(args.vq_beta)
+    if getattr(args, 'vq_decay', None) is not None:
+        check_decay(args.vq_decay)
+    if getattr(args, 'vq_restart', None) is not None:
+        check_restart(args.vq_restart)
+    if enc_mode is None:
+        return None
+    rvq.ResidualCodebook.check_mode(enc_mode, "--rvq_train needs enc_mode 'continues'")
+    try:
+        cb = vq.load_codebook(path, enc_mode, E=c_in)
+    except ValueError as e:
+        raise ValueError('--rvq_train: %s' % e)
+    if cb.kind != 'residual':
+        raise ValueError("--rvq_train: %s is no residual codebook (kind %r): --rvq_train takes FILE.rvq.npz, as --fit_codebook K "
+                         '--rvq S writes it; a vector codebook goes to --vq_train' % (path, cb.kind))
+    return cb
+
+
+def ckpt_path(checkpoint):
+    """<checkpoint name>.rvq.npz: the residual codebook beside a checkpoint."""
+    return checkpoint + '.rvq.npz'

@@ -46,8 +46,9 @@ class AEStep(object):
     final."""
 
     def __init__(self, encoder, decoder, lr=1e-4, betas=(0.5, 0.9), max_grad_norm=5.0, use_graph=None, ema=None, vq=None):
-        """vq (not in the reference): None, or a vq_train.VqBottleneck: the step then quantises the encoder's rows in front of the
-        Decoder and hands the Decoder's input gradient through it; its loss_vq stays beside loss_rec, in vq.loss."""
+        """vq (not in the reference): None, or a vq_train.VqBottleneck (or an rvq_train.RvqBottleneck, which has its interface:
+        DESIGN 34): the step then quantises the encoder's rows in front of the Decoder and hands the Decoder's input gradient through
+        it; its loss_vq stays beside loss_rec, in vq.loss."""
         self.Encoder, self.Decoder = encoder, decoder
         self.vq = vq
         self.adam_step = 0                   # the pair's Adam step count (on the device: _step_dev)
@@ -688,6 +689,8 @@ class Trainer(object):
         that codebook (vq_train.VqBottleneck inside the AEStep), logs loss_vq, the codewords used and the perplexity, and
         writes <checkpoint>.vq.npz beside every checkpoint.  Every other mode runs without the quantiser.  A fourth element is the
         threshold below which dead codewords are restarted; the log and the file's meta then carry the restarts.
+        The codebook's kind picks the bottleneck: an rvq.ResidualCodebook trains through its S stages (rvq_train.RvqBottleneck,
+        DESIGN 34), the log carries every stage's share of codewords used and the file is <checkpoint>.rvq.npz.
         valid (not in the reference): None, or a validation.ValidConfig: train(mode='pretrain_AE') then validates on its set
         every `every` iterations and after the last one (ValidStep), logs and records the result and keeps the best checkpoint.
         ema (not in the reference): None, or the decay in [0, 1) of an exponential moving average of the weights that every
@@ -759,6 +762,8 @@ class Trainer(object):
             cb, beta, decay = self.vq_train[:3]
             restart = self.vq_train[3] if len(self.vq_train) > 3 else None      # the threshold of zs_vq_restart
             cb.check_width(hps.enc_size, 'vq_train')
+            if cb.kind == 'residual':                   # the codebook's kind picks the bottleneck
+                from .rvq_train import RvqBottleneck as VqBottleneck
             self.vq = VqBottleneck(cb, beta, decay, encoded_rows(hps.batch_size, hps.seg_len), layers.Ctx(dev, dt), restart=restart)
         self.clf = ClfStep(self.ae, self.SpeakerClassifier, lr=hps.lr, betas=(0.5, 0.9), max_grad_norm=hps.max_grad_norm, ema=self.ema)
         self.s2 = None                      # PatchGANStep, built on first use (its optimizer state is 2 x 53 M floats)
@@ -1319,9 +1324,17 @@ class Trainer(object):
                 if log and bn is not None:
                     info = {f'{flag}/pre_loss_rec': loss_t.item()}                             # (the host sync)
                     s = bn.stats()                                                             # raises for a row left out of the average
-                    info.update({f'{flag}/pre_loss_vq': s['loss_vq'], f'{flag}/vq_used': s['used'] / float(s['K']),
-                                 f'{flag}/vq_perplexity': s['perplexity']})
-                    line = 'pre_AE:[%06d/%06d], loss_rec=%.3f, loss_vq=%.4f, used=%.3f, perplexity=%.1f'
+                    if 'stages' in s:                                                          # a residual codebook: every stage's share
+                        info[f'{flag}/pre_loss_vq'] = s['loss_vq']
+                        for i, stg in enumerate(s['stages']):
+                            info.update({f'{flag}/vq_used_%d' % i: stg['used'] / float(s['K']),
+                                         f'{flag}/vq_perplexity_%d' % i: stg['perplexity']})
+                        line = 'pre_AE:[%06d/%06d], loss_rec=%.3f, loss_vq=%.4f' + ''.join(
+                            ', used%d=%%.3f, perplexity%d=%%.1f' % (i, i) for i in range(len(s['stages'])))
+                    else:
+                        info.update({f'{flag}/pre_loss_vq': s['loss_vq'], f'{flag}/vq_used': s['used'] / float(s['K']),
+                                     f'{flag}/vq_perplexity': s['perplexity']})
+                        line = 'pre_AE:[%06d/%06d], loss_rec=%.3f, loss_vq=%.4f, used=%.3f, perplexity=%.1f'
                     if bn.restart is not None:
                         info[f'{flag}/vq_restarts'] = s['restarts']
                         line += ', restarts=%d'
@@ -1332,13 +1345,17 @@ class Trainer(object):
                     self.validate(iteration + 1, model_path, flag, keep_state)                 # before this iteration's checkpoint
 
             def save_codebook(path, iteration):
-                """<checkpoint>.vq.npz beside the checkpoint: the file --codebook reads (vq.VectorCodebook.save, format unchanged)."""
+                """<checkpoint>.vq.npz (.rvq.npz) beside the checkpoint: the file --codebook reads (the codebook's own save, format
+                unchanged)."""
                 s = bn.stats()
                 bn.to_codebook(bn.ckpt_meta(iteration, s)).save(ckpt_path(path))
 
             bn = self.vq
             if bn is not None:
-                from .vq_train import ckpt_path
+                if bn.kind == 'residual':
+                    from .rvq_train import ckpt_path
+                else:
+                    from .vq_train import ckpt_path
                 if resumable or vcfg is not None or parallel.multi_rank():
                     raise ValueError('vq_train cannot be combined with resume, validation or several ranks')
                 self.ae.vq = bn

@@ -79,6 +79,7 @@ class VqBottleneck(object):
     """The device state (code, cnorm, N, m) and the plan's buffers of the quantiser for `rows` encoder rows per step.
     codebook: the vq.VectorCodebook the run starts from (code = vectors, N = 1, m = code); ctx: a layers.Ctx (device, compute dtype
     and the buffer of q)."""
+    kind = 'vector'                                              # its codebook's (rvq_train.RvqBottleneck: 'residual')
 
     def __init__(self, codebook, beta=BETA, decay=DECAY, rows=0, ctx=None, restart=None):
         """restart: None, or the threshold in (0, 1) below which a codeword that took no row this step is put back onto one of the
@@ -221,9 +222,11 @@ def check_vq_train(args, enc_mode=None, c_in=None):
     import os
     path = getattr(args, 'vq_train', None)
     if path is None:
+        if getattr(args, 'rvq_train', None) is not None:       # the three options serve it too (rvq_train.check_rvq_train)
+            return None
         for flag in ('vq_beta', 'vq_decay', 'vq_restart'):
             if getattr(args, flag, None) is not None:
-                raise ValueError('--%s needs --vq_train' % flag)
+                raise ValueError('--%s needs --vq_train or --rvq_train' % flag)
         return None
     others = [f for f in ('train', 'train_p', 'train_tgat', 'train_c') if getattr(args, f, False)]
     if others or not getattr(args, 'train_ae', False):
