@@ -1426,6 +1426,30 @@ typedef struct {
   void* dz; int64_t ld_dz;
 } ZsRvqStBwd;
 int zs_rvq_st_bwd(const ZsRvqStBwd* p, void* stream);
+/* zs_xfade_gather: the vocoder's padded input out of decode windows that overlap (convert.unit_windows): every output row is one
+ * source row, or the cross-fade of two.  src fp32 [src_rows][ld_src]; out fp32 [rows][out_ld]; i0, i1 int32 [rows] and w0, w1 fp32
+ * [rows], device tables planned on the host (convert._xfade_tables); cols <= min(ld_src, out_ld):
+ *   out[r][f] = D( i0[r] < 0 ? 0
+ *                : i1[r] < 0 ? src[i0[r]][f]
+ *                : fl32(fl32(w0[r] * src[i0[r]][f]) + fl32(w1[r] * src[i1[r]][f])) )        f < cols
+ * Two products and one sum, each rounded once to fp32 (no fused multiply-add); a row with one source is copied, not multiplied, and
+ * w0, w1 are read for blended rows only.  D: the expression of zs_gl_denormalize / zs_gen_scatter (one shared device function: the
+ * same bits for the same input) when denorm is set, else the identity.  A row with i0 outside [-1, src_rows) or i1 outside
+ * [-1, src_rows) reads nothing and holds D(0), as zs_frag_gather treats a bad table entry.  out must not alias src; the columns
+ * cols <= f < out_ld are not written.  Rows need only 4-byte alignment (513 floats): one wave per row, the grid strides over rows,
+ * 16-byte stores over the 16-byte aligned middle of an output row (the source rows read in 16-byte pieces at their own 4-byte
+ * alignment, both rows of a blended frame in the same pass) and single elements at its two ends.
+ * No allocation, no synchronisation, no atomics; stream-ordered and bitwise reproducible.  Errors (ZS_EINVAL, nothing is launched):
+ * a null operand with rows > 0; a negative size; cols > ld_src or cols > out_ld; rows >= 2^31.  rows == 0 succeeds and launches
+ * nothing. */
+typedef struct {
+  const float* src; int64_t src_rows, ld_src;
+  const int32_t* i0; const int32_t* i1;
+  const float* w0; const float* w1;
+  float* out; int64_t rows, out_ld;
+  int32_t cols, denorm;
+} ZsXfadeGather;
+int zs_xfade_gather(const ZsXfadeGather* p, void* stream);
 
 #ifdef __cplusplus
 }

@@ -114,6 +114,16 @@ codewords used and perplexity; every checkpoint gets <checkpoint>.rvq.npz beside
 mode and a file that is no residual codebook are refused before anything is built:
   python main.py --enc_mode continues --train_ae --load_model --rvq_train ckpt_english/codebooks/K1024x4.rvq.npz
 
+--overlap FRAMES with --synth_dir or --convert_dir (zs_amd.convert.unit_windows): a long utterance is decoded in windows of seg_len
+frames that share FRAMES of them, and the shared frames are cross-faded on the device (zs_xfade_gather) instead of the pieces being
+laid end to end, so the spectrogram no longer jumps every seg_len frames.  FRAMES is 0 or a multiple of 8 up to half of seg_len (64 at
+the shipped settings).  The units do not change: --convert_dir encodes and writes them as without the flag and speaks them as
+--synth_dir --overlap would speak the files it wrote; an utterance of at most 2 (seg_len / 8) units is one window either way.  Both
+manifests gain "overlap"; a 'continues' model needs --codebook for --convert_dir --overlap, and the flag is refused without one of the
+two modes, before anything is built:
+  python main.py --synth_dir units/ --t_speaker V001 --ckpt_pth CKPT --overlap 32
+  python main.py --convert_dir in/ --t_speaker V001,V002 --ckpt_pth CKPT --overlap 32
+
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
 (--train_al, --train_t, --encode, --test_asr) are not part of this build and exit with a clear error.
@@ -320,6 +330,9 @@ def build_parser():
     p.add_argument('--vq_restart', type=float, default=None, metavar='T',
                    help='with --vq_train or --rvq_train: a codeword that took no row of the batch and whose averaged count fell below '
                         "T, in (0, 1), is put back onto one of the rows its stage quantised (default: dead codewords stay where they are)")
+    p.add_argument('--overlap', type=int, default=None, metavar='FRAMES',
+                   help='with --synth_dir / --convert_dir: decode in windows that share FRAMES spectrogram frames and cross-fade them '
+                        '(0, or a multiple of 8 up to 8 * ((seg_len // 8) // 2)); the units do not change; default: pieces laid end to end')
     p.add_argument('--out_sr', type=_out_sr, default=None,
                    help='sample rate of the wavs --test / --cross_test / --test_single write (hp.out_sr); default: 16000')
     return p
@@ -495,6 +508,27 @@ def check_rvq_train(args, enc_mode=None, c_in=None):
     return check(args, enc_mode, c_in)
 
 
+def check_overlap(args, seg_len=None, enc_mode=None):
+    """--overlap is refused, before anything is built, where it cannot do what it says: without --synth_dir or --convert_dir; and,
+    once hps is read (argument_runner calls this again with its seg_len and the enc_mode), for a value outside the window rule of
+    that seg_len (zs_amd.convert.check_overlap_value) and with --convert_dir on a 'continues' model without --codebook, which has
+    no units to speak from."""
+    overlap = getattr(args, 'overlap', None)
+    if overlap is None:
+        return
+    if args.convert_dir is None and args.synth_dir is None:
+        raise ValueError('--overlap needs --synth_dir or --convert_dir: it sets how their decode windows are joined')
+    if seg_len is None:
+        return
+    from zs_amd.convert import check_overlap_value
+    try:
+        check_overlap_value(overlap, seg_len)
+    except ValueError as e:
+        raise ValueError('--overlap: %s' % e)
+    if overlap and args.convert_dir is not None and enc_mode == 'continues' and getattr(args, 'codebook', None) is None:
+        raise ValueError("--overlap with --convert_dir speaks the units it writes: enc_mode 'continues' has none without --codebook")
+
+
 def convert_targets(args):
     """--convert_dir and --synth_dir take --t_speaker as a comma-separated list of distinct names (--test_single keeps the single name): the
     list, refused before anything is built when it names no speaker or one twice."""
@@ -519,6 +553,7 @@ def argument_runner(argv=None):
     check_vq_train(args)
     check_rvq_train(args)
     check_rvq(args)
+    check_overlap(args)
     args.t_speakers =convert_targets(args) if (args.convert_dir is not None or args.synth_dir is not None) else None
     if args.dataset == 'surprise':            # main.py:83-88: english -> surprise in every default path
         for action in parser._actions:
@@ -543,6 +578,7 @@ def argument_runner(argv=None):
     if args.vq_codebook is None:              # --rvq_train: the same slot, a residual codebook in it (the Trainer picks by its kind)
         args.vq_codebook = check_rvq_train(args, args.enc_mode, hps.enc_size)
     check_rvq(args, args.enc_mode)            # again, now that enc_mode is known (a residual codebook's fields are read here)
+    check_overlap(args, hps.seg_len, args.enc_mode)      # again, now that seg_len and enc_mode are known
     print('[Runner] - Generation mode: ', 'autoencoder only' if args.enc_only else 'with generator')
     print('[Runner] - Generator mode: ', args.g_mode)
     print('[Runner] - Encoder mode: ', args.enc_mode)
@@ -702,10 +738,12 @@ def main(argv=None):
             target_classify(trainer, hps.seg_len, args.synthesis_list, result_dir, flag='test')
         if args.convert_dir is not None:                  # not in the reference: a folder of sound files to the target voices
             convert_dir(trainer, hps.seg_len, args.convert_dir, args.speaker2id_path, os.path.join(result_dir, 'convert'), args.t_speakers,
-                        args.enc_only, voices=voices, codebook=cb, codebook_file=args.codebook)
+                        args.enc_only, voices=voices, codebook=cb, codebook_file=args.codebook,
+                        **({'overlap': args.overlap} if args.overlap is not None else {}))
         if args.synth_dir is not None:                    # not in the reference: a folder of unit files spoken by the target voices
             synth_dir(trainer, hps.seg_len, args.synth_dir, args.speaker2id_path, os.path.join(result_dir, 'synth'), args.t_speakers,
-                      args.enc_only, voices=voices, codebook=cb, codebook_file=args.codebook)
+                      args.enc_only, voices=voices, codebook=cb, codebook_file=args.codebook,
+                      **({'overlap': args.overlap} if args.overlap is not None else {}))
 
 
 if __name__ == '__main__':

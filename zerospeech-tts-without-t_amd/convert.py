@@ -350,6 +350,47 @@ def unit_fragments(n_units, seg_len):
     return out
 
 
+def check_overlap_value(overlap, seg_len):
+    """The overlap of two decode windows, in spectrogram frames like seg_len: 0 (none), or a multiple of 8 in [8, 8 * (Lu // 2)] with
+    Lu = seg_len // 8, so that no unit lies in more than two windows.  Returns it as an int; ValueError naming the value and the
+    range for anything else."""
+    Lu = int(seg_len) // 8
+    top = 8 * (Lu // 2)
+    try:
+        ok = int(overlap) == overlap and not isinstance(overlap, bool)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not (overlap == 0 or (overlap % 8 == 0 and 8 <= overlap <= top)):
+        raise ValueError('overlap must be 0 or a multiple of 8 in [8, %d] frames for seg_len %d (got %r)' % (top, int(seg_len), overlap))
+    return int(overlap)
+
+
+def unit_windows(n_units, seg_len, overlap):
+    """The decode windows of an utterance of n_units units, as [(a, b)] in units, for windows that share `overlap` frames
+    (check_overlap_value).  With Lu = seg_len // 8, Vu = overlap // 8 and Hu = Lu - Vu: an utterance of at most 2 Lu units is one
+    window (0, n); else windows (a, a + Lu) from a = 0 in steps of Hu while more than 2 Lu units lie behind a, then the tail (a, n)
+    of Lu + Vu < len <= 2 Lu units.  Consecutive windows share exactly Vu units and no unit lies in more than two.  With overlap 0
+    the window lengths are unit_fragments(n_units, seg_len).  The units themselves do not change: the overlap is the decode's alone."""
+    overlap = check_overlap_value(overlap, seg_len)
+    n, Lu = int(n_units), int(seg_len) // 8
+    if n < 1 or Lu < 1:
+        raise ValueError('unit_windows: need n_units >= 1 and seg_len >= 8 (got %d, %d)' % (n, seg_len))
+    Hu = Lu - overlap // 8
+    out, a = [], 0
+    while n - a > 2 * Lu:
+        out.append((a, a + Lu))
+        a += Hu
+    out.append((a, n))
+    return out
+
+
+def xfade_weights(V):
+    """The cross-fade over the V frames two windows share: frame j takes w[j] of the later window and u[j] of the earlier one,
+    w[j] = (2 j + 1) / (2 V) and u[j] = 1 - (2 j + 1) / (2 V), each evaluated in double and rounded once to fp32.  Returns (w, u)."""
+    x = (2.0 * np.arange(int(V), dtype=np.float64) + 1.0) / (2.0 * int(V))
+    return x.astype(np.float32), (1.0 - x).astype(np.float32)
+
+
 def convert(trainer, seg_len, src_speaker_spec, src_speaker, tar_speaker, utt_id, speaker2id, result_dir, enc_only=True,
             save=['wav', 'enc']):
     src_speaker_spec, PADDED = _pad_min(src_speaker_spec)
@@ -484,6 +525,11 @@ def _unit_items(u, n_units, seg_len):
     return [_Item(u, k, a, b, None) for k, (a, b) in enumerate(zip([0] + ends[:-1], ends))]
 
 
+def _window_items(u, n_units, seg_len, overlap):
+    """The items of utterance u of n_units units decoded in overlapping windows: those of unit_windows, which share units."""
+    return [_Item(u, k, a, b, None) for k, (a, b) in enumerate(unit_windows(n_units, seg_len, overlap))]
+
+
 def _split_chunks(items, full_len, max_batch):
     """Two kinds of batches instead of one per distinct length (the fragment rule leaves ~60 tail lengths per 64 utterances):
     the fragments of exactly full_len as plain batches, everything else (tails of seg_len .. 2 seg_len - 2 frames, short
@@ -579,6 +625,45 @@ def _gather_index(chunks, out_rows, shapes, n_utt):
     for it, r0, n, s in zip(flat, first, counts, at):
         idx[it.u, s:s + n] = np.arange(r0, r0 + n)
     return idx, ulens, total
+
+
+def _xfade_tables(chunks, first, n_utt):
+    """The tables of zs_xfade_gather for a batch decoded in overlapping windows (_window_items): per row of the vocoder's padded
+    input [n_utt, T_max], where it comes from in a source table of decoded rows.  first[j]: the source row of the first decoded
+    frame of the j-th window in chunk order (_flat), whose 8 n_j rows follow it one by one.  Frame t of utterance u lies in the
+    window(s) that hold unit t // 8: one window -> i0 its row, i1 = -1; the V frames windows k and k + 1 share, at j = t - 8 a_{k+1}
+    -> i0 the row in window k with w0 = u[j], i1 the row in window k + 1 with w1 = w[j] (xfade_weights(V)); behind an utterance's
+    end i0 = -1.  Returns (T_max, frames per utterance, i0 int32, i1 int32, w0 fp32, w1 fp32), the tables flat [n_utt * T_max]."""
+    by_utt = [[] for _ in range(n_utt)]
+    for it, r0 in zip(_flat(chunks), first):
+        by_utt[it.u].append((it.k, it.a, it.b, int(r0)))
+    ulens = []
+    for u, ws in enumerate(by_utt):
+        ws.sort()
+        if not ws or ws[0][1] != 0:
+            raise ValueError('utterance %d has no window that starts at its first unit' % u)
+        ulens.append(8 * ws[-1][2])
+    Tm = max(ulens)
+    i0 = np.full((n_utt, Tm), -1, dtype=np.int32)
+    i1 = np.full((n_utt, Tm), -1, dtype=np.int32)
+    w0 = np.zeros((n_utt, Tm), dtype=np.float32)
+    w1 = np.zeros((n_utt, Tm), dtype=np.float32)
+    for u, ws in enumerate(by_utt):
+        done = 0                                              # the frames the windows so far cover
+        for _, a, b, r0 in ws:
+            lo, hi = 8 * a, 8 * b
+            if not lo <= done < hi:
+                raise ValueError('utterance %d: the window of units [%d, %d) does not continue the %d frames before it' % (u, a, b, done))
+            V = done - lo                                     # shared with the window before
+            if V:
+                if (i1[u, lo:done] >= 0).any():
+                    raise ValueError('utterance %d: a frame of the window of units [%d, %d) lies in three windows' % (u, a, b))
+                w, uw = xfade_weights(V)
+                i1[u, lo:done] = np.arange(r0, r0 + V, dtype=np.int32)
+                w0[u, lo:done], w1[u, lo:done] = uw, w
+            i0[u, done:hi] = np.arange(r0 + V, r0 + hi - lo, dtype=np.int32)
+            done = hi
+    return Tm, ulens, i0.reshape(-1), i1.reshape(-1), w0.reshape(-1), w1.reshape(-1)
 
 
 def _upload_tables(starts, lens, chunks, dev):
@@ -691,6 +776,8 @@ class _Units(object):
     """What conversion does with units under a codebook of one kind (the codebook's units() hands one out per batch or folder run):
     the three points of a batch of _enqueue_encode (plan, operand, finish), the encodings _assemble returns, and what the folder
     drivers read, speak and write.  _BitUnits, _VectorUnits and _ResidualUnits answer the same calls."""
+
+    keep_units = False                            # finish leaves the utterance-ordered device buffer of the units in q.units_dev
 
     def __init__(self, codebook):
         self.cb = codebook
@@ -805,7 +892,10 @@ class _VectorUnits(_Units):
     def finish(self, q, units_dev):
         """Behind the last chunk: the chunks' indices into utterance order, then one copy.  The batch's device buffers go with it."""
         idx_all, dist_all = (torch.cat(self.idx), torch.cat(self.dist)) if len(self.idx) > 1 else (self.idx[0], self.dist[0])
-        q.idx_host = _to_host(idx_all[self.src])
+        idx_utt = idx_all[self.src]
+        q.idx_host = _to_host(idx_utt)
+        if self.keep_units:                                   # spoken from behind this batch (resynth_batch(overlap=...)): int32 [units]
+            q.units_dev = idx_utt
         q.cb_total = _to_host(dist_all[self.src].sum(dtype=torch.float64).reshape(1))
         self.idx = self.dist = self.work = self.src = self.dense = None
 
@@ -885,7 +975,10 @@ class _ResidualUnits(_VectorUnits):
         """Behind the last chunk: the planes into utterance order (_vq_index_map), then one copy: q.idx_host int32 [units, s'], a row per
         frame, and q.cb_total double [s'], the summed squared distance left behind every stage (the last: that of the units written)."""
         idx_all, dist_all = (torch.cat(self.idx, dim=1), torch.cat(self.dist, dim=1)) if len(self.idx) > 1 else (self.idx[0], self.dist[0])
-        q.idx_host = _to_host(idx_all[:, self.src].t().contiguous())
+        planes = idx_all[:, self.src]
+        q.idx_host = _to_host(planes.t().contiguous())
+        if self.keep_units:                                   # as _VectorUnits.finish: the planes int32 [s', units]
+            q.units_dev = planes
         q.cb_total = _to_host(dist_all[:, self.src].sum(dim=1, dtype=torch.float64))
         self.idx = self.dist = self.work = self.src = self.dense = self.resid = None
 
@@ -937,7 +1030,7 @@ class _ResidualUnits(_VectorUnits):
 
 
 def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host, enc_only=True, denorm=False, pack=False,
-                    codebook=None, rows_on_device=False):
+                    codebook=None, rows_on_device=False, keep_units=False):
     """Fragment rule + every Encoder / Decoder launch of a batch of utterances, WITHOUT a host synchronisation: the caller decides
     what else to put on the stream (the vocoder) before it waits.
     enc_only=False (decode_speakers required): the stage-2 generator as well, and zs_gen_scatter writes every chunk's converted rows
@@ -953,13 +1046,16 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
     chunk's rows, read in place from the engine's output -> zs_vq_gather (Decoder.forward_indices) -> the Decoder's launches; the
     chunks' indices are brought into utterance order on the device (_vq_index_map) and copied once (q.idx_host), with the summed
     squared distance of the returned units (q.cb_total, a double), and the encodings returned are the codewords of the indices.
-    rows_on_device: the fp32 encodings stay on the device (q.enc_dev, one tensor per chunk) instead of being copied to the host."""
+    rows_on_device: the fp32 encodings stay on the device (q.enc_dev, one tensor per chunk) instead of being copied to the host.
+    keep_units: under a vector or residual codebook the utterance-ordered device buffer of the indices, which the copy to the host is
+    made from, stays in q.units_dev (bit-packed units are there whenever they are packed), in the layout q.uoffs describes."""
     side = None                                               # what the codebook's kind does to this batch (_BitUnits, _VectorUnits)
     if codebook is not None:
         _check_codebook(codebook, trainer)
         if int(trainer.Encoder.enc_size) != codebook.E:
             raise ValueError("codebook field E is %d, the Encoder's enc_size is %d" % (codebook.E, int(trainer.Encoder.enc_size)))
         side, want_packed = codebook.units(), pack
+        side.keep_units = bool(keep_units)
         pack = pack or side.packs
     if pack and trainer.enc_mode == 'continues':
         raise ValueError("enc_mode 'continues' has no units to pack (its encodings are not 0 / 1)")
@@ -1161,7 +1257,7 @@ def _encode_result(q, decode_speakers, to_host, enc_only, units_on_device):
 
 
 def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, noise_fn=None, max_batch=256, defer=False, enc_only=True,
-                  momentum=None, codebook=None, want_idx=False):
+                  momentum=None, codebook=None, want_idx=False, overlap=0):
     """test_encode + convert(enc_only) + spectrogram2wav for a batch of utterances as ONE enqueue (convert.py:151-165, 55-62):
     the fragments' Encoder / Decoder launches, the gather of the decoded fragments into the vocoder's padded [n, T_max, 513]
     input (one index kernel on the device), de-normalisation, the Griffin-Lim loop, de-emphasis, the trim statistics and the
@@ -1175,10 +1271,18 @@ def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, 
     momentum: the vocoder's fast Griffin-Lim momentum (see griffin_lim_batch; None: hp.gl_momentum).
     codebook: as encode_batch's -- the Decoder, the generator and the returned encodings see the snapped units; want_idx=True
     makes the result (encodings, wavs, codeword indices int32 [U_i] per utterance, summed Hamming distance of the snap -- under a
-    vector codebook, enc_mode 'continues', the summed squared Euclidean distance, a float)."""
+    vector codebook, enc_mode 'continues', the summed squared Euclidean distance, a float).
+    overlap > 0 (frames; check_overlap_value): encode_batch, then the matching synth_units_batch / synth_index_batch(overlap=...) of
+    the units or indices it returns, as one enqueue -- the encoder runs without a decode, and the decode windows of unit_windows read
+    the units where the encoder left them on the device.  The encodings returned are encode_batch's.  An input padded to MIN_LEN is
+    spoken from the truncated units it returns, as --synth_dir would speak its file, so one of fewer than 2 units is refused, as is
+    enc_mode 'continues' without a codebook, which has nothing to speak from; both before anything is enqueued."""
     momentum = gl_momentum(momentum)
     if want_idx and codebook is None:
         raise ValueError('resynth_batch: want_idx needs a codebook')
+    if check_overlap_value(overlap, seg_len):
+        return _resynth_overlap(specs, trainer, seg_len, speakers, n_iter, do_trim, noise_fn, max_batch, defer, enc_only, momentum, codebook,
+                                want_idx, overlap)
     if not enc_only:
         q = _enqueue_encode(specs, trainer, seg_len, speakers, noise_fn, max_batch, dec_to_host=False, enc_only=False, denorm=True,
                             codebook=codebook)
@@ -1188,6 +1292,61 @@ def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, 
         t, ulens = _gather_decoded(q, [[8 * _t8(n) for n in lens] for _, lens in q.chunks])
         fin = _enqueue_vocoder(t, ulens, n_iter, do_trim, q.dev, momentum=momentum)
     return _finish_resynth(q, fin, defer, want_idx)
+
+
+def _unit_counts(specs, seg_len):
+    """The units encode_batch returns for each utterance, from the frame counts alone (the rules of _enqueue_encode: padding to
+    MIN_LEN and its truncation, _frame_items, _t8)."""
+    counts = []
+    for u, spec in enumerate(specs):
+        n = int(spec.shape[0])
+        items = _frame_items(u, max(n, MIN_LEN), seg_len, n < MIN_LEN)
+        counts.append(sum(it.trunc if it.trunc is not None else _t8(it.n) for it in items))
+    return counts
+
+
+def _resynth_overlap(specs, trainer, seg_len, speakers, n_iter, do_trim, noise_fn, max_batch, defer, enc_only, momentum, codebook, want_idx,
+                     overlap):
+    """resynth_batch with overlap > 0, as one enqueue: _enqueue_encode without a decode leaves the batch's units on the device in
+    utterance order -- bit-packed (pack=True, snapped in place under a bit codebook), or the index buffer a vector or residual
+    codebook's finish makes -- and _enqueue_synth decodes the windows of unit_windows over that buffer, whose layout (q.uoffs) is
+    the one _unit_tables expects."""
+    if len(speakers) != len(specs) or not len(specs):
+        raise ValueError('resynth_batch: %d target speakers for %d utterances' % (len(speakers), len(specs)))
+    if codebook is None and trainer.enc_mode == 'continues':
+        raise ValueError("resynth_batch: overlap = %d needs units to speak from, and enc_mode 'continues' has none without a codebook"
+                         % overlap)
+    if codebook is not None:
+        _check_codebook(codebook, trainer)
+    _check_speaker_range(speakers, int(trainer.Decoder.c_a))
+    shift = 0 if enc_only else check_gen_targets(trainer, speakers)
+    counts = _unit_counts(specs, seg_len)
+    short = [u for u, n in enumerate(counts) if n < 2]
+    if short:
+        raise ValueError('resynth_batch: overlap = %d speaks the units an utterance returns, and utterance %d returns %d (an input '
+                         'shorter than MIN_LEN = %d frames); the Decoder needs two' % (overlap, short[0], counts[short[0]], MIN_LEN))
+    dec, dev = trainer.Decoder, trainer.device
+    kind = getattr(codebook, 'kind', None)
+    q = _enqueue_encode(specs, trainer, seg_len, None, noise_fn, max_batch, dec_to_host=False, pack=codebook is None, codebook=codebook,
+                        keep_units=True)                      # (a bit codebook packs by itself and returns the units unpacked)
+    if [int(n) for n in np.diff(q.uoffs)] != counts:
+        raise L.ZsError('resynth_batch: the encoder left %s units where the plan has %s' % (np.diff(q.uoffs).tolist(), counts))
+    units_dev = q.units_dev
+    if kind in ('vector', 'residual'):
+        code_d, _ = codebook.to(dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        if kind == 'residual':                                # the planes int32 [s', units]
+            operand = lambda tab, B, T0, ch, lens_p: dec.forward_index_planes(units_dev, units_dev.shape[0], code_d, tab[0], tab[1], B, T0,
+                                                                              ch, bad, lengths=lens_p)
+        else:
+            operand = lambda tab, B, T0, ch, lens_p: dec.forward_indices(units_dev, code_d, tab[0], tab[1], B, T0, ch, bad, lengths=lens_p)
+    else:
+        operand = lambda tab, B, T0, ch, lens_p: dec.forward_units(units_dev, tab[0], tab[1], B, T0, ch, lengths=lens_p)
+    items = [it for u, n in enumerate(counts) for it in _window_items(u, n, seg_len, overlap)]
+    chunks = _split_chunks(items, int(seg_len) // 8, max_batch)
+    fin, _, _ = _enqueue_synth(trainer, seg_len, chunks, q.uoffs, speakers, enc_only, shift, n_iter, do_trim, momentum, False, operand,
+                               overlap=overlap)
+    return _finish_resynth(q, fin, defer, want_idx, unpack=(int(trainer.Encoder.enc_size) if codebook is None else None))
 
 
 def _gather_decoded(q, out_rows):
@@ -1209,10 +1368,13 @@ def _wait_vocoder(fin, dev):
     return wavs
 
 
-def _finish_resynth(q, fin, defer, want_idx=False):
+def _finish_resynth(q, fin, defer, want_idx=False, unpack=None):
+    """unpack: the width E of units that were bit-packed for the device's sake alone and are returned as [U_i, E] of 0 / 1."""
     def finish():
         q.enc_done.synchronize()                              # the encodings are on the host; the vocoder is still running
         encs, _ = _assemble(q, None)
+        if unpack is not None:
+            encs = [unpack_units(e, unpack) for e in encs]
         wavs = _wait_vocoder(fin, q.dev)
         return (encs, wavs) + _unit_indices(q.idx_host, q.cb_total, q.uoffs) if want_idx else (encs, wavs)
     return finish if defer else finish()
@@ -1246,7 +1408,7 @@ def _check_units(units, E, packed):
 
 
 def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=None, do_trim=True, max_batch=256, defer=False,
-                      momentum=None, packed=False, want_specs=False, codebook=None, want_idx=False):
+                      momentum=None, packed=False, want_specs=False, codebook=None, want_idx=False, overlap=0):
     """Speech from units: what resynth_batch does behind its encoder, from the units alone.  units: a list of [U_i, E] arrays of
     0 / 1 as encode_batch returns them (what read_units parses from a --test_encode file); packed=True: a list of uint8
     [U_i, (E + 7) // 8] arrays (pack_units, encode_batch(packed=True)).  speakers: the target id of each.
@@ -1262,7 +1424,11 @@ def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=N
     (check_gen_targets).
     codebook: a zs_amd.codebook.Codebook -- the one device buffer is snapped once, in place, before the first chunk, so every
     fragment is decoded from snapped units; want_idx=True appends (codeword indices int32 [U_i] per utterance, summed Hamming
-    distance of the snap) to the result."""
+    distance of the snap) to the result.
+    overlap (frames, like seg_len; check_overlap_value): the utterance is decoded in the windows of unit_windows, which share
+    overlap // 8 units, and the frames two windows share are cross-faded (zs_xfade_gather, on the normalised rows) instead of cut:
+    the spectrogram no longer jumps where a piece ends.  The units are the same; an utterance of at most 2 (seg_len // 8) units is
+    one window and is spoken exactly as with overlap 0, which is today's path launch for launch."""
     momentum = gl_momentum(momentum)
     if want_idx and codebook is None:
         raise ValueError('synth_units_batch: want_idx needs a codebook')
@@ -1282,30 +1448,34 @@ def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=N
             idx_h, total_h = _snap_units(codebook, packed_dev, dev, to_host=want_idx)
         return (lambda tab, B, T0, ch, lens_p: dec.forward_units(packed_dev, tab[0], tab[1], B, T0, ch, lengths=lens_p)), idx_h, total_h
     return _synth_batch('synth_units_batch', units, check_rows, operand, trainer, seg_len, speakers, enc_only, n_iter, do_trim, max_batch,
-                        defer, momentum, want_specs)
+                        defer, momentum, want_specs, overlap=overlap)
 
 
 def _synth_batch(who, units, check_rows, operand, trainer, seg_len, speakers, enc_only, n_iter, do_trim, max_batch, defer, momentum,
-                 want_specs):
+                 want_specs, overlap=0):
     """The one driver of synth_units_batch and synth_index_batch.  check_rows() -> the utterances as host arrays of one dtype and
     row shape (ValueError for what cannot be spoken); they go to the device once, in one pinned buffer and one copy, and
     unit_fragments cuts each into the row ranges the Decoder runs on.  operand(buffer, dev) -> (the function _enqueue_synth builds a
     chunk's Decoder operand with, and the pinned codeword indices and summed distance of a snap, or None, None)."""
     if len(speakers) != len(units) or not len(units):
         raise ValueError('%s: %d target speakers for %d utterances' % (who, len(speakers), len(units)))
+    overlap = check_overlap_value(overlap, seg_len)
     rows = check_rows()
     _check_speaker_range(speakers, int(trainer.Decoder.c_a))
     shift = 0 if enc_only else check_gen_targets(trainer, speakers)
     trainer.set_eval()
     dev = trainer.device
-    items = [it for u, r in enumerate(rows) for it in _unit_items(u, len(r), seg_len)]
+    if overlap:                                               # windows that share units (unit_windows); the units are the same
+        items = [it for u, r in enumerate(rows) for it in _window_items(u, len(r), seg_len, overlap)]
+    else:
+        items = [it for u, r in enumerate(rows) for it in _unit_items(u, len(r), seg_len)]
     chunks = _split_chunks(items, int(seg_len) // 8, max_batch)
     uoffs = np.concatenate(([0], np.cumsum([len(r) for r in rows]))).astype(np.int64)
     host = torch.empty((int(uoffs[-1]),) + rows[0].shape[1:], dtype=torch.from_numpy(rows[0]).dtype, pin_memory=True)
     np.concatenate(rows, axis=0, out=host.numpy())
     chunk_operand, idx_h, total_h = operand(host.to(dev, non_blocking=True), dev)     # the one H2D copy of the batch
     fin, spec_h, ulens = _enqueue_synth(trainer, seg_len, chunks, uoffs, speakers, enc_only, shift, n_iter, do_trim, momentum, want_specs,
-                                        chunk_operand)
+                                        chunk_operand, overlap=overlap)
 
     def finish():
         wavs = _wait_vocoder(fin, dev)
@@ -1315,17 +1485,64 @@ def _synth_batch(who, units, check_rows, operand, trainer, seg_len, speakers, en
     return finish if defer else finish()
 
 
-def _enqueue_synth(trainer, seg_len, chunks, uoffs, speakers, enc_only, shift, n_iter, do_trim, momentum, want_specs, operand):
+def _xfade_gather(src, chunks, first, n_utt, denorm, dev):
+    """The vocoder's padded input [n_utt, T_max, 513] fp32 of a batch decoded in overlapping windows, by ONE zs_xfade_gather over the
+    source table src (fp32 [rows, 513], contiguous): the plan of _xfade_tables goes to the device in one copy.  denorm: the rows are
+    written de-normalised (amplitudes).  Returns (t, frames per utterance)."""
+    Tm, ulens, i0, i1, w0, w1 = _xfade_tables(chunks, first, n_utt)
+    rows = n_utt * Tm
+    if rows >= 2 ** 31 or src.shape[0] >= 2 ** 31:
+        raise ValueError('overlapped batch too large: %d rows from %d' % (rows, src.shape[0]))
+    tab = torch.from_numpy(np.concatenate([i0, i1, w0.view(np.int32), w1.view(np.int32)])).to(dev, non_blocking=True)
+    i0_d, i1_d, w0_d, w1_d = torch.split(tab, rows)
+    t = torch.empty(n_utt, Tm, 513, dtype=torch.float32, device=dev)
+    L.call('zs_xfade_gather', 'ZsXfadeGather', torch.cuda.current_stream(dev).cuda_stream, src=L.ptr(src), src_rows=src.shape[0],
+           ld_src=src.stride(0), i0=L.ptr(i0_d), i1=L.ptr(i1_d), w0=L.ptr(w0_d), w1=L.ptr(w1_d), out=L.ptr(t), rows=rows, out_ld=513,
+           cols=513, denorm=int(denorm))
+    return t, ulens
+
+
+def _enqueue_synth(trainer, seg_len, chunks, uoffs, speakers, enc_only, shift, n_iter, do_trim, momentum, want_specs, operand, overlap=0):
     """The decode half and the vocoder of a batch of unit (or index) sequences, shared by synth_units_batch and synth_index_batch:
     operand(tab, B, T0, ch, lens_p) -> (bits, x_dec) builds and decodes one chunk's operand from its (start, len) device tables over
     the batch's one buffer.  Returns (the vocoder's finish function, the pinned copy of the spectrograms or None, frames per
-    utterance); nothing is waited for."""
+    utterance); nothing is waited for.
+    overlap > 0: the chunks hold the windows of _window_items, which share units, and ONE zs_xfade_gather builds the vocoder's input
+    from the decoded windows, cross-fading the frames two of them share (_xfade_gather) on the NORMALISED rows; the de-normalisation
+    is the gather's own, under the same want_specs rule.  enc_only: the decoded chunks laid end to end are the source table, as
+    _gather_decoded builds it.  With the generator, zs_gen_scatter writes each chunk's combined rows, not de-normalised, into a
+    staging buffer of _plan_scatter's layout in which an utterance's windows lie back to back (the shared rows twice), and the gather
+    reads that."""
     dev, n_utt = trainer.device, len(uoffs) - 1
     q = _Enqueued()
     q.n_utt, q.dev, q.chunks, q.dec_dev = n_utt, dev, [], []
     tabs = _upload_tables(*_unit_tables(chunks, uoffs), chunks, dev)
     denorm = not want_specs                               # the vocoder de-normalises (the same device function) when the rows are wanted
     gen_plan = None
+    if overlap:
+        flat = _flat(chunks)
+        if not enc_only:                                  # the staging buffer: [n_utt, rows of the longest utterance's windows, 513]
+            stage, _, dsts = _plan_scatter(chunks, n_utt, False, dev, rows_of=lambda n: 8 * n)
+            gen_plan = (stage, dsts, shift, False)
+            at, _ = _fragment_layout(flat, [8 * it.n for it in flat], n_utt)
+            first = [it.u * stage.shape[1] + s for it, s in zip(flat, at)]
+        for ci, (chunk, ragged) in enumerate(chunks):
+            lens = [it.n for it in chunk]
+            xd = _decode_chunk(trainer, ci, [it.u for it in chunk], (lens if ragged else None), speakers, enc_only, gen_plan,
+                               lambda ch, lens_p: operand(tabs[ci], len(chunk), max(lens), ch, lens_p))
+            q.dec_dev.append(xd)
+        if enc_only:
+            first, total = [], 0
+            for (chunk, _), x in zip(chunks, q.dec_dev):
+                first += [total + i * x.shape[1] for i in range(len(chunk))]
+                total += x.shape[0] * x.shape[1]
+            src = q.dec_dev[0].reshape(-1, 513) if len(q.dec_dev) == 1 else torch.cat([x.reshape(-1, 513) for x in q.dec_dev], dim=0)
+            src = src.float()
+        else:
+            src = stage.reshape(-1, 513)
+        t, ulens = _xfade_gather(src, chunks, first, n_utt, denorm, dev)
+        spec_h = _to_host(t) if want_specs else None
+        return _enqueue_vocoder(t, ulens, n_iter, do_trim, dev, amplitudes=denorm, momentum=momentum), spec_h, ulens
     if not enc_only:
         q.conv, q.ulens, dsts = _plan_scatter(chunks, n_utt, denorm, dev, rows_of=lambda n: 8 * n)
         gen_plan = (q.conv, dsts, shift, denorm)
@@ -1366,7 +1583,7 @@ def read_indices(path, K):
 
 
 def synth_index_batch(idx_lists, trainer, seg_len, speakers, codebook, enc_only=True, n_iter=None, do_trim=True, max_batch=256, defer=False,
-                      momentum=None, want_specs=False):
+                      momentum=None, want_specs=False, overlap=0):
     """Speech from codeword indices: synth_units_batch for enc_mode 'continues' under a vector codebook (zs_amd.vq.VectorCodebook).
     idx_lists: one integer sequence per utterance (what resynth_batch(want_idx=True) returns, what read_indices parses from an
     .idx.txt file).  Every index goes to the device once, in one int32 buffer; unit_fragments cuts each utterance as
@@ -1377,7 +1594,8 @@ def synth_index_batch(idx_lists, trainer, seg_len, speakers, codebook, enc_only=
     generator cannot take.
     Under a zs_amd.rvq.ResidualCodebook an utterance is integers [U_i, c], a row of c <= S indices per frame and the same c for the
     whole batch (what read_index_rows parses): the rows go to the device once, are transposed there into c planes, and zs_rvq_gather
-    (Decoder.forward_index_planes) writes each chunk's operand as the sum of the c stages' codewords.  The driver is the same."""
+    (Decoder.forward_index_planes) writes each chunk's operand as the sum of the c stages' codewords.  The driver is the same.
+    overlap: as synth_units_batch's -- overlapping decode windows over the same indices, cross-faded."""
     momentum = gl_momentum(momentum)
     planes = getattr(codebook, 'kind', None) == 'residual'    # a zs_amd.rvq.ResidualCodebook: [U_i, c] rows, c <= S the same for all
     if getattr(codebook, 'kind', None) != 'vector' and not planes:
@@ -1414,7 +1632,7 @@ def synth_index_batch(idx_lists, trainer, seg_len, speakers, codebook, enc_only=
                                                                             lengths=lens_p)), None, None
         return (lambda tab, B, T0, ch, lens_p: dec.forward_indices(idx_dev, code_d, tab[0], tab[1], B, T0, ch, bad, lengths=lens_p)), None, None
     return _synth_batch('synth_index_batch', idx_lists, check_rows, operand, trainer, seg_len, speakers, enc_only, n_iter, do_trim, max_batch,
-                        defer, momentum, want_specs)
+                        defer, momentum, want_specs, overlap=overlap)
 
 
 def out_rate():
@@ -1566,7 +1784,7 @@ def _wav_features(wavs, rates, dev, do_trim=True, strict=True):
 
 
 def convert_wavs(wavs, rates, trainer, seg_len, speakers, enc_only=True, n_iter=None, momentum=None, noise_fn=None, do_trim=True,
-                 defer=False, codebook=None):
+                 defer=False, codebook=None, overlap=0):
     """Waveforms in, converted waveforms out, as one enqueue: wavs is a list of 1-D float arrays at `rates` (None: hp.sr; one int,
     or one per wav), speakers the target id of each.  Inputs not at hp.sr are resampled on the device, zs_trim finds the trim
     bounds there, zs_pre_spectrogram reads the trimmed windows in place and resynth_batch runs on the device-resident
@@ -1574,9 +1792,13 @@ def convert_wavs(wavs, rates, trainer, seg_len, speakers, enc_only=True, n_iter=
     are those of preprocess.get_spectrograms_batch(wavs, sr=rates) followed by resynth_batch(specs, ...), bit for bit.
     Returns (encodings, wavs, info); info[i] = {'bounds': (start, stop) of the input's trim at hp.sr, 'frames'}.  do_trim is
     get_spectrograms' trim of the input and the vocoder's trim of the output together; defer, enc_only, n_iter, momentum and
-    noise_fn and codebook are resynth_batch's.  An input of fewer than 2 samples after trimming raises ValueError before the network
-    is enqueued."""
+    noise_fn, codebook and overlap are resynth_batch's.  An input of fewer than 2 samples after trimming raises ValueError before the
+    network is enqueued."""
     momentum = gl_momentum(momentum)
+    overlap = check_overlap_value(overlap, seg_len)
+    if overlap and codebook is None and trainer.enc_mode == 'continues':
+        raise ValueError("convert_wavs: overlap = %d needs units to speak from, and enc_mode 'continues' has none without a codebook"
+                         % overlap)
     if len(speakers) != len(wavs):
         raise ValueError('convert_wavs: %d target speakers for %d wavs' % (len(speakers), len(wavs)))
     if codebook is not None:
@@ -1585,7 +1807,7 @@ def convert_wavs(wavs, rates, trainer, seg_len, speakers, enc_only=True, n_iter=
         check_gen_targets(trainer, speakers)
     specs, info = _wav_features(wavs, rates, trainer.device, do_trim=do_trim)
     fin = resynth_batch(specs, trainer, seg_len, speakers, n_iter=n_iter, do_trim=do_trim, noise_fn=noise_fn, defer=True, enc_only=enc_only,
-                        momentum=momentum, codebook=codebook)
+                        momentum=momentum, codebook=codebook, **({'overlap': overlap} if overlap else {}))
 
     def finish():
         encs, out = fin()
@@ -1790,11 +2012,13 @@ def _scan_wavs(in_dir, skip):
     return files, durations
 
 
-def _write_manifest(path, in_dir, out_dir, t_speakers, enc_only, items, skipped, stats, voices, speaker2id):
+def _write_manifest(path, in_dir, out_dir, t_speakers, enc_only, items, skipped, stats, voices, speaker2id, overlap=None):
     """The manifest of a folder driver, written to `path` and returned: the run's fields, the driver's own `items`, what was
-    skipped, and 'codebook' / 'voices' when the run had them."""
+    skipped, and 'codebook' / 'voices' / 'overlap' when the run had them."""
     manifest = {'in_dir': in_dir, 'out_dir': out_dir, 'targets': t_speakers, 'sr': out_rate(), 'enc_only': bool(enc_only),
                 'items': items, 'skipped': skipped}
+    if overlap is not None:
+        manifest['overlap'] = int(overlap)
     if stats is not None:
         manifest['codebook'] = stats.manifest()
     if voices:
@@ -1805,7 +2029,7 @@ def _write_manifest(path, in_dir, out_dir, t_speakers, enc_only, items, skipped,
 
 
 def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None,
-                voices=None, codebook=None, codebook_file=None):
+                voices=None, codebook=None, codebook_file=None, overlap=None):
     """Every *.wav of in_dir (any PCM / float format, any rate, channels averaged: preprocess.read_wav) to every target speaker of
     t_speakers, on the device from the samples to the waveform: {out_dir}/{target}/{stem}.wav (PCM16 at out_rate()) and .txt (the
     units), plus the manifest {out_dir}/convert_dir.json, which is returned.
@@ -1821,10 +2045,18 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
     entropy_bits_per_unit, mean_distance} over the units written.  A zs_amd.vq.VectorCodebook for enc_mode 'continues': the same
     outputs, the .idx.txt being the unit file (the .txt holds what write_encodings writes for real-valued rows).  A
     zs_amd.rvq.ResidualCodebook: the .idx.txt holds one line of s' indices per frame (write_index_rows), s' the stages the codebook
-    was told to use (with_stages; default all), and the manifest's 'codebook' entry gains 'S' and per-stage figures under 'stages'."""
+    was told to use (with_stages; default all), and the manifest's 'codebook' entry gains 'S' and per-stage figures under 'stages'.
+    overlap (frames; None: not asked for): resynth_batch's -- the units written are the same, the wavs are spoken from them in
+    overlapping, cross-faded decode windows -- and the manifest gains 'overlap'.  A file of fewer than MIN_LEN frames, whose one unit
+    cannot be spoken, is then skipped with a reason; enc_mode 'continues' needs a codebook (ValueError before anything is read)."""
     from concurrent.futures import ThreadPoolExecutor
     from .preprocess import read_wav
     momentum = gl_momentum(momentum)
+    if overlap is not None:
+        overlap = check_overlap_value(overlap, seg_len)
+        if overlap and codebook is None and trainer.enc_mode == 'continues':
+            raise ValueError("convert_dir: overlap = %d needs units to speak from, and enc_mode 'continues' has none without a codebook"
+                             % overlap)
     stats = _codebook_stats(codebook, trainer, codebook_file)
     side = codebook.units() if codebook is not None else None    # how this kind of codebook writes an utterance's indices
     t_speakers = list(t_speakers)
@@ -1887,6 +2119,9 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
                     if spec is None:
                         skip(p, 'utterance too short after trimming')
                         feats[p] = None
+                    elif overlap and _unit_counts([spec], seg_len)[0] < 2:
+                        skip(p, '%d frames give fewer than 2 units: nothing to speak from with overlap' % inf['frames'])
+                        feats[p] = None
                     else:
                         feats[p] = (spec, data[p][1], len(data[p][0]), inf)
             live = [it for it in group if feats[it['file']] is not None]
@@ -1897,7 +2132,7 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
             if live:
                 fin = resynth_batch([feats[it['file']][0] for it in live], trainer, seg_len, [speaker2id[it['target']] for it in live],
                                     n_iter=n_iter, defer=True, enc_only=enc_only, momentum=momentum, codebook=codebook,
-                                    want_idx=codebook is not None)
+                                    want_idx=codebook is not None, **({'overlap': overlap} if overlap else {}))
             later = {it['file'] for g in groups[gi + 1:gi + 2] for it in g}
             for p in [p for p in feats if p not in later]:    # a file's items are adjacent: done with, drop its device rows
                 del feats[p]
@@ -1907,7 +2142,7 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
     items = [{'input': it['file'], 'rate': it['rate'], 'samples': it['samples'], 'target': it['target'], 'bounds': it['bounds'],
               'frames': it['frames'], 'wav': it['wav'], 'txt': it['txt']} for it in done]
     return _write_manifest(os.path.join(out_dir, 'convert_dir.json'), in_dir, out_dir, t_speakers, enc_only, items, skipped, stats,
-                           voices, speaker2id)
+                           voices, speaker2id, overlap=overlap)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1933,7 +2168,7 @@ def synth_dir_plan(files, n_units, targets, out_dir, batch=64, max_batch_units=6
 
 
 def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None, voices=None,
-              codebook=None, codebook_file=None):
+              codebook=None, codebook_file=None, overlap=None):
     """Every *.txt of in_dir -- unit files as write_encodings writes them (--test_encode, --test, --convert_dir, encode_batch), one
     line of 0 / 1 per unit -- spoken in the voice of every target speaker of t_speakers: {out_dir}/{target}/{stem}.wav (PCM16 at
     out_rate()), plus the manifest {out_dir}/synth_dir.json, which is returned.
@@ -1946,8 +2181,12 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
     each wav: {stem}.txt (the snapped units) and {stem}.idx.txt (one codeword index per line); the manifest gains 'codebook'.
     A zs_amd.vq.VectorCodebook (enc_mode 'continues', refused without one): the *.idx.txt of in_dir are read instead (read_indices:
     one integer in [0, K) per line), <name>.idx.txt is spoken as {stem}.wav through synth_index_batch, and the indices spoken are
-    written beside each wav as {stem}.idx.txt."""
+    written beside each wav as {stem}.idx.txt.
+    overlap (frames; None: not asked for): synth_units_batch's / synth_index_batch's -- overlapping, cross-faded decode windows --
+    and the manifest gains 'overlap', each item's 'fragments' holding the lengths of its windows."""
     momentum = gl_momentum(momentum)
+    if overlap is not None:
+        overlap = check_overlap_value(overlap, seg_len)
     t_speakers = list(t_speakers)
     speaker2id = _target_table('synth_dir', trainer, speaker2id_path, voices, t_speakers, enc_only)
     side = codebook.units() if codebook is not None else _BitUnits(None)      # which files are read, and how they are spoken and written
@@ -1990,13 +2229,16 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
 
     def enqueue(group):
         return group, side.speak([units[it['file']] for it in group], trainer, seg_len, [speaker2id[it['target']] for it in group],
-                                 enc_only=enc_only, n_iter=n_iter, defer=True, momentum=momentum)
+                                 enc_only=enc_only, n_iter=n_iter, defer=True, momentum=momentum, **({'overlap': overlap} if overlap else {}))
+
+    def pieces(n):                                            # the lengths, in units, of what an utterance of n units is decoded in
+        return [b - a for a, b in unit_windows(n, seg_len, overlap)] if overlap else unit_fragments(n, seg_len)
 
     _run_deferred(groups, enqueue, write)
-    items = [{'input': it['file'], 'units': it['units'], 'fragments': unit_fragments(it['units'], seg_len), 'target': it['target'],
+    items = [{'input': it['file'], 'units': it['units'], 'fragments': pieces(it['units']), 'target': it['target'],
               'wav': it['wav']} for it in done]
     return _write_manifest(os.path.join(out_dir, 'synth_dir.json'), in_dir, out_dir, t_speakers, enc_only, items, skipped, stats, voices,
-                           speaker2id)
+                           speaker2id, overlap=overlap)
 
 
 SINGLE_FILES = {            # convert.py:308-317: the utterances --test_single knows per source speaker

@@ -7,6 +7,7 @@
 // output, twiddle table of 512 entries built once per workgroup with sincospif).  The spectrogram of an
 // utterance (4.1 KB/frame) stays in L2/Infinity Cache across the 300 iterations: FFT/latency-bound.
 #include "zs_common.h"
+#include "zs_denorm.h"
 
 namespace {
 
@@ -177,13 +178,8 @@ __global__ void pre_mel_kernel(const float* amp, const float* basis, float* mel,
   }
 }
 
-// normalised magnitude -> amplitude (convert.py:56-58).  The one place this expression is compiled: gl_denorm_kernel and
-// gen_scatter_kernel both call it, so both produce the same bits for the same input.
-__device__ __forceinline__ float gl_denorm(float x) {
-  const float m = fminf(fmaxf(x, 0.f), 1.f) * 100.f - 100.f + 20.f;         // convert.py:57
-  return powf(10.0f, m * 0.05f);                                             // convert.py:58
-}
-
+// normalised magnitude -> amplitude (convert.py:56-58): gl_denorm of zs_denorm.h, the one place this expression is written.
+// gl_denorm_kernel and gen_scatter_kernel both call it, so both produce the same bits for the same input.
 __global__ void gl_denorm_kernel(const float* in, float* out, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     out[i] = gl_denorm(in[i]);
