@@ -124,6 +124,17 @@ two modes, before anything is built:
   python main.py --synth_dir units/ --t_speaker V001 --ckpt_pth CKPT --overlap 32
   python main.py --convert_dir in/ --t_speaker V001,V002 --ckpt_pth CKPT --overlap 32
 
+--segment LAMBDA with --convert_dir or --test_encode and --codebook (zs_amd.segment): the index sequence of every utterance is chosen
+at once -- the sum of the frames' scores plus LAMBDA for every change of codeword is minimised exactly, on the GPU (zs_seg_viterbi)
+-- instead of frame by frame, so a frame between two codewords no longer flips the symbol.  LAMBDA >= 0 is in the score's own units,
+squared Euclidean distance under a vector codebook and Hamming bits under a bit codebook (the run prints which); 0 gives the files
+written without the flag.  <name>.txt and <name>.idx.txt stay one line per frame, <name>.seg.txt beside them holds one line
+`codeword duration` per run, and the manifest gains "segment" (segments, mean run, entropy and bits per second).  --synth_dir
+--segments reads the *.seg.txt of its folder instead of the per-frame files and speaks <name>.seg.txt as <name>.wav.  A residual
+codebook, K > 4096 and every other mode are refused before anything is built:
+  python main.py --convert_dir in/ --t_speaker V001 --ckpt_pth CKPT --codebook ckpt_english/codebooks/K64.codebook.npz --segment 4
+  python main.py --synth_dir out/convert/V001 --t_speaker V002 --ckpt_pth CKPT --codebook ckpt_english/codebooks/K64.codebook.npz --segments
+
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
 (--train_al, --train_t, --encode, --test_asr) are not part of this build and exit with a clear error.
@@ -333,6 +344,12 @@ def build_parser():
     p.add_argument('--overlap', type=int, default=None, metavar='FRAMES',
                    help='with --synth_dir / --convert_dir: decode in windows that share FRAMES spectrogram frames and cross-fade them '
                         '(0, or a multiple of 8 up to 8 * ((seg_len // 8) // 2)); the units do not change; default: pieces laid end to end')
+    p.add_argument('--segment', type=float, default=None, metavar='LAMBDA',
+                   help='with --convert_dir / --test_encode and --codebook: choose the codeword sequence of every utterance at once, '
+                        "LAMBDA >= 0 per change of codeword in the score's own units (squared Euclidean distance or Hamming bits); "
+                        'writes <name>.seg.txt beside the per-frame unit files; default: every frame alone')
+    p.add_argument('--segments', action='store_true',
+                   help='with --synth_dir and --codebook: read the *.seg.txt run files of the folder instead of its per-frame unit files')
     p.add_argument('--out_sr', type=_out_sr, default=None,
                    help='sample rate of the wavs --test / --cross_test / --test_single write (hp.out_sr); default: 16000')
     return p
@@ -529,6 +546,47 @@ def check_overlap(args, seg_len=None, enc_mode=None):
         raise ValueError("--overlap with --convert_dir speaks the units it writes: enc_mode 'continues' has none without --codebook")
 
 
+SEGMENT_MODES = ('convert_dir', 'test_encode')
+NOT_SEGMENT_MODES = ('synth_dir', 'test', 'cross_test', 'test_single', 'test_classify', 'fit_codebook', 'adapt_voice', 'preprocess')
+
+
+def _residual_file(path):
+    """Whether the codebook file holds a residual codebook, by its fields (a file that cannot be read is reported where it is loaded)."""
+    from zs_amd.codebook import read_npz
+    try:
+        d = read_npz(path)
+    except ValueError:
+        return False
+    return 'kind' in d and d['kind'].shape == () and str(d['kind']) == 'residual'
+
+
+def check_segment(args, enc_mode=None):
+    """--segment and --segments are refused, before anything is built, where they cannot do what they say: --segment without
+    --convert_dir or --test_encode, beside any other mode, without --codebook, with --rvq_stages or a value that is no finite number
+    >= 0; --segments without --synth_dir or --codebook, or beside --segment; and either with a residual codebook (by the file's
+    name, and by its fields once hps is read: argument_runner calls this again)."""
+    lam, runs_in = getattr(args, 'segment', None), getattr(args, 'segments', False)
+    if lam is None and not runs_in:
+        return
+    flag = '--segment' if lam is not None else '--segments'
+    if lam is not None:
+        from zs_amd.segment import check_lambda
+        check_lambda(lam, '--segment')
+        if runs_in:
+            raise ValueError('--segment writes run files and --segments reads them: run them as two commands')
+        if not (args.convert_dir is not None or args.test_encode):
+            raise ValueError('--segment needs --convert_dir or --test_encode: it chooses the units they write')
+        other = [m for m in NOT_SEGMENT_MODES + tuple(TRAIN_MODES) if getattr(args, m, None) not in (None, False)]
+        if other:
+            raise ValueError('--segment serves --convert_dir and --test_encode alone: it cannot be combined with --%s' % other[0])
+    elif args.synth_dir is None:
+        raise ValueError('--segments needs --synth_dir: it makes it read the *.seg.txt run files of its folder')
+    if getattr(args, 'codebook', None) is None:
+        raise ValueError('%s needs --codebook FILE: the runs are sequences of its codewords' % flag)
+    if getattr(args, 'rvq_stages', None) is not None or args.codebook.endswith('.rvq.npz') or (enc_mode is not None and _residual_file(args.codebook)):
+        raise ValueError('%s does not segment the stages of a residual codebook: use a bit or a vector codebook' % flag)
+
+
 def convert_targets(args):
     """--convert_dir and --synth_dir take --t_speaker as a comma-separated list of distinct names (--test_single keeps the single name): the
     list, refused before anything is built when it names no speaker or one twice."""
@@ -554,6 +612,7 @@ def argument_runner(argv=None):
     check_rvq_train(args)
     check_rvq(args)
     check_overlap(args)
+    check_segment(args)
     args.t_speakers =convert_targets(args) if (args.convert_dir is not None or args.synth_dir is not None) else None
     if args.dataset == 'surprise':            # main.py:83-88: english -> surprise in every default path
         for action in parser._actions:
@@ -579,6 +638,7 @@ def argument_runner(argv=None):
         args.vq_codebook = check_rvq_train(args, args.enc_mode, hps.enc_size)
     check_rvq(args, args.enc_mode)            # again, now that enc_mode is known (a residual codebook's fields are read here)
     check_overlap(args, hps.seg_len, args.enc_mode)      # again, now that seg_len and enc_mode are known
+    check_segment(args, args.enc_mode)        # again: a residual codebook is told by its fields
     print('[Runner] - Generation mode: ', 'autoencoder only' if args.enc_only else 'with generator')
     print('[Runner] - Generator mode: ', args.g_mode)
     print('[Runner] - Encoder mode: ', args.enc_mode)
@@ -722,6 +782,11 @@ def main(argv=None):
             cb = load_codebook(args.codebook, trainer.enc_mode, E=int(trainer.Decoder.c_in))
             if args.rvq_stages is not None:               # (check_rvq has seen that the file is a residual codebook of that many stages)
                 cb = cb.with_stages(args.rvq_stages)
+            if args.segment is not None or args.segments:     # K > ZS_SEG_MAX_K: refused before anything is enqueued
+                from zs_amd import segment as sg
+                sg.check_codebook(cb)
+                if args.segment is not None:
+                    print('[Runner] - Segmenting: lambda = %g per change of codeword, in %s' % (args.segment, sg.unit_name(cb)))
         voices = None
         if args.voice:                                    # --voice NAME=FILE: rows appended to the Decoder's tables (zs_amd.voice)
             from zs_amd.voice import add_voices
@@ -733,17 +798,19 @@ def main(argv=None):
         if args.test_single:                              # main.py:190-191
             test_single(trainer, hps.seg_len, args.speaker2id_path, args.result_dir, args.enc_only, args.s_speaker, args.t_speaker)
         if args.test_encode:
-            test_encode(trainer, hps.seg_len, args.test_path, args.dataset_path, result_dir, flag='test', codebook=cb)
+            test_encode(trainer, hps.seg_len, args.test_path, args.dataset_path, result_dir, flag='test', codebook=cb,
+                        **({'segment': args.segment} if args.segment is not None else {}))
         if args.test_classify:                            # main.py:196-199
             target_classify(trainer, hps.seg_len, args.synthesis_list, result_dir, flag='test')
         if args.convert_dir is not None:                  # not in the reference: a folder of sound files to the target voices
             convert_dir(trainer, hps.seg_len, args.convert_dir, args.speaker2id_path, os.path.join(result_dir, 'convert'), args.t_speakers,
                         args.enc_only, voices=voices, codebook=cb, codebook_file=args.codebook,
-                        **({'overlap': args.overlap} if args.overlap is not None else {}))
+                        **({'overlap': args.overlap} if args.overlap is not None else {}),
+                        **({'segment': args.segment} if args.segment is not None else {}))
         if args.synth_dir is not None:                    # not in the reference: a folder of unit files spoken by the target voices
             synth_dir(trainer, hps.seg_len, args.synth_dir, args.speaker2id_path, os.path.join(result_dir, 'synth'), args.t_speakers,
                       args.enc_only, voices=voices, codebook=cb, codebook_file=args.codebook,
-                      **({'overlap': args.overlap} if args.overlap is not None else {}))
+                      **({'overlap': args.overlap} if args.overlap is not None else {}), **({'segments': True} if args.segments else {}))
 
 
 if __name__ == '__main__':

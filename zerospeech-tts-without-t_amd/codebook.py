@@ -44,6 +44,16 @@ def _check_rows(t, E, what):
         raise ValueError('%s must be a contiguous uint8 device tensor [n, >= %d] for E = %d' % (what, row_bytes(E), E))
 
 
+def _check_scores(out, n, K):
+    if not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != n or out.shape[1] < K \
+            or (out.shape[1] > 1 and out.stride(1) != 1) or (n > 1 and out.stride(0) < out.shape[1]):
+        raise ValueError('scores must be an fp32 device tensor [%d, >= %d] with unit column stride' % (n, K))
+
+
+def _scores_ld(out, K):
+    return int(out.stride(0)) if out.shape[0] > 1 else max(int(out.shape[1]), int(K))
+
+
 def assign(units, code, E, idx=None, dist=None, snapped=None, total=None):
     """zs_code_assign on the current stream.  units uint8 [n, row_bytes], code uint8 [K, code_bytes] (device); every output optional:
     idx / dist int32 [n], snapped uint8 like units (may be units itself), total int64 [1] (added to)."""
@@ -303,6 +313,18 @@ class Codebook(CodebookFile):
         snapped = units_dev.clone()                                # the bytes of a pitch behind the columns come along
         assign(units_dev, self.to(units_dev.device), self.E, idx=idx, snapped=snapped)
         return idx, snapped
+
+    def scores_(self, rows, out):
+        """out[i][k] = the Hamming distance of packed unit i and codeword k over the columns < E, exact in fp32 (one zs_code_scores on
+        the current stream, no synchronisation).  rows uint8 [n, row_bytes] and out fp32 [n, >= K] on the device; the columns of out
+        at or beyond K are not written.  What --segment chooses its paths from (zs_amd.segment)."""
+        from .segment import check_codebook
+        check_codebook(self)
+        _check_rows(rows, self.E, 'rows')
+        code = self.to(rows.device)
+        _check_scores(out, rows.shape[0], self.K)
+        L.call('zs_code_scores', 'ZsCodeScores', _stream(rows.device), units=L.ptr(rows), n=rows.shape[0], row_bytes=rows.shape[1],
+               code=L.ptr(code), K=self.K, code_bytes=code.shape[1], E=self.E, scores=L.ptr(out), ld_s=_scores_ld(out, self.K))
 
     def snap_host(self, packed):
         """Host rows uint8 [n, (E + 7) // 8] -> (idx int32 [n], snapped) as numpy arrays (one round trip through the device)."""

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import segment as sg
 from .hps import Hps, hp
 
 MIN_LEN = 9
@@ -491,7 +492,7 @@ class _Enqueued(object):
     nothing for is None.  With the generator (enc_only=False), `conv` holds the converted spectrograms [n_utt, T_max, 513] fp32 on
     the device (amplitudes when de-normalised) and `ulens` their frames."""
     __slots__ = ('n_utt', 'chunks', 'enc_host', 'dec_dev', 'dec_host', 'enc_done', 'dev', 'conv', 'ulens', 'units_host', 'uoffs',
-                 'units_dev', 'idx_host', 'cb_total', 'cb', 'enc_dev')
+                 'units_dev', 'idx_host', 'cb_total', 'cb', 'enc_dev', 'seg_scores', 'seg_row')
 
     def __init__(self):
         for slot in self.__slots__:
@@ -778,6 +779,7 @@ class _Units(object):
     drivers read, speak and write.  _BitUnits, _VectorUnits and _ResidualUnits answer the same calls."""
 
     keep_units = False                            # finish leaves the utterance-ordered device buffer of the units in q.units_dev
+    segment = None                                # lambda of --segment: finish chooses the batch's paths (zs_amd.segment), not its argmins
 
     def __init__(self, codebook):
         self.cb = codebook
@@ -793,6 +795,13 @@ class _Units(object):
         """An utterance's codeword indices as the .idx.txt beside its unit file."""
         write_indices(path, idx)
 
+    def path_indices(self, rows_dev, segment):
+        """The indices int32 (host) of the path --segment chooses for ONE utterance whose rows, in the form this kind's scores_ reads,
+        are on the device."""
+        scores = torch.empty(rows_dev.shape[0], self.cb.K, dtype=torch.float32, device=rows_dev.device)
+        self.cb.scores_(rows_dev, scores)
+        return sg.viterbi(scores, np.asarray([0, rows_dev.shape[0]]), segment)[0].cpu().numpy()
+
 
 class _BitUnits(_Units):
     """Under a bit codebook (zs_amd.codebook.Codebook).  codebook None: plain unit files, which synth_dir reads and speaks as it does
@@ -804,6 +813,8 @@ class _BitUnits(_Units):
         """Before the chunk loop: the chunk-local tables the Decoder's operands are packed by."""
         self.want_packed = want_packed
         self.dense = _upload_tables(*_dense_tables(chunks), chunks, q.dev) if decoding else None
+        if self.segment is not None:
+            sg.check_budget(int(q.uoffs[-1]), self.cb.K)
 
     def operand(self, ci, chunk, Tm, enc, act, dec, dev):
         """Behind the encoder's launches of chunk ci: the chunk's units -> chunk-local packed rows -> zs_code_assign in place.
@@ -820,7 +831,19 @@ class _BitUnits(_Units):
         return lambda ch, lens_p: dec.forward_units(snapped, st_c, ln_c, len(chunk), Tp, ch, lengths=lens_p)
 
     def finish(self, q, units_dev):
-        """Behind the last chunk: the utterance buffer snapped once, in place (the same rows, the same codewords)."""
+        """Behind the last chunk: the utterance buffer snapped once, in place (the same rows, the same codewords).
+        segment: zs_code_scores over that buffer, ONE zs_seg_viterbi over the batch, and the rows become the codewords of the path;
+        q.cb_total is the summed distance of the path."""
+        if self.segment is not None:
+            scores = torch.empty(units_dev.shape[0], self.cb.K, dtype=torch.float32, device=q.dev)
+            self.cb.scores_(units_dev, scores)
+            idx, _, _ = sg.viterbi(scores, q.uoffs, self.segment)
+            at = idx.long()
+            units_dev.copy_(self.cb.to(q.dev)[at])
+            q.idx_host = _to_host(idx)
+            q.cb_total = _to_host(scores.gather(1, at[:, None]).sum(dtype=torch.float64).to(torch.int64).reshape(1))
+            q.seg_scores, q.seg_row = scores, None
+            return
         q.idx_host, q.cb_total = _snap_units(self.cb, units_dev, q.dev, to_host=True)
 
     def encodings(self, q, u):
@@ -847,8 +870,19 @@ class _BitUnits(_Units):
         write_encodings(base + '.txt', unpack_units(self.cb.packed[idx], E))
         write_indices(base + '.idx.txt', idx)
 
-    def write_encoded(self, txt, units, dev):
-        """--test_encode: the snapped units as the .txt, their indices beside it."""
+    def from_indices(self, idx):
+        """What speak() takes for an utterance of these codeword indices: the packed codewords."""
+        return self.cb.packed[np.asarray(idx, dtype=np.int64)]
+
+    def write_encoded(self, txt, units, dev, segment=None):
+        """--test_encode: the snapped units as the .txt, their indices beside it.  segment: the codewords and indices of the path, and
+        its runs as the .seg.txt."""
+        if segment is not None:
+            idx = self.path_indices(torch.from_numpy(pack_units(units)).to(dev), segment)
+            write_encodings(txt, unpack_units(self.cb.packed[idx], self.cb.E))
+            write_indices(idx_path(txt), idx)
+            sg.write_segments(sg.seg_path(txt), sg.runs(idx))
+            return
         idx, snapped = self.cb.snap_host(pack_units(units))
         write_encodings(txt, unpack_units(snapped, self.cb.E))
         write_indices(idx_path(txt), idx)
@@ -869,15 +903,29 @@ class _VectorUnits(_Units):
         self.bad = torch.zeros(1, dtype=torch.int32, device=q.dev)
         q.uoffs, src = _vq_index_map(chunks, q.n_utt)
         self.src = torch.from_numpy(src).to(q.dev, non_blocking=True)
+        if self.segment is not None:                          # the scores of every chunk row, in chunk order (what _vq_index_map indexes)
+            rows = sum(len(chunk) * _t8(max(it.n for it in chunk)) for chunk, _ in chunks)
+            sg.check_budget(rows, self.cb.K)
+            self.scores = torch.empty(rows, self.cb.K, dtype=torch.float32, device=q.dev)
+            self.base, self.xn = 0, []
 
     def operand(self, ci, chunk, Tm, enc, act, dec, dev):
         """Behind the encoder's launches of chunk ci: zs_vq_assign over the chunk's rows, read in place from the engine's output.
-        Returns rows(ch, lens_p) for _decode_chunk: zs_vq_gather builds the Decoder's operand from the chunk's own indices."""
-        from .vq import launch_assign
+        Returns rows(ch, lens_p) for _decode_chunk: zs_vq_gather builds the Decoder's operand from the chunk's own indices.
+        segment: zs_vq_scores in its place, into the chunk's rows of the batch's score buffer (and the rows' squared norms, for the
+        distance of the path); nothing is decoded."""
+        from .vq import launch_assign, launch_scores
         bits = enc._last_bits
         Tp = int(bits.T)
         if Tp != _t8(Tm) or int(bits.B) != len(chunk):
             raise L.ZsError('conversion chunk %d: %d x %d encoded frames where the plan has %d x %d' % (ci, bits.B, Tp, len(chunk), _t8(Tm)))
+        if self.segment is not None:
+            n, K = len(chunk) * Tp, self.cb.K
+            launch_scores(torch.cuda.current_stream(dev).cuda_stream, enc._zs['ctx'].dt, bits.ptr(), n, bits.ld, self.code, self.cnorm,
+                          L.ptr(self.scores, self.base * K), K)
+            self.xn.append(bits.valid().float().pow(2).sum(-1).reshape(-1))
+            self.base += n
+            return None
         idx_c = torch.empty(len(chunk) * Tp, dtype=torch.int32, device=dev)
         dist_c = torch.empty(len(chunk) * Tp, dtype=torch.float32, device=dev)
         launch_assign(torch.cuda.current_stream(dev).cuda_stream, enc._zs['ctx'].dt, bits.ptr(), len(chunk) * Tp, bits.ld, self.code,
@@ -890,7 +938,20 @@ class _VectorUnits(_Units):
         return lambda ch, lens_p: dec.forward_indices(idx_c, self.code, st_c, ln_c, len(chunk), Tp, ch, self.bad, lengths=lens_p)
 
     def finish(self, q, units_dev):
-        """Behind the last chunk: the chunks' indices into utterance order, then one copy.  The batch's device buffers go with it."""
+        """Behind the last chunk: the chunks' indices into utterance order, then one copy.  The batch's device buffers go with it.
+        segment: ONE zs_seg_viterbi over the batch's score buffer through the row table of _vq_index_map gives the indices, already
+        in utterance order; q.cb_total is the summed distance of the path, max(0, |x|^2 + score) per unit."""
+        if self.segment is not None:
+            idx, _, _ = sg.viterbi(self.scores, q.uoffs, self.segment, row=self.src)
+            q.idx_host = _to_host(idx)
+            if self.keep_units:
+                q.units_dev = idx
+            xn = torch.cat(self.xn) if len(self.xn) > 1 else self.xn[0]
+            path = self.scores[self.src, idx.long()]
+            q.cb_total = _to_host((xn[self.src] + path).clamp_(min=0).sum(dtype=torch.float64).reshape(1))
+            q.seg_scores, q.seg_row = self.scores, self.src
+            self.scores = self.xn = self.work = self.src = self.dense = None
+            return
         idx_all, dist_all = (torch.cat(self.idx), torch.cat(self.dist)) if len(self.idx) > 1 else (self.idx[0], self.dist[0])
         idx_utt = idx_all[self.src]
         q.idx_host = _to_host(idx_utt)
@@ -918,10 +979,20 @@ class _VectorUnits(_Units):
     def write_spoken(self, base, idx, E):
         write_indices(base + '.idx.txt', idx)
 
-    def write_encoded(self, txt, units, dev):
-        """--test_encode: the .txt as without a codebook, the nearest codeword of every encoded frame beside it."""
-        idx, _ = self.cb.snap(torch.from_numpy(np.ascontiguousarray(units, dtype=np.float32)).to(dev))
+    def from_indices(self, idx):
+        return np.asarray(idx, dtype=np.int32)
+
+    def write_encoded(self, txt, units, dev, segment=None):
+        """--test_encode: the .txt as without a codebook, the nearest codeword of every encoded frame beside it.  segment: the
+        indices of the path instead, and its runs as the .seg.txt."""
+        x = torch.from_numpy(np.ascontiguousarray(units, dtype=np.float32)).to(dev)
         write_encodings(txt, units)
+        if segment is not None:
+            idx = self.path_indices(x, segment)
+            write_indices(idx_path(txt), idx)
+            sg.write_segments(sg.seg_path(txt), sg.runs(idx))
+            return
+        idx, _ = self.cb.snap(x)
         write_indices(idx_path(txt), idx.cpu().numpy())
 
 
@@ -1030,7 +1101,7 @@ class _ResidualUnits(_VectorUnits):
 
 
 def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host, enc_only=True, denorm=False, pack=False,
-                    codebook=None, rows_on_device=False, keep_units=False):
+                    codebook=None, rows_on_device=False, keep_units=False, segment=None):
     """Fragment rule + every Encoder / Decoder launch of a batch of utterances, WITHOUT a host synchronisation: the caller decides
     what else to put on the stream (the vocoder) before it waits.
     enc_only=False (decode_speakers required): the stage-2 generator as well, and zs_gen_scatter writes every chunk's converted rows
@@ -1048,7 +1119,17 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
     squared distance of the returned units (q.cb_total, a double), and the encodings returned are the codewords of the indices.
     rows_on_device: the fp32 encodings stay on the device (q.enc_dev, one tensor per chunk) instead of being copied to the host.
     keep_units: under a vector or residual codebook the utterance-ordered device buffer of the indices, which the copy to the host is
-    made from, stays in q.units_dev (bit-packed units are there whenever they are packed), in the layout q.uoffs describes."""
+    made from, stays in q.units_dev (bit-packed units are there whenever they are packed), in the layout q.uoffs describes.
+    segment (lambda >= 0; needs a bit or vector codebook and no decode): the units of the batch are the codewords of the paths
+    zs_seg_viterbi chooses, one launch behind the last chunk, over the scores of the batch (zs_amd.segment): zs_vq_scores
+    per chunk where zs_vq_assign runs without it, or zs_code_scores over the utterance-ordered packed buffer.  q.seg_scores and
+    q.seg_row keep the score buffer and its row table (None: unit i is row i)."""
+    if segment is not None:
+        segment = sg.check_lambda(segment, 'segment')
+        sg.check_codebook(codebook, 'segment')
+        if decode_speakers is not None:
+            raise ValueError('segment: the paths are chosen behind the last chunk, so nothing is decoded beside the encoder: '
+                             'resynth_batch(segment=...) speaks the units of the paths')
     side = None                                               # what the codebook's kind does to this batch (_BitUnits, _VectorUnits)
     if codebook is not None:
         _check_codebook(codebook, trainer)
@@ -1056,6 +1137,7 @@ def _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batc
             raise ValueError("codebook field E is %d, the Encoder's enc_size is %d" % (codebook.E, int(trainer.Encoder.enc_size)))
         side, want_packed = codebook.units(), pack
         side.keep_units = bool(keep_units)
+        side.segment = segment
         pack = pack or side.packs
     if pack and trainer.enc_mode == 'continues':
         raise ValueError("enc_mode 'continues' has no units to pack (its encodings are not 0 / 1)")
@@ -1211,7 +1293,7 @@ def encode_rows_on_device(specs, trainer, seg_len, noise_fn=None, max_batch=256)
 
 
 def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, max_batch=256, to_host=True, enc_only=True, packed=False,
-                 codebook=None, want_idx=False, units_on_device=False):
+                 codebook=None, want_idx=False, units_on_device=False, segment=None):
     """Batched encode()/convert() for many utterances: the same fragments the reference would send through the network one by
     one (convert.py:151-165), as a few large batches on the GPU.
     specs: list of [T_i, 513] arrays (host arrays, or torch tensors already on the device).  decode_speakers: optional list of
@@ -1229,13 +1311,16 @@ def encode_batch(specs, trainer, seg_len, decode_speakers=None, noise_fn=None, m
     codebook: a zs_amd.codebook.Codebook -- every unit is snapped to its nearest codeword before the Decoder and the generator see
     it and before it is returned (under the same truncation rules, in the form `packed` asks for); want_idx=True appends the list
     of codeword indices, int32 [U_i] per utterance, to the result.  For enc_mode 'continues' a zs_amd.vq.VectorCodebook: every encoded
-    frame is snapped to its nearest codeword in Euclidean distance and the encodings returned are those codewords, fp32 [U_i, E]."""
+    frame is snapped to its nearest codeword in Euclidean distance and the encodings returned are those codewords, fp32 [U_i, E].
+    segment (lambda >= 0, in the score's own units; needs a bit or vector codebook, and decode_speakers None): the units returned
+    are the codewords of the path zs_seg_viterbi chooses for the whole utterance (zs_amd.segment), not of each frame
+    alone; lambda = 0 gives the indices it gives without segment."""
     if want_idx and codebook is None:
         raise ValueError('encode_batch: want_idx needs a codebook')
     if units_on_device and not packed:
         raise ValueError('encode_batch: units_on_device needs packed=True')
     q = _enqueue_encode(specs, trainer, seg_len, decode_speakers, noise_fn, max_batch, dec_to_host=to_host, enc_only=enc_only,
-                        pack=packed, codebook=codebook)
+                        pack=packed, codebook=codebook, segment=segment)
     out = _encode_result(q, decode_speakers, to_host, enc_only, units_on_device)
     return out + (_unit_indices(q.idx_host, q.cb_total, q.uoffs)[0],) if want_idx else out
 
@@ -1257,7 +1342,7 @@ def _encode_result(q, decode_speakers, to_host, enc_only, units_on_device):
 
 
 def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, noise_fn=None, max_batch=256, defer=False, enc_only=True,
-                  momentum=None, codebook=None, want_idx=False, overlap=0):
+                  momentum=None, codebook=None, want_idx=False, overlap=0, segment=None):
     """test_encode + convert(enc_only) + spectrogram2wav for a batch of utterances as ONE enqueue (convert.py:151-165, 55-62):
     the fragments' Encoder / Decoder launches, the gather of the decoded fragments into the vocoder's padded [n, T_max, 513]
     input (one index kernel on the device), de-normalisation, the Griffin-Lim loop, de-emphasis, the trim statistics and the
@@ -1276,13 +1361,19 @@ def resynth_batch(specs, trainer, seg_len, speakers, n_iter=None, do_trim=True, 
     the units or indices it returns, as one enqueue -- the encoder runs without a decode, and the decode windows of unit_windows read
     the units where the encoder left them on the device.  The encodings returned are encode_batch's.  An input padded to MIN_LEN is
     spoken from the truncated units it returns, as --synth_dir would speak its file, so one of fewer than 2 units is refused, as is
-    enc_mode 'continues' without a codebook, which has nothing to speak from; both before anything is enqueued."""
+    enc_mode 'continues' without a codebook, which has nothing to speak from; both before anything is enqueued.
+    segment (lambda >= 0; encode_batch's): the same one enqueue at any overlap, 0 included -- the encoder runs without a decode,
+    zs_seg_viterbi chooses the batch's paths, and the units of the paths are spoken from the device buffer by the drivers of
+    synth_units_batch / synth_index_batch.  The indices and the summed distance returned are the path's."""
     momentum = gl_momentum(momentum)
     if want_idx and codebook is None:
         raise ValueError('resynth_batch: want_idx needs a codebook')
-    if check_overlap_value(overlap, seg_len):
+    if segment is not None:
+        segment = sg.check_lambda(segment, 'resynth_batch: segment')
+        sg.check_codebook(codebook, 'resynth_batch: segment')
+    if check_overlap_value(overlap, seg_len) or segment is not None:
         return _resynth_overlap(specs, trainer, seg_len, speakers, n_iter, do_trim, noise_fn, max_batch, defer, enc_only, momentum, codebook,
-                                want_idx, overlap)
+                                want_idx, overlap, segment)
     if not enc_only:
         q = _enqueue_encode(specs, trainer, seg_len, speakers, noise_fn, max_batch, dec_to_host=False, enc_only=False, denorm=True,
                             codebook=codebook)
@@ -1306,11 +1397,12 @@ def _unit_counts(specs, seg_len):
 
 
 def _resynth_overlap(specs, trainer, seg_len, speakers, n_iter, do_trim, noise_fn, max_batch, defer, enc_only, momentum, codebook, want_idx,
-                     overlap):
+                     overlap, segment=None):
     """resynth_batch with overlap > 0, as one enqueue: _enqueue_encode without a decode leaves the batch's units on the device in
     utterance order -- bit-packed (pack=True, snapped in place under a bit codebook), or the index buffer a vector or residual
     codebook's finish makes -- and _enqueue_synth decodes the windows of unit_windows over that buffer, whose layout (q.uoffs) is
-    the one _unit_tables expects."""
+    the one _unit_tables expects.  segment: the buffer holds the units of the chosen paths (_enqueue_encode), and overlap may be 0:
+    the windows are then the fragments of unit_fragments."""
     if len(speakers) != len(specs) or not len(specs):
         raise ValueError('resynth_batch: %d target speakers for %d utterances' % (len(speakers), len(specs)))
     if codebook is None and trainer.enc_mode == 'continues':
@@ -1328,7 +1420,7 @@ def _resynth_overlap(specs, trainer, seg_len, speakers, n_iter, do_trim, noise_f
     dec, dev = trainer.Decoder, trainer.device
     kind = getattr(codebook, 'kind', None)
     q = _enqueue_encode(specs, trainer, seg_len, None, noise_fn, max_batch, dec_to_host=False, pack=codebook is None, codebook=codebook,
-                        keep_units=True)                      # (a bit codebook packs by itself and returns the units unpacked)
+                        keep_units=True, segment=segment)     # (a bit codebook packs by itself and returns the units unpacked)
     if [int(n) for n in np.diff(q.uoffs)] != counts:
         raise L.ZsError('resynth_batch: the encoder left %s units where the plan has %s' % (np.diff(q.uoffs).tolist(), counts))
     units_dev = q.units_dev
@@ -1342,7 +1434,7 @@ def _resynth_overlap(specs, trainer, seg_len, speakers, n_iter, do_trim, noise_f
             operand = lambda tab, B, T0, ch, lens_p: dec.forward_indices(units_dev, code_d, tab[0], tab[1], B, T0, ch, bad, lengths=lens_p)
     else:
         operand = lambda tab, B, T0, ch, lens_p: dec.forward_units(units_dev, tab[0], tab[1], B, T0, ch, lengths=lens_p)
-    items = [it for u, n in enumerate(counts) for it in _window_items(u, n, seg_len, overlap)]
+    items = [it for u, n in enumerate(counts) for it in (_window_items(u, n, seg_len, overlap) if overlap else _unit_items(u, n, seg_len))]
     chunks = _split_chunks(items, int(seg_len) // 8, max_batch)
     fin, _, _ = _enqueue_synth(trainer, seg_len, chunks, q.uoffs, speakers, enc_only, shift, n_iter, do_trim, momentum, False, operand,
                                overlap=overlap)
@@ -1784,7 +1876,7 @@ def _wav_features(wavs, rates, dev, do_trim=True, strict=True):
 
 
 def convert_wavs(wavs, rates, trainer, seg_len, speakers, enc_only=True, n_iter=None, momentum=None, noise_fn=None, do_trim=True,
-                 defer=False, codebook=None, overlap=0):
+                 defer=False, codebook=None, overlap=0, segment=None):
     """Waveforms in, converted waveforms out, as one enqueue: wavs is a list of 1-D float arrays at `rates` (None: hp.sr; one int,
     or one per wav), speakers the target id of each.  Inputs not at hp.sr are resampled on the device, zs_trim finds the trim
     bounds there, zs_pre_spectrogram reads the trimmed windows in place and resynth_batch runs on the device-resident
@@ -1792,7 +1884,7 @@ def convert_wavs(wavs, rates, trainer, seg_len, speakers, enc_only=True, n_iter=
     are those of preprocess.get_spectrograms_batch(wavs, sr=rates) followed by resynth_batch(specs, ...), bit for bit.
     Returns (encodings, wavs, info); info[i] = {'bounds': (start, stop) of the input's trim at hp.sr, 'frames'}.  do_trim is
     get_spectrograms' trim of the input and the vocoder's trim of the output together; defer, enc_only, n_iter, momentum and
-    noise_fn, codebook and overlap are resynth_batch's.  An input of fewer than 2 samples after trimming raises ValueError before the
+    noise_fn, codebook, overlap and segment are resynth_batch's.  An input of fewer than 2 samples after trimming raises ValueError before the
     network is enqueued."""
     momentum = gl_momentum(momentum)
     overlap = check_overlap_value(overlap, seg_len)
@@ -1801,13 +1893,17 @@ def convert_wavs(wavs, rates, trainer, seg_len, speakers, enc_only=True, n_iter=
                          % overlap)
     if len(speakers) != len(wavs):
         raise ValueError('convert_wavs: %d target speakers for %d wavs' % (len(speakers), len(wavs)))
+    if segment is not None:
+        segment = sg.check_lambda(segment, 'convert_wavs: segment')
+        sg.check_codebook(codebook, 'convert_wavs: segment')
     if codebook is not None:
         _check_codebook(codebook, trainer)
     if not enc_only:
         check_gen_targets(trainer, speakers)
     specs, info = _wav_features(wavs, rates, trainer.device, do_trim=do_trim)
     fin = resynth_batch(specs, trainer, seg_len, speakers, n_iter=n_iter, do_trim=do_trim, noise_fn=noise_fn, defer=True, enc_only=enc_only,
-                        momentum=momentum, codebook=codebook, **({'overlap': overlap} if overlap else {}))
+                        momentum=momentum, codebook=codebook, **({'overlap': overlap} if overlap else {}),
+                        **({'segment': segment} if segment is not None else {}))
 
     def finish():
         encs, out = fin()
@@ -2012,9 +2108,9 @@ def _scan_wavs(in_dir, skip):
     return files, durations
 
 
-def _write_manifest(path, in_dir, out_dir, t_speakers, enc_only, items, skipped, stats, voices, speaker2id, overlap=None):
+def _write_manifest(path, in_dir, out_dir, t_speakers, enc_only, items, skipped, stats, voices, speaker2id, overlap=None, segment=None):
     """The manifest of a folder driver, written to `path` and returned: the run's fields, the driver's own `items`, what was
-    skipped, and 'codebook' / 'voices' / 'overlap' when the run had them."""
+    skipped, and 'codebook' / 'voices' / 'overlap' / 'segment' (a zs_amd.segment.SegmentStats) when the run had them."""
     manifest = {'in_dir': in_dir, 'out_dir': out_dir, 'targets': t_speakers, 'sr': out_rate(), 'enc_only': bool(enc_only),
                 'items': items, 'skipped': skipped}
     if overlap is not None:
@@ -2023,13 +2119,15 @@ def _write_manifest(path, in_dir, out_dir, t_speakers, enc_only, items, skipped,
         manifest['codebook'] = stats.manifest()
     if voices:
         manifest['voices'] = {t: int(voices[t]) for t in t_speakers if t in voices and speaker2id[t] == voices[t]}
+    if segment is not None:
+        manifest['segment'] = segment.manifest()
     with open(path, 'w') as f:
         json.dump(manifest, f, indent=1)
     return manifest
 
 
 def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None,
-                voices=None, codebook=None, codebook_file=None, overlap=None):
+                voices=None, codebook=None, codebook_file=None, overlap=None, segment=None):
     """Every *.wav of in_dir (any PCM / float format, any rate, channels averaged: preprocess.read_wav) to every target speaker of
     t_speakers, on the device from the samples to the waveform: {out_dir}/{target}/{stem}.wav (PCM16 at out_rate()) and .txt (the
     units), plus the manifest {out_dir}/convert_dir.json, which is returned.
@@ -2048,10 +2146,19 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
     was told to use (with_stages; default all), and the manifest's 'codebook' entry gains 'S' and per-stage figures under 'stages'.
     overlap (frames; None: not asked for): resynth_batch's -- the units written are the same, the wavs are spoken from them in
     overlapping, cross-faded decode windows -- and the manifest gains 'overlap'.  A file of fewer than MIN_LEN frames, whose one unit
-    cannot be spoken, is then skipped with a reason; enc_mode 'continues' needs a codebook (ValueError before anything is read)."""
+    cannot be spoken, is then skipped with a reason; enc_mode 'continues' needs a codebook (ValueError before anything is read).
+    segment (lambda; None: not asked for; needs a bit or vector codebook): resynth_batch's -- the units written and spoken are the
+    codewords of the path chosen for the whole utterance.  <name>.txt and <name>.idx.txt stay per-frame files, <name>.seg.txt beside
+    them holds the runs `codeword duration` (zs_amd.segment.write_segments), and the manifest gains 'segment': {lambda, units,
+    segments, mean_run_units, entropy_bits_per_segment, bits_per_second}.  A file of fewer than 2 units is skipped as with overlap."""
     from concurrent.futures import ThreadPoolExecutor
     from .preprocess import read_wav
     momentum = gl_momentum(momentum)
+    seg_stats = None
+    if segment is not None:
+        segment = sg.check_lambda(segment, 'convert_dir: segment')
+        sg.check_codebook(codebook, 'convert_dir: segment')
+        seg_stats = sg.SegmentStats(segment, codebook.K)
     if overlap is not None:
         overlap = check_overlap_value(overlap, seg_len)
         if overlap and codebook is None and trainer.enc_mode == 'continues':
@@ -2097,6 +2204,10 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
             write_encodings(it['txt'], e)
             if stats is not None:
                 side.write_idx(idx_path(it['txt']), res[2][i])
+            if seg_stats is not None:
+                r = sg.runs(res[2][i])
+                sg.write_segments(sg.seg_path(it['txt']), r)
+                seg_stats.add(r)
             done.append(it)
 
     with ThreadPoolExecutor(max_workers=1) as reader:
@@ -2119,8 +2230,9 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
                     if spec is None:
                         skip(p, 'utterance too short after trimming')
                         feats[p] = None
-                    elif overlap and _unit_counts([spec], seg_len)[0] < 2:
-                        skip(p, '%d frames give fewer than 2 units: nothing to speak from with overlap' % inf['frames'])
+                    elif (overlap or segment is not None) and _unit_counts([spec], seg_len)[0] < 2:
+                        skip(p, '%d frames give fewer than 2 units: nothing to speak from with %s' %
+                             (inf['frames'], 'overlap' if overlap else 'segment'))
                         feats[p] = None
                     else:
                         feats[p] = (spec, data[p][1], len(data[p][0]), inf)
@@ -2132,7 +2244,8 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
             if live:
                 fin = resynth_batch([feats[it['file']][0] for it in live], trainer, seg_len, [speaker2id[it['target']] for it in live],
                                     n_iter=n_iter, defer=True, enc_only=enc_only, momentum=momentum, codebook=codebook,
-                                    want_idx=codebook is not None, **({'overlap': overlap} if overlap else {}))
+                                    want_idx=codebook is not None, **({'overlap': overlap} if overlap else {}),
+                                    **({'segment': segment} if segment is not None else {}))
             later = {it['file'] for g in groups[gi + 1:gi + 2] for it in g}
             for p in [p for p in feats if p not in later]:    # a file's items are adjacent: done with, drop its device rows
                 del feats[p]
@@ -2142,7 +2255,7 @@ def convert_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, 
     items = [{'input': it['file'], 'rate': it['rate'], 'samples': it['samples'], 'target': it['target'], 'bounds': it['bounds'],
               'frames': it['frames'], 'wav': it['wav'], 'txt': it['txt']} for it in done]
     return _write_manifest(os.path.join(out_dir, 'convert_dir.json'), in_dir, out_dir, t_speakers, enc_only, items, skipped, stats,
-                           voices, speaker2id, overlap=overlap)
+                           voices, speaker2id, overlap=overlap, segment=seg_stats)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -2168,7 +2281,7 @@ def synth_dir_plan(files, n_units, targets, out_dir, batch=64, max_batch_units=6
 
 
 def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, enc_only, batch=64, n_iter=None, momentum=None, voices=None,
-              codebook=None, codebook_file=None, overlap=None):
+              codebook=None, codebook_file=None, overlap=None, segments=False):
     """Every *.txt of in_dir -- unit files as write_encodings writes them (--test_encode, --test, --convert_dir, encode_batch), one
     line of 0 / 1 per unit -- spoken in the voice of every target speaker of t_speakers: {out_dir}/{target}/{stem}.wav (PCM16 at
     out_rate()), plus the manifest {out_dir}/synth_dir.json, which is returned.
@@ -2183,8 +2296,14 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
     one integer in [0, K) per line), <name>.idx.txt is spoken as {stem}.wav through synth_index_batch, and the indices spoken are
     written beside each wav as {stem}.idx.txt.
     overlap (frames; None: not asked for): synth_units_batch's / synth_index_batch's -- overlapping, cross-faded decode windows --
-    and the manifest gains 'overlap', each item's 'fragments' holding the lengths of its windows."""
+    and the manifest gains 'overlap', each item's 'fragments' holding the lengths of its windows.
+    segments (needs a bit or vector codebook): the *.seg.txt of in_dir are read instead (zs_amd.segment.read_segments: one run
+    `codeword duration` per line), <name>.seg.txt is spoken as {stem}.wav -- the runs are expanded to one codeword per unit and go
+    through the same drivers -- and what was spoken is written beside each wav with its {stem}.seg.txt; the manifest gains 'segment'
+    (lambda null: the files do not say what they were made with)."""
     momentum = gl_momentum(momentum)
+    if segments:
+        sg.check_codebook(codebook, 'synth_dir: segments')
     if overlap is not None:
         overlap = check_overlap_value(overlap, seg_len)
     t_speakers = list(t_speakers)
@@ -2195,11 +2314,12 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
         check_gen_targets(trainer, [speaker2id[t] for t in t_speakers])
     E = int(trainer.Decoder.c_in)
     stats = _codebook_stats(codebook, trainer, codebook_file)
+    seg_stats = sg.SegmentStats(None, codebook.K) if segments else None
     skipped, skip = _skip_log('Synthesiser')
     units = {}
-    for path in sorted(glob.glob(os.path.join(in_dir, side.unit_glob))):
+    for path in sorted(glob.glob(os.path.join(in_dir, '*.seg.txt' if segments else side.unit_glob))):
         try:
-            units[path] = side.read_unit_file(path, E)
+            units[path] = side.from_indices(sg.expand(sg.read_segments(path, codebook.K))) if segments else side.read_unit_file(path, E)
         except (OSError, ValueError) as e:
             skip(path, 'cannot be read: %s' % e)
     files = sorted(units)
@@ -2208,7 +2328,7 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
         skip(s['file'], s['reason'])
     groups = plan['groups']
     for it in (it for g in groups for it in g):
-        it['stem'] = side.spoken_stem(it['stem'])
+        it['stem'] = it['stem'][:-len('.seg')] if segments else side.spoken_stem(it['stem'])
         it['wav'] = os.path.join(out_dir, it['target'], it['stem'] + '.wav')
     print('[Synthesiser] - %d unit files, %d target speakers, %d syntheses in %d groups' %
           (len(files) - len(plan['skipped']), len(t_speakers), sum(len(g) for g in groups), len(groups)))
@@ -2225,6 +2345,10 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
             write_wav(it['wav'], w, out_rate())
             if stats is not None:                             # what was spoken, beside the wav
                 side.write_spoken(os.path.splitext(it['wav'])[0], idxs[i], E)
+            if seg_stats is not None:
+                r = sg.runs(idxs[i])
+                sg.write_segments(os.path.splitext(it['wav'])[0] + '.seg.txt', r)
+                seg_stats.add(r)
             done.append(it)
 
     def enqueue(group):
@@ -2238,7 +2362,7 @@ def synth_dir(trainer, seg_len, in_dir, speaker2id_path, out_dir, t_speakers, en
     items = [{'input': it['file'], 'units': it['units'], 'fragments': pieces(it['units']), 'target': it['target'],
               'wav': it['wav']} for it in done]
     return _write_manifest(os.path.join(out_dir, 'synth_dir.json'), in_dir, out_dir, t_speakers, enc_only, items, skipped, stats, voices,
-                           speaker2id, overlap=overlap)
+                           speaker2id, overlap=overlap, segment=seg_stats)
 
 
 SINGLE_FILES = {            # convert.py:308-317: the utterances --test_single knows per source speaker
@@ -2271,10 +2395,15 @@ def test_single(trainer, seg_len, speaker2id_path, result_dir, enc_only, s_speak
     return wav_data, encodings
 
 
-def test_encode(trainer, seg_len, test_path, data_path, result_dir, flag='test', codebook=None):
+def test_encode(trainer, seg_len, test_path, data_path, result_dir, flag='test', codebook=None, segment=None):
     """convert.py:342-360.  codebook (not in the reference): every file's units are snapped to their codewords before they are
     written, and each .txt gets a sibling .idx.txt with one codeword index per line.  Under a zs_amd.vq.VectorCodebook ('continues')
-    the .txt is written as without a codebook and the .idx.txt holds the nearest codeword of every encoded frame."""
+    the .txt is written as without a codebook and the .idx.txt holds the nearest codeword of every encoded frame.
+    segment (lambda; needs a bit or vector codebook): the codewords and indices written are those of the path chosen for the whole
+    file (zs_amd.segment), and its runs go to a sibling .seg.txt."""
+    if segment is not None:
+        segment = sg.check_lambda(segment, 'test_encode: segment')
+        sg.check_codebook(codebook, 'test_encode: segment')
     if codebook is not None:
         _check_codebook(codebook, trainer)
     files = sorted(glob.glob(os.path.join(test_path, '*.wav')))
@@ -2290,7 +2419,7 @@ def test_encode(trainer, seg_len, test_path, data_path, result_dir, flag='test',
                 continue
             units = encode(f_h5[f"test/{feed['s_id']}/{feed['utt_id']}/lin"][()], trainer, seg_len, save=False)
             txt = os.path.join(dir_path, f"{feed['s_id']}_{feed['utt_id']}.txt")
-            codebook.units().write_encoded(txt, units, trainer.device)
+            codebook.units().write_encoded(txt, units, trainer.device, **({'segment': segment} if segment is not None else {}))
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -10,6 +10,8 @@
 //                       index whatever the order the codewords come in -- the tie rule survives tiling over K and the split below.
 //                       S > 1 (few rows, an inference chunk): the S waves of a workgroup hold the SAME 64 rows and take an S-th of
 //                       every pass each; their words meet in LDS and wave 0 writes the results.
+//   code_scores_kernel  zs_code_scores (--segment): the same rows in registers and the same LDS tiles (stage_codes, one function for
+//                       both), every distance written as fp32 instead of reduced.
 //   code_accum_kernel   a workgroup owns a tile of codewords (those whose counters, KT x E int32, fit 64 KiB of LDS) and a slice of
 //                       the rows.  It scans its slice of idx, lists the rows of its codewords and adds their bits to the LDS
 //                       counters (one lane per byte of a row), then adds the non-zero counters to `ones` and `cnt` with integer
@@ -84,6 +86,63 @@ __device__ __forceinline__ int wave_sum_i(int v) {
   return v;
 }
 
+// THE codeword tiling of zs_code_assign and zs_code_scores: the codewords k0 .. k0 + nk - 1, W dwords each and masked to the columns
+// < E, into s_code; between two barriers (the pass before has been read; the first time, every row is loaded)
+template <int W, int NT>
+__device__ __forceinline__ void stage_codes(uint32_t* s_code, const uint8_t* code, int code_bytes, int k0, int nk, int nbytes, int E,
+                                            int cmode) {
+  __syncthreads();
+  for (int i = threadIdx.x; i < nk * W; i += NT) {
+    const int k = i / W, w = i & (W - 1);
+    s_code[i] = row_word(code + (int64_t)(k0 + k) * code_bytes, w, nbytes, cmode != 0) & word_mask(w, E);
+  }
+  __syncthreads();
+}
+
+// zs_code_scores: code_assign_kernel's rows and passes (one row per lane, 256 lanes); the distances of 4 consecutive codewords leave
+// as one 16-byte store where `vec` (scores 16-byte aligned, ld_s a multiple of 4; a pass starts at a multiple of 4 codewords).
+template <int W> __global__ void __launch_bounds__(256) code_scores_kernel(const ZsCodeScores p, const int umode, const int cmode, const int vec) {
+  constexpr int NT = 256, TK = TILE_WORDS / W;
+  static_assert(TK % 4 == 0, "a pass starts at a multiple of 4 codewords");
+  __shared__ __attribute__((aligned(16))) uint32_t s_code[TILE_WORDS];
+  const int nbytes = (p.E + 7) >> 3;
+  const int64_t row = (int64_t)blockIdx.x * NT + threadIdx.x;
+  const bool live = row < p.n;
+  uint32_t u[W];
+  if (live) {
+    load_row<W>(p.units + row * p.row_bytes, nbytes, p.E, umode, u);
+  } else {
+#pragma unroll
+    for (int i = 0; i < W; ++i) u[i] = 0;
+  }
+  float* out = p.scores + (live ? row : 0) * p.ld_s;
+  for (int k0 = 0; k0 < p.K; k0 += TK) {
+    const int nk = p.K - k0 < TK ? p.K - k0 : TK;
+    stage_codes<W, NT>(s_code, p.code, p.code_bytes, k0, nk, nbytes, p.E, cmode);
+    if (!live) continue;
+    for (int k = 0; k < nk; k += 4) {
+      float d[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        uint32_t s = 0;
+        if (k + q < nk) {
+          const uint32_t* c = s_code + (k + q) * W;
+#pragma unroll
+          for (int i = 0; i < W; ++i) s += __popc(u[i] ^ c[i]);
+        }
+        d[q] = (float)s;
+      }
+      if (vec && k + 4 <= nk) {
+        *reinterpret_cast<float4*>(out + k0 + k) = make_float4(d[0], d[1], d[2], d[3]);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (k + q < nk) out[k0 + k + q] = d[q];
+      }
+    }
+  }
+}
+
 template <int W, int R, int S> __global__ void __launch_bounds__(S > 1 ? 64 * S : 256)
 code_assign_kernel(const ZsCodeAssign p, const int umode, const int cmode) {
   static_assert(S == 1 || R == 1, "shared rows: one row per lane");
@@ -108,12 +167,7 @@ code_assign_kernel(const ZsCodeAssign p, const int umode, const int cmode) {
   }
   for (int k0 = 0; k0 < p.K; k0 += TK) {
     const int nk = p.K - k0 < TK ? p.K - k0 : TK;
-    __syncthreads();                                              // the pass before has been read (and, the first time, every row loaded)
-    for (int i = threadIdx.x; i < nk * W; i += NT) {
-      const int k = i / W, w = i & (W - 1);
-      s_code[i] = row_word(p.code + (int64_t)(k0 + k) * p.code_bytes, w, nbytes, cmode != 0) & word_mask(w, p.E);
-    }
-    __syncthreads();
+    stage_codes<W, NT>(s_code, p.code, p.code_bytes, k0, nk, nbytes, p.E, cmode);
     int ka = 0, kb = nk;
     if (S > 1) {
       const int per = (nk + S - 1) / S;
@@ -358,4 +412,30 @@ extern "C" int zs_code_update(const ZsCodeUpdate* p, void* stream) {
   const int vec = p->E % 8 == 0 && (reinterpret_cast<uintptr_t>(p->ones) & 15) == 0;
   hipLaunchKernelGGL(code_update_kernel, dim3((unsigned)p->K), dim3(UPD_NT), 0, (hipStream_t)stream, *p, vec);
   return zs_check_launch("zs_code_update");
+}
+
+extern "C" int zs_code_scores(const ZsCodeScores* p, void* stream) {
+  ZS_REQUIRE(p, "zs_code_scores: null argument");
+  const char* why = check_shape("zs_code_scores", p->n, p->K, p->E, p->row_bytes, p->code_bytes);
+  ZS_REQUIRE(!why, "zs_code_scores: %s (n %lld, K %d, E %d, row_bytes %d, code_bytes %d)", why, (long long)p->n, p->K, p->E, p->row_bytes,
+             p->code_bytes);
+  ZS_REQUIRE(p->n <= 0x7fffffff, "zs_code_scores: n must be in [0, 2^31) (got %lld)", (long long)p->n);
+  ZS_REQUIRE(p->K <= ZS_SEG_MAX_K, "zs_code_scores: K must be in [1, %d] (got %d)", ZS_SEG_MAX_K, p->K);
+  ZS_REQUIRE(p->ld_s >= p->K, "zs_code_scores: ld_s %lld is below K %d", (long long)p->ld_s, p->K);
+  if (p->n == 0) return ZS_OK;
+  ZS_REQUIRE(p->units && p->code && p->scores, "zs_code_scores: null operand");
+  ZS_REQUIRE((reinterpret_cast<uintptr_t>(p->scores) & 3) == 0, "zs_code_scores: scores is not aligned to its element");
+  const int nbytes = (p->E + 7) / 8;
+  const int umode = align_mode(p->units, p->row_bytes, nbytes), cmode = align_mode(p->code, p->code_bytes, nbytes);
+  const int vec = (reinterpret_cast<uintptr_t>(p->scores) & 15) == 0 && p->ld_s % 4 == 0;
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)((p->n + 255) / 256)), block(256);
+  const int words = (p->E + 31) / 32;
+  if (words <= 1) hipLaunchKernelGGL(code_scores_kernel<1>, grid, block, 0, st, *p, umode, cmode, vec);
+  else if (words <= 2) hipLaunchKernelGGL(code_scores_kernel<2>, grid, block, 0, st, *p, umode, cmode, vec);
+  else if (words <= 4) hipLaunchKernelGGL(code_scores_kernel<4>, grid, block, 0, st, *p, umode, cmode, vec);
+  else if (words <= 8) hipLaunchKernelGGL(code_scores_kernel<8>, grid, block, 0, st, *p, umode, cmode, vec);
+  else if (words <= 16) hipLaunchKernelGGL(code_scores_kernel<16>, grid, block, 0, st, *p, umode, cmode, vec);
+  else hipLaunchKernelGGL(code_scores_kernel<32>, grid, block, 0, st, *p, umode, cmode, vec);
+  return zs_check_launch("zs_code_scores");
 }

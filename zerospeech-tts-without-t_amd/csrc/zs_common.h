@@ -10,6 +10,7 @@
 #include <mutex>
 
 #include "../../include/zs_amd.h"
+#include "../../include/zs_amd_segment.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;

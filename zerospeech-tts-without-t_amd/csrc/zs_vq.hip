@@ -13,6 +13,8 @@
 //                      sits in a tile, in either decomposition.
 //                      blockIdx.y splits K (rows below ZS_VQ_SPLIT_N with a workspace): the words of a row meet by a 64-bit
 //                      atomic min in the workspace, and vq_finish_kernel writes the outputs.
+//   vq_scores_kernel   zs_vq_scores (--segment): the same tile loop and score expression (vq_tile_products, vq_score: one device function
+//                      each, compiled into both kernels), one 128 x 128 tile per workgroup, the scores stored instead of reduced.
 //   vq_accum_kernel    zs_code_accum's scheme: a workgroup owns a tile of codewords (those whose int64 sums fit 64 KiB of LDS) and
 //                      a slice of the rows, lists the rows of its codewords per round and adds their quantised columns with LDS
 //                      atomics; the non-zero sums go to memory with one 64-bit atomic each.
@@ -77,6 +79,56 @@ __device__ __forceinline__ void vq_finish_row(const ZsVqAssign& p, bool live, in
   }
 }
 
+// THE tile loop of zs_vq_assign and zs_vq_scores: the products of the workgroup's 128 rows (from row0) with the codewords k0 .. k0 +
+// 127 (those below kend; the others are zero) over the E columns, zero-padded to pairs, into the wave's 4 accumulators; cnorm of the
+// tile into sCn.  SQ: the squared norms of the rows are added to sq as the rows pass (zs_vq_assign's dist).
+template <typename S, bool SQ, typename P>
+__device__ __forceinline__ void vq_tile_products(const P& o, int64_t row0, int k0, int kend, int xvec, int cvec, float* sX,
+                                                 float* sC, float* sCn, f32x16 (&acc)[4], bool want_sq, float (&sq)[4], int wave) {
+  const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l32 = lane & 31;
+  const S* x = static_cast<const S*>(o.x);
+  const int g = tid & 7, rr = tid >> 3;                           // staging: columns 4g .. 4g + 3 of the tile rows rr + 32q
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[cb][v] = 0.f;
+  for (int j0 = 0; j0 < o.E; j0 += VQ_KC) {
+    __syncthreads();                                              // the chunk (and the tile's epilogue) before is done with LDS
+    if (j0 == 0 && tid < VQ_BN) sCn[tid] = k0 + tid < kend ? o.cnorm[k0 + tid] : 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int r = rr + 32 * q;
+      float v[4];
+      vq_load4<S>(x + (row0 + r) * o.ld_x, j0 + 4 * g, o.E, row0 + r < o.n, xvec != 0, v);
+      if (SQ && want_sq) sq[q] += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) sX[(4 * g + i) * VQ_P + r] = v[i];
+      vq_load4<float>(o.code + (int64_t)(k0 + r) * o.ld_code, j0 + 4 * g, o.E, k0 + r < kend, cvec != 0, v);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) sC[(4 * g + i) * VQ_P + r] = v[i];
+    }
+    __syncthreads();
+    const int cols = o.E - j0 < VQ_KC ? o.E - j0 : VQ_KC;         // an odd last column pairs with a zero one
+    const int steps = (cols + 1) >> 1;
+    const float* xb = sX + half * VQ_P + wave * 32 + l32;
+    const float* cb0 = sC + half * VQ_P + l32;
+    for (int s = 0; s < steps; ++s) {
+      const float b = xb[2 * s * VQ_P];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+        acc[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(cb0[2 * s * VQ_P + cb * 32], b, acc[cb], 0, 0, 0);
+    }
+  }
+}
+
+// THE score of a (row, codeword) pair from its accumulator register
+__device__ __forceinline__ float vq_score(float cn, float acc) {
+  const float s = cn - 2.f * acc;
+  return s == 0.f ? 0.f : s;                                      // one zero
+}
+// register v of accumulator cb: codeword k0 + 32 cb + 8 (v / 4) + 4 half + v % 4, row wave * 32 + l32
+__device__ __forceinline__ int vq_acc_codeword(int cb, int v, int half) { return 32 * cb + 8 * (v >> 2) + 4 * half + (v & 3); }
+
 template <typename S> __global__ void __launch_bounds__(VQ_NT)
 vq_assign_kernel(const ZsVqAssign p, const int kper, const int xvec, const int cvec, const int split) {
   __shared__ float sX[VQ_KC * VQ_P], sC[VQ_KC * VQ_P];
@@ -85,53 +137,20 @@ vq_assign_kernel(const ZsVqAssign p, const int kper, const int xvec, const int c
   const int half = lane >> 5, l32 = lane & 31;
   const int64_t row0 = (int64_t)blockIdx.x * VQ_BM;
   const int kbeg = blockIdx.y * kper, kend = kbeg + kper < p.K ? kbeg + kper : p.K;
-  const S* x = static_cast<const S*>(p.x);
-  const int g = tid & 7, rr = tid >> 3;                           // staging: columns 4g .. 4g + 3 of the tile rows rr + 32q
+  const int g = tid & 7, rr = tid >> 3;
   const bool want_norm = p.dist != nullptr && blockIdx.y == 0;
   float sq[4] = {0.f, 0.f, 0.f, 0.f};
   uint64_t best = ~(uint64_t)0;
   for (int k0 = kbeg; k0 < kend; k0 += VQ_BN) {
     f32x16 acc[4];
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[cb][v] = 0.f;
-    for (int j0 = 0; j0 < p.E; j0 += VQ_KC) {
-      __syncthreads();                                            // the chunk (and the tile's epilogue) before is done with LDS
-      if (j0 == 0 && tid < VQ_BN) sCn[tid] = k0 + tid < kend ? p.cnorm[k0 + tid] : 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int r = rr + 32 * q;
-        float v[4];
-        vq_load4<S>(x + (row0 + r) * p.ld_x, j0 + 4 * g, p.E, row0 + r < p.n, xvec != 0, v);
-        if (want_norm && k0 == kbeg) sq[q] += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sX[(4 * g + i) * VQ_P + r] = v[i];
-        vq_load4<float>(p.code + (int64_t)(k0 + r) * p.ld_code, j0 + 4 * g, p.E, k0 + r < kend, cvec != 0, v);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sC[(4 * g + i) * VQ_P + r] = v[i];
-      }
-      __syncthreads();
-      const int cols = p.E - j0 < VQ_KC ? p.E - j0 : VQ_KC;       // an odd last column pairs with a zero one
-      const int steps = (cols + 1) >> 1;
-      const float* xb = sX + half * VQ_P + wave * 32 + l32;
-      const float* cb0 = sC + half * VQ_P + l32;
-      for (int s = 0; s < steps; ++s) {
-        const float b = xb[2 * s * VQ_P];
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
-          acc[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(cb0[2 * s * VQ_P + cb * 32], b, acc[cb], 0, 0, 0);
-      }
-    }
-    // register v of accumulator cb: codeword k0 + 32 cb + 8 (v / 4) + 4 half + v % 4, row wave * 32 + l32
+    vq_tile_products<S, true>(p, row0, k0, kend, xvec, cvec, sX, sC, sCn, acc, want_norm && k0 == kbeg, sq, wave);
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int kl = 32 * cb + 8 * (v >> 2) + 4 * half + (v & 3);
+        const int kl = vq_acc_codeword(cb, v, half);
         if (k0 + kl < kend) {
-          float s = sCn[kl] - 2.f * acc[cb][v];
-          s = s == 0.f ? 0.f : s;                                 // one zero
+          const float s = vq_score(sCn[kl], acc[cb][v]);
           const uint64_t key = ((uint64_t)vq_ord(s) << 32) | (uint32_t)(k0 + kl);
           best = key < best ? key : best;
         }
@@ -173,6 +192,41 @@ __global__ void __launch_bounds__(VQ_NT) vq_finish_kernel(const ZsVqAssign p) {
   const uint64_t key = live ? keys[row] : 0;
   const float xn = live && p.dist ? reinterpret_cast<const float*>(keys + p.n)[row] : 0.f;
   vq_finish_row(p, live, row, key, xn);
+}
+
+// zs_vq_scores: workgroup (x, y) writes the tile of rows 128 x .. and codewords 128 y ..: vq_tile_products and vq_score, then stores.
+// A lane's registers 4i .. 4i + 3 of an accumulator are 4 consecutive codewords of its row: one 16-byte store where VEC (scores 16-byte
+// aligned, ld_s a multiple of 4; a group of 4 starts at a multiple of 4 and K cuts it only in the last one), single elements otherwise.
+template <typename S, bool VEC> __global__ void __launch_bounds__(VQ_NT)
+vq_scores_kernel(const ZsVqScores p, const int xvec, const int cvec) {
+  __shared__ float sX[VQ_KC * VQ_P], sC[VQ_KC * VQ_P];
+  __shared__ float sCn[VQ_BN];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int half = lane >> 5, l32 = lane & 31;
+  const int64_t row0 = (int64_t)blockIdx.x * VQ_BM;
+  const int k0 = blockIdx.y * VQ_BN, kend = p.K;
+  float sq[4] = {0.f, 0.f, 0.f, 0.f};
+  f32x16 acc[4];
+  vq_tile_products<S, false>(p, row0, k0, kend, xvec, cvec, sX, sC, sCn, acc, false, sq, wave);
+  const int64_t row = row0 + wave * 32 + l32;
+  if (row >= p.n) return;
+  float* out = p.scores + row * p.ld_s + k0;
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+    for (int v4 = 0; v4 < 16; v4 += 4) {
+      const int kl = vq_acc_codeword(cb, v4, half);
+      float s[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s[i] = vq_score(sCn[kl + i], acc[cb][v4 + i]);
+      if (VEC && k0 + kl + 4 <= kend) {
+        *reinterpret_cast<float4*>(out + kl) = make_float4(s[0], s[1], s[2], s[3]);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (k0 + kl + i < kend) out[kl + i] = s[i];
+      }
+    }
 }
 
 // ---- accum -------------------------------------------------------------------------------------------------------------------------
@@ -345,6 +399,31 @@ extern "C" int zs_vq_assign(const ZsVqAssign* p, void* stream) {
   if (split && (p->idx || p->dist))
     hipLaunchKernelGGL(vq_finish_kernel, dim3((unsigned)((p->n + VQ_NT - 1) / VQ_NT)), dim3(VQ_NT), 0, st, *p);
   return zs_check_launch("zs_vq_assign");
+}
+
+extern "C" int zs_vq_scores(const ZsVqScores* p, void* stream) {
+  ZS_REQUIRE(p, "zs_vq_scores: null argument");
+  const char* why = vq_shape(p->K, p->E, p->n, p->ld_x, p->ld_code);
+  ZS_REQUIRE(!why, "zs_vq_scores: %s (n %lld, K %d, E %d, ld_x %lld, ld_code %lld)", why, (long long)p->n, p->K, p->E, (long long)p->ld_x,
+             (long long)p->ld_code);
+  ZS_REQUIRE(p->K <= ZS_SEG_MAX_K, "zs_vq_scores: K must be in [1, %d] (got %d)", ZS_SEG_MAX_K, p->K);
+  ZS_REQUIRE(p->ld_s >= p->K, "zs_vq_scores: ld_s %lld is below K %d", (long long)p->ld_s, p->K);
+  ZS_REQUIRE(p->dtype == ZS_F32 || p->dtype == ZS_BF16, "zs_vq_scores: bad dtype");
+  if (p->n == 0) return ZS_OK;
+  ZS_REQUIRE(p->x && p->code && p->cnorm && p->scores, "zs_vq_scores: null operand");
+  const bool f32 = p->src_f32 || p->dtype == ZS_F32;
+  ZS_REQUIRE(!misaligned(p->x, f32 ? 4 : 2) && !misaligned(p->code, 4) && !misaligned(p->cnorm, 4) && !misaligned(p->scores, 4),
+             "zs_vq_scores: an operand is not aligned to its element");
+  const int xvec = !misaligned(p->x, f32 ? 16 : 8) && p->ld_x % 4 == 0;
+  const int cvec = !misaligned(p->code, 16) && p->ld_code % 4 == 0;
+  const bool svec = !misaligned(p->scores, 16) && p->ld_s % 4 == 0;
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)((p->n + VQ_BM - 1) / VQ_BM), (unsigned)((p->K + VQ_BN - 1) / VQ_BN));
+  if (f32 && svec) hipLaunchKernelGGL((vq_scores_kernel<float, true>), grid, dim3(VQ_NT), 0, st, *p, xvec, cvec);
+  else if (f32) hipLaunchKernelGGL((vq_scores_kernel<float, false>), grid, dim3(VQ_NT), 0, st, *p, xvec, cvec);
+  else if (svec) hipLaunchKernelGGL((vq_scores_kernel<bf16_t, true>), grid, dim3(VQ_NT), 0, st, *p, xvec, cvec);
+  else hipLaunchKernelGGL((vq_scores_kernel<bf16_t, false>), grid, dim3(VQ_NT), 0, st, *p, xvec, cvec);
+  return zs_check_launch("zs_vq_scores");
 }
 
 extern "C" int zs_vq_accum(const ZsVqAccum* p, void* stream) {

@@ -153,6 +153,11 @@ class ResidualCodebook(CodebookFile):
         from .convert import _ResidualUnits
         return _ResidualUnits(self, self.stages if stages is None else stages)
 
+    def scores_(self, rows, out):
+        """Refused: --segment chooses one path among the codewords of one codebook, and the stages of a residual codebook have none."""
+        from .segment import check_codebook
+        check_codebook(self)
+
     def snap(self, x_dev, stages=None, work=None, residuals=None):
         """(idx int32 [S', n], dist fp32 [S', n]) of the rows of x_dev (fp32 / bf16 [n, >= E]) through the first S' = stages stages, on
         the device: dist[s] is the squared distance left behind stage s.  work: a zs_vq_assign workspace, or None for the row

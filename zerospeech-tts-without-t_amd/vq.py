@@ -76,6 +76,12 @@ def assign(x, code, cnorm, idx=None, dist=None, moved=None, work=None, E=None):
                   (x.stride(0) if n > 1 else max(int(x.shape[1]), E)), code, cnorm, E=E, idx=idx, dist=dist, moved=moved, work=work)
 
 
+def launch_scores(stream, dt, x, n, ld_x, code, cnorm, out, ld_s, E=None):
+    """THE zs_vq_scores launch: launch_assign's operands; out: the device pointer of fp32 [n][ld_s], ld_s >= K."""
+    L.call('zs_vq_scores', 'ZsVqScores', stream, dtype=dt, src_f32=0, x=x, n=n, ld_x=ld_x, code=L.ptr(code), ld_code=code.stride(0),
+           cnorm=L.ptr(cnorm), K=code.shape[0], E=(int(code.shape[1]) if E is None else int(E)), scores=out, ld_s=ld_s)
+
+
 def launch_gather(stream, dt, idx, code, start, length, n_frag, T, dst, ld_dst, bad, E=None):
     """THE zs_vq_gather launch: the operand [n_frag, T, ld_dst] of the compute dtype dt at the device pointer dst from idx int32
     [n_idx], code fp32 [K, E] and the device tables start int64 / length int32 [n_frag]; bad int32 [1] is added to."""
@@ -140,6 +146,20 @@ class VectorCodebook(CodebookFile):
         dist = torch.empty(x_dev.shape[0], dtype=torch.float32, device=x_dev.device)
         assign(x_dev, code, cn, idx=idx, dist=dist, work=work)
         return idx, dist
+
+    def scores_(self, rows, out):
+        """out[i][k] = the score zs_vq_assign computes for row i and codeword k, bitwise (one zs_vq_scores on the current stream, no
+        synchronisation).  rows fp32 / bf16 [n, >= E] and out fp32 [n, >= K] on the device; the columns of out at or beyond K are not
+        written.  What --segment chooses its paths from (zs_amd.segment)."""
+        from .codebook import _check_scores, _scores_ld
+        from .segment import check_codebook
+        check_codebook(self)
+        _check_x(rows, self.E, 'rows')
+        n = int(rows.shape[0])
+        _check_scores(out, n, self.K)
+        code, cn = self.to(rows.device)
+        launch_scores(_stream(rows.device), (L.ZS_F32 if rows.dtype == torch.float32 else L.ZS_BF16), L.ptr(rows), n,
+                      (rows.stride(0) if n > 1 else max(int(rows.shape[1]), self.E)), code, cn, L.ptr(out), _scores_ld(out, self.K))
 
     @classmethod
     def _dir_rows(cls, trainer, seg_len, in_dir, batch, E):
