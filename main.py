@@ -114,6 +114,14 @@ codewords used and perplexity; every checkpoint gets <checkpoint>.rvq.npz beside
 mode and a file that is no residual codebook are refused before anything is built:
   python main.py --enc_mode continues --train_ae --load_model --rvq_train ckpt_english/codebooks/K1024x4.rvq.npz
 
+--rvq_dropout P with --rvq_train (zs_amd.rvq_train, quantiser dropout): each step, each sample of the batch is with probability P, in
+(0, 1], decoded from a number of stages drawn uniformly from 1 .. S instead of all S (drawn on the device from the step's own seed
+stream, so a captured step draws anew on every replay); the stages a sample does not use neither commit its rows nor count them in
+their codebooks' averages.  A model trained so has decoded rows built from 1, 2, .. stages: what --rvq_stages s speaks.  The log gains
+every stage's share of active rows.  It combines with everything --rvq_train combines with, and is refused before anything is built
+without --rvq_train, beside --vq_train and for a P outside (0, 1]:
+  python main.py --enc_mode continues --train_ae --load_model --rvq_train ckpt_english/codebooks/K1024x4.rvq.npz --rvq_dropout 0.5
+
 --overlap FRAMES with --synth_dir or --convert_dir (zs_amd.convert.unit_windows): a long utterance is decoded in windows of seg_len
 frames that share FRAMES of them, and the shared frames are cross-faded on the device (zs_xfade_gather) instead of the pieces being
 laid end to end, so the spectrogram no longer jumps every seg_len frames.  FRAMES is 0 or a multiple of 8 up to half of seg_len (64 at
@@ -341,6 +349,9 @@ def build_parser():
     p.add_argument('--vq_restart', type=float, default=None, metavar='T',
                    help='with --vq_train or --rvq_train: a codeword that took no row of the batch and whose averaged count fell below '
                         "T, in (0, 1), is put back onto one of the rows its stage quantised (default: dead codewords stay where they are)")
+    p.add_argument('--rvq_dropout', type=float, default=None, metavar='P',
+                   help='with --rvq_train: quantiser dropout -- with probability P in (0, 1] a sample of the batch is decoded from a number '
+                        'of stages drawn uniformly from 1 .. S instead of all S (default: every sample from all S)')
     p.add_argument('--overlap', type=int, default=None, metavar='FRAMES',
                    help='with --synth_dir / --convert_dir: decode in windows that share FRAMES spectrogram frames and cross-fade them '
                         '(0, or a multiple of 8 up to 8 * ((seg_len // 8) // 2)); the units do not change; default: pieces laid end to end')
@@ -518,7 +529,8 @@ def check_vq_train(args, enc_mode=None, c_in=None):
 def check_rvq_train(args, enc_mode=None, c_in=None):
     """--rvq_train is refused, before anything is built and naming the flag, where it cannot do what it says
     (zs_amd.rvq_train.check_rvq_train): beside --vq_train, without --train_ae or beside another --train* mode, under a multi-rank
-    launch, with --resume or --valid_every, its options out of range; and, once enc_mode is known (argument_runner calls this again
+    launch, with --resume or --valid_every, its options out of range (--rvq_dropout too: without --rvq_train, beside --vq_train or with
+    a P outside (0, 1]); and, once enc_mode is known (argument_runner calls this again
     after reading hps), an enc_mode other than 'continues', a file that is no residual codebook or a width other than the Decoder's
     c_in.  Returns the loaded codebook on that second call (None without --rvq_train)."""
     from zs_amd.rvq_train import check_rvq_train as check
@@ -719,7 +731,8 @@ def main(argv=None):
                         args.vq_decay if args.vq_decay is not None else DECAY)
             if args.vq_restart is not None:
                 vq_train += (args.vq_restart,)
-        trainer = Trainer(hps, data_loader, args.g_mode, args.enc_mode, dtype=args.dtype, ema=args.ema, valid=valid, vq_train=vq_train)
+        more = {'rvq_dropout': args.rvq_dropout} if args.rvq_dropout is not None else {}      # --rvq_dropout: with --rvq_train alone
+        trainer = Trainer(hps, data_loader, args.g_mode, args.enc_mode, dtype=args.dtype, ema=args.ema, valid=valid, vq_train=vq_train, **more)
         if args.load_model:
             trainer.load_model(os.path.join(args.ckpt_dir, args.load_train_model_name), load_model_list=hps.load_model_list,
                                use_ema=args.use_ema)

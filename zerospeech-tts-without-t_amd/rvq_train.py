@@ -9,7 +9,12 @@ of the residuals, the index zs_vq_accum reads and the loss's partial sums in one
 Step t reads, in every stage, the codebook step t - 1 left: the averages are written to the `next` copies, which become the live ones at
 the head of the next forward.  Everything is enqueued on the current stream with launch arguments that do not change between
 iterations, so the captured step replays it; nothing adds floats atomically, so a run is bitwise reproducible.
-tests/rvq_train_ref.py is the numpy definition.  Not in the reference, which has no codebook."""
+tests/rvq_train_ref.py is the numpy definition.  Not in the reference, which has no codebook.
+Quantiser dropout (`--rvq_dropout P`): with probability P a sample of the batch is decoded from s_b stages, uniform over
+1 .. S, drawn on the device from the step's own seed stream (zs_rvq_drop_draw); the stages at or above s_b neither commit that
+sample's rows nor count them (zs_rvq_commit_drop in place of zs_rvq_commit) and the Decoder reads the sum of its first s_b codewords
+(zs_rvq_gather_frag in place of zs_rvq_gather), so every coarser bitrate --rvq_stages s offers is a trained operating point.
+csrc/zs_rvq_drop.hip, include/zs_amd_rvq_drop.h; tests/rvq_drop_ref.py is the numpy definition.  Without it nothing new is launched."""
 import numpy as np
 import torch
 
@@ -18,6 +23,25 @@ from . import rvq, vq
 from .vq_train import BETA, DECAY, MAX_ABS, PARTS, check_beta, check_decay, check_restart, perplexity, restart_stride
 
 GOLDEN = 0x9E3779B97F4A7C15        # stage s restarts with the seed (seed + s GOLDEN) mod 2^64
+DROP_ONE = 1 << 24                 # zs_rvq_drop_draw compares 24 bits of the draw with floor(P 2^24)
+
+
+def check_dropout(p, what='--rvq_dropout'):
+    """P of quantiser dropout as a float: finite and in (0, 1] (and at least 2^-24, the draw's resolution), else ValueError."""
+    try:
+        v = float(p)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be a number in (0, 1] (got %r)' % (what, p))
+    if not np.isfinite(v) or not 0.0 < v <= 1.0:
+        raise ValueError('%s must be in (0, 1] (got %r)' % (what, p))
+    if drop_threshold(v) < 1:
+        raise ValueError('%s must be at least 2^-24, the resolution of the draw (got %r)' % (what, p))
+    return v
+
+
+def drop_threshold(p):
+    """thr = floor(P 2^24), the integer zs_rvq_drop_draw compares with (P 2^24 is exact in a double: a shift of the exponent)."""
+    return int(np.floor(float(p) * DROP_ONE))
 
 
 class RvqBottleneck(object):
@@ -26,9 +50,12 @@ class RvqBottleneck(object):
     m = code); ctx: a layers.Ctx (device, compute dtype and the buffer of q)."""
     kind = 'residual'
 
-    def __init__(self, codebook, beta=BETA, decay=DECAY, rows=0, ctx=None, restart=None):
+    dropout = None
+
+    def __init__(self, codebook, beta=BETA, decay=DECAY, rows=0, ctx=None, restart=None, dropout=None):
         """restart: None, or the threshold in (0, 1) below which a codeword of any stage that took no row this step is put back onto
-        one of the rows that stage quantised (zs_vq_restart)."""
+        one of the rows that stage quantised (zs_vq_restart).  dropout: None, or P in (0, 1]: the probability with which a
+        sample is decoded from a number of stages drawn uniformly from 1 .. S instead of all S."""
         if not isinstance(codebook, rvq.ResidualCodebook):
             raise ValueError('RvqBottleneck: a residual codebook (rvq.ResidualCodebook) is needed')
         self.beta, self.decay = check_beta(beta), check_decay(decay)
@@ -74,6 +101,12 @@ class RvqBottleneck(object):
             self.stride = restart_stride(n)                      # a host constant of the plan
             self.rwork = torch.zeros(K + 2, **i32)
         self._frag = {}                                          # (B, T') -> the device table of zs_rvq_gather
+        self.dropout = None if dropout is None else check_dropout(dropout, 'RvqBottleneck: dropout')
+        if self.dropout is not None:
+            self.thr = drop_threshold(self.dropout)              # a host constant of the plan
+            self.active = torch.zeros(S, **i32)                  # rows that took part in stage s in the last step
+            self._s_use = {}                                     # B -> the stage count of every sample, int32 [B]
+            self.s_use = None                                    # the one the last forward wrote
         self.steps = 0
         self._bits = None
 
@@ -85,12 +118,20 @@ class RvqBottleneck(object):
                                         torch.full((B,), T, dtype=torch.int32, device=self.device))
         return tab
 
+    def _counts(self, B):
+        """s_use int32 [B]: what zs_rvq_drop_draw writes for a batch of B samples (built once per shape, before any capture)."""
+        t = self._s_use.get(B)
+        if t is None:
+            t = self._s_use[B] = torch.zeros(B, dtype=torch.int32, device=self.device)
+        return t
+
     # ---- the step ----------------------------------------------------------------------------------------------------------------------
     def forward(self, bits, seed=0, seed_ptr=None):
         """bits: the Act [B, T', E] EncoderEngine.forward returns.  Enqueues, per stage, assign, commit, accum and the codebook's
         average (and the restart), then the loss and the gather; returns q, an Act the DecoderEngine takes as it takes bits.
         (seed, seed_ptr): the pair the encoder's forward of this step was given; with restart on, the rows that dead codewords take
-        follow it."""
+        follow it.  With dropout the step's stage counts are drawn from the same pair first, every commit is zs_rvq_commit_drop and
+        the gather zs_rvq_gather_frag."""
         ctx, S, K, E, n = self.ctx, self.S, self.K, self.E, self.rows
         if bits.rows != n or bits.C != E or bits.t.dtype != ctx.tdt:
             raise ValueError('RvqBottleneck: built for %d rows of %d columns of %s, got %d rows of %d of %s' %
@@ -102,6 +143,14 @@ class RvqBottleneck(object):
         self.acc.zero_()
         wide = ctx.tdt != torch.float32                          # the rows need an fp32 copy for zs_vq_accum
         acc32 = self.acc.view(torch.int32)
+        drop = None
+        if self.dropout is not None:
+            if bits.B * bits.T != n:
+                raise ValueError('RvqBottleneck: dropout needs %d samples of %d rows to be the %d rows' % (bits.B, bits.T, n))
+            s_use = self.s_use = self._counts(bits.B)
+            L.call('zs_rvq_drop_draw', 'ZsRvqDropDraw', st, seed=int(seed or 0) % (1 << 64), seed_ptr=seed_ptr, thr=self.thr, S=S,
+                   n_frag=bits.B, rows_per_frag=bits.T, s_use=L.ptr(s_use), active=L.ptr(self.active))
+            drop = dict(s_use=L.ptr(s_use), rows_per_frag=bits.T)
         for s in range(S):
             code, cn = self.code_live[s], self.cnorm_live[s]
             if s == 0:
@@ -112,11 +161,15 @@ class RvqBottleneck(object):
                 ld_x = ld32 = E
                 f32 = 1
             vq.launch_assign(st, (L.ZS_F32 if f32 else ctx.dt), x, n, ld_x, code, cn, idx=self.idx[s], work=self.work)
-            L.call('zs_rvq_commit', 'ZsRvqCommit', st, dtype=ctx.dt, src_f32=f32, first=int(s == 0), x=x, n=n, ld_x=ld_x,
-                   idx=L.ptr(self.idx[s]), code=L.ptr(code), ld_code=E, K=K, E=E, r=L.ptr(self.res[(s + 1) & 1]), ld_r=E,
-                   x_f32=(L.ptr(self.res[0]) if s == 0 and wide else None), ld_xf=(E if s == 0 and wide else 0),
-                   idx_acc=L.ptr(self.idx_acc[s]), a=L.ptr(self.a), ld_a=E, partial=L.ptr(self.partial[s]), bad=L.ptr(self.stat),
-                   over=L.ptr(self.stat, 1))
+            commit = dict(dtype=ctx.dt, src_f32=f32, first=int(s == 0), x=x, n=n, ld_x=ld_x,
+                          idx=L.ptr(self.idx[s]), code=L.ptr(code), ld_code=E, K=K, E=E, r=L.ptr(self.res[(s + 1) & 1]), ld_r=E,
+                          x_f32=(L.ptr(self.res[0]) if s == 0 and wide else None), ld_xf=(E if s == 0 and wide else 0),
+                          idx_acc=L.ptr(self.idx_acc[s]), a=L.ptr(self.a), ld_a=E, partial=L.ptr(self.partial[s]), bad=L.ptr(self.stat),
+                          over=L.ptr(self.stat, 1))
+            if drop is None:
+                L.call('zs_rvq_commit', 'ZsRvqCommit', st, **commit)
+            else:
+                L.call('zs_rvq_commit_drop', 'ZsRvqCommitDrop', st, stage=s, **dict(commit, **drop))
             head = s * self.acc.stride(0) * 2                    # this stage's (used | bad) words, in int32 elements
             L.call('zs_vq_accum', 'ZsVqAccum', st, x=rows32, idx=L.ptr(self.idx_acc[s]), n=n, ld_x=ld32, K=K, E=E, shift=self.shift,
                    cnt=L.ptr(self.cnt[s]), sum=L.ptr(self.sums[s]), bad=L.ptr(acc32, head + 1))
@@ -130,7 +183,13 @@ class RvqBottleneck(object):
                        stride=self.stride, work=L.ptr(self.rwork), restarted=L.ptr(self.stat, 3), skipped=L.ptr(self.stat, 4))
         L.call('zs_rvq_loss', 'ZsRvqLoss', st, partial=L.ptr(self.partial), S=S, scale=self.scale, loss=L.ptr(self.loss))
         q = ctx.act('rvq_q_%d_%d' % (bits.B, bits.T), bits.B, bits.T, E)
-        rvq.launch_gather(st, ctx.dt, self.idx, S, self.code_live, start, length, bits.B, bits.T, q.ptr(), q.ld, self.stat[2:])
+        if drop is None:
+            rvq.launch_gather(st, ctx.dt, self.idx, S, self.code_live, start, length, bits.B, bits.T, q.ptr(), q.ld, self.stat[2:])
+        else:
+            code = self.code_live
+            L.call('zs_rvq_gather_frag', 'ZsRvqGatherFrag', st, dtype=ctx.dt, idx=L.ptr(self.idx), n_idx=n, ld_idx=n, S=S, s_use=drop['s_use'],
+                   code=L.ptr(code), ld_code=code.stride(1), plane_code=code.stride(0), K=K, E=E, start=L.ptr(start), len=L.ptr(length),
+                   n_frag=bits.B, T=bits.T, dst=q.ptr(), ld_dst=q.ld, bad=L.ptr(self.stat, 2))
         self._bits = bits
         self.steps += 1
         return q
@@ -146,7 +205,9 @@ class RvqBottleneck(object):
     # ---- host side ---------------------------------------------------------------------------------------------------------------------
     def stats(self):
         """The last step's figures, read from the device (a synchronisation: call where the host syncs anyway): loss_vq, K, S and
-        `stages`, per stage dict(loss_vq, used, perplexity); `used` is the list of the stages' counts.  RuntimeError when a row was
+        `stages`, per stage dict(loss_vq, used, perplexity); `used` is the list of the stages' counts.  With dropout every stage also
+        has `active`, the rows that took part in it, and the result `active` (their list) and `s_use_mean`, the mean stage count of
+        the last step's samples; the rows a stage left out and the restarts skipped for them raise nothing.  RuntimeError when a row was
         left out of an average because an element reached ZS_VQ_MAX_ABS, or an index was outside [0, K)."""
         stat = self.stat.cpu().numpy()
         if stat[1]:
@@ -164,6 +225,11 @@ class RvqBottleneck(object):
                'perplexity': [st['perplexity'] for st in stages]}
         if self.restart is not None:
             out.update(restarts=int(stat[3]), skipped=int(stat[4]), dead=[int(v) for v in (self.N < self.restart).sum(1).cpu()])
+        if self.dropout is not None:
+            active = [int(v) for v in self.active.cpu()]
+            for stg, v in zip(stages, active):
+                stg['active'] = v
+            out.update(active=active, s_use_mean=(float(self.s_use.cpu().numpy().mean()) if self.s_use is not None else float(self.S)))
         return out
 
     def state_dict(self):
@@ -182,6 +248,8 @@ class RvqBottleneck(object):
         meta = {'trained_iterations': int(iteration), 'beta': self.beta, 'decay': self.decay, 'used': list(s['used'])}
         if self.restart is not None:
             meta.update(restart=self.restart, restarts=s['restarts'])
+        if self.dropout is not None:
+            meta.update(dropout=self.dropout)
         return meta
 
     def to_codebook(self, meta=None):
@@ -199,7 +267,15 @@ def check_rvq_train(args, enc_mode=None, c_in=None):
     import os
     path = getattr(args, 'rvq_train', None)
     if path is None:
+        if getattr(args, 'rvq_dropout', None) is not None:
+            if getattr(args, 'vq_train', None) is not None:
+                raise ValueError('--rvq_dropout cannot be combined with --vq_train: a vector codebook has one stage and nothing to drop; '
+                                 'it serves --rvq_train FILE.rvq.npz')
+            raise ValueError('--rvq_dropout needs --rvq_train FILE.rvq.npz: it drops stages of the residual codebook the run trains '
+                             'through')
         return None
+    if getattr(args, 'rvq_dropout', None) is not None and getattr(args, 'vq_train', None) is not None:
+        raise ValueError('--rvq_dropout cannot be combined with --vq_train: a vector codebook has one stage and nothing to drop')
     if getattr(args, 'vq_train', None) is not None:
         raise ValueError('--rvq_train cannot be combined with --vq_train: a run trains through one codebook, a residual one '
                          '(--rvq_train FILE.rvq.npz) or a vector one (--vq_train FILE.vq.npz)')
@@ -220,6 +296,8 @@ def check_rvq_train(args, enc_mode=None, c_in=None):
         check_decay(args.vq_decay)
     if getattr(args, 'vq_restart', None) is not None:
         check_restart(args.vq_restart)
+    if getattr(args, 'rvq_dropout', None) is not None:
+        check_dropout(args.rvq_dropout)
     if enc_mode is None:
         return None
     rvq.ResidualCodebook.check_mode(enc_mode, "--rvq_train needs enc_mode 'continues'")

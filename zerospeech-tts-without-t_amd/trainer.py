@@ -684,13 +684,15 @@ class Trainer(object):
     _best_due = False
 
     def __init__(self, hps, data_loader, g_mode, enc_mode, log_dir='./log/', dtype=None, device=None, ema=None, valid=None,
-                 vq_train=None):
+                 vq_train=None, rvq_dropout=None):
         """vq_train (not in the reference): None, or (vq.VectorCodebook, beta, decay): train(mode='pretrain_AE') then trains through
         that codebook (vq_train.VqBottleneck inside the AEStep), logs loss_vq, the codewords used and the perplexity, and
         writes <checkpoint>.vq.npz beside every checkpoint.  Every other mode runs without the quantiser.  A fourth element is the
         threshold below which dead codewords are restarted; the log and the file's meta then carry the restarts.
         The codebook's kind picks the bottleneck: an rvq.ResidualCodebook trains through its S stages (rvq_train.RvqBottleneck,
         DESIGN 34), the log carries every stage's share of codewords used and the file is <checkpoint>.rvq.npz.
+        rvq_dropout (not in the reference): None, or P in (0, 1]: quantiser dropout of that residual bottleneck; the log
+        then carries every stage's share of active rows.
         valid (not in the reference): None, or a validation.ValidConfig: train(mode='pretrain_AE') then validates on its set
         every `every` iterations and after the last one (ValidStep), logs and records the result and keeps the best checkpoint.
         ema (not in the reference): None, or the decay in [0, 1) of an exponential moving average of the weights that every
@@ -699,6 +701,9 @@ class Trainer(object):
         self.ema = check_ema(ema)
         self.valid = validation.check_config(valid, hps) if valid is not None else None
         self.vq_train = vq_train
+        self.rvq_dropout = rvq_dropout
+        if rvq_dropout is not None and (vq_train is None or getattr(vq_train[0], 'kind', None) != 'residual'):
+            raise ValueError('rvq_dropout needs vq_train with a residual codebook (rvq.ResidualCodebook)')
         if vq_train is not None:
             from .vq import VectorCodebook
             VectorCodebook.check_mode(enc_mode, "vq_train needs enc_mode 'continues'")
@@ -764,7 +769,8 @@ class Trainer(object):
             cb.check_width(hps.enc_size, 'vq_train')
             if cb.kind == 'residual':                   # the codebook's kind picks the bottleneck
                 from .rvq_train import RvqBottleneck as VqBottleneck
-            self.vq = VqBottleneck(cb, beta, decay, encoded_rows(hps.batch_size, hps.seg_len), layers.Ctx(dev, dt), restart=restart)
+            more = {'dropout': self.rvq_dropout} if self.rvq_dropout is not None else {}
+            self.vq = VqBottleneck(cb, beta, decay, encoded_rows(hps.batch_size, hps.seg_len), layers.Ctx(dev, dt), restart=restart, **more)
         self.clf = ClfStep(self.ae, self.SpeakerClassifier, lr=hps.lr, betas=(0.5, 0.9), max_grad_norm=hps.max_grad_norm, ema=self.ema)
         self.s2 = None                      # PatchGANStep, built on first use (its optimizer state is 2 x 53 M floats)
         self.source_loader = self.target_loader = None
@@ -1331,6 +1337,10 @@ class Trainer(object):
                                          f'{flag}/vq_perplexity_%d' % i: stg['perplexity']})
                         line = 'pre_AE:[%06d/%06d], loss_rec=%.3f, loss_vq=%.4f' + ''.join(
                             ', used%d=%%.3f, perplexity%d=%%.1f' % (i, i) for i in range(len(s['stages'])))
+                        if 'active' in s:                                                      # quantiser dropout: the rows of every stage
+                            for i, v in enumerate(s['active']):
+                                info[f'{flag}/vq_active_%d' % i] = v / float(bn.rows)
+                            line += ''.join(', active%d=%%.3f' % i for i in range(len(s['active'])))
                     else:
                         info.update({f'{flag}/pre_loss_vq': s['loss_vq'], f'{flag}/vq_used': s['used'] / float(s['K']),
                                      f'{flag}/vq_perplexity': s['perplexity']})
