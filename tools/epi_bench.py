@@ -40,6 +40,7 @@ c3 = conv(2 * C, C, 3, split2=True)
 X, Y, Y2, D, R = act('x', B, T, C), act('y', B, T, C), act('y2', B, T, C), act('d', B, T, C), act('r', B, T, C)
 Y3 = act('y3', B, T, 3 * C)
 X64, YA, S = act('x64', B, 64, C), act('ya', B, 64, 2 * C), act('s', B, 128, C)
+X16, YA16, S16 = act('x16', B, 16, C), act('ya16', B, 16, 2 * C), act('s16', B, 32, C)      # conv1: 128 tiles, the ring kernel
 emb = torch.randn(102, C, device=dev)
 idx = torch.randint(0, 102, (B,), device=dev)
 cs = torch.zeros(B, C, device=dev)
@@ -50,9 +51,14 @@ CASES = {
     'plain  N3072 (GRU input projection)': (lambda: lin3.fwd(X, out=Y3), 6.0 * B * T * C * C),
     'split2 conv k3 1024->2048 T64 + out2 shuffled + emb': (lambda: c3.fwd(X64, out=YA, act=L.ZS_ACT_LRELU, slope=0.01, out2=S, vec2=emb, idx=idx,
                                                                               store_mode2=L.ZS_STORE_SPLIT2), 2.0 * B * 64 * 2 * C * C * 3),
+    'split2 conv k3 1024->2048 T64, one output': (lambda: c3.fwd(X64, out=YA, act=L.ZS_ACT_LRELU, slope=0.01), 2.0 * B * 64 * 2 * C * C * 3),
+    'ring   split2 conv k3 1024->2048 T16 + out2 shuffled + emb': (lambda: c3.fwd(X16, out=YA16, act=L.ZS_ACT_LRELU, slope=0.01, out2=S16, vec2=emb, idx=idx,
+                                                                                     store_mode2=L.ZS_STORE_SPLIT2), 2.0 * B * 16 * 2 * C * C * 3),
+    'ring   split2 conv k3 1024->2048 T16, one output': (lambda: c3.fwd(X16, out=YA16, act=L.ZS_ACT_LRELU, slope=0.01), 2.0 * B * 16 * 2 * C * C * 3),
     'dgrad  plain': (lambda: lin.dgrad(Y, T, D), 2.0 * B * T * C * C),
     'dgrad  * lrelu\'(dact)': (lambda: lin.dgrad(Y, T, D, dact_src=X, slope=0.01), 2.0 * B * T * C * C),
     'dgrad  + add_src': (lambda: lin.dgrad(Y, T, D, add_src=R), 2.0 * B * T * C * C),
+    'dgrad  dact + add': (lambda: lin.dgrad(Y, T, D, dact_src=X, slope=0.01, add_src=R), 2.0 * B * T * C * C),
     'dgrad  mask + colsum': (lambda: lin.dgrad(Y, T, D, dact_src=X, slope=0.01, colsum=col), 2.0 * B * T * C * C),
     'dgrad  add + colsum': (lambda: lin.dgrad(Y, T, D, add_src=R, colsum=col), 2.0 * B * T * C * C),
 }
@@ -80,4 +86,4 @@ for r in range(a.rounds):
 for k, (fn, fl) in CASES.items():
     if res[k]:
         t = min(res[k])
-        print('%-56s %7.1f us  %6.0f TFLOP/s   (rounds: %s)' % (k, t * 1e3, fl / t / 1e9, ' '.join('%.1f' % (x * 1e3) for x in res[k])))
+        print('%-62s %7.1f us  %6.0f TFLOP/s   (rounds: %s)' % (k, t * 1e3, fl / t / 1e9, ' '.join('%.1f' % (x * 1e3) for x in res[k])))

@@ -924,8 +924,20 @@ __host__ __device__ __forceinline__ bool p8_regs_epilogue_ok(const ZsGemmConv& p
 // accumulators in registers and the WHOLE tile is staged as bf16 (132 KiB), so the finish is a deeply unrolled LDS -> global copy
 // with 16-byte accesses that also applies what needs a second operand (lrelu' mask of dact_src, add_src; all of a thread's loads
 // in flight at once) and the pixel-shuffle row mapping.  out2 (= value + vec2[idx[b]]) is staged and copied the same way from
-// the values still in registers; colsum (per-sample column sums: the nn.Embedding part of the backward) reads the staged tile.
-// HAS2 (out2 given) is a template parameter so that without it the accumulators die at the first staging (registers for the copy).
+// its bf16 values, formed at the first staging and kept packed in registers; colsum (per-sample column sums: the nn.Embedding
+// part of the backward) reads the staged tile.  No thread issues a global load after its first global store.
+// HAS2 (out2 given) is a template parameter: without it nothing but the staged tile survives the first staging.
+// -DZS_EPI2_PROFILE (diagnostic build, tools/epi2_profile.py): waves 0 and 4 of every workgroup stamp the phases of the register
+// epilogue with the cycle counter and add them to zs_epi2_prof[wave group][slot]: 0 first staging, 1 its barrier, 2 colsum and
+// copy-out of `out` (issue, with the second-operand loads and waits), 3 barrier, 4 second staging, 5 barrier, 6 copy-out of out2
+// (issue), 7 drain (the wait for every store of the wave, which the product build does not have), 8 workgroups
+#ifdef ZS_EPI2_PROFILE
+__device__ unsigned long long zs_epi2_prof[2][12];
+#define ZS_EPT(k) { __builtin_amdgcn_sched_barrier(0); const long long pt1_ = __builtin_readcyclecounter(); pc[k] += pt1_ - pt0; pt0 = pt1_; \
+                    __builtin_amdgcn_sched_barrier(0); }
+#else
+#define ZS_EPT(k)
+#endif
 template <bool HAS2>
 __device__ __forceinline__ void p8_regs_epilogue(const ZsGemmConv& p, f32x4_m (&c)[2][2][4][2], unsigned char* smem, int M, int m0, int n0,
                                                  int tid, int lane, int wr, int wc, int g) {
@@ -934,16 +946,59 @@ __device__ __forceinline__ void p8_regs_epilogue(const ZsGemmConv& p, f32x4_m (&
   const int colb = wc * 64 + (lane & 15);
   const int rbase = wr * 128 + 4 * (lane >> 4);
   const int half = p.N >> 1;
+#ifdef ZS_EPI2_PROFILE
+  long long pc[8], pt0 = __builtin_readcyclecounter();
+#pragma unroll
+  for (int i = 0; i < 8; ++i) pc[i] = 0;
+#endif
   // sample (row of pre_vec / vec2) of each 16-row block of this wave: T_out is a multiple of 16 when they are given
   int64_t bsel[2][4];
   const bool need_b = p.pre_vec != nullptr || p.vec2 != nullptr;
 #pragma unroll
   for (int mq = 0; mq < 2; ++mq)
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      const int mb = m0 + wr * 128 + mq * 64 + mt * 16;
-      bsel[mq][mt] = (need_b && mb < M) ? p.vec_idx[mb / p.T_out] : 0;
+    for (int mt = 0; mt < 4; ++mt) bsel[mq][mt] = 0;
+  if (need_b) {                                     // eight loads in flight, not eight round trips (a block past M reads the last sample's)
+    int64_t bi[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) bi[q] = p.vec_idx[min(m0 + wr * 128 + q * 16, M - 1) / p.T_out];
+    __builtin_amdgcn_sched_barrier(0);              // (hipcc otherwise waits for each index where it loads it)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) bsel[q >> 2][q & 3] = m0 + wr * 128 + q * 16 < M ? bi[q] : 0;
+  }
+  // HAS2: the vec2 values of all four (nq, nt) groups are fetched here, before the first global store of the wave (a load issued
+  // behind a store waits for the store's round trip), and out2's bf16 values are formed beside out's, packed two per register:
+  // the accumulators die at the first staging and the second staging is LDS writes only, under which the stores of `out` drain
+  constexpr int H2 = HAS2 ? 2 : 1;
+  unsigned o2[H2][H2][2][4][2];                                     // [nq][nt][mq][mt][i4 >> 1]: bf16 of i4 = 0|2 low, 1|3 high
+  float eva[H2 * H2][2][4];                                         // vec2 of every (nq, nt) group: 32 loads in flight at once
+  if constexpr (HAS2) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int mq = 0; mq < 2; ++mq)
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) eva[q][mq][mt] = 0.f;
+    if (p.vec2 != nullptr) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {                                 // a lane past N reads column N - 1 (no branch per lane)
+        const int nn = n0 + colb + q * 16;
+        const int nc = min(nn, p.N - 1);
+        const int ocv = p.store_mode2 == ZS_STORE_SPLIT2 ? (nc >= half ? nc - half : nc) : nc;
+#pragma unroll
+        for (int mq = 0; mq < 2; ++mq)
+#pragma unroll
+          for (int mt = 0; mt < 4; ++mt) eva[q][mq][mt] = p.vec2[bsel[mq][mt] * p.vec2_ld + ocv];
+      }
     }
+  }
+  float bva[4];                                                     // the bias of every group, requested at once as well
+#pragma unroll
+  for (int q = 0; q < 4; ++q) bva[q] = 0.f;
+  if (p.bias != nullptr) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bva[q] = p.bias[(int64_t)g * p.bias_gstride + min(n0 + colb + q * 16, p.N - 1)];
+  }
 #pragma unroll
   for (int nq = 0; nq < 2; ++nq)
 #pragma unroll
@@ -951,7 +1006,7 @@ __device__ __forceinline__ void p8_regs_epilogue(const ZsGemmConv& p, f32x4_m (&
       const int col = colb + nq * 32 + nt * 16;
       const int n = n0 + col;
       const bool cval = n < p.N;
-      const float bv = (p.bias != nullptr && cval) ? p.bias[(int64_t)g * p.bias_gstride + n] : 0.f;
+      const float bv = cval ? bva[nq * 2 + nt] : 0.f;
       float pv[2][4];
 #pragma unroll
       for (int mq = 0; mq < 2; ++mq)
@@ -963,6 +1018,13 @@ __device__ __forceinline__ void p8_regs_epilogue(const ZsGemmConv& p, f32x4_m (&
 #pragma unroll
           for (int mt = 0; mt < 4; ++mt) pv[mq][mt] += p.pre_vec[bsel[mq][mt] * p.pre_vec_ld + n];
       }
+      float ev[2][4];
+      if constexpr (HAS2) {
+#pragma unroll
+        for (int mq = 0; mq < 2; ++mq)
+#pragma unroll
+          for (int mt = 0; mt < 4; ++mt) ev[mq][mt] = cval ? eva[nq * 2 + nt][mq][mt] : 0.f;
+      }
 #pragma unroll
       for (int mq = 0; mq < 2; ++mq)
 #pragma unroll
@@ -972,11 +1034,23 @@ __device__ __forceinline__ void p8_regs_epilogue(const ZsGemmConv& p, f32x4_m (&
             float v = c[mq][nq][mt][nt][i4] + pv[mq][mt];
             if (p.act == ZS_ACT_LRELU) v = lrelu_f(v, p.slope);
             if (!cval) v = 0.f;                                     // columns [N, out_cols) are written as zeros
-            if constexpr (HAS2) c[mq][nq][mt][nt][i4] = v;
             sT[(rbase + mq * 64 + mt * 16 + i4) * PT + col] = f2bf(v);
+            if constexpr (HAS2) {
+              const unsigned h = (unsigned)f2bf(v + ev[mq][mt]);
+              if (i4 & 1) {
+                o2[nq][nt][mq][mt][i4 >> 1] |= h << 16;
+                // pins the packed pair here: left to itself hipcc sinks v + ev down to the second staging and keeps the
+                // fp32 values (in scratch) until then
+                asm volatile("" : "+v"(o2[nq][nt][mq][mt][i4 >> 1]));
+              } else {
+                o2[nq][nt][mq][mt][i4 >> 1] = h;
+              }
+            }
           }
     }
+  ZS_EPT(0)
   __syncthreads();
+  ZS_EPT(1)
 
   const bool cs_post = !HAS2 && p.colsum != nullptr && p.colsum_post && (p.dact_src != nullptr || p.add_src != nullptr);
   auto colsum_pass = [&]() {
@@ -1027,82 +1101,84 @@ __device__ __forceinline__ void p8_regs_epilogue(const ZsGemmConv& p, f32x4_m (&
       const bf16_t* dsrc = (const bf16_t*)p.dact_src;
       const bf16_t* asrc = (const bf16_t*)p.add_src;
       const bool tail = n + 8 > p.N;                               // the group reaches into the zero columns [N, out_cols)
-#pragma unroll 1
-      for (int it0 = 0; it0 < 16; it0 += 8) {
-        Raw8<bf16_t> rd[8], ra[8];
-        uint4 w[8];
+      // all 16 rows' second operands are requested before the first store (a load behind a store of its wave waits for the
+      // store's round trip; the accumulators are dead here, so the registers are free); the staged rows are read 8 at a time
+      Raw8<bf16_t> rd[16], ra[16];
+      if (dsrc) {
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int row = r0 + 16 * (it0 + u);
-          const int m = min(m0 + row, M - 1);
-          if (dsrc) rd[u].ld(dsrc + (int64_t)m * p.dact_ld + n);
-          if (asrc) ra[u].ld(asrc + (int64_t)m * p.add_ld + n);
-          w[u] = *reinterpret_cast<const uint4*>(sT + row * PT + c8);
-        }
+        for (int u = 0; u < 16; ++u) rd[u].ld(dsrc + (int64_t)min(m0 + r0 + 16 * u, M - 1) * p.dact_ld + n);
+      }
+      if (asrc) {
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int row = r0 + 16 * (it0 + u);
-          const int m = m0 + row;
-          if (m < M) {
-            float v[8], y[8];
-            Raw8<bf16_t> rw; rw.a = w[u]; rw.cvt(v);
-            if (dsrc) {
-              rd[u].cvt(y);
+        for (int u = 0; u < 16; ++u) ra[u].ld(asrc + (int64_t)min(m0 + r0 + 16 * u, M - 1) * p.add_ld + n);
+      }
+      // FULL (every row of the tile is below M; all but the last row tile): the stores are unconditional, so hipcc counts them and
+      // a row's wait for its operand stays a counted wait above the stores in flight; behind `if (m < M)` it has to take the
+      // path without stores as possible and waits each row for one memory operation more, from the 8th row on for stores
+      auto rows = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
 #pragma unroll
-              for (int j = 0; j < 8; ++j) v[j] *= dlrelu_f(y[j], p.slope);
+        for (int it0 = 0; it0 < 16; it0 += 8) {
+          uint4 w[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) w[u] = *reinterpret_cast<const uint4*>(sT + (r0 + 16 * (it0 + u)) * PT + c8);
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+            const int row = r0 + 16 * (it0 + u);
+            const int m = m0 + row;
+            if (FULL || m < M) {
+              float v[8], y[8];
+              Raw8<bf16_t> rw; rw.a = w[u]; rw.cvt(v);
+              if (dsrc) {
+                rd[it0 + u].cvt(y);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] *= dlrelu_f(y[j], p.slope);
+              }
+              if (asrc) {
+                ra[it0 + u].cvt(y);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] += y[j];
+              }
+              if (tail) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) if (n + j >= p.N) v[j] = 0.f;
+              }
+              const int64_t orow = sp ? 2 * (int64_t)m + hi : (int64_t)m;
+              store8<bf16_t>(outp + orow * p.ldc + oc, v);
+              if (cs_post) store8<bf16_t>(sT + row * PT + c8, v);   // the stored value back into the staging tile (own slot)
             }
-            if (asrc) {
-              ra[u].cvt(y);
-#pragma unroll
-              for (int j = 0; j < 8; ++j) v[j] += y[j];
-            }
-            if (tail) {
-#pragma unroll
-              for (int j = 0; j < 8; ++j) if (n + j >= p.N) v[j] = 0.f;
-            }
-            const int64_t orow = sp ? 2 * (int64_t)m + hi : (int64_t)m;
-            store8<bf16_t>(outp + orow * p.ldc + oc, v);
-            if (cs_post) store8<bf16_t>(sT + row * PT + c8, v);     // the stored value back into the staging tile (own slot)
           }
         }
-      }
+      };
+      if (m0 + PBM <= M) rows(std::true_type{});
+      else rows(std::false_type{});
     }
   }
+  ZS_EPT(2)
   if (cs_post) {                                                    // column sums of the STORED values (colsum_post)
     __syncthreads();
     colsum_pass();
   }
   if constexpr (HAS2) {
     __syncthreads();                                                // every thread is done with the first staging
+    ZS_EPT(3)
     const bool sp = p.store_mode2 == ZS_STORE_SPLIT2;
 #pragma unroll
     for (int nq = 0; nq < 2; ++nq)
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt) {
         const int col = colb + nq * 32 + nt * 16;
-        const int nn = n0 + col;
-        const bool cval = nn < p.N;
-        const int ocv = sp ? (nn >= half ? nn - half : nn) : nn;
-        float ev[2][4];
-#pragma unroll
-        for (int mq = 0; mq < 2; ++mq)
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) ev[mq][mt] = 0.f;
-        if (p.vec2 != nullptr && cval) {
-#pragma unroll
-          for (int mq = 0; mq < 2; ++mq)
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) ev[mq][mt] = p.vec2[bsel[mq][mt] * p.vec2_ld + ocv];
-        }
 #pragma unroll
         for (int mq = 0; mq < 2; ++mq)
 #pragma unroll
           for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
             for (int i4 = 0; i4 < 4; ++i4)
-              sT[(rbase + mq * 64 + mt * 16 + i4) * PT + col] = f2bf(c[mq][nq][mt][nt][i4] + ev[mq][mt]);
+              sT[(rbase + mq * 64 + mt * 16 + i4) * PT + col] = (unsigned short)(o2[nq][nt][mq][mt][i4 >> 1] >> (16 * (i4 & 1)));
       }
+    ZS_EPT(4)
     __syncthreads();
+    ZS_EPT(5)
     unsigned short* outp = (unsigned short*)p.out2;
     const int hi = sp ? (n >= half) : 0;
     const int oc = n - hi * half;
@@ -1120,6 +1196,16 @@ __device__ __forceinline__ void p8_regs_epilogue(const ZsGemmConv& p, f32x4_m (&
       }
     }
   }
+#ifdef ZS_EPI2_PROFILE
+  ZS_EPT(6)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  ZS_EPT(7)
+  if (lane == 0 && (tid >> 6 & 3) == 0) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) atomicAdd(&zs_epi2_prof[wr][i], (unsigned long long)pc[i]);
+    atomicAdd(&zs_epi2_prof[wr][8], 1ull);
+  }
+#endif
 }
 
 template <typename T>
@@ -2508,6 +2594,19 @@ extern "C" int zs_wgp8_profile_read(unsigned long long* out, int reset) {
   if (reset) {
     unsigned long long z[48] = {0};
     if (hipMemcpyToSymbol(HIP_SYMBOL(zs_wgp8_prof), z, sizeof(z)) != hipSuccess) return 1;
+  }
+  return 0;
+}
+#endif
+
+#ifdef ZS_EPI2_PROFILE
+// diagnostic build only: copies out (and optionally clears) the stamps of p8_regs_epilogue, [wave group][slot]
+extern "C" int zs_epi2_profile_read(unsigned long long* out, int reset) {
+  if (hipDeviceSynchronize() != hipSuccess) return 1;
+  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(zs_epi2_prof), sizeof(unsigned long long) * 24) != hipSuccess) return 1;
+  if (reset) {
+    unsigned long long z[24] = {0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(zs_epi2_prof), z, sizeof(z)) != hipSuccess) return 1;
   }
   return 0;
 }
