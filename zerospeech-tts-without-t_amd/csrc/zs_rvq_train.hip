@@ -2,14 +2,18 @@
 // straight-through quantiser leaves over, with everything the step wants of it in the same pass (zs_rvq_commit), the commitment loss of
 // the S stages from its partial sums (zs_rvq_loss) and the gradient (zs_rvq_st_bwd).  All three are memory-bound; the search, the
 // fixed-point sums, the codebook's average and the restart of every stage are zs_vq_assign, zs_vq_accum, zs_vq_ema and zs_vq_restart,
-// unchanged.  Nothing here adds floats atomically, so a step is bitwise reproducible.
+// unchanged.  Nothing here adds floats atomically, so a step is bitwise reproducible.  zs_rvq_commit_drop (include/zs_amd_rvq_drop.h,
+// DESIGN 37), the commit of a step under quantiser dropout, is the same kernel and the same host checks with DROP set.
 //   rvq_commit_kernel   rvq_residual_kernel's layout: a row is owned by a team of 2^t <= 64 lanes of one wave, four columns per lane
 //                       and round.  A lane reads its piece of x, of the one codeword row and (behind the first stage) of a, and
 //                       writes its piece of r, of a and of the fp32 copy: every operand crosses the memory system once.  The row's
 //                       magnitude check is an OR over the team by shuffles, as in vq_commit_kernel, and so is the tree of the doubles.
+//                       One text for both entry points: zs_rvq_commit_drop with every count at S is zs_rvq_commit by construction.
 //   rvq_loss_kernel     one workgroup: the [S][ZS_VQ_COMMIT_PARTS] partials in a fixed order.
 //   rvq_st_bwd_kernel   one lane per 16-byte piece of dz, grid-stride.
-#include "zs_common.h"
+// The row accesses and the teams' launch arithmetic are zs_quant.h's.
+#include "zs_quant.h"
+#include "../../include/zs_amd_rvq_drop.h"
 
 // the definitions are stated operation by operation (a rounding each): nothing in this file may be fused into a multiply-add
 #pragma clang fp contract(off)
@@ -18,47 +22,13 @@ namespace {
 
 constexpr int RT_NT = 256;
 
-// four columns c .. c + 3 of a row as fp32; those at or above E read nothing and are zero
-template <typename S> __device__ __forceinline__ void rt_load4(const S* row, int c, int E, bool vec, float (&v)[4]);
-template <> __device__ __forceinline__ void rt_load4<float>(const float* row, int c, int E, bool vec, float (&v)[4]) {
-  v[0] = v[1] = v[2] = v[3] = 0.f;
-  if (vec && c + 4 <= E) {
-    const float4 a = *reinterpret_cast<const float4*>(row + c);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (c + i < E) v[i] = row[c + i];
-}
-template <> __device__ __forceinline__ void rt_load4<bf16_t>(const bf16_t* row, int c, int E, bool vec, float (&v)[4]) {
-  v[0] = v[1] = v[2] = v[3] = 0.f;
-  if (vec && c + 4 <= E) {
-    const uint2 a = *reinterpret_cast<const uint2*>(row + c);
-    v[0] = __uint_as_float(a.x << 16); v[1] = __uint_as_float(a.x & 0xffff0000u);
-    v[2] = __uint_as_float(a.y << 16); v[3] = __uint_as_float(a.y & 0xffff0000u);
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (c + i < E) v[i] = bf2f(row[c + i]);
-}
-// the columns below E of c .. c + 3 of an fp32 row
-__device__ __forceinline__ void rt_store4(float* row, int c, int E, bool vec, const float (&v)[4]) {
-  if (vec && c + 4 <= E) {
-    *reinterpret_cast<float4*>(row + c) = make_float4(v[0], v[1], v[2], v[3]);
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (c + i < E) row[c + i] = v[i];
-}
-
 struct RtVec { int x, code, r, xf, a; };                          // which operands take 16-byte (x bf16: 8-byte) accesses
 
 // ---- commit ------------------------------------------------------------------------------------------------------------------------
-template <typename S> __global__ void __launch_bounds__(RT_NT)
-rvq_commit_kernel(const ZsRvqCommit p, const int tl, const int groups, const RtVec vec) {
+// DROP (zs_rvq_commit_drop, P = ZsRvqCommitDrop): only the rows of samples that still use stage p.stage take part (`act`).  Whether a
+// row does is a property of its fragment, so of the whole team: the trip counts and the shuffles do not depend on it.
+template <typename S, bool DROP, typename P> __global__ void __launch_bounds__(RT_NT)
+rvq_commit_kernel(const P p, const int tl, const int groups, const RtVec vec) {
   __shared__ double s_part[RT_NT / 64];
   const int tid = threadIdx.x, tlane = tid & (tl - 1);
   const int64_t n_teams = (int64_t)gridDim.x * (RT_NT / tl);
@@ -70,8 +40,10 @@ rvq_commit_kernel(const ZsRvqCommit p, const int tl, const int groups, const RtV
   for (int64_t rd = 0; rd < rounds; ++rd) {
     const int64_t row = team + rd * n_teams;
     const bool live = row < p.n;
-    const int k = live ? p.idx[row] : 0;
-    const bool ok = live && k >= 0 && k < p.K;                      // else never an index: the row passes unsubtracted
+    bool act = live;                                                // the fragment's count decides for the whole team (a row has one
+    if constexpr (DROP) act = live && p.stage < p.s_use[(int)row / p.rows_per_frag];        // fragment): the loop below runs either way
+    const int k = act ? p.idx[row] : 0;
+    const bool ok = act && k >= 0 && k < p.K;                       // else never an index: the row passes unsubtracted
     int big = 0;
     if (live) {
       const S* xr = x + row * p.ld_x;
@@ -81,16 +53,16 @@ rvq_commit_kernel(const ZsRvqCommit p, const int tl, const int groups, const RtV
       for (int g = tlane; g < groups; g += tl) {
         const int c = 4 * g;
         float xv[4], rv[4], av[4] = {0.f, 0.f, 0.f, 0.f};
-        rt_load4<S>(xr, c, p.E, vec.x != 0, xv);
+        q_load4<S>(xr, c, p.E, vec.x != 0, xv);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          big |= !(fabsf(xv[j]) < (float)ZS_VQ_MAX_ABS);            // (NaN: not below; the columns at or above E are zero)
+          big |= (!DROP || act) && !(fabsf(xv[j]) < (float)ZS_VQ_MAX_ABS);     // (NaN: not below; the columns at or above E are zero)
           rv[j] = xv[j];
         }
         if (ok) {
           float cv[4];
-          rt_load4<float>(cr, c, p.E, vec.code != 0, cv);
-          if (!p.first) rt_load4<float>(ar, c, p.E, vec.a != 0, av);
+          q_load4<float>(cr, c, p.E, vec.code != 0, cv);
+          if (!p.first) q_load4<float>(ar, c, p.E, vec.a != 0, av);
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             rv[j] = xv[j] - cv[j];                                  // one IEEE subtraction
@@ -98,14 +70,14 @@ rvq_commit_kernel(const ZsRvqCommit p, const int tl, const int groups, const RtV
             av[j] = p.first ? rv[j] : av[j] + rv[j];                // one fp32 add
           }
         }
-        rt_store4(rr, c, p.E, vec.r != 0, rv);
-        if (p.x_f32) rt_store4(p.x_f32 + row * p.ld_xf, c, p.E, vec.xf != 0, xv);
-        if (ok || p.first) rt_store4(ar, c, p.E, vec.a != 0, av);   // (a bad row: zero at the first stage, as it is behind it)
+        q_store4(rr, c, p.E, vec.r != 0, rv);                       // (a row that takes no part: the fp32 value of x)
+        if (p.x_f32) q_store4(p.x_f32 + row * p.ld_xf, c, p.E, vec.xf != 0, xv);
+        if (ok || ((!DROP || act) && p.first)) q_store4(ar, c, p.E, vec.a != 0, av);   // (a bad row: zero at the first stage, as behind it)
       }
     }
-    for (int o = 1; o < tl; o <<= 1) big |= __shfl_xor(big, o, 64);  // over the team
+    for (int o = 1; o < tl; o <<= 1) big |= __shfl_xor(big, o, 64);  // over the team; every lane of the wave is here
     if (live && tlane == 0) {
-      bad += !ok;
+      bad += (!DROP || act) && !ok;
       over += big;
       p.idx_acc[row] = (ok && !big) ? k : -1;
     }
@@ -167,8 +139,8 @@ template <typename T> __global__ void __launch_bounds__(RT_NT) rvq_st_bwd_kernel
       float dv[8], lo[4], hi[4] = {0.f, 0.f, 0.f, 0.f};
       rt_load_piece<T>(dq + row * p.ld_dq + c, dv);               // (dq is 16-byte aligned at a pitch of whole pieces)
       const float* ar = p.a + row * p.ld_a;
-      rt_load4<float>(ar, c, p.E, avec != 0, lo);
-      if (PER == 8) rt_load4<float>(ar, c + 4, p.E, avec != 0, hi);
+      q_load4<float>(ar, c, p.E, avec != 0, lo);
+      if (PER == 8) q_load4<float>(ar, c + 4, p.E, avec != 0, hi);
 #pragma unroll
       for (int j = 0; j < PER; ++j) {
         const float t = p.g * (j < 4 ? lo[j & 3] : hi[j & 3]);      // two fp32 operations, a rounding each (contract off)
@@ -182,53 +154,65 @@ template <typename T> __global__ void __launch_bounds__(RT_NT) rvq_st_bwd_kernel
   }
 }
 
-inline bool misaligned(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; }
-
 const char* rt_shape(int E, int64_t n) {
   if (E < 1 || E > ZS_CODE_MAX_E) return "E must be in [1, 1024]";
   if (n < 0 || n > 0x7fffffff) return "n must be in [0, 2^31)";
   return nullptr;
 }
 
-}  // namespace
-
-extern "C" int zs_rvq_commit(const ZsRvqCommit* p, void* stream) {
-  ZS_REQUIRE(p, "zs_rvq_commit: null argument");
+// zs_rvq_commit (P = ZsRvqCommit) and zs_rvq_commit_drop (DROP, P = ZsRvqCommitDrop): the checks, the teams and the launch
+template <bool DROP, typename P> int commit_launch(const P* p, void* stream, const char* name) {
+  ZS_REQUIRE(p, "%s: null argument", name);
   const char* why = rt_shape(p->E, p->n);
   if (!why && (p->K < 1 || p->K > ZS_CODE_MAX_K)) why = "K must be in [1, 65536]";
   if (!why && (p->ld_x < p->E || p->ld_code < p->E || p->ld_r < p->E || p->ld_a < p->E || (p->x_f32 && p->ld_xf < p->E)))
     why = "a leading dimension is below E";
-  ZS_REQUIRE(!why, "zs_rvq_commit: %s (n %lld, K %d, E %d, ld_x %lld, ld_code %lld, ld_r %lld, ld_xf %lld, ld_a %lld)", why, (long long)p->n,
+  ZS_REQUIRE(!why, "%s: %s (n %lld, K %d, E %d, ld_x %lld, ld_code %lld, ld_r %lld, ld_xf %lld, ld_a %lld)", name, why, (long long)p->n,
              p->K, p->E, (long long)p->ld_x, (long long)p->ld_code, (long long)p->ld_r, (long long)p->ld_xf, (long long)p->ld_a);
-  ZS_REQUIRE(p->dtype == ZS_F32 || p->dtype == ZS_BF16, "zs_rvq_commit: bad dtype");
+  ZS_REQUIRE(p->dtype == ZS_F32 || p->dtype == ZS_BF16, "%s: bad dtype", name);
+  const void* s_use = nullptr;                                    // DROP: an operand like the others
+  if constexpr (DROP) {
+    ZS_REQUIRE(p->rows_per_frag >= 1 && p->stage >= 0 && p->stage < ZS_RVQ_MAX_S && (p->first != 0) == (p->stage == 0),
+               "%s: rows_per_frag must be >= 1, stage in [0, %d) and first set at stage 0 alone (got %d, stage %d, first %d)", name,
+               ZS_RVQ_MAX_S, p->rows_per_frag, p->stage, p->first);
+    s_use = p->s_use;
+  }
   if (p->n == 0) return ZS_OK;
-  ZS_REQUIRE(p->x && p->idx && p->code && p->r && p->idx_acc && p->a && p->partial && p->bad && p->over, "zs_rvq_commit: null operand");
+  ZS_REQUIRE(p->x && p->idx && p->code && p->r && p->idx_acc && p->a && p->partial && p->bad && p->over && (!DROP || s_use),
+             "%s: null operand", name);
   const bool f32 = p->src_f32 || p->dtype == ZS_F32;
   ZS_REQUIRE(!misaligned(p->x, f32 ? 4 : 2) && !misaligned(p->idx, 4) && !misaligned(p->code, 4) && !misaligned(p->r, 4) &&
                  !misaligned(p->x_f32, 4) && !misaligned(p->idx_acc, 4) && !misaligned(p->a, 4) && !misaligned(p->partial, 8) &&
-                 !misaligned(p->bad, 4) && !misaligned(p->over, 4), "zs_rvq_commit: an operand is not aligned to its element");
+                 !misaligned(p->bad, 4) && !misaligned(p->over, 4) && !misaligned(s_use, 4),
+             "%s: an operand is not aligned to its element", name);
   const void* xv = p->x;
   ZS_REQUIRE(p->r != xv && p->a != xv && p->x_f32 != xv && p->r != p->a && p->r != p->x_f32 && p->a != p->x_f32,
-             "zs_rvq_commit: r, x_f32 and a must not be x or each other");
-  ZS_REQUIRE(p->idx_acc != p->idx, "zs_rvq_commit: idx_acc must not be idx");
+             "%s: r, x_f32 and a must not be x or each other", name);
+  ZS_REQUIRE(p->idx_acc != p->idx && (!DROP || p->idx_acc != s_use), "%s: idx_acc must not be idx%s", name, DROP ? " or s_use" : "");
   RtVec vec;
   vec.x = !misaligned(p->x, f32 ? 16 : 8) && p->ld_x % 4 == 0;
   vec.code = !misaligned(p->code, 16) && p->ld_code % 4 == 0;
   vec.r = !misaligned(p->r, 16) && p->ld_r % 4 == 0;
   vec.xf = p->x_f32 && !misaligned(p->x_f32, 16) && p->ld_xf % 4 == 0;
   vec.a = !misaligned(p->a, 16) && p->ld_a % 4 == 0;
-  const int groups = (p->E + 3) / 4;
-  int tl = 1;
-  while (tl < groups && tl < 64) tl <<= 1;
-  const int64_t per_wg = RT_NT / tl;
-  int64_t wgs = (p->n + per_wg - 1) / per_wg;
-  wgs = wgs > ZS_VQ_COMMIT_PARTS ? ZS_VQ_COMMIT_PARTS : wgs;       // the rows beyond are strided over
+  const int groups = (p->E + 3) / 4, tl = team_lanes(groups);
+  const dim3 grid(team_wgs(p->n, tl, RT_NT, ZS_VQ_COMMIT_PARTS));
   const hipStream_t st = (hipStream_t)stream;
   if (f32)
-    hipLaunchKernelGGL(rvq_commit_kernel<float>, dim3((unsigned)wgs), dim3(RT_NT), 0, st, *p, tl, groups, vec);
+    hipLaunchKernelGGL((rvq_commit_kernel<float, DROP, P>), grid, dim3(RT_NT), 0, st, *p, tl, groups, vec);
   else
-    hipLaunchKernelGGL(rvq_commit_kernel<bf16_t>, dim3((unsigned)wgs), dim3(RT_NT), 0, st, *p, tl, groups, vec);
-  return zs_check_launch("zs_rvq_commit");
+    hipLaunchKernelGGL((rvq_commit_kernel<bf16_t, DROP, P>), grid, dim3(RT_NT), 0, st, *p, tl, groups, vec);
+  return zs_check_launch(name);
+}
+
+}  // namespace
+
+extern "C" int zs_rvq_commit(const ZsRvqCommit* p, void* stream) {
+  return commit_launch<false>(p, stream, "zs_rvq_commit");
+}
+
+extern "C" int zs_rvq_commit_drop(const ZsRvqCommitDrop* p, void* stream) {
+  return commit_launch<true>(p, stream, "zs_rvq_commit_drop");
 }
 
 extern "C" int zs_rvq_loss(const ZsRvqLoss* p, void* stream) {

@@ -19,8 +19,11 @@
 //                      a slice of the rows, lists the rows of its codewords per round and adds their quantised columns with LDS
 //                      atomics; the non-zero sums go to memory with one 64-bit atomic each.
 //   vq_update_kernel   one workgroup per codeword.
-//   vq_gather_kernel   one lane per 16-byte piece of the operand, as units_unpack_kernel.
-#include "zs_common.h"
+//   vq_gather_kernel   one lane per 16-byte piece of the operand, as units_unpack_kernel (the piece store is zs_quant.h's).
+#include "zs_quant.h"
+
+// nothing in this file is defined a rounding at a time: the scores and the norms contract as the compiler sees fit
+#pragma clang fp contract(fast)
 
 namespace {
 
@@ -310,12 +313,6 @@ __global__ void __launch_bounds__(VQ_NT) vq_update_kernel(const ZsVqUpdate p, co
 }
 
 // ---- gather ------------------------------------------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ void vq_store_piece(T* p, const float (&v)[8]);
-template <> __device__ __forceinline__ void vq_store_piece<float>(float* p, const float (&v)[8]) {
-  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
-template <> __device__ __forceinline__ void vq_store_piece<bf16_t>(bf16_t* p, const float (&v)[8]) { store8<bf16_t>(p, v); }
-
 template <typename T> __global__ void __launch_bounds__(VQ_NT) vq_gather_kernel(const ZsVqGather p) {
   constexpr int PER = 16 / (int)sizeof(T);                        // columns of a 16-byte piece
   const int groups = (int)(p.ld_dst / PER);
@@ -341,13 +338,11 @@ template <typename T> __global__ void __launch_bounds__(VQ_NT) vq_gather_kernel(
             if (PER * g + j < p.E) v[j] = cw[PER * g + j];
         }
       }
-      vq_store_piece<T>(dst + (int64_t)t * p.ld_dst + PER * g, v);
+      q_store_piece<T>(dst + (int64_t)t * p.ld_dst + PER * g, v);
     }
   }
   if (bad) atomicAdd(p.bad, bad);
 }
-
-inline bool misaligned(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; }
 
 const char* vq_shape(int K, int E, int64_t n, int64_t ld_a, int64_t ld_b) {
   if (K < 1 || K > ZS_CODE_MAX_K) return "K must be in [1, 65536]";

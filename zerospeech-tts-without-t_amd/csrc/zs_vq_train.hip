@@ -10,7 +10,9 @@
 //   vq_ema_kernel       one workgroup per codeword, as vq_update_kernel (the same order of the norm's sum).
 //   vq_restart_*        zs_vq_restart: one workgroup ranks the dead codewords, then one workgroup per dead codeword copies
 //                       an encoder row over it, as vq_ema_kernel is laid out.
-#include "zs_common.h"
+// The piece store, the hash of the restart's draw and the teams' launch arithmetic are zs_quant.h's; vt_load and vt_load_code stay here
+// (their early return for a piece at or above E is part of vq_commit_kernel's and vq_st_bwd_kernel's instruction streams).
+#include "zs_quant.h"
 
 // the definitions are stated operation by operation (a rounding each): nothing in this file may be fused into a multiply-add
 #pragma clang fp contract(off)
@@ -65,13 +67,6 @@ template <int PER> __device__ __forceinline__ void vt_load_code(const float* row
     if (c + i < E) v[i] = row[c + i];
 }
 
-// one 16-byte piece of an operand of T
-template <typename T> __device__ __forceinline__ void vt_store(T* p, const float (&v)[8]);
-template <> __device__ __forceinline__ void vt_store<float>(float* p, const float (&v)[8]) {
-  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
-template <> __device__ __forceinline__ void vt_store<bf16_t>(bf16_t* p, const float (&v)[8]) { store8<bf16_t>(p, v); }
-
 // ---- commit ------------------------------------------------------------------------------------------------------------------------
 template <typename T> __global__ void __launch_bounds__(VT_NT)
 vq_commit_kernel(const ZsVqCommit p, const int tl, const int groups, const int zvec, const int cvec, const int fvec) {
@@ -110,7 +105,7 @@ vq_commit_kernel(const ZsVqCommit p, const int tl, const int groups, const int z
         }
 #pragma unroll
         for (int j = 0; j < PER; ++j) big |= !(fabsf(zv[j]) < (float)ZS_VQ_MAX_ABS);        // (NaN: not below)
-        vt_store<T>(q + row * p.ld_q + c, qv);
+        q_store_piece<T>(q + row * p.ld_q + c, qv);
         if (p.z_f32 && c < p.E) {
           float* fr = p.z_f32 + row * p.ld_zf + c;
           if (fvec && c + PER <= p.E) {
@@ -185,7 +180,7 @@ vq_st_bwd_kernel(const ZsVqStBwd p, const int groups, const int zvec, const int 
         }
       }
     }
-    vt_store<T>(dz + row * p.ld_dz + c, out);
+    q_store_piece<T>(dz + row * p.ld_dz + c, out);
   }
   if (bad) atomicAdd(p.bad, bad);
 }
@@ -268,13 +263,6 @@ __global__ void __launch_bounds__(VT_NT) vq_restart_rank_kernel(const ZsVqRestar
   if (tid == VT_NT - 1) p.work[p.K] = rank;                       // (the last lane's rank behind its own words: all of them)
 }
 
-__device__ __forceinline__ uint64_t vr_mix64(uint64_t z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-
 // One workgroup per dead codeword, laid out as vq_ema_kernel (the same order of the norm's sum).
 __global__ void __launch_bounds__(VT_NT) vq_restart_copy_kernel(const ZsVqRestart p) {
   __shared__ double s_part[VT_NT / 64];
@@ -282,7 +270,7 @@ __global__ void __launch_bounds__(VT_NT) vq_restart_copy_kernel(const ZsVqRestar
   const int dead = p.work[p.K];
   if ((int)blockIdx.x >= dead) return;                            // the usual case: nothing is written
   const uint64_t n = (uint64_t)p.n;
-  const uint64_t start = vr_mix64(p.seed + (p.seed_ptr ? *p.seed_ptr : 0ull) + 0x5651524553544152ull) % n;
+  const uint64_t start = q_mix64(p.seed + (p.seed_ptr ? *p.seed_ptr : 0ull) + 0x5651524553544152ull) % n;
   for (int j = blockIdx.x; j < dead; j += gridDim.x) {
     const int k = p.work[j];
     const int64_t r = (int64_t)((start + ((uint64_t)j % n) * (uint64_t)p.stride) % n);
@@ -312,8 +300,6 @@ __global__ void __launch_bounds__(VT_NT) vq_restart_copy_kernel(const ZsVqRestar
   }
 }
 
-inline bool misaligned(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; }
-
 const char* vt_shape(int K, int E, int64_t n, int64_t ld_a, int64_t ld_b, int64_t ld_c) {
   if (K < 1 || K > ZS_CODE_MAX_K) return "K must be in [1, 65536]";
   if (E < 1 || E > ZS_CODE_MAX_E) return "E must be in [1, 1024]";
@@ -341,20 +327,16 @@ extern "C" int zs_vq_commit(const ZsVqCommit* p, void* stream) {
                  !misaligned(p->over, 4), "zs_vq_commit: an operand is misaligned (q: 16 bytes)");
   ZS_REQUIRE(!p->idx_acc || p->idx_acc != p->idx, "zs_vq_commit: idx_acc must not be idx");
   const int per = 16 / (int)es;
-  const int groups = (int)(p->ld_q / per);
-  int tl = 1;
-  while (tl < 64 && tl < groups) tl <<= 1;
+  const int groups = (int)(p->ld_q / per), tl = team_lanes(groups);
   const int zvec = !misaligned(p->z, 16) && p->ld_z % per == 0;
   const int cvec = !misaligned(p->code, 16) && p->ld_code % 4 == 0;
   const int fvec = p->z_f32 && !misaligned(p->z_f32, 16) && p->ld_zf % 4 == 0;
-  const int64_t per_wg = VT_NT / tl;
-  int64_t wgs = (p->n + per_wg - 1) / per_wg;
-  wgs = wgs > ZS_VQ_COMMIT_PARTS ? ZS_VQ_COMMIT_PARTS : wgs;
+  const unsigned wgs = team_wgs(p->n, tl, VT_NT, ZS_VQ_COMMIT_PARTS);
   const hipStream_t st = (hipStream_t)stream;
   if (p->dtype == ZS_F32)
-    hipLaunchKernelGGL(vq_commit_kernel<float>, dim3((unsigned)wgs), dim3(VT_NT), 0, st, *p, tl, groups, zvec, cvec, fvec);
+    hipLaunchKernelGGL(vq_commit_kernel<float>, dim3(wgs), dim3(VT_NT), 0, st, *p, tl, groups, zvec, cvec, fvec);
   else
-    hipLaunchKernelGGL(vq_commit_kernel<bf16_t>, dim3((unsigned)wgs), dim3(VT_NT), 0, st, *p, tl, groups, zvec, cvec, fvec);
+    hipLaunchKernelGGL(vq_commit_kernel<bf16_t>, dim3(wgs), dim3(VT_NT), 0, st, *p, tl, groups, zvec, cvec, fvec);
   if (p->loss) hipLaunchKernelGGL(vq_commit_finish_kernel, dim3(1), dim3(VT_NT), 0, st, p->partial, (int)wgs, p->scale, p->loss);
   return zs_check_launch("zs_vq_commit");
 }

@@ -14,15 +14,17 @@ Quantiser dropout (`--rvq_dropout P`): with probability P a sample of
 1 .. S, drawn on the device from the step's own seed stream (zs_rvq_drop_draw); the stages at or above s_b neither commit that
 sample's rows nor count them (zs_rvq_commit_drop in place of zs_rvq_commit) and the Decoder reads the sum of its first s_b codewords
 (zs_rvq_gather_frag in place of zs_rvq_gather), so every coarser bitrate --rvq_stages s offers is a trained operating point.
-csrc/zs_rvq_drop.hip, include/zs_amd_rvq_drop.h; tests/rvq_drop_ref.py is the numpy definition.  Without it nothing new is launched."""
+include/zs_amd_rvq_drop.h; the draw is csrc/zs_rvq_drop.hip, the other two are the commit's and the gather's own kernels with the mask
+compiled in; tests/rvq_drop_ref.py is the numpy definition.  Without it nothing new is launched.
+What this class shares with vq_train.VqBottleneck is vq_train.Bottleneck."""
 import numpy as np
 import torch
 
 from . import _lib as L
 from . import rvq, vq
-from .vq_train import BETA, DECAY, MAX_ABS, PARTS, check_beta, check_decay, check_restart, perplexity, restart_stride
+from .vq_train import (BETA, DECAY, GOLDEN, MAX_ABS, PARTS, Bottleneck, check_beta, check_decay, check_restart,  # noqa: F401
+                       check_train_flags, load_for, perplexity, restart_stride)
 
-GOLDEN = 0x9E3779B97F4A7C15        # stage s restarts with the seed (seed + s GOLDEN) mod 2^64
 DROP_ONE = 1 << 24                 # zs_rvq_drop_draw compares 24 bits of the draw with floor(P 2^24)
 
 
@@ -44,11 +46,12 @@ def drop_threshold(p):
     return int(np.floor(float(p) * DROP_ONE))
 
 
-class RvqBottleneck(object):
+class RvqBottleneck(Bottleneck):
     """The device state (per stage code, cnorm, N, m) and the plan's buffers of the S-stage quantiser for `rows` encoder rows per
     step: vq_train.VqBottleneck's interface.  codebook: the rvq.ResidualCodebook the run starts from (code = vectors, N = 1,
     m = code); ctx: a layers.Ctx (device, compute dtype and the buffer of q)."""
-    kind = 'residual'
+    kind, flag, ckpt_suffix = 'residual', '--rvq_train', '.rvq.npz'
+    over_text = "%s: %d rows of a stage held a value of magnitude >= %g (or not finite) and were left out of that stage's average"
 
     dropout = None
 
@@ -58,48 +61,19 @@ class RvqBottleneck(object):
         sample is decoded from a number of stages drawn uniformly from 1 .. S instead of all S."""
         if not isinstance(codebook, rvq.ResidualCodebook):
             raise ValueError('RvqBottleneck: a residual codebook (rvq.ResidualCodebook) is needed')
-        self.beta, self.decay = check_beta(beta), check_decay(decay)
-        self.rows = int(rows)
-        if not 1 <= self.rows < 2 ** 31:
-            raise ValueError('RvqBottleneck: rows must be in [1, 2^31) (got %d)' % self.rows)
-        self.ctx, self.base = ctx, codebook
-        self.S, self.K, self.E = codebook.S, codebook.K, codebook.E
-        dev = self.device = ctx.device
-        S, K, E, n = self.S, self.K, self.E, self.rows
-        self.shift = vq.vq_shift(n, MAX_ABS)                     # one host constant: a row above MAX_ABS is left out in every stage
-        self.scale = self.beta / (float(n) * E)                  # loss_vq = scale * sum_s sum r_{s+1}^2
-        self.g = float(np.float32(2.0 * self.beta / (float(n) * E)))
+        self.S = codebook.S
+        super(RvqBottleneck, self).__init__(codebook, beta, decay, rows, ctx, restart, stages=self.S)
+        S, E, n, dev = self.S, self.E, self.rows, self.device
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
-        # the state: what the last step left (`code`, `cnorm` are the `next` copies the averages write)
-        self.code = torch.from_numpy(codebook.vectors).to(dev).contiguous()          # [S, K, E]
-        self.cnorm = torch.from_numpy(codebook.cnorm).to(dev).contiguous()           # [S, K]
-        self.N = torch.ones(S, K, **f32)
-        self.m = self.code.clone()
-        # the live copies: what this step's assigns, commits and gather read
-        self.code_live, self.cnorm_live = self.code.clone(), self.cnorm.clone()
-        self.idx = torch.zeros(S, n, **i32)                      # the planes zs_rvq_gather reads
-        self.idx_acc = torch.zeros(S, n, **i32)
-        # zeroed at the head of every step, per stage: (used | accum's own bad count) | cnt int32 [K] | sum int64 [K][E]
-        self._cnt_at = 1
-        self._sum_at = 1 + (K + 1) // 2
-        self.acc = torch.zeros(S, self._sum_at + K * E, dtype=torch.int64, device=dev)
-        self.cnt = [self.acc[s, self._cnt_at:self._sum_at].view(torch.int32)[:K] for s in range(S)]
-        self.sums = [self.acc[s, self._sum_at:].view(K, E) for s in range(S)]
-        self.partial = torch.zeros(S, PARTS, dtype=torch.float64, device=dev)
         self.loss = torch.zeros(1 + S, **f32)                    # loss_vq of the last step, then every stage's share of it
         # sticky: bad idx (commit) | rows above MAX_ABS | bad frames (gather) | codewords restarted so far | restarts skipped
         self.stat = torch.zeros(5, **i32)
-        self.work = vq.workspace(dev) if n < vq.SPLIT_N else None
         # two fp32 [n, E] buffers in ping-pong: stage s reads r_s in one and writes r_{s+1} to the other; the fp32 copy of bf16
         # rows is the first one's first content.  zs_vq_accum, the average and the restart of stage s read r_s behind the commit
         # of stage s and in front of the commit of stage s + 1, which overwrites it: stream order keeps that safe.
         self.res = [torch.zeros(n, E, **f32), torch.zeros(n, E, **f32)]
         self.a = torch.zeros(n, E, **f32)                        # r_1 + .. + r_S, what the backward reads
-        self.restart = None if restart is None else check_restart(restart)
-        if self.restart is not None:
-            self.stride = restart_stride(n)                      # a host constant of the plan
-            self.rwork = torch.zeros(K + 2, **i32)
         self._frag = {}                                          # (B, T') -> the device table of zs_rvq_gather
         self.dropout = None if dropout is None else check_dropout(dropout, 'RvqBottleneck: dropout')
         if self.dropout is not None:
@@ -107,8 +81,6 @@ class RvqBottleneck(object):
             self.active = torch.zeros(S, **i32)                  # rows that took part in stage s in the last step
             self._s_use = {}                                     # B -> the stage count of every sample, int32 [B]
             self.s_use = None                                    # the one the last forward wrote
-        self.steps = 0
-        self._bits = None
 
     def _table(self, B, T):
         """start[b] = b T', len[b] = T': the batch as the B fragments of zs_rvq_gather (built once per shape, before any capture)."""
@@ -133,16 +105,13 @@ class RvqBottleneck(object):
         follow it.  With dropout the step's stage counts are drawn from the same pair first, every commit is zs_rvq_commit_drop and
         the gather zs_rvq_gather_frag."""
         ctx, S, K, E, n = self.ctx, self.S, self.K, self.E, self.rows
-        if bits.rows != n or bits.C != E or bits.t.dtype != ctx.tdt:
-            raise ValueError('RvqBottleneck: built for %d rows of %d columns of %s, got %d rows of %d of %s' %
-                             (n, E, ctx.tdt, bits.rows, bits.C, bits.t.dtype))
+        self._check_forward(bits)
         st = ctx.stream
         start, length = self._table(bits.B, bits.T)
         self.code_live.copy_(self.code)                          # the codebooks the step before left
         self.cnorm_live.copy_(self.cnorm)
         self.acc.zero_()
         wide = ctx.tdt != torch.float32                          # the rows need an fp32 copy for zs_vq_accum
-        acc32 = self.acc.view(torch.int32)
         drop = None
         if self.dropout is not None:
             if bits.B * bits.T != n:
@@ -170,17 +139,7 @@ class RvqBottleneck(object):
                 L.call('zs_rvq_commit', 'ZsRvqCommit', st, **commit)
             else:
                 L.call('zs_rvq_commit_drop', 'ZsRvqCommitDrop', st, stage=s, **dict(commit, **drop))
-            head = s * self.acc.stride(0) * 2                    # this stage's (used | bad) words, in int32 elements
-            L.call('zs_vq_accum', 'ZsVqAccum', st, x=rows32, idx=L.ptr(self.idx_acc[s]), n=n, ld_x=ld32, K=K, E=E, shift=self.shift,
-                   cnt=L.ptr(self.cnt[s]), sum=L.ptr(self.sums[s]), bad=L.ptr(acc32, head + 1))
-            L.call('zs_vq_ema', 'ZsVqEma', st, cnt=L.ptr(self.cnt[s]), sum=L.ptr(self.sums[s]), K=K, E=E, shift=self.shift,
-                   decay=self.decay, N=L.ptr(self.N[s]), m=L.ptr(self.m[s]), code=L.ptr(self.code[s]), ld_code=E,
-                   cnorm=L.ptr(self.cnorm[s]), used=L.ptr(acc32, head))
-            if self.restart is not None:
-                L.call('zs_vq_restart', 'ZsVqRestart', st, thresh=self.restart, x=rows32, n=n, ld_x=ld32, idx_acc=L.ptr(self.idx_acc[s]),
-                       cnt=L.ptr(self.cnt[s]), K=K, E=E, N=L.ptr(self.N[s]), m=L.ptr(self.m[s]), code=L.ptr(self.code[s]), ld_code=E,
-                       cnorm=L.ptr(self.cnorm[s]), seed=(int(seed or 0) + s * GOLDEN) % (1 << 64), seed_ptr=seed_ptr,
-                       stride=self.stride, work=L.ptr(self.rwork), restarted=L.ptr(self.stat, 3), skipped=L.ptr(self.stat, 4))
+            self._average(s, rows32, ld32, seed, seed_ptr)
         L.call('zs_rvq_loss', 'ZsRvqLoss', st, partial=L.ptr(self.partial), S=S, scale=self.scale, loss=L.ptr(self.loss))
         q = ctx.act('rvq_q_%d_%d' % (bits.B, bits.T), bits.B, bits.T, E)
         if drop is None:
@@ -196,8 +155,7 @@ class RvqBottleneck(object):
 
     def backward(self, dbits):
         """dbits: the Act [B, T', E] the Decoder's backward returns (d loss / d q).  Returns d loss / d z, written in place."""
-        if self._bits is None or dbits.rows != self.rows or dbits.C != self.E:
-            raise ValueError('RvqBottleneck.backward: no forward of %d rows before it' % dbits.rows)
+        self._check_backward(dbits)
         L.call('zs_rvq_st_bwd', 'ZsRvqStBwd', self.ctx.stream, dtype=self.ctx.dt, dq=dbits.ptr(), n=self.rows, ld_dq=dbits.ld,
                a=L.ptr(self.a), ld_a=self.E, E=self.E, g=self.g, dz=dbits.ptr(), ld_dz=dbits.ld)
         return dbits
@@ -209,12 +167,7 @@ class RvqBottleneck(object):
         has `active`, the rows that took part in it, and the result `active` (their list) and `s_use_mean`, the mean stage count of
         the last step's samples; the rows a stage left out and the restarts skipped for them raise nothing.  RuntimeError when a row was
         left out of an average because an element reached ZS_VQ_MAX_ABS, or an index was outside [0, K)."""
-        stat = self.stat.cpu().numpy()
-        if stat[1]:
-            raise RuntimeError('--rvq_train: %d rows of a stage held a value of magnitude >= %g (or not finite) and were left out of '
-                               "that stage's average" % (int(stat[1]), MAX_ABS))
-        if stat[0] or stat[2]:
-            raise RuntimeError('--rvq_train: zs_vq_assign gave %d indices outside [0, %d)' % (int(stat[0]) + int(stat[2]), self.K))
+        stat = self._checked_stat()
         head = self.acc[:, :self._sum_at].cpu().numpy()
         loss = self.loss.cpu().numpy()
         stages = []
@@ -232,31 +185,12 @@ class RvqBottleneck(object):
             out.update(active=active, s_use_mean=(float(self.s_use.cpu().numpy().mean()) if self.s_use is not None else float(self.S)))
         return out
 
-    def state_dict(self):
-        return {'code': self.code, 'cnorm': self.cnorm, 'N': self.N, 'm': self.m}
-
-    def load_state_dict(self, sd):
-        for k in ('code', 'cnorm', 'N', 'm'):
-            dst, src = getattr(self, k), torch.as_tensor(sd[k])
-            if tuple(src.shape) != tuple(dst.shape):
-                raise ValueError('RvqBottleneck: state %r has shape %s, this bottleneck %s' % (k, tuple(src.shape), tuple(dst.shape)))
-        for k in ('code', 'cnorm', 'N', 'm'):
-            getattr(self, k).copy_(torch.as_tensor(sd[k]).to(torch.float32))
-
     def ckpt_meta(self, iteration, s):
         """The meta fields of <checkpoint>.rvq.npz after `iteration` iterations; s: stats()."""
-        meta = {'trained_iterations': int(iteration), 'beta': self.beta, 'decay': self.decay, 'used': list(s['used'])}
-        if self.restart is not None:
-            meta.update(restart=self.restart, restarts=s['restarts'])
+        meta = super(RvqBottleneck, self).ckpt_meta(iteration, dict(s, used=list(s['used'])))
         if self.dropout is not None:
             meta.update(dropout=self.dropout)
         return meta
-
-    def to_codebook(self, meta=None):
-        """The codebooks as the last step left them: an rvq.ResidualCodebook whose meta is the starting file's plus `meta`."""
-        out = dict(self.base.meta)
-        out.update(meta or {})
-        return rvq.ResidualCodebook(self.code.cpu().numpy(), out)
 
 
 def check_rvq_train(args, enc_mode=None, c_in=None):
@@ -264,7 +198,6 @@ def check_rvq_train(args, enc_mode=None, c_in=None):
     the flag combinations) and again once enc_mode and the Decoder's width are known: then the file is read, and the loaded
     ResidualCodebook returned (None without --rvq_train).  --vq_beta, --vq_decay and --vq_restart serve --vq_train or --rvq_train;
     without either, vq_train.check_vq_train refuses them."""
-    import os
     path = getattr(args, 'rvq_train', None)
     if path is None:
         if getattr(args, 'rvq_dropout', None) is not None:
@@ -279,32 +212,13 @@ def check_rvq_train(args, enc_mode=None, c_in=None):
     if getattr(args, 'vq_train', None) is not None:
         raise ValueError('--rvq_train cannot be combined with --vq_train: a run trains through one codebook, a residual one '
                          '(--rvq_train FILE.rvq.npz) or a vector one (--vq_train FILE.vq.npz)')
-    others = [f for f in ('train', 'train_p', 'train_tgat', 'train_c') if getattr(args, f, False)]
-    if others or not getattr(args, 'train_ae', False):
-        raise ValueError('--rvq_train trains the autoencoder through its residual codebook: it needs --train_ae and no other --train* '
-                         'mode' + (' (got --%s)' % others[0] if others else ''))
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        raise ValueError("--rvq_train runs on one GPU: every stage's counts and sums would need an all-reduce (WORLD_SIZE = %s)"
-                         % os.environ['WORLD_SIZE'])
-    if getattr(args, 'resume', False):
-        raise ValueError('--rvq_train cannot be combined with --resume: the train-state file does not carry the codebooks')
-    if getattr(args, 'valid_every', None) is not None:
-        raise ValueError('--rvq_train cannot be combined with --valid_every: the validation step does not quantise')
-    if getattr(args, 'vq_beta', None) is not None:
-        check_beta(args.vq_beta)
-    if getattr(args, 'vq_decay', None) is not None:
-        check_decay(args.vq_decay)
-    if getattr(args, 'vq_restart', None) is not None:
-        check_restart(args.vq_restart)
+    check_train_flags(args, '--rvq_train', 'residual codebook', "every stage's", 'codebooks')
     if getattr(args, 'rvq_dropout', None) is not None:
         check_dropout(args.rvq_dropout)
     if enc_mode is None:
         return None
     rvq.ResidualCodebook.check_mode(enc_mode, "--rvq_train needs enc_mode 'continues'")
-    try:
-        cb = vq.load_codebook(path, enc_mode, E=c_in)
-    except ValueError as e:
-        raise ValueError('--rvq_train: %s' % e)
+    cb = load_for('--rvq_train', path, enc_mode, c_in)
     if cb.kind != 'residual':
         raise ValueError("--rvq_train: %s is no residual codebook (kind %r): --rvq_train takes FILE.rvq.npz, as --fit_codebook K "
                          '--rvq S writes it; a vector codebook goes to --vq_train' % (path, cb.kind))
@@ -313,4 +227,4 @@ def check_rvq_train(args, enc_mode=None, c_in=None):
 
 def ckpt_path(checkpoint):
     """<checkpoint name>.rvq.npz: the residual codebook beside a checkpoint."""
-    return checkpoint + '.rvq.npz'
+    return checkpoint + RvqBottleneck.ckpt_suffix

@@ -763,14 +763,13 @@ class Trainer(object):
         self.TargetClassifier = TargetClassifier(ns=ns, n_class=3, seg_len=hps.seg_len, dtype=dt).to(dev)
         self.ae = AEStep(self.Encoder, self.Decoder, lr=hps.lr, betas=(0.5, 0.9), max_grad_norm=hps.max_grad_norm, ema=self.ema)
         if self.vq_train is not None:                   # the --train_ae loop alone: train() hands it to the AEStep for that mode
-            from .vq_train import VqBottleneck, encoded_rows
+            from .vq_train import Bottleneck, encoded_rows
             cb, beta, decay = self.vq_train[:3]
             restart = self.vq_train[3] if len(self.vq_train) > 3 else None      # the threshold of zs_vq_restart
             cb.check_width(hps.enc_size, 'vq_train')
-            if cb.kind == 'residual':                   # the codebook's kind picks the bottleneck
-                from .rvq_train import RvqBottleneck as VqBottleneck
             more = {'dropout': self.rvq_dropout} if self.rvq_dropout is not None else {}
-            self.vq = VqBottleneck(cb, beta, decay, encoded_rows(hps.batch_size, hps.seg_len), layers.Ctx(dev, dt), restart=restart, **more)
+            bottleneck = Bottleneck.of_kind(cb.kind)    # the codebook's kind picks the bottleneck
+            self.vq = bottleneck(cb, beta, decay, encoded_rows(hps.batch_size, hps.seg_len), layers.Ctx(dev, dt), restart=restart, **more)
         self.clf = ClfStep(self.ae, self.SpeakerClassifier, lr=hps.lr, betas=(0.5, 0.9), max_grad_norm=hps.max_grad_norm, ema=self.ema)
         self.s2 = None                      # PatchGANStep, built on first use (its optimizer state is 2 x 53 M floats)
         self.source_loader = self.target_loader = None
@@ -1358,14 +1357,10 @@ class Trainer(object):
                 """<checkpoint>.vq.npz (.rvq.npz) beside the checkpoint: the file --codebook reads (the codebook's own save, format
                 unchanged)."""
                 s = bn.stats()
-                bn.to_codebook(bn.ckpt_meta(iteration, s)).save(ckpt_path(path))
+                bn.to_codebook(bn.ckpt_meta(iteration, s)).save(path + bn.ckpt_suffix)
 
             bn = self.vq
             if bn is not None:
-                if bn.kind == 'residual':
-                    from .rvq_train import ckpt_path
-                else:
-                    from .vq_train import ckpt_path
                 if resumable or vcfg is not None or parallel.multi_rank():
                     raise ValueError('vq_train cannot be combined with resume, validation or several ranks')
                 self.ae.vq = bn
