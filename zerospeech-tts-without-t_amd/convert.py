@@ -775,8 +775,11 @@ _NO_UNITS = "enc_mode 'continues' has no units: its encodings are real-valued an
 
 class _Units(object):
     """What conversion does with units under a codebook of one kind (the codebook's units() hands one out per batch or folder run):
-    the three points of a batch of _enqueue_encode (plan, operand, finish), the encodings _assemble returns, and what the folder
-    drivers read, speak and write.  _BitUnits, _VectorUnits and _ResidualUnits answer the same calls."""
+    the three points of a batch of _enqueue_encode (plan, operand, finish), the encodings _assemble returns, what _synth_batch
+    speaks (check_rows, after_upload), and what the folder drivers read, speak and write.  decoder_over(dec, buf) is the one place
+    where a kind builds the Decoder's operand over a batch's utterance-ordered device buffer in its own layout: it returns the
+    fn(tab, B, T0, ch, lens_p) -> (bits, x_dec) that _enqueue_synth calls per chunk.  _BitUnits, _VectorUnits and _ResidualUnits
+    answer the same calls."""
 
     keep_units = False                            # finish leaves the utterance-ordered device buffer of the units in q.units_dev
     segment = None                                # lambda of --segment: finish chooses the batch's paths (zs_amd.segment), not its argmins
@@ -786,6 +789,14 @@ class _Units(object):
 
     def check_speakable(self, enc_mode):
         pass
+
+    def after_upload(self, dec, rows_dev):
+        """Behind the one H2D copy of check_rows' arrays: (decoder_over them, the pinned indices and distance of a snap or None, None)."""
+        return self.decoder_over(dec, rows_dev), None, None
+
+    def speak(self, units, trainer, seg_len, speakers, **kw):
+        """A batch of what read_unit_file reads, spoken: _synth_batch with this kind (kw: its keywords)."""
+        return _synth_batch(self, units, trainer, seg_len, speakers, **kw)
 
     def spoken_stem(self, stem):
         """The stem of the wav a unit file of that stem speaks as."""
@@ -808,6 +819,48 @@ class _BitUnits(_Units):
     under a bit codebook."""
     packs = True                                  # the batch's units are bit-packed: a bit codebook implies pack
     unit_glob = '*.txt'
+    who = 'synth_units_batch'
+    packed_rows = want_idx = True                 # speak takes packed rows and returns the indices of a snap; synth_units_batch: as asked
+
+    def check_rows(self, units, trainer):
+        """The utterances as packed rows (uint8 [U_i, (E + 7) // 8]), checked on the host: ValueError for a width other than E, a value
+        other than 0 / 1 (packed: a bit set above column E) and an utterance of fewer than 2 units; then the codebook's own checks."""
+        E = int(trainer.Decoder.c_in)
+        row_bytes = (E + 7) // 8
+        out = []
+        for i, u in enumerate(units):
+            a = np.asarray(u.cpu() if torch.is_tensor(u) else u)
+            if self.packed_rows:
+                if a.dtype != np.uint8 or a.ndim != 2 or a.shape[1] != row_bytes:
+                    raise ValueError("utterance %d: packed units must be uint8 [U, %d] for the Decoder's %d columns (got %s %s)" %
+                                     (i, row_bytes, E, a.dtype, a.shape))
+                if E % 8 and (a[:, -1] >> (E % 8)).any():
+                    raise ValueError('utterance %d: packed units have a bit set above column %d' % (i, E))
+            else:
+                if a.ndim != 2 or a.shape[1] != E:
+                    raise ValueError("utterance %d: units must be [U, %d], the Decoder's input width (got shape %s)" % (i, E, a.shape))
+                try:
+                    a = pack_units(a)
+                except ValueError:
+                    raise ValueError('utterance %d: units must be 0 or 1' % i)
+            if a.shape[0] < 2:
+                raise ValueError('utterance %d has fewer than 2 units (the Decoder needs two rows; the one-unit files written for inputs '
+                                 'shorter than MIN_LEN frames were decoded from two units and cannot be reproduced)' % i)
+            out.append(np.ascontiguousarray(a))
+        if self.cb is not None:
+            _check_codebook(self.cb, trainer)
+        return out
+
+    def after_upload(self, dec, packed_dev):
+        """The one buffer snapped once, in place, before the first chunk."""
+        idx_h = total_h = None
+        if self.cb is not None:
+            idx_h, total_h = _snap_units(self.cb, packed_dev, packed_dev.device, to_host=self.want_idx)
+        return self.decoder_over(dec, packed_dev), idx_h, total_h
+
+    def decoder_over(self, dec, packed_dev):
+        """Over packed rows, uint8 [units, row_bytes]: zs_units_unpack writes each chunk's Decoder operand."""
+        return lambda tab, B, T0, ch, lens_p: dec.forward_units(packed_dev, tab[0], tab[1], B, T0, ch, lengths=lens_p)
 
     def plan(self, q, chunks, decoding, want_packed):
         """Before the chunk loop: the chunk-local tables the Decoder's operands are packed by."""
@@ -858,9 +911,6 @@ class _BitUnits(_Units):
     def read_unit_file(self, path, E):
         return pack_units(read_units(path, E))
 
-    def speak(self, units, trainer, seg_len, speakers, **kw):
-        return synth_units_batch(units, trainer, seg_len, speakers, packed=True, codebook=self.cb, want_idx=self.cb is not None, **kw)
-
     def spoken(self, res, units):
         """(the indices spoken per utterance, the summed distance) of a batch speak() has finished (res) from `units`."""
         return res[2], res[3]
@@ -893,6 +943,31 @@ class _VectorUnits(_Units):
     and the unit files are <name>.idx.txt."""
     packs = False
     unit_glob = '*.idx.txt'
+    who = 'synth_index_batch'
+
+    def check_rows(self, idx_lists, trainer):
+        """The utterances of synth_index_batch as contiguous int32 arrays, checked on the host: ValueError for a shape or dtype other
+        than the kind's, fewer than 2 rows and an index outside [0, K)."""
+        rows = []
+        for i, seq in enumerate(idx_lists):
+            a = np.asarray(seq.cpu() if torch.is_tensor(seq) else seq)
+            self._check_shape(i, a, rows)
+            if a.shape[0] < 2:
+                raise ValueError('utterance %d has fewer than 2 indices (the Decoder needs two rows)' % i)
+            if (a < 0).any() or (a >= self.cb.K).any():
+                raise ValueError('utterance %d: an index is outside [0, K = %d)' % (i, self.cb.K))
+            rows.append(np.ascontiguousarray(a.astype(np.int32)))
+        return rows
+
+    def _check_shape(self, i, a, rows):
+        if a.ndim != 1 or a.dtype.kind not in 'iu':
+            raise ValueError('utterance %d: indices must be a 1-D integer sequence (got %s %s)' % (i, a.dtype, a.shape))
+
+    def decoder_over(self, dec, idx_dev):
+        """Over indices, int32 [units]: zs_vq_gather writes each chunk's Decoder operand from the codewords."""
+        code_d, _ = self.cb.to(idx_dev.device)
+        bad = torch.zeros(1, dtype=torch.int32, device=idx_dev.device)
+        return lambda tab, B, T0, ch, lens_p: dec.forward_indices(idx_dev, code_d, tab[0], tab[1], B, T0, ch, bad, lengths=lens_p)
 
     def plan(self, q, chunks, decoding, want_packed):
         """Before the chunk loop: the codebook and the workspace on the device, and where the returned units will lie."""
@@ -910,32 +985,36 @@ class _VectorUnits(_Units):
             self.base, self.xn = 0, []
 
     def operand(self, ci, chunk, Tm, enc, act, dec, dev):
-        """Behind the encoder's launches of chunk ci: zs_vq_assign over the chunk's rows, read in place from the engine's output.
-        Returns rows(ch, lens_p) for _decode_chunk: zs_vq_gather builds the Decoder's operand from the chunk's own indices.
+        """Behind the encoder's launches of chunk ci: the kind's _assign over the chunk's rows, read in place from the engine's output.
+        Returns rows(ch, lens_p) for _decode_chunk: the kind's gather builds the Decoder's operand from the chunk's own indices.
         segment: zs_vq_scores in its place, into the chunk's rows of the batch's score buffer (and the rows' squared norms, for the
         distance of the path); nothing is decoded."""
-        from .vq import launch_assign, launch_scores
         bits = enc._last_bits
         Tp = int(bits.T)
         if Tp != _t8(Tm) or int(bits.B) != len(chunk):
             raise L.ZsError('conversion chunk %d: %d x %d encoded frames where the plan has %d x %d' % (ci, bits.B, Tp, len(chunk), _t8(Tm)))
+        st, dt, n = torch.cuda.current_stream(dev).cuda_stream, enc._zs['ctx'].dt, len(chunk) * Tp
         if self.segment is not None:
-            n, K = len(chunk) * Tp, self.cb.K
-            launch_scores(torch.cuda.current_stream(dev).cuda_stream, enc._zs['ctx'].dt, bits.ptr(), n, bits.ld, self.code, self.cnorm,
-                          L.ptr(self.scores, self.base * K), K)
+            from .vq import launch_scores
+            launch_scores(st, dt, bits.ptr(), n, bits.ld, self.code, self.cnorm, L.ptr(self.scores, self.base * self.cb.K), self.cb.K)
             self.xn.append(bits.valid().float().pow(2).sum(-1).reshape(-1))
             self.base += n
             return None
-        idx_c = torch.empty(len(chunk) * Tp, dtype=torch.int32, device=dev)
-        dist_c = torch.empty(len(chunk) * Tp, dtype=torch.float32, device=dev)
-        launch_assign(torch.cuda.current_stream(dev).cuda_stream, enc._zs['ctx'].dt, bits.ptr(), len(chunk) * Tp, bits.ld, self.code,
-                      self.cnorm, idx=idx_c, dist=dist_c, work=self.work)
+        idx_c, dist_c, forward = self._assign(st, dt, bits, n, dec, dev)
         self.idx.append(idx_c)
         self.dist.append(dist_c)
         if self.dense is None:
             return None
         st_c, ln_c = self.dense[ci]
-        return lambda ch, lens_p: dec.forward_indices(idx_c, self.code, st_c, ln_c, len(chunk), Tp, ch, self.bad, lengths=lens_p)
+        return lambda ch, lens_p: forward(st_c, ln_c, len(chunk), Tp, ch, self.bad, lengths=lens_p)
+
+    def _assign(self, st, dt, bits, n, dec, dev):
+        """zs_vq_assign over the n rows of `bits`.  Returns (indices, distances, the Decoder's forward over them: zs_vq_gather)."""
+        from .vq import launch_assign
+        idx_c = torch.empty(n, dtype=torch.int32, device=dev)
+        dist_c = torch.empty(n, dtype=torch.float32, device=dev)
+        launch_assign(st, dt, bits.ptr(), n, bits.ld, self.code, self.cnorm, idx=idx_c, dist=dist_c, work=self.work)
+        return idx_c, dist_c, lambda *a, **kw: dec.forward_indices(idx_c, self.code, *a, **kw)
 
     def finish(self, q, units_dev):
         """Behind the last chunk: the chunks' indices into utterance order, then one copy.  The batch's device buffers go with it.
@@ -969,9 +1048,6 @@ class _VectorUnits(_Units):
 
     def spoken_stem(self, stem):
         return stem[:-len('.idx')]                            # <name>.idx.txt speaks as <name>.wav
-
-    def speak(self, units, trainer, seg_len, speakers, **kw):
-        return synth_index_batch(units, trainer, seg_len, speakers, self.cb, **kw)
 
     def spoken(self, res, units):
         return units, 0.0                                     # the file's own indices: nothing was snapped
@@ -1007,24 +1083,38 @@ class _ResidualUnits(_VectorUnits):
         self.stages = None if stages is None else check_stages(stages, codebook.S, '--rvq_stages')
         self.s_use = codebook.S if self.stages is None else self.stages
 
+    def _check_shape(self, i, a, rows):
+        if a.ndim != 2 or a.dtype.kind not in 'iu' or not 1 <= a.shape[1] <= self.cb.S:
+            raise ValueError('utterance %d: indices must be integers [U, 1 .. S = %d] (got %s %s)' % (i, self.cb.S, a.dtype, a.shape))
+        if rows and a.shape[1] != rows[0].shape[1]:
+            raise ValueError('utterance %d has %d indices per frame where utterance 0 has %d' % (i, a.shape[1], rows[0].shape[1]))
+
+    def after_upload(self, dec, rows_dev):
+        """The batch's rows [units, c] as c planes, every column used: decoder_over makes the transposed view contiguous."""
+        return self.decoder_over(dec, rows_dev.t()), None, None
+
+    def decoder_over(self, dec, planes):
+        """Over planes, int32 [s', units] (a strided view is copied once, behind the codebook's upload and the `bad` word):
+        zs_rvq_gather writes each chunk's Decoder operand as the sum of the s' stages' codewords."""
+        code_d, _ = self.cb.to(planes.device)
+        bad = torch.zeros(1, dtype=torch.int32, device=planes.device)
+        planes = planes.contiguous()
+        return lambda tab, B, T0, ch, lens_p: dec.forward_index_planes(planes, planes.shape[0], code_d, tab[0], tab[1], B, T0, ch, bad,
+                                                                       lengths=lens_p)
+
     def plan(self, q, chunks, decoding, want_packed):
         """_VectorUnits.plan, and the one fp32 residual buffer of the batch: the rows of its largest chunk."""
         super(_ResidualUnits, self).plan(q, chunks, decoding, want_packed)
         rows = max(len(chunk) * _t8(max(it.n for it in chunk)) for chunk, _ in chunks)
         self.resid = torch.empty(rows if self.s_use > 1 else 0, self.cb.E, dtype=torch.float32, device=q.dev)
 
-    def operand(self, ci, chunk, Tm, enc, act, dec, dev):
-        """Behind the encoder's launches of chunk ci: stage 0 is zs_vq_assign over the chunk's rows, read in place from the engine's
-        output; zs_rvq_residual writes what it leaves into the fp32 buffer, and every further stage assigns on that buffer and
-        subtracts in place.  Returns rows(ch, lens_p) for _decode_chunk: zs_rvq_gather builds the Decoder's operand from the planes."""
+    def _assign(self, st, dt, bits, n, dec, dev):
+        """Stage 0 is zs_vq_assign over the n rows of `bits`; zs_rvq_residual writes what it leaves into the fp32 buffer, and every
+        further stage assigns on that buffer and subtracts in place.  Returns (the planes, the distances behind every stage, the
+        Decoder's forward over the planes: zs_rvq_gather)."""
         from .rvq import launch_residual
         from .vq import launch_assign
-        bits = enc._last_bits
-        Tp = int(bits.T)
-        if Tp != _t8(Tm) or int(bits.B) != len(chunk):
-            raise L.ZsError('conversion chunk %d: %d x %d encoded frames where the plan has %d x %d' % (ci, bits.B, Tp, len(chunk), _t8(Tm)))
-        n, E, s_use = len(chunk) * Tp, self.cb.E, self.s_use
-        st, dt = torch.cuda.current_stream(dev).cuda_stream, enc._zs['ctx'].dt
+        E, s_use = self.cb.E, self.s_use
         idx_c = torch.empty(s_use, n, dtype=torch.int32, device=dev)
         dist_c = torch.empty(s_use, n, dtype=torch.float32, device=dev)
         launch_assign(st, dt, bits.ptr(), n, bits.ld, self.code[0], self.cnorm[0], idx=idx_c[0], dist=dist_c[0], work=self.work)
@@ -1035,12 +1125,7 @@ class _ResidualUnits(_VectorUnits):
             else:
                 launch_residual(st, L.ZS_F32, 1, r, n, E, idx_c[s - 1], self.code[s - 1], r, E, self.bad)
             launch_assign(st, L.ZS_F32, r, n, E, self.code[s], self.cnorm[s], idx=idx_c[s], dist=dist_c[s], work=self.work)
-        self.idx.append(idx_c)
-        self.dist.append(dist_c)
-        if self.dense is None:
-            return None
-        st_c, ln_c = self.dense[ci]
-        return lambda ch, lens_p: dec.forward_index_planes(idx_c, s_use, self.code, st_c, ln_c, len(chunk), Tp, ch, self.bad, lengths=lens_p)
+        return idx_c, dist_c, lambda *a, **kw: dec.forward_index_planes(idx_c, s_use, self.code, *a, **kw)
 
     def finish(self, q, units_dev):
         """Behind the last chunk: the planes into utterance order (_vq_index_map), then one copy: q.idx_host int32 [units, s'], a row per
@@ -1066,15 +1151,16 @@ class _ResidualUnits(_VectorUnits):
         return rows if self.stages is None else np.ascontiguousarray(rows[:, :self.stages])
 
     def speak(self, units, trainer, seg_len, speakers, **kw):
-        """synth_index_batch with the planes operand.  Files of different widths (no s' given: each speaks with its own columns) go
-        through it width by width, and the results come back in the order given."""
+        """Files of different widths (no s' given: each speaks with its own columns) are spoken width by width, and the results come
+        back in the order given."""
+        one = super(_ResidualUnits, self).speak
         widths = sorted({int(u.shape[1]) for u in units})
         if len(widths) == 1:
-            return synth_index_batch(units, trainer, seg_len, speakers, self.cb, **kw)
+            return one(units, trainer, seg_len, speakers, **kw)
         parts = []
         for c in widths:
             sel = [i for i, u in enumerate(units) if u.shape[1] == c]
-            parts.append((sel, synth_index_batch([units[i] for i in sel], trainer, seg_len, [speakers[i] for i in sel], self.cb, **kw)))
+            parts.append((sel, one([units[i] for i in sel], trainer, seg_len, [speakers[i] for i in sel], **kw)))
 
         def finish():
             specs, wavs = [None] * len(units), [None] * len(units)
@@ -1403,42 +1489,46 @@ def _resynth_overlap(specs, trainer, seg_len, speakers, n_iter, do_trim, noise_f
     codebook's finish makes -- and _enqueue_synth decodes the windows of unit_windows over that buffer, whose layout (q.uoffs) is
     the one _unit_tables expects.  segment: the buffer holds the units of the chosen paths (_enqueue_encode), and overlap may be 0:
     the windows are then the fragments of unit_fragments."""
-    if len(speakers) != len(specs) or not len(specs):
-        raise ValueError('resynth_batch: %d target speakers for %d utterances' % (len(speakers), len(specs)))
-    if codebook is None and trainer.enc_mode == 'continues':
-        raise ValueError("resynth_batch: overlap = %d needs units to speak from, and enc_mode 'continues' has none without a codebook"
-                         % overlap)
-    if codebook is not None:
-        _check_codebook(codebook, trainer)
-    _check_speaker_range(speakers, int(trainer.Decoder.c_a))
-    shift = 0 if enc_only else check_gen_targets(trainer, speakers)
-    counts = _unit_counts(specs, seg_len)
+    def count_units():
+        if codebook is None and trainer.enc_mode == 'continues':
+            raise ValueError("resynth_batch: overlap = %d needs units to speak from, and enc_mode 'continues' has none without a codebook"
+                             % overlap)
+        if codebook is not None:
+            _check_codebook(codebook, trainer)
+        return _unit_counts(specs, seg_len)
+    counts, shift = _speak_checks('resynth_batch', trainer, speakers, len(specs), count_units, enc_only)
     short = [u for u, n in enumerate(counts) if n < 2]
     if short:
         raise ValueError('resynth_batch: overlap = %d speaks the units an utterance returns, and utterance %d returns %d (an input '
                          'shorter than MIN_LEN = %d frames); the Decoder needs two' % (overlap, short[0], counts[short[0]], MIN_LEN))
-    dec, dev = trainer.Decoder, trainer.device
-    kind = getattr(codebook, 'kind', None)
+    side = codebook.units() if codebook is not None else _BitUnits(None)      # whose layout q.units_dev has
     q = _enqueue_encode(specs, trainer, seg_len, None, noise_fn, max_batch, dec_to_host=False, pack=codebook is None, codebook=codebook,
                         keep_units=True, segment=segment)     # (a bit codebook packs by itself and returns the units unpacked)
     if [int(n) for n in np.diff(q.uoffs)] != counts:
         raise L.ZsError('resynth_batch: the encoder left %s units where the plan has %s' % (np.diff(q.uoffs).tolist(), counts))
-    units_dev = q.units_dev
-    if kind in ('vector', 'residual'):
-        code_d, _ = codebook.to(dev)
-        bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        if kind == 'residual':                                # the planes int32 [s', units]
-            operand = lambda tab, B, T0, ch, lens_p: dec.forward_index_planes(units_dev, units_dev.shape[0], code_d, tab[0], tab[1], B, T0,
-                                                                              ch, bad, lengths=lens_p)
-        else:
-            operand = lambda tab, B, T0, ch, lens_p: dec.forward_indices(units_dev, code_d, tab[0], tab[1], B, T0, ch, bad, lengths=lens_p)
-    else:
-        operand = lambda tab, B, T0, ch, lens_p: dec.forward_units(units_dev, tab[0], tab[1], B, T0, ch, lengths=lens_p)
-    items = [it for u, n in enumerate(counts) for it in (_window_items(u, n, seg_len, overlap) if overlap else _unit_items(u, n, seg_len))]
-    chunks = _split_chunks(items, int(seg_len) // 8, max_batch)
+    operand = side.decoder_over(trainer.Decoder, q.units_dev)
+    chunks = _speak_chunks(counts, seg_len, overlap, max_batch)               # host work behind the encoder's enqueue, as it always was
     fin, _, _ = _enqueue_synth(trainer, seg_len, chunks, q.uoffs, speakers, enc_only, shift, n_iter, do_trim, momentum, False, operand,
                                overlap=overlap)
     return _finish_resynth(q, fin, defer, want_idx, unpack=(int(trainer.Encoder.enc_size) if codebook is None else None))
+
+
+def _speak_checks(who, trainer, speakers, n_utt, count_units, enc_only):
+    """The refusals of a batch spoken from units (_resynth_overlap, _synth_batch), before anything is enqueued: a speaker per
+    utterance; count_units() -> the units of each, behind the caller's own refusals, which keep their place between that check and
+    the speakers' (the Decoder's table, the generator's targets).  Returns (units per utterance, the shift of check_gen_targets or 0)."""
+    if len(speakers) != n_utt or not n_utt:
+        raise ValueError('%s: %d target speakers for %d utterances' % (who, len(speakers), n_utt))
+    counts = count_units()
+    _check_speaker_range(speakers, int(trainer.Decoder.c_a))
+    return counts, (0 if enc_only else check_gen_targets(trainer, speakers))
+
+
+def _speak_chunks(counts, seg_len, overlap, max_batch):
+    """The chunks of a batch spoken from units: each utterance cut into the windows of unit_windows (overlap > 0), which share units,
+    or the pieces of unit_fragments."""
+    items = [it for u, n in enumerate(counts) for it in (_window_items(u, n, seg_len, overlap) if overlap else _unit_items(u, n, seg_len))]
+    return _split_chunks(items, int(seg_len) // 8, max_batch)
 
 
 def _gather_decoded(q, out_rows):
@@ -1472,33 +1562,6 @@ def _finish_resynth(q, fin, defer, want_idx=False, unpack=None):
     return finish if defer else finish()
 
 
-def _check_units(units, E, packed):
-    """The utterances of synth_units_batch as packed rows (uint8 [U_i, (E + 7) // 8]), checked on the host: ValueError for a width
-    other than E, a value other than 0 / 1 (packed: a bit set above column E) and an utterance of fewer than 2 units."""
-    row_bytes = (E + 7) // 8
-    out = []
-    for i, u in enumerate(units):
-        a = np.asarray(u.cpu() if torch.is_tensor(u) else u)
-        if packed:
-            if a.dtype != np.uint8 or a.ndim != 2 or a.shape[1] != row_bytes:
-                raise ValueError("utterance %d: packed units must be uint8 [U, %d] for the Decoder's %d columns (got %s %s)" %
-                                 (i, row_bytes, E, a.dtype, a.shape))
-            if E % 8 and (a[:, -1] >> (E % 8)).any():
-                raise ValueError('utterance %d: packed units have a bit set above column %d' % (i, E))
-        else:
-            if a.ndim != 2 or a.shape[1] != E:
-                raise ValueError("utterance %d: units must be [U, %d], the Decoder's input width (got shape %s)" % (i, E, a.shape))
-            try:
-                a = pack_units(a)
-            except ValueError:
-                raise ValueError('utterance %d: units must be 0 or 1' % i)
-        if a.shape[0] < 2:
-            raise ValueError('utterance %d has fewer than 2 units (the Decoder needs two rows; the one-unit files written for inputs '
-                             'shorter than MIN_LEN frames were decoded from two units and cannot be reproduced)' % i)
-        out.append(np.ascontiguousarray(a))
-    return out
-
-
 def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=None, do_trim=True, max_batch=256, defer=False,
                       momentum=None, packed=False, want_specs=False, codebook=None, want_idx=False, overlap=0):
     """Speech from units: what resynth_batch does behind its encoder, from the units alone.  units: a list of [U_i, E] arrays of
@@ -1526,46 +1589,31 @@ def synth_units_batch(units, trainer, seg_len, speakers, enc_only=True, n_iter=N
         raise ValueError('synth_units_batch: want_idx needs a codebook')
     if trainer.enc_mode == 'continues':
         raise ValueError(_NO_UNITS)
-    dec = trainer.Decoder
-
-    def check_rows():
-        rows = _check_units(units, int(dec.c_in), packed)
-        if codebook is not None:
-            _check_codebook(codebook, trainer)
-        return rows
-
-    def operand(packed_dev, dev):                             # the snap of the one buffer, then zs_units_unpack per chunk
-        idx_h = total_h = None
-        if codebook is not None:
-            idx_h, total_h = _snap_units(codebook, packed_dev, dev, to_host=want_idx)
-        return (lambda tab, B, T0, ch, lens_p: dec.forward_units(packed_dev, tab[0], tab[1], B, T0, ch, lengths=lens_p)), idx_h, total_h
-    return _synth_batch('synth_units_batch', units, check_rows, operand, trainer, seg_len, speakers, enc_only, n_iter, do_trim, max_batch,
-                        defer, momentum, want_specs, overlap=overlap)
+    side = _BitUnits(codebook)                                # rows of bits whatever the codebook: check_rows refuses one of another kind
+    side.packed_rows, side.want_idx = packed, want_idx
+    return _synth_batch(side, units, trainer, seg_len, speakers, enc_only, n_iter, do_trim, max_batch, defer, momentum, want_specs, overlap)
 
 
-def _synth_batch(who, units, check_rows, operand, trainer, seg_len, speakers, enc_only, n_iter, do_trim, max_batch, defer, momentum,
-                 want_specs, overlap=0):
-    """The one driver of synth_units_batch and synth_index_batch.  check_rows() -> the utterances as host arrays of one dtype and
-    row shape (ValueError for what cannot be spoken); they go to the device once, in one pinned buffer and one copy, and
-    unit_fragments cuts each into the row ranges the Decoder runs on.  operand(buffer, dev) -> (the function _enqueue_synth builds a
-    chunk's Decoder operand with, and the pinned codeword indices and summed distance of a snap, or None, None)."""
-    if len(speakers) != len(units) or not len(units):
-        raise ValueError('%s: %d target speakers for %d utterances' % (who, len(speakers), len(units)))
-    overlap = check_overlap_value(overlap, seg_len)
-    rows = check_rows()
-    _check_speaker_range(speakers, int(trainer.Decoder.c_a))
-    shift = 0 if enc_only else check_gen_targets(trainer, speakers)
+def _synth_batch(side, units, trainer, seg_len, speakers, enc_only=True, n_iter=None, do_trim=True, max_batch=256, defer=False, momentum=None,
+                 want_specs=False, overlap=0):
+    """The one driver of synth_units_batch, synth_index_batch and the kinds' speak.  side.check_rows -> the utterances as host
+    arrays of one dtype and row shape (ValueError for what cannot be spoken); they go to the device once, in one pinned buffer and
+    one copy, and _speak_chunks cuts each into the row ranges the Decoder runs on.  side.after_upload -> (the function _enqueue_synth
+    builds a chunk's Decoder operand with, and the pinned codeword indices and summed distance of a snap, or None, None)."""
+    rows = []
+
+    def count_units():
+        check_overlap_value(overlap, seg_len)
+        rows.extend(side.check_rows(units, trainer))
+        return [len(r) for r in rows]
+    counts, shift = _speak_checks(side.who, trainer, speakers, len(units), count_units, enc_only)
+    chunks = _speak_chunks(counts, seg_len, overlap, max_batch)
     trainer.set_eval()
     dev = trainer.device
-    if overlap:                                               # windows that share units (unit_windows); the units are the same
-        items = [it for u, r in enumerate(rows) for it in _window_items(u, len(r), seg_len, overlap)]
-    else:
-        items = [it for u, r in enumerate(rows) for it in _unit_items(u, len(r), seg_len)]
-    chunks = _split_chunks(items, int(seg_len) // 8, max_batch)
-    uoffs = np.concatenate(([0], np.cumsum([len(r) for r in rows]))).astype(np.int64)
+    uoffs = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
     host = torch.empty((int(uoffs[-1]),) + rows[0].shape[1:], dtype=torch.from_numpy(rows[0]).dtype, pin_memory=True)
     np.concatenate(rows, axis=0, out=host.numpy())
-    chunk_operand, idx_h, total_h = operand(host.to(dev, non_blocking=True), dev)     # the one H2D copy of the batch
+    chunk_operand, idx_h, total_h = side.after_upload(trainer.Decoder, host.to(dev, non_blocking=True))     # the one H2D copy of the batch
     fin, spec_h, ulens = _enqueue_synth(trainer, seg_len, chunks, uoffs, speakers, enc_only, shift, n_iter, do_trim, momentum, want_specs,
                                         chunk_operand, overlap=overlap)
 
@@ -1611,18 +1659,16 @@ def _enqueue_synth(trainer, seg_len, chunks, uoffs, speakers, enc_only, shift, n
     tabs = _upload_tables(*_unit_tables(chunks, uoffs), chunks, dev)
     denorm = not want_specs                               # the vocoder de-normalises (the same device function) when the rows are wanted
     gen_plan = None
+    if not enc_only:                                      # zs_gen_scatter's buffer: the vocoder's input; overlap: the staging buffer
+        q.conv, q.ulens, dsts = _plan_scatter(chunks, n_utt, denorm and not overlap, dev, rows_of=lambda n: 8 * n)
+        gen_plan = (q.conv, dsts, shift, denorm and not overlap)
+    for ci, (chunk, ragged) in enumerate(chunks):
+        lens = [it.n for it in chunk]
+        xd = _decode_chunk(trainer, ci, [it.u for it in chunk], (lens if ragged else None), speakers, enc_only, gen_plan,
+                           lambda ch, lens_p: operand(tabs[ci], len(chunk), max(lens), ch, lens_p))
+        q.chunks.append((chunk, lens))
+        q.dec_dev.append(xd)
     if overlap:
-        flat = _flat(chunks)
-        if not enc_only:                                  # the staging buffer: [n_utt, rows of the longest utterance's windows, 513]
-            stage, _, dsts = _plan_scatter(chunks, n_utt, False, dev, rows_of=lambda n: 8 * n)
-            gen_plan = (stage, dsts, shift, False)
-            at, _ = _fragment_layout(flat, [8 * it.n for it in flat], n_utt)
-            first = [it.u * stage.shape[1] + s for it, s in zip(flat, at)]
-        for ci, (chunk, ragged) in enumerate(chunks):
-            lens = [it.n for it in chunk]
-            xd = _decode_chunk(trainer, ci, [it.u for it in chunk], (lens if ragged else None), speakers, enc_only, gen_plan,
-                               lambda ch, lens_p: operand(tabs[ci], len(chunk), max(lens), ch, lens_p))
-            q.dec_dev.append(xd)
         if enc_only:
             first, total = [], 0
             for (chunk, _), x in zip(chunks, q.dec_dev):
@@ -1630,48 +1676,20 @@ def _enqueue_synth(trainer, seg_len, chunks, uoffs, speakers, enc_only, shift, n
                 total += x.shape[0] * x.shape[1]
             src = q.dec_dev[0].reshape(-1, 513) if len(q.dec_dev) == 1 else torch.cat([x.reshape(-1, 513) for x in q.dec_dev], dim=0)
             src = src.float()
-        else:
-            src = stage.reshape(-1, 513)
+        else:                                             # [n_utt, rows of the longest utterance's windows, 513]
+            flat = _flat(chunks)
+            at, _ = _fragment_layout(flat, [8 * it.n for it in flat], n_utt)
+            first = [it.u * q.conv.shape[1] + s for it, s in zip(flat, at)]
+            src = q.conv.reshape(-1, 513)
         t, ulens = _xfade_gather(src, chunks, first, n_utt, denorm, dev)
-        spec_h = _to_host(t) if want_specs else None
-        return _enqueue_vocoder(t, ulens, n_iter, do_trim, dev, amplitudes=denorm, momentum=momentum), spec_h, ulens
-    if not enc_only:
-        q.conv, q.ulens, dsts = _plan_scatter(chunks, n_utt, denorm, dev, rows_of=lambda n: 8 * n)
-        gen_plan = (q.conv, dsts, shift, denorm)
-    for ci, (chunk, ragged) in enumerate(chunks):
-        lens = [it.n for it in chunk]
-        xd = _decode_chunk(trainer, ci, [it.u for it in chunk], (lens if ragged else None), speakers, enc_only, gen_plan,
-                           lambda ch, lens_p: operand(tabs[ci], len(chunk), max(lens), ch, lens_p))
-        q.chunks.append((chunk, lens))
-        q.dec_dev.append(xd)
-    if enc_only:
+        amplitudes = denorm
+    elif enc_only:
         t, ulens = _gather_decoded(q, [[8 * n for n in lens] for _, lens in q.chunks])
+        amplitudes = False
     else:
-        t, ulens = q.conv, q.ulens
+        t, ulens, amplitudes = q.conv, q.ulens, denorm
     spec_h = _to_host(t) if want_specs else None
-    fin = _enqueue_vocoder(t, ulens, n_iter, do_trim, dev, amplitudes=(denorm and not enc_only), momentum=momentum)
-    return fin, spec_h, ulens
-
-
-def read_indices(path, K):
-    """The parser of what write_indices writes: one integer in [0, K) per line -> int32 [U].  ValueError naming the file and the line
-    for anything else, and for a file without a line."""
-    out = []
-    with open(path, 'r') as f:
-        for no, line in enumerate(f, 1):
-            tokens = line.split()
-            if len(tokens) != 1:
-                raise ValueError('%s, line %d: %d values, expected one index' % (path, no, len(tokens)))
-            try:
-                k = int(tokens[0], 10)
-            except ValueError:
-                raise ValueError('%s, line %d: %r is not an integer' % (path, no, tokens[0]))
-            if not 0 <= k < K:
-                raise ValueError('%s, line %d: index %d is outside [0, K = %d)' % (path, no, k, K))
-            out.append(k)
-    if not out:
-        raise ValueError('%s: no indices (the file is empty)' % path)
-    return np.asarray(out, dtype=np.int32)
+    return _enqueue_vocoder(t, ulens, n_iter, do_trim, dev, amplitudes=amplitudes, momentum=momentum), spec_h, ulens
 
 
 def synth_index_batch(idx_lists, trainer, seg_len, speakers, codebook, enc_only=True, n_iter=None, do_trim=True, max_batch=256, defer=False,
@@ -1689,42 +1707,12 @@ def synth_index_batch(idx_lists, trainer, seg_len, speakers, codebook, enc_only=
     (Decoder.forward_index_planes) writes each chunk's operand as the sum of the c stages' codewords.  The driver is the same.
     overlap: as synth_units_batch's -- overlapping decode windows over the same indices, cross-faded."""
     momentum = gl_momentum(momentum)
-    planes = getattr(codebook, 'kind', None) == 'residual'    # a zs_amd.rvq.ResidualCodebook: [U_i, c] rows, c <= S the same for all
-    if getattr(codebook, 'kind', None) != 'vector' and not planes:
-        if trainer.enc_mode == 'continues':
-            raise ValueError(_NO_UNITS)
+    side = codebook.units() if codebook is not None else _BitUnits(None)
+    if not isinstance(side, _VectorUnits):                    # (a zs_amd.rvq.ResidualCodebook's kind is a _VectorUnits)
+        side.check_speakable(trainer.enc_mode)
         raise ValueError('synth_index_batch: the codebook must be a vector codebook (zs_amd.vq.VectorCodebook)')
     _check_codebook(codebook, trainer)
-    dec = trainer.Decoder
-
-    def check_rows():
-        rows = []
-        for i, seq in enumerate(idx_lists):
-            a = np.asarray(seq.cpu() if torch.is_tensor(seq) else seq)
-            if planes:
-                if a.ndim != 2 or a.dtype.kind not in 'iu' or not 1 <= a.shape[1] <= codebook.S:
-                    raise ValueError('utterance %d: indices must be integers [U, 1 .. S = %d] (got %s %s)' % (i, codebook.S, a.dtype, a.shape))
-                if rows and a.shape[1] != rows[0].shape[1]:
-                    raise ValueError('utterance %d has %d indices per frame where utterance 0 has %d' % (i, a.shape[1], rows[0].shape[1]))
-            elif a.ndim != 1 or a.dtype.kind not in 'iu':
-                raise ValueError('utterance %d: indices must be a 1-D integer sequence (got %s %s)' % (i, a.dtype, a.shape))
-            if a.shape[0] < 2:
-                raise ValueError('utterance %d has fewer than 2 indices (the Decoder needs two rows)' % i)
-            if (a < 0).any() or (a >= codebook.K).any():
-                raise ValueError('utterance %d: an index is outside [0, K = %d)' % (i, codebook.K))
-            rows.append(np.ascontiguousarray(a.astype(np.int32)))
-        return rows
-
-    def operand(idx_dev, dev):                                # zs_vq_gather per chunk, from the one index buffer and the codewords
-        code_d, _ = codebook.to(dev)
-        bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        if planes:                                            # zs_rvq_gather: the batch's rows [n, c] as c planes, every column used
-            idx_p = idx_dev.t().contiguous()
-            return (lambda tab, B, T0, ch, lens_p: dec.forward_index_planes(idx_p, idx_p.shape[0], code_d, tab[0], tab[1], B, T0, ch, bad,
-                                                                            lengths=lens_p)), None, None
-        return (lambda tab, B, T0, ch, lens_p: dec.forward_indices(idx_dev, code_d, tab[0], tab[1], B, T0, ch, bad, lengths=lens_p)), None, None
-    return _synth_batch('synth_index_batch', idx_lists, check_rows, operand, trainer, seg_len, speakers, enc_only, n_iter, do_trim, max_batch,
-                        defer, momentum, want_specs, overlap=overlap)
+    return _synth_batch(side, idx_lists, trainer, seg_len, speakers, enc_only, n_iter, do_trim, max_batch, defer, momentum, want_specs, overlap)
 
 
 def out_rate():
@@ -1964,11 +1952,16 @@ def convert_dir_plan(files, durations, targets, out_dir, batch=64, max_batch_sec
     return _dir_plan('convert_dir_plan', files, [float(d) for d in durations], 'durations', targets, batch, max_batch_seconds, reject, item)
 
 
+def _write_index_lines(path, rows):
+    """The one writer of index files: a line per row, its integers separated by one blank."""
+    with open(path, 'w') as f:
+        for r in rows:
+            f.write(' '.join('%d' % int(k) for k in r) + '\n')
+
+
 def write_indices(path, idx):
     """The sibling of a unit file under a codebook: one codeword index per line, one line per unit."""
-    with open(path, 'w') as f:
-        for i in idx:
-            f.write('%d\n' % int(i))
+    _write_index_lines(path, ([i] for i in idx))
 
 
 def write_index_rows(path, rows):
@@ -1976,19 +1969,21 @@ def write_index_rows(path, rows):
     rows = np.asarray(rows)
     if rows.ndim != 2 or rows.shape[1] < 1 or rows.dtype.kind not in 'iu':
         raise ValueError('write_index_rows: rows must be integers [U, c >= 1] (got %s %s)' % (rows.dtype, rows.shape))
-    with open(path, 'w') as f:
-        for r in rows:
-            f.write(' '.join('%d' % int(k) for k in r) + '\n')
+    _write_index_lines(path, rows)
 
 
 def read_index_rows(path, K, S):
     """The parser of what write_index_rows writes: c integers in [0, K) per line, 1 <= c <= S, the same c on every line -> int32
-    [U, c].  ValueError naming the file and the line for anything else, and for a file without a line."""
+    [U, c].  ValueError naming the file and the line for anything else, and for a file without a line.  S None: read_indices' file,
+    one integer per line, refused in its words."""
     out, c = [], None
     with open(path, 'r') as f:
         for no, line in enumerate(f, 1):
             tokens = line.split()
-            if c is None:
+            if S is None:
+                if len(tokens) != 1:
+                    raise ValueError('%s, line %d: %d values, expected one index' % (path, no, len(tokens)))
+            elif c is None:
                 if not 1 <= len(tokens) <= S:
                     raise ValueError('%s, line %d: %d values, expected 1 to S = %d indices' % (path, no, len(tokens), S))
                 c = len(tokens)
@@ -2007,6 +2002,12 @@ def read_index_rows(path, K, S):
     if not out:
         raise ValueError('%s: no indices (the file is empty)' % path)
     return np.asarray(out, dtype=np.int32)
+
+
+def read_indices(path, K):
+    """The parser of what write_indices writes: one integer in [0, K) per line -> int32 [U].  ValueError naming the file and the line
+    for anything else, and for a file without a line."""
+    return read_index_rows(path, K, None).reshape(-1)
 
 
 def idx_path(txt):
