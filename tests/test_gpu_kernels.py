@@ -513,11 +513,15 @@ def test_instnorm_rng_dropout_consistency(zs, dtype):
     _close('kept values', o[keep], (xh / (1 - p))[keep], _tol(dtype))
 
 
-def test_mbv_bit_exact_and_grad(zs):
+# 21900 rows: rows * E = 525 600 (forward: bits_fill_cols = E) and rows * fill_cols / 2 = 700 800 (backward) are both above
+# 524 288 = 2048 blocks x 256 threads, the cap of mbv_fwd_kernel / mbv_bwd_kernel: their grid-stride loops run
+@pytest.mark.parametrize('rows', [37, 21900])
+def test_mbv_bit_exact_and_grad(zs, rows):
     L, layers = zs
     import zs_oracle as O
     torch.manual_seed(0)
-    rows, E = 37, 24
+    E = 24
+    assert rows == 37 or (rows * E > 2048 * 256 and rows * 64 // 2 > 2048 * 256)
     logits = torch.randn(rows, 2 * E) * 3
     U = torch.rand(rows, E, 2)
     G = O.gumbel_from_uniform(U)
