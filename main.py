@@ -143,6 +143,15 @@ codebook, K > 4096 and every other mode are refused before anything is built:
   python main.py --convert_dir in/ --t_speaker V001 --ckpt_pth CKPT --codebook ckpt_english/codebooks/K64.codebook.npz --segment 4
   python main.py --synth_dir out/convert/V001 --t_speaker V002 --ckpt_pth CKPT --codebook ckpt_english/codebooks/K64.codebook.npz --segments
 
+--score_units DIR --abx_item FILE (zs_amd.abx, needs no checkpoint): the ABX phone discriminability of the unit files of DIR and their
+bitrate.  Every token of the .item file (`file onset offset phone prev next speaker` per line, seconds) is the unit rows whose centre
+lies inside it; tokens that share a context (prev, next) are compared by a dynamic time warp over frame distances (zs_abx_dtw),
+Hamming for the bit unit files <name>.txt, angular for the rows of the <name>.idx.txt under --codebook, and the triplets won are
+counted on the GPU (zs_abx_count).  Writes score.json (--score_out) and prints one [Score] line.  The unit files carry no time
+offset (--convert_dir and preprocessing trim leading silence and do not record by how much): --abx_offsets gives it per file.
+  python main.py --score_units out/convert/V001 --abx_item english.item --abx_task within,across
+  python main.py --score_units out/convert/V001 --abx_item english.item --codebook ckpt_english/codebooks/K64.vq.npz
+
 Multi-GPU training: `python -m torch.distributed.run --nproc-per-node N main.py --train_ae ...` (one
 process per GPU; gradients are averaged with RCCL).  Modes outside the stage-1 autoencoder path
 (--train_al, --train_t, --encode, --test_asr) are not part of this build and exit with a clear error.
@@ -361,6 +370,18 @@ def build_parser():
                         'writes <name>.seg.txt beside the per-frame unit files; default: every frame alone')
     p.add_argument('--segments', action='store_true',
                    help='with --synth_dir and --codebook: read the *.seg.txt run files of the folder instead of its per-frame unit files')
+    p.add_argument('--score_units', type=str, default=None, metavar='DIR',
+                   help='score the unit files of DIR (no checkpoint needed): ABX error by batched DTW on the GPU against --abx_item, and '
+                        'the bitrate; <name>.txt bit unit files, or <name>.idx.txt with --codebook; writes score.json')
+    p.add_argument('--abx_item', type=str, default=None, metavar='FILE',
+                   help='with --score_units: the ABX .item file (a # header, then `file onset offset phone prev next speaker`, seconds)')
+    p.add_argument('--abx_task', type=str, default=None, metavar='TASKS', help='with --score_units: within, across or within,across (default both)')
+    p.add_argument('--abx_metric', choices=['hamming', 'angular'], default=None,
+                   help='with --score_units: the frame distance (default hamming for bit units, angular under a vector or residual codebook)')
+    p.add_argument('--abx_offsets', type=str, default=None, metavar='FILE.json',
+                   help='with --score_units: a json object of seconds to add per file stem; --convert_dir and preprocessing trim leading '
+                        'silence and do not record by how much, so a trimmed file needs its offset from here')
+    p.add_argument('--score_out', type=str, default=None, metavar='FILE', help='with --score_units: where score.json goes (default DIR/score.json)')
     p.add_argument('--out_sr', type=_out_sr, default=None,
                    help='sample rate of the wavs --test / --cross_test / --test_single write (hp.out_sr); default: 16000')
     return p
@@ -480,8 +501,9 @@ def check_codebook(parser, args):
                 parser.error('--%s needs --fit_codebook' % flag)
     elif any(getattr(args, f) for f in TRAIN_MODES):
         parser.error('--fit_codebook fits a codebook to a finished checkpoint: it cannot be combined with a --train* mode')
-    if args.codebook is not None and not (args.convert_dir is not None or args.synth_dir is not None or args.test_encode):
-        parser.error('--codebook needs --convert_dir, --synth_dir or --test_encode')
+    if args.codebook is not None and not (args.convert_dir is not None or args.synth_dir is not None or args.test_encode or
+                                          getattr(args, 'score_units', None) is not None):
+        parser.error('--codebook needs --convert_dir, --synth_dir or --test_encode (or --score_units)')
     if args.codebook is not None and args.fit_codebook is not None:
         parser.error('--codebook uses a codebook and --fit_codebook writes one: run them as two commands')
 
@@ -599,6 +621,29 @@ def check_segment(args, enc_mode=None):
         raise ValueError('%s does not segment the stages of a residual codebook: use a bit or a vector codebook' % flag)
 
 
+SCORE_FLAGS = ('abx_item', 'abx_task', 'abx_metric', 'abx_offsets', 'score_out')
+NOT_SCORE_MODES = ('convert_dir', 'synth_dir', 'test', 'cross_test', 'test_single', 'test_encode', 'test_classify', 'fit_codebook',
+                   'adapt_voice', 'preprocess', 'segment', 'segments', 'rvq_stages', 'overlap')
+
+
+def check_score(args):
+    """--score_units and its options are refused, before anything is read, where they cannot do what they say: an option without
+    --score_units, --score_units without --abx_item, beside any other mode, or with an --abx_task other than within / across."""
+    if getattr(args, 'score_units', None) is None:
+        for flag in SCORE_FLAGS:
+            if getattr(args, flag, None) is not None:
+                raise ValueError('--%s needs --score_units DIR' % flag)
+        return
+    if args.abx_item is None:
+        raise ValueError('--score_units needs --abx_item FILE: the tokens to compare')
+    other = [m for m in NOT_SCORE_MODES + tuple(TRAIN_MODES) if getattr(args, m, None) not in (None, False)]
+    if other:
+        raise ValueError('--score_units scores unit files that are already written: it cannot be combined with --%s' % other[0])
+    if args.abx_task is not None:
+        from zs_amd.abx import check_tasks
+        check_tasks(args.abx_task)
+
+
 def convert_targets(args):
     """--convert_dir and --synth_dir take --t_speaker as a comma-separated list of distinct names (--test_single keeps the single name): the
     list, refused before anything is built when it names no speaker or one twice."""
@@ -625,6 +670,9 @@ def argument_runner(argv=None):
     check_rvq(args)
     check_overlap(args)
     check_segment(args)
+    check_score(args)
+    if args.score_units is not None:          # needs no checkpoint and no hps: nothing below applies
+        return args, None
     args.t_speakers =convert_targets(args) if (args.convert_dir is not None or args.synth_dir is not None) else None
     if args.dataset == 'surprise':            # main.py:83-88: english -> surprise in every default path
         for action in parser._actions:
@@ -694,6 +742,12 @@ def training_sets(args, hps, world=1):
 def main(argv=None):
     import zs_amd  # noqa: F401
     args, hps = argument_runner(argv)
+    if args.score_units is not None:                      # not in the reference: ABX error and bitrate of a folder of unit files (zs_amd.abx)
+        from zs_amd import abx
+        cb = abx.load_codebook(args.codebook) if args.codebook is not None else None
+        abx.score_units(args.score_units, args.abx_item, tasks=(args.abx_task or 'within,across'), metric=args.abx_metric, codebook=cb,
+                        offsets=(abx.read_offsets(args.abx_offsets) if args.abx_offsets is not None else None), out_path=args.score_out)
+        return
     bad = [f for f in OUT_OF_SCOPE if getattr(args, f)]
     if bad:
         raise NotImplementedError('--%s is outside the stage-1 autoencoder hot path this build covers' % bad[0])

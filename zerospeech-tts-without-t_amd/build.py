@@ -37,7 +37,7 @@ def needs_build(out=None):
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    deps = sources() + glob.glob(os.path.join(CSRC, '*.h')) + [os.path.join(os.path.dirname(_PKG), 'include', h) for h in ('zs_amd.h', 'zs_amd_segment.h', 'zs_amd_rvq_drop.h')]
+    deps = sources() + glob.glob(os.path.join(CSRC, '*.h')) + [os.path.join(os.path.dirname(_PKG), 'include', h) for h in ('zs_amd.h', 'zs_amd_segment.h', 'zs_amd_rvq_drop.h', 'zs_amd_abx.h')]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -71,7 +71,7 @@ def build(force=False, verbose=True):
     hipcc = os.environ.get('HIPCC', 'hipcc')
     od = obj_dir(san)
     os.makedirs(od, exist_ok=True)
-    hdrs = glob.glob(os.path.join(CSRC, '*.h')) + [os.path.join(os.path.dirname(_PKG), 'include', h) for h in ('zs_amd.h', 'zs_amd_segment.h', 'zs_amd_rvq_drop.h')]
+    hdrs = glob.glob(os.path.join(CSRC, '*.h')) + [os.path.join(os.path.dirname(_PKG), 'include', h) for h in ('zs_amd.h', 'zs_amd_segment.h', 'zs_amd_rvq_drop.h', 'zs_amd_abx.h')]
     t_h = max(os.path.getmtime(h) for h in hdrs)
     jobs, objs = [], []
     for src in sources():

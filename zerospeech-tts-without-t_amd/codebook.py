@@ -326,6 +326,11 @@ class Codebook(CodebookFile):
         L.call('zs_code_scores', 'ZsCodeScores', _stream(rows.device), units=L.ptr(rows), n=rows.shape[0], row_bytes=rows.shape[1],
                code=L.ptr(code), K=self.K, code_bytes=code.shape[1], E=self.E, scores=L.ptr(out), ld_s=_scores_ld(out, self.K))
 
+    def rows_at(self, idx):
+        """The packed rows uint8 [n, (E + 7) // 8] of the codewords idx (integers [n] in [0, K)) on the host: what an index file
+        stands for (zs_amd.abx)."""
+        return self.packed[np.asarray(idx, dtype=np.int64).reshape(-1)]
+
     def snap_host(self, packed):
         """Host rows uint8 [n, (E + 7) // 8] -> (idx int32 [n], snapped) as numpy arrays (one round trip through the device)."""
         idx, s = self.snap(torch.from_numpy(np.ascontiguousarray(packed)).cuda())

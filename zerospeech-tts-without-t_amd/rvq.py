@@ -199,6 +199,11 @@ class ResidualCodebook(CodebookFile):
         q[~ok] = 0.0
         return q
 
+    def rows_at(self, idx):
+        """The rows fp32 [n, E] of the index rows idx (integers [n, c], c <= S: an index file's lines) on the host: the sum of the
+        stages a line holds (reconstruct)."""
+        return self.reconstruct(np.asarray(idx).T)
+
     # ---- CodebookFile.fit_dir's hooks -------------------------------------------------------------------------------------------
     _dir_rows = VectorCodebook._dir_rows
 

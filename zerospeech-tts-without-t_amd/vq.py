@@ -139,6 +139,10 @@ class VectorCodebook(CodebookFile):
         from .convert import _VectorUnits
         return _VectorUnits(self)
 
+    def rows_at(self, idx):
+        """The rows fp32 [n, E] of the codewords idx (integers [n] in [0, K)) on the host: what an index file stands for (zs_amd.abx)."""
+        return self.vectors[np.asarray(idx, dtype=np.int64).reshape(-1)]
+
     def snap(self, x_dev, work=None):
         """(idx int32 [n], dist fp32 [n]) of the rows of x_dev (fp32 / bf16 [n, >= E]), on the device."""
         code, cn = self.to(x_dev.device)
