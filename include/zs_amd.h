@@ -906,6 +906,8 @@ typedef struct {
   int32_t gp_rows;                                /* rows of gp per (b, h_out) block; 0 = Wd + 2*pad (a stride-2 data gradient is
                                                      computed by output parity and keeps an even number of rows per block) */
   int32_t full;                                   /* transpose of zs_conv2d_gather(full): gp rows (b, ho, wo), columns (kh*k + kw)*C + c */
+  /* Refused: 0 < gp_rows < Wd + 2*pad; out_f32 with ldo < C; REFLECT with pad >= H_in or pad >= Wd (as zs_conv2d_gather).
+   * Columns [C, fill_cols) of a T-dtype row are written as zeros and read nothing: ldg >= k*C is all that gp needs. */
 } ZsConv2dFold;
 int zs_conv2d_fold(const ZsConv2dFold* p, void* stream);
 /* zs_conv1_fwd: the critic's FIRST Conv2d (one input channel, k x k taps, k*k <= 32, stride 2, padding k/2) computed directly from

@@ -900,7 +900,9 @@ def test_conv1_fwd_direct_vs_torch_and_im2col_path(zs, case):
     assert (got == ref.valid().float().cpu().reshape(B, Ho, Wo, Cout)).float().mean().item() > 0.98
 
 
-@pytest.mark.parametrize('case', [(2, 12, 17, 64, 5, True), (3, 64, 257, 64, 5, True), (2, 9, 20, 32, 3, False), (1, 16, 33, 16, 5, True)])
+# (2, 512, 513, ...): 131 584 positions = 4112 tiles of 32 > 1024 workgroups x 4 waves: a wave takes a second tile, whose staging overwrites the first
+@pytest.mark.parametrize('case', [(2, 12, 17, 64, 5, True), (3, 64, 257, 64, 5, True), (2, 9, 20, 32, 3, False), (1, 16, 33, 16, 5, True),
+                                  (2, 512, 513, 64, 5, True)])
 def test_conv1_wgrad_direct_vs_torch(zs, case):
     """zs_conv1_wgrad (weight + bias gradient of the critic's first Conv2d straight from the fp32 image) against autograd on the
     bf16-rounded operands; accumulate adds; two runs are bitwise equal (fixed tile -> wave assignment, fixed-order reduction)."""

@@ -380,7 +380,8 @@ __global__ __launch_bounds__(NTP) void conv2d_fold_kernel(const ZsConv2dFold p) 
     if (w <= p.Wd - 2 && w >= p.Wd - 1 - p.pad) ws[nw++] = 2 * (p.Wd - 1) - w;
   }
   const int r0 = (hi + p.pad) % p.stride, ho0 = (hi + p.pad - r0) / p.stride;       // taps kh = r0 + stride j  <->  rows ho0 - j
-  if (nh == 1 && nw == 1 && (p.C & 7) == 0 && r0 + 4 * p.stride >= p.k) {           // interior, at most 4 taps
+  if (c0 >= p.C) {                                                                  // a fill group: zeros only, nothing of gp is read
+  } else if (nh == 1 && nw == 1 && (p.C & 7) == 0 && r0 + 4 * p.stride >= p.k) {    // interior, at most 4 taps
     const T* base = (const T*)p.gp + (int64_t)(w + p.pad) * p.ldg + c0;
     float v[4][8];
     bool ok[4];
@@ -950,6 +951,8 @@ extern "C" int zs_conv2d_fold(const ZsConv2dFold* p, void* stream) {
   ZS_REQUIRE(p && p->gp && p->out, "zs_conv2d_fold: null operand");
   ZS_DT_OK(p);
   ZS_REQUIRE(p->B > 0 && p->H_in > 0 && p->H_out > 0 && p->Wd > 0 && p->C > 0 && p->k > 0 && p->stride > 0 && p->pad >= 0, "zs_conv2d_fold: sizes");
+  ZS_REQUIRE(p->pad_mode != ZS_PAD_REFLECT || (p->pad < p->H_in && p->pad < p->Wd), "zs_conv2d_fold: Padding size should be less than the corresponding input dimension");
+  ZS_REQUIRE(!p->out_f32 || p->ldo >= p->C, "zs_conv2d_fold: fp32 output rows of ldo %lld < C %d", (long long)p->ldo, p->C);
   if (p->full) {
     const int W_out = (p->Wd + 2 * p->pad - p->k) / p->stride + 1;
     ZS_REQUIRE(p->ldg >= (int64_t)p->k * p->k * p->C && W_out > 0, "zs_conv2d_fold(full): ldg");
@@ -960,6 +963,7 @@ extern "C" int zs_conv2d_fold(const ZsConv2dFold* p, void* stream) {
     return zs_check_launch("zs_conv2d_fold.full");
   }
   ZS_REQUIRE(p->ldg >= (int64_t)p->k * p->C && al16p(p->gp), "zs_conv2d_fold: ldg");
+  ZS_REQUIRE(p->gp_rows == 0 || p->gp_rows >= p->Wd + 2 * p->pad, "zs_conv2d_fold: gp_rows %d < Wd + 2 pad = %d", p->gp_rows, p->Wd + 2 * p->pad);
   if (!p->out_f32) ZS_REQUIRE(p->fill_cols >= p->C && p->fill_cols % 8 == 0 && p->fill_cols <= p->ldo && al16p(p->out) && p->ldo % 8 == 0, "zs_conv2d_fold: fill_cols / ldo");
   if ((p->C & 7) == 0) ZS_REQUIRE(p->ldg % 8 == 0, "zs_conv2d_fold: ldg alignment");
   const int cols = p->out_f32 ? p->C : p->fill_cols;
