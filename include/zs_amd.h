@@ -605,6 +605,8 @@ int zs_softmax_ce(const ZsSoftmaxCE* p, void* stream);
  * zs_gl_istft: frames of spec (complex64 [n_utt][T_max][513]) -> windowed irfft -> overlap-add /
  *              window-sum-square -> wav [n_utt][wav_ld] (200*(T-1) samples, centre-trimmed).
  * zs_gl_stft_project: wav -> reflect-padded frames -> rfft -> spec = mag * E/max(1e-8,|E|).
+ * Utterances with lengths[u] < 4 frames are skipped by zs_gl_istft, zs_gl_stft_project and zs_gl_iter alike: nothing of their
+ * rows is read or written (the reflect padding of 512 samples needs 200*(T-1) > 512).
  */
 typedef struct {
   const float* spec; const float* mag; const int32_t* lengths; int32_t n_utt, T_max;
@@ -661,7 +663,10 @@ int zs_gl_chains_used(void);
  * librosa.effects.trim): wav [n_utt][wav_ld] fp32, n_samples[u] valid samples ->
  *   mag[u][t][0..513) = clip((20 log10(max(1e-5, |STFT(preemph(y))|)) - ref_db + max_db) / max_db, 1e-8, 1), t < 1 + n_samples/200
  *   amp (optional, [n_utt][T_max][513]): the linear magnitudes, input of zs_pre_mel.
- * STFT as in the vocoder: n_fft 1024, hop 200, hann(800) centred, reflect-padded centre frames.
+ * STFT as in the vocoder: n_fft 1024, hop 200, hann(800) centred, reflect-padded centre frames.  The padding is numpy's
+ * mode='reflect' for ANY window length n >= 2, the triangle wave zs_trim documents below (P = 2 (n - 1), m = j mod P taken
+ * non-negative, refl(j) = m if m < n else P - m): a window shorter than the padding of 512 folds back and forth as numpy's does.
+ * Rows with n_samples[u] < 2 and frames t >= 1 + n_samples[u]/200 are not written.
  */
 typedef struct {
   const float* wav; int64_t wav_ld; const int32_t* n_samples; int32_t n_utt, T_max;

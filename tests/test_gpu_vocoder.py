@@ -148,11 +148,13 @@ def test_deemphasis_kernel_vs_scipy_lfilter(cv):
     w = torch.from_numpy(x).to(dev)
     L.check(L.lib().zs_gl_deemphasis(L.ptr(w), n, L.ptr(lens), 2, 0.97, torch.cuda.current_stream().cuda_stream), 'zs_gl_deemphasis')
     got = w.cpu().numpy()
+    coef = float(np.float32(0.97))                                 # the C entry point takes a float: the filter's pole is this number
     for i, m in enumerate((n, 200 * 450)):
-        ref = scipy.signal.lfilter([1], [1, -0.97], x[i, :m].astype(np.float64))
-        err = np.abs(got[i, :m] - ref).max() / np.abs(ref).max()
-        assert err < 1e-3, (i, err)
-    print('deemphasis rel err', err)
+        ref = scipy.signal.lfilter([1], [1, -coef], x[i, :m].astype(np.float64))
+        d = np.abs(got[i, :m] - ref)
+        tol = 2.0 ** -23 * np.abs(ref) + 2.0 ** -40 * np.abs(ref).max()   # one fp32 rounding of an fp64 recursion
+        print('deemphasis row %d: max |d| / tol %.3f' % (i, (d / tol).max()))
+        assert (d <= tol).all(), (i, (d / tol).max())
 
 
 @pytest.mark.parametrize('n_iter', [8, 60])

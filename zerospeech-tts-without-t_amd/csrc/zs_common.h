@@ -147,6 +147,16 @@ __device__ __host__ __forceinline__ int zs_reflect(int s, int T) {
   return s;
 }
 
+// ---- reflect index (np.pad mode='reflect') for ANY pad width: a triangle wave of period 2 (n - 1); n == 1 maps everything to 0 ----
+__device__ __host__ __forceinline__ int64_t zs_reflect_tri(int64_t j, int64_t n) {
+  if (j >= 0 && j < n) return j;
+  if (n == 1) return 0;
+  const int64_t P = 2 * (n - 1);
+  int64_t m = j % P;
+  if (m < 0) m += P;
+  return m < n ? m : P - m;
+}
+
 // ---- wave / block reductions -----------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -18,15 +18,6 @@ namespace {
 constexpr int TRIM_WAVES = 4;                   // waves (blocks of hop samples) per workgroup of trim_block_sums
 constexpr int TRIM_FIN = 256;                   // threads of trim_finish
 
-// np.pad(mode='reflect') for any pad width: a triangle wave of period 2 (n - 1); n == 1 maps everything to 0
-__device__ __forceinline__ int64_t trim_refl(int64_t j, int64_t n) {
-  if (n == 1) return 0;
-  const int64_t P = 2 * (n - 1);
-  int64_t m = j % P;
-  if (m < 0) m += P;
-  return m < n ? m : P - m;
-}
-
 __device__ __forceinline__ int trim_len(const ZsTrim& p, int u) {
   const int64_t n = p.n_samples[u];
   return (int)(n < 0 ? 0 : (n > p.wav_ld ? p.wav_ld : n));
@@ -52,7 +43,7 @@ __global__ __launch_bounds__(64 * TRIM_WAVES) void trim_block_sums(const ZsTrim 
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        if (base + k < p.hop) v[k] = w[interior ? j0 + base + k : trim_refl(j0 + base + k, n)];
+        if (base + k < p.hop) v[k] = w[interior ? j0 + base + k : zs_reflect_tri(j0 + base + k, n)];
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) acc += (double)v[k] * (double)v[k];           // samples past the block's end add an exact zero

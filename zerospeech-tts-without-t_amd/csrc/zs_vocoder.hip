@@ -61,7 +61,7 @@ __global__ __launch_bounds__(NTV) void gl_iframes_kernel(const ZsGlIstft p) {
   __shared__ float2 bufB[NFFT];
   __shared__ float2 tw[NFFT / 2];
   const int tid = threadIdx.x, t = blockIdx.x, u = blockIdx.y;
-  if (t >= p.lengths[u]) return;                                   // uniform per workgroup
+  if (t >= p.lengths[u] || p.lengths[u] < 4) return;               // uniform per workgroup; < 4 frames: skipped, as in gl_iter_kernel
   build_twiddles(tw, tid);
   const float2* S = reinterpret_cast<const float2*>(p.spec) + ((int64_t)u * p.T_max + t) * NBIN;
   for (int k = tid; k < NFFT; k += NTV) {                           // Hermitian extension (irfft semantics)
@@ -81,7 +81,7 @@ __global__ void gl_ola_kernel(const ZsGlIstft p) {
   const int T = p.lengths[u];
   const int L = HOP * (T - 1);
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= L) return;
+  if (T < 4 || n >= L) return;
   const int pos = n + NFFT / 2;
   int i0 = (pos - (NFFT - 1) + HOP - 1) / HOP; if (i0 < 0) i0 = 0;
   int i1 = pos / HOP; if (i1 > T - 1) i1 = T - 1;
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(NTV) void gl_stft_project_kernel(const ZsGlStft p) 
   __shared__ float2 tw[NFFT / 2];
   const int tid = threadIdx.x, t = blockIdx.x, u = blockIdx.y;
   const int T = p.lengths[u];
-  if (t >= T) return;
+  if (t >= T || T < 4) return;                                      // the single reflection below needs 512 < L = 200 (T - 1)
   build_twiddles(tw, tid);
   const int L = HOP * (T - 1);
   const float* w = p.wav + (int64_t)u * p.wav_ld;
@@ -144,10 +144,8 @@ __global__ __launch_bounds__(NTV) void pre_spectrogram_kernel(const ZsPreSpec p)
   build_twiddles(tw, tid);
   const float* w = p.wav + (int64_t)u * p.wav_ld + s0;
   for (int n = tid; n < NFFT; n += NTV) {
-    int idx = t * HOP + n - NFFT / 2;                               // np.pad(y, 512, mode='reflect') of the pre-emphasised signal
-    if (idx < 0) idx = -idx;
-    if (idx >= L) idx = 2 * (L - 1) - idx;
-    idx = min(max(idx, 0), L - 1);
+    // np.pad(y, 512, mode='reflect') of the pre-emphasised signal: the triangle wave, so windows shorter than the padding fold as numpy's do
+    const int idx = (int)zs_reflect_tri(t * HOP + n - NFFT / 2, L);
     const float y = idx > 0 ? w[idx] - p.preemph * w[idx - 1] : w[0];
     bufA[n] = make_float2(y * hann_padded(n), 0.f);
   }
