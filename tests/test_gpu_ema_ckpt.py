@@ -264,3 +264,25 @@ def test_a_state_with_another_average_is_refused(dev, tmp_path, tmp_path_factory
         tr.ae.opt['enc'].load_state_dict(A['tr'].ae.opt['enc'].state_dict())
     with pytest.raises(ValueError, match='ema'):
         A['tr'].ae.opt['enc'].load_state_dict(tr.ae.opt['enc'].state_dict())
+
+
+def test_stage_two_checkpoint_is_the_same_from_both_writers(dev, tmp_path):
+    """A patchGAN run with averages to its first checkpoint, resume=True (test_gpu_resume.py's patchgan_tg case): a prefixed net
+    has an average, and the averages of three nets lie outside this mode's state tree.  save_model writes the same file."""
+    from zs_amd.dataloader import DataLoader, SyntheticDataset
+    from zs_amd.trainer import Trainer
+    hps = _hps(EVERY)
+    torch.manual_seed(0)
+    tr = Trainer(hps, None, hps.g_mode, hps.enc_mode, log_dir=str(tmp_path / 'log'), dtype='bf16', device=dev, ema=DECAY)
+    tr.ae.use_graph = True
+    tr.add_duo_loader(DataLoader(SyntheticDataset(96, seg_len=128, n_speakers=100, seed=1), hps.batch_size),
+                      DataLoader(SyntheticDataset(96, seg_len=128, n_speakers=2, seed=2, speaker_offset=100), hps.batch_size))
+    with redirect_stdout(io.StringIO()):
+        tr.train(str(tmp_path / 'r' / 'model.pth'), 'train', mode='patchGAN', target_guided=True, resume=True)
+    torch.cuda.synchronize()
+    ck = torch.load(str(tmp_path / 'r' / ('model.pth-s2-%d' % EVERY)), weights_only=True)
+    assert list(ck) == list(NETS) + ['encoder_ema', 'decoder_ema', 'generator_ema', 'classifier_ema', 'patch_discriminator_ema']
+    assert ck['patch_discriminator_ema'] and all(k.startswith('module.') for k in ck['patch_discriminator_ema'])
+    assert not any(k.startswith('module.') for k in ck['generator_ema'])
+    tr.save_model(str(tmp_path / 'sync.pth'), 's2', EVERY)
+    _assert_same_file(ck, torch.load(str(tmp_path / ('sync.pth-s2-%d' % EVERY)), weights_only=True))

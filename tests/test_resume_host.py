@@ -179,13 +179,19 @@ def test_restored_window_removes_the_right_checkpoint_and_its_state_file(tmp_pat
 
 
 def test_save_model_continues_a_restored_window(tmp_path):
-    """Trainer.save_model itself (stub nets: state_dict() of a CPU tensor each) on a restored model_kept."""
+    """Trainer.save_model itself (tiny nets on the CPU: one parameter `w` each) on a restored model_kept."""
     import zs_amd  # noqa: F401
     from zs_amd import resume
+    from zs_amd.model import ZsModule
     from zs_amd.trainer import Trainer
+
+    class Net(ZsModule):
+        def __init__(self):
+            super(Net, self).__init__(dtype='fp32')
+            self.w = torch.nn.Parameter(torch.ones(2))
+
     tr = Trainer.__new__(Trainer)
-    net = types.SimpleNamespace(state_dict=lambda: {'w': torch.ones(2)})
-    tr.Encoder = tr.Decoder = tr.Generator = tr.SpeakerClassifier = tr.PatchDiscriminator = tr.TargetClassifier = net
+    tr.Encoder, tr.Decoder, tr.Generator, tr.SpeakerClassifier, tr.PatchDiscriminator, tr.TargetClassifier = (Net() for _ in range(6))
     model_path = str(tmp_path / 'model.pth')
     old = [model_path + '-ae-3', model_path + '-ae-6']
     for p in old:

@@ -8,7 +8,7 @@ save (weights + train state, written by a worker thread), and the step time betw
       iteration the checkpoint of its arm; it ends, as Trainer.train does, by waiting for the writer and the device.  Arms,
       interleaved, `rounds` windows each:
         none        no checkpoint                                     resume=False
-        sync        Trainer.save_model (weights only, synchronous)    resume=False: what every run did before train states
+        sync        Trainer.save_model (weights only, synchronous)    resume=False: every checkpoint of a run without --resume
         resumable   Trainer._checkpoint_async (weights + state)       resume=True
         counted     no checkpoint falls in the window                 resume=True (the batch counts are the only difference)
       stall of an arm = (its median window - none's median window) / ckpts.  Medians, spreads (max - min), both stalls, the

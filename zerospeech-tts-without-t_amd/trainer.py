@@ -660,6 +660,14 @@ class TclfStep(object):
         return self.loss, self.correct
 
 
+PREFIX = 'module.'                       # on the keys of the two nets the reference wraps in nn.DataParallel (_ckpt_sources puts it there)
+
+
+def strip_prefix(sd):
+    """A state dict of a checkpoint without the prefix of the wrapped nets: what net.load_state_dict takes."""
+    return {(k[len(PREFIX):] if k.startswith(PREFIX) else k): v for k, v in sd.items()}
+
+
 class _Slot(int):
     """Placeholder of a device tensor in the skeleton of a state tree: the index of its snapshot buffer."""
 
@@ -781,6 +789,10 @@ class Trainer(object):
     def nets(self):
         return [self.Encoder, self.Decoder, self.Generator, self.SpeakerClassifier, self.PatchDiscriminator, self.TargetClassifier]
 
+    def named_nets(self):
+        """[(checkpoint key, net)] in the order of nets()."""
+        return list(zip(train_state.NET_NAMES, self.nets()))
+
     def add_duo_loader(self, source_loader, target_loader):
         """trainer.py:171-173."""
         self.source_loader, self.target_loader = source_loader, target_loader
@@ -821,31 +833,22 @@ class Trainer(object):
         self.model_kept = []
 
     # ---- checkpoints (trainer.py:103-168) -----------------------------------------------------
-    def _model_dict(self, model_all=True):
-        """The checkpoint dict (the reference's, plus `<net>_ema` entries with weight averages) as CPU tensors."""
-        all_model = {
-            'encoder': self.Encoder.state_dict(),
-            'decoder': self.Decoder.state_dict(),
-            'generator': self.Generator.state_dict(),
-            'classifier': self.SpeakerClassifier.state_dict(),
-        }
-        if model_all:                                  # the reference wraps these two in nn.DataParallel: keys carry 'module.'
-            all_model['patch_discriminator'] = {'module.' + k: v for k, v in self.PatchDiscriminator.state_dict().items()}
-            all_model['target_classifier'] = {'module.' + k: v for k, v in self.TargetClassifier.state_dict().items()}
-        else:
-            del all_model['classifier']
-        nets = dict(zip(train_state.NET_NAMES, self.nets()))
-        for key, opt in self.ema_opts().items():           # `<net>_ema`: the net's entry with the average in place of the weights
-            if key in all_model:
-                offs, sd = nets[key]._zs['offsets'], nets[key].state_dict()
-                pre = 'module.' if key in ('patch_discriminator', 'target_classifier') else ''
-                all_model[key + '_ema'] = {pre + k: (opt.ema[offs[k]:offs[k] + v.numel()].view(v.shape) if k in offs else v)
-                                           for k, v in sd.items()}
-        return {k: {n: t.detach().cpu().clone() for n, t in sd.items()} for k, sd in all_model.items()}
+    def _ckpt_blocking(self):
+        """The checkpoint dict (the reference's, plus `<net>_ema` entries with weight averages) as CPU tensors, by blocking copies
+        on the calling thread: the layout of _ckpt_sources, which the resumable checkpoints fill from their snapshot, filled
+        here by one copy per source an entry uses (its flat buffer and each buffer outside it); one entry's host copies are
+        alive at a time."""
+        srcs, layout, _ = self._ckpt_sources({})
+        ckpt = {}
+        for key, pre, ents in layout:
+            host = {s: srcs[s].detach().cpu() for s in {e[1] for e in ents}}
+            ckpt[key] = {pre + k: host[s][o:o + n].view(shape).clone() for k, s, o, n, shape in ents}
+        return ckpt
 
     def save_model(self, model_path, name, iteration, model_all=True):
+        """model_all: the reference's parameter, kept for its signature; no caller passes False and every file holds all six nets."""
         new_model_path = '{}-{}-{}'.format(model_path, name, iteration)
-        torch.save(self._model_dict(model_all), new_model_path)
+        train_state.atomic_save(self._ckpt_blocking(), new_model_path)
         for old in train_state.roll_window(self.model_kept, new_model_path, self.max_keep):
             train_state.remove_checkpoint(old)                                 # its train-state file, if it has one, goes with it
 
@@ -923,8 +926,8 @@ class Trainer(object):
     def _load_all_nets(self, ckpt_path):
         """All six nets from a checkpoint of this build's own loop, strictly (load_model prints and goes on)."""
         all_model = torch.load(ckpt_path, map_location='cpu', weights_only=True)
-        for key, net in zip(train_state.NET_NAMES, self.nets()):
-            net.load_state_dict({(k[7:] if k.startswith('module.') else k): v for k, v in all_model[key].items()})
+        for key, net in self.named_nets():
+            net.load_state_dict(strip_prefix(all_model[key]))
         self.sync_params()                                                # (the averages restart from these weights; load_state follows)
 
     def _reserve(self, srcs):
@@ -1033,21 +1036,15 @@ class Trainer(object):
             src = train_state.ema_keys(all_model.keys(), train_state.NET_NAMES, model_path)
         if verbose:
             print('[Trainer] - ', end='')
-        strip = lambda sd: {(k[7:] if k.startswith('module.') else k): v for k, v in sd.items()}
-        for key, net, tag in (('encoder', self.Encoder, 'encoder'), ('decoder', self.Decoder, 'decoder'),
-                              ('generator', self.Generator, 'generator'), ('classifier', self.SpeakerClassifier, 'classifier'),
-                              ('patch_discriminator', self.PatchDiscriminator, 'patch_discriminator'),
-                              ('target_classifier', self.TargetClassifier, 'target_classifier')):
+        for key, net in self.named_nets():
             if key in load_model_list:
+                tag = key
                 try:
-                    if key == 'target_classifier' and clf_path is not None:        # trainer.py:157-161: taken from ANOTHER checkpoint
-                        clf_model = torch.load(clf_path, map_location='cpu', weights_only=True)
-                        avg = use_ema and 'target_classifier_ema' in clf_model
-                        net.load_state_dict(strip(clf_model['target_classifier_ema' if avg else 'target_classifier']))
-                        tag = 'target_classifier_ema_another' if avg else 'target_classifier_another'
-                    else:
-                        net.load_state_dict(strip(all_model[src[key]]))
-                        tag = src[key]
+                    other = key == 'target_classifier' and clf_path is not None    # trainer.py:157-161: taken from ANOTHER checkpoint
+                    file = torch.load(clf_path, map_location='cpu', weights_only=True) if other else all_model
+                    entry = (key + '_ema' if use_ema and key + '_ema' in file else key) if other else src[key]
+                    net.load_state_dict(strip_prefix(file[entry]))
+                    tag = entry + ('_another' if other else '')
                     if key == 'target_classifier':
                         self.tclf_loaded = True
                     if verbose:
@@ -1259,7 +1256,7 @@ class Trainer(object):
                 elif keep_state is not None:
                     self._checkpoint_async(model_path, 'ae', iteration, *keep_state, best=True)
                 else:
-                    train_state.atomic_save(self._model_dict(), validation.best_path(model_path))
+                    train_state.atomic_save(self._ckpt_blocking(), validation.best_path(model_path))
         return rec
 
     def _finish_writer(self):
